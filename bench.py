@@ -9,6 +9,11 @@ preprocess -> RFN.loss forward (extractor, ConvLSTM, latent recurrence, upscaler
 backward -> gradient all-reduce (N>1) -> Adam, on the canonical SM-MNIST configuration (RFN/default_rfn_job.sh) at
 global batch 32, seq_len 20, fp32.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 Strong scaling: the global batch (32 sequences) is fixed and sharded over the ranks (north_star).
+
+A plain run measures the headline arithmetic only (RFN_CONV_PRECISION, default `mixed`): set-up, warm-up, the K timed
+steps and the JSON line.  `--full` adds what takes runs of its own: the other two arithmetics, the GPU-vs-oracle bits/dim
+parity that picks the headline among them, the forward-only rate, the per-kernel roofline and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -260,6 +265,34 @@ def parity_check(device, T=10, scales=(0.003, 0.01, 0.1)):
     return res
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each flattened parameter-sized output (16 MB of fp32)
+
+
+def dump_outputs(d, solver):
+    """--dump-outputs: what the timed path handed its caller in its last step, as .npy files in `d`:
+    step_scalars.npy (float64: loss / t, kl / t, nll / t, bits/dim; t = modeled frames, as Solver records them),
+    params.npy and grads.npy (float32: every parameter after the step's Adam update and the gradient the step computed,
+    flattened and concatenated in named_parameters order; a parameter without a gradient contributes zeros).  The
+    canonical model has 36.5 M parameters, so both hold the same fixed sample of DUMP_SAMPLE positions (seed 0, sorted).
+    The inputs are the same in every run with the same arguments; the outputs agree between runs to rounding, not bit for
+    bit: the backward pass combines weight-gradient partial sums with float atomics, and the optimizer
+    steps before the last one carry that rounding forward."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    params = [p for _, p in solver.model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        idx = idx.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    scalars = [solver.losses[-1], solver.kl_loss[-1], solver.recon_loss[-1], solver.bits[-1]]
+    np.save(os.path.join(d, "step_scalars.npy"), np.array(scalars, dtype=np.float64))
+    np.save(os.path.join(d, "params.npy"), flat_p.float().cpu().numpy())
+    np.save(os.path.join(d, "grads.npy"), flat_g.float().cpu().numpy())
+
+
 DTYPE_STR = {"mixed": "f32 (forward convolutions fp32-grade: fused scaled-fp16 split f16x3s / three-piece bf16x6 split; "
                       "gradient convolutions bf16x3 split MFMA; fp32 accumulate everywhere)",
              "bf16x3": "f32 (convolutions: bf16x3 split-precision MFMA, fp32 accumulate)",
@@ -343,10 +376,19 @@ def launch_ranks(n, argv=None, env=None, timeout=None, script=None):
 
 
 def supervise():
-    """The parent never touches the GPU.  It runs the measurement once per convolution arithmetic (RFN_CONV_PRECISION =
-    mixed, bf16x3, f32), each in a fresh child process, and prints ONE line holding all of them.  The headline (`value`,
-    `ms_per_step`, `dtype`) is the first of (mixed, bf16x3) whose bits/dim parity against the oracle, measured in this same
-    run (B=2, T=10, flow perturbed), is within north_star's 1e-4; otherwise the all-fp32-MFMA run."""
+    """The parent never touches the GPU.  It runs the measurement in a fresh child process for the headline arithmetic
+    (RFN_CONV_PRECISION, default mixed) and prints ONE line.  With --full it runs every convolution arithmetic (mixed,
+    bf16x3, f32), each in its own child, and the line holds all of them: the headline (`value`, `ms_per_step`, `dtype`)
+    is then the first of (mixed, bf16x3) whose bits/dim parity against the oracle, measured in this same run (B=2, T=10,
+    flow perturbed), is within north_star's 1e-4; otherwise the all-fp32-MFMA run."""
+    import tempfile
+    a = make_parser().parse_args()
+    with tempfile.TemporaryDirectory(prefix="bench_dump_") as tmp:  # other arithmetics' --dump-outputs, until the
+        return _supervise(a, tmp)                                     # headline is known
+
+
+def _supervise(a, tmp):
+    import shutil
     rank = int(os.environ.get("RANK", 0))
     first = os.environ.get("RFN_CONV_PRECISION", "mixed")
     order = [first] + [p for p in ("mixed", "bf16x3", "f32") if p != first]
@@ -355,11 +397,14 @@ def supervise():
     for prec in order:
         # N > 1: the headline arithmetic only (its parity is established by the N = 1 run: same kernels, same shapes
         # per rank or smaller); three rendezvous per invocation would triple the driver's wall time for nothing
-        if prec != first and (os.environ.get("RFN_BENCH_ONE_PRECISION") == "1" or world > 1):
+        if prec != first and (not a.full or os.environ.get("RFN_BENCH_ONE_PRECISION") == "1" or world > 1):
             break
         env = dict(os.environ)
         env["RFN_CONV_PRECISION"] = prec
-        out, fell_back = _run_child([] if prec == first else ["--secondary"], env)
+        extra = [] if prec == first else ["--secondary"]
+        if a.dump_outputs and prec != first:
+            extra += ["--dump-outputs", os.path.join(tmp, prec)]
+        out, fell_back = _run_child(extra, env)
         if out is None:
             if prec == first:
                 return 1
@@ -383,6 +428,9 @@ def supervise():
         head = "f32" if "f32" in runs else first
     if world > 1:
         head = first
+    if a.dump_outputs and head != first:   # the dumped outputs are the headline run's
+        for f in os.listdir(os.path.join(tmp, head)):
+            shutil.copy(os.path.join(tmp, head, f), os.path.join(a.dump_outputs, f))
     out = dict(runs[first])                     # roofline / cpu_baseline / kernel tables come from the primary run
     for k in ("value", "ms_per_step", "modeled_frames_per_s", "bits_per_dim_last_step", "launch_mode", "dtype",
               "graph_fallback", "parity"):
@@ -394,20 +442,27 @@ def supervise():
     return 0
 
 
-def main():
+def make_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32, help="GLOBAL batch (sequences)")
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the other arithmetics, parity vs the oracle, forward-only rate, roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a captured hipGraph step")
     ap.add_argument("--no-parity", action="store_true", help="skip the GPU-vs-oracle bits/dim check (profiling runs)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--secondary", action="store_true", help=argparse.SUPPRESS)  # second precision: timing + parity only
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = make_parser().parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", 1))
     rank = int(os.environ.get("RANK", 0))
@@ -437,7 +492,7 @@ def main():
     from rfn_hip import lib as rlib
     for i in range(max(a.warmup, 1)):
         solver.train_step(batches[i % 2])
-    profile = rank == 0 and world == 1 and not a.no_roofline and not a.secondary
+    profile = a.full and rank == 0 and world == 1 and not a.no_roofline and not a.secondary
     rec = None
     if profile:
         # kernel roofline: HIP events on the launch stream around every librfn_hip launch of eager training steps
@@ -480,6 +535,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     solver.flush_log()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, solver)
     if rank == 0:
         print("[bench] timed region done: %.1f ms/step (%s)" % (1e3 * dt / a.steps, "graph" if graphed else "eager"),
               file=sys.stderr, flush=True)
@@ -501,9 +558,9 @@ def main():
                       "global_batch": a.batch, "seq_len": a.frames, "parallelism": "dp%d" % world},
            "modeled_frames_per_s": a.batch * (a.frames - 1) * a.steps / dt, "bits_per_dim_last_step": bpd,
            "launch_mode": "hipGraph replay (fwd+bwd captured)" if graphed else "eager"}
-    if rank == 0 and world == 1 and a.secondary and not a.no_parity:
+    if a.full and rank == 0 and world == 1 and a.secondary and not a.no_parity:
         out["parity"] = parity_check(device)
-    if rank == 0 and world == 1 and not a.secondary:
+    if a.full and rank == 0 and world == 1 and not a.secondary:
         # forward-only rate: RFN.loss under no_grad on the same batch, eager launches
         with torch.no_grad():
             xin = solver.preprocess(batches[0])
@@ -517,8 +574,8 @@ def main():
         if profile:
             roof, table = kernel_roofline(rec, 2)
             out["roofline"] = roof
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_kernel_table.json"), "w") as f:
+            os.makedirs(os.path.join(ROOT, "bench_out"), exist_ok=True)
+            with open(os.path.join(ROOT, "bench_out", "bench_kernel_table.json"), "w") as f:
                 json.dump({"columns": ["kernel", "launches_per_step", "ms_per_step", "TFLOP/s (fp32-equivalent)",
                                        "algorithmic GB/s"],
                            "rows": table["kernels"], "by_shape": table["shapes"]}, f, indent=1)

@@ -1,6 +1,6 @@
-"""Developer tool: print gpurun_out/bench_kernel_table.json rows matching a substring."""
+"""Developer tool: print bench_out/bench_kernel_table.json (written by `bench.py --full`) rows matching a substring."""
 import json, sys
-d = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/bench_kernel_table.json"))
+d = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "bench_out/bench_kernel_table.json"))
 pat = sys.argv[2] if len(sys.argv) > 2 else ""
 print("---- kernels")
 for r in d["rows"]:
