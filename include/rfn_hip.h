@@ -476,6 +476,18 @@ int rfn_adam_chunk_elems(void);
 int rfn_adam_step_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1, double beta2,
                       double eps, double weight_decay, int t, rfn_stream_t stream);
 
+/* ---- video-prediction quality of uint8 frames  (evaluation_metrics/error_metrics.py:154-171, Evaluator.eval_seq: skimage
+ * 0.17.2 `structural_similarity` / `peak_signal_noise_ratio` per channel, with their defaults on uint8: 7x7 uniform window,
+ * data_range 255, K1 = 0.01, K2 = 0.03, sample covariance (x 49/48), S map averaged over the interior (H-6) x (W-6)).
+ * a, b: uint8 NCHW frames (frame strides a_ns / b_ns in elements, i.e. bytes); per frame n (float32 [N] outputs):
+ *   mse[n]  = sum of squared differences / (C*H*W),
+ *   psnr[n] = mean over channels of 10 log10(255^2 / mean((a-b)^2)), +inf when a channel is identical,
+ *   ssim[n] = mean over channels of the single-channel SSIM.
+ * Window sums and (co)variances are exact integers, the S formula runs in fp64, reductions in a fixed order: results
+ * are bit-reproducible.  H < 7 or W < 7 is an argument error (skimage: "win_size exceeds image extent"). */
+int rfn_frame_quality_u8(const void* a, long a_ns, const void* b, long b_ns, float* mse, float* psnr, float* ssim,
+                         int N, int C, int H, int W, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

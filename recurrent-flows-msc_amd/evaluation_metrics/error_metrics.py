@@ -1,8 +1,12 @@
-"""Evaluator — the bits-per-dim part of the reference's evaluation driver (evaluation_metrics/error_metrics.py): the
-`compute_loss` bookkeeping (:358-368) and the test-set loop `get_loss` (:370-417) that re-uses `Solver.preprocess` and
-`RFN.loss`, plus thin wrappers over the model's analysis methods (`RFN.reconstruct_elbo_gap`, `.probability_future`,
-`.param_analysis`, RFN/RFN_new.py:496-788).  The image-quality metrics of that file (PSNR / SSIM / LPIPS / FVD) and its
-plotting need lpips, skimage and a TF-hub network and are outside the hot-path scope."""
+"""Evaluator — the evaluation driver of the reference (evaluation_metrics/error_metrics.py): the `compute_loss`
+bookkeeping (:358-368), the bits-per-dim test-set loop `get_loss` (:370-417) that re-uses `Solver.preprocess` and
+`RFN.loss`, the per-frame image-quality scores `eval_seq` (:154-171: MSE, PSNR and SSIM with skimage 0.17.2's defaults,
+computed on the GPU by one rfn_frame_quality_u8 launch per call instead of a per-channel CPU loop), the best-of-N
+prediction evaluation `get_eval_values` (:419-598, without its plots), plus thin wrappers over the model's analysis
+methods (`RFN.reconstruct_elbo_gap`, `.probability_future`, `.param_analysis`, RFN/RFN_new.py:496-788).
+LPIPS and FVD need pretrained AlexNet / I3D networks and are not computed; the plots are not drawn."""
+import warnings
+
 import numpy as np
 import torch
 
@@ -17,6 +21,14 @@ class Evaluator(object):
         # the reference evaluates the loss on as many frames as the model was trained on (:387-388)
         self.n_trained = getattr(settings, "n_trained", None) or getattr(self.args, "n_frames", None)
         self.device = solver.device
+        # get_eval_values (:419-598) reads the evaluation settings; unset ones default to the training arguments
+        self.n_frames = getattr(settings, "n_frames", None) or getattr(self.args, "n_frames", None)
+        self.start_predictions = (getattr(settings, "start_predictions", None) or
+                                  getattr(self.args, "n_conditions", None))
+        self.resample = getattr(settings, "resample", None) or 1
+        self.extra_plots = bool(getattr(settings, "extra_plots", False))
+        self.debug_plot = bool(getattr(settings, "debug_plot", False))
+        self._warned_plots = False
 
     def compute_loss(self, nll, kl, dims, t=10):
         """error_metrics.py:358-368 -> (bits/dim, kl / t, nll / t)"""
@@ -50,6 +62,97 @@ class Evaluator(object):
             mean = means.mean()
             std = means.std() if loss_resamples > 1 else -1
         return mean, std
+
+    @staticmethod
+    def _as_u8(x, name):
+        """uint8 view of a frame tensor: uint8 as is, a float tensor only when it holds integers in [0, 255] (what the
+        reference passes after `preprocess(reverse=True)` and its FloatTensor cast)"""
+        if not isinstance(x, torch.Tensor):
+            raise ValueError("eval_seq: %s must be a tensor, got %s" % (name, type(x).__name__))
+        if x.dtype == torch.uint8:
+            return x
+        if not x.is_floating_point():
+            raise ValueError("eval_seq: %s must be uint8 or a float tensor of integers in [0, 255], got %s" %
+                             (name, x.dtype))
+        if x.numel() and not bool(((x >= 0) & (x <= 255) & (x == torch.floor(x))).all()):
+            raise ValueError("eval_seq: %s holds values that are not integers in [0, 255]" % name)
+        return x.to(torch.uint8)
+
+    def eval_seq(self, gt, pred):
+        """error_metrics.py:154-171: per-frame (mse, ssim, psnr) of ground truth and prediction [bs, T, C, H, W]
+        (uint8, or float tensors of integers in [0, 255], on the GPU) as CPU float32 [bs, T]: ssim / psnr are the means
+        over channels of skimage 0.17.2's single-channel SSIM / PSNR (+inf on an identical channel), mse the mean of the
+        squared difference over (C, H, W).  One kernel launch; no CPU fallback."""
+        from rfn_hip import ops
+        if not (isinstance(gt, torch.Tensor) and isinstance(pred, torch.Tensor)):
+            raise ValueError("eval_seq: gt and pred must be tensors")
+        if gt.dim() != 5 or tuple(gt.shape) != tuple(pred.shape):
+            raise ValueError("eval_seq: gt and pred must both be [bs, T, C, H, W], got %s and %s" %
+                             (tuple(gt.shape), tuple(pred.shape)))
+        mse, psnr, ssim = ops.frame_quality(self._as_u8(gt, "gt"), self._as_u8(pred, "pred"))
+        return mse.cpu(), ssim.cpu(), psnr.cpu()
+
+    def get_eval_values(self, model_name="rfn.pt", loader=None, max_batches=None):
+        """error_metrics.py:419-598 without the plots: per test batch, `resample` rounds of RFN.predict (conditioned on
+        start_predictions frames, n_frames - start_predictions predicted), the loss on the first n_trained frames and
+        eval_seq of the predictions against the ground truth; per sequence the best of the draws is kept (strictly
+        higher time-mean PSNR / SSIM, strictly lower MSE; ties keep the earlier draw).  Returns the reference's tuple
+        (MSE, PSNR, SSIM, LPIPS, BPD, DKL, RECON, SSIM_std, PSNR_std, LPIPS_std): MSE / PSNR / SSIM [n_seq, n_pred] of the
+        best draws; LPIPS and LPIPS_std None (no pretrained network here); BPD / DKL / RECON one value per batch, from its
+        last resample; SSIM_std / PSNR_std [n_seq, n_pred], the mean over the draws.
+
+        Reference quirk kept on purpose, so that the figures stay comparable with published ones: the first draw's
+        SSIM / PSNR tensors ARE the best-so-far tensors (the reference aliases them) and the best-of-N updates write into
+        them in place, so the "mean over draws" averages the final best values in place of draw 0."""
+        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        if (self.extra_plots or self.debug_plot) and not self._warned_plots:
+            warnings.warn("Evaluator.get_eval_values: extra_plots / debug_plot only draw figures; skipped")
+            self._warned_plots = True
+        loader = loader if loader is not None else self.test_loader
+        start, n_frames = self.start_predictions, self.n_frames
+        mse_values, psnr_values, ssim_values, ssim_std_values, psnr_std_values = [], [], [], [], []
+        bpd_list, dkl_list, recon_list = [], [], []
+        with torch.no_grad():
+            self.model.eval()
+            for batch_i, true_image in enumerate(loader):
+                if max_batches is not None and batch_i >= max_batches:
+                    break
+                image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
+                image = self.solver.preprocess(image.to(self.device))
+                imageloss = image[:, :self.n_trained] if self.n_trained else image
+                image_u8 = self.solver.preprocess(image, reverse=True)
+                ssim_draws, psnr_draws = [], []
+                for r in range(self.resample):
+                    _, predictions = self.model.predict(image, n_frames - start, start)
+                    _, kl, nll = self.model.loss(imageloss, 0)
+                    bpd, kl_loss, recon_loss = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:],
+                                                                 t=imageloss.shape[1] - 1)
+                    pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 0, 2, 3, 4)
+                    pred_u8 = pred_u8.to(self.device)
+                    gt_u8 = image_u8[:, start:start + pred_u8.shape[1]]
+                    mse, ssim, psnr = self.eval_seq(gt_u8, pred_u8)
+                    if r == 0:
+                        mse_best, ssim_best, psnr_best = mse, ssim, psnr   # aliased, as in the reference
+                    else:
+                        better = psnr_best.mean(-1) < psnr.mean(-1)
+                        psnr_best[better, :] = psnr[better, :]
+                        better = ssim_best.mean(-1) < ssim.mean(-1)
+                        ssim_best[better, :] = ssim[better, :]
+                        better = mse_best.mean(-1) > mse.mean(-1)
+                        mse_best[better, :] = mse[better, :]
+                    ssim_draws.append(ssim)
+                    psnr_draws.append(psnr)
+                ssim_std_values.append(torch.stack(ssim_draws).mean(0))
+                psnr_std_values.append(torch.stack(psnr_draws).mean(0))
+                mse_values.append(mse_best)
+                psnr_values.append(psnr_best)
+                ssim_values.append(ssim_best)
+                bpd_list.append(bpd)
+                dkl_list.append(kl_loss)
+                recon_list.append(recon_loss)
+        return (torch.cat(mse_values), torch.cat(psnr_values), torch.cat(ssim_values), None,
+                torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
+                torch.cat(ssim_std_values), torch.cat(psnr_std_values), None)
 
     # ---- the analyses the reference's evaluator drives (error_metrics.py: plot_elbo_gap, plot_prob_of_t, param_plots)
     def elbo_gap(self, image, sample=False):
