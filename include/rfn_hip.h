@@ -488,6 +488,19 @@ int rfn_adam_step_f32(const rfn_adam_entry* table, const int* chunks, int n_chun
 int rfn_frame_quality_u8(const void* a, long a_ns, const void* b, long b_ns, float* mse, float* psnr, float* ssim,
                          int N, int C, int H, int W, rfn_stream_t stream);
 
+/* ---- Stochastic Moving MNIST rendered on the device  (data_generators/stochasticMovingMnist.py:48-127,
+ * MovingMNIST.__getitem__ as RFN/trainer.py:112-131 calls it: normalize=False; digit_size 28, for which the Resize(28)
+ * of :33-37 is the identity).  digits: uint8 [N, 28, 28] device table.  Writes out: fp32 [B, T, C, S, S] in [0, 1]
+ * (16-byte aligned for the vector stores; any 4-byte alignment works), sequence b of the launch having the id
+ * first_id + b; traj (nullable): int64 [B, num_digits, T, 3] of (digit index, y, x) per digit and frame.  Every random
+ * draw is addressed: Philox4x64-10 with key (seed, split) and counter (draw number, retry, sequence id, digit), bounded
+ * by Lemire's multiply-shift with rejection (csrc/moving_mnist.hip states the scheme); the walk, its draw order and the
+ * float32 pixel pipeline are the reference's.  deterministic != 0: a wall bounce negates the velocity component.
+ * Limits: 28 < S <= 4096, 1 <= num_digits <= 8, step_length >= 1, seed, split, first_id >= 0.  One launch. */
+int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long* traj, int B, int T, int C, int S,
+                                int num_digits, int step_length, int deterministic, long seed, long split,
+                                long first_id, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 """Solver — training driver with the reference's surface (RFN/trainer.py of the reference): `Solver(args).build();
 .train(); .load(ckpt)`, `preprocess`, `compute_loss` (bits/dim bookkeeping), β annealing, linear LR decay, checkpoint
-dict layout.  Plotting (matplotlib PNG panels) and the file-backed datasets are outside the hot-path scope; a synthetic
-SM-MNIST-shaped loader is built in (`--synthetic_data`).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
+dict layout.  Plotting (matplotlib PNG panels) and the BAIR / KTH datasets are outside the hot-path scope; a synthetic
+SM-MNIST-shaped loader is built in (`--synthetic_data`), and Stochastic Moving MNIST is rendered on the GPU from local
+MNIST files (`--choose_data mnist`, data_generators/moving_mnist.py).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
 import math
 import os
 
@@ -91,7 +92,9 @@ class Solver(object):
 
     def create_loaders(self):
         if not getattr(self.args, "synthetic_data", False):
-            raise RuntimeError("the file-backed datasets of the reference (MNIST download, BAIR, KTH) are outside this "
+            if self.choose_data == "mnist":
+                return self.create_mnist_loaders()
+            raise RuntimeError("the file-backed datasets of the reference (BAIR, KTH) are outside this "
                                "implementation's scope; pass --synthetic_data for SM-MNIST-shaped synthetic video")
         c = self.args.x_dim[1]
         mk = lambda seed: SyntheticMovingMNIST(seq_len=self.n_frames, image_size=self.image_size,
@@ -100,6 +103,28 @@ class Solver(object):
                                                seed=seed * self.world + self.rank)
         kw = dict(batch_size=self.batch_size, num_workers=self.num_workers, shuffle=True, drop_last=True)
         return DataLoader(mk(0), **kw), DataLoader(mk(1), **kw)
+
+    def create_mnist_loaders(self):
+        """RFN/trainer.py:112-131, :155-161: Stochastic Moving MNIST (deterministic=False, normalize=False) rendered on
+        the GPU from the MNIST files under --mnist_root (default "Mnist", relative to the working directory, like the
+        reference).  One channel, or three copies when x_dim asks for 3.  With --use_validation_set the train split
+        is its first 500 sequences per epoch.  Every rank renders its own rows of each global batch; the test split is
+        the same set of sequences on every evaluation."""
+        from data_generators import MovingMNIST, MovingMNISTLoader
+        c = self.args.x_dim[1]
+        if c not in (1, 3):
+            raise ValueError("Stochastic Moving MNIST has 1 or 3 (replicated) channels; x_dim asks for %d" % c)
+        root = getattr(self.args, "mnist_root", "Mnist")   # (Namespaces saved before these flags existed)
+        seed = getattr(self.args, "data_seed", 0)
+        mk = lambda train, length=None: MovingMNIST(train, root, seq_len=self.n_frames, num_digits=self.num_digits,
+                                                    image_size=self.image_size, digit_size=self.digit_size,
+                                                    deterministic=False, three_channels=c == 3,
+                                                    step_length=self.step_length, normalize=False, seed=seed,
+                                                    device=self.device, length=length)
+        trainset = mk(True, 500 if self.use_validation_set else None)
+        testset = mk(False)
+        return (MovingMNISTLoader(trainset, self.batch_size, self.rank, self.world),
+                MovingMNISTLoader(testset, self.batch_size, self.rank, self.world))
 
     # ---------------------------------------------------------------------------------------------- arithmetic
     def preprocess(self, x, reverse=False):
@@ -265,6 +290,8 @@ class Solver(object):
         max_steps = getattr(self.args, "max_steps", 0)
         for _ in range(self.n_epochs):
             self.model.train()
+            if hasattr(self.train_loader, "set_epoch"):   # the device loader: epoch e renders its own sequences
+                self.train_loader.set_epoch(self.epoch_i)
             self.epoch_i += 1
             for image in self.train_loader:
                 image = image[0] if self.choose_data == "bair" and isinstance(image, (list, tuple)) else image

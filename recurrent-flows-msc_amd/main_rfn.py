@@ -1,7 +1,12 @@
 """Command line entry with the reference's flags (main_rfn.py of the reference: same names, types and defaults), so
 a job script written for the reference drives this implementation unchanged.  Additions (all optional):
   --synthetic_data   use the built-in SM-MNIST-shaped generator instead of files on disk (no dataset ships here);
-  --max_steps        stop after that many optimizer steps.
+  --max_steps        stop after that many optimizer steps;
+  --mnist_root       where `--choose_data mnist` reads the MNIST digits (default "Mnist" in the working directory, as
+                     the reference; torchvision's MNIST/raw or MNIST/processed files, never downloaded);
+  --data_seed        keys the random draws of Stochastic Moving MNIST (default 0).
+With `--choose_data mnist` and no `--synthetic_data`, Stochastic Moving MNIST is rendered on the GPU (one kernel launch
+per batch, no DataLoader workers); BAIR and KTH still need `--synthetic_data`.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main_rfn.py ... --multigpu`; one process
 per GPU, the global batch is sharded over ranks and gradients are all-reduced with RCCL (see rfn_hip/dist.py).
 """
@@ -137,6 +142,9 @@ def build_parser():
     # additions of this implementation
     add_bool_arg(p, "synthetic_data", default=False, help="SM-MNIST-shaped synthetic video instead of files on disk")
     p.add_argument("--max_steps", help="Stop after this many optimizer steps (0 = no limit)", default=0, type=int)
+    p.add_argument("--mnist_root", help="Directory holding torchvision's MNIST files for --choose_data mnist",
+                   default="Mnist", type=str)
+    p.add_argument("--data_seed", help="Seed of the Stochastic Moving MNIST sequences", default=0, type=int)
     return p
 
 

@@ -125,6 +125,8 @@ SIGNATURES = {
     "rfn_convlstm_gates_bwd_f32": [_c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f,
                                    _c_l, _c_i, _c_i, _c_i, _c_s],
     "rfn_frame_quality_u8": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_moving_mnist_render_f32": [ctypes.c_void_p, _c_i, _c_f, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
+                                    _c_l, _c_l, _c_l, _c_s],
 }
 _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_packed_weight_size": ctypes.c_long,
              "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,

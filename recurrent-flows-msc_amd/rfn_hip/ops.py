@@ -1800,3 +1800,44 @@ def frame_quality(a, b):
                _i(H), _i(W), meta=("shell", "frame_quality", 0.0, "x".join(str(int(d)) for d in a.shape),
                                   2.0 * a.numel()))
     return mse, psnr, ssim
+
+
+def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, deterministic, seed, split, first_id,
+                        trajectories=False):
+    """Stochastic Moving MNIST batch rendered on the GPU (rfn_moving_mnist_render_f32: the reference's
+    MovingMNIST.__getitem__, stochasticMovingMnist.py:48-127, with addressed random draws): a fresh float32 tensor
+    [B, T, C, S, S] in [0, 1] on the digits' device, sequence b having the id first_id + b; with trajectories=True also
+    the int64 [B, num_digits, T, 3] (digit index, y, x) of every digit and frame.  `digits`: uint8 [N, 28, 28] device
+    table.  One launch on the current stream; no CPU fallback."""
+    if not isinstance(digits, torch.Tensor) or digits.dtype != torch.uint8:
+        raise TypeError("moving_mnist_render: digits must be a uint8 tensor, got %s" %
+                        (digits.dtype if isinstance(digits, torch.Tensor) else type(digits).__name__))
+    if digits.dim() != 3 or tuple(digits.shape[1:]) != (28, 28) or digits.shape[0] < 1:
+        raise ValueError("moving_mnist_render: digits must be [N >= 1, 28, 28], got %s" % (tuple(digits.shape),))
+    if not digits.is_cuda:
+        raise RuntimeError("rfn_hip kernels need device tensors; digits is on %s (no CPU fallback)" % digits.device)
+    B, T, C, S, nd, L_, seed, split, first_id = (int(v) for v in (B, T, C, S, num_digits, step_length, seed, split,
+                                                                  first_id))
+    if B < 0 or T < 1 or C < 1:
+        raise ValueError("moving_mnist_render: need B >= 0, T >= 1, C >= 1 (got %d, %d, %d)" % (B, T, C))
+    if not 28 < S <= 4096:
+        raise ValueError("moving_mnist_render: image size %d must exceed the digit size 28 (and be <= 4096)" % S)
+    if not 1 <= nd <= 8:
+        raise ValueError("moving_mnist_render: num_digits %d not in [1, 8]" % nd)
+    if not 1 <= L_ <= 1 << 20:
+        raise ValueError("moving_mnist_render: step_length %d must be >= 1" % L_)
+    for v, nm in ((seed, "seed"), (split, "split"), (first_id, "first_id")):
+        if not 0 <= v < 1 << 63:
+            raise ValueError("moving_mnist_render: %s %d not in [0, 2^63)" % (nm, v))
+    if B * T > 0x7fffffff:
+        raise ValueError("moving_mnist_render: B * T = %d frames exceed one launch" % (B * T))
+    digits = digits.contiguous()
+    out = torch.empty((B, T, C, S, S), device=digits.device, dtype=torch.float32)
+    traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
+    if B:
+        with torch.cuda.device(digits.device):
+            L.call("rfn_moving_mnist_render_f32", ctypes.c_void_p(digits.data_ptr()), _i(int(digits.shape[0])),
+                   L.dev(out), ctypes.c_void_p(traj.data_ptr()) if traj is not None else None, _i(B), _i(T), _i(C),
+                   _i(S), _i(nd), _i(L_), _i(1 if deterministic else 0), _l(seed), _l(split), _l(first_id),
+                   meta=("shell", "moving_mnist", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
+    return (out, traj) if trajectories else out
