@@ -129,8 +129,9 @@ class Conv2dNorm(nn.Module):
             return
         if self.training:
             w = self.conv.weight
-            u = K.conv2d_raw(input.detach(), None if input2 is None else input2.detach(), K.pack_weight(w),
-                             int(w.shape[0]), int(w.shape[2]))
+            fp = K.fwd_prec(int(input.shape[2]), int(input.shape[3]))  # the forward's arithmetic, not the gradients'
+            u = K.conv2d_raw(input.detach(), None if input2 is None else input2.detach(), K.pack_weight(w, prec=fp),
+                             int(w.shape[0]), int(w.shape[2]), prec=fp)
             an.set_from_stats(*K.channel_stats(u))
         an.mark_initialized()
 
