@@ -32,6 +32,11 @@ extern "C" {
 
 typedef void* rfn_stream_t;
 
+/* Version of this ABI, checked by the loader.  2: the conv weight pack from a DEVICE descriptor table is removed (host
+ * descriptors only: rfn_pack_conv_weights_hostdescs_bf16x3); rfn_coupling_po_fwd gained the mask outputs m1 / m2,
+ * rfn_stepbn_bwd_f32 its stage / world arguments; the log-det argument of rfn_glow_shell_fwd_f32 is a written
+ * [blocks][slots] partials buffer (rfn_logdet_reduce_f32) and that of rfn_invconv_weights_fwd_f32 is written, not
+ * accumulated. */
 int rfn_abi_version(void);
 const char* rfn_last_error(void);
 
@@ -138,8 +143,9 @@ int rfn_conv2d_dgrad_act_bf16x3(const float* gin, long gin_ns, int Cin, const fl
                                 const float* logs, int act, float* out, long out_ns, float* part, int Cout, int N,
                                 int H, int W, int ks, rfn_stream_t stream);
 
-/* Pack MANY weights in one launch (a whole flow: ~300 descriptors per training step instead of ~370 launches).
- * descs_device: device array of n rfn_pack_desc; mode 0 forward, 1 data-gradient (transposed, taps mirrored),
+/* Pack many weights at once: n descriptors in HOST memory, 64 per launch (the table travels in the kernel arguments).
+ * The host collects the packs a step asks for back to back and hands them over in one call; rfn_pack_conv_weight_bf16x3
+ * / _bf16x6 are the one-descriptor form of this call.  mode 0 forward, 1 data-gradient (transposed, taps mirrored),
  * 2 tap-expanded 1x1 form of a 3x3 conv with tiny Cout (w'[tap*Cout+co][ci] = w[co][ci][tap]); mode + 4: three planes
  * (bf16x6) instead of two.  Each wpk must hold rfn_packed_weight_size_bf16x3 (or _bf16x6) floats of the LOGICAL conv
  * (mode 2: Cout' = 9*Cout, ks' = 1). */
@@ -148,8 +154,6 @@ typedef struct {
     float* wpk;
     int Cout, Cin, ks, mode;
 } rfn_pack_desc;
-int rfn_pack_conv_weights_batched_bf16x3(const void* descs_device, int n, rfn_stream_t stream);
-/* the same for descriptors in HOST memory (packs queued by the host between two launches): 64 per launch */
 int rfn_pack_conv_weights_hostdescs_bf16x3(const void* descs_host, int n, rfn_stream_t stream);
 
 /* ---- a5 fused  AffineCoupling.net forward for the shallow levels (Flow/glow_modules.py:232-238 with :119-121 and
@@ -379,8 +383,9 @@ int rfn_latent_step_bwd_f32(const float* enc, const float* pri, const float* eps
 long rfn_smallmap_packed_size(int Cout, int Cin, int H, int W, int transpose);
 int rfn_smallmap_pack_bf16x3(const float* w, int Cout, int Cin, int H, int W, int transpose, float* packed,
                              rfn_stream_t stream);
-/* The same for n matrices in ceil(n / 64) launches: host array of descriptors (the packs of one training step -- latent
- * nets, ConvLSTM, the 2x2 flow level -- are queued by the host and flushed before their first consumer). */
+/* The same for n matrices in ceil(n / 64) launches: host array of descriptors (the host hands over the packs a step asks
+ * for back to back -- a recurrent net's layers, a ConvLSTM's two weight halves -- in one call; rfn_smallmap_pack_bf16x3
+ * is the one-descriptor form of this call). */
 typedef struct {
     const float* w;   /* [Cout][Cin][3][3] */
     float* packed;    /* rfn_smallmap_packed_size(Cout, Cin, H, W, transpose) bytes, 16-byte aligned */

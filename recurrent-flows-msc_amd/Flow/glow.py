@@ -183,69 +183,54 @@ class ListGlow(nn.Module):
         return True
 
     def _packed_weights(self, x_shape, condition):
-        """two launches re-pack every coupling-net weight of the flow: the split-precision (bf16x3) packs of the
-        data-gradient convolutions -- and of the forward convolutions where bf16x3 is the forward arithmetic -- and the
-        fragment streams of the fused forward kernel (shallow levels, 'mixed' arithmetic).
-        Returns {GlowStep: (w1 f, w1 d, w2 f, w2 d, w3 f, w3 d, fused forward stream, fused backward stream)} (entries
-        None where unused) or None."""
+        """re-pack every coupling-net weight of the flow, one launch per kind: the dense small-map packs of the deepest
+        levels, the split-precision packs of the data-gradient convolutions -- and of the forward convolutions where a
+        split arithmetic is the forward arithmetic -- and the fragment streams of the fused kernels (shallow levels,
+        'mixed' arithmetic).  Re-packed on every call: a captured training step must contain the launches (a
+        version-keyed cache would be hit during capture and the replays would run on stale packs).
+        Returns {GlowStep: rfn_hip.ops.StepPacks} or None."""
         if not K.bwd_b3():
             return None
         levels = self._level_steps()
         if not levels or not levels[0][1] or not levels[0][1][0].affine.net[0].conv.weight.is_cuda:
             return None
         N, C, H, W = (int(v) for v in x_shape)
-        items, nets, slots = [], [], {}
-        for l, (_, steps, split) in enumerate(levels):
-            C, H, W = C * 4, H // 2, W // 2
-            Cc = int(condition[l].shape[1])
-            for s in steps:
-                n0, n2, n4 = s.affine.net[0], s.affine.net[2], s.affine.net[4]
-                w1, w2, w3 = n0.conv.weight, n2.conv.weight, n4.conv.weight
-                fused = s.flow_norm != "batchnorm" and int(w2.shape[2]) == 1 and \
-                    K.coupling_po_ok(N, C, Cc, int(w1.shape[0]), H, W, w1, w3)
-                fp = K.fwd_prec(H, W)
-                b3fwd = not fused and fp in ("bf16x3", "bf16x6")
-                x6 = 4 if fp == "bf16x6" else 0   # forward packs in three planes where bf16x6 is the forward arithmetic
-                slot = [None] * 7
-                for j, (w, mode) in enumerate(((w1, 0), (w1, 1), (w2, 0), (w2, 1),
-                                               (w3, 2 if K.zeros_conv_uses_taps(w3) else 0), (w3, 1))):
-                    if j % 2 == 1 or b3fwd:
-                        slot[j] = len(items)
-                        items.append((w, mode + (x6 if j % 2 == 0 else 0)))
-                if fused:
-                    slot[6] = len(nets)
-                    nets.append((w1, w2, w3))
-                slots[s] = slot
-            if split is not None:
-                C = C // 2
-        # the dense packs of the small-map levels (H*W <= 16: level 4 of the canonical flow), forward and -- when a
-        # gradient will be asked for -- data-gradient orientation: queued here, all of them leave in ONE launch before the
-        # first kernel that reads one (rfn_hip.ops.smallmap_pack).  Re-packed on every call like the plans below: a
-        # captured training step must contain the launch (a version-keyed cache would be hit during capture and the
-        # replays would run on stale packs).
-        dense = {}
-        Cd, Hd_, Wd_ = (int(v) for v in x_shape[1:])
-
-        def dense_pack(s_, slot, w, transpose):
-            return K.smallmap_pack(w, Hd_, Wd_, transpose)
-
-        for l, (_, steps, split) in enumerate(levels):
-            Cd, Hd_, Wd_ = Cd * 4, Hd_ // 2, Wd_ // 2
-            Ccd = int(condition[l].shape[1])
-            for s in steps:
-                w1, w3 = s.affine.net[0].conv.weight, s.affine.net[4].conv.weight
-                k33 = int(w1.shape[2]) == 3 and int(w3.shape[2]) == 3
-                d8 = d9 = d10 = None
-                if k33 and K.smallmap_conv_ok(Hd_, Wd_, Cd // 2, Ccd, int(w1.shape[0]), N):
-                    d8 = dense_pack(s, 8, w1, False)
-                if k33 and K.smallmap_conv_ok(Hd_, Wd_, int(w1.shape[0]), 0, Cd, N) and not K.zeros_conv_uses_taps(w3):
-                    d9 = dense_pack(s, 9, w3, False)
-                if (torch.is_grad_enabled() and k33
-                        and K.smallmap_conv_ok(Hd_, Wd_, int(w1.shape[0]), 0, Cd // 2 + Ccd, N, bwd=True)):
-                    d10 = dense_pack(s, 10, w1, True)
-                dense[s] = (d8, d9, d10)
-            if split is not None:
-                Cd = Cd // 2
+        items, nets, slots, dense = [], [], {}, {}
+        with K.PackBatch() as pb:
+            for l, (_, steps, split) in enumerate(levels):
+                C, H, W = C * 4, H // 2, W // 2
+                Cc = int(condition[l].shape[1])
+                for s in steps:
+                    n0, n2, n4 = s.affine.net[0], s.affine.net[2], s.affine.net[4]
+                    w1, w2, w3 = n0.conv.weight, n2.conv.weight, n4.conv.weight
+                    Hd = int(w1.shape[0])
+                    fused = s.flow_norm != "batchnorm" and int(w2.shape[2]) == 1 and \
+                        K.coupling_po_ok(N, C, Cc, Hd, H, W, w1, w3)
+                    fp = K.fwd_prec(H, W)
+                    b3fwd = not fused and fp in ("bf16x3", "bf16x6")
+                    x6 = 4 if fp == "bf16x6" else 0   # forward packs in three planes where bf16x6 is the forward arithmetic
+                    slot = {}
+                    for name, w, mode in (("w1_fwd", w1, 0), ("w1_dgrad", w1, 1), ("w2_fwd", w2, 0), ("w2_dgrad", w2, 1),
+                                          ("w3_fwd", w3, 2 if K.zeros_conv_uses_taps(w3) else 0), ("w3_dgrad", w3, 1)):
+                        if mode == 1 or b3fwd:
+                            slot[name] = len(items)
+                            items.append((w, mode if mode == 1 else mode + x6))
+                    if fused:
+                        slot["po"] = len(nets)
+                        nets.append((w1, w2, w3))
+                    slots[s] = slot
+                    # the dense packs of the small-map levels (H*W <= 16: level 4 of the canonical flow), forward and --
+                    # when a gradient will be asked for -- data-gradient orientation
+                    k33 = int(w1.shape[2]) == 3 and int(w3.shape[2]) == 3
+                    d = dense[s] = {}
+                    if k33 and K.smallmap_conv_ok(H, W, C // 2, Cc, Hd, N):
+                        d["w1_dense_fwd"] = pb.dense(w1, H, W, False)
+                    if k33 and K.smallmap_conv_ok(H, W, Hd, 0, C, N) and not K.zeros_conv_uses_taps(w3):
+                        d["w3_dense_fwd"] = pb.dense(w3, H, W, False)
+                    if torch.is_grad_enabled() and k33 and K.smallmap_conv_ok(H, W, Hd, 0, C // 2 + Cc, N, bwd=True):
+                        d["w1_dense_dgrad"] = pb.dense(w1, H, W, True)
+                if split is not None:
+                    C = C // 2
         plan = getattr(self, "_pack_plan", None)
         if plan is None or not plan.valid_for(items):
             plan = self._pack_plan = K.PackPlan(items)
@@ -256,10 +241,13 @@ class ListGlow(nn.Module):
             if po is None or not po.valid_for(nets):
                 po = self._po_plan = K.POPackPlan(nets)
             po.run(bwd=torch.is_grad_enabled())
-        return {s: tuple((None if i is None else plan.bufs[i]) for i in sl[:6])
-                + ((None if sl[6] is None else po.bufs[sl[6]]), (None if sl[6] is None else po.bwd_bufs[sl[6]]))
-                + dense[s]
-                for s, sl in slots.items()}
+        out = {}
+        for s, slot in slots.items():
+            kw = {name: plan.bufs[i] for name, i in slot.items() if name != "po"}
+            if "po" in slot:
+                kw.update(po_fwd=po.bufs[slot["po"]], po_bwd=po.bwd_bufs[slot["po"]])
+            out[s] = K.StepPacks(**kw, **dense[s])
+        return out
 
     def f(self, x, condition, logdet):
         """Flow/glow.py:105-117 (same order of operations; per-level batching of the tiny parameter algebra)."""

@@ -13,7 +13,6 @@ from torch.utils.data import DataLoader
 
 from data_generators import SyntheticMovingMNIST
 from rfn_hip import dist as rdist
-from rfn_hip import ops as K
 from Utils import set_gpu
 from .RFN_new import RFN
 
@@ -221,7 +220,6 @@ class Solver(object):
                     self.optimizer.zero_grad(set_to_none=True)
             torch.cuda.current_stream().wait_stream(side)
             self.optimizer.zero_grad(set_to_none=True)
-            K.flush_packs()   # (nothing queued outside may be launched -- and replayed -- inside the capture)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._graph_body()

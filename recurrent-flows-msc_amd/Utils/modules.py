@@ -131,15 +131,16 @@ def per_step_batchnorm_act(bn, x, steps, act_code, slope):
 
 def queue_conv_packs(seqs, x):
     """{conv module: (forward pack, data-gradient pack or None)} for every convolution of the nn.Sequentials `seqs` that
-    runs on the package's kernels (forward arithmetic; data gradient when one will be asked for).  The packs are QUEUED
-    (rfn_hip.ops.pack_weight): asked for up front, all of a network's leave in one launch before its first convolution."""
+    runs on the package's kernels (forward arithmetic; data gradient when one will be asked for).  Asked for up front:
+    all of a network's packs leave in one launch (rfn_hip.ops.PackBatch)."""
     packs = {}
     if x.is_cuda and x.dtype == torch.float32 and K.CONV_PRECISION != "f32" and K.bwd_b3():
-        for seq in seqs:
-            for m in seq:
-                if _own_conv(m, x) and not K.fewcin_ok(x, None, m.weight, 0):
-                    packs[m] = (K.pack_weight(m.weight, prec="bf16x6"),
-                                K.pack_weight(m.weight, flip=True) if torch.is_grad_enabled() else None)
+        with K.PackBatch() as pb:
+            for seq in seqs:
+                for m in seq:
+                    if _own_conv(m, x) and not K.fewcin_ok(x, None, m.weight, 0):
+                        packs[m] = (pb.conv(m.weight, prec="bf16x6"),
+                                    pb.conv(m.weight, flip=True) if torch.is_grad_enabled() else None)
     return packs
 
 
@@ -524,7 +525,8 @@ def recurrent_pair(net0, net1):
 
     def run(x0, x1):
         H, W = int(x0.shape[2]), int(x0.shape[3])
-        k0, k1 = f0.dense_packs(x0), f1.dense_packs(x1)
+        with K.PackBatch() as pb:
+            k0, k1 = f0.dense_packs(x0, pb), f1.dense_packs(x1, pb)
         if k0 is None or k1 is None or tuple(x1.shape[2:]) != (H, W) or x0.shape[0] != x1.shape[0]:
             return f0(x0), f1(x1)
         for i in range(len(p0)):
@@ -627,15 +629,16 @@ class SimpleParamNet(nn.Module):
         ws_p, _ = _WeightPort.apply(ws, None, st_s)
         wr_p, b_p = _WeightPort.apply(wr, c0.bias, st_r)
         ports = [(wr_p, b_p, st_r, convs[0][1])]
-        packs = [(K.smallmap_pack(wr, H, W, False), K.smallmap_pack(wr, H, W, True))]
-        for c, slope in convs[1:]:
-            st = _StepStash()
-            w, b = _WeightPort.apply(c.weight, c.bias, st)
-            ports.append((w, b, st, slope))
-            packs.append((K.smallmap_pack(c.weight, H, W, False), K.smallmap_pack(c.weight, H, W, True)))
+        with K.PackBatch() as pb:
+            packs = [(pb.dense(wr, H, W, False), pb.dense(wr, H, W, True))]
+            for c, slope in convs[1:]:
+                st = _StepStash()
+                w, b = _WeightPort.apply(c.weight, c.bias, st)
+                ports.append((w, b, st, slope))
+                packs.append((pb.dense(c.weight, H, W, False), pb.dense(c.weight, H, W, True)))
+            ws_packs = (pb.dense(ws, H, W, False), pb.dense(ws, H, W, True))
         # all steps' static projection in one product (no bias, no activation: both belong to the per-step launch)
-        proj = _StepDenseAct.apply(static_all, ws_p, None, st_s, None,
-                                   (K.smallmap_pack(ws, H, W, False), K.smallmap_pack(ws, H, W, True)))
+        proj = _StepDenseAct.apply(static_all, ws_p, None, st_s, None, ws_packs)
         return SimpleNamespace(ports=ports, packs=packs, proj=proj.view(steps, B, *proj.shape[1:]).unbind(0))
 
     def recurrent(self, force=False):
@@ -653,14 +656,16 @@ class SimpleParamNet(nn.Module):
 
         packs = {}
 
-        def dense_packs(x):
-            """packed (forward, data-gradient) matrices of every layer for x's map size, or None (dense path unusable)"""
+        def dense_packs(x, pb=None):
+            """packed (forward, data-gradient) matrices of every layer for x's map size, or None (dense path unusable);
+            `pb`: the caller's PackBatch (they are filled when it is left), else they are filled on return"""
             H, W = int(x.shape[2]), int(x.shape[3])
             if not (x.is_cuda and all(K.smallmap_supported(c, H, W) for c, _ in convs)):
                 return None
             if (H, W) not in packs:  # once per loss evaluation: both products of every layer
-                packs[(H, W)] = [(K.smallmap_pack(c.weight, H, W, False), K.smallmap_pack(c.weight, H, W, True))
-                                 for c, _ in convs]
+                with K.PackBatch() as own:
+                    b = pb if pb is not None else own
+                    packs[(H, W)] = [(b.dense(c.weight, H, W, False), b.dense(c.weight, H, W, True)) for c, _ in convs]
             return packs[(H, W)]
 
         def run(x):

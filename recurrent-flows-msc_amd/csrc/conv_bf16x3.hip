@@ -22,42 +22,6 @@ static inline void packed_dims_b3(int Cout_l, int Cin_l, int* CoutP, int* Cin16)
     *Cin16 = (Cin_l + 15) / 16;
 }
 
-// packed unit (16 bytes = 8 bf16) index: (((c16*T + tap)*2 + plane)*2 + g)*CoutP + co ; element j <-> cin = c16*16+g*8+j
-// NPL = 2: (hi, lo) -- bf16x3;  NPL = 3: (hi, mid, lo), 24 significant bits -- "bf16x6" (six products per fp32 product)
-__global__ void pack_weight_b3_kernel(const float* __restrict__ w, bf16x8* __restrict__ wpk, int Cout, int Cin, int KS,
-                                      int CoutP, int Cin16, int transpose_flip, int NPL) {
-    const int T = KS * KS;
-    const int Co_l = transpose_flip ? Cin : Cout;
-    const int Ci_l = transpose_flip ? Cout : Cin;
-    const long total = (long)Cin16 * T * 2 * CoutP;  // (hi, lo) pairs of units
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int co = (int)(idx % CoutP);
-        long r = idx / CoutP;
-        const int g = (int)(r & 1);
-        r >>= 1;
-        const int tap = (int)(r % T);
-        const int c16 = (int)(r / T);
-        bf16x8 hi, lo, l3;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int ci = c16 * 16 + g * 8 + j;
-            float v = 0.f;
-            if (co < Co_l && ci < Ci_l)
-                v = transpose_flip ? w[((long)ci * Cin + co) * T + (T - 1 - tap)] : w[((long)co * Cin + ci) * T + tap];
-            const __bf16 h = (__bf16)v;
-            const float r1 = v - (float)h;
-            const __bf16 m = (__bf16)r1;
-            hi[j] = h;
-            lo[j] = m;
-            l3[j] = (__bf16)(r1 - (float)m);
-        }
-        const long base = ((long)(c16 * T + tap) * NPL) * 2 * CoutP;
-        wpk[base + (long)(0 * 2 + g) * CoutP + co] = hi;
-        wpk[base + (long)(1 * 2 + g) * CoutP + co] = lo;
-        if (NPL == 3) wpk[base + (long)(2 * 2 + g) * CoutP + co] = l3;
-    }
-}
-
 extern "C" long rfn_packed_weight_size_bf16x3(int Cout, int Cin, int ks) {
     // in FLOATS (4 bytes), large enough for both orientations
     int a, b, c, d;
@@ -70,48 +34,21 @@ extern "C" long rfn_packed_weight_size_bf16x6(int Cout, int Cin, int ks) {
     return rfn_packed_weight_size_bf16x3(Cout, Cin, ks) / 2 * 3;  // three planes instead of two
 }
 
-static int pack_conv_weight_planes(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip, int NPL,
-                                   rfn_stream_t stream);
-extern "C" int rfn_pack_conv_weight_bf16x3(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip,
-                                           rfn_stream_t stream) {
-    return pack_conv_weight_planes(w, wpk, Cout, Cin, ks, transpose_flip, 2, stream);
-}
-extern "C" int rfn_pack_conv_weight_bf16x6(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip,
-                                           rfn_stream_t stream) {
-    return pack_conv_weight_planes(w, wpk, Cout, Cin, ks, transpose_flip, 3, stream);
-}
-static int pack_conv_weight_planes(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip, int NPL,
-                                   rfn_stream_t stream) {
-    RFN_CHECK_ARG(w && wpk && Cout > 0 && Cin > 0 && (ks == 1 || ks == 3), -1);
-    RFN_CHECK_ARG(((uintptr_t)wpk & 15) == 0, -2);
-    int CoutP, Cin16;
-    if (!transpose_flip)
-        packed_dims_b3(Cout, Cin, &CoutP, &Cin16);
-    else
-        packed_dims_b3(Cin, Cout, &CoutP, &Cin16);
-    long total = (long)Cin16 * ks * ks * 2 * CoutP;
-    int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(pack_weight_b3_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<bf16x8*>(wpk), Cout, Cin, ks, CoutP, Cin16, transpose_flip, NPL);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- all weights of a model in ONE launch: descriptor table in device memory, blockIdx.y = descriptor.
-// mode 0: forward conv, 1: data-gradient conv (transposed + mirrored taps), 2: tap-expanded 1x1 form of a 3x3 conv with
-// tiny Cout (logical weight w'[tap*Cout + co][ci] = w[co][ci][tap], see rfn_tap_gather_f32).
+// ---- the weight pack: up to PACK_TABLE_MAX weights per launch, the descriptors by value in the kernel arguments,
+// blockIdx.y = descriptor.  mode 0: forward conv, 1: data-gradient conv (transposed + mirrored taps), 2: tap-expanded 1x1
+// form of a 3x3 conv with tiny Cout (logical weight w'[tap*Cout + co][ci] = w[co][ci][tap], see rfn_tap_gather_f32);
+// mode + 4: NPL = 3 planes.
+// packed unit (16 bytes = 8 bf16) index: (((c16*T + tap)*NPL + plane)*2 + g)*CoutP + co ; element j <-> cin = c16*16+g*8+j
+// NPL = 2: (hi, lo) -- bf16x3;  NPL = 3: (hi, mid, lo), 24 significant bits -- "bf16x6" (six products per fp32 product)
 struct PackDesc {  // mirrors rfn_pack_desc in include/rfn_hip.h
     const float* w;
     float* wpk;
     int Cout, Cin, ks, mode;
 };
-__device__ __forceinline__ void pack_weights_one(const PackDesc d);
-__global__ void pack_weights_batched_b3_kernel(const PackDesc* __restrict__ descs) { pack_weights_one(descs[blockIdx.y]); }
-// the same with the descriptors by value in the kernel arguments (packs queued by the host between two launches)
 #define PACK_TABLE_MAX 64
 struct PackTable { PackDesc d[PACK_TABLE_MAX]; };
-__global__ void pack_weights_table_b3_kernel(const PackTable t) { pack_weights_one(t.d[blockIdx.y]); }
-__device__ __forceinline__ void pack_weights_one(const PackDesc d) {
+__global__ void pack_weights_table_b3_kernel(const PackTable t) {
+    const PackDesc d = t.d[blockIdx.y];
     const int T_src = d.ks * d.ks;
     const int NPL = (d.mode & 4) ? 3 : 2, mode = d.mode & 3;  // (mode + 4: three planes = bf16x6)
     int Co_l, Ci_l, T;
@@ -154,14 +91,6 @@ __device__ __forceinline__ void pack_weights_one(const PackDesc d) {
         if (NPL == 3) wpk[base + (long)(2 * 2 + g) * CoutP + co] = l3;
     }
 }
-extern "C" int rfn_pack_conv_weights_batched_bf16x3(const void* descs_device, int n, rfn_stream_t stream) {
-    RFN_CHECK_ARG(descs_device && n >= 0, -1);
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(pack_weights_batched_b3_kernel, dim3(96, n), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const PackDesc*>(descs_device));
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
 /* n descriptors in HOST memory: ceil(n / 64) launches, the table travels in the kernel arguments */
 extern "C" int rfn_pack_conv_weights_hostdescs_bf16x3(const void* descs_host, int n, rfn_stream_t stream) {
     RFN_CHECK_ARG(descs_host && n >= 0, -1);
@@ -189,6 +118,17 @@ extern "C" int rfn_pack_conv_weights_hostdescs_bf16x3(const void* descs_host, in
     }
     RFN_LAUNCH_CHECK();
     return 0;
+}
+// one weight: a one-descriptor table
+extern "C" int rfn_pack_conv_weight_bf16x3(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip,
+                                           rfn_stream_t stream) {
+    const PackDesc d = {w, wpk, Cout, Cin, ks, transpose_flip ? 1 : 0};
+    return rfn_pack_conv_weights_hostdescs_bf16x3(&d, 1, stream);
+}
+extern "C" int rfn_pack_conv_weight_bf16x6(const float* w, float* wpk, int Cout, int Cin, int ks, int transpose_flip,
+                                           rfn_stream_t stream) {
+    const PackDesc d = {w, wpk, Cout, Cin, ks, (transpose_flip ? 1 : 0) + 4};
+    return rfn_pack_conv_weights_hostdescs_bf16x3(&d, 1, stream);
 }
 
 // NPL = 2: two bf16 pieces per operand, three products (bf16x3); NPL = 3: three pieces, six products ("bf16x6", 24
@@ -620,7 +560,7 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p, con
     const long total = (long)p.N * HW;
     const int co_base = blockIdx.y * 256 + wave * 32;
 
-    // weights -> registers (packed unit index ((s*2 + plane)*2 + kk)*CoutP + co, see pack_weight_b3_kernel)
+    // weights -> registers (packed unit index ((s*2 + plane)*2 + kk)*CoutP + co, see pack_weights_table_b3_kernel)
     bf16x8 wh[NSTEPS], wl[NSTEPS];
     {
         const bf16x8* wp = reinterpret_cast<const bf16x8*>(p.wpk) + co_base + l31;

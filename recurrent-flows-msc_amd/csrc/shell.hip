@@ -13,7 +13,7 @@ void rfn_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* rfn_last_error(void) { return g_err; }
-extern "C" int rfn_abi_version(void) { return 1; }
+extern "C" int rfn_abi_version(void) { return 2; }
 
 #include <map>
 #include <mutex>

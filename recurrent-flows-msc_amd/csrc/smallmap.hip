@@ -17,48 +17,9 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------ packing
 // packed[((tile*KS + ks)*2 + plane)*64 + lane] (16-byte units): lane -> n = tile*32 + lane%32, k = ks*16 + (lane/32)*8 + j
 // transpose = 0: k = (ci,pi), n = (co,po)   (forward)        transpose = 1: k = (co,po), n = (ci,pi)   (data gradient)
-__device__ __forceinline__ void smallmap_pack_item(const float* __restrict__ w, const int Cout, const int Cin, const int H,
-                                                   const int W, const int transpose, bf16x8* __restrict__ packed,
-                                                   const int KS, const long idx);
-__global__ void smallmap_pack_kernel(const float* __restrict__ w, int Cout, int Cin, int H, int W, int transpose,
-                                     bf16x8* __restrict__ packed, int KS, int NTILES) {
-    const long total = (long)NTILES * KS * 64;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x)
-        smallmap_pack_item(w, Cout, Cin, H, W, transpose, packed, KS, idx);
-}
-
-// one fragment pair (hi, lo) of a packed matrix: the body of both pack kernels
-__device__ __forceinline__ void smallmap_pack_item(const float* __restrict__ w, const int Cout, const int Cin, const int H,
-                                                   const int W, const int transpose, bf16x8* __restrict__ packed,
-                                                   const int KS, const long idx) {
-    const int HW = H * W;
-    const int lane = (int)(idx & 63);
-    const long r = idx >> 6;
-    const int ks = (int)(r % KS), tile = (int)(r / KS);
-    const int n = tile * 32 + (lane & 31);
-    const int kbase = ks * 16 + (lane >> 5) * 8;
-    bf16x8 hi, lo;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int k = kbase + j;
-        const int cn = n / HW, pn = n - cn * HW, ck = k / HW, pk = k - ck * HW;
-        const int co = transpose ? ck : cn, po = transpose ? pk : pn;
-        const int ci = transpose ? cn : ck, pi = transpose ? pn : pk;
-        const int dy = pi / W - po / W + 1, dx = pi % W - po % W + 1;
-        float v = 0.f;
-        if (co < Cout && ci < Cin && dy >= 0 && dy < 3 && dx >= 0 && dx < 3)
-            v = w[((long)co * Cin + ci) * 9 + dy * 3 + dx];
-        const __bf16 h = (__bf16)v;
-        hi[j] = h;
-        lo[j] = (__bf16)(v - (float)h);
-    }
-    packed[(r * 2 + 0) * 64 + lane] = hi;
-    packed[(r * 2 + 1) * 64 + lane] = lo;
-}
-
 // Up to SM_PACK_MAX matrices in ONE launch (the weights change every optimizer step: the latent nets, the ConvLSTM and the
-// 2x2 flow level re-pack ~60 matrices per step, each a ~10 us launch of its own until round 3).  The descriptors travel
-// by value in the kernel arguments; block (x, y) works on matrix y.
+// 2x2 flow level re-pack ~60 matrices per step).  The descriptors travel by value in the kernel arguments; block (x, y)
+// works on matrix y, one fragment pair (hi, lo) per index.
 #define SM_PACK_MAX 64
 struct SmallmapPackDesc {   // mirrors rfn_smallmap_pack_desc in include/rfn_hip.h
     const float* w;
@@ -68,11 +29,34 @@ struct SmallmapPackDesc {   // mirrors rfn_smallmap_pack_desc in include/rfn_hip
 struct SmallmapPackTable { SmallmapPackDesc d[SM_PACK_MAX]; };
 __global__ __launch_bounds__(256) void smallmap_pack_batched_kernel(const SmallmapPackTable t) {
     const SmallmapPackDesc d = t.d[blockIdx.y];
-    const int HW = d.H * d.W;
-    const int KS = ((d.transpose ? d.Cout : d.Cin) * HW + 15) / 16, NT = ((d.transpose ? d.Cin : d.Cout) * HW + 31) / 32;
+    const int HW = d.H * d.W, W = d.W, transpose = d.transpose;
+    const int KS = ((transpose ? d.Cout : d.Cin) * HW + 15) / 16, NT = ((transpose ? d.Cin : d.Cout) * HW + 31) / 32;
+    bf16x8* packed = reinterpret_cast<bf16x8*>(d.packed);
     const long total = (long)NT * KS * 64;
-    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256)
-        smallmap_pack_item(d.w, d.Cout, d.Cin, d.H, d.W, d.transpose, reinterpret_cast<bf16x8*>(d.packed), KS, idx);
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int lane = (int)(idx & 63);
+        const long r = idx >> 6;
+        const int ks = (int)(r % KS), tile = (int)(r / KS);
+        const int n = tile * 32 + (lane & 31);
+        const int kbase = ks * 16 + (lane >> 5) * 8;
+        bf16x8 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = kbase + j;
+            const int cn = n / HW, pn = n - cn * HW, ck = k / HW, pk = k - ck * HW;
+            const int co = transpose ? ck : cn, po = transpose ? pk : pn;
+            const int ci = transpose ? cn : ck, pi = transpose ? pn : pk;
+            const int dy = pi / W - po / W + 1, dx = pi % W - po % W + 1;
+            float v = 0.f;
+            if (co < d.Cout && ci < d.Cin && dy >= 0 && dy < 3 && dx >= 0 && dx < 3)
+                v = d.w[((long)co * d.Cin + ci) * 9 + dy * 3 + dx];
+            const __bf16 h = (__bf16)v;
+            hi[j] = h;
+            lo[j] = (__bf16)(v - (float)h);
+        }
+        packed[(r * 2 + 0) * 64 + lane] = hi;
+        packed[(r * 2 + 1) * 64 + lane] = lo;
+    }
 }
 
 static void smallmap_dims(int Cout, int Cin, int HW, int transpose, int* K, int* N, int* KS, int* NTILES) {
@@ -86,20 +70,6 @@ extern "C" long rfn_smallmap_packed_size(int Cout, int Cin, int H, int W, int tr
     int K, N, KS, NT;
     smallmap_dims(Cout, Cin, H * W, transpose, &K, &N, &KS, &NT);
     return (long)NT * KS * 2 * 64 * 16;
-}
-
-extern "C" int rfn_smallmap_pack_bf16x3(const float* w, int Cout, int Cin, int H, int W, int transpose, float* packed,
-                                        rfn_stream_t stream) {
-    RFN_CHECK_ARG(w && packed && Cout > 0 && Cin > 0 && H > 0 && W > 0 && H * W <= 16, -1);
-    RFN_CHECK_ARG(((uintptr_t)packed & 15) == 0, -2);
-    int K, N, KS, NT;
-    smallmap_dims(Cout, Cin, H * W, transpose, &K, &N, &KS, &NT);
-    const long total = (long)NT * KS * 64;
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(smallmap_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin, H, W, transpose,
-                       reinterpret_cast<bf16x8*>(packed), KS, NT);
-    RFN_LAUNCH_CHECK();
-    return 0;
 }
 
 /* n matrices (host array of descriptors) in ceil(n / 64) launches */
@@ -127,6 +97,12 @@ extern "C" int rfn_smallmap_pack_batched_bf16x3(const void* descs_host, int n, r
     }
     RFN_LAUNCH_CHECK();
     return 0;
+}
+// one matrix: a one-descriptor table
+extern "C" int rfn_smallmap_pack_bf16x3(const float* w, int Cout, int Cin, int H, int W, int transpose, float* packed,
+                                        rfn_stream_t stream) {
+    const SmallmapPackDesc d = {w, packed, Cout, Cin, H, W, transpose ? 1 : 0, 0};
+    return rfn_smallmap_pack_batched_bf16x3(&d, 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ dense product

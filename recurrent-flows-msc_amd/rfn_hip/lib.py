@@ -42,7 +42,6 @@ SIGNATURES = {
     "rfn_conv2d_dgrad_act_rows_bf16x3": [_c_i, _c_i, _c_i, _c_i, _c_i, _c_i],
     "rfn_conv2d_dgrad_act_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_i, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i,
                                     _c_i, _c_i, _c_s],
-    "rfn_pack_conv_weights_batched_bf16x3": [_c_f, _c_i, _c_s],
     "rfn_gather_affine_f32": [_c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i,
                               _c_i, _c_s],
     "rfn_affine_zeros_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f,
@@ -134,6 +133,8 @@ _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_stepbn_scratch_floats": cty
              "rfn_coupling_po_packed_bytes": ctypes.c_long, "rfn_coupling_po_mask_floats": ctypes.c_long, "rfn_glow_shell_fwd_ld_floats": ctypes.c_long,
              "rfn_coupling_po_bwd_packed_bytes": ctypes.c_long, "rfn_coupling_po_bwd_part_floats": ctypes.c_long}
 
+ABI_VERSION = 2  # rfn_abi_version() of the library this binding matches (include/rfn_hip.h)
+
 _lib = None
 
 
@@ -147,6 +148,10 @@ def load():
             "librfn_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C recurrent-flows-msc_amd/csrc`. There is no fallback path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
+    lib.rfn_abi_version.restype = ctypes.c_int
+    if lib.rfn_abi_version() != ABI_VERSION:
+        raise RuntimeError("%s has ABI version %d, this package needs %d: rebuild the library (`make -C "
+                           "recurrent-flows-msc_amd/csrc`)" % (LIB_PATH, lib.rfn_abi_version(), ABI_VERSION))
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
@@ -160,17 +165,8 @@ def load():
 PROFILE = None
 
 
-# work queued by rfn_hip.ops that must be launched before the next kernel (weight packs collected into one launch): a
-# callable, run -- once -- at the top of the next call()
-PENDING_FLUSH = None
-
-
 def call(name, *args, meta=None):
     """Invoke an int-returning entry point on the current torch stream; raise on a non-zero code."""
-    global PENDING_FLUSH
-    if PENDING_FLUSH is not None:
-        flush, PENDING_FLUSH = PENDING_FLUSH, None
-        flush()
     lib = load()
     cur = torch.cuda.current_stream()
     stream = ctypes.c_void_p(cur.cuda_stream)

@@ -4,6 +4,7 @@ Everything here runs on the GPU through librfn_hip.so; torch is used for memory,
 Frame-batched layout: tensors are [N, C, H, W] fp32 where N = all frames handed over by the caller (the RFN driver
 time-batches B*(T-1) frames into one call).
 """
+import collections
 import ctypes
 
 import torch
@@ -144,41 +145,67 @@ class _ConvPackDesc(ctypes.Structure):   # rfn_pack_desc (include/rfn_hip.h)
                 ("ks", ctypes.c_int), ("mode", ctypes.c_int)]
 
 
-# split-precision conv-weight packs asked for but not launched yet; they leave in ONE launch
-# (rfn_pack_conv_weights_hostdescs_bf16x3) before the next kernel of the library (rfn_hip.lib.PENDING_FLUSH)
-_CONV_PACK_QUEUE = []
+class _SmallmapPackDesc(ctypes.Structure):   # rfn_smallmap_pack_desc (include/rfn_hip.h)
+    _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("transpose", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
+class PackBatch:
+    """The weight packs one piece of code asks for back to back, launched together (weights change every optimizer
+    step: they are re-packed per call).  conv() / dense() return the buffers; leaving the `with` block fills them with at
+    most one rfn_pack_conv_weights_hostdescs_bf16x3 and one rfn_smallmap_pack_batched_bf16x3 call, on the stream
+    current then.  No buffer may be read before the block is left."""
+
+    def __init__(self):
+        self._conv, self._dense, self._keep = [], [], []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            if self._conv:
+                arr = (_ConvPackDesc * len(self._conv))(*self._conv)
+                L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(arr)))
+            if self._dense:
+                arr = (_SmallmapPackDesc * len(self._dense))(*self._dense)
+                L.call("rfn_smallmap_pack_batched_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(arr)))
+        self._conv, self._dense, self._keep = [], [], []   # (the contiguous weights were held until the launch)
+
+    def conv(self, w, flip=False, prec=None):
+        """w [Cout,Cin,k,k] in the layout of the MFMA conv kernels (flip=True: data-gradient conv).  prec: 'bf16x3' |
+        'bf16x6' | 'f32' (default: the gradient arithmetic, which is what un-annotated callers are); the f32 pack is
+        launched at once."""
+        Cout, Cin, ks = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        prec = prec if prec is not None else ("bf16x3" if bwd_b3() else "f32")
+        sfx = {"bf16x3": "_bf16x3", "bf16x6": "_bf16x6", "f32": ""}[prec]
+        wpk = torch.empty(getattr(L.load(), "rfn_packed_weight_size" + sfx)(Cout, Cin, ks), device=w.device,
+                          dtype=torch.float32)
+        wc = w.detach().contiguous()
+        if prec == "f32":
+            L.call("rfn_pack_conv_weight_f32", L.dev(wc, "w"), L.dev(wpk), _i(Cout), _i(Cin), _i(ks), _i(1 if flip else 0))
+            return wpk
+        self._conv.append(_ConvPackDesc(L.dev(wc, "w").value, wpk.data_ptr(), Cout, Cin, ks,
+                                        (1 if flip else 0) + (4 if prec == "bf16x6" else 0)))
+        self._keep += [wc, wpk]
+        return wpk
+
+    def dense(self, w, H, W, transpose):
+        """w [Cout, Cin, 3, 3] -> MFMA-fragment-ordered bf16 (hi, lo) dense matrix of the H x W map (smallmap_dense)"""
+        Cout, Cin = int(w.shape[0]), int(w.shape[1])
+        nbytes = int(L.load().rfn_smallmap_packed_size(Cout, Cin, H, W, 1 if transpose else 0))
+        buf = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
+        wc = w.detach().contiguous()
+        self._dense.append(_SmallmapPackDesc(L.dev(wc, "w").value, buf.data_ptr(), Cout, Cin, int(H), int(W),
+                                             1 if transpose else 0, 0))
+        self._keep += [wc, buf]
+        return buf
 
 
 def pack_weight(w, flip=False, prec=None):
-    """Pack a torch-layout conv weight [Cout,Cin,k,k] for the MFMA conv kernel (flip=True: data-gradient conv).
-    Done per call (weights change every optimizer step).  The split-precision packs are QUEUED: the buffer is returned at
-    once, its contents exist when the next kernel of the library is launched (every pack queued until then shares one
-    launch: a module that knows its convolutions up front -- the extractor / upscaler -- asks for all of them first).
-    prec: 'bf16x3' | 'bf16x6' | 'f32' (default: the gradient arithmetic, which is what un-annotated callers are)."""
-    Cout, Cin, ks = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
-    prec = prec if prec is not None else ("bf16x3" if bwd_b3() else "f32")
-    sfx = {"bf16x3": "_bf16x3", "bf16x6": "_bf16x6", "f32": ""}[prec]
-    size = getattr(L.load(), "rfn_packed_weight_size" + sfx)(Cout, Cin, ks)
-    wpk = torch.empty(size, device=w.device, dtype=torch.float32)
-    wc = w.detach().contiguous()
-    if prec == "f32":
-        L.call("rfn_pack_conv_weight_f32", L.dev(wc, "w"), L.dev(wpk), _i(Cout), _i(Cin), _i(ks), _i(1 if flip else 0))
-        return wpk
-    L.dev(wc, "w")
-    _CONV_PACK_QUEUE.append(((wc.data_ptr(), wpk.data_ptr(), Cout, Cin, ks, (1 if flip else 0) + (4 if prec == "bf16x6" else 0)),
-                             wc, wpk))
-    L.PENDING_FLUSH = flush_packs
-    return wpk
-
-
-def flush_packs():
-    """launch every queued weight pack (conv packs and small-map dense packs), one launch per kind and 64 matrices"""
-    if _CONV_PACK_QUEUE:
-        q = list(_CONV_PACK_QUEUE)
-        del _CONV_PACK_QUEUE[:]
-        arr = (_ConvPackDesc * len(q))(*[_ConvPackDesc(*f) for f, _, _ in q])
-        L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(q)))
-    smallmap_pack_flush()
+    """PackBatch.conv of one weight: the buffer is filled when the call returns."""
+    with PackBatch() as b:
+        return b.conv(w, flip, prec)
 
 
 def conv2d_dgrad_act(gin, wpk_flip, y, logs, act, Cout, ks, arena=None):
@@ -200,35 +227,31 @@ def conv2d_dgrad_act(gin, wpk_flip, y, logs, act, Cout, ks, arena=None):
 
 
 class PackPlan:
-    """Persistent packed-weight buffers for a list of (weight, mode) and ONE launch that refreshes all of them
-    (rfn_pack_conv_weights_batched_bf16x3).  mode: 0 forward, 1 data-gradient, 2 tap-expanded 1x1 (tiny-Cout 3x3);
-    + 4: three planes per operand (bf16x6)."""
+    """Persistent packed-weight buffers for a list of (weight, mode) and the descriptors that refresh all of them
+    (rfn_pack_conv_weights_hostdescs_bf16x3, 64 per launch).  mode: 0 forward, 1 data-gradient, 2 tap-expanded 1x1
+    (tiny-Cout 3x3); + 4: three planes per operand (bf16x6)."""
 
     def __init__(self, items):
-        import numpy as np
         self.items = list(items)
         self.ptrs = [w.data_ptr() for w, _ in self.items]
-        dev = self.items[0][0].device
         lib = L.load()
         self.bufs = []
-        rec = np.zeros(len(self.items), dtype=np.dtype([("w", "<u8"), ("wpk", "<u8"), ("Cout", "<i4"), ("Cin", "<i4"),
-                                                          ("ks", "<i4"), ("mode", "<i4")]))
-        for i, (w, mode) in enumerate(self.items):
+        for w, mode in self.items:
             Cout, Cin, ks = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
             assert w.is_contiguous() and w.dtype == torch.float32
             lc, lk = (9 * Cout, 1) if (mode & 3) == 2 else (Cout, ks)
             size_fn = lib.rfn_packed_weight_size_bf16x6 if (mode & 4) else lib.rfn_packed_weight_size_bf16x3
-            buf = torch.empty(size_fn(lc, Cin, lk), device=dev, dtype=torch.float32)
-            self.bufs.append(buf)
-            rec[i] = (w.data_ptr(), buf.data_ptr(), Cout, Cin, ks, mode)
-        self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+            self.bufs.append(torch.empty(size_fn(lc, Cin, lk), device=w.device, dtype=torch.float32))
+        self.descs = (_ConvPackDesc * len(self.items))(*[
+            _ConvPackDesc(w.data_ptr(), b.data_ptr(), int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), mode)
+            for (w, mode), b in zip(self.items, self.bufs)])
 
     def valid_for(self, items):
         return (len(items) == len(self.items) and all(w.data_ptr() == p for (w, _), p in zip(items, self.ptrs))
                 and all(m == m0 for (_, m), (_, m0) in zip(items, self.items)))
 
     def run(self):
-        L.call("rfn_pack_conv_weights_batched_bf16x3", L._c_f(self.table.data_ptr()), _i(len(self.items)))
+        L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(self.descs, ctypes.c_void_p), _i(len(self.descs)))
 
 
 # ------------------------------------------------------------------------------------------------ fused coupling net
@@ -759,7 +782,7 @@ class ConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, in1, in2, w, p0, p1, ep_mode, act, prec=None, packs=None):
-        # packs: (forward pack, data-gradient pack or None) queued by the caller (run_time_batched), else packed here
+        # packs: (forward pack, data-gradient pack or None) from the caller's PackBatch (run_time_batched), else packed here
         Cout, ks = int(w.shape[0]), int(w.shape[2])
         ctx.pk_b = None if packs is None else packs[1]
         p0f = None if p0 is None else p0.detach().reshape(-1).contiguous()
@@ -806,7 +829,7 @@ class ConvFn(torch.autograd.Function):
 
 def conv_ep(in1, in2, w, p0, p1, ep_mode, act, prec=None, packs=None):
     """`prec` (optional): forward arithmetic ('bf16x3' | 'bf16x6' | 'f32') instead of this map size's default;
-    `packs` (optional): (forward pack in that arithmetic, data-gradient pack or None) already queued by the caller"""
+    `packs` (optional): (forward pack in that arithmetic, data-gradient pack or None) already packed by the caller"""
     return ConvFn.apply(in1, in2, w, p0, p1, ep_mode, act, prec, packs)
 
 
@@ -814,9 +837,13 @@ def _f(t):
     return None if t is None else t.detach().reshape(-1).contiguous()
 
 
-# per-step pack tuple handed to the coupling nets: [0..5] split-precision conv packs (w1 f, w1 d, w2 f, w2 d, w3 f, w3 d),
-# [6] / [7] fused forward / backward streams, [8] / [9] / [10] dense small-map packs (w1 forward, w3 forward, w1 data gradient)
-PACK_SLOTS = 11
+# the packed weights of one Glow step's coupling net, kept fresh by the caller (Flow/glow.py ListGlow._packed_weights);
+# a field left None is packed where it is needed.  *_fwd / *_dgrad: split-precision conv packs of the forward (in the
+# map's forward arithmetic) / data-gradient convolutions; po_fwd / po_bwd: the fused kernels' weight streams
+# (POPackPlan); *_dense_*: dense small-map packs (smallmap_conv).
+StepPacks = collections.namedtuple("StepPacks", ["w1_fwd", "w1_dgrad", "w2_fwd", "w2_dgrad", "w3_fwd", "w3_dgrad",
+                                                 "po_fwd", "po_bwd", "w1_dense_fwd", "w3_dense_fwd", "w1_dense_dgrad"],
+                                   defaults=(None,) * 11)
 
 
 def dgrad_small_ok(N, Cin, Cout, H, W, ks):
@@ -845,7 +872,7 @@ def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk, want_mask
     """coupling network of one Glow step (glow_modules.py:232-238) on z's first channel half and `cond`.
     Returns (h1, h2, o, P, masks): either o (finished Conv2dZeros output) or P (its tap-expanded pre-gather form, fused
     forward kernel) is None; masks: the fused kernel's activation masks for the fused backward kernel (or None).
-    `pk`: the step's 8 pack-plan entries (see GlowStepFn.forward)."""
+    `pk`: the step's StepPacks."""
     N, C, H, W = z.shape
     Ch = C // 2
     Hd = int(w1.shape[0])
@@ -856,12 +883,12 @@ def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk, want_mask
     fp = fwd_prec(H, W)
     if coupling_po_ok(N, C, Cc_, Hd, H, W, w1, w3) and int(w2.shape[2]) == 1:
         # shallow levels: the whole coupling net in one kernel (csrc/coupling_po.hip), h1 / h2 written once
-        po = pk[6]
+        po = pk.po_fwd
         if po is None:
             plan = POPackPlan([(w1.detach(), w2.detach(), w3.detach())])
             plan.run()
             po = plan.bufs[0]
-        want = want_masks and pk[7] is not None and coupling_po_bwd_ok(N, C, H, W)
+        want = want_masks and pk.po_bwd is not None and coupling_po_bwd_ok(N, C, H, W)
         h1, h2, P, masks = coupling_po_fwd(z, cin2, po, _f(n1b), _f(n1l), _f(n2b), _f(n2l), C, act, want_masks=want)
         return h1, h2, None, P, masks
     # the two deepest levels (H*W <= 16): a launch is a few thousand pixels against megabytes of weights, the
@@ -870,17 +897,18 @@ def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk, want_mask
     dense3 = k33 and smallmap_conv_ok(H, W, Hd, 0, C, N) and not zeros_conv_uses_taps(w3)
     b3fwd = fp in ("bf16x3", "bf16x6")  # the caller's pack plan holds forward packs in this map's split arithmetic
     if dense:
-        h1 = smallmap_conv(z1, cin2, pk[8] if pk[8] is not None else smallmap_pack(w1, H, W, False), Hd, 1, _f(n1b),
-                           _f(n1l), act)
+        h1 = smallmap_conv(z1, cin2, pk.w1_dense_fwd if pk.w1_dense_fwd is not None else smallmap_pack(w1, H, W, False),
+                           Hd, 1, _f(n1b), _f(n1l), act)
     else:
-        h1 = conv2d_raw(z1, cin2, pk[0] if (pk[0] is not None and b3fwd) else pack_weight(w1, prec=fp), Hd,
+        h1 = conv2d_raw(z1, cin2, pk.w1_fwd if (pk.w1_fwd is not None and b3fwd) else pack_weight(w1, prec=fp), Hd,
                         int(w1.shape[2]), 1, _f(n1b), _f(n1l), act, prec=fp)
-    h2 = conv2d_raw(h1, None, pk[2] if (pk[2] is not None and b3fwd) else pack_weight(w2, prec=fp), Hd,
+    h2 = conv2d_raw(h1, None, pk.w2_fwd if (pk.w2_fwd is not None and b3fwd) else pack_weight(w2, prec=fp), Hd,
                     int(w2.shape[2]), 1, _f(n2b), _f(n2l), act, prec=fp)
     if dense3:
-        o = smallmap_conv(h2, None, pk[9] if pk[9] is not None else smallmap_pack(w3, H, W, False), C, 2, _f(b3), _f(l3), 0)
+        o = smallmap_conv(h2, None, pk.w3_dense_fwd if pk.w3_dense_fwd is not None else smallmap_pack(w3, H, W, False), C, 2,
+                          _f(b3), _f(l3), 0)
     else:
-        o = zeros_conv_fwd(h2, w3, _f(b3), _f(l3), pk[4] if b3fwd else None, prec=fp)
+        o = zeros_conv_fwd(h2, w3, _f(b3), _f(l3), pk.w3_fwd if b3fwd else None, prec=fp)
     return h1, h2, o, None, None
 
 
@@ -890,7 +918,7 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gc
     (gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3); the data gradient of conv1 is ADDED to gz[:, :C/2] and written (acc_cond:
     added) to gcond.  With `defer` (a dict of three lists) the weight gradients are NOT computed: their operands are
     appended to defer["w1" | "w2" | "w3"] and None is returned in their place (grouped launch by the caller).
-    With `masks` (the fused forward kernel's activation masks; needs n1b, n2b and the step's backward stream pk[7]) the
+    With `masks` (the fused forward kernel's activation masks; needs n1b, n2b and the step's backward stream pk.po_bwd) the
     data-gradient chain conv3^T -> act' -> conv2^T -> act' is ONE kernel (rfn_coupling_po_bwd) that reads no
     activation; the four ActNorm gradients then come from the weight gradients (rfn_coupling_po_bwd_finish): a ticket
     is appended to `fin` (the caller runs coupling_po_bwd_finish once its weight gradients exist; ticket[2] / [5] = gw1 /
@@ -902,14 +930,15 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gc
     k1, k2, k3 = int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2])
     dfr = defer is not None and bwd_b3() and Hd % 64 == 0 and _hw(h2) % 4 == 0
     gw3 = None if dfr else zeros_conv_wgrad(h2, go, C, k3, arena)
-    fused = (pk[7] is not None and (masks is not None or act == 0) and n1b is not None and n2b is not None
+    fused = (pk.po_bwd is not None and (masks is not None or act == 0) and n1b is not None and n2b is not None
              and k2 == 1 and k1 == 3 and k3 == 3 and Hd == 256 and coupling_po_bwd_ok(N, C, H, W))
-    w3f = w2f = None
-    if not fused:
-        w3f = pk[5] if pk[5] is not None else pack_weight(w3, True)
-        w2f = pk[3] if pk[3] is not None else pack_weight(w2, True)
+    w3f, w2f = pk.w3_dgrad, pk.w2_dgrad
+    if not fused and (w3f is None or w2f is None):
+        with PackBatch() as b:
+            w3f = w3f if w3f is not None else b.conv(w3, True)
+            w2f = w2f if w2f is not None else b.conv(w2, True)
     if fused:
-        gh2, gh1, part = coupling_po_bwd(go.contiguous(), pk[7], _f(n1l), _f(n2l), masks, act)
+        gh2, gh1, part = coupling_po_bwd(go.contiguous(), pk.po_bwd, _f(n1l), _f(n2l), masks, act)
         gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
         o4 = torch.empty((4, 256), device=go.device, dtype=torch.float32)
         gn1b, gn1l, gn2b, gn2l = o4[0], o4[1], o4[2], o4[3]
@@ -941,13 +970,14 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gc
         defer["w2"].append((h1, gh2))
         defer["w1"].append((z1, cond if has_cond else None, gh1))
     if k1 == 3 and k3 == 3 and smallmap_conv_ok(H, W, Hd, 0, Ch + Cc, N, bwd=True):
-        smallmap_conv(gh1, None, pk[10] if pk[10] is not None else smallmap_pack(w1, H, W, True), Ch + Cc, 0, out1=gz[:, :Ch],
-                      out2=gcond if has_cond else None, cout_split=Ch, acc1=True, acc2=acc_cond)
+        smallmap_conv(gh1, None, pk.w1_dense_dgrad if pk.w1_dense_dgrad is not None else smallmap_pack(w1, H, W, True),
+                      Ch + Cc, 0, out1=gz[:, :Ch], out2=gcond if has_cond else None, cout_split=Ch, acc1=True,
+                      acc2=acc_cond)
     elif dgrad_small_ok(N, Hd, Ch + Cc, H, W, k1):
-        conv3x3_smallcout(gh1, pk[1] if pk[1] is not None else pack_weight(w1, True), Ch + Cc, gz[:, :Ch],
+        conv3x3_smallcout(gh1, pk.w1_dgrad if pk.w1_dgrad is not None else pack_weight(w1, True), Ch + Cc, gz[:, :Ch],
                           gcond if has_cond else None, Ch, True, acc_cond)
     else:
-        conv2d_raw(gh1, None, pk[1] if pk[1] is not None else pack_weight(w1, True), Ch + Cc, k1, 0,
+        conv2d_raw(gh1, None, pk.w1_dgrad if pk.w1_dgrad is not None else pack_weight(w1, True), Ch + Cc, k1, 0,
                    None, None, 0, out1=gz[:, :Ch], out2=gcond if has_cond else None, cout_split=Ch, acc1=True,
                    acc2=acc_cond)
     return gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3
@@ -1001,11 +1031,10 @@ class GlowStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cond, Wm, an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift,
                 act, clamp_type, packs=None):
-        """`packs` (optional): (w1 fwd, w1 dgrad, w2 fwd, w2 dgrad, w3 fwd, w3 dgrad, fused-forward stream, fused-backward stream) packed
-        buffers kept fresh by the caller's pack plans (entries may be None: packed on the fly); the forward entries are
-        bf16x3 packs and only used where that is the forward arithmetic."""
+        """`packs` (optional): the step's StepPacks (or a sequence in its field order); the forward conv packs are only
+        used where their split arithmetic is the forward arithmetic."""
         out = actnorm_invconv_fwd(x, _f(an_bias), _f(an_logs), Wm.detach())
-        pk = tuple(packs) + (None,) * (PACK_SLOTS - len(packs)) if packs is not None else (None,) * PACK_SLOTS
+        pk = StepPacks(*packs) if packs is not None else StepPacks()
         ctx.packs = pk
         h1, h2, o, P, masks = _net_fwd(out, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk,
                                        want_masks=any(ctx.needs_input_grad))
@@ -1048,7 +1077,8 @@ class GlowLevelFn(torch.autograd.Function):
     single launch each way does the shell work (rfn_glow_shell_fwd_f32: coupling tail of step k + ActNorm/InvConv head
     of step k+1; rfn_glow_shell_bwd_f32: the mirror image); the gradient wrt the shared condition map accumulates
     inside the data-gradient kernels and the per-frame log-det inside the shell kernel, so autograd adds nothing.
-    apply(x, cond, Wst[K,C,C], act, clamp_type, packs (list of K 7-tuples or None), *13K step parameters)
+    apply(x, cond, Wst[K,C,C], act, clamp_type, packs (None, or a list of K StepPacks or sequences in its field order),
+    *13K step parameters)
     -> (out, dlogdet[N] = sum over the K steps of the data dependent log-det AND of the ActNorm parameter term
     H*W * sum_c logs[c]; the InvConv term sum log|s| * H*W stays with the caller, who builds the matrices)."""
 
@@ -1058,9 +1088,7 @@ class GlowLevelFn(torch.autograd.Function):
         assert len(flat) == STEP_NPARAM * Kn
         N, C, H, W = x.shape
         prm = [flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)] for k in range(Kn)]
-        pks = [(tuple(packs[k]) + (None,) * PACK_SLOTS)[:PACK_SLOTS] if packs is not None and packs[k] is not None
-               else (None,) * PACK_SLOTS
-               for k in range(Kn)]
+        pks = [StepPacks(*packs[k]) if packs is not None and packs[k] is not None else StepPacks() for k in range(Kn)]
         want_masks = any(ctx.needs_input_grad)
         Wd = Wst.detach().contiguous()
         # log-det: every shell launch WRITES its per-block partial sums into its own slice; one reduce launch adds them
@@ -1304,45 +1332,15 @@ def smallmap_supported(conv, H, W):
             and (conv.out_channels * H * W) % 8 == 0)
 
 
-class _SmallmapPackDesc(ctypes.Structure):   # rfn_smallmap_pack_desc (include/rfn_hip.h)
-    _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
-                ("H", ctypes.c_int), ("W", ctypes.c_int), ("transpose", ctypes.c_int), ("pad_", ctypes.c_int)]
-
-
-# packs asked for but not launched yet: (descriptor fields, weight tensor kept alive).  The weights change every
-# optimizer step, so a training step re-packs ~60 matrices (latent nets, ConvLSTM, the 2x2 flow level); they are queued
-# here and go out in ONE launch (rfn_smallmap_pack_batched_bf16x3) right before the first kernel that reads any of them
-# -- every consumer (smallmap_dense / _pair / _conv) calls smallmap_pack_flush() first.
-_PACK_QUEUE = []
-
-
 def smallmap_pack(w, H, W, transpose):
-    """w [Cout, Cin, 3, 3] -> MFMA-fragment-ordered bf16 (hi, lo) dense matrix of the H x W map.  The buffer is returned
-    at once; its contents exist after smallmap_pack_flush() (called by every consumer)."""
-    Cout, Cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = int(L.load().rfn_smallmap_packed_size(Cout, Cin, H, W, 1 if transpose else 0))
-    buf = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
-    wc = w.detach().contiguous()
-    L.dev(wc, "w")
-    _PACK_QUEUE.append(((wc.data_ptr(), buf.data_ptr(), Cout, Cin, int(H), int(W), 1 if transpose else 0, 0), wc, buf))
-    L.PENDING_FLUSH = flush_packs
-    return buf
-
-
-def smallmap_pack_flush():
-    """launch the queued packs (one launch per 64 matrices)"""
-    if not _PACK_QUEUE:
-        return
-    q = list(_PACK_QUEUE)
-    del _PACK_QUEUE[:]
-    arr = (_SmallmapPackDesc * len(q))(*[_SmallmapPackDesc(*f) for f, _, _ in q])
-    L.call("rfn_smallmap_pack_batched_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(q)))
+    """PackBatch.dense of one weight: the buffer is filled when the call returns."""
+    with PackBatch() as b:
+        return b.dense(w, H, W, transpose)
 
 
 def smallmap_dense(a, packed, n_channels, bias=None, slope_out=None, y=None, slope_in=0.0, want_a_out=False, add=None):
     """out[B, n_channels, H, W] = a'[B, C, H, W] (as rows) x packed (+ bias, leaky_relu) -- rfn_smallmap_dense_bf16x3.
     With y: a' = a * (y > 0 ? 1 : slope_in); returns (out, a') when want_a_out."""
-    smallmap_pack_flush()
     a = a.contiguous()
     B, H, W = int(a.shape[0]), int(a.shape[2]), int(a.shape[3])
     K, HW = int(a.shape[1]) * H * W, H * W
@@ -1360,7 +1358,6 @@ def smallmap_dense_pair(a0, packed0, n_ch0, a1, packed1, n_ch1, bias0=None, bias
                         y0=None, y1=None, slope_in0=0.0, slope_in1=0.0, want_a_out=False, add0=None, add1=None):
     """two independent smallmap_dense products in ONE launch (rfn_smallmap_dense_pair_bf16x3): same batch and map size.
     Returns (out0, out1) or (out0, a0', out1, a1') with want_a_out.  add0 / add1: optional [B, n_ch, H, W] addends."""
-    smallmap_pack_flush()
     a0, a1 = a0.contiguous(), a1.contiguous()
     B, H, W = int(a0.shape[0]), int(a0.shape[2]), int(a0.shape[3])
     assert int(a1.shape[0]) == B and tuple(a1.shape[2:]) == (H, W)
@@ -1398,7 +1395,6 @@ def smallmap_conv_ok(H, W, C1, C2, Cout, N, bwd=False):
 def smallmap_conv(in1, in2, packed, Cout, ep_mode=0, p0=None, p1=None, act=0, out1=None, out2=None, cout_split=None,
                   acc1=False, acc2=False):
     """conv2d_raw's contract (3x3, pad 1) on an H*W <= 16 map through the dense split-precision product."""
-    smallmap_pack_flush()
     N, C1, H, W = in1.shape
     C2 = 0 if in2 is None else int(in2.shape[1])
     if cout_split is None:
@@ -1593,7 +1589,8 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         x_all, h0, c0 = x_all.contiguous(), h0.contiguous(), c0.contiguous()
         wd = w.detach()
         wx, wh = wd[:, :Cx].contiguous(), wd[:, Cx:].contiguous()
-        pk_xf, pk_hf = smallmap_pack(wx, H, W, False), smallmap_pack(wh, H, W, False)
+        with PackBatch() as pb:
+            pk_xf, pk_hf = pb.dense(wx, H, W, False), pb.dense(wh, H, W, False)
         pre = smallmap_dense(x_all.view(S * B, Cx, H, W), pk_xf, 4 * Hc, bias=None if b is None else b.detach())
         pre = pre.view(S, B, 4 * Hc, H, W)
         h_all = torch.empty((S, B, Hc, H, W), device=x_all.device, dtype=torch.float32)
@@ -1619,7 +1616,8 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         ns = Hc * HW
         wd = w.detach()
         wx, wh = wd[:, :Cx].contiguous(), wd[:, Cx:].contiguous()
-        pk_xb, pk_hb = smallmap_pack(wx, H, W, True), smallmap_pack(wh, H, W, True)
+        with PackBatch() as pb:
+            pk_xb, pk_hb = pb.dense(wx, H, W, True), pb.dense(wh, H, W, True)
         g_hall = None if g_hall is None else g_hall.contiguous()
         gcc = torch.empty_like(gates)
         gh_rec, gc = None, (None if g_cS is None else g_cS.contiguous())
@@ -1729,7 +1727,7 @@ class StepBatchNormActFn(torch.autograd.Function):
         x, mean, var, gm, bt = ctx.saved_tensors
         S, B, C, HW, eps, act, slope, affine, nscr = ctx.cfg
         if g is None:
-            return (None,) * PACK_SLOTS
+            return (None,) * 8
         g = g.contiguous()
         sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
         gx = torch.empty_like(x)

@@ -19,9 +19,9 @@
    outputs, final rounding included.  With the two third-plane products removed from the bf16x6 kernel, its e_abs rises
    to 1.4-6.1e-6 at K <= 256 and 4.7e-7 / 6.7e-7 at K = 4608 / 2304: every case fails, the large-K ones through the
    comparison with fp32 MFMA.
-2. The three routes to the weight pack kernels (direct, host-queued descriptors, device descriptor table), modes 0 / 1 /
-   2 with two and three planes, bit for bit against a CPU restatement of the layout, with nothing written past the
-   packed extent.
+2. The routes to the weight pack kernels (one-descriptor entry points, host descriptor tables, PackPlan, PackBatch),
+   modes 0 / 1 / 2 with two and three planes, and the small-map dense packs, bit for bit against CPU restatements of
+   the layouts, with nothing written past the packed extent.
 3. The arithmetic every forward convolution of the canonical SM-MNIST model actually gets under RFN_CONV_PRECISION=mixed.
 """
 import ctypes
@@ -228,7 +228,7 @@ def test_bf16x6_tap_expanded_zeros_conv_vs_fp64(K, N, Cin, C, H, W):
 
 # --------------------------------------------------------------------------------- 2. weight packs, bit for bit
 def pack_ref(w, mode, npl):
-    """CPU restatement of the split-precision weight pack (pack_weight_b3_kernel / pack_weights_one) as int16 bits.
+    """CPU restatement of the split-precision weight pack (pack_weights_table_b3_kernel) as int16 bits.
     Logical weight wl[co][ci][tap]: mode 0 = w; mode 1 (data gradient) = w transposed with mirrored taps; mode 2
     (tap-expanded 1x1) = w.permute(2,3,0,1).reshape(9*Cout, Cin).  Planes hi = bf16(v), mid = bf16(v - hi),
     lo = bf16((v - hi) - mid) (round to nearest even; the fp32 subtractions are exact); two-plane packs hold (hi, mid).
@@ -334,8 +334,8 @@ def _mode_size(lib, w, mode):
 
 @pytest.mark.parametrize("n_rep", [1, 3])
 def test_pack_hostdescs_route_bit_exact(K, n_rep):
-    """rfn_pack_conv_weights_hostdescs_bf16x3 (what flush_packs launches): every mode, two and three planes; n_rep=3
-    queues 78 descriptors, more than one 64-entry kernel-argument table"""
+    """rfn_pack_conv_weights_hostdescs_bf16x3 (what PackBatch and PackPlan launch): every mode, two and three planes;
+    n_rep=3 hands over 78 descriptors, more than one 64-entry kernel-argument table"""
     from rfn_hip import lib as L
     lib = L.load()
     items = _desc_items() * n_rep
@@ -350,35 +350,94 @@ def test_pack_hostdescs_route_bit_exact(K, n_rep):
         _check_pack(b, pack_ref(w, m & 3, 3 if m & 4 else 2), ("hostdescs", i, tuple(w.shape), m))
 
 
-def test_pack_device_table_route_bit_exact(K):
-    """PackPlan -> rfn_pack_conv_weights_batched_bf16x3 (the flow's per-step pack plan): every mode, two and three
-    planes, sentinel-filled buffers"""
-    items = [(w.cuda(), m) for w, m in _desc_items()]
-    plan = K.PackPlan(items)
-    for b in plan.bufs:
-        b.view(torch.int32).fill_(SENTINEL)
-    plan.run()
-    for (w, m), b in zip(items, plan.bufs):
-        _check_pack(b, pack_ref(w.cpu(), m & 3, 3 if m & 4 else 2), ("device table", tuple(w.shape), m))
+def test_pack_plan_bit_exact(K):
+    """PackPlan (the flow's per-step pack plan, descriptors built once, rfn_pack_conv_weights_hostdescs_bf16x3): every
+    mode, two and three planes, sentinel-filled buffers; with three repetitions the plan holds 78 descriptors, more
+    than one table"""
+    for n_rep in (1, 3):
+        items = [(w.cuda(), m) for w, m in _desc_items() * n_rep]
+        plan = K.PackPlan(items)
+        for b in plan.bufs:
+            b.view(torch.int32).fill_(SENTINEL)
+        plan.run()
+        for (w, m), b in zip(items, plan.bufs):
+            _check_pack(b, pack_ref(w.cpu(), m & 3, 3 if m & 4 else 2), ("pack plan", n_rep, tuple(w.shape), m))
 
 
-def test_pack_weight_queue_of_70_one_flush(K):
-    """70 pack_weight calls queued before ONE flush (two kernel-argument tables) land bit for bit where the returned
-    buffers say, in the orientation and plane count asked for"""
+def smallmap_pack_ref(w, H, W, transpose):
+    """CPU restatement of the small-map dense pack (smallmap_pack_batched_kernel) as int16 bits.  Dense matrix
+    M[(ci,pi)][(co,po)] = w[co][ci][tap(po, pi)] (transpose: M^T), zero-padded to KS*16 rows and NT*32 columns, split
+    into bf16 hi = bf16(v), lo = bf16(v - hi); unit index ((tile*KS + ks)*2 + plane)*64 + lane, element j <->
+    k = ks*16 + (lane/32)*8 + j, n = tile*32 + lane%32."""
+    Cout, Cin, HW = int(w.shape[0]), int(w.shape[1]), H * W
+    M = torch.zeros(Cin * HW, Cout * HW)
+    for po in range(HW):
+        for pi in range(HW):
+            dy, dx = pi // W - po // W + 1, pi % W - po % W + 1
+            if 0 <= dy < 3 and 0 <= dx < 3:
+                M[pi::HW, po::HW] = w[:, :, dy, dx].t()
+    if transpose:
+        M = M.t()
+    KS, NT = -(-M.shape[0] // 16), -(-M.shape[1] // 32)
+    P = torch.zeros(KS * 16, NT * 32)
+    P[:M.shape[0], :M.shape[1]] = M
+    hi = P.to(torch.bfloat16)
+    lo = (P - hi.float()).to(torch.bfloat16)
+    planes = [p.view(KS, 2, 8, NT, 32).permute(3, 0, 1, 4, 2) for p in (hi, lo)]   # [tile, ks, lane/32, lane%32, j]
+    return torch.stack(planes, 2).contiguous().view(torch.int16).reshape(-1)
+
+
+SMALLMAP_SHAPES = [(12, 5, 2, 2), (7, 16, 4, 4), (33, 3, 1, 3), (64, 40, 2, 4), (3, 9, 3, 3)]
+
+
+@pytest.mark.parametrize("shape", SMALLMAP_SHAPES)
+def test_smallmap_pack_direct_route_bit_exact(K, shape):
+    """rfn_smallmap_pack_bf16x3 (the one-descriptor entry point), both orientations, sentinel-filled buffers"""
     from rfn_hip import lib as L
-    K.flush_packs()
-    asked = []
-    for i in range(70):
-        Cout, Cin, ks = PACK_SHAPES[i % len(PACK_SHAPES)]
-        w = _weight((Cout, Cin, ks, ks), 60 + i)
-        flip, prec = bool(i % 2), ("bf16x6", "bf16x3")[(i // 2) % 2]
-        asked.append((w, flip, prec, K.pack_weight(w.cuda(), flip=flip, prec=prec)))
-    assert len(K._CONV_PACK_QUEUE) == 70 and L.PENDING_FLUSH is not None
-    K.flush_packs()
-    L.PENDING_FLUSH = None
+    Cout, Cin, H, W = shape
+    w = _weight((Cout, Cin, 3, 3), 120 + Cout)
+    wd = w.cuda()
+    for tr in (0, 1):
+        ref = smallmap_pack_ref(w, H, W, tr)
+        nbytes = int(L.load().rfn_smallmap_packed_size(Cout, Cin, H, W, tr))
+        assert nbytes == 2 * ref.numel(), ("size function", shape, tr)
+        buf = _sentinel_buf(nbytes // 4 + MARGIN)
+        L.call("rfn_smallmap_pack_bf16x3", L.dev(wd), ctypes.c_int(Cout), ctypes.c_int(Cin), ctypes.c_int(H),
+               ctypes.c_int(W), ctypes.c_int(tr), L.dev(buf))
+        _check_pack(buf, ref, ("smallmap direct", shape, tr))
+
+
+def test_pack_batch_of_70_one_launch_per_kind(K, monkeypatch):
+    """70 conv packs and 70 small-map packs asked for in ONE PackBatch (two kernel-argument tables each) leave in
+    exactly one rfn_pack_conv_weights_hostdescs_bf16x3 and one rfn_smallmap_pack_batched_bf16x3 call, made when the
+    batch is left, and land bit for bit where the returned buffers say, in the orientation and plane count asked for"""
+    from rfn_hip import lib as L
+    calls, real = [], L.call
+
+    def spy(name, *args, **kw):
+        calls.append(name)
+        return real(name, *args, **kw)
+    monkeypatch.setattr(L, "call", spy)
+    asked, dense = [], []
+    with K.PackBatch() as pb:
+        for i in range(70):
+            Cout, Cin, ks = PACK_SHAPES[i % len(PACK_SHAPES)]
+            w = _weight((Cout, Cin, ks, ks), 60 + i)
+            flip, prec = bool(i % 2), ("bf16x6", "bf16x3")[(i // 2) % 2]
+            asked.append((w, flip, prec, pb.conv(w.cuda(), flip=flip, prec=prec)))
+            Cout, Cin, H, W = SMALLMAP_SHAPES[i % len(SMALLMAP_SHAPES)]
+            w = _weight((Cout, Cin, 3, 3), 140 + i)
+            tr = bool((i // 5) % 2)
+            dense.append((w, H, W, tr, pb.dense(w.cuda(), H, W, tr)))
+        assert calls == []
+    assert calls == ["rfn_pack_conv_weights_hostdescs_bf16x3", "rfn_smallmap_pack_batched_bf16x3"]
     for w, flip, prec, b in asked:
         ref = pack_ref(w, int(flip), 3 if prec == "bf16x6" else 2)
         assert torch.equal(b.view(torch.int32).cpu()[:ref.numel() // 2].view(torch.int16), ref), (tuple(w.shape), flip, prec)
+    for w, H, W, tr, b in dense:
+        ref = smallmap_pack_ref(w, H, W, tr)
+        assert ref.numel() == 2 * b.numel(), ("size", tuple(w.shape), H, W, tr)
+        assert torch.equal(b.view(torch.int32).cpu().view(torch.int16), ref), (tuple(w.shape), H, W, tr)
 
 
 # --------------------------------------------------------------------------------- 3. arithmetic of the forward pass

@@ -95,7 +95,7 @@ def test_library_exports_and_binds_frame_quality():
     assert lib.SIGNATURES["rfn_frame_quality_u8"] == [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long,
                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    assert L.rfn_abi_version() == 1
+    assert L.rfn_abi_version() == lib.ABI_VERSION == 2
 
 
 def test_restatement_matches_skimage_transcription():

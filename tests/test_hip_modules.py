@@ -4,6 +4,7 @@ from argparse import Namespace
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
@@ -459,6 +460,43 @@ def test_graph_captured_step_equals_eager_step():
         if n in eager:
             torch.testing.assert_close(p.grad, eager[n], rtol=1e-4, atol=1e-5 * float(eager[n].abs().max()) + 1e-7,
                                        msg=lambda m: n + ": " + m)
+
+
+def test_graph_replay_repacks_weights_updated_in_place():
+    """a captured body that asks for a conv pack and a small-map pack (one PackBatch) and consumes both: the packs are
+    part of the graph, so a replay after an in-place weight update computes with the new weights, as an eager run does"""
+    from rfn_hip import ops as K
+    g = torch.Generator().manual_seed(12)
+    N, Cin, Cout, S = 4, 16, 32, 8
+    x, xs = cu(torch.randn(N, Cin, S, S, generator=g)), cu(torch.randn(N, Cin, 2, 2, generator=g))
+    w, ws = cu(torch.randn(Cout, Cin, 3, 3, generator=g) / 12), cu(torch.randn(Cout, Cin, 3, 3, generator=g) / 12)
+    fp = K.fwd_prec(S, S)
+
+    def body():
+        with K.PackBatch() as pb:
+            pc, pd = pb.conv(w, prec=fp), pb.dense(ws, 2, 2, False)
+        return K.conv2d_raw(x, None, pc, Cout, 3, prec=fp), K.smallmap_dense(xs, pd, Cout)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        body()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = body()
+    graph.replay()
+    old = [o.clone() for o in out]
+    w.mul_(-0.5).add_(0.03)
+    ws.mul_(1.5).sub_(0.02)
+    graph.replay()
+    torch.cuda.synchronize()
+    eager = body()
+    ref = (F.conv2d(x.cpu().double(), w.cpu().double(), padding=1), F.conv2d(xs.cpu().double(), ws.cpu().double(), padding=1))
+    for o, o_old, e, r in zip(out, old, eager, ref):
+        close(o, e.cpu(), 1e-6, 0.0)               # the replay equals the eager run on the new weights
+        close(o, r, 2e-5, 0.0)                     # ... which is the convolution with them (bf16x3 at worst)
+        assert float((o - o_old).abs().max()) > 0.1 * float(r.abs().max())   # and not the old result
 
 
 def test_graph_replays_are_reproducible_canonical_architecture():
@@ -1400,7 +1438,7 @@ def test_fused_backward_chain_equals_unfused_backward(conv_precision, N, C, Cc, 
     plan = K.POPackPlan([(st[2].detach(), st[5].detach(), st[8].detach()) for st in steps])
     plan.run()
     assert all(b is not None for b in plan.bwd_bufs) and K.coupling_po_bwd_ok(N, C, S, S)
-    packs = [(None,) * 6 + (plan.bufs[k], plan.bwd_bufs[k]) for k in range(Kn)]
+    packs = [K.StepPacks(po_fwd=plan.bufs[k], po_bwd=plan.bwd_bufs[k]) for k in range(Kn)]
     gout = torch.randn(N, C, S, S, generator=g).cuda()
     gdl = torch.randn(N, generator=g).cuda()
     leaves = [x, cond, Wst] + [t for st in steps for t in st]

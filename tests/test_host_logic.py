@@ -47,7 +47,17 @@ def test_c_abi_exports_every_declared_symbol():
             want.append(cmap[ty])
         assert want == lib.SIGNATURES[name], "%s: header %s vs binding %s" % (name, want, lib.SIGNATURES[name])
     assert set(lib.SIGNATURES) == set(protos), set(lib.SIGNATURES) ^ set(protos)
-    assert L.rfn_abi_version() == 1
+    assert L.rfn_abi_version() == lib.ABI_VERSION == 2
+
+
+def test_load_refuses_a_library_of_another_abi_version(monkeypatch):
+    """lib.load() checks rfn_abi_version() against the version the binding was written for"""
+    from rfn_hip import lib
+    lib.load()
+    monkeypatch.setattr(lib, "_lib", None)
+    monkeypatch.setattr(lib, "ABI_VERSION", lib.ABI_VERSION + 1)
+    with pytest.raises(RuntimeError, match="rebuild the library"):
+        lib.load()
 
 
 def test_product_fails_loudly_without_gpu_tensors():
