@@ -258,9 +258,10 @@ int rfn_actnorm_invconv_bwd_ld_f32(const float* x, long x_ns, const float* bias,
                                    const float* gz, long gz_ns, float* gx, long gx_ns, float* gW, float* gbias,
                                    float* glogs, const float* glogdet, int N, int C, int HW, rfn_stream_t stream);
 
-/* ---- 3x3 convolution (stride 1, pad 1) with at most 64 output channels and Cin % 16 == 0 input channels on 32x32 or
- * 16x16 maps, bf16x3 arithmetic, one input tensor: the data gradient of the first coupling-net convolution at the two
- * finest flow levels (256 -> C/2 + Cc channels; backward of Flow/glow_modules.py:232-238).  wpk: the
+/* ---- 3x3 convolution (stride 1, pad 1) with few output channels (at most 64 on 32x32 and 16x16 maps, at most 96 on
+ * 8x8 maps) and Cin % 32 == 0 input channels, bf16x3 arithmetic, one input tensor whose N * Cin * H * W * 4 bytes stay
+ * below 0xFFFFFF00: the data gradient of the first coupling-net convolution at the three finest flow levels
+ * (256 -> C/2 + Cc channels; backward of Flow/glow_modules.py:232-238).  rfn_dgrad_small_supported tells.  wpk: the
  * rfn_pack_conv_weight_bf16x3 buffer of the logical weight (transpose_flip = 1 of the forward weight for a data
  * gradient).  Output channels [0, cout_split) go to out1, the rest to out2; acc1 / acc2: add into what is there. */
 int rfn_dgrad_small_supported(int N, int Cin, int Cout, int H, int W);
