@@ -836,7 +836,12 @@ static bool conv3x3_ws_eligible(const ConvParams& p, int ks) {
     static const bool off = getenv("RFN_CONV_WS") && atoi(getenv("RFN_CONV_WS")) == 0;
     const int Cin = p.C1 + p.C2;
     const bool pow2 = (p.H & (p.H - 1)) == 0 && (p.W & (p.W - 1)) == 0;
-    const bool shape = !off && ks == 3 && p.Cout % 256 == 0 && pow2 && p.W >= 8 && (long)p.H * p.W >= 64 &&
+    // the tile launch_conv3x3_ws_t cuts: TW = min(W, 32) columns by TH = 32 * PT / TW rows (PT = 2 for the 9- and 27-unit
+    // variants, 1 for the 45-unit one).  A frame must hold at least one: a 1 x W map with W >= 64 and PT = 2 has TH = 2
+    // and would get zero tiles
+    const int PT = (p.ep_mode == 4 || Cin <= 24) ? 2 : 1;
+    const int TH = 32 * PT / (p.W >= 32 ? 32 : (p.W > 0 ? p.W : 1));
+    const bool shape = !off && ks == 3 && p.Cout % 256 == 0 && pow2 && p.W >= 8 && (long)p.H * p.W >= 64 && p.H >= TH &&
                        (long)p.N * p.H * p.W >= 64L * 256 && p.cout_split == p.Cout && !p.acc1;
     if (p.ep_mode == 4) return shape && Cin <= 8 && p.C2 == 0;  // fused activation backward: 9-unit variant only
     return shape && Cin <= 40 && p.ep_mode >= 0 && p.ep_mode <= 3;

@@ -431,8 +431,10 @@ def conv_b3_kernel_name(Cout, ks, npix=1 << 30, Cin=None, hw=None, plain=True, a
     ws_on = os.environ.get("RFN_CONV_WS") != "0"
     if ks == 3 and ws_on and hw is not None and plain and Cout % 256 == 0 and npix >= 64 * 256:
         H, W = hw
-        if H & (H - 1) == 0 and W & (W - 1) == 0 and W >= 8 and H * W >= 64:
-            cin = Cin if isinstance(Cin, int) else None
+        cin = Cin if isinstance(Cin, int) else None
+        # at least one TW x TH tile per frame (TW = min(W, 32), TH = 32 * PT / TW): a 1 x W map with PT = 2 has none
+        PT = 2 if (actbwd or (cin is not None and cin <= 24)) else 1
+        if H & (H - 1) == 0 and W & (W - 1) == 0 and W >= 8 and H * W >= 64 and H >= 32 * PT // min(W, 32):
             if actbwd and cin is not None and cin <= 8:
                 return "conv3x3_ws_kernel<1,2,0>"
             if not actbwd and Cin is not None and Cin <= 40:
@@ -573,7 +575,10 @@ def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_sta
                _i(C2), pw, _i(G), _i(N), _i(H), _i(W),
                meta=("wgrad", "gemm_wgrad_dma_impl_kernel<grouped 4,2,2,3>" if (
                          Cout > 128 and G * N * H * W >= 100000 and N * H * W >= 2048 and (H * W) % 32 == 0 and gns % 4 == 0
-                         and os.environ.get("RFN_WGRAD_DMA", "1") != "0") else "gemm_wgrad_b3_kernel<grouped implicit>",
+                         and os.environ.get("RFN_WGRAD_DMA", "1") != "0") else
+                     # (a group never takes the 32-row tiling: p.G == 0 is part of its predicate)
+                     "gemm_wgrad_b3_kernel<grouped %s,1>" % ("4,2,2,3,64" if Cout > 128 and N * H * W >= 100000
+                                                             else "2,2,2,2,64"),
                      2.0 * G * N * H * W * Cout * 9 * Cin,
                      "G%d F%d %dx%d HW%d implicit3x3" % (G, N, Cout, 9 * Cin, H * W),
                      4.0 * G * (N * H * W * (Cout + Cin) + Cout * 9 * Cin)))
