@@ -17,11 +17,13 @@
  *     being captured into a hipGraph: run the shape eagerly once first) and serves every stream of the device, so
  *     split-K convolutions on DIFFERENT streams of one device must not overlap in time;
  *   - return value: 0 on success, otherwise a hipError_t / negative argument-check code; rfn_last_error() gives text;
- *   - global state: the (thread-local) last-error string, and five developer knobs that the kernel selectors read ONCE
+ *   - global state: the (thread-local) last-error string, and six developer knobs that the kernel selectors read ONCE
  *     from the environment at their first call and then keep for the life of the process: RFN_CONV_WS (0: no
- *     weight-stationary kernels), RFN_CONV_VARIANT, RFN_WGRAD_VARIANT, RFN_WGRAD_SPLIT, RFN_WGRAD_BPX128 (tile / split-K
- *     experiments; unset = production choice).  They pick between kernels that compute the same result; nothing else is
- *     cached between calls, and the library is safe to call from several host threads on distinct streams.
+ *     weight-stationary kernels), RFN_WGRAD_DMA (0: no LDS-DMA ring kernels), RFN_CONV_VARIANT, RFN_WGRAD_VARIANT,
+ *     RFN_WGRAD_SPLIT, RFN_WGRAD_BPX128 (tile / split-K experiments; unset = production choice).  They pick between
+ *     kernels that compute the same result; nothing else is cached between calls, and the library is safe to call from
+ *     several host threads on distinct streams.  The *_kernel_label_* queries answer with the same knobs applied, so a
+ *     caller may cache their answers for the life of the process.
  */
 #ifndef RFN_HIP_H
 #define RFN_HIP_H
@@ -96,6 +98,11 @@ int rfn_conv2d_fwd_f32(const float* in1, long in1_ns, int C1, const float* in2, 
                        const float* wpk, float* out1, long out1_ns, float* out2, long out2_ns, int Cout,
                        int cout_split, int acc1, int acc2, int N, int H, int W, int ks, int ep_mode,
                        const float* p0, const float* p1, int act, rfn_stream_t stream);
+/* Host-only label queries (here and below, *_kernel_label_*): the template instantiation the entry point named in the
+ * comment launches for these arguments, e.g. "conv_mfma_kernel<1,2,2,2,2,32>", as a pointer to static storage.  Each is
+ * answered by the very function the launcher switches on, needs no device, launches nothing, and takes every argument
+ * the choice depends on.  This one: rfn_conv2d_fwd_f32. */
+const char* rfn_conv2d_kernel_label_f32(int ks, int Cout, int N, int H, int W);
 
 /* ---- split-precision variant of the same convolution ("bf16x3"): every fp32 operand x is split on the fly into two
  * bf16 numbers hi + lo and a*b is formed as a_hi*b_hi + a_hi*b_lo + a_lo*b_hi by three v_mfma_f32_32x32x16_bf16 with
@@ -119,6 +126,10 @@ int rfn_conv2d_fwd_bf16x6(const float* in1, long in1_ns, int C1, const float* in
                           const float* wpk, float* out1, long out1_ns, float* out2, long out2_ns, int Cout,
                           int cout_split, int acc1, int acc2, int N, int H, int W, int ks, int ep_mode,
                           const float* p0, const float* p1, int act, rfn_stream_t stream);
+/* label query for rfn_conv2d_fwd_bf16x3 (npl = 2), rfn_conv2d_fwd_bf16x6 (npl = 3) and, with ep_mode = 4, cout_split =
+ * Cout, C2 = 0 and acc1 = 0, rfn_conv2d_dgrad_act_bf16x3 (C1 = its Cin) */
+const char* rfn_conv2d_kernel_label_bf16x3(int npl, int ks, int C1, int C2, int Cout, int cout_split, int acc1,
+                                          int ep_mode, int N, int H, int W);
 
 /* 3x3 / pad 1 convolution of an image with 1 .. 4 channels into 16 or 32 feature maps as plain fp32 FMAs (exact), one
  * thread per pixel: the first convolution of the frame extractor (Utils/modules.py:81, VGG_downscaler's 3x3 / stride 1 /
@@ -283,6 +294,8 @@ int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long
  * latency-class problem): a, b, gw are host arrays of G device pointers; strides and sizes are shared. */
 int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, int M, const float* const* b, long b_ns, int Nc,
                                   float* const* gw, int G, int F, int HW, rfn_stream_t stream);
+/* label query for both (G = 0: rfn_gemm_wgrad_bf16x3) */
+const char* rfn_gemm_wgrad_kernel_label_bf16x3(int M, int Nc, long a_ns, long b_ns, int G, int F, int HW);
 /* out[n][tap*Cin+ci][y][x] = in[n][ci][y+dy-1][x+dx-1] (0 outside); two-source input; out dense [N,9*Cin,H,W]. */
 /* 3x3 (pad 1) weight gradient without the im2col buffer (W % 8 == 0): gw[Cout][9*(C1+C2)] += sum over frames and
  * pixels of g[co][px] * in[ci][px + tap], column index ci*9 + tap: gw is the torch weight layout [Cout][Cin][3][3].
@@ -293,6 +306,8 @@ int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int Cout, const
 int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, long g_ns, int Cout, const float* const* in1,
                                               long in1_ns, int C1, const float* const* in2, long in2_ns, int C2,
                                               float* const* gw, int G, int F, int H, int W, rfn_stream_t stream);
+/* label query for both (G = 0: the ungrouped entry point) */
+const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W);
 int rfn_im2col3x3_f32(const float* in1, long in1_ns, int C1, const float* in2, long in2_ns, int C2, float* out, int N,
                       int H, int W, rfn_stream_t stream);
 
@@ -310,6 +325,7 @@ int rfn_pack_conv_weight_f32(const float* w, float* wpk, int Cout, int Cin, int 
 int rfn_conv2d_wgrad_f32(const float* in1, long in1_ns, int C1, const float* in2, long in2_ns, int C2,
                          const float* g, long g_ns, int Cout, float* gwt, int N, int H, int W, int ks,
                          rfn_stream_t stream);
+const char* rfn_conv2d_wgrad_kernel_label_f32(int ks, int Cin, int Cout, int H, int W); /* label query */
 /* gw[Cout][Cin][ks][ks] (torch layout) = (accumulate ? gw : 0) + transpose of gwt[ks*ks][Cout][Cin]. */
 int rfn_wgrad_finish_f32(const float* gwt, float* gw, int Cout, int Cin, int ks, int accumulate, rfn_stream_t stream);
 

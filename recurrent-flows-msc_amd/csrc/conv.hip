@@ -321,6 +321,42 @@ static int launch_conv(ConvParams& p, hipStream_t s) {
     return 0;
 }
 
+// ---- kernel choice: choose_conv_f32 maps a shape to a route (and launches nothing), rfn_conv2d_fwd_f32 switches over
+// the route, rfn_conv2d_kernel_label_f32 reads the route's label.  Instantiations are <KS,WCO,WPX,TCO,TPX,KC>.
+enum ConvF32Route { F3_COUT32, F3_COUT64, F3_FEW, F3_MANY, F1_COUT32, F1_COUT64, F1_FEW, F1_128x128, F1_256x64, F1_V1,
+                    F1_V2, F1_V4, F1_V5 };
+static const char* const kConvF32Labels[] = {
+    "conv_mfma_kernel<3,1,4,1,2,8>",    // F3_COUT32
+    "conv_mfma_kernel<3,1,4,2,1,8>",    // F3_COUT64
+    "conv_mfma_kernel<3,4,1,1,1,8>",    // F3_FEW
+    "conv_mfma_kernel<3,2,2,2,2,8>",    // F3_MANY
+    "conv_mfma_kernel<1,1,4,1,2,32>",   // F1_COUT32
+    "conv_mfma_kernel<1,1,4,2,1,32>",   // F1_COUT64
+    "conv_mfma_kernel<1,4,1,1,1,32>",   // F1_FEW
+    "conv_mfma_kernel<1,2,2,2,2,32>",   // F1_128x128
+    "conv_mfma_kernel<1,4,1,2,2,32>",   // F1_256x64
+    "conv_mfma_kernel<1,2,2,2,2,64>",   // F1_V1 (RFN_CONV_VARIANT=1; 2, 4, 5 below)
+    "conv_mfma_kernel<1,2,2,2,4,32>",   // F1_V2
+    "conv_mfma_kernel<1,2,2,4,2,32>",   // F1_V4
+    "conv_mfma_kernel<1,2,2,2,2,16>",   // F1_V5
+};
+static_assert(sizeof(kConvF32Labels) / sizeof(kConvF32Labels[0]) == F1_V5 + 1, "one label per route");
+static ConvF32Route choose_conv_f32(int ks, int Cout, int N, int H, int W) {
+    static const int variant = getenv("RFN_CONV_VARIANT") ? atoi(getenv("RFN_CONV_VARIANT")) : 0;
+    // few pixels in total (deep flow levels, ConvLSTM): 32-pixel tiles so that enough workgroups exist
+    const bool few_px = Cout > 64 && (long)N * H * W * ((Cout + 127) / 128) < 256L * 128;
+    if (ks == 3) return Cout <= 32 ? F3_COUT32 : (Cout <= 64 ? F3_COUT64 : (few_px ? F3_FEW : F3_MANY));
+    if (Cout <= 32) return F1_COUT32;
+    if (Cout <= 64) return F1_COUT64;
+    if (few_px) return F1_FEW;
+    if (Cout <= 128) return F1_128x128;  // <= 128 couts: one 128-row block, not a half-empty 256-row one
+    return variant == 1 ? F1_V1 : variant == 2 ? F1_V2 : variant == 4 ? F1_V4 : variant == 5 ? F1_V5
+           : variant == 6 ? F1_128x128 : F1_256x64;
+}
+extern "C" const char* rfn_conv2d_kernel_label_f32(int ks, int Cout, int N, int H, int W) {
+    return kConvF32Labels[choose_conv_f32(ks, Cout, N, H, W)];
+}
+
 extern "C" int rfn_conv2d_fwd_f32(const float* in1, long in1_ns, int C1, const float* in2, long in2_ns, int C2,
                                   const float* wpk, float* out1, long out1_ns, float* out2, long out2_ns, int Cout,
                                   int cout_split, int acc1, int acc2, int N, int H, int W, int ks, int ep_mode,
@@ -341,37 +377,21 @@ extern "C" int rfn_conv2d_fwd_f32(const float* in1, long in1_ns, int C1, const f
     packed_dims(Cout, C1 + C2, &p.CoutP, &p.Cin8);
     p.ep_mode = ep_mode; p.act = act; p.p0 = p0; p.p1 = p1;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    // few pixels in total (deep flow levels, ConvLSTM): 32-pixel tiles so that enough workgroups exist
-    const bool few_px = Cout > 64 && (long)N * H * W * ((Cout + 127) / 128) < 256L * 128;
-    if (ks == 3) {
-        if (Cout <= 32)
-            rc = launch_conv<3, 1, 4, 1, 2, 8>(p, s);
-        else if (Cout <= 64)
-            rc = launch_conv<3, 1, 4, 2, 1, 8>(p, s);
-        else if (few_px)
-            rc = launch_conv<3, 4, 1, 1, 1, 8>(p, s);
-        else
-            rc = launch_conv<3, 2, 2, 2, 2, 8>(p, s);
-    } else {
-        if (Cout <= 32)
-            rc = launch_conv<1, 1, 4, 1, 2, 32>(p, s);
-        else if (Cout <= 64)
-            rc = launch_conv<1, 1, 4, 2, 1, 32>(p, s);
-        else if (few_px)
-            rc = launch_conv<1, 4, 1, 1, 1, 32>(p, s);
-        else {
-            static int variant = getenv("RFN_CONV_VARIANT") ? atoi(getenv("RFN_CONV_VARIANT")) : 0;
-            switch (Cout <= 128 ? 6 : variant) {  // <= 128 couts: one 128-row block, not a half-empty 256-row one
-                case 1: rc = launch_conv<1, 2, 2, 2, 2, 64>(p, s); break;
-                case 2: rc = launch_conv<1, 2, 2, 2, 4, 32>(p, s); break;
-                case 3: rc = launch_conv<1, 4, 1, 2, 2, 32>(p, s); break;
-                case 4: rc = launch_conv<1, 2, 2, 4, 2, 32>(p, s); break;
-                case 5: rc = launch_conv<1, 2, 2, 2, 2, 16>(p, s); break;
-                case 6: rc = launch_conv<1, 2, 2, 2, 2, 32>(p, s); break;
-                default: rc = launch_conv<1, 4, 1, 2, 2, 32>(p, s);
-            }
-        }
+    int rc = -9;
+    switch (choose_conv_f32(ks, Cout, N, H, W)) {
+        case F3_COUT32:  rc = launch_conv<3, 1, 4, 1, 2, 8>(p, s); break;
+        case F3_COUT64:  rc = launch_conv<3, 1, 4, 2, 1, 8>(p, s); break;
+        case F3_FEW:     rc = launch_conv<3, 4, 1, 1, 1, 8>(p, s); break;
+        case F3_MANY:    rc = launch_conv<3, 2, 2, 2, 2, 8>(p, s); break;
+        case F1_COUT32:  rc = launch_conv<1, 1, 4, 1, 2, 32>(p, s); break;
+        case F1_COUT64:  rc = launch_conv<1, 1, 4, 2, 1, 32>(p, s); break;
+        case F1_FEW:     rc = launch_conv<1, 4, 1, 1, 1, 32>(p, s); break;
+        case F1_128x128: rc = launch_conv<1, 2, 2, 2, 2, 32>(p, s); break;
+        case F1_256x64:  rc = launch_conv<1, 4, 1, 2, 2, 32>(p, s); break;
+        case F1_V1:      rc = launch_conv<1, 2, 2, 2, 2, 64>(p, s); break;
+        case F1_V2:      rc = launch_conv<1, 2, 2, 2, 4, 32>(p, s); break;
+        case F1_V4:      rc = launch_conv<1, 2, 2, 4, 2, 32>(p, s); break;
+        case F1_V5:      rc = launch_conv<1, 2, 2, 2, 2, 16>(p, s); break;
     }
     if (rc) return rc;
     RFN_LAUNCH_CHECK();
@@ -562,16 +582,35 @@ static void launch_wgrad_bpx(WgradParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
 }
 
-// tiny maps (<= 4x4) use 64-pixel tiles: their zero-padded LDS image is 2.25-4x the tile, and 128 would not fit.
-template <int KS, int WCO, int WCI, int TCO, int TCI>
-static void launch_wgrad(WgradParams& p, hipStream_t s) {
+// ---- kernel choice, as for the forward convolution: <KS,WCO,WCI,TCO,TCI> and the pixels per stage (64 or 128)
+enum WgradF32Tile { W3_128x32, W3_32x128, W3_64x64, W1_256x32, W1_32x256, W1_64x256, W1_128x128 };
+struct WgradF32Route { WgradF32Tile tile; bool bpx128; };
+static const char* const kWgradF32Labels[][2] = {
+    {"wgrad_mfma_kernel<3,4,1,1,1,64>", "wgrad_mfma_kernel<3,4,1,1,1,128>"},   // 128 co x 32 ci
+    {"wgrad_mfma_kernel<3,1,4,1,1,64>", "wgrad_mfma_kernel<3,1,4,1,1,128>"},   // 32 co x 128 ci
+    {"wgrad_mfma_kernel<3,2,2,1,1,64>", "wgrad_mfma_kernel<3,2,2,1,1,128>"},   // 64 x 64
+    {"wgrad_mfma_kernel<1,4,1,2,1,64>", "wgrad_mfma_kernel<1,4,1,2,1,128>"},   // 256 co x 32 ci
+    {"wgrad_mfma_kernel<1,1,4,1,2,64>", "wgrad_mfma_kernel<1,1,4,1,2,128>"},   // 32 co x 256 ci
+    {"wgrad_mfma_kernel<1,1,4,2,2,64>", nullptr},   // 64 co x 256 ci (tap-expanded conv3 at level 0: 36 rows), 64 only
+    {"wgrad_mfma_kernel<1,2,2,2,2,64>", "wgrad_mfma_kernel<1,2,2,2,2,128>"},   // 128 x 128
+};
+static_assert(sizeof(kWgradF32Labels) / sizeof(kWgradF32Labels[0]) == W1_128x128 + 1, "one row per tile");
+static WgradF32Route choose_wgrad_f32(int ks, int Cin, int Cout, int H, int W) {
     // 64-pixel stages everywhere: the G+X stage then takes <= ~66 KB of LDS, so 2-3 workgroups share a CU and one's
-    // staging overlaps another's MFMAs (128-pixel stages left a single workgroup per CU: 57 -> 70 TFLOP/s on conv2)
-    static int use128 = getenv("RFN_WGRAD_BPX128") ? atoi(getenv("RFN_WGRAD_BPX128")) : 0;
-    if (p.H * p.W <= 16 || !use128)
-        launch_wgrad_bpx<KS, WCO, WCI, TCO, TCI, 64>(p, s);
-    else
-        launch_wgrad_bpx<KS, WCO, WCI, TCO, TCI, 128>(p, s);
+    // staging overlaps another's MFMAs (128-pixel stages left a single workgroup per CU: 57 -> 70 TFLOP/s on conv2);
+    // tiny maps (<= 4x4) always: their zero-padded LDS image is 2.25-4x the tile, and 128 would not fit.
+    static const int use128 = getenv("RFN_WGRAD_BPX128") ? atoi(getenv("RFN_WGRAD_BPX128")) : 0;
+    const WgradF32Tile t = ks == 3 ? (Cin <= 32 ? W3_128x32 : (Cout <= 32 ? W3_32x128 : W3_64x64))
+                                   : (Cin <= 32 ? W1_256x32 : (Cout <= 32 ? W1_32x256 : (Cout <= 64 ? W1_64x256 : W1_128x128)));
+    return {t, use128 && H * W > 16 && t != W1_64x256};
+}
+extern "C" const char* rfn_conv2d_wgrad_kernel_label_f32(int ks, int Cin, int Cout, int H, int W) {
+    const WgradF32Route r = choose_wgrad_f32(ks, Cin, Cout, H, W);
+    return kWgradF32Labels[r.tile][r.bpx128];
+}
+template <int KS, int WCO, int WCI, int TCO, int TCI>
+static void launch_wgrad(WgradParams& p, bool bpx128, hipStream_t s) {
+    bpx128 ? launch_wgrad_bpx<KS, WCO, WCI, TCO, TCI, 128>(p, s) : launch_wgrad_bpx<KS, WCO, WCI, TCO, TCI, 64>(p, s);
 }
 
 extern "C" int rfn_conv2d_wgrad_f32(const float* in1, long in1_ns, int C1, const float* in2, long in2_ns, int C2,
@@ -586,23 +625,15 @@ extern "C" int rfn_conv2d_wgrad_f32(const float* in1, long in1_ns, int C1, const
     p.in1 = in1; p.in2 = in2; p.in1_ns = in1_ns; p.in2_ns = in2_ns; p.C1 = C1; p.C2 = C2;
     p.g = g; p.g_ns = g_ns; p.Cout = Cout; p.gwt = gwt; p.N = N; p.H = H; p.W = W;
     hipStream_t s = (hipStream_t)stream;
-    const int Cin = C1 + C2;
-    if (ks == 3) {
-        if (Cin <= 32)
-            launch_wgrad<3, 4, 1, 1, 1>(p, s);   // 128 co x 32 ci
-        else if (Cout <= 32)
-            launch_wgrad<3, 1, 4, 1, 1>(p, s);   // 32 co x 128 ci
-        else
-            launch_wgrad<3, 2, 2, 1, 1>(p, s);   // 64 x 64
-    } else {
-        if (Cin <= 32)
-            launch_wgrad<1, 4, 1, 2, 1>(p, s);   // 256 co x 32 ci
-        else if (Cout <= 32)
-            launch_wgrad<1, 1, 4, 1, 2>(p, s);   // 32 co x 256 ci
-        else if (Cout <= 64)
-            launch_wgrad_bpx<1, 1, 4, 2, 2, 64>(p, s);  // 64 co x 256 ci (tap-expanded conv3 at level 0: 36 rows)
-        else
-            launch_wgrad<1, 2, 2, 2, 2>(p, s);   // 128 x 128
+    const WgradF32Route r = choose_wgrad_f32(ks, C1 + C2, Cout, H, W);
+    switch (r.tile) {
+        case W3_128x32:  launch_wgrad<3, 4, 1, 1, 1>(p, r.bpx128, s); break;
+        case W3_32x128:  launch_wgrad<3, 1, 4, 1, 1>(p, r.bpx128, s); break;
+        case W3_64x64:   launch_wgrad<3, 2, 2, 1, 1>(p, r.bpx128, s); break;
+        case W1_256x32:  launch_wgrad<1, 4, 1, 2, 1>(p, r.bpx128, s); break;
+        case W1_32x256:  launch_wgrad<1, 1, 4, 1, 2>(p, r.bpx128, s); break;
+        case W1_64x256:  launch_wgrad_bpx<1, 1, 4, 2, 2, 64>(p, s); break;
+        case W1_128x128: launch_wgrad<1, 2, 2, 2, 2>(p, r.bpx128, s); break;
     }
     RFN_LAUNCH_CHECK();
     return 0;

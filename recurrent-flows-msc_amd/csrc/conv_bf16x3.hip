@@ -441,31 +441,78 @@ static int launch_conv_b3(ConvParams& p, hipStream_t s) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ kernel choice
+// Every instantiation a split-precision convolution can run is one route: choose_conv_b3 is the only place a shape is
+// mapped to a route (it launches nothing), dispatch_conv_b3 the only place a route is mapped to a launch, and the label
+// queries of the C ABI read the same table.  Generic tile kernel: <KS,WCO,WPX,TCO,TPX,KC>, BPX = 32 * TPX * WPX pixels
+// per workgroup; weight-stationary kernels: BPX pixels per tile of a persistent workgroup, WPX = 0.
+enum ConvB3Route { G3_32x128, G3_64x64, G3_64x128, G1_32x128, G1_64x64, G1_128x128, G1_256x64, WS1, WS3_ACTBWD, WS3_27,
+                   WS3_45 };
+static const struct { const char* label; int BPX, WPX; } kConvB3Routes[] = {
+    {"conv_b3_kernel<3,1,4,1,1,16>", 128, 4},   // 32 co x 128 px
+    {"conv_b3_kernel<3,2,2,1,1,16>", 64, 2},    // 64 co x 64 px (32-channel chunks measured 1.6x slower)
+    {"conv_b3_kernel<3,2,2,1,2,16>", 128, 2},   // 64 co x 128 px
+    {"conv_b3_kernel<1,1,4,1,1,32>", 128, 4},
+    {"conv_b3_kernel<1,2,2,1,1,32>", 64, 2},    // 64 co x 64 px
+    {"conv_b3_kernel<1,2,2,2,2,32>", 128, 2},   // 128 co x 128 px
+    {"conv_b3_kernel<1,4,1,2,2,32>", 64, 1},    // 256 co x 64 px: the input tile is read once for 256 couts
+    {"conv1x1_ws_kernel<16>", 32, 0},
+    {"conv3x3_ws_kernel<1,2,0>", 64, 0},        // 9 units, fused activation backward (ep_mode 4)
+    {"conv3x3_ws_kernel<3,2,1>", 64, 0},        // Cin <= 24: 27 units (112 weight registers), two accumulator tiles per step
+    {"conv3x3_ws_kernel<5,1,1>", 32, 0},        // Cin <= 40: 45 units (184), one
+};
+static_assert(sizeof(kConvB3Routes) / sizeof(kConvB3Routes[0]) == WS3_45 + 1, "one row per route");
+
+// needs of p: N, H, W, C1, C2, Cout, cout_split, acc1, ep_mode, npl
+static ConvB3Route choose_conv_b3(const ConvParams& p, int ks) {
+    static const bool ws_off = getenv("RFN_CONV_WS") && atoi(getenv("RFN_CONV_WS")) == 0;
+    const int Cin = p.C1 + p.C2, Cout = p.Cout;
+    const long npix = (long)p.N * p.H * p.W;
+    // bf16x6 (npl == 3): the generic tile kernel only (forward convolutions of the middle flow levels)
+    if (p.npl != 3 && !ws_off && Cout % 256 == 0 && npix >= 64L * 256) {
+        if (ks == 1 && p.C2 == 0 && Cin > 128 && Cin <= 256) return WS1;
+        // the tile launch_conv3x3_ws_t cuts: TW = min(W, 32) columns by TH = 32 * PT / TW rows (PT = 2 for the 9- and
+        // 27-unit variants, 1 for the 45-unit one).  A frame must hold at least one: a 1 x W map with W >= 64 and PT = 2
+        // has TH = 2 and would get zero tiles
+        const int PT = (p.ep_mode == 4 || Cin <= 24) ? 2 : 1;
+        const int TH = 32 * PT / (p.W >= 32 ? 32 : (p.W > 0 ? p.W : 1));
+        const bool pow2 = (p.H & (p.H - 1)) == 0 && (p.W & (p.W - 1)) == 0;
+        if (ks == 3 && pow2 && p.W >= 8 && (long)p.H * p.W >= 64 && p.H >= TH && p.cout_split == Cout && !p.acc1) {
+            if (p.ep_mode == 4 && Cin <= 8 && p.C2 == 0) return WS3_ACTBWD;
+            if (p.ep_mode >= 0 && p.ep_mode <= 3 && Cin <= 40) return Cin <= 24 ? WS3_27 : WS3_45;
+        }
+    }
+    const bool few_px = npix * ((Cout + 127) / 128) < 256L * 128;
+    if (ks == 3) return Cout <= 32 ? G3_32x128 : (few_px ? G3_64x64 : G3_64x128);
+    if (Cout <= 32) return G1_32x128;
+    if (few_px || Cout <= 64) return G1_64x64;
+    return Cout <= 128 ? G1_128x128 : G1_256x64;
+}
 static int dispatch_conv_b3(ConvParams& p, int ks, hipStream_t s);
 
-// number of partial-sum rows rfn_conv2d_dgrad_act_bf16x3 writes for (N,H,W,ks,Cout): pixel tiles x waves along pixels
-static bool conv1x1_ws_eligible(int ks, int Cin, int C2, int Cout, long npix);
-static bool conv3x3_ws_rows(int N, int H, int W, int ks, int Cout, int Cin, int* rows);
-extern "C" int rfn_conv2d_dgrad_act_rows_bf16x3(int N, int H, int W, int ks, int Cout, int Cin) {
-    if (conv1x1_ws_eligible(ks, Cin, 0, Cout, (long)N * H * W)) {
-        const long nt = ((long)N * H * W + 31) / 32;
-        return (int)(nt < 256 ? nt : 256);  // one row per persistent workgroup
-    }
-    int ws3_rows = 0;
-    if (conv3x3_ws_rows(N, H, W, ks, Cout, Cin, &ws3_rows)) return ws3_rows;
+static ConvParams conv_b3_shape(int npl, int C1, int C2, int Cout, int cout_split, int acc1, int ep_mode, int N, int H,
+                                int W) {
     ConvParams p;
     memset(&p, 0, sizeof(p));
-    p.N = N; p.H = H; p.W = W; p.Cout = Cout;
-    const bool few_px = (long)N * H * W * ((Cout + 127) / 128) < 256L * 128;
-    int BPX, WPX;
-    if (ks == 3) { BPX = few_px ? 64 : 128; WPX = 2; }
-    else if (few_px || Cout <= 64) { BPX = 64; WPX = 2; }
-    else if (Cout <= 128) { BPX = 128; WPX = 2; }
-    else { BPX = 64; WPX = 1; }
-    if (Cout <= 32) { BPX = 128; WPX = 4; }
+    p.npl = npl; p.C1 = C1; p.C2 = C2; p.Cout = Cout; p.cout_split = cout_split; p.acc1 = acc1; p.ep_mode = ep_mode;
+    p.N = N; p.H = H; p.W = W;
+    return p;
+}
+extern "C" const char* rfn_conv2d_kernel_label_bf16x3(int npl, int ks, int C1, int C2, int Cout, int cout_split, int acc1,
+                                                     int ep_mode, int N, int H, int W) {
+    return kConvB3Routes[choose_conv_b3(conv_b3_shape(npl, C1, C2, Cout, cout_split, acc1, ep_mode, N, H, W), ks)].label;
+}
+// number of partial-sum rows rfn_conv2d_dgrad_act_bf16x3 writes for (N,H,W,ks,Cout): pixel tiles x waves along pixels,
+// or one row per persistent workgroup of a weight-stationary kernel
+extern "C" int rfn_conv2d_dgrad_act_rows_bf16x3(int N, int H, int W, int ks, int Cout, int Cin) {
+    const auto& r = kConvB3Routes[choose_conv_b3(conv_b3_shape(2, Cin, 0, Cout, Cout, 0, 4, N, H, W), ks)];
+    if (r.WPX == 0) {
+        const long nt = ((long)N * H * W + r.BPX - 1) / r.BPX;
+        return (int)(nt < 256 ? nt : 256);
+    }
     int TWp, TH, TF;
-    tile_geometry(H, W, BPX, &TWp, &TH, &TF);
-    return ceil_div(W, TWp) * ceil_div(H, TH) * ceil_div(N, TF) * WPX;
+    tile_geometry(H, W, r.BPX, &TWp, &TH, &TF);
+    return ceil_div(W, TWp) * ceil_div(H, TH) * ceil_div(N, TF) * r.WPX;
 }
 
 // data-gradient conv fused with the backward of the producer's Conv2dNorm epilogue (ActNorm + activation):
@@ -832,31 +879,6 @@ __global__ __launch_bounds__(512) void conv3x3_ws_kernel(const ConvParams p, con
     }
 }
 
-static bool conv3x3_ws_eligible(const ConvParams& p, int ks) {
-    static const bool off = getenv("RFN_CONV_WS") && atoi(getenv("RFN_CONV_WS")) == 0;
-    const int Cin = p.C1 + p.C2;
-    const bool pow2 = (p.H & (p.H - 1)) == 0 && (p.W & (p.W - 1)) == 0;
-    // the tile launch_conv3x3_ws_t cuts: TW = min(W, 32) columns by TH = 32 * PT / TW rows (PT = 2 for the 9- and 27-unit
-    // variants, 1 for the 45-unit one).  A frame must hold at least one: a 1 x W map with W >= 64 and PT = 2 has TH = 2
-    // and would get zero tiles
-    const int PT = (p.ep_mode == 4 || Cin <= 24) ? 2 : 1;
-    const int TH = 32 * PT / (p.W >= 32 ? 32 : (p.W > 0 ? p.W : 1));
-    const bool shape = !off && ks == 3 && p.Cout % 256 == 0 && pow2 && p.W >= 8 && (long)p.H * p.W >= 64 && p.H >= TH &&
-                       (long)p.N * p.H * p.W >= 64L * 256 && p.cout_split == p.Cout && !p.acc1;
-    if (p.ep_mode == 4) return shape && Cin <= 8 && p.C2 == 0;  // fused activation backward: 9-unit variant only
-    return shape && Cin <= 40 && p.ep_mode >= 0 && p.ep_mode <= 3;
-}
-// rows of partial sums the ep_mode-4 variant writes: one per 64-pixel tile
-static bool conv3x3_ws_rows(int N, int H, int W, int ks, int Cout, int Cin, int* rows) {
-    ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.N = N; p.H = H; p.W = W; p.Cout = Cout; p.cout_split = Cout; p.C1 = Cin; p.ep_mode = 4;
-    if (!conv3x3_ws_eligible(p, ks)) return false;
-    const long nt = (long)N * H * W / 64;
-    *rows = (int)(nt < 256 ? nt : 256);  // one row per persistent workgroup
-    return true;
-}
-
 template <int NG, int PT, bool FASTEP = true>
 static int launch_conv3x3_ws_t(ConvParams& p, hipStream_t s) {
     const int TW = p.W < 32 ? p.W : 32, TH = 32 * PT / TW;
@@ -876,16 +898,6 @@ static int launch_conv3x3_ws_t(ConvParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, p, n_tiles, tw_shift, tpf_shift, wt_shift);
     return 0;
 }
-static int launch_conv3x3_ws(ConvParams& p, hipStream_t s) {
-    // Cin <= 24: 27 units (112 weight registers), two accumulator tiles per step; Cin <= 40: 45 units (184), one
-    if (p.ep_mode == 4) return launch_conv3x3_ws_t<1, 2, false>(p, s);
-    return p.C1 + p.C2 <= 24 ? launch_conv3x3_ws_t<3, 2>(p, s) : launch_conv3x3_ws_t<5, 1>(p, s);
-}
-
-static bool conv1x1_ws_eligible(int ks, int Cin, int C2, int Cout, long npix) {
-    static const bool off = getenv("RFN_CONV_WS") && atoi(getenv("RFN_CONV_WS")) == 0;
-    return !off && ks == 1 && C2 == 0 && Cout % 256 == 0 && Cin > 128 && Cin <= 256 && npix >= 64L * 256;
-}
 
 static int launch_conv1x1_ws(ConvParams& p, hipStream_t s) {
     const int HW = p.H * p.W;
@@ -902,48 +914,25 @@ static int launch_conv1x1_ws(ConvParams& p, hipStream_t s) {
     return 0;
 }
 
+// the generic tile kernel on two (bf16x3) or three (bf16x6) planes per operand
+template <int KS, int WCO, int WPX, int TCO, int TPX, int KC>
+static int launch_conv_b3_npl(ConvParams& p, hipStream_t s) {
+    return p.npl == 3 ? launch_conv_b3<KS, WCO, WPX, TCO, TPX, KC, 3>(p, s) : launch_conv_b3<KS, WCO, WPX, TCO, TPX, KC>(p, s);
+}
+
 static int dispatch_conv_b3(ConvParams& p, int ks, hipStream_t s) {
-    const int Cout = p.Cout, N = p.N, H = p.H, W = p.W;
-    const bool few_px = (long)N * H * W * ((Cout + 127) / 128) < 256L * 128;
-    int rc;
-    if (p.npl == 3) {  // bf16x6: the generic tile kernel only (forward convolutions of the middle flow levels)
-        if (ks == 3) {
-            if (Cout <= 32)
-                rc = launch_conv_b3<3, 1, 4, 1, 1, 16, 3>(p, s);
-            else if (few_px)
-                rc = launch_conv_b3<3, 2, 2, 1, 1, 16, 3>(p, s);
-            else
-                rc = launch_conv_b3<3, 2, 2, 1, 2, 16, 3>(p, s);
-        } else {
-            if (Cout <= 32)
-                rc = launch_conv_b3<1, 1, 4, 1, 1, 32, 3>(p, s);
-            else if (few_px || Cout <= 64)
-                rc = launch_conv_b3<1, 2, 2, 1, 1, 32, 3>(p, s);
-            else if (Cout <= 128)
-                rc = launch_conv_b3<1, 2, 2, 2, 2, 32, 3>(p, s);
-            else
-                rc = launch_conv_b3<1, 4, 1, 2, 2, 32, 3>(p, s);
-        }
-        return rc;
+    switch (choose_conv_b3(p, ks)) {
+        case G3_32x128:  return launch_conv_b3_npl<3, 1, 4, 1, 1, 16>(p, s);
+        case G3_64x64:   return launch_conv_b3_npl<3, 2, 2, 1, 1, 16>(p, s);
+        case G3_64x128:  return launch_conv_b3_npl<3, 2, 2, 1, 2, 16>(p, s);
+        case G1_32x128:  return launch_conv_b3_npl<1, 1, 4, 1, 1, 32>(p, s);
+        case G1_64x64:   return launch_conv_b3_npl<1, 2, 2, 1, 1, 32>(p, s);
+        case G1_128x128: return launch_conv_b3_npl<1, 2, 2, 2, 2, 32>(p, s);
+        case G1_256x64:  return launch_conv_b3_npl<1, 4, 1, 2, 2, 32>(p, s);
+        case WS1:        return launch_conv1x1_ws(p, s);
+        case WS3_ACTBWD: return launch_conv3x3_ws_t<1, 2, false>(p, s);
+        case WS3_27:     return launch_conv3x3_ws_t<3, 2>(p, s);
+        case WS3_45:     return launch_conv3x3_ws_t<5, 1>(p, s);
     }
-    if (conv1x1_ws_eligible(ks, p.C1 + p.C2, p.C2, Cout, (long)N * H * W)) return launch_conv1x1_ws(p, s);
-    if (conv3x3_ws_eligible(p, ks)) return launch_conv3x3_ws(p, s);
-    if (ks == 3) {
-        if (Cout <= 32)
-            rc = launch_conv_b3<3, 1, 4, 1, 1, 16>(p, s);   // 32 co x 128 px
-        else if (few_px)
-            rc = launch_conv_b3<3, 2, 2, 1, 1, 16>(p, s);   // 64 co x 64 px (32-channel chunks measured 1.6x slower)
-        else
-            rc = launch_conv_b3<3, 2, 2, 1, 2, 16>(p, s);   // 64 co x 128 px
-    } else {
-        if (Cout <= 32)
-            rc = launch_conv_b3<1, 1, 4, 1, 1, 32>(p, s);
-        else if (few_px || Cout <= 64)
-            rc = launch_conv_b3<1, 2, 2, 1, 1, 32>(p, s);   // 64 co x 64 px
-        else if (Cout <= 128)
-            rc = launch_conv_b3<1, 2, 2, 2, 2, 32>(p, s);   // 128 co x 128 px
-        else
-            rc = launch_conv_b3<1, 4, 1, 2, 2, 32>(p, s);   // 256 co x 64 px: the input tile is read once for 256 couts
-    }
-    return rc;
+    return -9;
 }

@@ -740,14 +740,6 @@ static void launch_gemm_wgrad_dma_impl(GemmWgradParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
 }
 
-// shapes the LDS-DMA kernel takes: a plain (1x1-form) gradient -- or a group of them -- over whole 32-pixel stages
-static bool wgrad_dma_ok(const GemmWgradParams& p) {
-    static const int off = getenv("RFN_WGRAD_DMA") ? atoi(getenv("RFN_WGRAD_DMA")) == 0 : 0;
-    // (grouped: the K gradients of a level together are the problem size)
-    return !off && p.HW % 32 == 0 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 && p.a_ns % 4 == 0 &&
-           p.b_ns % 4 == 0 && p.N > 128;
-}
-
 template <int WM, int WN, int TM, int TN, int KP, int IMPL = 0>
 static void launch_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
@@ -769,29 +761,90 @@ static void launch_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
 }
 
-static void select_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
+// ---- kernel choice: choose_gemm_wgrad / choose_wgrad_implicit map a shape to a route (and launch nothing),
+// launch_wgrad_route is the only place a route is mapped to a launch, the label queries of the C ABI read the same table.
+// Instantiations: gemm_wgrad_dma_kernel<WM,WN,TM,TN,KP,NST>, gemm_wgrad_b3_kernel<WM,WN,TM,TN,KP[,IMPL]>.
+enum WgradB3Route { DMA_256x256, DMA_64x256, R_256x192, R_256x192_KP32, R_256x256, R_256x256_KP32, R_64x256, R_256x64,
+                    R_128x128, IMPL_DMA_256x192, IMPL_256x192, IMPL_32x256, IMPL_128x128 };
+static const char* const kWgradB3Labels[] = {
+    "gemm_wgrad_dma_kernel<2,4,4,2,32,2>",   // 256 x 256, two slots of 64 KB
+    "gemm_wgrad_dma_kernel<1,8,2,1,32,3>",   // 64 x 256, ring of 3 x 40 KB
+    "gemm_wgrad_b3_kernel<4,2,2,3,64>",      // 256 x 192, 8 waves, 64-pixel stages
+    "gemm_wgrad_b3_kernel<4,2,2,3,32>",      // (RFN_WGRAD_VARIANT=2: 32-pixel stages)
+    "gemm_wgrad_b3_kernel<2,4,4,2,64>",      // 256 x 256, 8 waves, 64-pixel stages
+    "gemm_wgrad_b3_kernel<2,4,4,2,32>",      // (RFN_WGRAD_VARIANT=2)
+    "gemm_wgrad_b3_kernel<1,4,2,2,32>",      // 64 x 256
+    "gemm_wgrad_b3_kernel<4,1,2,2,32>",      // 256 x 64
+    "gemm_wgrad_b3_kernel<2,2,2,2,64>",      // 128 x 128
+    "gemm_wgrad_dma_impl_kernel<4,2,2,3>",   // implicit 3x3: 256 x 192, 8 waves, A through the DMA ring
+    "gemm_wgrad_b3_kernel<4,2,2,3,64,1>",    // 256 x 192, 8 waves
+    "gemm_wgrad_b3_kernel<1,4,1,2,32,1>",    // 32 x 256
+    "gemm_wgrad_b3_kernel<2,2,2,2,64,1>",    // 128 x 128
+};
+static_assert(sizeof(kWgradB3Labels) / sizeof(kWgradB3Labels[0]) == IMPL_128x128 + 1, "one label per route");
+static bool wgrad_dma_off() {
+    static const int off = getenv("RFN_WGRAD_DMA") ? atoi(getenv("RFN_WGRAD_DMA")) == 0 : 0;
+    return off;
+}
+// the shape fields of p both choices read: M, N, a_ns, b_ns, G (0: ungrouped), total, HW
+static GemmWgradParams wgrad_shape(int M, int Nc, long a_ns, long b_ns, int G, int F, int HW) {
+    GemmWgradParams p;
+    memset(&p, 0, sizeof(p));
+    p.M = M; p.N = Nc; p.a_ns = a_ns; p.b_ns = b_ns; p.G = G; p.F = F; p.HW = HW; p.total = (long)F * HW;
+    return p;
+}
+
+static WgradB3Route choose_gemm_wgrad(const GemmWgradParams& p) {
     const int M = p.M, Nc = p.N;
     static const int variant = getenv("RFN_WGRAD_VARIANT") ? atoi(getenv("RFN_WGRAD_VARIANT")) : 0;
-    if (variant == 0 && wgrad_dma_ok(p)) {
-        if (M >= 192 && Nc % 256 == 0) return launch_gemm_wgrad_dma<2, 4, 4, 2, 32, 2>(p, s);   // 256 x 256, two slots of 64 KB
-        if (M <= 64 && Nc % 256 == 0) return launch_gemm_wgrad_dma<1, 8, 2, 1, 32, 3>(p, s);   // 64 x 256, ring of 3 x 40 KB
+    // the LDS-DMA kernels take a plain (1x1-form) gradient -- or a group of them: the K gradients of a level together are
+    // the problem size -- over whole 32-pixel stages
+    if (variant == 0 && !wgrad_dma_off() && p.HW % 32 == 0 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 &&
+        p.a_ns % 4 == 0 && p.b_ns % 4 == 0 && Nc > 128 && Nc % 256 == 0) {
+        if (M >= 192) return DMA_256x256;
+        if (M <= 64) return DMA_64x256;
     }
-    const bool big = variant != 1 && M > 128 && Nc > 128 && p.total >= 100000;
-    if (big && ceil_div(Nc, 192) * 192 < ceil_div(Nc, 256) * 256) {
-        if (variant == 2)
-            launch_gemm_wgrad<4, 2, 2, 3, 32>(p, s);
-        else
-            launch_gemm_wgrad<4, 2, 2, 3, 64>(p, s);   // 256 x 192, 8 waves, 64-pixel stages
-    } else if (big && variant == 2)
-        launch_gemm_wgrad<2, 4, 4, 2, 32>(p, s);
-    else if (big)
-        launch_gemm_wgrad<2, 4, 4, 2, 64>(p, s);   // 256 x 256, 8 waves, 64-pixel stages
-    else if (M <= 64)
-        launch_gemm_wgrad<1, 4, 2, 2, 32>(p, s);   // 64 x 256
-    else if (Nc <= 64)
-        launch_gemm_wgrad<4, 1, 2, 2, 32>(p, s);   // 256 x 64
-    else
-        launch_gemm_wgrad<2, 2, 2, 2, 64>(p, s);   // 128 x 128
+    if (variant != 1 && M > 128 && Nc > 128 && p.total >= 100000) {
+        if (ceil_div(Nc, 192) * 192 < ceil_div(Nc, 256) * 256) return variant == 2 ? R_256x192_KP32 : R_256x192;
+        return variant == 2 ? R_256x256_KP32 : R_256x256;
+    }
+    return M <= 64 ? R_64x256 : (Nc <= 64 ? R_256x64 : R_128x128);
+}
+extern "C" const char* rfn_gemm_wgrad_kernel_label_bf16x3(int M, int Nc, long a_ns, long b_ns, int G, int F, int HW) {
+    return kWgradB3Labels[choose_gemm_wgrad(wgrad_shape(M, Nc, a_ns, b_ns, G, F, HW))];
+}
+
+// 3x3 weight gradient without the im2col buffer (rfn_conv3x3_wgrad_implicit_bf16x3 below): M = Cout, a = the gradient
+static WgradB3Route choose_wgrad_implicit(const GemmWgradParams& p) {
+    // (grouped: the K gradients of a level together are the problem size)
+    if (p.M > 128 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 && !wgrad_dma_off() && p.HW % 32 == 0 &&
+        p.a_ns % 4 == 0)
+        return IMPL_DMA_256x192;
+    if (p.M > 128 && p.total >= 100000) return IMPL_256x192;
+    // few output channels (the 16- / 32-channel blocks of the extractor / upscaler on 64x64 and 32x32 maps): one 32-row
+    // tile instead of 128 rows of which 16 are real (the clamped rows were 8x the loads and MFMAs of the gradient)
+    return p.M <= 32 && p.G == 0 ? IMPL_32x256 : IMPL_128x128;
+}
+extern "C" const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W) {
+    return kWgradB3Labels[choose_wgrad_implicit(wgrad_shape(Cout, 0, g_ns, 0, G, F, H * W))];
+}
+
+static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s) {
+    switch (r) {
+        case DMA_256x256:      return launch_gemm_wgrad_dma<2, 4, 4, 2, 32, 2>(p, s);
+        case DMA_64x256:       return launch_gemm_wgrad_dma<1, 8, 2, 1, 32, 3>(p, s);
+        case R_256x192:        return launch_gemm_wgrad<4, 2, 2, 3, 64>(p, s);
+        case R_256x192_KP32:   return launch_gemm_wgrad<4, 2, 2, 3, 32>(p, s);
+        case R_256x256:        return launch_gemm_wgrad<2, 4, 4, 2, 64>(p, s);
+        case R_256x256_KP32:   return launch_gemm_wgrad<2, 4, 4, 2, 32>(p, s);
+        case R_64x256:         return launch_gemm_wgrad<1, 4, 2, 2, 32>(p, s);
+        case R_256x64:         return launch_gemm_wgrad<4, 1, 2, 2, 32>(p, s);
+        case R_128x128:        return launch_gemm_wgrad<2, 2, 2, 2, 64>(p, s);
+        case IMPL_DMA_256x192: return launch_gemm_wgrad_dma_impl<4, 2, 2, 3>(p, s);
+        case IMPL_256x192:     return launch_gemm_wgrad<4, 2, 2, 3, 64, 1>(p, s);
+        case IMPL_32x256:      return launch_gemm_wgrad<1, 4, 1, 2, 32, 1>(p, s);
+        case IMPL_128x128:     return launch_gemm_wgrad<2, 2, 2, 2, 64, 1>(p, s);
+    }
 }
 
 extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw,
@@ -805,7 +858,7 @@ extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const flo
     memset(&p, 0, sizeof(p));
     p.a = a; p.b = b; p.a_ns = a_ns; p.b_ns = b_ns; p.M = M; p.N = Nc; p.gw = gw; p.F = F; p.HW = HW;
     p.total = (long)F * HW;
-    select_gemm_wgrad(p, (hipStream_t)stream);
+    launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
@@ -826,7 +879,7 @@ extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, i
     p.G = G; p.a = a[0]; p.b = b[0]; p.gw = gw[0];
     p.a_ns = a_ns; p.b_ns = b_ns; p.M = M; p.N = Nc; p.F = F; p.HW = HW;
     p.total = (long)F * HW;
-    select_gemm_wgrad(p, (hipStream_t)stream);
+    launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
@@ -834,21 +887,6 @@ extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, i
 // 3x3 weight gradient without the im2col buffer: gw[co][ci][tap] = sum_{frames,pixels} g[co][px] * in[ci][px + tap]
 // (pad 1), the shifted planes built while staging (rows of one image row, W % 8 == 0).  The output is the torch weight
 // layout [Cout][Cin][3][3] (the GEMM on rfn_im2col3x3_f32's buffer gives [Cout][tap][Cin] instead).
-static void select_wgrad_implicit(GemmWgradParams& p, hipStream_t s) {
-    static const int dma_off = getenv("RFN_WGRAD_DMA") ? atoi(getenv("RFN_WGRAD_DMA")) == 0 : 0;
-    // (grouped: the K gradients of a level together are the problem size)
-    if (p.M > 128 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 && !dma_off && p.HW % 32 == 0 && p.a_ns % 4 == 0)
-        launch_gemm_wgrad_dma_impl<4, 2, 2, 3>(p, s);   // 256 x 192, 8 waves, A through the DMA ring
-    else if (p.M > 128 && p.total >= 100000)
-        launch_gemm_wgrad<4, 2, 2, 3, 64, 1>(p, s);   // 256 x 192, 8 waves
-    else if (p.M <= 32 && p.G == 0)
-        // few output channels (the 16- / 32-channel blocks of the extractor / upscaler on 64x64 and 32x32 maps): one 32-row
-        // tile instead of 128 rows of which 16 are real (the clamped rows were 8x the loads and MFMAs of the gradient)
-        launch_gemm_wgrad<1, 4, 1, 2, 32, 1>(p, s);   // 32 x 256
-    else
-        launch_gemm_wgrad<2, 2, 2, 2, 64, 1>(p, s);   // 128 x 128
-}
-
 extern "C" int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
                                                  const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
                                                  rfn_stream_t stream) {
@@ -862,7 +900,7 @@ extern "C" int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int 
     p.a = g; p.a_ns = g_ns; p.M = Cout; p.b = in1; p.b_ns = in1_ns; p.b2 = C2 ? in2 : in1; p.b2_ns = C2 ? in2_ns : in1_ns;
     p.C1 = C1; p.C2 = C2; p.H = H; p.W = W; p.N = 9 * (C1 + C2); p.gw = gw; p.F = F; p.HW = H * W;
     p.total = (long)F * H * W;
-    select_wgrad_implicit(p, (hipStream_t)stream);
+    launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
@@ -887,7 +925,7 @@ extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, 
     p.a_ns = g_ns; p.M = Cout; p.b_ns = in1_ns; p.b2_ns = C2 ? in2_ns : in1_ns;
     p.C1 = C1; p.C2 = C2; p.H = H; p.W = W; p.N = 9 * (C1 + C2); p.F = F; p.HW = H * W;
     p.total = (long)F * H * W;
-    select_wgrad_implicit(p, (hipStream_t)stream);
+    launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }

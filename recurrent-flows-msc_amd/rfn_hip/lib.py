@@ -31,6 +31,7 @@ SIGNATURES = {
     "rfn_invconv_actnorm_rev_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_i, _c_i, _c_i, _c_s],
     "rfn_conv2d_fwd_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
                            _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
+    "rfn_conv2d_kernel_label_f32": [_c_i] * 5,
     "rfn_conv2d_fwd_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
                               _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
     "rfn_packed_weight_size_bf16x3": [_c_i, _c_i, _c_i],
@@ -39,6 +40,7 @@ SIGNATURES = {
     "rfn_pack_conv_weight_bf16x6": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_conv2d_fwd_bf16x6": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
                               _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
+    "rfn_conv2d_kernel_label_bf16x3": [_c_i] * 11,
     "rfn_conv2d_dgrad_act_rows_bf16x3": [_c_i, _c_i, _c_i, _c_i, _c_i, _c_i],
     "rfn_conv2d_dgrad_act_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_i, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i,
                                     _c_i, _c_i, _c_s],
@@ -76,10 +78,13 @@ SIGNATURES = {
     "rfn_gemm_wgrad_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_s],
     "rfn_conv3x3_wgrad_implicit_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i,
                                           _c_s],
+    "rfn_gemm_wgrad_kernel_label_bf16x3": [_c_i, _c_i, _c_l, _c_l, _c_i, _c_i, _c_i],
+    "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i],
     "rfn_im2col3x3_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
     "rfn_packed_weight_size": [_c_i, _c_i, _c_i],
     "rfn_pack_conv_weight_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_conv2d_wgrad_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_conv2d_wgrad_kernel_label_f32": [_c_i] * 5,
     "rfn_wgrad_finish_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_tap_gather_f32": [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_tap_scatter_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
@@ -127,7 +132,11 @@ SIGNATURES = {
     "rfn_moving_mnist_render_f32": [ctypes.c_void_p, _c_i, _c_f, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
                                     _c_l, _c_l, _c_l, _c_s],
 }
-_RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_packed_weight_size": ctypes.c_long,
+_RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": ctypes.c_char_p,
+             "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,
+             "rfn_gemm_wgrad_kernel_label_bf16x3": ctypes.c_char_p,
+             "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": ctypes.c_char_p,
+             "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_packed_weight_size": ctypes.c_long,
              "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,
              "rfn_smallmap_packed_size": ctypes.c_long,
              "rfn_coupling_po_packed_bytes": ctypes.c_long, "rfn_coupling_po_mask_floats": ctypes.c_long, "rfn_glow_shell_fwd_ld_floats": ctypes.c_long,

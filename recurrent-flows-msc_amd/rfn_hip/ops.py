@@ -6,6 +6,7 @@ time-batches B*(T-1) frames into one call).
 """
 import collections
 import ctypes
+import functools
 
 import torch
 
@@ -63,6 +64,14 @@ def squeeze2d_raw(x, undo=False):
     L.call("rfn_squeeze2d_f32", xp, _l(xns), yp, _l(yns), _i(N), _i(C), _i(H), _i(W), _i(1 if undo else 0),
            meta=_shell("squeeze2d", x, 2))
     return y
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_label(query, *args):
+    """the kernel instantiation the library launches for the integer arguments `args` of its host-only query `query`
+    (the *_kernel_label_* functions of include/rfn_hip.h, answered by the function the launcher itself switches on): the
+    label of a launch's profiling metadata.  Memoised: the library reads its selector knobs once per process."""
+    return getattr(L.load(), query)(*args).decode()
 
 
 def _shell(name, t, n_tensors):
@@ -220,7 +229,8 @@ def conv2d_dgrad_act(gin, wpk_flip, y, logs, act, Cout, ks, arena=None):
     sums = _zeros(arena, 2, Cout, device=gin.device)
     L.call("rfn_conv2d_dgrad_act_bf16x3", gp, _l(gns), _i(Cin), L.dev(wpk_flip), yp, _l(yns), L.dev(logs), _i(act), up,
            _l(uns), L.dev(sums), _i(Cout), _i(N), _i(H), _i(W), _i(ks),
-           meta=("conv", conv_b3_kernel_name(Cout, ks, N * H * W, Cin, (H, W), True, True) + "+actbwd", 2.0 * N * H * W * Cin * Cout * ks * ks,
+           meta=("conv", kernel_label("rfn_conv2d_kernel_label_bf16x3", 2, ks, Cin, 0, Cout, Cout, 0, 4, N, H, W) + "+actbwd",
+                 2.0 * N * H * W * Cin * Cout * ks * ks,
                  "N%d %d->%d %dx%d k%d dgrad+actbwd" % (N, Cin, Cout, H, W, ks),
                  4.0 * (N * H * W * (Cin + 2 * Cout) + Cin * Cout * ks * ks)))
     return gu, sums[0], sums[1]
@@ -399,11 +409,11 @@ def conv2d_raw(in1, in2, wpk, Cout, ks, ep_mode=0, p0=None, p1=None, act=0, out1
     o1p, o1ns = L.frames(out1, "out1")
     o2p, o2ns = (None, 0) if out2 is None else L.frames(out2, "out2")
     prec = prec if prec is not None else ("bf16x3" if bwd_b3() else "f32")
-    b3 = prec == "bf16x3"
     fn = {"bf16x3": "rfn_conv2d_fwd_bf16x3", "bf16x6": "rfn_conv2d_fwd_bf16x6", "f32": "rfn_conv2d_fwd_f32"}[prec]
-    kname = (_fwd_b3_name(Cout, ks, N, H, W, C1, C2, cout_split, acc1, acc2, ep_mode) if b3 else
-             conv_b3_kernel_name(Cout, ks, N * H * W, None, None, False) + " x6" if prec == "bf16x6" else
-             conv_kernel_name(Cout, ks, N * H * W))
+    x6 = prec == "bf16x6"
+    kname = (kernel_label("rfn_conv2d_kernel_label_f32", ks, Cout, N, H, W) if prec == "f32" else
+             kernel_label("rfn_conv2d_kernel_label_bf16x3", 3 if x6 else 2, ks, C1, C2, Cout, cout_split, 1 if acc1 else 0,
+                          ep_mode, N, H, W) + (" x6" if x6 else ""))
     L.call(fn, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2),
            L.dev(wpk), o1p, _l(o1ns), o2p,
            _l(o2ns), _i(Cout), _i(cout_split), _i(1 if acc1 else 0), _i(1 if acc2 else 0), _i(N), _i(H), _i(W), _i(ks),
@@ -416,69 +426,6 @@ def conv2d_raw(in1, in2, wpk, Cout, ks, ep_mode=0, p0=None, p1=None, act=0, out1
     return out1
 
 
-def _fwd_b3_name(Cout, ks, N, H, W, C1, C2, cout_split, acc1, acc2, ep_mode):
-    plain = cout_split == Cout and not acc1 and not acc2 and ep_mode <= 3
-    if ks == 1:
-        return conv_b3_kernel_name(Cout, ks, N * H * W, (C1 + C2) if C2 == 0 else None)
-    return conv_b3_kernel_name(Cout, ks, N * H * W, C1 + C2, (H, W), plain, False)
-
-
-def conv_b3_kernel_name(Cout, ks, npix=1 << 30, Cin=None, hw=None, plain=True, actbwd=False):
-    """the template instantiation rfn_conv2d_fwd_bf16x3 dispatches to (mirrors csrc/conv_bf16x3.hip) -- for profiling
-    labels.  Cin = total input channels when the input is ONE tensor (else None); hw = (H, W); plain = single output
-    tensor, no accumulate."""
-    few = npix * ((Cout + 127) // 128) < 256 * 128
-    ws_on = os.environ.get("RFN_CONV_WS") != "0"
-    if ks == 3 and ws_on and hw is not None and plain and Cout % 256 == 0 and npix >= 64 * 256:
-        H, W = hw
-        cin = Cin if isinstance(Cin, int) else None
-        # at least one TW x TH tile per frame (TW = min(W, 32), TH = 32 * PT / TW): a 1 x W map with PT = 2 has none
-        PT = 2 if (actbwd or (cin is not None and cin <= 24)) else 1
-        if H & (H - 1) == 0 and W & (W - 1) == 0 and W >= 8 and H * W >= 64 and H >= 32 * PT // min(W, 32):
-            if actbwd and cin is not None and cin <= 8:
-                return "conv3x3_ws_kernel<1,2,0>"
-            if not actbwd and Cin is not None and Cin <= 40:
-                return "conv3x3_ws_kernel<%s>" % ("3,2,1" if Cin <= 24 else "5,1,1")
-    if ks == 3:
-        cfg = "1,4,1,1" if Cout <= 32 else ("2,2,1,1" if few else "2,2,1,2")
-        return "conv_b3_kernel<3,%s,16>" % cfg
-    if ks == 1 and Cin is not None and Cout % 256 == 0 and 128 < Cin <= 256 and npix >= 64 * 256 and os.environ.get("RFN_CONV_WS") != "0":
-        return "conv1x1_ws_kernel<16>"
-    cfg = "1,4,1,1" if Cout <= 32 else ("2,2,1,1" if (few or Cout <= 64) else ("2,2,2,2" if Cout <= 128 else "4,1,2,2"))
-    return "conv_b3_kernel<1,%s,32>" % cfg
-
-
-def conv_kernel_name(Cout, ks, npix=1 << 30):
-    """the template instantiation rfn_conv2d_fwd_f32 dispatches to (mirrors csrc/conv.hip) — for profiling labels"""
-    few = Cout > 64 and npix * ((Cout + 127) // 128) < 256 * 128
-    cfg = "1,4,1,2" if Cout <= 32 else ("1,4,2,1" if Cout <= 64 else ("4,1,1,1" if few else
-                                                                     ("4,1,2,2" if ks == 1 else "2,2,2,2")))
-    return "conv_mfma_kernel<%d,%s,%d>" % (ks, cfg, 8 if ks == 3 else 32)
-
-
-def wgrad_kernel_name(Cout, Cin, ks, HW):
-    if ks == 3:
-        cfg = "4,1,1,1" if Cin <= 32 else ("1,4,1,1" if Cout <= 32 else "2,2,1,1")
-    else:
-        cfg = "4,1,2,1" if Cin <= 32 else ("1,4,1,2" if Cout <= 32 else "2,2,2,2")
-    if ks == 1 and 32 < Cout <= 64 and Cin > 32:
-        cfg = "1,4,2,2"
-    return "wgrad_mfma_kernel<%d,%s,64>" % (ks, cfg)
-
-
-def _gemm_wgrad_name(M, Nc, total, HW=0, ans=0, bns=0, G=1):
-    """mirror of the kernel / tile choice in rfn_gemm_wgrad_bf16x3 (csrc/wgrad_bf16x3.hip), for profiling labels only"""
-    if (os.environ.get("RFN_WGRAD_DMA", "1") != "0" and not os.environ.get("RFN_WGRAD_VARIANT") and total * G >= 100000
-            and total >= 2048 and HW % 32 == 0 and ans % 4 == 0 and bns % 4 == 0 and Nc > 128 and Nc % 256 == 0
-            and (M >= 192 or M <= 64)):
-        return "gemm_wgrad_dma_kernel<%s>" % ("2,4,4,2,32,2" if M > 128 else "1,8,2,1,32,3")
-    if M > 128 and Nc > 128 and total >= 100000:
-        cfg = "4,2,2,3,64" if -(-Nc // 192) * 192 < -(-Nc // 256) * 256 else "2,4,4,2,64"
-    else:
-        cfg = "1,4,2,2,32" if M <= 64 else ("4,1,2,2,32" if Nc <= 64 else "2,2,2,2,64")
-    return "gemm_wgrad_b3_kernel<%s>" % cfg
-
-
 def gemm_wgrad(a, b, M, Nc, arena=None):
     """gw[M][Nc] = Σ_{frames,pixels} a[f,m,p] b[f,n,p] on the split-precision MFMA GEMM (rfn_gemm_wgrad_bf16x3)."""
     F_, HW = int(a.shape[0]), _hw(a)
@@ -486,7 +433,7 @@ def gemm_wgrad(a, b, M, Nc, arena=None):
     bp, bns = L.frames(b, "b")
     gw = _zeros(arena, M, Nc, device=a.device)
     L.call("rfn_gemm_wgrad_bf16x3", ap, _l(ans), _i(M), bp, _l(bns), _i(Nc), L.dev(gw), _i(F_), _i(HW),
-           meta=("wgrad", _gemm_wgrad_name(M, Nc, F_ * HW, HW, ans, bns),
+           meta=("wgrad", kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, ans, bns, 0, F_, HW),
                  2.0 * F_ * HW * M * Nc, "F%d %dx%d HW%d" % (F_, M, Nc, HW), 4.0 * (F_ * HW * (M + Nc) + M * Nc)))
     return gw
 
@@ -506,12 +453,9 @@ def conv2d_wgrad_b3(in1, in2, g, Cout, ks, arena=None):
         i2p, i2ns = (None, 0) if in2 is None else L.frames(in2, "in2")
         gp, gns = L.frames(g, "g")
         gw = _zeros(arena, Cout, 9 * Cin, device=in1.device)
-        big = Cout > 128 and N * H * W >= 100000
-        dma = (big and (H * W) % 32 == 0 and gns % 4 == 0 and os.environ.get("RFN_WGRAD_DMA", "1") != "0")
         L.call("rfn_conv3x3_wgrad_implicit_bf16x3", gp, _l(gns), _i(Cout), i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2),
                L.dev(gw), _i(N), _i(H), _i(W),
-               meta=("wgrad", "gemm_wgrad_dma_impl_kernel<4,2,2,3>" if dma else
-                     "gemm_wgrad_b3_kernel<%s,1>" % ("4,2,2,3,64" if big else ("1,4,1,2,32" if Cout <= 32 else "2,2,2,2,64")),
+               meta=("wgrad", kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, gns, 0, N, H, W),
                      2.0 * N * H * W * Cout * 9 * Cin, "F%d %dx%d HW%d implicit3x3" % (N, Cout, 9 * Cin, H * W),
                      4.0 * (N * H * W * (Cout + Cin) + Cout * 9 * Cin)))
         return gw.view(Cout, Cin, 3, 3)  # rows of the implicit operand are (ci, tap): already the torch layout
@@ -540,7 +484,8 @@ def gemm_wgrad_grouped(a_list, b_list, M, Nc, arena=None):
     pa, pb = L.ptr_array(a_list, "a"), L.ptr_array(b_list, "b")
     pg = L.ptr_array([gw[g] for g in range(G)], "gw")
     L.call("rfn_gemm_wgrad_grouped_bf16x3", pa, _l(ans), _i(M), pb, _l(bns), _i(Nc), pg, _i(G), _i(F_), _i(HW),
-           meta=("wgrad", _gemm_wgrad_name(M, Nc, F_ * HW, HW, ans, bns, G).replace("<", "<grouped "),
+           meta=("wgrad", kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, ans, bns, G, F_,
+                                       HW).replace("<", "<grouped "),
                  2.0 * G * F_ * HW * M * Nc, "G%d F%d %dx%d HW%d" % (G, F_, M, Nc, HW),
                  4.0 * G * (F_ * HW * (M + Nc) + M * Nc)))
     return gw
@@ -573,12 +518,8 @@ def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_sta
         pw = L.ptr_array([gw[i] for i in range(G)], "gw")
         L.call("rfn_conv3x3_wgrad_implicit_grouped_bf16x3", pg, _l(gns), _i(Cout), p1, _l(i1ns), _i(C1), p2, _l(i2ns),
                _i(C2), pw, _i(G), _i(N), _i(H), _i(W),
-               meta=("wgrad", "gemm_wgrad_dma_impl_kernel<grouped 4,2,2,3>" if (
-                         Cout > 128 and G * N * H * W >= 100000 and N * H * W >= 2048 and (H * W) % 32 == 0 and gns % 4 == 0
-                         and os.environ.get("RFN_WGRAD_DMA", "1") != "0") else
-                     # (a group never takes the 32-row tiling: p.G == 0 is part of its predicate)
-                     "gemm_wgrad_b3_kernel<grouped %s,1>" % ("4,2,2,3,64" if Cout > 128 and N * H * W >= 100000
-                                                             else "2,2,2,2,64"),
+               meta=("wgrad", kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, gns, G, N, H,
+                                           W).replace("<", "<grouped "),
                      2.0 * G * N * H * W * Cout * 9 * Cin,
                      "G%d F%d %dx%d HW%d implicit3x3" % (G, N, Cout, 9 * Cin, H * W),
                      4.0 * G * (N * H * W * (Cout + Cin) + Cout * 9 * Cin)))
@@ -628,7 +569,8 @@ def conv2d_wgrad(in1, in2, g, Cout, ks, arena=None):
     gwt = _zeros(arena, ks * ks, Cout, Cin, device=in1.device)
     L.call("rfn_conv2d_wgrad_f32", i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), gp, _l(gns), _i(Cout), L.dev(gwt),
            _i(N), _i(H), _i(W), _i(ks),
-           meta=("wgrad", wgrad_kernel_name(Cout, Cin, ks, H * W), 2.0 * N * H * W * Cin * Cout * ks * ks,
+           meta=("wgrad", kernel_label("rfn_conv2d_wgrad_kernel_label_f32", ks, Cin, Cout, H, W),
+                 2.0 * N * H * W * Cin * Cout * ks * ks,
                  "N%d %d->%d %dx%d k%d" % (N, Cin, Cout, H, W, ks), 4.0 * (N * H * W * (Cin + Cout) + Cin * Cout * ks * ks)))
     if ks == 1:
         return gwt.view(Cout, Cin, 1, 1)  # tap-major == torch layout when there is a single tap

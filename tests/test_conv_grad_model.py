@@ -19,9 +19,9 @@ Per case:
   magnitude     data gradients: the input times 2^k, k in {-40, -12, +12}, gives the output times 2^k BIT FOR BIT
                 (bf16 keeps the fp32 exponent; the kernels add in a fixed order).  Weight gradients end in float atomics
                 and are exempt; they are held to the model tolerance at k = -40.
-  route         the label of every launch equals the table entry written here from the C++ predicates
-                (dispatch_conv_b3, conv1x1_ws_eligible, conv3x3_ws_eligible, select_gemm_wgrad, select_wgrad_implicit);
-                the set of table entries equals ROUTES.  profiles/conv_grad_model_kernel_symbols.txt is the list of
+  route         the label of every launch (the library's own answer: rfn_hip.ops.kernel_label) equals the table entry
+                written here from the C++ choices (choose_conv_b3, choose_gemm_wgrad, choose_wgrad_implicit); the set of
+                table entries equals ROUTES; tests/test_kernel_routes_host.py asks the same without a device.  profiles/conv_grad_model_kernel_symbols.txt is the list of
                 kernel symbols a traced run of this module launched: the device-side confirmation of the table.
 
 Measured on an MI355X (max over the cases of a route; e_abs of bf16x3 vs the model / bf16x3 vs fp64 / fp32 kernel vs fp64):
@@ -186,7 +186,7 @@ WS1 = "conv1x1_ws_kernel<16>"
 WS3A, WS3B = "conv3x3_ws_kernel<3,2,1>", "conv3x3_ws_kernel<5,1,1>"
 
 # name: (N, C1, C2, Cout, H, W, ks, flip, label).  flip: the weight is packed as a data gradient's (transposed, taps
-# mirrored), i.e. the call is the data gradient of a conv Cout -> C1 + C2.  The label is what dispatch_conv_b3 must
+# mirrored), i.e. the call is the data gradient of a conv Cout -> C1 + C2.  The label is what choose_conv_b3 must
 # choose: few_px = N*H*W*ceil(Cout/128) < 32768; 1x1 ws: one source, Cout % 256 == 0, 128 < Cin <= 256, >= 16384 pixels;
 # 3x3 ws: Cout % 256 == 0, H and W powers of two, W >= 8, H*W >= 64, H >= TH, >= 16384 pixels, Cin <= 24 -> <3,2>
 # (64-pixel tiles, TH = 64 / min(W, 32)), Cin <= 40 -> <5,1> (32-pixel tiles, TH = 32 / min(W, 32)).
@@ -413,7 +413,7 @@ DMA, B3 = "gemm_wgrad_dma_kernel<%s>", "gemm_wgrad_b3_kernel<%s>"
 GEMM = ("rfn_gemm_wgrad_bf16x3", "rfn_gemm_wgrad_grouped_bf16x3")
 
 # plain GEMM gradients gw[M][Nc] = Σ a b^T (K.gemm_wgrad / K.gemm_wgrad_grouped).  name: (G, M, Nc, F, H, W, view, tile).
-# view: the operands are channel slices of wider tensors (a_ns = (M + 8) * HW, b_ns = (Nc + 4) * HW).  select_gemm_wgrad:
+# view: the operands are channel slices of wider tensors (a_ns = (M + 8) * HW, b_ns = (Nc + 4) * HW).  choose_gemm_wgrad:
 # the DMA ring needs HW % 32 == 0, G * F*HW >= 100000, F*HW >= 2048, Nc % 256 == 0 and M >= 192 (256x256) or M <= 64
 # (64x256); `big` = M > 128, Nc > 128, F*HW >= 100000 -> 256x192 when ceil(Nc/192)*192 < ceil(Nc/256)*256, else 256x256;
 # then M <= 64 -> 64x256, Nc <= 64 -> 256x64, else 128x128.  6x6 maps: HW = 36 keeps the DMA ring out, F*HW is not a
@@ -438,7 +438,7 @@ GEMM_CASES = {
 IMPL = ("rfn_conv3x3_wgrad_implicit_bf16x3", "rfn_conv3x3_wgrad_implicit_grouped_bf16x3")
 # convolution weight gradients (K.conv2d_wgrad / K.conv2d_wgrad_grouped).  name: (G, N, C1, C2, Cout, H, W, ks, view,
 # launches).  view: in1 is a channel slice z[:, :C1] of a tensor twice as wide.  3x3 with Cin <= Cout and W % 8 == 0 is
-# implicit (select_wgrad_implicit): Cout > 128, G*N*HW >= 100000, N*HW >= 2048, HW % 32 == 0 -> the DMA ring kernel;
+# implicit (choose_wgrad_implicit): Cout > 128, G*N*HW >= 100000, N*HW >= 2048, HW % 32 == 0 -> the DMA ring kernel;
 # Cout > 128, N*HW >= 100000 -> 256x192; Cout <= 32 and not grouped -> 32x256; else 128x128.  W % 8 != 0 -> im2col (vector
 # kernel when W % 4 == 0, scalar otherwise) + GEMM; Cin > Cout -> tap scatter + GEMM; H*W % 4 != 0 -> the fp32 kernel.
 WGRAD_CASES = {
@@ -577,20 +577,20 @@ def test_wgrad_fp32_route_vs_fp64(K, launches):
 
 # ------------------------------------------------------------------------------------------------ 3. the route set
 ROUTES = {
-    # dispatch_conv_b3 at npl == 2
+    # choose_conv_b3 at npl == 2
     G3 % "1,4,1,1", G3 % "2,2,1,1", G3 % "2,2,1,2", G1 % "1,4,1,1", G1 % "2,2,1,1", G1 % "2,2,2,2", G1 % "4,1,2,2",
     WS1, WS3A, WS3B,
     # rfn_conv2d_dgrad_act_bf16x3 (ep_mode 4)
     "conv3x3_ws_kernel<1,2,0>+actbwd", WS1 + "+actbwd", G3 % "2,2,1,1" + "+actbwd", G3 % "2,2,1,2" + "+actbwd",
     G1 % "2,2,1,1" + "+actbwd",
     "dgrad_small_kernel",
-    # select_gemm_wgrad, single and grouped (the two RFN_WGRAD_VARIANT tilings are read from the environment once per
+    # choose_gemm_wgrad, single and grouped (the two RFN_WGRAD_VARIANT tilings are read from the environment once per
     # process and are not selections of the shipped configuration)
     DMA % "2,4,4,2,32,2", DMA % "1,8,2,1,32,3", B3 % "4,2,2,3,64", B3 % "2,4,4,2,64", B3 % "1,4,2,2,32",
     B3 % "4,1,2,2,32", B3 % "2,2,2,2,64",
     DMA % "grouped 2,4,4,2,32,2", DMA % "grouped 1,8,2,1,32,3", B3 % "grouped 4,2,2,3,64", B3 % "grouped 2,4,4,2,64",
     B3 % "grouped 1,4,2,2,32", B3 % "grouped 4,1,2,2,32", B3 % "grouped 2,2,2,2,64",
-    # select_wgrad_implicit, single and grouped (a group never takes the 32-row tiling)
+    # choose_wgrad_implicit, single and grouped (a group never takes the 32-row tiling)
     "gemm_wgrad_dma_impl_kernel<4,2,2,3>", B3 % "4,2,2,3,64,1", B3 % "1,4,1,2,32,1", B3 % "2,2,2,2,64,1",
     "gemm_wgrad_dma_impl_kernel<grouped 4,2,2,3>", B3 % "grouped 4,2,2,3,64,1", B3 % "grouped 2,2,2,2,64,1",
     # operand expansion and the fp32 weight gradient

@@ -106,7 +106,7 @@ FWD_CASES = [
 
 def _x6_label(K, case):
     N, C1, C2, Cout, H, W, ks = case
-    return K.conv_b3_kernel_name(Cout, ks, N * H * W, None, None, False)
+    return K.kernel_label("rfn_conv2d_kernel_label_bf16x3", 3, ks, C1, C2, Cout, Cout, 0, 0, N, H, W)
 
 
 def test_forward_cases_reach_every_bf16x6_instantiation(K):

@@ -1,0 +1,109 @@
+"""CPU-only: the kernel the library would launch, asked of the library itself.
+
+The *_kernel_label_* queries of include/rfn_hip.h are answered by the C++ functions the launchers switch on
+(choose_conv_b3, choose_conv_f32, choose_wgrad_f32, choose_gemm_wgrad, choose_wgrad_implicit) and need no device, so
+the route tables that the GPU tests assert launch by launch (tests/test_conv_grad_model.py, test_conv_split_precision.py)
+are checked here on any machine, through the same helper (rfn_hip.ops.kernel_label) and with the same arguments and
+decorations (" x6", "+actbwd", "grouped ") the launch wrappers of rfn_hip/ops.py use."""
+import pytest
+
+from tests.test_conv_grad_model import ACTBWD_CASES, CONV_CASES, GEMM_CASES, WGRAD_CASES
+from tests.test_conv_split_precision import FWD_CASES, X6_KERNELS
+
+B3, F32 = "rfn_conv2d_kernel_label_bf16x3", "rfn_conv2d_kernel_label_f32"
+
+
+@pytest.fixture(scope="module")
+def K():
+    from rfn_hip import ops
+    return ops
+
+
+@pytest.mark.parametrize("name", list(CONV_CASES))
+def test_conv_cases_take_their_table_route(K, name):
+    N, C1, C2, Cout, H, W, ks, flip, label = CONV_CASES[name]
+    assert K.kernel_label(B3, 2, ks, C1, C2, Cout, Cout, 0, 0, N, H, W) == label
+
+
+@pytest.mark.parametrize("acc1", [0, 1])
+@pytest.mark.parametrize("HW", [(16, 16), (12, 12)])
+def test_conv1x1_ws_takes_split_and_accumulating_outputs(K, HW, acc1):
+    """the shapes of test_conv1x1_ws_views_vs_model"""
+    H, W = HW
+    assert K.kernel_label(B3, 2, 1, 200, 0, 256, 100, acc1, 0, 16384 // (H * W) + 7, H, W) == "conv1x1_ws_kernel<16>"
+
+
+@pytest.mark.parametrize("name", list(ACTBWD_CASES))
+def test_actbwd_cases_take_their_table_route(K, name):
+    N, Cmid, Cnext, H, W, ks, act, label = ACTBWD_CASES[name]
+    assert K.kernel_label(B3, 2, ks, Cnext, 0, Cmid, Cmid, 0, 4, N, H, W) + "+actbwd" == label
+
+
+# rfn_conv2d_dgrad_act_rows_bf16x3 for the ACTBWD_CASES shapes, as returned by the build that still derived the generic
+# tile sizes by hand beside dispatch_conv_b3
+ACTBWD_ROWS = {"ws3_16x16": 256, "ws3_16x32": 256, "ws3_4x16": 256, "ws1_16x16": 256, "g3_8x8": 6, "g3_4x16": 10,
+               "g3_1x64": 300, "g1_4x4": 4}
+
+
+def test_dgrad_act_rows_are_those_of_the_chosen_route():
+    from rfn_hip import lib
+    assert set(ACTBWD_ROWS) == set(ACTBWD_CASES)
+    for name, (N, Cmid, Cnext, H, W, ks, act, label) in ACTBWD_CASES.items():
+        assert lib.load().rfn_conv2d_dgrad_act_rows_bf16x3(N, H, W, ks, Cmid, Cnext) == ACTBWD_ROWS[name], name
+
+
+def test_bf16x6_cases_take_the_generic_routes(K):
+    labels = {K.kernel_label(B3, 3, ks, C1, C2, Cout, Cout, 0, 0, N, H, W) for N, C1, C2, Cout, H, W, ks in FWD_CASES}
+    assert labels == X6_KERNELS
+    # three planes never take a weight-stationary kernel, whatever the shape
+    assert K.kernel_label(B3, 3, 1, 256, 0, 256, 256, 0, 0, 70, 16, 16) == "conv_b3_kernel<1,4,1,2,2,32>"
+    assert K.kernel_label(B3, 3, 3, 8, 0, 256, 256, 0, 0, 70, 16, 16) == "conv_b3_kernel<3,2,2,1,2,16>"
+
+
+@pytest.mark.parametrize("name", list(GEMM_CASES))
+def test_gemm_cases_take_their_table_route(K, name):
+    G, M, Nc, F_, H, W, view, tile = GEMM_CASES[name]
+    HW = H * W
+    a_ns, b_ns = (M + (8 if view else 0)) * HW, (Nc + (4 if view else 0)) * HW
+    label = K.kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, a_ns, b_ns, G, F_, HW)
+    assert (label.replace("<", "<grouped ") if G else label) == tile
+
+
+def _wgrad_labels(K, G, N, C1, C2, Cout, H, W, ks):
+    """the labelled launches of K.conv2d_wgrad / K.conv2d_wgrad_grouped for one case: its operand choices, then the
+    queries (dense gradient; the GEMM operands of the 3x3 forms are dense expansions)"""
+    Cin, HW = C1 + C2, H * W
+    grouped = (lambda s: s.replace("<", "<grouped ")) if G else (lambda s: s)
+    gemm = "rfn_gemm_wgrad_grouped_bf16x3" if G else "rfn_gemm_wgrad_bf16x3"
+    if HW % 4 != 0:
+        assert not G
+        return [("rfn_conv2d_wgrad_f32", K.kernel_label("rfn_conv2d_wgrad_kernel_label_f32", ks, Cin, Cout, H, W)),
+                ("rfn_wgrad_finish_f32", "wgrad_finish")]
+    if ks == 3 and Cin <= Cout and W % 8 == 0:
+        impl = "rfn_conv3x3_wgrad_implicit_grouped_bf16x3" if G else "rfn_conv3x3_wgrad_implicit_bf16x3"
+        return [(impl, grouped(K.kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, Cout * HW, G, N, H, W)))]
+    if ks == 1:      # a = the gradient, b = the input (C2 == 0 in the table: in1 itself, a slice when `view`)
+        M, Nc, pre = Cout, Cin, []
+    elif Cin <= Cout:
+        M, Nc, pre = Cout, 9 * Cin, [("rfn_im2col3x3_f32", "im2col3x3")] * max(G, 1)
+    else:
+        M, Nc, pre = 9 * Cout, Cin, [("rfn_tap_scatter_f32", "tap_scatter")]
+    return pre + [(gemm, grouped(K.kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, M * HW, Nc * HW, G, N, HW)))]
+
+
+@pytest.mark.parametrize("name", list(WGRAD_CASES))
+def test_wgrad_cases_take_their_table_routes(K, name):
+    G, N, C1, C2, Cout, H, W, ks, view, want = WGRAD_CASES[name]
+    assert ks == 3 and C1 + C2 <= Cout or not (view and C2 == 0)   # (_wgrad_labels: no sliced GEMM operand in the table)
+    assert _wgrad_labels(K, G, N, C1, C2, Cout, H, W, ks) == want
+
+
+def test_fp32_1x1_between_65_and_128_outputs_takes_the_128_row_block(K):
+    """rfn_conv2d_fwd_f32, 1x1, 64 < Cout <= 128, not few-pixel: one 128-row block (case 6 of its former switch), not the
+    256-row tiling that the Python copy of this ladder used to report"""
+    assert K.kernel_label(F32, 1, 128, 300, 12, 12) == "conv_mfma_kernel<1,2,2,2,2,32>"
+    assert K.kernel_label(F32, 1, 65, 300, 12, 12) == "conv_mfma_kernel<1,2,2,2,2,32>"
+    assert K.kernel_label(F32, 1, 129, 300, 12, 12) == "conv_mfma_kernel<1,4,1,2,2,32>"
+    assert K.kernel_label(F32, 1, 128, 7, 6, 6) == "conv_mfma_kernel<1,4,1,1,1,32>"     # few pixels
+    assert K.kernel_label(F32, 1, 64, 300, 12, 12) == "conv_mfma_kernel<1,1,4,2,1,32>"
+    assert K.kernel_label(F32, 3, 128, 300, 12, 12) == "conv_mfma_kernel<3,2,2,2,2,8>"

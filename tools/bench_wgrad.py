@@ -21,7 +21,8 @@ def run(F_, M, Nc, S, reps=10):
     dt = (time.perf_counter() - t0) / reps
     by = 4.0 * F_ * S * S * (M + Nc)
     print("F%d %dx%d %dx%d  %s  %.3f ms  %.2f TB/s  %.0f TFLOP/s" % (
-        F_, M, Nc, S, S, K._gemm_wgrad_name(M, Nc, F_ * S * S, S * S).split("<")[0], dt * 1e3, by / dt / 1e12,
+        F_, M, Nc, S, S, K.kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, M * S * S, Nc * S * S, 0, F_,
+                                        S * S).split("<")[0], dt * 1e3, by / dt / 1e12,
         2.0 * F_ * S * S * M * Nc / dt / 1e12), flush=True)
 
 
