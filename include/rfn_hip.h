@@ -523,6 +523,19 @@ int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long
                                 int num_digits, int step_length, int deterministic, long seed, long split,
                                 long first_id, rfn_stream_t stream);
 
+/* ---- clips of a device-resident frame store as float32 batches  (the per-item work of the file-backed datasets,
+ * data_generators/bair_push.py:66-109 and data_generators/kth.py:34-65, and the DataLoader collation of
+ * RFN/trainer.py:132-161, for a whole batch in one launch).  store: uint8 [n_frames, H, W, Cs] device tensor,
+ * channel-interleaved as an image decoder leaves it, Cs in {1, 3}; first: int64 [B] device tensor, the store index of
+ * each clip's first frame.  Writes out: fp32 [B, T, C, H, W],
+ *   out[b,t,c,y,x] = float32(store[first[b]+t, y, x, c']) / float32(255)   (the correctly rounded float32 quotient),
+ * c' = c when C == Cs, c' = 0 when Cs == 1 (C in {1, 3} copies); any other (C, Cs) is an argument error.  A clip with
+ * first[b] < 0 or first[b] + T > n_frames reads nothing: all its T frames are NaN.  16-byte loads and float4 stores
+ * when H*W is a multiple of 4, H*W*Cs a multiple of 16 and both bases are 16-byte aligned; single pixels otherwise.
+ * B == 0 returns 0 without a launch.  One launch. */
+int rfn_clip_gather_u8_f32(const void* store, long n_frames, const void* first, float* out, int B, int T, int C, int Cs,
+                           int H, int W, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,9 @@
 """Solver — training driver with the reference's surface (RFN/trainer.py of the reference): `Solver(args).build();
 .train(); .load(ckpt)`, `preprocess`, `compute_loss` (bits/dim bookkeeping), β annealing, linear LR decay, checkpoint
-dict layout.  Plotting (matplotlib PNG panels) and the BAIR / KTH datasets are outside the hot-path scope; a synthetic
-SM-MNIST-shaped loader is built in (`--synthetic_data`), and Stochastic Moving MNIST is rendered on the GPU from local
-MNIST files (`--choose_data mnist`, data_generators/moving_mnist.py).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
+dict layout.  Plotting (matplotlib PNG panels) is outside the hot-path scope; a synthetic SM-MNIST-shaped loader is
+built in (`--synthetic_data`); otherwise the dataset lives on the GPU: Stochastic Moving MNIST is rendered from local
+MNIST files (`--choose_data mnist`, data_generators/moving_mnist.py), BAIR push and KTH clips are gathered from their
+packed frames (`bair`, `kth`; data_generators/clips.py).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
 import math
 import os
 
@@ -93,8 +94,7 @@ class Solver(object):
         if not getattr(self.args, "synthetic_data", False):
             if self.choose_data == "mnist":
                 return self.create_mnist_loaders()
-            raise RuntimeError("the file-backed datasets of the reference (BAIR, KTH) are outside this "
-                               "implementation's scope; pass --synthetic_data for SM-MNIST-shaped synthetic video")
+            return self.create_clip_loaders()
         c = self.args.x_dim[1]
         mk = lambda seed: SyntheticMovingMNIST(seq_len=self.n_frames, image_size=self.image_size,
                                                digit_size=self.digit_size, num_digits=self.num_digits,
@@ -124,6 +124,47 @@ class Solver(object):
         testset = mk(False)
         return (MovingMNISTLoader(trainset, self.batch_size, self.rank, self.world),
                 MovingMNISTLoader(testset, self.batch_size, self.rank, self.world))
+
+    def create_clip_loaders(self):
+        """RFN/trainer.py:132-161: BAIR push (`<root>/{train,test}/traj_*/*/*.png`) or KTH (`<root>/processed/...`) from
+        --data_root (default, as the reference: bair_robot_data/processed_data/ or kth_data under the working
+        directory).  The frames of each split are packed once into a device-resident store (kept under --data_cache
+        while the files match) and every batch is one launch of the clip-gather kernel.  x_dim must agree with the
+        frames: 3 channels for BAIR, 1 or 3 (copies) for KTH, H = W = the stored side.  With --use_validation_set
+        the train split is its first 500 sequences, as the reference's Subset."""
+        from data_generators import KTH, ClipLoader, PushDataset
+        bair = self.choose_data == "bair"
+        root = getattr(self.args, "data_root", None)   # (Namespaces saved before these flags existed)
+        cache_dir = getattr(self.args, "data_cache", None)
+        seed = getattr(self.args, "data_seed", 0)
+        if root is None:
+            root = os.path.join(os.path.abspath(os.getcwd()), "bair_robot_data/processed_data/" if bair else "kth_data")
+            if not os.path.isdir(root):
+                raise RuntimeError("%s data not found at %s (nothing is downloaded): pass --data_root, or "
+                                   "--synthetic_data for SM-MNIST-shaped synthetic video" %
+                                   ("BAIR" if bair else "KTH", root))
+        elif not os.path.isdir(root):
+            raise FileNotFoundError("--data_root %s is not a directory" % root)
+        _, c, h, w = self.args.x_dim
+        if h != w or c not in ((3,) if bair else (1, 3)):
+            raise ValueError("%s frames are square with %s channels; x_dim asks for %dx%dx%d" %
+                             ("BAIR" if bair else "KTH", "3" if bair else "1 (or 3 copies)", c, h, w))
+        if not bair and h != self.image_size:
+            raise ValueError("KTH frames are image_size = %d wide; x_dim asks for %d" % (self.image_size, h))
+        length = 500 if self.use_validation_set else None
+        cache = lambda name: None if cache_dir is None else os.path.join(cache_dir, "%s_%dx%d" % (name, h, w))
+        if bair:
+            mk = lambda split, length=None: PushDataset(split=split, dataset_dir=root, seq_len=self.n_frames, img_side=h,
+                                                        seed=seed, device=self.device, cache=cache("bair_" + split),
+                                                        length=length)
+            trainset, testset = mk("train", length), mk("test")
+        else:
+            mk = lambda train, length=None: KTH(train=train, data_root=root, seq_len=self.n_frames, image_size=h,
+                                                seed=seed, device=self.device, channels=c, length=length,
+                                                cache=cache("kth_" + ("train" if train else "test")))
+            trainset, testset = mk(True, length), mk(False)
+        return (ClipLoader(trainset, self.batch_size, self.rank, self.world),
+                ClipLoader(testset, self.batch_size, self.rank, self.world))
 
     # ---------------------------------------------------------------------------------------------- arithmetic
     def preprocess(self, x, reverse=False):

@@ -4,9 +4,12 @@ a job script written for the reference drives this implementation unchanged.  Ad
   --max_steps        stop after that many optimizer steps;
   --mnist_root       where `--choose_data mnist` reads the MNIST digits (default "Mnist" in the working directory, as
                      the reference; torchvision's MNIST/raw or MNIST/processed files, never downloaded);
-  --data_seed        keys the random draws of Stochastic Moving MNIST (default 0).
-With `--choose_data mnist` and no `--synthetic_data`, Stochastic Moving MNIST is rendered on the GPU (one kernel launch
-per batch, no DataLoader workers); BAIR and KTH still need `--synthetic_data`.
+  --data_seed        keys the random draws of Stochastic Moving MNIST and the clip choice of BAIR / KTH (default 0);
+  --data_root        where `--choose_data bair` / `kth` read their files (default, as the reference:
+                     `bair_robot_data/processed_data/` / `kth_data` in the working directory; never downloaded);
+  --data_cache       directory for the packed frame stores of BAIR / KTH (decoded once, reused while the files match).
+Without `--synthetic_data` the datasets live on the GPU and a batch is one kernel launch, with no DataLoader workers:
+Stochastic Moving MNIST is rendered (`--choose_data mnist`), BAIR push and KTH clips are gathered from the packed frames.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main_rfn.py ... --multigpu`; one process
 per GPU, the global batch is sharded over ranks and gradients are all-reduced with RCCL (see rfn_hip/dist.py).
 """
@@ -144,7 +147,12 @@ def build_parser():
     p.add_argument("--max_steps", help="Stop after this many optimizer steps (0 = no limit)", default=0, type=int)
     p.add_argument("--mnist_root", help="Directory holding torchvision's MNIST files for --choose_data mnist",
                    default="Mnist", type=str)
-    p.add_argument("--data_seed", help="Seed of the Stochastic Moving MNIST sequences", default=0, type=int)
+    p.add_argument("--data_seed", help="Seed of the Stochastic Moving MNIST sequences and of the BAIR / KTH clip choice",
+                   default=0, type=int)
+    p.add_argument("--data_root", help="Directory holding the files of --choose_data bair / kth (default: the "
+                   "reference's, under the working directory)", default=None, type=str)
+    p.add_argument("--data_cache", help="Directory for the packed frame stores of --choose_data bair / kth",
+                   default=None, type=str)
     return p
 
 

@@ -1786,3 +1786,47 @@ def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, determinist
                    _i(S), _i(nd), _i(L_), _i(1 if deterministic else 0), _l(seed), _l(split), _l(first_id),
                    meta=("shell", "moving_mnist", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
     return (out, traj) if trajectories else out
+
+
+def clip_gather(store, first, T, C):
+    """Clips of a device-resident frame store as one float32 batch (rfn_clip_gather_u8_f32: what the reference's
+    PushDataset / KTH __getitem__ and the DataLoader's collation produce, bair_push.py:66-109, kth.py:34-65,
+    trainer.py:132-161): a fresh [B, T, C, H, W] tensor on the store's device, clip b being frames first[b] ..
+    first[b] + T - 1 as float32(byte) / 255.  `store`: uint8 [F, H, W, Cs] device tensor, Cs in {1, 3}; `first`: int64
+    [B] on the same device; C == Cs, or C == 3 copies of a one-channel store.  A clip that would leave the store is
+    NaN (nothing is read).  One launch on the current stream; no CPU fallback."""
+    for t, nm, dt in ((store, "store", torch.uint8), (first, "first", torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError("clip_gather: %s must be a %s tensor, got %s" %
+                            (nm, str(dt).replace("torch.", ""), t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+    if store.dim() != 4 or min(int(d) for d in store.shape[1:3]) < 1:
+        raise ValueError("clip_gather: store must be [F, H >= 1, W >= 1, Cs], got %s" % (tuple(store.shape),))
+    if first.dim() != 1:
+        raise ValueError("clip_gather: first must be [B], got %s" % (tuple(first.shape),))
+    F, H, W, Cs = (int(d) for d in store.shape)
+    B, T, C = int(first.shape[0]), int(T), int(C)
+    if T < 1:
+        raise ValueError("clip_gather: need T >= 1, got %d" % T)
+    if (C, Cs) not in ((1, 1), (3, 1), (3, 3)):
+        raise ValueError("clip_gather: %d output channels from %d stored ones (C == Cs in {1, 3}, or 3 copies of 1)" %
+                         (C, Cs))
+    for t, nm in ((store, "store"), (first, "first")):
+        if not t.is_cuda:
+            raise ValueError("clip_gather: %s is on %s; the kernel needs device tensors (no CPU fallback)" %
+                             (nm, t.device))
+    if store.device != first.device:
+        raise ValueError("clip_gather: store is on %s, first on %s" % (store.device, first.device))
+    if B and F < 1:
+        raise ValueError("clip_gather: the store holds no frame")
+    chunks = -(-H * W // 1024)
+    if H * W > 0x7fffffff // 4 or B * T * chunks > 0x7fffffff:
+        raise ValueError("clip_gather: %d clips of %d frames of %dx%d exceed one launch" % (B, T, H, W))
+    store, first = store.contiguous(), first.contiguous()
+    out = torch.empty((B, T, C, H, W), device=store.device, dtype=torch.float32)
+    if B:
+        with torch.cuda.device(store.device):
+            L.call("rfn_clip_gather_u8_f32", ctypes.c_void_p(store.data_ptr()), _l(F), ctypes.c_void_p(first.data_ptr()),
+                   L.dev(out), _i(B), _i(T), _i(C), _i(Cs), _i(H), _i(W),
+                   meta=("shell", "clip_gather", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, H, W),
+                         4.0 * out.numel() + float(B * T * H * W * Cs)))
+    return out
