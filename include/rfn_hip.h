@@ -254,6 +254,16 @@ int rfn_glow_shell_fwd_f32(float* z, long z_ns, const float* P, const float* o_i
 long rfn_glow_shell_fwd_ld_floats(int N, int C, int H, int W);
 int rfn_logdet_reduce_f32(const float* part, int n_launch, float* logdet, int accumulate, int N, int C, int H, int W,
                           rfn_stream_t stream);
+/* Host-only label queries of the shell launches (the structs the launchers themselves read; "unsupported" where the
+ * launcher refuses).  Forward: "glow_shell_fwd_kernel PB=.. blocks=.. slots=.. lds=<bytes> ld=<frame | pow2x<G> | generic |
+ * frame+generic> prod=<none | global | lds2 | lds4>" -- the log-det branch of the launch's blocks and the form of the
+ * head's C x C product.  Backward (tail = 1: rfn_glow_shell_bwd_f32, 0: rfn_actnorm_invconv_bwd[_ld]_f32):
+ * "actnorm_invconv_bwd_small_kernel<C,tail> grid=.. sweeps=.. lds=.." or "actnorm_invconv_bwd_kernel<tail> PB=.. grid=..
+ * ny=.. gW=<split | owned> sweeps=.. lds=..".  rfn_glow_shell_supported: 1 when the forward head AND both backward entry
+ * points accept the shape (C even; at most 144 channels), which is what a flow level needs. */
+const char* rfn_glow_shell_fwd_kernel_label(int N, int C, int H, int W, int head);
+const char* rfn_glow_shell_bwd_kernel_label(int N, int C, int HW, int tail);
+int rfn_glow_shell_supported(int N, int C, int H, int W);
 /* (ld_const = 1: the head also adds its ActNorm's parameter-only log-det term H*W * sum_c logs[c] to logdet[n],
  * glow_modules.py:47-52; the backward kernels below then add H*W * sum_n glogdet[n] to glogs.) */
 /* Backward: rfn_actnorm_invconv_bwd_f32 of step k+1 (x = its input = step k's output, gz = gradient wrt its

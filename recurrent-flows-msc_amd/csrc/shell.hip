@@ -632,45 +632,91 @@ __global__ __launch_bounds__(256) void actnorm_invconv_bwd_small_kernel(
     }
 }
 
+// The launch decision of the ActNorm/InvConv backward (TAIL: with the previous step's coupling backward appended), made
+// once: launch_actnorm_invconv_bwd launches what it says and rfn_glow_shell_bwd_kernel_label prints it.
+struct ShellBwdRoute {
+    bool ok;       // false: C too large for the LDS-staged kernel (nothing is launched)
+    int small;     // 4 / 8: actnorm_invconv_bwd_small_kernel<small, TAIL>; 0: actnorm_invconv_bwd_kernel<TAIL>
+    int PB;        // pixels per tile (small kernel: one pixel per thread, 256)
+    int grid, ny;  // blocks along x (pixel tiles) and y (gW entries / output channels split)
+    bool owned;    // big kernel, C*C > 256: a thread owns gW entries; else the pixels of an entry are split over threads
+    int sweeps;    // most tiles one block sweeps: ceil(tiles / grid)
+    size_t lds;    // bytes (big kernel: dynamic; small kernel: its static array)
+};
+static ShellBwdRoute choose_shell_bwd(int N, int C, int HW, bool tail) {
+    ShellBwdRoute r = {};
+    const long tot = (long)N * HW;
+    if (C == 4 || C == 8) {
+        // few, fat blocks: every block ends with C*C+2C same-address atomics, which serialise at the memory side
+        // (512 / 1024 blocks measured slower: 256-deep same-address atomic chains per accumulator are the budget)
+        const long tiles = (tot + 255) / 256;
+        r.ok = true;
+        r.small = C;
+        r.PB = 256;
+        r.grid = (int)(tiles < 256 ? tiles : 256);
+        r.ny = 1;
+        r.sweeps = (int)((tiles + r.grid - 1) / r.grid);
+        r.lds = (size_t)(C * C + 5 * C) * 4;
+        return r;
+    }
+    int PB = 256;
+    const size_t extra = ((size_t)C * C + 2 * C + (tail ? 3 * C : 0)) * 4;
+    while ((size_t)2 * C * (PB + 1) * 4 + extra > 65536 && PB > 64) PB >>= 1;
+    r.PB = PB;
+    r.lds = (size_t)2 * C * (PB + 1) * 4 + extra;
+    r.owned = C * C > 256;
+    if (r.lds > 160 * 1024) return r;
+    r.ok = true;
+    const int ntiles = (int)((tot + PB - 1) / PB);
+    r.grid = ntiles < 512 ? ntiles : 512;
+    // blockIdx.y splits the gW entries (C*C > 256) and the output channels of the gx part: aim at <= 2 channels per thread
+    int ny = r.owned ? (C * C + 511) / 512 : 1;
+    const int jpt = C * PB / 256;  // channels per thread without a split
+    if (ny < jpt / 2) ny = jpt / 2;
+    if (ny > 8) ny = 8;
+    while (ny > 1 && r.grid * ny > 512) ny >>= 1;  // one wave of workgroups: the y-blocks re-stage the same tile
+    r.ny = ny;
+    r.sweeps = (ntiles + r.grid - 1) / r.grid;
+    return r;
+}
+extern "C" const char* rfn_glow_shell_bwd_kernel_label(int N, int C, int HW, int tail) {
+    static thread_local char buf[160];
+    if (N <= 0 || C <= 0 || HW <= 0 || (tail && C % 2)) return "unsupported";
+    const ShellBwdRoute r = choose_shell_bwd(N, C, HW, tail != 0);
+    if (!r.ok) return "unsupported";
+    if (r.small)
+        snprintf(buf, sizeof(buf), "actnorm_invconv_bwd_small_kernel<%d,%d> grid=%d sweeps=%d lds=%zu", r.small, tail ? 1 : 0,
+                 r.grid, r.sweeps, r.lds);
+    else
+        snprintf(buf, sizeof(buf), "actnorm_invconv_bwd_kernel<%d> PB=%d grid=%d ny=%d gW=%s sweeps=%d lds=%zu", tail ? 1 : 0,
+                 r.PB, r.grid, r.ny, r.owned ? "owned" : "split", r.sweeps, r.lds);
+    return buf;
+}
+
 template <bool TAIL>
 static int launch_actnorm_invconv_bwd(const float* x, long x_ns, const float* bias, const float* logs, const float* Wm,
                                       const float* gz, long gz_ns, float* gx, long gx_ns, float* gW, float* gbias,
                                       float* glogs, int N, int C, int HW, const ShellBwdTail& tl, hipStream_t st) {
-    if (C == 4 || C == 8) {
-        long tot = (long)N * HW;
-        // few, fat blocks: every block ends with C*C+2C same-address atomics, which serialise at the memory side
-        // (512 / 1024 blocks measured slower: 256-deep same-address atomic chains per accumulator are the budget)
-        int grid = (int)((tot + 255) / 256 < 256 ? (tot + 255) / 256 : 256);
-        if (C == 4)
-            hipLaunchKernelGGL((actnorm_invconv_bwd_small_kernel<4, TAIL>), dim3(grid), dim3(256), 0, st, x, x_ns, bias,
+    const ShellBwdRoute r = choose_shell_bwd(N, C, HW, TAIL);
+    if (!r.ok) {
+        rfn_set_error("actnorm_invconv_bwd: C=%d too large (%zu bytes of LDS, at most %d)", C, r.lds, 160 * 1024);
+        return -3;
+    }
+    if (r.small) {
+        if (r.small == 4)
+            hipLaunchKernelGGL((actnorm_invconv_bwd_small_kernel<4, TAIL>), dim3(r.grid), dim3(256), 0, st, x, x_ns, bias,
                                logs, Wm, gz, gz_ns, gx, gx_ns, gW, gbias, glogs, N, HW, tl);
         else
-            hipLaunchKernelGGL((actnorm_invconv_bwd_small_kernel<8, TAIL>), dim3(grid), dim3(256), 0, st, x, x_ns, bias,
+            hipLaunchKernelGGL((actnorm_invconv_bwd_small_kernel<8, TAIL>), dim3(r.grid), dim3(256), 0, st, x, x_ns, bias,
                                logs, Wm, gz, gz_ns, gx, gx_ns, gW, gbias, glogs, N, HW, tl);
         return 0;
     }
-    int PB = 256;
-    const size_t extra = ((size_t)C * C + 2 * C + (TAIL ? 3 * C : 0)) * 4;
-    while ((size_t)2 * C * (PB + 1) * 4 + extra > 65536 && PB > 64) PB >>= 1;
-    size_t lds = (size_t)2 * C * (PB + 1) * 4 + extra;
-    if (lds > 160 * 1024) {
-        rfn_set_error("actnorm_invconv_bwd: C=%d too large", C);
-        return -3;
-    }
-    if (lds > 65536)
+    if (r.lds > 65536)
         (void)hipFuncSetAttribute((const void*)actnorm_invconv_bwd_kernel<TAIL>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    long tot = (long)N * HW;
-    int ntiles = (int)((tot + PB - 1) / PB);
-    int grid = ntiles < 512 ? ntiles : 512;
-    // blockIdx.y splits the gW entries (C*C > 256) and the output channels of the gx part: aim at <= 2 channels per thread
-    int ny = (C * C > 256) ? (C * C + 511) / 512 : 1;
-    const int jpt = C * PB / 256;  // channels per thread without a split
-    if (ny < jpt / 2) ny = jpt / 2;
-    if (ny > 8) ny = 8;
-    while (ny > 1 && grid * ny > 512) ny >>= 1;  // one wave of workgroups: the y-blocks re-stage the same tile
-    hipLaunchKernelGGL(actnorm_invconv_bwd_kernel<TAIL>, dim3(grid, ny), dim3(256), lds, st, x, x_ns, bias, logs, Wm, gz,
-                       gz_ns, gx, gx_ns, gW, gbias, glogs, N, C, HW, PB, ntiles, tl);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+    const int ntiles = (int)(((long)N * HW + r.PB - 1) / r.PB);
+    hipLaunchKernelGGL(actnorm_invconv_bwd_kernel<TAIL>, dim3(r.grid, r.ny), dim3(256), r.lds, st, x, x_ns, bias, logs, Wm,
+                       gz, gz_ns, gx, gx_ns, gW, gbias, glogs, N, C, HW, r.PB, ntiles, tl);
     return 0;
 }
 
@@ -1112,19 +1158,80 @@ __global__ __launch_bounds__(256) void glow_shell_fwd_kernel(const ShellFwdParam
     }
 }
 
-// pixels per block of glow_shell_fwd_kernel for N frames of HW pixels and C channels (also fixes the layout of its log-det
-// partials: rfn_glow_shell_fwd_ld_floats)
-static int shell_fwd_pb(int N, int C, int HW) {
+// The launch decision of glow_shell_fwd_kernel for N frames of HW pixels and C channels, made once: the launcher, the
+// size of the log-det partials (rfn_glow_shell_fwd_ld_floats), their reduction and rfn_glow_shell_fwd_kernel_label all
+// read this struct.  ld_class / prod name the branch the kernel's own (block-uniform) tests take for these sizes.
+enum { SHELL_LD_FRAME = 1, SHELL_LD_POW2 = 2, SHELL_LD_GENERIC = 4 };
+enum { SHELL_PROD_NONE, SHELL_PROD_GLOBAL, SHELL_PROD_LDS2, SHELL_PROD_LDS4 };
+struct ShellFwdRoute {
+    bool ok;       // false: C too large for the LDS-staged head (nothing is launched)
+    int PB;        // pixels per block: the widest the LDS allows, halved while the launch has fewer than 256 blocks
+    long blocks;
+    int ld_slots;  // frames a block can touch: (PB - 1) / HW + 2; the partials are [blocks][ld_slots]
+    size_t lds;    // dynamic LDS bytes: head [C][PB] (+ the transposed C x C matrix from C = 16 on)
+    int ld_class;  // SHELL_LD_* of the launch's blocks (FRAME | GENERIC when they differ)
+    int G;         // SHELL_LD_POW2: lanes per group = min(HW, 64)
+    int prod;      // SHELL_PROD_*: how the head forms its C x C product
+};
+static ShellFwdRoute choose_shell_fwd(int N, int C, int HW, bool head) {
+    ShellFwdRoute r = {};
     int PB = shell_pb(C);
     const long tot = (long)N * HW;
     while (PB > 32 && tot / PB < 256) PB >>= 1;
-    return PB;
+    r.PB = PB;
+    r.blocks = (tot + PB - 1) / PB;
+    r.ld_slots = (PB - 1) / HW + 2;
+    r.lds = head ? (size_t)C * PB * 4 + (C >= 16 ? (size_t)C * C * 4 : 0) : 0;
+    r.ok = r.lds <= 160 * 1024;
+    if (HW % PB == 0) {
+        r.ld_class = SHELL_LD_FRAME;  // no block straddles a frame, the last block is full
+    } else if (HW > PB) {
+        r.ld_class = SHELL_LD_FRAME | SHELL_LD_GENERIC;  // block 0 is inside frame 0, a later one straddles or is ragged
+    } else if ((HW & (HW - 1)) == 0 && HW >= 4) {
+        r.ld_class = SHELL_LD_POW2;
+        r.G = HW < 64 ? HW : 64;
+    } else {
+        r.ld_class = SHELL_LD_GENERIC;
+    }
+    const int NG = 256 / PB;
+    if (!head)
+        r.prod = SHELL_PROD_NONE;
+    else if (C >= 16 && C % NG == 0 && (C / NG) % 2 == 0)
+        r.prod = ((C / NG) % 4 == 0 && C % 4 == 0) ? SHELL_PROD_LDS4 : SHELL_PROD_LDS2;
+    else
+        r.prod = SHELL_PROD_GLOBAL;
+    return r;
+}
+extern "C" const char* rfn_glow_shell_fwd_kernel_label(int N, int C, int H, int W, int head) {
+    static thread_local char buf[160];
+    if (N <= 0 || C <= 0 || (C % 2) || H <= 0 || W <= 0) return "unsupported";
+    const ShellFwdRoute r = choose_shell_fwd(N, C, H * W, head != 0);
+    if (!r.ok) return "unsupported";
+    char ld[24];
+    if (r.ld_class == SHELL_LD_POW2)
+        snprintf(ld, sizeof(ld), "pow2x%d", r.G);
+    else
+        snprintf(ld, sizeof(ld), "%s", r.ld_class == SHELL_LD_FRAME ? "frame"
+                                       : r.ld_class == SHELL_LD_GENERIC ? "generic" : "frame+generic");
+    static const char* const prod[] = {"none", "global", "lds2", "lds4"};
+    snprintf(buf, sizeof(buf), "glow_shell_fwd_kernel PB=%d blocks=%ld slots=%d lds=%zu ld=%s prod=%s", r.PB, r.blocks,
+             r.ld_slots, r.lds, ld, prod[r.prod]);
+    return buf;
 }
 /* floats of ONE launch's log-det partials ([blocks][slots]) */
 extern "C" long rfn_glow_shell_fwd_ld_floats(int N, int C, int H, int W) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    const int HW = H * W, PB = shell_fwd_pb(N, C, HW);
-    return (((long)N * HW + PB - 1) / PB) * ((PB - 1) / HW + 2);
+    const ShellFwdRoute r = choose_shell_fwd(N, C, H * W, false);
+    return r.blocks * r.ld_slots;
+}
+/* 1 when a flow level of this shape can run forward AND backward through the shell kernels: the forward head, the fused
+ * backward (rfn_glow_shell_bwd_f32, the tightest: C <= 144) and the first step's rfn_actnorm_invconv_bwd_ld_f32 all fit
+ * their LDS.  (The forward alone accepts up to C = 186 on few pixels: a level must not start what it cannot finish.) */
+extern "C" int rfn_glow_shell_supported(int N, int C, int H, int W) {
+    if (N < 0 || C <= 0 || (C % 2) || H <= 0 || W <= 0) return 0;
+    if (N == 0) return 1;
+    return choose_shell_fwd(N, C, H * W, true).ok && choose_shell_bwd(N, C, H * W, true).ok &&
+           choose_shell_bwd(N, C, H * W, false).ok;
 }
 // logdet[n] (+)= sum over launches k (ascending) and over the blocks b that touch frame n (ascending) of part[k][b][n - n0(b)]
 __global__ __launch_bounds__(256) void logdet_reduce_kernel(const float* __restrict__ part, long per_launch, int n_launch,
@@ -1146,9 +1253,10 @@ extern "C" int rfn_logdet_reduce_f32(const float* part, int n_launch, float* log
                                      int W, rfn_stream_t stream) {
     RFN_CHECK_ARG(part && logdet && n_launch >= 1 && N >= 0 && C > 0 && H > 0 && W > 0, -1);
     if (N == 0) return 0;
-    const int HW = H * W, PB = shell_fwd_pb(N, C, HW);
+    const int HW = H * W;
+    const ShellFwdRoute r = choose_shell_fwd(N, C, HW, false);
     hipLaunchKernelGGL(logdet_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, part,
-                       rfn_glow_shell_fwd_ld_floats(N, C, H, W), n_launch, N, HW, PB, (PB - 1) / HW + 2, logdet, accumulate);
+                       r.blocks * r.ld_slots, n_launch, N, HW, r.PB, r.ld_slots, logdet, accumulate);
     RFN_LAUNCH_CHECK();
     return 0;
 }
@@ -1166,21 +1274,18 @@ extern "C" int rfn_glow_shell_fwd_f32(float* z, long z_ns, const float* P, const
     RFN_CHECK_ARG(!head || (bias && logs && znext), -5);
     RFN_CHECK_ARG(!ld_const || (head && logdet), -7);
     if (N == 0) return 0;
-    const int HW = H * W;
-    const int PB = shell_fwd_pb(N, C, HW);
-    const long tot = (long)N * HW;
-    size_t lds = head ? (size_t)C * PB * 4 + (C >= 16 ? (size_t)C * C * 4 : 0) : 0;
-    if (lds > 160 * 1024) {
-        rfn_set_error("glow_shell_fwd: C=%d too large for the LDS-staged kernel", C);
+    const ShellFwdRoute r = choose_shell_fwd(N, C, H * W, head != 0);
+    if (!r.ok) {
+        rfn_set_error("glow_shell_fwd: C=%d too large for the LDS-staged kernel (%zu bytes of LDS, at most %d)", C, r.lds,
+                      160 * 1024);
         return -6;
     }
-    if (lds > 65536)
+    if (r.lds > 65536)
         (void)hipFuncSetAttribute((const void*)glow_shell_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
+                                  (int)r.lds);
     ShellFwdParams a = {z, z_ns, P, o_in, o_ns, b3, l3, o_out, scale, scale_shift, logdet, clamp_type, tail,
-                        bias, logs, Wm, znext, znext_ns, head, N, C, H, W, PB, ld_const, (PB - 1) / HW + 2};
-    hipLaunchKernelGGL(glow_shell_fwd_kernel, dim3((unsigned)((tot + PB - 1) / PB)), dim3(256), lds, (hipStream_t)stream,
-                       a);
+                        bias, logs, Wm, znext, znext_ns, head, N, C, H, W, r.PB, ld_const, r.ld_slots};
+    hipLaunchKernelGGL(glow_shell_fwd_kernel, dim3((unsigned)r.blocks), dim3(256), r.lds, (hipStream_t)stream, a);
     RFN_LAUNCH_CHECK();
     return 0;
 }

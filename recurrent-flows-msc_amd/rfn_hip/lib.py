@@ -67,6 +67,9 @@ SIGNATURES = {
                             _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_glow_shell_fwd_ld_floats": [_c_i, _c_i, _c_i, _c_i],
     "rfn_logdet_reduce_f32": [_c_f, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_glow_shell_fwd_kernel_label": [_c_i] * 5,
+    "rfn_glow_shell_bwd_kernel_label": [_c_i] * 4,
+    "rfn_glow_shell_supported": [_c_i] * 4,
     "rfn_coupling_po_mask_floats": [_c_i, _c_i, _c_i],
     "rfn_coupling_po_bwd_supported": [_c_i, _c_i, _c_i, _c_i],
     "rfn_coupling_po_bwd_packed_bytes": [_c_i],
@@ -137,6 +140,7 @@ _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": c
              "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,
              "rfn_gemm_wgrad_kernel_label_bf16x3": ctypes.c_char_p,
              "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": ctypes.c_char_p,
+             "rfn_glow_shell_fwd_kernel_label": ctypes.c_char_p, "rfn_glow_shell_bwd_kernel_label": ctypes.c_char_p,
              "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_packed_weight_size": ctypes.c_long,
              "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,
              "rfn_smallmap_packed_size": ctypes.c_long,

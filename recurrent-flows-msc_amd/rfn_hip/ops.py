@@ -1034,6 +1034,10 @@ class GlowLevelFn(torch.autograd.Function):
         Kn = int(Wst.shape[0])
         assert len(flat) == STEP_NPARAM * Kn
         N, C, H, W = x.shape
+        # the forward shell accepts more channels than the backward ones: refuse here what could not be differentiated
+        if not L.load().rfn_glow_shell_supported(N, C, H, W):
+            raise RuntimeError("GlowLevelFn: a flow level of C=%d channels on %dx%d maps does not fit the shell kernels "
+                               "(C must be even and at most 144: rfn_glow_shell_supported)" % (C, H, W))
         prm = [flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)] for k in range(Kn)]
         pks = [StepPacks(*packs[k]) if packs is not None and packs[k] is not None else StepPacks() for k in range(Kn)]
         want_masks = any(ctx.needs_input_grad)
