@@ -546,6 +546,33 @@ int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long
 int rfn_clip_gather_u8_f32(const void* store, long n_frames, const void* first, float* out, int B, int T, int C, int Cs,
                            int H, int W, rfn_stream_t stream);
 
+/* ---- a sheet of frames as 8-bit RGB pixels  (the subplot grids of plotter(), RFN/trainer.py:325-417, and of
+ * Evaluator.plot_samples, evaluation_metrics/error_metrics.py:128-152, as pixels only: no text, axes or titles).
+ * R rows x N columns of H x W cells with `gutter` pixels of the grey level `bg` between the cells and around the sheet:
+ *   Hs = R*H + (R+1)*gutter,  Ws = N*W + (N+1)*gutter,  cell (r, i) at (gutter + r*(H+gutter), gutter + i*(W+gutter)).
+ * rows_table: HOST array of R rfn_sheet_row, copied into the launch (R <= RFN_SHEET_MAX_ROWS): the frame of cell (r, i)
+ * is the dense [C, H, W] block at ptr + i*step (in elements; rows may be views such as image[0, i] of [B,T,C,H,W] or
+ * samples[i, 0] of [T,B,C,H,W]) for i < count, 0 <= count <= N; cells i >= count are background.  kind 0: fp32 in
+ * model space, turned into a byte as Solver.preprocess(x, reverse=True) does (RFN/trainer.py:165-188):
+ *   v = x + 0.5 if range_half else x;  v = v * 2^n_bits;  q = floor(v) * (256 / 2^n_bits);  byte = clamp(q, 0, 255),
+ * NaN -> 0, every operation rounded to fp32 on its own (all factors are powers of two: bit-equal to torch).  kind 1:
+ * uint8, copied.  C in {1, 3}; C == 1 writes the value to R, G and B; any other C is an argument error.
+ * out_addr: the device address of the uint8 output, of any byte alignment (the header has no mutable byte pointer type):
+ * lead 0: [Hs, Ws, 3];  lead 1: [Hs, 1 + 3*Ws] with byte 0 of every line 0, the PNG filter type "None", i.e. the raw
+ * stream of a PNG before deflate.  Every output byte is written exactly once (nothing needs zeroing), with dword stores
+ * on the 4-byte-aligned part of each line and byte stores at its ragged ends; no atomics; nothing is read outside the
+ * listed frames.  1 <= n_bits <= 8, 0 <= bg <= 255, gutter >= 0.  One launch. */
+#define RFN_SHEET_MAX_ROWS 32
+typedef struct rfn_sheet_row {
+    const void* ptr;
+    long step;
+    int kind;
+    int count;
+} rfn_sheet_row;
+int rfn_sheet_max_rows(void);
+int rfn_sheet_compose_u8(const void* rows_table, int R, int N, int C, int H, int W, int gutter, int bg, int n_bits,
+                         int range_half, int lead, long out_addr, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

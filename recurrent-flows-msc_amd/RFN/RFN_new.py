@@ -334,9 +334,15 @@ class RFN(nn.Module):
         el = [take() for _ in range(self.L - 1)] if pinned else None
         return self.flow.sample(z, fc, hz, temperature=self.temperature, eps_base=eb, eps_list=el)
 
+    # predict / reconstruct / sample end in `.cpu()`, as the reference's do; the `_*_device` bodies return the same
+    # tensors where they were computed (Solver.plotter composes its sheet from them without a host round trip).
     def predict(self, x, n_predictions, n_conditions, draws=None):
         """RFN/RFN_new.py:256-360 — condition on n_conditions frames, roll the prior forward n_predictions frames.
         draws: per warm-up step prior eps, encoder eps; per prediction prior eps, base eps, Split2d eps list."""
+        true_x, predictions = self._predict_device(x, n_predictions, n_conditions, draws)
+        return true_x.cpu(), predictions.cpu()
+
+    def _predict_device(self, x, n_predictions, n_conditions, draws=None):
         assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
         with torch.no_grad():
             take, dr = self._taker(draws, x.device)
@@ -356,7 +362,7 @@ class RFN(nn.Module):
                     prior_mean, prior_std = self.prior(torch.cat((ht, zprev), dim=1))
                 zprev = prior_mean + prior_std * self.kl_temperature * take(prior_mean)
                 zxprev = enc_mean + enc_std * take(enc_mean)
-            true_x = x[:, :n_conditions].transpose(0, 1).detach().cpu().clone()
+            true_x = x[:, :n_conditions].transpose(0, 1).detach().clone()
             frames = []  # kept on the device: ONE device-to-host copy at the end instead of a sync per frame
             prediction = x[:, n_conditions - 1]
             for i in range(n_predictions):
@@ -367,13 +373,17 @@ class RFN(nn.Module):
                     prediction, ht, ct, zt = self._gen_step(prediction, hprev, cprev, zprev, eps, self.kl_temperature)
                 frames.append(prediction.detach())
                 hprev, cprev, zprev = ht, ct, zt
-            predictions = (torch.stack(frames, 0).cpu() if frames else torch.zeros((0, *x[:, 0].shape)))
+            predictions = torch.stack(frames, 0) if frames else torch.zeros((0, *x[:, 0].shape), device=x.device)
         return true_x, predictions
 
     def reconstruct(self, x, draws=None):
         """RFN/RFN_new.py:362-450 — posterior reconstructions and the flow bijection check g(f(x)).
         draws: per frame encoder eps, dequantisation noise, Split2d eps list of g(f(x)), base eps + Split2d eps list of
         the fresh sample."""
+        recons, recons_flow = self._reconstruct_device(x, draws)
+        return recons.cpu(), recons_flow.cpu()
+
+    def _reconstruct_device(self, x, draws=None):
         assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
         with torch.no_grad():
             take, dr = self._taker(draws, x.device)
@@ -400,11 +410,14 @@ class RFN(nn.Module):
                 recons_flow[i] = self._flow_sample(fc, hz, take, dr is not None, z=z)
                 recons[i] = self._flow_sample(fc, hz, take, dr is not None)
                 zxprev = zxt
-        return recons.cpu(), recons_flow.cpu()
+        return recons, recons_flow
 
     def sample(self, x, n_samples, draws=None):
         """RFN/RFN_new.py:453-494 — unconditional roll-out from the first frame.
         draws: per sample prior eps, base eps, Split2d eps list."""
+        return self._sample_device(x, n_samples, draws).cpu()
+
+    def _sample_device(self, x, n_samples, draws=None):
         assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
         with torch.no_grad():
             take, dr = self._taker(draws, x.device)
@@ -419,7 +432,7 @@ class RFN(nn.Module):
                     sample, ht, ct, zt = self._gen_step(sample, hprev, cprev, zprev, eps, 1.0)
                 frames.append(sample)
                 zprev, hprev, cprev = zt, ht, ct
-            samples = torch.stack(frames, 0).cpu() if frames else torch.zeros((0, *x[:, 0].shape))
+            samples = torch.stack(frames, 0) if frames else torch.zeros((0, *x[:, 0].shape), device=x.device)
         return samples
 
     # ------------------------------------------------------------------------------------------------ analyses

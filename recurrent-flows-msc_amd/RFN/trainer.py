@@ -1,7 +1,9 @@
 """Solver — training driver with the reference's surface (RFN/trainer.py of the reference): `Solver(args).build();
 .train(); .load(ckpt)`, `preprocess`, `compute_loss` (bits/dim bookkeeping), β annealing, linear LR decay, checkpoint
-dict layout.  Plotting (matplotlib PNG panels) is outside the hot-path scope; a synthetic SM-MNIST-shaped loader is
-built in (`--synthetic_data`); otherwise the dataset lives on the GPU: Stochastic Moving MNIST is rendered from local
+dict layout.  `plotter` writes the reference's sheet of frames (ground truth, samples, predictions, reconstructions,
+bijection check of one test sequence) as `png_folder/samples<k>.png`, composed on the GPU in one launch and encoded
+with zlib: pixels only, no matplotlib, no titles, no loss-curve panel; `--plot_every N` calls it after every N-th
+epoch (default: never).  A synthetic SM-MNIST-shaped loader is built in (`--synthetic_data`); otherwise the dataset lives on the GPU: Stochastic Moving MNIST is rendered from local
 MNIST files (`--choose_data mnist`, data_generators/moving_mnist.py), BAIR push and KTH clips are gathered from their
 packed frames (`bair`, `kth`; data_generators/clips.py).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
 import math
@@ -339,6 +341,9 @@ class Solver(object):
                     self.stop = True
                     break
             self.flush_log()   # graph mode keeps the last step's scalars on the device until asked
+            plot_every = getattr(self.args, "plot_every", 0)   # (Namespaces saved before the flag existed)
+            if plot_every > 0 and self.epoch_i % plot_every == 0:
+                self.plotter()   # (rank 0 only, no collective, leaves model, RNG states and counters as they were)
             epoch_loss = float(np.mean(self.losses)) if self.losses else math.nan
             # every rank must take the same decisions (checkpoint value, early stop, plateau scheduler): rank-local
             # losses would let learning rates diverge or leave one rank waiting in an all-reduce the others never enter
@@ -358,6 +363,61 @@ class Solver(object):
                 print("Epoch {} Loss: {:.2f}".format(self.epoch_i, epoch_loss))
             elif self.rank == 0:
                 self.status()
+
+    # ---------------------------------------------------------------------------------------------- sheets
+    def _plot_rows(self, image):
+        """the five rows of the plotter's sheet for a preprocessed batch [B, T, C, H, W]: views of device tensors, one
+        [n, C, H, W] each (sequence 0 of the batch), in model space"""
+        x_conditions, predictions = self.model._predict_device(image, self.n_predictions, self.n_conditions)
+        recons, recons_flow = self.model._reconstruct_device(image)
+        samples = self.model._sample_device(image, self.n_frames)
+        plot_preds = torch.cat((x_conditions, predictions), 0)
+        n = self.n_frames
+        return [image[0, :n], samples[:n, 0], plot_preds[:n, 0], recons[:n, 0], recons_flow[:n, 0]]
+
+    def plotter(self):
+        """RFN/trainer.py:325-417, the frames only: for sequence 0 of the first test batch, a sheet of 5 rows x n_frames
+        columns -- ground truth, samples from the first frame, n_conditions given frames followed by n_predictions
+        predicted ones, posterior reconstructions, and the flow bijection check g(f(x)) -- written to
+        `png_folder/samples<plot_counter>.png`; plot_counter is then incremented.  One compose launch on the GPU
+        (rfn_hip.ops.compose_sheet), zlib on the host; no text is drawn and there is no loss-curve panel.
+        Two deviations from the reference: its fifth row shows `recons` a second time under the title
+        "Recon-Bijection", ours shows `recons_flow`, which is what the title says; and where n_conditions +
+        n_predictions < n_frames the missing cells of the prediction row are background (the reference raises).
+        Only rank 0 plots and nothing here is a collective.  On return model.training, every parameter and buffer and
+        torch's CPU and GPU generator states are what they were (the device datasets draw by address and keep no
+        counter), so a run with sheets takes the same training steps as a run without.  Returns the file's path
+        (None on other ranks)."""
+        if self.rank != 0:
+            return None
+        from rfn_hip import ops
+        from Utils.png import write_png
+        if self.model._flow_needs_init():
+            # generation marks untouched ActNorm layers initialised (as the reference does), which would change
+            # buffers and cancel the data dependent initialisation of the first training step
+            raise RuntimeError("plotter: the flow's ActNorm layers are not initialised yet; train a step or load a "
+                               "checkpoint first")
+        was_training = self.model.training
+        on_gpu = self.device.type == "cuda"
+        cpu_rng = torch.get_rng_state()
+        gpu_rng = torch.cuda.get_rng_state(self.device) if on_gpu else None
+        try:
+            with torch.no_grad():
+                self.model.eval()
+                image = next(iter(self.test_loader))
+                image = image[0] if self.choose_data == "bair" and isinstance(image, (list, tuple)) else image
+                image = self.preprocess(image.to(self.device))
+                sheet = ops.compose_sheet(self._plot_rows(image), self.n_frames, n_bits=self.n_bits,
+                                          preprocess_range=self.preprocess_range, scanlines=True)
+            path = self.path + "png_folder/samples%d.png" % self.plot_counter
+            write_png(path, sheet)
+        finally:
+            self.model.train(was_training)
+            torch.set_rng_state(cpu_rng)
+            if on_gpu:
+                torch.cuda.set_rng_state(gpu_rng, self.device)
+        self.plot_counter += 1
+        return path
 
     # ---------------------------------------------------------------------------------------------- state
     def checkpoint(self, model_name, epoch, loss):

@@ -4,7 +4,9 @@ bookkeeping (:358-368), the bits-per-dim test-set loop `get_loss` (:370-417) tha
 computed on the GPU by one rfn_frame_quality_u8 launch per call instead of a per-channel CPU loop), the best-of-N
 prediction evaluation `get_eval_values` (:419-598, without its plots), plus thin wrappers over the model's analysis
 methods (`RFN.reconstruct_elbo_gap`, `.probability_future`, `.param_analysis`, RFN/RFN_new.py:496-788).
-LPIPS and FVD need pretrained AlexNet / I3D networks and are not computed; the plots are not drawn."""
+`plot_samples` (:128-152) writes its ground-truth / prediction grid as a PNG of pixels (no titles, no PDF).
+LPIPS and FVD need pretrained AlexNet / I3D networks and are not computed; the other plots are not drawn."""
+import os
 import warnings
 
 import numpy as np
@@ -91,6 +93,36 @@ class Evaluator(object):
                              (tuple(gt.shape), tuple(pred.shape)))
         mse, psnr, ssim = ops.frame_quality(self._as_u8(gt, "gt"), self._as_u8(pred, "pred"))
         return mse.cpu(), ssim.cpu(), psnr.cpu()
+
+    def plot_samples(self, predictions, true_image, name="samples", n=None):
+        """error_metrics.py:128-152 as pixels: a sheet of 2*n rows x T columns, row 2k the ground truth of sequence k
+        and row 2k+1 its prediction, written to `<path>eval_folder/<name>.png` (the reference writes a PDF whose cells
+        carry score titles; no text is rendered here).  predictions, true_image: uint8 [bs, T, C, H, W] on either
+        device (moved to the solver's); n (default: all bs sequences) is how many sequences to show.  One compose
+        launch; returns the file's path."""
+        from rfn_hip import ops
+        from Utils.png import write_png
+        for t, nm in ((predictions, "predictions"), (true_image, "true_image")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 5:
+                raise ValueError("plot_samples: %s must be a uint8 tensor [bs, T, C, H, W], got %s" %
+                                 (nm, (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if tuple(predictions.shape) != tuple(true_image.shape):
+            raise ValueError("plot_samples: predictions %s and true_image %s differ in shape" %
+                             (tuple(predictions.shape), tuple(true_image.shape)))
+        bs, T = int(predictions.shape[0]), int(predictions.shape[1])
+        n = bs if n is None else int(n)
+        if not 1 <= n <= bs or T < 1:
+            raise ValueError("plot_samples: n = %d sequences of %d, %d frames each" % (n, bs, T))
+        predictions, true_image = predictions.to(self.device), true_image.to(self.device)
+        rows = []
+        for k in range(n):
+            rows += [true_image[k], predictions[k]]
+        sheet = ops.compose_sheet(rows, T, scanlines=True)
+        folder = self.solver.path + "eval_folder"
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, name + ".png")
+        write_png(path, sheet)
+        return path
 
     def get_eval_values(self, model_name="rfn.pt", loader=None, max_batches=None):
         """error_metrics.py:419-598 without the plots: per test batch, `resample` rounds of RFN.predict (conditioned on

@@ -7,7 +7,9 @@ a job script written for the reference drives this implementation unchanged.  Ad
   --data_seed        keys the random draws of Stochastic Moving MNIST and the clip choice of BAIR / KTH (default 0);
   --data_root        where `--choose_data bair` / `kth` read their files (default, as the reference:
                      `bair_robot_data/processed_data/` / `kth_data` in the working directory; never downloaded);
-  --data_cache       directory for the packed frame stores of BAIR / KTH (decoded once, reused while the files match).
+  --data_cache       directory for the packed frame stores of BAIR / KTH (decoded once, reused while the files match);
+  --plot_every       write a sheet of ground truth, samples, predictions and reconstructions of one test sequence to
+                     `png_folder/samples<k>.png` after every N-th epoch (default 0: never).
 Without `--synthetic_data` the datasets live on the GPU and a batch is one kernel launch, with no DataLoader workers:
 Stochastic Moving MNIST is rendered (`--choose_data mnist`), BAIR push and KTH clips are gathered from the packed frames.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main_rfn.py ... --multigpu`; one process
@@ -153,6 +155,8 @@ def build_parser():
                    "reference's, under the working directory)", default=None, type=str)
     p.add_argument("--data_cache", help="Directory for the packed frame stores of --choose_data bair / kth",
                    default=None, type=str)
+    p.add_argument("--plot_every", help="Write png_folder/samples<k>.png after every N-th epoch (0 = never)", default=0,
+                   type=int)
     return p
 
 

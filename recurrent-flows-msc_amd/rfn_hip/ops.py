@@ -1834,3 +1834,86 @@ def clip_gather(store, first, T, C):
                    meta=("shell", "clip_gather", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, H, W),
                          4.0 * out.numel() + float(B * T * H * W * Cs)))
     return out
+
+
+class _SheetRow(ctypes.Structure):
+    """rfn_sheet_row of include/rfn_hip.h"""
+    _fields_ = [("ptr", ctypes.c_void_p), ("step", ctypes.c_long), ("kind", ctypes.c_int), ("count", ctypes.c_int)]
+
+
+SHEET_MAX_ROWS = 32   # RFN_SHEET_MAX_ROWS: the row descriptors travel in the launch's arguments
+
+
+def sheet_shape(n_rows, n_cols, H, W, gutter):
+    """(Hs, Ws) of a sheet of n_rows x n_cols cells of H x W pixels with `gutter` pixels between and around them"""
+    return n_rows * H + (n_rows + 1) * gutter, n_cols * W + (n_cols + 1) * gutter
+
+
+def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.5", scanlines=False, out=None):
+    """A sheet of frames as 8-bit RGB pixels (rfn_sheet_compose_u8: the subplot grids of the reference's plotter and
+    Evaluator.plot_samples, trainer.py:325-417, error_metrics.py:128-152, as pixels only).  `rows`: a list of device
+    tensors [n, C, H, W], n <= n_cols, fp32 in model space or uint8, each with dense CHW frames and any stride along n
+    (pass views such as image[0] of [B, T, C, H, W] or samples[:, 0] of [T, B, C, H, W]: nothing is copied).  Row r fills
+    the first n cells of sheet row r, the rest is background `bg`; cells are `gutter` pixels apart.  fp32 frames become
+    bytes exactly as Solver.preprocess(x, reverse=True) with this n_bits / preprocess_range makes them; uint8 frames are
+    copied; C == 1 is written to R, G and B.  Returns uint8 [Hs, Ws, 3], or with scanlines=True [Hs, 1 + 3*Ws] whose
+    lines start with the PNG filter byte 0 (Utils.png.write_png takes either); `out` (optional) is a contiguous uint8
+    tensor of that shape on the rows' device to write into, at any byte address.  One launch on the current stream; no
+    CPU fallback."""
+    if not isinstance(rows, (list, tuple)) or not rows:
+        raise TypeError("compose_sheet: rows must be a non-empty list of tensors, got %s" % type(rows).__name__)
+    for r, t in enumerate(rows):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("compose_sheet: row %d must be a float32 or uint8 tensor, got %s" %
+                            (r, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.dim() != 4:
+            raise ValueError("compose_sheet: row %d must be [n, C, H, W], got %s" % (r, tuple(t.shape)))
+    n_cols, gutter, bg, n_bits = int(n_cols), int(gutter), int(bg), int(n_bits)
+    C, H, W = (int(d) for d in rows[0].shape[1:])
+    if C not in (1, 3) or H < 1 or W < 1:
+        raise ValueError("compose_sheet: frames must be [C in {1, 3}, H >= 1, W >= 1], got %s" % ((C, H, W),))
+    for r, t in enumerate(rows):
+        if tuple(t.shape[1:]) != (C, H, W):
+            raise ValueError("compose_sheet: row %d has frames %s, row 0 has %s" % (r, tuple(t.shape[1:]), (C, H, W)))
+        s = t.stride()
+        if not ((W == 1 or s[3] == 1) and (H == 1 or s[2] == W) and (C == 1 or s[1] == H * W)):
+            raise ValueError("compose_sheet: the frames of row %d must be dense CHW, got shape %s stride %s" %
+                             (r, tuple(t.shape), tuple(s)))
+    if n_cols < 1 or gutter < 0 or not 0 <= bg <= 255 or not 1 <= n_bits <= 8:
+        raise ValueError("compose_sheet: need n_cols >= 1, gutter >= 0, bg in [0, 255], n_bits in [1, 8] (got %d, %d, "
+                         "%d, %d)" % (n_cols, gutter, bg, n_bits))
+    if len(rows) > SHEET_MAX_ROWS:
+        raise ValueError("compose_sheet: %d rows exceed the %d of one launch" % (len(rows), SHEET_MAX_ROWS))
+    for r, t in enumerate(rows):
+        if int(t.shape[0]) > n_cols:
+            raise ValueError("compose_sheet: row %d holds %d frames for %d columns" % (r, int(t.shape[0]), n_cols))
+    for r, t in enumerate(rows):
+        if not t.is_cuda:
+            raise ValueError("compose_sheet: row %d is on %s; the kernel needs device tensors (no CPU fallback)" %
+                             (r, t.device))
+        if t.device != rows[0].device:
+            raise ValueError("compose_sheet: row 0 is on %s, row %d on %s" % (rows[0].device, r, t.device))
+    Hs, Ws = sheet_shape(len(rows), n_cols, H, W, gutter)
+    if Hs > 0x7fffffff or 3 * Ws + 1 > 0x7fffffff or C * H * W > 0x7fffffff:
+        raise ValueError("compose_sheet: a %dx%d sheet of %dx%dx%d frames exceeds one launch" % (Hs, Ws, C, H, W))
+    tab = (_SheetRow * len(rows))()
+    for r, t in enumerate(rows):
+        n = int(t.shape[0])
+        tab[r].ptr = t.data_ptr() if n else None
+        tab[r].step = int(t.stride(0)) if n > 1 else 0
+        tab[r].kind = 1 if t.dtype == torch.uint8 else 0
+        tab[r].count = n
+    dev = rows[0].device
+    shape = (Hs, 1 + 3 * Ws) if scanlines else (Hs, Ws, 3)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or
+          not out.is_contiguous() or out.device != dev):
+        raise ValueError("compose_sheet: out must be a contiguous uint8 tensor %s on %s" % (shape, dev))
+    with torch.cuda.device(dev):
+        L.call("rfn_sheet_compose_u8", ctypes.cast(tab, ctypes.c_void_p), _i(len(rows)), _i(n_cols), _i(C), _i(H), _i(W),
+               _i(gutter), _i(bg), _i(n_bits), _i(1 if preprocess_range == "0.5" else 0), _i(1 if scanlines else 0),
+               _l(out.data_ptr()),
+               meta=("shell", "sheet_compose", 0.0, "%dx%dx%dx%dx%d" % (len(rows), n_cols, C, H, W),
+                     float(out.numel()) + sum(float(t.numel() * t.element_size()) for t in rows)))
+    return out
