@@ -573,6 +573,37 @@ int rfn_sheet_max_rows(void);
 int rfn_sheet_compose_u8(const void* rows_table, int R, int N, int C, int H, int W, int gutter, int bg, int n_bits,
                          int range_half, int lead, long out_addr, rfn_stream_t stream);
 
+/* ---- LPIPS with the AlexNet trunk over a batch of uint8 frames  (evaluation_metrics/error_metrics.py:72, :173-187:
+ * lpips.LPIPS(net='alex') of `lpips` 0.1.3, version 0.1, lpips=True, spatial=False, eval mode; one call per frame there).
+ * Frame [C, H, W] uint8, C in {1, 3} (one channel stands for all three): x = p/255*2 - 1, then (x - shift[c]) / scale[c]
+ * with shift = (-.030, -.088, -.188), scale = (.458, .448, .450).  Five taps, each after a ReLU, all convolutions with
+ * bias and zero padding in the scaled domain: conv 3->64 11x11 stride 4 pad 2 | maxpool 3x3 stride 2, conv 64->192 5x5
+ * pad 2 | maxpool 3x3 stride 2, conv 192->384 3x3 pad 1 | conv 384->256 3x3 pad 1 | conv 256->256 3x3 pad 1.  Head: per
+ * tap l and pixel n(f) = f / (sqrt(sum_c f_c^2) + 1e-10), d_l = mean over pixels of sum_c lin_l[c] (n(fa)_c - n(fb)_c)^2,
+ * d = d_1 + ... + d_5 in tap order.  H, W >= 31 (the second pool needs a 3x3 map); smaller is an argument error.
+ *
+ * rfn_lpips_alex_sizes (host only, no GPU needed): out[0..9] = (rows, columns) of the five taps, out[10] = floats per
+ *   frame of the feature pack (the taps one after the other, each [rows*columns][channels], channels 64, 192, 384, 256,
+ *   256), out[11] = workspace floats per frame.
+ * rfn_lpips_alex_weight_layout (host only): the packed trunk weights are one float buffer; out[l] = offset of
+ *   convolution l's weights, [Kpad_l][Cout_l] with k = (ky*ks + kx)*Cin + ci and zero rows from Cin*ks*ks up to Kpad_l;
+ *   out[5 + l] = offset of its Cout_l biases; out[10 + l] = Kpad_l; out[15] = floats in all.
+ * rfn_lpips_alex_features_u8: the trunk.  frames: uint8 NCHW, frame stride in bytes; feats_out: [N][out[10]];
+ *   workspace: at least N * out[11] floats, free again when the call's work is done.  Convolutions on
+ *   v_mfma_f32_32x32x2_f32 (exact fp32 products, one k-ordered fma chain per value): a frame's features do not depend on
+ *   its index, on N or on how a batch is split into calls, and C == 1 gives the bits of three identical channels.
+ *   Seven launches.
+ * rfn_lpips_alex_distance: the head.  feats_a, feats_b: [N][out[10]]; lin: the 1152 lin weights in tap order;
+ *   per_layer_out: [N][5] = d_l; out: [N] = d.  Fixed reduction order, no atomics: bit-reproducible, exactly 0 on equal
+ *   features and the same bits for (a, b) and (b, a).  One launch. */
+int rfn_lpips_alex_sizes(int H, int W, long long* out);
+int rfn_lpips_alex_weight_layout(long long* out);
+int rfn_lpips_alex_features_u8(const void* frames, long frame_stride, int N, int C, int H, int W, const float* wpack,
+                               long wpack_floats, float* feats_out, float* workspace, long workspace_floats,
+                               rfn_stream_t stream);
+int rfn_lpips_alex_distance(const float* feats_a, const float* feats_b, const float* lin, int N, int H, int W,
+                            float* per_layer_out, float* out, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,11 @@ computed on the GPU by one rfn_frame_quality_u8 launch per call instead of a per
 prediction evaluation `get_eval_values` (:419-598, without its plots), plus thin wrappers over the model's analysis
 methods (`RFN.reconstruct_elbo_gap`, `.probability_future`, `.param_analysis`, RFN/RFN_new.py:496-788).
 `plot_samples` (:128-152) writes its ground-truth / prediction grid as a PNG of pixels (no titles, no PDF).
-LPIPS and FVD need pretrained AlexNet / I3D networks and are not computed; the other plots are not drawn."""
+`get_lpips` (:173-187) scores frames with LPIPS on the AlexNet trunk (`lpips` 0.1.3, net='alex', version 0.1; the
+definition is pinned in rfn_hip/lpips.py) on the GPU, one trunk pass per argument and one head launch instead of one
+network call per frame, once `settings.lpips_weights` names the two upstream weight files (torchvision's AlexNet and
+the lpips package's alex.pth; nothing is downloaded); without that setting LPIPS is not computed.  FVD needs a
+pretrained TensorFlow I3D network and is not computed; the other plots are not drawn."""
 import os
 import warnings
 
@@ -31,6 +35,10 @@ class Evaluator(object):
         self.extra_plots = bool(getattr(settings, "extra_plots", False))
         self.debug_plot = bool(getattr(settings, "debug_plot", False))
         self._warned_plots = False
+        # optional: a directory or a list of files holding the LPIPS-alex weights (rfn_hip.ops.lpips_alex_load); loaded
+        # on first use
+        self.lpips_weights = getattr(settings, "lpips_weights", None)
+        self._lpips = None
 
     def compute_loss(self, nll, kl, dims, t=10):
         """error_metrics.py:358-368 -> (bits/dim, kl / t, nll / t)"""
@@ -94,6 +102,35 @@ class Evaluator(object):
         mse, psnr, ssim = ops.frame_quality(self._as_u8(gt, "gt"), self._as_u8(pred, "pred"))
         return mse.cpu(), ssim.cpu(), psnr.cpu()
 
+    def _lpips_loaded(self):
+        """the packed LPIPS-alex weights on the solver's device, loaded once"""
+        if self.lpips_weights is None:
+            raise RuntimeError("Evaluator: LPIPS needs pretrained weights: set settings.lpips_weights to a directory or "
+                               "a list of files holding torchvision's AlexNet state dict and the lpips package's "
+                               "alex.pth (nothing is downloaded)")
+        if self._lpips is None:
+            from rfn_hip import ops
+            self._lpips = ops.lpips_alex_load(self.lpips_weights, self.device)
+        return self._lpips
+
+    def _lpips_frames(self, x, name):
+        if not isinstance(x, torch.Tensor) or x.dim() != 5:
+            raise ValueError("get_lpips: %s must be a tensor [bs, T, C, H, W]" % name)
+        return self._as_u8(x, name).to(self.device)
+
+    def get_lpips(self, X, Y):
+        """error_metrics.py:173-187: per-frame LPIPS (AlexNet trunk; rfn_hip/lpips.py pins the definition) of two video
+        tensors [bs, T, C, H, W] (uint8, or float tensors of integers in [0, 255]; C in {1, 3}, one channel standing
+        for three) as CPU float32 [bs, T].  One trunk pass per argument and one head launch; no CPU fallback.  Needs
+        settings.lpips_weights."""
+        from rfn_hip import ops
+        w = self._lpips_loaded()
+        X, Y = self._lpips_frames(X, "X"), self._lpips_frames(Y, "Y")
+        if tuple(X.shape) != tuple(Y.shape):
+            raise ValueError("get_lpips: X and Y must both be [bs, T, C, H, W], got %s and %s" %
+                             (tuple(X.shape), tuple(Y.shape)))
+        return ops.lpips_alex_distance(w, ops.lpips_alex_features(w, X), ops.lpips_alex_features(w, Y)).cpu()
+
     def plot_samples(self, predictions, true_image, name="samples", n=None):
         """error_metrics.py:128-152 as pixels: a sheet of 2*n rows x T columns, row 2k the ground truth of sequence k
         and row 2k+1 its prediction, written to `<path>eval_folder/<name>.png` (the reference writes a PDF whose cells
@@ -130,11 +167,14 @@ class Evaluator(object):
         eval_seq of the predictions against the ground truth; per sequence the best of the draws is kept (strictly
         higher time-mean PSNR / SSIM, strictly lower MSE; ties keep the earlier draw).  Returns the reference's tuple
         (MSE, PSNR, SSIM, LPIPS, BPD, DKL, RECON, SSIM_std, PSNR_std, LPIPS_std): MSE / PSNR / SSIM [n_seq, n_pred] of the
-        best draws; LPIPS and LPIPS_std None (no pretrained network here); BPD / DKL / RECON one value per batch, from its
-        last resample; SSIM_std / PSNR_std [n_seq, n_pred], the mean over the draws.
+        best draws; BPD / DKL / RECON one value per batch, from its last resample; SSIM_std / PSNR_std [n_seq, n_pred], the
+        mean over the draws.  LPIPS and LPIPS_std are None unless settings.lpips_weights is set; with weights they are
+        CPU float32 [n_seq, n_pred] like SSIM and SSIM_std (best draw: strictly lower time-mean LPIPS, :511-512), the
+        ground truth's AlexNet features computed once per batch and reused for every draw (resample + 1 trunk passes per
+        batch).
 
         Reference quirk kept on purpose, so that the figures stay comparable with published ones: the first draw's
-        SSIM / PSNR tensors ARE the best-so-far tensors (the reference aliases them) and the best-of-N updates write into
+        SSIM / PSNR / LPIPS tensors ARE the best-so-far tensors (the reference aliases them) and the best-of-N updates write into
         them in place, so the "mean over draws" averages the final best values in place of draw 0."""
         assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
         if (self.extra_plots or self.debug_plot) and not self._warned_plots:
@@ -142,6 +182,10 @@ class Evaluator(object):
             self._warned_plots = True
         loader = loader if loader is not None else self.test_loader
         start, n_frames = self.start_predictions, self.n_frames
+        lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
+        lpips_values, lpips_std_values = [], []
+        if lpips_w is not None:
+            from rfn_hip import ops
         mse_values, psnr_values, ssim_values, ssim_std_values, psnr_std_values = [], [], [], [], []
         bpd_list, dkl_list, recon_list = [], [], []
         with torch.no_grad():
@@ -153,7 +197,8 @@ class Evaluator(object):
                 image = self.solver.preprocess(image.to(self.device))
                 imageloss = image[:, :self.n_trained] if self.n_trained else image
                 image_u8 = self.solver.preprocess(image, reverse=True)
-                ssim_draws, psnr_draws = [], []
+                ssim_draws, psnr_draws, lpips_draws = [], [], []
+                gt_feats = None
                 for r in range(self.resample):
                     _, predictions = self.model.predict(image, n_frames - start, start)
                     _, kl, nll = self.model.loss(imageloss, 0)
@@ -163,6 +208,17 @@ class Evaluator(object):
                     pred_u8 = pred_u8.to(self.device)
                     gt_u8 = image_u8[:, start:start + pred_u8.shape[1]]
                     mse, ssim, psnr = self.eval_seq(gt_u8, pred_u8)
+                    if lpips_w is not None:
+                        if gt_feats is None:
+                            gt_feats = ops.lpips_alex_features(lpips_w, self._as_u8(gt_u8, "gt"))
+                        lpips = ops.lpips_alex_distance(lpips_w, ops.lpips_alex_features(
+                            lpips_w, self._as_u8(pred_u8, "pred")), gt_feats).cpu()
+                        if r == 0:
+                            lpips_best = lpips   # aliased, as in the reference
+                        else:
+                            better = lpips_best.mean(-1) > lpips.mean(-1)
+                            lpips_best[better, :] = lpips[better, :]
+                        lpips_draws.append(lpips)
                     if r == 0:
                         mse_best, ssim_best, psnr_best = mse, ssim, psnr   # aliased, as in the reference
                     else:
@@ -176,15 +232,20 @@ class Evaluator(object):
                     psnr_draws.append(psnr)
                 ssim_std_values.append(torch.stack(ssim_draws).mean(0))
                 psnr_std_values.append(torch.stack(psnr_draws).mean(0))
+                if lpips_w is not None:
+                    lpips_std_values.append(torch.stack(lpips_draws).mean(0))
+                    lpips_values.append(lpips_best)
                 mse_values.append(mse_best)
                 psnr_values.append(psnr_best)
                 ssim_values.append(ssim_best)
                 bpd_list.append(bpd)
                 dkl_list.append(kl_loss)
                 recon_list.append(recon_loss)
-        return (torch.cat(mse_values), torch.cat(psnr_values), torch.cat(ssim_values), None,
+        return (torch.cat(mse_values), torch.cat(psnr_values), torch.cat(ssim_values),
+                torch.cat(lpips_values) if lpips_w is not None else None,
                 torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
-                torch.cat(ssim_std_values), torch.cat(psnr_std_values), None)
+                torch.cat(ssim_std_values), torch.cat(psnr_std_values),
+                torch.cat(lpips_std_values) if lpips_w is not None else None)
 
     # ---- the analyses the reference's evaluator drives (error_metrics.py: plot_elbo_gap, plot_prob_of_t, param_plots)
     def elbo_gap(self, image, sample=False):

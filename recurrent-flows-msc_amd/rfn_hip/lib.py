@@ -137,6 +137,10 @@ SIGNATURES = {
     "rfn_clip_gather_u8_f32": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_sheet_max_rows": [],
     "rfn_sheet_compose_u8": [ctypes.c_void_p] + [_c_i] * 10 + [_c_l, _c_s],
+    "rfn_lpips_alex_sizes": [_c_i, _c_i, ctypes.c_void_p],
+    "rfn_lpips_alex_weight_layout": [ctypes.c_void_p],
+    "rfn_lpips_alex_features_u8": [ctypes.c_void_p, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_f, _c_l, _c_s],
+    "rfn_lpips_alex_distance": [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_s],
 }
 _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": ctypes.c_char_p,
              "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,

@@ -1917,3 +1917,8 @@ def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.
                meta=("shell", "sheet_compose", 0.0, "%dx%dx%dx%dx%d" % (len(rows), n_cols, C, H, W),
                      float(out.numel()) + sum(float(t.numel() * t.element_size()) for t in rows)))
     return out
+
+
+# LPIPS with the AlexNet trunk (rfn_hip/lpips.py holds the loader and the wrappers of csrc/lpips.hip)
+from .lpips import (LpipsAlexWeights, LpipsFeatures, lpips_alex, lpips_alex_distance, lpips_alex_features,  # noqa: E402,F401
+                    lpips_alex_load, lpips_alex_pack, lpips_alex_sizes)
