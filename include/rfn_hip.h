@@ -604,6 +604,40 @@ int rfn_lpips_alex_features_u8(const void* frames, long frame_stride, int N, int
 int rfn_lpips_alex_distance(const float* feats_a, const float* feats_b, const float* lin, int N, int H, int W,
                             float* per_layer_out, float* out, rfn_stream_t stream);
 
+/* ---- Inflated-3D Inception trunk (I3D, Kinetics-400, RGB stream) for the Frechet Video Distance (evaluation_metrics/
+ * FVD.py, FVD_score.py, error_metrics.py:1006-1063; DESIGN.md section 14 is the definition).  rfn_hip/i3d.py holds the
+ * layer table and drives these kernels layer by layer.  Activations are channels-last float32 [N, T, H, W, C]; every
+ * convolution and pool pads as TF "SAME": out = ceil(in / s), pad_total = max((out - 1) s + k - in, 0), pad_before =
+ * pad_total / 2, the rest after.
+ *
+ * rfn_i3d_same (host only): out[0] = output extent, out[1] = pad before, of one axis.
+ * rfn_i3d_conv_pack_dims (host only): out[0] = Kpad (Cin k^3 rounded up to the k chunk), out[1] = Coutpad (Cout rounded up
+ *   to the column tile) of a packed convolution [Kpad][Coutpad], k = ((kt k + ky) k + kx) Cin + ci, zero rows and columns
+ *   past K and Cout; the bias has Coutpad entries.
+ * rfn_i3d_conv3d_f32: cubic convolution (k in {1, 3, 7}, stride 1 or 2 on every axis) + bias + optional ReLU as an implicit
+ *   GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products, one k-ordered fma chain per value: a value does not depend on
+ *   N or on the position of its video in the call).  in: dense [N, T, H, W, Cin]; out: rows of out_pitch floats, one per
+ *   output position, the Cout values written at out_coff (everything else in the row is left alone).
+ * rfn_i3d_maxpool3d_f32: SAME max pool, window kt x khw x khw, stride st x shw x shw, dense in and out; cells outside the
+ *   map are ignored, not read as zero.
+ * rfn_i3d_resize_u8: uint8 frames [NF][C][H][W] (C in {1, 3}, one channel standing for three; frame stride in bytes) to
+ *   float [NF][224][224][3] with TF1's resize_bilinear (align_corners=False, no half-pixel centres), then 2 v / 255 - 1.
+ * rfn_i3d_head_f32: in [N][Tp][P][C] -> out [N][Cout]: average over windows of 2 time steps x all P cells (stride 1,
+ *   VALID), logits bias + avg w from a packed [C][Coutpad] convolution, mean over the Tp - 1 windows; fixed order.
+ * The *_floats arguments are the sizes of the buffers; the entry points refuse a call that would leave them.
+ * No atomics anywhere. */
+int rfn_i3d_same(int in, int k, int s, long long* out);
+int rfn_i3d_conv_pack_dims(int Cin, int Cout, int k, long long* out);
+int rfn_i3d_conv3d_f32(const float* in, long in_floats, int N, int T, int H, int W, int Cin, const float* wpack,
+                       long wpack_floats, const float* bias, int Cout, int k, int stride, int relu, float* out,
+                       long out_floats, int out_coff, int out_pitch, rfn_stream_t stream);
+int rfn_i3d_maxpool3d_f32(const float* in, long in_floats, int N, int T, int H, int W, int C, int kt, int khw, int st,
+                          int shw, float* out, long out_floats, rfn_stream_t stream);
+int rfn_i3d_resize_u8(const void* frames, long frame_stride, int NF, int C, int H, int W, float* out, long out_floats,
+                      rfn_stream_t stream);
+int rfn_i3d_head_f32(const float* in, long in_floats, int N, int Tp, int P, int C, const float* wpack, long wpack_floats,
+                     const float* bias, int Cout, float* out, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,8 +8,11 @@ methods (`RFN.reconstruct_elbo_gap`, `.probability_future`, `.param_analysis`, R
 `get_lpips` (:173-187) scores frames with LPIPS on the AlexNet trunk (`lpips` 0.1.3, net='alex', version 0.1; the
 definition is pinned in rfn_hip/lpips.py) on the GPU, one trunk pass per argument and one head launch instead of one
 network call per frame, once `settings.lpips_weights` names the two upstream weight files (torchvision's AlexNet and
-the lpips package's alex.pth; nothing is downloaded); without that setting LPIPS is not computed.  FVD needs a
-pretrained TensorFlow I3D network and is not computed; the other plots are not drawn."""
+the lpips package's alex.pth; nothing is downloaded); without that setting LPIPS is not computed.
+`get_fvd_values` (:1006-1063) is the Frechet Video Distance on the logits of the I3D network (Kinetics-400, RGB stream;
+the definition is pinned in rfn_hip/i3d.py), the trunk on the GPU, once `settings.fvd_weights` names local files with
+the I3D weights (a PyTorch state dict or an .npz of the TF variables; nothing is downloaded); without that setting it
+raises.  The other plots are not drawn."""
 import os
 import warnings
 
@@ -39,6 +42,9 @@ class Evaluator(object):
         # on first use
         self.lpips_weights = getattr(settings, "lpips_weights", None)
         self._lpips = None
+        # optional: a directory or a list of files holding the I3D weights (rfn_hip.ops.i3d_load); loaded on first use
+        self.fvd_weights = getattr(settings, "fvd_weights", None)
+        self._i3d = None
 
     def compute_loss(self, nll, kl, dims, t=10):
         """error_metrics.py:358-368 -> (bits/dim, kl / t, nll / t)"""
@@ -130,6 +136,61 @@ class Evaluator(object):
             raise ValueError("get_lpips: X and Y must both be [bs, T, C, H, W], got %s and %s" %
                              (tuple(X.shape), tuple(Y.shape)))
         return ops.lpips_alex_distance(w, ops.lpips_alex_features(w, X), ops.lpips_alex_features(w, Y)).cpu()
+
+    def _i3d_loaded(self):
+        """the packed I3D weights on the solver's device, loaded once"""
+        if self.fvd_weights is None:
+            raise RuntimeError("Evaluator: FVD needs pretrained weights: set settings.fvd_weights to a directory or a "
+                               "list of files holding the I3D (Kinetics-400, RGB) weights, as the PyTorch port's state "
+                               "dict or as an .npz of the TF variables (nothing is downloaded)")
+        if self._i3d is None:
+            from rfn_hip import ops
+            self._i3d = ops.i3d_load(self.fvd_weights, self.device)
+        return self._i3d
+
+    def get_fvd_values(self, model_name="rfn.pt", n_predicts=None, loader=None, max_batches=None):
+        """error_metrics.py:1006-1063: (mean, std) of two Frechet Video Distances between the test set's ground truth,
+        frames start_predictions : start_predictions + n_predicts of every sequence, and the model's predictions of
+        those frames, each of the two passes over the test data with fresh draws (np.std: the population figure, as
+        the reference).  A short last batch is padded with zeros up to the first batch's size for `predict` and cut
+        again.  The videos are embedded by the I3D trunk on the GPU (rfn_hip.ops.i3d_embed; embeddings stay on the
+        device) and compared by rfn_hip.ops.frechet_distance.  The ground truth's embeddings do not depend on the draw:
+        they are computed in the first pass only.  n_predicts defaults to n_frames - start_predictions and must be at
+        least 9; fewer than 16 sequences is a ValueError.  Needs settings.fvd_weights."""
+        from rfn_hip import ops
+        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        w = self._i3d_loaded()
+        loader = loader if loader is not None else self.test_loader
+        start = self.start_predictions
+        n_predicts = int(n_predicts) if n_predicts is not None else self.n_frames - start
+        values, gt_emb, batch_size = [], None, getattr(self.args, "batch_size", None)
+        with torch.no_grad():
+            self.model.eval()
+            for _ in range(2):
+                preds, gts = [], []
+                for batch_i, true_image in enumerate(loader):
+                    if max_batches is not None and batch_i >= max_batches:
+                        break
+                    image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
+                    image = self.solver.preprocess(image.to(self.device))
+                    cur_bs = int(image.shape[0])
+                    batch_size = batch_size or cur_bs
+                    if cur_bs < batch_size:
+                        pad = torch.zeros((batch_size - cur_bs,) + tuple(image.shape[1:]), device=image.device,
+                                          dtype=image.dtype)
+                        _, predictions = self.model.predict(torch.cat((image, pad), 0), n_predicts, start)
+                        predictions = predictions[:, :cur_bs]
+                    else:
+                        _, predictions = self.model.predict(image, n_predicts, start)
+                    pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 0, 2, 3, 4).to(self.device)
+                    preds.append(ops.i3d_embed(w, self._as_u8(pred_u8, "pred")))
+                    if gt_emb is None:
+                        gt_u8 = self.solver.preprocess(image, reverse=True)[:, start:start + n_predicts]
+                        gts.append(ops.i3d_embed(w, self._as_u8(gt_u8, "gt").to(self.device)))
+                if gt_emb is None:
+                    gt_emb = torch.cat(gts)
+                values.append(ops.frechet_distance(gt_emb, torch.cat(preds)))
+        return float(np.mean(values)), float(np.std(values))
 
     def plot_samples(self, predictions, true_image, name="samples", n=None):
         """error_metrics.py:128-152 as pixels: a sheet of 2*n rows x T columns, row 2k the ground truth of sequence k

@@ -141,6 +141,13 @@ SIGNATURES = {
     "rfn_lpips_alex_weight_layout": [ctypes.c_void_p],
     "rfn_lpips_alex_features_u8": [ctypes.c_void_p, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_f, _c_l, _c_s],
     "rfn_lpips_alex_distance": [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_s],
+    "rfn_i3d_same": [_c_i, _c_i, _c_i, ctypes.c_void_p],
+    "rfn_i3d_conv_pack_dims": [_c_i, _c_i, _c_i, ctypes.c_void_p],
+    "rfn_i3d_conv3d_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l,
+                           _c_i, _c_i, _c_s],
+    "rfn_i3d_maxpool3d_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_s],
+    "rfn_i3d_resize_u8": [ctypes.c_void_p, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_s],
+    "rfn_i3d_head_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_i, _c_f, _c_s],
 }
 _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": ctypes.c_char_p,
              "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,

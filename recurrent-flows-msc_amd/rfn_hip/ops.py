@@ -1922,3 +1922,8 @@ def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.
 # LPIPS with the AlexNet trunk (rfn_hip/lpips.py holds the loader and the wrappers of csrc/lpips.hip)
 from .lpips import (LpipsAlexWeights, LpipsFeatures, lpips_alex, lpips_alex_distance, lpips_alex_features,  # noqa: E402,F401
                     lpips_alex_load, lpips_alex_pack, lpips_alex_sizes)
+
+# Frechet Video Distance: the I3D trunk and the Frechet distance (rfn_hip/i3d.py holds the layer table, the loader and the
+# wrappers of csrc/i3d.hip)
+from .i3d import (I3DWeights, frechet_distance, i3d_embed, i3d_head, i3d_inception, i3d_load, i3d_logits,  # noqa: E402,F401
+                  i3d_maxpool, i3d_pack, i3d_preprocess, i3d_same, i3d_sizes, i3d_unit)
