@@ -472,11 +472,22 @@ int rfn_stepbn_bwd_f32(const float* x, const float* gamma, const float* beta, co
 int rfn_stepbn_apply_f32(const float* x, const float* gamma, const float* beta, float* y, const float* mean,
                          const float* var, int S, int B, int C, int HW, float eps, int act, float slope,
                          rfn_stream_t stream);
+/* Host-only label query: "stepbn ny=.. stats=vec|scalar apply=vec4|vec1 grid=.. sweeps=..".  ny = workgroups per (step,
+ * channel) of the stats / reduce kernel (= rfn_stepbn_scratch_floats / (2*S*C)); grid = streaming workgroups of the
+ * apply kernel, sweeps = the most grid-stride iterations of one.  `aligned` is a bit mask the caller derives from the
+ * pointers it will pass: bit 0 = every pointer the stats (x) or, with bwd, the reduce kernel (x, g) tests is 16-byte
+ * aligned; bit 1 = the same for the apply kernel (x, y; with bwd x, g, gx). */
+const char* rfn_stepbn_kernel_label(int S, int B, int C, int HW, int aligned, int bwd);
 
 /* ---- a9  ConvLSTMLayer.forward gate update  (Utils/modules.py:370-377): cc = conv output [N,4*Hc,HW] in gate order
  * i,f,o,g;  i=σ(cc_i+Wci∘c) f=σ(cc_f+Wcf∘c) g=tanh(cc_g) c'=f∘c+i∘g o=σ(cc_o+Wco∘c') h'=o∘tanh(c').
  * Wci/Wcf/Wco [Hc*HW] may be NULL (== 0, which is what the reference trains with).  gates [N,4*Hc,HW] receives the
  * post-nonlinearity i,f,o,g for the backward pass (may be NULL). */
+/* Host-only label queries of the grid-stride launches above and below (answered by the host functions the launchers
+ * call for their grids): "latent_step grid=.. sweeps=.." / "convlstm_gates grid=.. sweeps=..", sweeps = the most
+ * grid-stride iterations of a thread; "unsupported" for sizes that launch nothing. */
+const char* rfn_latent_step_kernel_label(int B, int ZHW);
+const char* rfn_convlstm_gates_kernel_label(int N, int Hc, int HW);
 int rfn_convlstm_gates_fwd_f32(const float* cc, const float* c_prev, long c_ns, const float* Wci, const float* Wcf,
                                const float* Wco, float* h_out, long h_ns, float* c_out, long co_ns, float* gates,
                                int N, int Hc, int HW, rfn_stream_t stream);

@@ -1923,6 +1923,43 @@ __global__ void stepbn_bwd_apply_kernel(const float* __restrict__ x, const float
             gx[idx] = xv[0];
     }
 }
+// The launch decisions of the per-step BatchNorm entry points, made once: the launchers below launch what this says and
+// rfn_stepbn_kernel_label prints it.  `aligned` bit 0: every pointer the stats (x) / reduce (x, g) kernel tests is
+// 16-byte aligned; bit 1: the same for the apply kernel (forward x, y; backward x, g, gx).  The stats / reduce kernels
+// decide their load width on the device, by the test restated in stats_vec.
+struct StepBnRoute {
+    int ny;          // workgroups per (step, channel) of the stats / reduce kernel (stepbn_split)
+    bool stats_vec;  // stats / reduce kernel: 16-byte loads over flattened (frame, pixel quad) pairs; else the scalar loops
+    bool v4;         // apply kernel: stepbn_*apply_kernel<4>; else <1>
+    int grid;        // streaming workgroups of the apply kernel (the launch adds the one that finalises, if any)
+    int sweeps;      // most grid-stride iterations of an apply workgroup
+};
+static StepBnRoute choose_stepbn(int S, int B, int C, int HW, int aligned) {
+    StepBnRoute r;
+    const long total = (long)S * B * C * HW;
+    r.ny = stepbn_split(S, B, C);
+    r.stats_vec = HW % 4 == 0 && (aligned & 1);
+    r.v4 = HW % 4 == 0 && (aligned & 2);
+    const long nthr = r.v4 ? total / 4 : total;
+    r.grid = (int)((nthr + 255) / 256 < 16384 ? (nthr + 255) / 256 : 16384);
+    r.sweeps = (int)((nthr + (long)r.grid * 256 - 1) / ((long)r.grid * 256));
+    return r;
+}
+static int stepbn_aligned(const void* s0, const void* s1, const void* a0, const void* a1, const void* a2) {
+    const uintptr_t st = (uintptr_t)s0 | (uintptr_t)s1, ap = (uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)a2;
+    return ((st & 15) == 0 ? 1 : 0) | ((ap & 15) == 0 ? 2 : 0);
+}
+// bwd says which pair of kernels `aligned` was derived for (forward: stats + apply, backward: reduce + apply); the
+// route arithmetic is the same either way, so it changes nothing printed
+extern "C" const char* rfn_stepbn_kernel_label(int S, int B, int C, int HW, int aligned, int bwd) {
+    static thread_local char buf[160];
+    if (S <= 0 || B <= 0 || C <= 0 || HW <= 0 || (long)S * B * C * HW >= (1L << 31)) return "unsupported";
+    const StepBnRoute r = choose_stepbn(S, B, C, HW, aligned);
+    (void)bwd;
+    snprintf(buf, sizeof(buf), "stepbn ny=%d stats=%s apply=%s grid=%d sweeps=%d", r.ny, r.stats_vec ? "vec" : "scalar",
+             r.v4 ? "vec4" : "vec1", r.grid, r.sweeps);
+    return buf;
+}
 // floats of scratch rfn_stepbn_fwd_f32 (acc) / rfn_stepbn_bwd_f32 (sums) need for these sizes
 extern "C" long rfn_stepbn_scratch_floats(int S, int B, int C) {
     if (S <= 0 || B <= 0 || C <= 0) return 0;
@@ -1941,15 +1978,13 @@ extern "C" int rfn_stepbn_fwd_f32(const float* x, const float* gamma, const floa
     const long total = (long)S * B * C * HW;
     RFN_CHECK_ARG(total < (1L << 31), -3);
     hipStream_t st = (hipStream_t)stream;
-    const int ny = stepbn_split(S, B, C);
+    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, nullptr, x, y, nullptr));
+    const int ny = r.ny, grid = r.grid;
     hipLaunchKernelGGL(stepbn_stats_kernel, dim3(S * C, ny), dim3(256), 0, st, x, acc, B, C, HW);
     StepBnFused f;
     f.acc = acc; f.mean_out = mean; f.var_out = var; f.run_mean = run_mean; f.run_var = run_var; f.coef = coef;
     f.coef_u = coef_u; f.decay = decay; f.nbt = nbt; f.S = S; f.ny = ny;
-    const bool v4 = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-    const long nthr = v4 ? total / 4 : total;
-    const int grid = (int)((nthr + 255) / 256 < 16384 ? (nthr + 255) / 256 : 16384);
-    if (v4)
+    if (r.v4)
         hipLaunchKernelGGL(stepbn_apply_kernel<4>, dim3(grid + 1), dim3(256), 0, st, x, gamma, beta, y, (unsigned)total, B, C,
                            HW, eps, act, slope, f);
     else
@@ -1970,10 +2005,9 @@ extern "C" int rfn_stepbn_apply_f32(const float* x, const float* gamma, const fl
     StepBnFused f;
     memset(&f, 0, sizeof(f));
     f.mean_out = const_cast<float*>(mean); f.var_out = const_cast<float*>(var); f.S = S;
-    const bool v4 = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-    const long nthr = v4 ? total / 4 : total;
-    const int grid = (int)((nthr + 255) / 256 < 16384 ? (nthr + 255) / 256 : 16384);
-    if (v4)
+    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, nullptr, x, y, nullptr));
+    const int grid = r.grid;
+    if (r.v4)
         hipLaunchKernelGGL(stepbn_apply_kernel<4>, dim3(grid + 1), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
                            (unsigned)total, B, C, HW, eps, act, slope, f);
     else
@@ -1997,7 +2031,8 @@ extern "C" int rfn_stepbn_bwd_f32(const float* x, const float* gamma, const floa
     const long total = (long)S * B * C * HW;
     RFN_CHECK_ARG(total < (1L << 31), -3);
     hipStream_t st = (hipStream_t)stream;
-    const int ny = stepbn_split(S, B, C);
+    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, g, x, g, gx));
+    const int ny = r.ny, grid = r.grid;
     float* sg = sums;
     float* sgx = sums + (long)ny * S * C;
     if (stage != 2)
@@ -2007,11 +2042,8 @@ extern "C" int rfn_stepbn_bwd_f32(const float* x, const float* gamma, const floa
         RFN_LAUNCH_CHECK();
         return 0;
     }
-    const bool v4 = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)g | (uintptr_t)gx) & 15) == 0;
-    const long nthr = v4 ? total / 4 : total;
-    const int grid = (int)((nthr + 255) / 256 < 16384 ? (nthr + 255) / 256 : 16384);
     const int extra = ggamma ? 1 : 0;
-    if (v4)
+    if (r.v4)
         hipLaunchKernelGGL(stepbn_bwd_apply_kernel<4>, dim3(grid + extra), dim3(256), 0, st, x, beta, g, mean, var, gamma,
                            sg, sgx, gx, (unsigned)total, B, C, HW, eps, act, slope, ggamma, gbeta, S, ny, world);
     else
@@ -2202,6 +2234,35 @@ extern "C" int rfn_invconv_weights_bwd_f32(const float* const* p, const float* c
 //   ps = softplus(pri_raw), es = softplus(enc_raw), pm = pri_loc, em = enc_loc (+ pm with res_q)
 //   zt = pm + ps*eps_p ;  zxt = em + es*eps_q ;  kl = KL(N(em,es) || N(pm,ps)) element-wise
 // One launch instead of ~25 tiny elementwise kernels per timestep (and ~50 in backward).
+// grid of an elementwise grid-stride kernel of 256 threads: one thread per element up to `cap` workgroups (the latent
+// step and ConvLSTM gate launchers launch this; their label queries print it)
+struct StrideRoute {
+    int grid;    // workgroups
+    int sweeps;  // most grid-stride iterations of a thread
+};
+static StrideRoute choose_stride_grid(long tot, int cap) {
+    StrideRoute r;
+    const long blocks = (tot + 255) / 256;
+    r.grid = (int)(blocks < cap ? blocks : cap);
+    r.sweeps = (int)((blocks + r.grid - 1) / r.grid);
+    return r;
+}
+constexpr int LATENT_STEP_MAX_GRID = 1024, CONVLSTM_GATES_MAX_GRID = 2048;
+extern "C" const char* rfn_latent_step_kernel_label(int B, int ZHW) {
+    static thread_local char buf[96];
+    if (B <= 0 || ZHW <= 0) return "unsupported";
+    const StrideRoute r = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID);
+    snprintf(buf, sizeof(buf), "latent_step grid=%d sweeps=%d", r.grid, r.sweeps);
+    return buf;
+}
+extern "C" const char* rfn_convlstm_gates_kernel_label(int N, int Hc, int HW) {
+    static thread_local char buf[96];
+    if (N <= 0 || Hc <= 0 || HW <= 0) return "unsupported";
+    const StrideRoute r = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID);
+    snprintf(buf, sizeof(buf), "convlstm_gates grid=%d sweeps=%d", r.grid, r.sweeps);
+    return buf;
+}
+
 __device__ __forceinline__ float sigmoid_sp(float raw) { return raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw)); }
 
 __global__ void latent_step_fwd_kernel(const float* __restrict__ enc, const float* __restrict__ pri,
@@ -2254,8 +2315,7 @@ extern "C" int rfn_latent_step_fwd_f32(const float* enc, const float* pri, const
                                        int res_q, rfn_stream_t stream) {
     RFN_CHECK_ARG(enc && pri && eps_p && eps_q && zt && zxt && kl && em && es && B >= 0 && ZHW > 0, -1);
     if (B == 0) return 0;
-    long tot = (long)B * ZHW;
-    int grid = (int)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024);
+    const int grid = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID).grid;
     hipLaunchKernelGGL(latent_step_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc, pri, eps_p, eps_q, zt,
                        zxt, kl, em, es, B, ZHW, res_q);
     RFN_LAUNCH_CHECK();
@@ -2268,8 +2328,7 @@ extern "C" int rfn_latent_step_bwd_f32(const float* enc, const float* pri, const
     RFN_CHECK_ARG(enc && pri && eps_p && eps_q && g_enc && g_pri && B >= 0 && ZHW > 0, -1);
     RFN_CHECK_ARG((!g_zt || g_zt_ns >= ZHW) && (!g_zxt || g_zxt_ns >= ZHW), -1);
     if (B == 0) return 0;
-    long tot = (long)B * ZHW;
-    int grid = (int)((tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024);
+    const int grid = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID).grid;
     hipLaunchKernelGGL(latent_step_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc, pri, eps_p, eps_q,
                        g_zt, g_zt_ns, g_zxt, g_zxt_ns, g_kl, g_em, g_es, g_enc, g_pri, B, ZHW, res_q);
     RFN_LAUNCH_CHECK();
@@ -2311,8 +2370,7 @@ extern "C" int rfn_convlstm_gates_fwd_f32(const float* cc, const float* c_prev, 
                                           long co_ns, float* gates, int N, int Hc, int HW, rfn_stream_t stream) {
     RFN_CHECK_ARG(cc && c_prev && h_out && c_out && N >= 0 && Hc > 0 && HW > 0, -1);
     if (N == 0) return 0;
-    long tot = (long)N * Hc * HW;
-    int grid = (int)((tot + 255) / 256 < 2048 ? (tot + 255) / 256 : 2048);
+    const int grid = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID).grid;
     hipLaunchKernelGGL(convlstm_gates_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, cc, c_prev, c_ns, Wci,
                        Wcf, Wco, h_out, h_ns, c_out, co_ns, gates, N, Hc, HW);
     RFN_LAUNCH_CHECK();
@@ -2357,8 +2415,7 @@ extern "C" int rfn_convlstm_gates_bwd_f32(const float* gates, const float* c_pre
                                           float* gc_prev, long gcp_ns, int N, int Hc, int HW, rfn_stream_t stream) {
     RFN_CHECK_ARG(gates && c_prev && c_out && gcc && gc_prev && N >= 0 && Hc > 0 && HW > 0, -1);
     if (N == 0) return 0;
-    long tot = (long)N * Hc * HW;
-    int grid = (int)((tot + 255) / 256 < 2048 ? (tot + 255) / 256 : 2048);
+    const int grid = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID).grid;
     hipLaunchKernelGGL(convlstm_gates_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, gates, c_prev, c_ns,
                        c_out, co_ns, gh, gh_ns, gc_next, gcn_ns, Wci, Wcf, Wco, gcc, gc_prev, gcp_ns, N, Hc, HW);
     RFN_LAUNCH_CHECK();

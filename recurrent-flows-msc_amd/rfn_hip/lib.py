@@ -118,6 +118,9 @@ SIGNATURES = {
     "rfn_smallmap_conv_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
                                  _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
     "rfn_stepbn_scratch_floats": [_c_i, _c_i, _c_i],
+    "rfn_stepbn_kernel_label": [_c_i] * 6,
+    "rfn_convlstm_gates_kernel_label": [_c_i] * 3,
+    "rfn_latent_step_kernel_label": [_c_i] * 2,
     "rfn_stepbn_fwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, ctypes.c_float, ctypes.c_void_p,
                            _c_i, _c_i, _c_i, _c_i, ctypes.c_float, _c_i, ctypes.c_float, _c_s],
     "rfn_stepbn_bwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, ctypes.c_float,
@@ -154,6 +157,8 @@ _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": c
              "rfn_gemm_wgrad_kernel_label_bf16x3": ctypes.c_char_p,
              "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": ctypes.c_char_p,
              "rfn_glow_shell_fwd_kernel_label": ctypes.c_char_p, "rfn_glow_shell_bwd_kernel_label": ctypes.c_char_p,
+             "rfn_stepbn_kernel_label": ctypes.c_char_p, "rfn_convlstm_gates_kernel_label": ctypes.c_char_p,
+             "rfn_latent_step_kernel_label": ctypes.c_char_p,
              "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_packed_weight_size": ctypes.c_long,
              "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,
              "rfn_smallmap_packed_size": ctypes.c_long,

@@ -621,6 +621,21 @@ def test_latent_step_fwd_bwd(K, res_q, use):
     sum((outs[i] * cu(gouts[i].repeat_interleave(2, dim=-1))[..., ::2]).sum() for i in sel).backward()
     assert relerr(ek.grad, enc.grad) < 1e-5
     assert relerr(pk.grad, pri.grad) < 1e-5
+    # incoming g_zt / g_zxt as [:, a:b] channel slices of a wider gradient, handed to the node as they are: g[0] is
+    # contiguous and stride(0) is wider, so LatentStepFn.backward reads them in place (the row-stride path of training)
+    ek2, pk2 = cu(enc.detach()).requires_grad_(True), cu(pri.detach()).requires_grad_(True)
+    outs2 = K.LatentStepFn.apply(ek2, pk2, cu(ep), cu(eq), res_q)
+    gin = []
+    for i in sel:
+        if i < 2:
+            wide = cu(torch.cat([torch.full((B, 2, H, W), 7.0), gouts[i], torch.full((B, 3, H, W), -7.0)], 1))
+            gin.append(wide[:, 2:2 + Z])
+            assert gin[-1][0].is_contiguous() and gin[-1].stride(0) == (Z + 5) * H * W
+        else:
+            gin.append(cu(gouts[i]))
+    torch.autograd.backward([outs2[i] for i in sel], gin)
+    assert relerr(ek2.grad, enc.grad) < 1e-5
+    assert relerr(pk2.grad, pri.grad) < 1e-5
 
 
 @pytest.mark.parametrize("N,Cin,C,H,W", [(3, 40, 4, 8, 8), (2, 256, 8, 16, 16), (5, 24, 2, 3, 5)])

@@ -287,18 +287,27 @@ def test_convlstm(golden, name):
     close(ctn, f["ct_none"], 1e-5, 1e-6)
 
 
-@pytest.mark.parametrize("who,cin,hc", [("SRNN lstm_h", 256, 60), ("SRNN lstm_a", 316, 60), ("VRNN lstm", 384, 256)])
+@pytest.mark.parametrize("who,cin,hc", [("SRNN lstm_h", 256, 60), ("SRNN lstm_a", 316, 60), ("VRNN lstm", 384, 256),
+                                        ("SRNN lstm_h with peepholes", 256, 60)])
 def test_convlstm_at_the_sibling_models_sizes(who, cin, hc):
     """the SRNN / VRNN baselines drive the same ConvLSTM one frame at a time on 8x8 maps
     (SRNN/SRNN.py:161-171,210-240: in = 256 or 256 + h_dim, hidden 60; VRNN/VRNN.py:169-173,199-201: in = 256 + 128,
     hidden 256; defaults of main_srnn.py / main_vrnn.py).  Three recurrent steps with gradients at those channel counts,
     HIP module against the CPU oracle on the same weights (the golden fixture `sibling_8x8` pins the oracle on this shape
-    class at reduced channel counts)."""
+    class at reduced channel counts).  The last variant sets nonzero peephole tensors Wci / Wcf / Wco on the module
+    and, through the state dict, in the oracle (as a reference CPU checkpoint that carries them would): the peephole
+    terms of both gate kernels run; same bounds, and the Wc gradients themselves are not produced, so not compared."""
     from Utils import ConvLSTM
     torch.manual_seed(91)
     B, H, W, S = 3, 8, 8, 3
     m = ConvLSTM(cin, hc, [3, 3], bias=True, peephole=True).cuda()
     g = torch.Generator().manual_seed(92)
+    if "peepholes" in who:
+        gp = torch.Generator().manual_seed(93)
+        for n in ("Wci", "Wcf", "Wco"):
+            m.LSTMlayer.register_parameter(n, torch.nn.Parameter((0.5 * torch.randn(1, hc, H, W, generator=gp)).cuda(),
+                                                                 requires_grad=False))
+        assert all(t is not None for t in m.LSTMlayer._peephole_tensors(H, W, "cuda"))
     xs = [torch.randn(B, 1, cin, H, W, generator=g) for _ in range(S)]
     h0, c0 = torch.randn(B, hc, H, W, generator=g) * 0.5, torch.randn(B, hc, H, W, generator=g) * 0.5
     wh, wc = torch.randn(B, hc, H, W, generator=g), torch.randn(B, hc, H, W, generator=g)
