@@ -300,8 +300,8 @@ int rfn_conv3x3_smallcout_bf16x3(const float* in, long in_ns, int Cin, const flo
  * RFN_WGRAD_SPLIT: tile / K-split experiments). */
 int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw, int F, int HW,
                           rfn_stream_t stream);
-/* G (<= 16) gradients of ONE shape in one launch (the K steps of a flow level, where a single gradient is a
- * latency-class problem): a, b, gw are host arrays of G device pointers; strides and sizes are shared. */
+/* G (<= 16) gradients of ONE shape in one launch (the K steps of a flow level: one tail of atomics instead of K): a, b,
+ * gw are host arrays of G device pointers; strides and sizes are shared. */
 int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, int M, const float* const* b, long b_ns, int Nc,
                                   float* const* gw, int G, int F, int HW, rfn_stream_t stream);
 /* label query for both (G = 0: rfn_gemm_wgrad_bf16x3) */
@@ -318,6 +318,16 @@ int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, long g_ns, 
                                               float* const* gw, int G, int F, int H, int W, rfn_stream_t stream);
 /* label query for both (G = 0: the ungrouped entry point) */
 const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W);
+/* K split of a GROUPED launch of the LDS-DMA ring kernels (gemm_wgrad_dma_kernel, gemm_wgrad_dma_impl_kernel), as
+ * host-only queries that launch nothing and run the very functions the kernels and launchers run.  The unit of work is
+ * the flat stage space of one output tile: G * n_stages stages (n_stages = F * HW / 32), group g owning
+ * [g * n_stages, (g + 1) * n_stages).  rfn_wgrad_split_workgroups: the workgroups Wt a launch starts per tile,
+ * min(256 / tiles, G * n_stages / 8), at least 1.  rfn_wgrad_split_parts: workgroup w of Wt owns the stages
+ * [w T / Wt, (w + 1) T / Wt) of T = G * n_stages and processes them as parts that never cross a group; writes up to
+ * max_parts triples (group, first stage within the group, count) in processing order and returns the number of parts
+ * of w (0 for an empty range; negative: argument error). */
+int rfn_wgrad_split_workgroups(int tiles, int G, int n_stages);
+int rfn_wgrad_split_parts(int G, int n_stages, int Wt, int w, long long* parts, int max_parts);
 int rfn_im2col3x3_f32(const float* in1, long in1_ns, int C1, const float* in2, long in2_ns, int C2, float* out, int N,
                       int H, int W, rfn_stream_t stream);
 

@@ -27,8 +27,10 @@ struct GemmWgradParams {
     const float* b2;
     long b2_ns;
     int C1, C2, H, W;
-    // grouped launch (G > 0): G independent gradients of the SAME shape in one launch -- the K steps of a flow level at
-    // the deep levels / small batches, where a single gradient is a latency-class problem.  blockIdx.z = grp * mtiles + mt.
+    // grouped launch (G > 0): G independent gradients of the SAME shape in one launch -- the K steps of a flow level, one
+    // atomic tail instead of K.  gemm_wgrad_b3_kernel: blockIdx.z = grp * mtiles + mt, a K split per group; the ring
+    // kernels: no grid dimension carries the group, the workgroups of a tile split the groups' flat stage range
+    // (wg_split_part below).
     int G, mtiles;
     const float* ga[16];
     const float* gb[16];
@@ -53,6 +55,54 @@ __device__ __forceinline__ WgOperands wg_operands(const GemmWgradParams& p, cons
             }
     }
     return o;
+}
+// The same for the ring kernels, which change group INSIDE their K loop (wg_split_part): there the compile-time select
+// keeps all 64 table entries live in SGPRs across the stage loop (hundreds of spills).  They read the four pointers of
+// the group from the kernel-argument segment itself instead -- p is the kernel's only argument, so the segment IS a
+// GemmWgradParams -- with four scalar loads at a run-time offset; the by-value copy is still never indexed.  The
+// launchers of the kernels that call this assert the kernel's signature (wg_sole_argument): a second kernel argument
+// would move nothing (p stays first) but a wrapper that passes p differently must not compile.
+__device__ __forceinline__ WgOperands wg_operands_kernarg(const int grp) {
+    typedef const GemmWgradParams __attribute__((address_space(4))) KernargParams;
+    KernargParams* kp = (KernargParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    WgOperands o = {kp->ga[grp], kp->gb[grp], kp->gb2[grp], kp->ggw[grp]};
+    return o;
+}
+template <class Kern>
+constexpr bool wg_sole_argument(Kern) { return std::is_same<Kern, void (*)(GemmWgradParams)>::value; }
+// q, which points into the operand `from`, moved to the same place of the operand `to` (the next group's)
+__device__ __forceinline__ const float* wg_rebase(const float* q, const float* from, const float* to) {
+    return reinterpret_cast<const float*>((uintptr_t)q - (uintptr_t)from + (uintptr_t)to);
+}
+
+// K split of a grouped launch of the ring kernels: the unit of work is the flat stage space of ONE output tile,
+// T = G * n_stages stages with group g owning [g * n_stages, (g + 1) * n_stages).  Workgroup w of the Wt of a tile owns
+// the contiguous range [w T / Wt, (w + 1) T / Wt) -- two ranges differ by at most one stage, and every CU works
+// whatever G is (a per-group split S = 256 / (tiles G) leaves 256 - S tiles G of them idle).  A range that crosses group
+// boundaries is processed as parts, one per group it touches: (group, first stage of the group, count).
+// wg_split_part hands out the parts of workgroup w in order: `pos` starts at wg_split_begin and is advanced; false when
+// the range is used up (at once for an empty range, Wt > T).  The kernels and the launchers share it; the C ABI exports
+// it as rfn_wgrad_split_parts.
+struct WgPart { int grp, s0, cnt; };
+__host__ __device__ inline long wg_split_begin(int G, int n_stages, int Wt, int w) {
+    return (long)w * ((long)G * n_stages) / Wt;
+}
+__host__ __device__ inline bool wg_split_part(int G, int n_stages, int Wt, int w, long& pos, WgPart& part) {
+    const long end = (long)(w + 1) * ((long)G * n_stages) / Wt;
+    if (pos >= end) return false;
+    const long g = pos / n_stages;
+    part.grp = (int)g;
+    part.s0 = (int)(pos - g * n_stages);
+    const long left = end - pos, in_group = (long)n_stages - part.s0;
+    part.cnt = (int)(left < in_group ? left : in_group);
+    pos += part.cnt;
+    return true;
+}
+// workgroups per output tile of a grouped ring launch: the chip's 256 CUs over the tiles, at least 8 stages each
+__host__ __device__ inline int wg_split_workgroups(int tiles, int G, int n_stages) {
+    long Wt = 256 / tiles, cap = (long)G * n_stages / 8;
+    if (Wt > cap) Wt = cap;
+    return Wt < 1 ? 1 : (int)Wt;
 }
 
 // WM x WN waves (4 or 8) of TM x TN 32x32 tiles each.  The 8-wave 256-row configurations read both operands of the
@@ -325,21 +375,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, kk = lane >> 5;
-    // grouped launch (G > 0): blockIdx.z = group * mtiles + row tile; the groups share shapes and strides
-    const int grp = p.G > 0 ? (int)blockIdx.z / p.mtiles : 0;
-    const int m0 = (p.G > 0 ? (int)blockIdx.z - grp * p.mtiles : (int)blockIdx.z) * BM, n0 = blockIdx.y * BN;
-    const WgOperands ops_ = wg_operands(p, grp);
-    const float* const pa_ = ops_.a;
-    const float* const pb_ = ops_.b;
-    float* const pgw_ = ops_.gw;
+    const int m0 = blockIdx.z * BM, n0 = blockIdx.y * BN;
+    // the operands in hand: the single gradient's, or (grouped launch, G > 0) those of the group of the current part --
+    // the groups share shapes and strides, so everything below is computed once and only the bases move (wg_rebase)
+    const float* pa_ = p.a;
+    const float* pb_ = p.b;
+    float* pgw_ = p.gw;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     // this lane's share of a stage: PPW pieces; piece q = wave + j NW covers stacked rows RPP q .. (A rows, then B rows)
     const float* prow[PPW];   // row base + this lane's (swizzled) unit
@@ -361,12 +404,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
     }
     const unsigned uHW = (unsigned)p.HW;
     const int S = gridDim.x;
-    const int nmine = (p.n_stages - (int)blockIdx.x + S - 1) / S;   // my stages: blockIdx.x, + S, ...
+    // my stages: first, first + step, ... (nmine of them).  Ungrouped: blockIdx.x, + S, ...; grouped: the stages of one
+    // part of my range of the flat stage space (wg_split_part), consecutive
+    int first = blockIdx.x, step = S, nmine = (p.n_stages - (int)blockIdx.x + S - 1) / S;
     // frame / pixel offsets of my stage t (clamped to my last one: pieces past the end re-read it and are never used)
     long offa = 0, offb = 0;
     auto stage_offsets = [&](int t) {
         t = t < nmine ? t : nmine - 1;
-        const unsigned q0 = (unsigned)(blockIdx.x + t * S) * KP;
+        const unsigned q0 = (unsigned)(first + t * step) * KP;
         const unsigned f = q0 / uHW, px = q0 - f * uHW;          // a stage never straddles a frame (HW % KP == 0)
         offa = (long)f * p.a_ns + px;
         offb = (long)f * p.b_ns + px;
@@ -395,13 +440,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
         r[1] = *reinterpret_cast<const f32x4*>(sb + (o ^ 16));
     };
 
-    // prologue: stages 0 .. NST-2 in flight; (LOOK) stage 0 landed, its first fragments read and split
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t) {
-        stage_offsets(t);
-#pragma unroll
-        for (int j = 0; j < PPW; ++j) piece(j, t);
-    }
     f32x4 ra[2][2], rb[TN][2];
     bf16x8 ah[2], al[2], bh[2][TN], bl[2][TN];
     auto first_fragments = [&](const unsigned char* sb0) {
@@ -413,96 +451,142 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
         for (int j = 0; j < TN; ++j) wg_split8(rb[j][0], rb[j][1], bh[0][j], bl[0][j]);
         wg_split8(ra[0][0], ra[0][1], ah[0], al[0]);
     };
-    if (LOOK) {
-        wg_wait_vm<(NST - 2) * PPW>();
-        __builtin_amdgcn_s_barrier();
-        first_fragments(lds_raw);
-    }
 
-    int slot = 0;
-    for (int it = 0; it < nmine; ++it) {
-        // top of stage `it`.  LOOK: my pieces of stage it + 1 have landed once only those of the stages issued after it
-        // are outstanding; the barrier makes that everybody's pieces and frees the slot of stage it - 1.  Two slots: the
-        // same for stage `it` itself (nothing younger is outstanding).
-        wg_wait_vm<LOOK ? (NST - 3) * PPW : 0>();
-        __builtin_amdgcn_s_barrier();
-        const int nslot = slot + 1 == NST ? 0 : slot + 1;
-        const int fslot = slot == 0 ? NST - 1 : slot - 1;          // slot of stage it - 1 = slot of stage it + NST - 1
-        const unsigned char* sb = lds_raw + slot * STAGE;
-        const unsigned char* sn = lds_raw + nslot * STAGE;
-        stage_offsets(it + NST - 1);
-        if (!LOOK) {
-            // two slots: the next stage's pieces have exactly this stage to land -- issued before anything else
+    // one pass per part: a single pass over the interleaved stages set up above for an ungrouped launch, one pass per
+    // group my range touches for a grouped one
+    WgPart part;
+    long pos = p.G > 0 ? wg_split_begin(p.G, p.n_stages, S, blockIdx.x) : 0;
+    for (int part_i = 0; p.G > 0 ? wg_split_part(p.G, p.n_stages, S, blockIdx.x, pos, part) : part_i == 0; ++part_i) {
+        if (p.G > 0) {
+            const WgOperands o = wg_operands_kernarg(part.grp);
 #pragma unroll
-            for (int j = 0; j < PPW; ++j) piece(j, fslot);
-            first_fragments(sb);
+            for (int j = 0; j < PPW; ++j) prow[j] = pisa[j] ? wg_rebase(prow[j], pa_, o.a) : wg_rebase(prow[j], pb_, o.b);
+            pa_ = o.a;
+            pb_ = o.b;
+            pgw_ = o.gw;
+            first = part.s0;
+            step = 1;
+            nmine = part.cnt;
+        }
+        if (part_i > 0) {
+            // the previous part's atomics have retired (they count in vmcnt like the pieces the waits below count), its
+            // fragment reads have returned, and nobody reads a slot the prologue is about to fill
+            wg_wait_vm<0>();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
         }
 #pragma unroll
-        for (int u = 0; u < NU_; ++u) {
-            const int s_ = u / TM, i = u % TM, cur = u & 1, kb = s_ & 1;
-            // raw A fragment of unit u + 2 (this stage or the next one)
-            if (u + 2 < NU_) raw(sb, aoff[(u + 2) % TM], (u + 2) / TM, ra[cur]);
-            else if (LOOK) raw(sn, aoff[(u + 2) % TM], 0, ra[cur]);
-            // raw B fragments of the next k-step
-            if (i == 0) {
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (s_ + 1 < NK) raw(sb, boff[j], s_ + 1, rb[j]);
-                    else if (LOOK) raw(sn, boff[j], 0, rb[j]);
-                }
-            }
-            // the DMA pieces of the stage that will fill the freed slot (NST - 2 stages to land): one per MFMA gap of
-            // the first unit(s)
-            if (LOOK && u == 0) {
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+        // prologue: stages 0 .. NST-2 in flight; (LOOK) stage 0 landed, its first fragments read and split
+#pragma unroll
+        for (int t = 0; t < NST - 1; ++t) {
+            stage_offsets(t);
+#pragma unroll
+            for (int j = 0; j < PPW; ++j) piece(j, t);
+        }
+        if (LOOK) {
+            wg_wait_vm<(NST - 2) * PPW>();
+            __builtin_amdgcn_s_barrier();
+            first_fragments(lds_raw);
+        }
+
+        int slot = 0;
+        for (int it = 0; it < nmine; ++it) {
+            // top of stage `it`.  LOOK: my pieces of stage it + 1 have landed once only those of the stages issued after it
+            // are outstanding; the barrier makes that everybody's pieces and frees the slot of stage it - 1.  Two slots: the
+            // same for stage `it` itself (nothing younger is outstanding).
+            wg_wait_vm<LOOK ? (NST - 3) * PPW : 0>();
+            __builtin_amdgcn_s_barrier();
+            const int nslot = slot + 1 == NST ? 0 : slot + 1;
+            const int fslot = slot == 0 ? NST - 1 : slot - 1;          // slot of stage it - 1 = slot of stage it + NST - 1
+            const unsigned char* sb = lds_raw + slot * STAGE;
+            const unsigned char* sn = lds_raw + nslot * STAGE;
+            stage_offsets(it + NST - 1);
+            if (!LOOK) {
+                // two slots: the next stage's pieces have exactly this stage to land -- issued before anything else
 #pragma unroll
                 for (int j = 0; j < PPW; ++j) piece(j, fslot);
+                first_fragments(sb);
             }
+#pragma unroll
+            for (int u = 0; u < NU_; ++u) {
+                const int s_ = u / TM, i = u % TM, cur = u & 1, kb = s_ & 1;
+                // raw A fragment of unit u + 2 (this stage or the next one)
+                if (u + 2 < NU_) raw(sb, aoff[(u + 2) % TM], (u + 2) / TM, ra[cur]);
+                else if (LOOK) raw(sn, aoff[(u + 2) % TM], 0, ra[cur]);
+                // raw B fragments of the next k-step
+                if (i == 0) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        if (s_ + 1 < NK) raw(sb, boff[j], s_ + 1, rb[j]);
+                        else if (LOOK) raw(sn, boff[j], 0, rb[j]);
+                    }
+                }
+                // the DMA pieces of the stage that will fill the freed slot (NST - 2 stages to land): one per MFMA gap of
+                // the first unit(s)
+                if (LOOK && u == 0) {
+#pragma unroll
+                    for (int j = 0; j < PPW; ++j) piece(j, fslot);
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur], bh[kb][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bl[kb][j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bh[kb][j], acc[i][j], 0, 0, 0);
+                }
+                if (LOOK || u + 1 < NU_) wg_split8(ra[cur ^ 1][0], ra[cur ^ 1][1], ah[cur ^ 1], al[cur ^ 1]);
+                if (i >= 1 && i <= TN && (LOOK || s_ + 1 < NK))
+                    wg_split8(rb[i - 1][0], rb[i - 1][1], bh[kb ^ 1][i - 1], bl[kb ^ 1][i - 1]);
+            }
+            if (LOOK && (NK & 1)) {   // an odd number of k-steps per stage: the next stage starts on the other B buffer
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    bh[0][j] = bh[1][j];
+                    bl[0][j] = bl[1][j];
+                }
+            }
+            // the schedule of the stage, spelled out for the compiler (left alone it issues the conversions in long VALU
+            // runs and the MFMAs back to back, i.e. one after the other): after every MFMA up to six VALU, one LDS read
+            // and (first units) one DMA piece in its shadow
+            if (!LOOK) {
+                __builtin_amdgcn_sched_group_barrier(0x020, PPW, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 2 * TN + 4, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 30 * (TN + 1), 0);
+            }
+#pragma unroll
+            for (int g = 0; g < NU_ * TN * 3; ++g) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                if (LOOK && g < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            }
+            slot = nslot;
+        }
+        wg_wait_vm<0>();   // (pieces past the end)
+        // (the tile origin made opaque per part: the offsets and bounds masks of the 16 TM TN atomics do not depend on the
+        // part, and hoisted out of the part loop they live, and spill, through the stage loop -- 256 VGPRs + 92 spilled and
+        // 234 spilled SGPRs for the 256 x 256 tile without this, 240 and none with it, as before the part loop.  The empty
+        // asm computes nothing; if a compiler stops honouring it, tools/kernel_resources.py shows spills and a ScratchSize
+        // above 0 for the three ring kernels)
+        int m0e = m0, n0e = n0;
+        asm volatile("" : "+s"(m0e), "+s"(n0e));
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur], bh[kb][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bl[kb][j], acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bh[kb][j], acc[i][j], 0, 0, 0);
+                const int n = n0e + (wn * TN + j) * 32 + l31;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = m0e + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                    if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
+                }
             }
-            if (LOOK || u + 1 < NU_) wg_split8(ra[cur ^ 1][0], ra[cur ^ 1][1], ah[cur ^ 1], al[cur ^ 1]);
-            if (i >= 1 && i <= TN && (LOOK || s_ + 1 < NK))
-                wg_split8(rb[i - 1][0], rb[i - 1][1], bh[kb ^ 1][i - 1], bl[kb ^ 1][i - 1]);
-        }
-        if (LOOK && (NK & 1)) {   // an odd number of k-steps per stage: the next stage starts on the other B buffer
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                bh[0][j] = bh[1][j];
-                bl[0][j] = bl[1][j];
-            }
-        }
-        // the schedule of the stage, spelled out for the compiler (left alone it issues the conversions in long VALU
-        // runs and the MFMAs back to back, i.e. one after the other): after every MFMA up to six VALU, one LDS read
-        // and (first units) one DMA piece in its shadow
-        if (!LOOK) {
-            __builtin_amdgcn_sched_group_barrier(0x020, PPW, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 2 * TN + 4, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 30 * (TN + 1), 0);
-        }
-#pragma unroll
-        for (int g = 0; g < NU_ * TN * 3; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 6, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            if (LOOK && g < PPW) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
-        slot = nslot;
-    }
-    wg_wait_vm<0>();   // (pieces past the end)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
-            }
-        }
+    }   // parts
 }
 
 template <int WM, int WN, int TM, int TN, int KP, int NST>
@@ -511,14 +595,14 @@ static void launch_gemm_wgrad_dma(GemmWgradParams& p, hipStream_t s) {
     p.n_stages = (int)(p.total / KP);
     const size_t lds = (size_t)NST * (BM + BN) * KP * 4;
     const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    const int G = p.G > 0 ? p.G : 1;
-    int S = 256 / (tiles * G);   // one 8-wave workgroup per CU (see launch_gemm_wgrad)
-    if (S > p.n_stages / 8) S = p.n_stages / 8;
-    if (S < 1) S = 1;
+    // one 8-wave workgroup per CU (see launch_gemm_wgrad), at least 8 stages each; grouped: over the flat stage space
+    // of the G groups (wg_split_part), so gridDim.x is the split of a TILE and no grid dimension carries the group
+    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages);
     auto kern = gemm_wgrad_dma_kernel<WM, WN, TM, TN, KP, NST>;
+    static_assert(wg_sole_argument(decltype(kern){}), "wg_operands_kernarg reads p from the kernel-argument segment");
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     p.mtiles = ceil_div(p.M, BM);
-    dim3 grid(S, ceil_div(p.N, BN), p.mtiles * G);
+    dim3 grid(S, ceil_div(p.N, BN), p.mtiles);
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
 }
 
@@ -545,22 +629,14 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, kk = lane >> 5;
-    // grouped launch (G > 0): blockIdx.z = group * mtiles + row tile; the groups share shapes and strides
-    const int grp = p.G > 0 ? (int)blockIdx.z / p.mtiles : 0;
-    const int m0 = (p.G > 0 ? (int)blockIdx.z - grp * p.mtiles : (int)blockIdx.z) * BM, n0 = blockIdx.y * BN;
-    const WgOperands ops_ = wg_operands(p, grp);
-    const float* const pa_ = ops_.a;
-    const float* const pb_ = ops_.b;
-    const float* const pb2_ = ops_.b2;
-    float* const pgw_ = ops_.gw;
+    const int m0 = blockIdx.z * BM, n0 = blockIdx.y * BN;
+    // the operands in hand (see gemm_wgrad_dma_kernel): the single gradient's, or those of the current part's group
+    const float* pa_ = p.a;
+    const float* pb_ = p.b;
+    const float* pb2_ = p.b2;
+    float* pgw_ = p.gw;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
     // ---- A: DMA pieces of this lane (rows 8 q .. 8 q + 7 of the tile, swizzled units: see gemm_wgrad_dma_kernel)
     const float* prow[PPW];
@@ -583,6 +659,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
     const float* uplane[BU];
     long uns[BU];
     int udy[BU], udx[BU];
+    bool uin1[BU];
 #pragma unroll
     for (int u = 0; u < BU; ++u) {
         int row = n0 + r0 + u * (NT / NU);
@@ -590,20 +667,21 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
         const int ci = row / 9, tap = row - ci * 9;
         udy[u] = tap / 3 - 1;
         udx[u] = tap % 3 - 1;
-        const bool first = ci < p.C1;
-        uplane[u] = first ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
-        uns[u] = first ? p.b_ns : p.b2_ns;
+        uin1[u] = ci < p.C1;
+        uplane[u] = uin1[u] ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
+        uns[u] = uin1[u] ? p.b_ns : p.b2_ns;
     }
     const unsigned uHW = (unsigned)p.HW;
     const int S = gridDim.x;
-    const int nmine = (p.n_stages - (int)blockIdx.x + S - 1) / S;
+    // my stages: first, first + step, ... (ungrouped: blockIdx.x, + S, ...; grouped: one part of my range)
+    int first = blockIdx.x, step = S, nmine = (p.n_stages - (int)blockIdx.x + S - 1) / S;
     float4 bst[BU][2];
     float bedge[BU];
     unsigned rowmask = 0, edgemask = 0;
     // loads of my stage t: DMA pieces of A into `slot`, B units into registers (clamped to my last stage)
     auto fetch = [&](int t, const int slot) {
         t = t < nmine ? t : nmine - 1;
-        const unsigned q0 = (unsigned)(blockIdx.x + t * S) * KP;
+        const unsigned q0 = (unsigned)(first + t * step) * KP;
         const unsigned f = q0 / uHW, px = q0 - f * uHW;
         const long offa = (long)f * p.a_ns + px;
 #pragma unroll
@@ -662,65 +740,100 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
     };
     const int brow = (wn * TN * 32 + l31) * RS + kk;
 
-    // prologue: stage 0 loaded and committed
-    fetch(0, 0);
-    commit(0);
-    int slot = 0;
-    for (int it = 0; it < nmine; ++it) {
-        wg_wait_vm<0>();                    // (my pieces of this stage: older than the B loads just committed)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();       // everybody's pieces and planes of stage `it`; the other slot / buffer is free
-        fetch(it + 1, slot ^ 1);
-        const unsigned char* sb = lds_raw + slot * ASLOT;
-        const bf16x8* Bh = Bbase + slot * 2 * BPLANE;
-        const bf16x8* Bl = Bh + BPLANE;
-        f32x4 ra[2][TM][2];
-        bf16x8 ah[2][TM], al[2][TM];
+    // one pass per part (see gemm_wgrad_dma_kernel)
+    WgPart part;
+    long pos = p.G > 0 ? wg_split_begin(p.G, p.n_stages, S, blockIdx.x) : 0;
+    for (int part_i = 0; p.G > 0 ? wg_split_part(p.G, p.n_stages, S, blockIdx.x, pos, part) : part_i == 0; ++part_i) {
+        if (p.G > 0) {
+            const WgOperands o = wg_operands_kernarg(part.grp);
 #pragma unroll
-        for (int i = 0; i < TM; ++i) rawA(sb, i, 0, ra[0][i]);
+            for (int j = 0; j < PPW; ++j) prow[j] = wg_rebase(prow[j], pa_, o.a);
 #pragma unroll
-        for (int i = 0; i < TM; ++i) wg_split8(ra[0][i][0], ra[0][i][1], ah[0][i], al[0][i]);
+            for (int u = 0; u < BU; ++u) uplane[u] = uin1[u] ? wg_rebase(uplane[u], pb_, o.b) : wg_rebase(uplane[u], pb2_, o.b2);
+            pa_ = o.a;
+            pb_ = o.b;
+            pb2_ = o.b2;
+            pgw_ = o.gw;
+            first = part.s0;
+            step = 1;
+            nmine = part.cnt;
+        }
+        if (part_i > 0) {
+            // the previous part's atomics have retired, its fragment reads have returned, and nobody reads the slot and the
+            // planes the prologue is about to fill
+            wg_wait_vm<0>();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
 #pragma unroll
-        for (int s_ = 0; s_ < NK; ++s_) {
-            const int cur = s_ & 1;
-            if (s_ + 1 < NK) {
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int i = 0; i < TM; ++i) rawA(sb, i, s_ + 1, ra[cur ^ 1][i]);
-            }
-            bf16x8 bh[TN], bl[TN];
+            for (int j = 0; j < TN; ++j)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                bh[j] = Bh[brow + j * 32 * RS + 2 * s_];
-                bl[j] = Bl[brow + j * 32 * RS + 2 * s_];
-            }
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+        // prologue: stage 0 loaded and committed
+        fetch(0, 0);
+        commit(0);
+        int slot = 0;
+        for (int it = 0; it < nmine; ++it) {
+            wg_wait_vm<0>();                    // (my pieces of this stage: older than the B loads just committed)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();       // everybody's pieces and planes of stage `it`; the other slot / buffer is free
+            fetch(it + 1, slot ^ 1);
+            const unsigned char* sb = lds_raw + slot * ASLOT;
+            const bf16x8* Bh = Bbase + slot * 2 * BPLANE;
+            const bf16x8* Bl = Bh + BPLANE;
+            f32x4 ra[2][TM][2];
+            bf16x8 ah[2][TM], al[2][TM];
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TM; ++i) rawA(sb, i, 0, ra[0][i]);
+#pragma unroll
+            for (int i = 0; i < TM; ++i) wg_split8(ra[0][i][0], ra[0][i][1], ah[0][i], al[0][i]);
+#pragma unroll
+            for (int s_ = 0; s_ < NK; ++s_) {
+                const int cur = s_ & 1;
+                if (s_ + 1 < NK) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) rawA(sb, i, s_ + 1, ra[cur ^ 1][i]);
+                }
+                bf16x8 bh[TN], bl[TN];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bh[j], acc[i][j], 0, 0, 0);
+                    bh[j] = Bh[brow + j * 32 * RS + 2 * s_];
+                    bl[j] = Bl[brow + j * 32 * RS + 2 * s_];
                 }
-            if (s_ + 1 < NK) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) wg_split8(ra[cur ^ 1][i][0], ra[cur ^ 1][i][1], ah[cur ^ 1][i], al[cur ^ 1][i]);
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][i], bh[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bl[j], acc[i][j], 0, 0, 0);
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bh[j], acc[i][j], 0, 0, 0);
+                    }
+                if (s_ + 1 < NK) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) wg_split8(ra[cur ^ 1][i][0], ra[cur ^ 1][i][1], ah[cur ^ 1][i], al[cur ^ 1][i]);
+                }
             }
+            commit(slot ^ 1);   // B planes of stage it + 1 (nobody reads that buffer before the next barrier)
+            slot ^= 1;
         }
-        commit(slot ^ 1);   // B planes of stage it + 1 (nobody reads that buffer before the next barrier)
-        slot ^= 1;
-    }
-    wg_wait_vm<0>();
+        wg_wait_vm<0>();
+        int m0e = m0, n0e = n0;   // (opaque per part: see gemm_wgrad_dma_kernel)
+        asm volatile("" : "+s"(m0e), "+s"(n0e));
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 32 + l31;
+            for (int j = 0; j < TN; ++j) {
+                const int n = n0e + (wn * TN + j) * 32 + l31;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
+                for (int r = 0; r < 16; ++r) {
+                    const int m = m0e + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                    if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
+                }
             }
-        }
+    }   // parts
 }
 
 template <int WM, int WN, int TM, int TN>
@@ -729,14 +842,12 @@ static void launch_gemm_wgrad_dma_impl(GemmWgradParams& p, hipStream_t s) {
     p.n_stages = (int)(p.total / 32);
     const size_t lds = (size_t)2 * BM * 128 + (size_t)2 * 2 * BN * 5 * 16;
     const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    const int G = p.G > 0 ? p.G : 1;
-    int S = 256 / (tiles * G);
-    if (S > p.n_stages / 8) S = p.n_stages / 8;
-    if (S < 1) S = 1;
+    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages);   // (see launch_gemm_wgrad_dma)
     auto kern = gemm_wgrad_dma_impl_kernel<WM, WN, TM, TN>;
+    static_assert(wg_sole_argument(decltype(kern){}), "wg_operands_kernarg reads p from the kernel-argument segment");
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     p.mtiles = ceil_div(p.M, BM);
-    dim3 grid(S, ceil_div(p.N, BN), p.mtiles * G);
+    dim3 grid(S, ceil_div(p.N, BN), p.mtiles);
     hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
 }
 
@@ -827,6 +938,25 @@ static WgradB3Route choose_wgrad_implicit(const GemmWgradParams& p) {
 }
 extern "C" const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W) {
     return kWgradB3Labels[choose_wgrad_implicit(wgrad_shape(Cout, 0, g_ns, 0, G, F, H * W))];
+}
+
+// K split of the grouped ring launches, as queries that launch nothing: the workgroups per output tile the launchers
+// start, and the parts (group, first stage, count) of workgroup w of Wt -- the very functions the kernels run
+extern "C" int rfn_wgrad_split_workgroups(int tiles, int G, int n_stages) {
+    RFN_CHECK_ARG(tiles >= 1 && G >= 1 && G <= 16 && n_stages >= 1, -1);
+    return wg_split_workgroups(tiles, G, n_stages);
+}
+extern "C" int rfn_wgrad_split_parts(int G, int n_stages, int Wt, int w, long long* parts, int max_parts) {
+    RFN_CHECK_ARG(G >= 1 && G <= 16 && n_stages >= 1 && Wt >= 1 && w >= 0 && w < Wt && (parts || max_parts == 0), -1);
+    int n = 0;
+    WgPart part;
+    for (long pos = wg_split_begin(G, n_stages, Wt, w); wg_split_part(G, n_stages, Wt, w, pos, part); ++n)
+        if (n < max_parts) {
+            parts[3 * n] = part.grp;
+            parts[3 * n + 1] = part.s0;
+            parts[3 * n + 2] = part.cnt;
+        }
+    return n;
 }
 
 static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s) {

@@ -83,6 +83,8 @@ SIGNATURES = {
                                           _c_s],
     "rfn_gemm_wgrad_kernel_label_bf16x3": [_c_i, _c_i, _c_l, _c_l, _c_i, _c_i, _c_i],
     "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i],
+    "rfn_wgrad_split_workgroups": [_c_i, _c_i, _c_i],
+    "rfn_wgrad_split_parts": [_c_i, _c_i, _c_i, _c_i, ctypes.c_void_p, _c_i],
     "rfn_im2col3x3_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
     "rfn_packed_weight_size": [_c_i, _c_i, _c_i],
     "rfn_pack_conv_weight_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],

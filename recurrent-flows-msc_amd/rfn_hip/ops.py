@@ -491,7 +491,33 @@ def gemm_wgrad_grouped(a_list, b_list, M, Nc, arena=None):
     return gw
 
 
-GROUPED_WGRAD_MAX_PIX = 100000  # below this many pixels a single weight gradient is a latency-class launch
+_grouped_wgrad_budget = {}  # device index -> bytes
+
+
+def grouped_wgrad_budget(device):
+    """bytes of operands a flow level may keep alive to compute its 3 K weight gradients in grouped launches:
+    RFN_WGRAD_GROUPED_MAX_BYTES, or one eighth of the device's memory (read once per device)"""
+    env = os.environ.get("RFN_WGRAD_GROUPED_MAX_BYTES")
+    if env is not None:
+        return int(env)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _grouped_wgrad_budget:
+        _grouped_wgrad_budget[idx] = torch.cuda.get_device_properties(idx).total_memory // 8
+    return _grouped_wgrad_budget[idx]
+
+
+def grouped_wgrad_retained_bytes(Kn, N, Hd, HW, o_numel):
+    """what deferring the weight gradients of a level of Kn steps keeps alive until the level ends: the two hidden
+    gradients gh1, gh2 [N, Hd, HW] of every step, and the Kn conv3-output gradients stacked in one buffer (o_numel
+    elements each); h1 / h2 and the step inputs are saved tensors either way"""
+    return 4 * Kn * (2 * N * Hd * HW + o_numel)
+
+
+def group_level_wgrad(Kn, N, Hd, HW, o_numel, device):
+    """grouped launches add no atomic bytes and idle no CU at any shape (the ring kernels split the flat stage space of
+    the groups evenly): memory is the only reason not to group.  RFN_WGRAD_GROUPED=0: one launch per step."""
+    return (1 < Kn <= 16 and os.environ.get("RFN_WGRAD_GROUPED") != "0" and
+            grouped_wgrad_retained_bytes(Kn, N, Hd, HW, o_numel) <= grouped_wgrad_budget(device))
 
 
 def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_stacked=None):
@@ -1116,17 +1142,14 @@ class GlowLevelFn(torch.autograd.Function):
         # last step: stand-alone coupling backward; earlier steps get theirs from the fused shell launch below
         (_, _, _, _, _, _, _, _, _, _, l3, scale, scale_shift) = prm[Kn - 1]
         # (with deferred weight gradients the K conv3-output gradients live in one buffer: one tap-scatter for all)
-        go_all = (torch.empty((Kn,) + tuple(os_[0].shape), device=x.device, dtype=torch.float32)
-                  if (N * HW <= GROUPED_WGRAD_MAX_PIX and 1 < Kn <= 16 and os.environ.get("RFN_WGRAD_GROUPED") != "0")
-                  else None)
+        grouped = group_level_wgrad(Kn, N, int(w1.shape[0]), HW, os_[0].numel(), x.device)
+        go_all = torch.empty((Kn,) + tuple(os_[0].shape), device=x.device, dtype=torch.float32) if grouped else None
         gz, go, gscale, gshift, gb3, gl3 = _affine_zeros_bwd(outs[Kn - 1], os_[Kn - 1], gout, gdl, scale, scale_shift, l3,
                                                             clamp_type, arena, None if go_all is None else go_all[Kn - 1])
         gx = None
-        # latency-class levels (deep levels, small batches): the 3 K weight gradients are computed at the end, K of one
-        # shape per launch (their operands stay alive until then: a few hundred MB at most)
-        defer = ({"w1": [], "w2": [], "w3": []}
-                 if (N * HW <= GROUPED_WGRAD_MAX_PIX and 1 < Kn <= 16 and os.environ.get("RFN_WGRAD_GROUPED") != "0")
-                 else None)
+        # the 3 K weight gradients are computed at the end, K of one shape per launch (one atomic tail per launch
+        # instead of K); their operands stay alive until then, which is what group_level_wgrad budgets
+        defer = {"w1": [], "w2": [], "w3": []} if grouped else None
         for k in range(Kn - 1, -1, -1):
             (an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift) = prm[k]
             nfin = len(fin)

@@ -1,11 +1,15 @@
 """developer probe: the big weight-gradient GEMMs of the shallow flow levels (N = 608 frames), LDS-DMA ring kernel
-against the register-staged one.  python tools/bench_wgrad.py   (RFN_WGRAD_DMA=0 for the register-staged kernel)"""
+against the register-staged one.  python tools/bench_wgrad.py   (RFN_WGRAD_DMA=0 for the register-staged kernel)
+python tools/bench_wgrad.py level [frames ...]: the three weight gradients of a Glow step at flow levels 0 - 2 (K = 10
+steps per level), as ten single launches and as one grouped launch, GEMM launches only (HIP events of rfn_hip.lib.PROFILE).
+RFN_PKG_DIR selects another build of the package (A/B on the same box, as bench.py)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "recurrent-flows-msc_amd")):
+for p in (ROOT, os.environ.get("RFN_PKG_DIR") or os.path.join(ROOT, "recurrent-flows-msc_amd")):
     sys.path.insert(0, p)
 import torch
 from rfn_hip import ops as K
+from rfn_hip import lib as L
 
 
 def run(F_, M, Nc, S, reps=10):
@@ -42,7 +46,51 @@ def run_implicit(F_, C1, C2, S, reps=10):
     print("F%d 256x%d %dx%d implicit3x3  %.3f ms  %.2f TB/s" % (F_, 9 * (C1 + C2), S, S, dt * 1e3, by / dt / 1e12), flush=True)
 
 
+def _wgrad_ms(fn, reps=5):
+    """fn() reps times after one warm-up: (median over the reps of the summed weight-gradient GEMM time in ms, launches
+    per call, label of the first)"""
+    fn()
+    torch.cuda.synchronize()
+    sums = []
+    for _ in range(reps):
+        L.PROFILE = []
+        fn()
+        torch.cuda.synchronize()
+        ev = [(m[1], e0.elapsed_time(e1)) for (_, m, e0, e1) in L.PROFILE if m is not None and m[0] == "wgrad"]
+        L.PROFILE = None
+        sums.append(sum(t for _, t in ev))
+    sums.sort()
+    return sums[len(sums) // 2], len(ev), ev[0][0]
+
+
+def level(F_, G=10):
+    """conv1 (3x3, C/2 + cond -> 256), conv2 (1x1, 256 -> 256), conv3 (3x3, 256 -> C) of levels 0 - 2"""
+    torch.manual_seed(0)
+    rn = lambda *shape: torch.randn(*shape, device="cuda")
+    for lvl, (C, Cc, S) in enumerate([(4, 16, 32), (8, 32, 16), (16, 64, 8)]):
+        h = [rn(F_, 256, S, S) for _ in range(G)]       # h1 / h2 stand-ins
+        gh = [rn(F_, 256, S, S) for _ in range(G)]      # gh1 / gh2 stand-ins
+        z = [rn(F_, C, S, S) for _ in range(G)]
+        cond = rn(F_, Cc, S, S)
+        go = rn(G, F_, C, S, S)
+        cases = [("conv1 256x%d" % (9 * (C // 2 + Cc)), [t[:, :C // 2] for t in z], [cond] * G, gh, 256, 3, None),
+                 ("conv2 256x256", h, None, gh, 256, 1, None),
+                 ("conv3 %dx256" % (9 * C), h, None, [go[i] for i in range(G)], C, 3, go)]
+        for name, in1, in2, gl, Cout, ks, stacked in cases:
+            one = lambda: [K.conv2d_wgrad(in1[i], None if in2 is None else in2[i], gl[i], Cout, ks) for i in range(G)]
+            grp = lambda: K.conv2d_wgrad_grouped(in1, in2, gl, Cout, ks, g_stacked=stacked)
+            t1, n1, l1 = _wgrad_ms(one)
+            tg, ng, lg = _wgrad_ms(grp)
+            print("F%d level %d %-14s  %d singles %7.3f ms (%s)   grouped G%d %7.3f ms in %d launch (%s)" % (
+                F_, lvl, name, n1, t1, l1, G, tg, ng, lg), flush=True)
+        del h, gh, z, cond, go
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "level":
+        for F_ in [int(v) for v in sys.argv[2:]] or [608, 76]:
+            level(F_)
+        sys.exit(0)
     run_implicit(608, 2, 16, 32)
     run_implicit(608, 4, 32, 16)
     run(608, 256, 256, 32)
