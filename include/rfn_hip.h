@@ -523,11 +523,41 @@ typedef struct rfn_adam_entry {
     float* v;
     long n;
     int step_offset;
-    int reserved;
+    int flags; /* bit 0: this tensor's gradient is rank-local (see rfn_grad_sumsq_f32); 0 in tables built before it existed */
 } rfn_adam_entry;
 int rfn_adam_chunk_elems(void);
 int rfn_adam_step_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1, double beta2,
                       double eps, double weight_decay, int t, rfn_stream_t stream);
+
+/* ---- guard of the Adam step: global gradient-norm clipping and "skip the step if the gradients are not finite", decided
+ * on the device from the same `table` and `chunks` (no host read; sumsq -> [all-reduce of sumsq[1] under data parallelism]
+ * -> guard -> guarded step).
+ *
+ * rfn_grad_sumsq_f32: sumsq[0] = sum of g^2 over the tensors whose flags bit 0 is clear, sumsq[1] = over those with it
+ * set.  `partials` is a caller-provided workspace of n_chunks floats.  Two launches: one workgroup per chunk stores that
+ * chunk's partial (<= 32 serial fp32 adds per lane, then a fixed tree), one workgroup adds the partials in a fixed order
+ * in double and rounds once.  No float atomics: equal inputs give bit-identical results on every run and every rank.
+ *
+ * rfn_grad_guard_f32 (one tiny launch): with s = sumsq[0] + sumsq[1] in double,
+ *   stats[0] = norm  = sqrt(s), rounded to float;
+ *   stats[1] = scale = min(1, max_norm / (norm + 1e-6)) in double, rounded once (torch's clip_grad_norm_); 1 when
+ *              max_norm <= 0;
+ *   stats[2] = 1.0 if skip_nonfinite != 0 and the norm is not finite, else 0.0; then *skipped is incremented.
+ * A sum of squares that overflows fp32 COUNTS AS NON-FINITE, although a wider format could still hold it: the partial
+ * sums are fp32, and s itself is tested after rounding to float.
+ *
+ * rfn_adam_step_guarded_f32: rfn_adam_step_f32 with three differences.  stats[2] != 0: nothing is written (p, m, v keep
+ * their bits).  The gradient used is stats[1] * g, applied before weight decay (clipping precedes the optimizer); g is
+ * never written.  A tensor's step count is t - step_offset - *skipped, so bias correction does not advance over skipped
+ * steps.  With stats[1] == 1.0f and *skipped == 0 the update is bit-identical to rfn_adam_step_f32.  `skipped` is only
+ * read here. */
+int rfn_grad_sumsq_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, float* partials, float* sumsq,
+                       rfn_stream_t stream);
+int rfn_grad_guard_f32(const float* sumsq, double max_norm, int skip_nonfinite, float* stats, long long* skipped,
+                       rfn_stream_t stream);
+int rfn_adam_step_guarded_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1,
+                              double beta2, double eps, double weight_decay, int t, const float* stats,
+                              long long* skipped, rfn_stream_t stream);
 
 /* ---- video-prediction quality of uint8 frames  (evaluation_metrics/error_metrics.py:154-171, Evaluator.eval_seq: skimage
  * 0.17.2 `structural_similarity` / `peak_signal_noise_ratio` per channel, with their defaults on uint8: 7x7 uniform window,

@@ -54,6 +54,13 @@ class Solver(object):
         self.plot_counter, self.epoch_i, self.counter = 0, 0, 0
         self.losses, self.kl_loss, self.recon_loss, self.bits = [], [], [], []
         self.best_loss, self.beta, self.stop = 1e15, args.beta_min, False
+        # the guard of the optimizer step (Namespaces saved before these flags existed do not have them: all off)
+        self.grad_clip_norm = float(getattr(args, "grad_clip_norm", 0.0) or 0.0)
+        self.skip_nonfinite_steps = bool(getattr(args, "skip_nonfinite_steps", False))
+        self.max_skipped_steps = int(getattr(args, "max_skipped_steps", 100))
+        self.guard_on = self.grad_clip_norm > 0.0 or self.skip_nonfinite_steps
+        self._host_guard = {"grad_norm": 0.0, "scale": 1.0, "skipped_steps": 0}   # CPU parameters only
+        self._guard_last, self._skipped_before_epoch = None, 0
         self.rank = int(os.environ.get("RANK", 0))
         self.world = int(os.environ.get("WORLD_SIZE", 1))
         self.device = set_gpu(True)
@@ -76,20 +83,29 @@ class Solver(object):
         self.model = RFN(self.args).to(self.device)
         rdist.broadcast_module_state(self.model)
         self.reducer = rdist.GradBucketReducer(list(self.model.named_parameters()))
-        self.optimizer = self.make_optimizer(self.model.parameters(), self.learning_rate)
+        self.optimizer = self.make_optimizer(self.model.parameters(), self.learning_rate, **self.guard_kwargs())
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, "min", patience=self.patience_lr,
                                                                     factor=self.factor_lr, min_lr=self.min_lr)
         self.earlystopping = EarlyStopping(min_delta=0, patience=self.patience_es, verbose=self.verbose)
         self.counter, self.stop = 0, False
 
+    def guard_kwargs(self):
+        """the guard's keywords for `make_optimizer`, from --grad_clip_norm / --skip_nonfinite_steps; the batch-sharded
+        initial states are the tensors whose gradients are rank-local"""
+        return dict(max_grad_norm=self.grad_clip_norm, skip_nonfinite=self.skip_nonfinite_steps,
+                    rank_local=tuple(self.reducer.sharded))
+
     @staticmethod
-    def make_optimizer(params, lr):
+    def make_optimizer(params, lr, max_grad_norm=0.0, skip_nonfinite=False, rank_local=(), group=None):
         """RFN/trainer.py:96: Adam with torch's defaults.  On the GPU the whole update is one launch of the HIP kernel
-        (rfn_hip.optim.HipAdam, same state layout as torch.optim.Adam); CPU parameters only occur in host-logic tests."""
+        (rfn_hip.optim.HipAdam, same state layout as torch.optim.Adam) and the guard, when asked for, runs in front of it
+        on the device; CPU parameters only occur in host-logic tests, where torch.optim.Adam steps and
+        `Solver.optimizer_step` guards it with a few torch ops."""
         params = list(params)
         if params and params[0].is_cuda:
             from rfn_hip.optim import HipAdam
-            return HipAdam(params, lr=lr)
+            return HipAdam(params, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                           rank_local=rank_local, group=group)
         return torch.optim.Adam(params, lr=lr)
 
     def create_loaders(self):
@@ -198,11 +214,50 @@ class Solver(object):
         loss = nll + self.beta * kl_free_bit
         kl_store, nll_store = kl.detach(), nll.detach()
         bits = (kl_store + nll_store) / (np.log(2.) * float(np.prod(list(dims))) * t)
-        self.bits.append(float(bits))
-        self.losses.append(float(loss.detach()) / t)
-        self.kl_loss.append(float(kl_store) / t)
-        self.recon_loss.append(float(nll_store) / t)
+        self._log_step(float(bits), float(loss.detach()) / t, float(kl_store) / t, float(nll_store) / t)
         return loss
+
+    def _log_step(self, bits, loss, kl, nll):
+        """one step's scalars into the histories.  With --skip_nonfinite_steps a step whose scalars are not finite (the
+        optimizer skips it) leaves no trace, so the epoch mean that drives early stopping and the plateau scheduler
+        survives it."""
+        if self.skip_nonfinite_steps and not all(math.isfinite(v) for v in (bits, loss, kl, nll)):
+            return
+        self.bits.append(bits)
+        self.losses.append(loss)
+        self.kl_loss.append(kl)
+        self.recon_loss.append(nll)
+
+    def optimizer_step(self):
+        """optimizer.step() behind the guard.  HipAdam carries the guard itself (on the device, no host read).  For CPU
+        parameters the same semantics in torch ops: global norm with the rank-local part summed over ranks, skip when
+        it is not finite (an fp32 overflow of the sum of squares counts), scale by min(1, max / (norm + 1e-6))."""
+        opt = self.optimizer
+        if not self.guard_on or hasattr(opt, "guard_stats"):
+            return opt.step()
+        grads = [p.grad for g in opt.param_groups for p in g["params"] if p.grad is not None]
+        local = {id(p.grad) for p in self.reducer.sharded if p.grad is not None}
+        sq = torch.zeros(2, dtype=torch.float64)
+        for g in grads:
+            sq[int(id(g) in local)] += g.detach().double().pow(2).sum().cpu()
+        if rdist.is_dist() and self.reducer.sharded:
+            rdist.all_reduce_sum_(sq[1:2])
+        total = float(sq.sum())
+        norm = math.sqrt(total) if total >= 0.0 else math.nan
+        scale = min(1.0, self.grad_clip_norm / (norm + 1e-6)) if self.grad_clip_norm > 0.0 else 1.0
+        self._host_guard.update(grad_norm=norm, scale=scale)
+        if self.skip_nonfinite_steps and not (total <= float(torch.finfo(torch.float32).max)):
+            self._host_guard["skipped_steps"] += 1
+            return None
+        if scale != 1.0:
+            torch._foreach_mul_(grads, scale)
+        return opt.step()
+
+    def guard_stats(self):
+        """{"grad_norm", "scale", "skipped_steps"}: one device->host read with HipAdam"""
+        if hasattr(self.optimizer, "guard_stats"):
+            return self.optimizer.guard_stats()
+        return dict(self._host_guard)
 
     # ---------------------------------------------------------------------------------------------- loop
     def train_step(self, image):
@@ -220,7 +275,7 @@ class Solver(object):
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.reducer.finish()
-        self.optimizer.step()
+        self.optimizer_step()
         if self.scheduler_type == "linear":
             self.adjust_learning_rate(self.counter)
         self.counter += 1
@@ -298,7 +353,7 @@ class Solver(object):
             mark(); self._g_in.copy_(image, non_blocking=True); self._g_beta.fill_(self.beta)
             mark(); self._graph.replay()
             mark(); self.reducer.finish()
-            mark(); self.optimizer.step()
+            mark(); self.optimizer_step()
             mark()
             print("[step %d rank %d] copy %.3f replay %.3f reduce %.3f adam %.3f s" % (
                 self.counter, self.rank, ts[1] - ts[0], ts[2] - ts[1], ts[3] - ts[2], ts[4] - ts[3]), flush=True)
@@ -307,7 +362,7 @@ class Solver(object):
             self._g_beta.fill_(self.beta)
             self._graph.replay()
             self.reducer.finish()
-            self.optimizer.step()
+            self.optimizer_step()
         if self.scheduler_type == "linear":
             self.adjust_learning_rate(self.counter)
         self.counter += 1
@@ -321,10 +376,7 @@ class Solver(object):
         out, shape = self._pending_log
         loss, _, kl, nll = [float(v) for v in out.tolist()]
         t = shape[1] - 1
-        self.bits.append((kl + nll) / (np.log(2.) * float(np.prod(shape[2:])) * t))
-        self.losses.append(loss / t)
-        self.kl_loss.append(kl / t)
-        self.recon_loss.append(nll / t)
+        self._log_step((kl + nll) / (np.log(2.) * float(np.prod(shape[2:])) * t), loss / t, kl / t, nll / t)
         self._pending_log = None
 
     def train(self):
@@ -341,6 +393,8 @@ class Solver(object):
                     self.stop = True
                     break
             self.flush_log()   # graph mode keeps the last step's scalars on the device until asked
+            if self.guard_on:
+                self._end_of_epoch_guard()   # (may set self.stop: before the consensus below)
             plot_every = getattr(self.args, "plot_every", 0)   # (Namespaces saved before the flag existed)
             if plot_every > 0 and self.epoch_i % plot_every == 0:
                 self.plotter()   # (rank 0 only, no collective, leaves model, RNG states and counters as they were)
@@ -363,6 +417,22 @@ class Solver(object):
                 print("Epoch {} Loss: {:.2f}".format(self.epoch_i, epoch_loss))
             elif self.rank == 0:
                 self.status()
+
+    def _end_of_epoch_guard(self):
+        """read the guard once per epoch; more than --max_skipped_steps skipped steps in one epoch end the training after
+        this epoch's checkpoint (whose weights are finite: a skipped step writes nothing)"""
+        gs = self._guard_last = self.guard_stats()
+        skipped = gs["skipped_steps"] - self._skipped_before_epoch
+        self._skipped_before_epoch = gs["skipped_steps"]
+        if skipped > self.max_skipped_steps:
+            self.stop = True
+            why = "STOP: %d steps of epoch %d were skipped for non-finite gradients (--max_skipped_steps %d)" % (
+                skipped, self.epoch_i, self.max_skipped_steps)
+            if self.rank == 0:
+                with open(self.path + "model_folder/status.txt", "a") as f:
+                    print(why, file=f)
+            if self.verbose:
+                print(why)
 
     # ---------------------------------------------------------------------------------------------- sheets
     def _plot_rows(self, image):
@@ -469,6 +539,8 @@ class Solver(object):
         # the file holds the moments of the GLOBAL rows of the batch-sharded initial states: every rank takes its own
         # (torch's load_state_dict does not compare shapes, and HipAdam indexes the moments by the parameter's numel)
         self.optimizer.load_state_dict(rdist.shard_optimizer_state(load_model["optimizer_state_dict"], self.model))
+        # (the count of skipped steps restarts with the loaded state, in HipAdam and for CPU parameters)
+        self._skipped_before_epoch = self._host_guard["skipped_steps"] = 0
         self.epoch_i += load_model["epoch"]
         loss = load_model["loss"]
         self.kl_loss, self.recon_loss = load_model["kl_loss"], load_model["recon_loss"]
@@ -486,3 +558,6 @@ class Solver(object):
                 print("\tKL and Reconstruction loss: {:.4f}, {:.4f}".format(self.kl_loss[-1], self.recon_loss[-1]),
                       file=f)
             print(f"\tEpoch {self.epoch_i}, Beta value {self.beta:.4f}, Learning rate {lr}", file=f)
+            if self.guard_on and self._guard_last is not None:
+                print("\tGradient norm {:.4g}, skipped steps {}".format(self._guard_last["grad_norm"],
+                                                                        self._guard_last["skipped_steps"]), file=f)

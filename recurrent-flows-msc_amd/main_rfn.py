@@ -9,7 +9,11 @@ a job script written for the reference drives this implementation unchanged.  Ad
                      `bair_robot_data/processed_data/` / `kth_data` in the working directory; never downloaded);
   --data_cache       directory for the packed frame stores of BAIR / KTH (decoded once, reused while the files match);
   --plot_every       write a sheet of ground truth, samples, predictions and reconstructions of one test sequence to
-                     `png_folder/samples<k>.png` after every N-th epoch (default 0: never).
+                     `png_folder/samples<k>.png` after every N-th epoch (default 0: never);
+  --grad_clip_norm   clip the global gradient norm to this value before every Adam step (default 0: off);
+  --skip_nonfinite_steps   leave parameters and Adam moments untouched on a step whose gradients are not finite, and keep
+                     that step out of the loss histories (default off);
+  --max_skipped_steps      end the training after an epoch in which more steps than this were skipped (default 100).
 Without `--synthetic_data` the datasets live on the GPU and a batch is one kernel launch, with no DataLoader workers:
 Stochastic Moving MNIST is rendered (`--choose_data mnist`), BAIR push and KTH clips are gathered from the packed frames.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main_rfn.py ... --multigpu`; one process
@@ -156,6 +160,12 @@ def build_parser():
     p.add_argument("--data_cache", help="Directory for the packed frame stores of --choose_data bair / kth",
                    default=None, type=str)
     p.add_argument("--plot_every", help="Write png_folder/samples<k>.png after every N-th epoch (0 = never)", default=0,
+                   type=int)
+    p.add_argument("--grad_clip_norm", help="Clip the global gradient norm to this value before the Adam step (0 = off)",
+                   default=0.0, type=float)
+    add_bool_arg(p, "skip_nonfinite_steps", default=False,
+                 help="Skip the Adam step, on the device, when the gradients are not finite")
+    p.add_argument("--max_skipped_steps", help="Stop after an epoch with more skipped steps than this", default=100,
                    type=int)
     return p
 

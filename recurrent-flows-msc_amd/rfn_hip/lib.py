@@ -132,6 +132,10 @@ SIGNATURES = {
     "rfn_adam_chunk_elems": [],
     "rfn_adam_step_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, ctypes.c_double, _c_i, _c_s],
+    "rfn_grad_sumsq_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_f, _c_f, _c_s],
+    "rfn_grad_guard_f32": [_c_f, ctypes.c_double, _c_i, _c_f, ctypes.c_void_p, _c_s],
+    "rfn_adam_step_guarded_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i, _c_f, ctypes.c_void_p, _c_s],
     "rfn_convlstm_gates_fwd_f32": [_c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i,
                                    _c_s],
     "rfn_convlstm_gates_bwd_f32": [_c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f,

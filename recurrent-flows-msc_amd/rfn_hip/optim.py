@@ -5,7 +5,17 @@ by either load into the other (the reference's rfn.pt holds `optimizer_state_dic
 
 The kernel reads a device table of (p, g, m, v, numel, step offset) per tensor.  The table is rebuilt whenever a pointer
 changed: never in hipGraph mode (the gradient tensors are the graph's static outputs), every step in eager mode (autograd
-allocates fresh gradients), where the rebuild is one small host-to-device copy next to ~7000 eager launches."""
+allocates fresh gradients), where the rebuild is one small host-to-device copy next to ~7000 eager launches.
+
+The guard (`max_grad_norm` > 0 and / or `skip_nonfinite`; both off by default, and then step() is exactly the plain launch)
+decides on the device: rfn_grad_sumsq_f32 -> rfn_grad_guard_f32 -> rfn_adam_step_guarded_f32 over the same table, clipping
+to the global gradient norm (torch's clip_grad_norm_ formula) and leaving p, m, v untouched when the norm is not finite.
+The host never learns of a skip on the step path: the kernels count skipped steps in a device counter and take it out of
+the bias corrections; the host's step counts are settled against that counter where a read is allowed anyway (table
+rebuild, state_dict(), guard_stats()).  Under data parallelism the squares of the rank-local gradients (`rank_local`, the
+batch-sharded initial states; GradBucketReducer.finish() has divided them by the world size) are summed over ranks with
+one scalar all-reduce, which gives every rank the norm of one process on the global batch, bit for bit, and hence the
+same decision."""
 import ctypes
 
 import numpy as np
@@ -15,9 +25,20 @@ from . import lib as L
 
 
 class HipAdam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
+                 skip_nonfinite=False, rank_local=(), group=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, foreach=False,
                          fused=False)
+        self.max_grad_norm = float(max_grad_norm)
+        if not self.max_grad_norm >= 0.0:
+            raise ValueError("HipAdam: max_grad_norm must be >= 0 (0 = no clipping), got %r" % (max_grad_norm,))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guarded = self.max_grad_norm > 0.0 or self.skip_nonfinite
+        self._rank_local = {id(p) for p in rank_local}
+        self._group = group
+        self._gbuf = None     # guard on: 8 device floats = stats[0:3] | pad | sumsq[4:6] | skipped counter (int64) at [6:8]
+        self._guard = None    # (partials, stats, sumsq, skipped, all-reduce sumsq[1]?) for the current table
+        self._settled = 0     # skipped steps already taken out of _steps
         self._key = None
         self._keep = None
         self._t = 0           # kernel step counter; a tensor's own count is _t - its step_offset
@@ -25,7 +46,36 @@ class HipAdam(torch.optim.Adam):
         self._dirty = False
 
     # ---- torch-visible state -------------------------------------------------------------------------------------
-    def _sync_step_tensors(self):
+    def _settle_skipped(self, gbuf_host=None):
+        """take the steps the device skipped since the last look out of the host's counts (one device->host read).  The
+        tensors of the current table are the ones that took part in every call since it was built."""
+        if self._gbuf is None:
+            return
+        if gbuf_host is None:
+            gbuf_host = self._gbuf.cpu()
+        total = int(gbuf_host[6:8].view(torch.int64))
+        delta = total - self._settled
+        if delta and self._keep is not None:
+            for p in self._keep[3]:
+                if id(p) in self._steps:
+                    self._steps[id(p)] -= delta
+            self._dirty = True
+        self._settled = total
+
+    def guard_stats(self):
+        """{"grad_norm", "scale", "skipped_steps"} of the last guarded step / of all steps since construction or
+        load_state_dict: one device->host read, for the end of an epoch and for tests.  Also brings state["step"] up to
+        date."""
+        if self._gbuf is None:
+            return {"grad_norm": 0.0, "scale": 1.0, "skipped_steps": 0}
+        h = self._gbuf.cpu()
+        self._settle_skipped(h)
+        self._sync_step_tensors(settle=False)
+        return {"grad_norm": float(h[0]), "scale": float(h[1]), "skipped_steps": self._settled}
+
+    def _sync_step_tensors(self, settle=True):
+        if settle:
+            self._settle_skipped()
         if self._dirty:
             for group in self.param_groups:
                 for p in group["params"]:
@@ -41,11 +91,17 @@ class HipAdam(torch.optim.Adam):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._key, self._steps, self._dirty = None, {}, False
+        self._keep = self._gbuf = self._guard = None   # the skipped-step counter restarts with the loaded counts
+        self._settled = 0
 
     # ---- the step ------------------------------------------------------------------------------------------------
     def _build(self, group, params, key):
         dev = params[0].device
         chunk = int(L.load().rfn_adam_chunk_elems())
+        if self.guarded:
+            if self._gbuf is None:
+                self._gbuf = torch.zeros(8, dtype=torch.float32, device=dev)
+            self._settle_skipped()   # (the previous table's tensors; a read is allowed here)
         ent = np.zeros((len(params), 6), dtype=np.int64)   # rfn_adam_entry: 4 pointers, long n, (int offset, int pad)
         chunks = []
         for i, p in enumerate(params):
@@ -66,8 +122,10 @@ class HipAdam(torch.optim.Adam):
                 if t.numel() != n:   # e.g. moments of another batch size loaded from a checkpoint: the kernel indexes by n
                     raise RuntimeError("HipAdam: %s has %d elements, its parameter %d (shape %s)" %
                                        (name, t.numel(), n, tuple(p.shape)))
-            off = self._t - self._steps[id(p)]
-            ent[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, off & 0xFFFFFFFF)
+            # the guarded kernel subtracts the device's running count of skipped steps as well
+            off = self._t - self._steps[id(p)] - self._settled
+            flags = 1 if id(p) in self._rank_local else 0
+            ent[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, (off & 0xFFFFFFFF) | (flags << 32))
             nck = (n + chunk - 1) // chunk
             chunks.append(np.stack([np.full(nck, i, dtype=np.int32), np.arange(nck, dtype=np.int32)], 1))
         chunks = np.concatenate(chunks, 0) if chunks else np.zeros((0, 2), np.int32)
@@ -75,6 +133,12 @@ class HipAdam(torch.optim.Adam):
         chk_d = torch.from_numpy(np.ascontiguousarray(chunks).reshape(-1)).to(dev)
         self._keep = (tab_d, chk_d, int(chunks.shape[0]), list(params), 28.0 * sum(p.numel() for p in params))
         self._key = key
+        if self.guarded:
+            import torch.distributed as dist
+            from . import dist as rdist
+            partials = torch.empty(max(1, int(chunks.shape[0])), dtype=torch.float32, device=dev)
+            reduce_local = bool(self._rank_local) and rdist.is_dist() and dist.get_world_size(self._group) > 1
+            self._guard = (partials, self._gbuf[0:3], self._gbuf[4:6], self._gbuf[6:8], reduce_local)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -104,6 +168,10 @@ class HipAdam(torch.optim.Adam):
             self._steps[id(p)] += 1
         self._dirty = True
         beta1, beta2 = group["betas"]
+        if self.guarded:
+            self._guarded_launches(group, beta1, beta2)
+            torch.autograd.graph.increment_version(plist)
+            return loss
         L.call("rfn_adam_step_f32", ctypes.c_void_p(tab_d.data_ptr()), ctypes.c_void_p(chk_d.data_ptr()), ctypes.c_int(nck),
                ctypes.c_double(float(group["lr"])), ctypes.c_double(beta1), ctypes.c_double(beta2),
                ctypes.c_double(group["eps"]), ctypes.c_double(group["weight_decay"]), ctypes.c_int(self._t),
@@ -112,3 +180,21 @@ class HipAdam(torch.optim.Adam):
         # `p._version` relies on (ListGlow._reverse_cache, RFN._gen_graph: cached inverse matrices / packs / hipGraph)
         torch.autograd.graph.increment_version(plist)
         return loss
+
+    def _guarded_launches(self, group, beta1, beta2):
+        """sumsq -> (rank-local part summed over ranks) -> guard -> guarded Adam; nothing here reads from the device"""
+        from . import dist as rdist
+        tab_d, chk_d, nck, plist, nbytes = self._keep
+        partials, stats, sumsq, skipped, reduce_local = self._guard
+        tab, chk = ctypes.c_void_p(tab_d.data_ptr()), ctypes.c_void_p(chk_d.data_ptr())
+        L.call("rfn_grad_sumsq_f32", tab, chk, ctypes.c_int(nck), ctypes.c_void_p(partials.data_ptr()),
+               ctypes.c_void_p(sumsq.data_ptr()), meta=("shell", "grad_sumsq", 0.0, "%d tensors" % len(plist), nbytes / 7.0))
+        if reduce_local:
+            rdist.all_reduce_sum_(sumsq[1:2], group=self._group)
+        L.call("rfn_grad_guard_f32", ctypes.c_void_p(sumsq.data_ptr()), ctypes.c_double(self.max_grad_norm),
+               ctypes.c_int(int(self.skip_nonfinite)), ctypes.c_void_p(stats.data_ptr()),
+               ctypes.c_void_p(skipped.data_ptr()), meta=("shell", "grad_guard", 0.0, "", 0.0))
+        L.call("rfn_adam_step_guarded_f32", tab, chk, ctypes.c_int(nck), ctypes.c_double(float(group["lr"])),
+               ctypes.c_double(beta1), ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
+               ctypes.c_double(group["weight_decay"]), ctypes.c_int(self._t), ctypes.c_void_p(stats.data_ptr()),
+               ctypes.c_void_p(skipped.data_ptr()), meta=("shell", "adam_guarded", 0.0, "%d tensors" % len(plist), nbytes))
