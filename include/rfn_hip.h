@@ -584,6 +584,29 @@ int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long
                                 int num_digits, int step_length, int deterministic, long seed, long split,
                                 long first_id, rfn_stream_t stream);
 
+/* ---- addressed normal noise  (the draws of RFN.predict_draws and of the Evaluator's batched best-of-N; DESIGN.md
+ * section 16).  One launch fills up to 8 tensors ("slots") of shape [rows, numel_j], fp32 contiguous, with N(0,1) values.
+ * Each value depends only on its address, not on the launch geometry.
+ * Row i of a launch stands for (draw, sequence): draw = first_draw + i / B, seq = first_seq + i % B (draw-major:
+ * row i = r_local * B + b).
+ * Block q of slot j at step t is Philox4x64-10(key = (seed, (t << 32) | j), counter = (q, 0, seq, draw)).  It has four
+ * 64-bit words w0..w3 (the round function and constants of csrc/moving_mnist.hip; csrc/philox.h).
+ * Word w_i of block q gives elements 8q + 2i and 8q + 2i + 1 of the row (flattened C*H*W):
+ *   a = w >> 32, b = w & 0xffffffff
+ *   u1 = ((a >> 8) + 1) * 2^-24, in (0, 1]
+ *   u2 = (b >> 8) * 2^-24, in [0, 1)
+ *   rad = sqrtf(-2 * logf(u1))
+ *   the two values are rad * cospif(2 * u2) and rad * sinpif(2 * u2),
+ * with the accurate fp32 functions, not fast-math intrinsics; 2 * u2 is exact, so no rounded 2 pi enters;
+ * |value| <= sqrt(48 ln 2) ~ 5.77.
+ * outs, numels: HOST arrays of n_slots device pointers and row lengths, 1 <= n_slots <= 8; slot j is the array position;
+ * numels[j] == 0 skips slot j (its pointer is not read).  rows is a multiple of B >= 1; seed, first_seq, first_draw and
+ * step are >= 0 (step and j are 32-bit words of the key).  Two 16-byte stores per lane where numels[j] % 8 == 0 and
+ * outs[j] is 16-byte aligned, single stores otherwise (outs[j] must be 4-byte aligned).  No atomics, no LDS.  One launch
+ * (none when nothing is to be written). */
+int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, long seed, int step,
+                         long first_seq, long first_draw, rfn_stream_t stream);
+
 /* ---- clips of a device-resident frame store as float32 batches  (the per-item work of the file-backed datasets,
  * data_generators/bair_push.py:66-109 and data_generators/kth.py:34-65, and the DataLoader collation of
  * RFN/trainer.py:132-161, for a whole batch in one launch).  store: uint8 [n_frames, H, W, Cs] device tensor,

@@ -293,24 +293,45 @@ class RFN(nn.Module):
         shapes.append((B, c, h, w))          # base distribution = what is left after the last level
         return shapes + split[::-1]
 
-    def _gen_step_graphed(self, prediction, hprev, cprev, zprev, kl_temp):
+    _GEN_GRAPHS_KEPT = 4   # captured generation graphs kept per model, one per batch shape
+
+    def _gen_step_graphed(self, prediction, hprev, cprev, zprev, kl_temp, eps_fill=None):
         """_gen_step with fresh N(0,1) draws, replayed from a hipGraph: generation is one frame at a time, a few hundred
         launches of a few microseconds each, i.e. bound by the host's launch rate when launched eagerly (38 ms per frame at
-        B = 32 against ~6 ms of GPU work).  The graph is rebuilt whenever a parameter changed (the inverse matrices and
-        weight packs of ListGlow._reverse_cache are baked into it) or the shapes do; the draws are inputs of the graph."""
+        B = 32 against ~6 ms of GPU work).  A graph is rebuilt whenever a parameter changed (the inverse matrices and
+        weight packs of ListGlow._reverse_cache are baked into it); the draws are inputs of the graph.  One graph is kept
+        per batch shape (`_gen_graphs`, the last few shapes used), so that predict at batch B and predict_draws at batch
+        P*B alternate without a rebuild; `_gen_graph` is the one used last.
+        eps_fill (optional): a callable that writes the draws into the list of eps tensors it is given, in place
+        (predict_draws: addressed noise, written straight into the graph's inputs); without it the draws come from
+        torch's generator, L + 1 launches."""
         import rfn_hip
         dev = prediction.device
-        eps = [torch.randn(sh, device=dev) for sh in self._gen_eps_shapes(prediction.shape[0])]
-        args = [prediction, hprev, cprev, zprev] + eps
+        shapes = self._gen_eps_shapes(prediction.shape[0])
         ok = (dev.type == "cuda" and rfn_hip.graph_capture_safe() and not self.training
               and os.environ.get("RFN_GEN_GRAPH", "1") != "0")
+        if eps_fill is None:
+            eps = [torch.randn(sh, device=dev) for sh in shapes]
+        elif not ok:
+            eps = [torch.empty(sh, device=dev) for sh in shapes]
+            eps_fill(eps)
+        else:
+            eps = None   # written into the graph's inputs below
+        state = [prediction, hprev, cprev, zprev]
         if not ok:
             return self._gen_step(prediction, hprev, cprev, zprev, eps, kl_temp)
-        key = (tuple((p._version, p.data_ptr()) for p in self.parameters()), tuple(tuple(a.shape) for a in args),
+        shape_key = tuple(tuple(a.shape) for a in state) + tuple(shapes)
+        key = (tuple((p._version, p.data_ptr()) for p in self.parameters()), shape_key,
                float(kl_temp), float(self.temperature))
-        g = getattr(self, "_gen_graph", None)
+        graphs = self.__dict__.setdefault("_gen_graphs", {})
+        g = graphs.pop(shape_key, None)
         if g is None or g[0] != key:
-            static_in = [a.clone() for a in args]
+            static_in = [a.clone() for a in state]
+            if eps is not None:
+                static_in += [a.clone() for a in eps]
+            else:
+                static_in += [torch.empty(sh, device=dev) for sh in shapes]
+                eps_fill(static_in[4:])
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -320,11 +341,20 @@ class RFN(nn.Module):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 static_out = self._gen_step(*static_in[:4], static_in[4:], kl_temp)
-            g = self._gen_graph = (key, graph, static_in, static_out)
+            g = (key, graph, static_in, static_out)
             self._gen_graph_builds = getattr(self, "_gen_graph_builds", 0) + 1
+        graphs[shape_key] = g          # most recently used last
+        while len(graphs) > self._GEN_GRAPHS_KEPT:
+            graphs.pop(next(iter(graphs)))
+        self._gen_graph = g
         _, graph, static_in, static_out = g
-        for s_, a in zip(static_in, args):
+        for s_, a in zip(static_in, state):
             s_.copy_(a)
+        if eps is not None:
+            for s_, a in zip(static_in[4:], eps):
+                s_.copy_(a)
+        else:
+            eps_fill(static_in[4:])
         graph.replay()
         return tuple(o.clone() for o in static_out)
 
@@ -374,6 +404,73 @@ class RFN(nn.Module):
                 frames.append(prediction.detach())
                 hprev, cprev, zprev = ht, ct, zt
             predictions = torch.stack(frames, 0) if frames else torch.zeros((0, *x[:, 0].shape), device=x.device)
+        return true_x, predictions
+
+    def predict_draws(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+        """`predict` for n_draws independent draws of every sequence in one pass, with addressed noise: returns
+        (true_x, predictions), predictions [n_predictions, n_draws, B, C, H, W] on the CPU (`_predict_draws_device`: the
+        same on the device).  The extractor and the ConvLSTM run once over the conditioning frames of the B sequences;
+        from the first latent step on everything runs on n_draws*B rows, draw-major (row r*B + b: draw first_draw + r
+        of sequence first_seq + b), the generation through _gen_step / its hipGraph at that batch.
+        Noise: rfn_hip.ops.keyed_normal, one launch per step.  Conditioning step i (1 .. n_conditions-1) uses t = i:
+        slot 0 the prior eps, slot 1 the encoder eps.  Generated frame i uses t = n_conditions + i: slot 0 the prior
+        eps, slot 2 the flow's base eps, slots 3.. the Split2d eps list, coarsest first (the order of _gen_eps_shapes).
+        A frame therefore depends on (seed, sequence id, draw id) and the data alone: not on B, on n_draws, on how the
+        draws are split into calls, or on torch's generator, which is left untouched.  Eval mode only: batch statistics
+        would couple the draws."""
+        true_x, predictions = self._predict_draws_device(x, n_predictions, n_conditions, n_draws, seed, first_seq,
+                                                         first_draw)
+        return true_x.cpu(), predictions.cpu()
+
+    def _predict_draws_device(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+        assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
+        if self.training:
+            raise RuntimeError("RFN.predict_draws needs eval mode: in training mode the batch statistics of the "
+                               "normalisation layers would couple the draws (call model.eval() first)")
+        P, B = int(n_draws), int(x.shape[0])
+        if P < 1:
+            raise ValueError("RFN.predict_draws: n_draws must be at least 1, got %d" % P)
+        if self.L + 2 > K.KEYED_NORMAL_MAX_SLOTS:
+            raise ValueError("RFN.predict_draws: L = %d needs %d noise slots, one launch fills %d" %
+                             (self.L, self.L + 2, K.KEYED_NORMAL_MAX_SLOTS))
+
+        def rep(t):   # draw-major: row r*B + b is sequence b
+            return t.repeat((P,) + (1,) * (t.dim() - 1))
+
+        with torch.no_grad():
+            hprev, cprev, aprev, caprev, zprev, zxprev, _, _, _ = self.get_inits()
+            feats = [self.extractor(x[:, i]) for i in range(n_conditions)]
+            store_ht, store_at, hprev, cprev = self._deterministic_states(feats, n_conditions, hprev, cprev, aprev, caprev)
+            zprev, zxprev = rep(zprev), rep(zxprev)
+            zshape = tuple(zprev.shape[1:])
+            for i in range(1, n_conditions):
+                eps_p, eps_q = K.keyed_normal([zshape, zshape], B, P, seed, i, first_seq, first_draw, device=x.device)
+                ht = rep(store_ht[i - 1])
+                if self.enable_smoothing:
+                    enc_mean, enc_std = self.encoder(torch.cat((rep(store_at[i - 1]), zxprev), dim=1))
+                else:
+                    enc_mean, enc_std = self.encoder(torch.cat((ht, zxprev, rep(self._last(feats[i]))), dim=1))
+                if self.res_q:
+                    prior_mean, prior_std = self.prior(torch.cat((ht, zxprev), dim=1))
+                    enc_mean = prior_mean + enc_mean
+                else:
+                    prior_mean, prior_std = self.prior(torch.cat((ht, zprev), dim=1))
+                zprev = prior_mean + prior_std * self.kl_temperature * eps_p
+                zxprev = enc_mean + enc_std * eps_q
+            true_x = x[:, :n_conditions].transpose(0, 1).detach().clone()
+            frames = []
+            prediction, hprev, cprev = rep(x[:, n_conditions - 1]), rep(hprev), rep(cprev)
+            for i in range(n_predictions):
+                def fill(eps, t=n_conditions + i):   # slot 1 (the encoder eps) is not drawn while generating
+                    K.keyed_normal(None, B, P, seed, t, first_seq, first_draw, out=[eps[0], None] + list(eps[1:]))
+                prediction, ht, ct, zt = self._gen_step_graphed(prediction, hprev, cprev, zprev, self.kl_temperature,
+                                                                eps_fill=fill)
+                frames.append(prediction.detach())
+                hprev, cprev, zprev = ht, ct, zt
+            if frames:
+                predictions = torch.stack(frames, 0).view(n_predictions, P, B, *x.shape[2:])
+            else:
+                predictions = torch.zeros((0, P, B, *x.shape[2:]), device=x.device)
         return true_x, predictions
 
     def reconstruct(self, x, draws=None):

@@ -38,6 +38,11 @@ class Evaluator(object):
         self.extra_plots = bool(getattr(settings, "extra_plots", False))
         self.debug_plot = bool(getattr(settings, "debug_plot", False))
         self._warned_plots = False
+        # optional: P draws of every sequence per generation pass, with addressed noise (get_eval_values); unset: one
+        # RFN.predict call per draw, noise from torch's generator
+        self.draws_per_pass = getattr(settings, "draws_per_pass", None)
+        self.seed = int(getattr(settings, "seed", None) or 0)
+        self.num_samples_to_plot = int(getattr(settings, "num_samples_to_plot", None) or 5)
         # optional: a directory or a list of files holding the LPIPS-alex weights (rfn_hip.ops.lpips_alex_load); loaded
         # on first use
         self.lpips_weights = getattr(settings, "lpips_weights", None)
@@ -236,8 +241,13 @@ class Evaluator(object):
 
         Reference quirk kept on purpose, so that the figures stay comparable with published ones: the first draw's
         SSIM / PSNR / LPIPS tensors ARE the best-so-far tensors (the reference aliases them) and the best-of-N updates write into
-        them in place, so the "mean over draws" averages the final best values in place of draw 0."""
+        them in place, so the "mean over draws" averages the final best values in place of draw 0.
+
+        With settings.draws_per_pass = P the draws of a batch are generated P at a time with addressed noise
+        (settings.seed) and the figures are reproducible: see _get_eval_values_draws."""
         assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        if self.draws_per_pass is not None:
+            return self._get_eval_values_draws(loader, max_batches)
         if (self.extra_plots or self.debug_plot) and not self._warned_plots:
             warnings.warn("Evaluator.get_eval_values: extra_plots / debug_plot only draw figures; skipped")
             self._warned_plots = True
@@ -307,6 +317,120 @@ class Evaluator(object):
                 torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
                 torch.cat(ssim_std_values), torch.cat(psnr_std_values),
                 torch.cat(lpips_std_values) if lpips_w is not None else None)
+
+    def _get_eval_values_draws(self, loader=None, max_batches=None):
+        """get_eval_values with settings.draws_per_pass = P: per batch ceil(resample / P) calls of
+        RFN._predict_draws_device, each generating P draws of the B sequences as P*B rows of one batch (the extractor
+        and the ConvLSTM over the conditioning frames run once per call, every generated frame is one hipGraph replay
+        for all P*B rows).  The noise is addressed (rfn_hip.ops.keyed_normal): draw r of sequence batch_i * B + b under
+        settings.seed is the same numbers whatever P, the batch size or anything drawn before, so the result for a
+        given (seed, resample) does not depend on P; a last pass still runs P draws and ignores draws >= resample.
+        Per pass one frame_quality launch scores the P*B sequences (with lpips_weights: one trunk pass over the P*B*T
+        predicted frames; the ground truth's features are computed once per batch), the scores come to the host in
+        one copy and the predictions stay on the device.  The best-of-N rules are those of get_eval_values, applied to
+        the draws in ascending draw id: strict comparisons of time-means, ties keep the earlier draw, and the
+        reference's aliasing of draw 0 in the "mean over draws".  Same tuple, dtypes, shapes and devices.
+        model.loss runs once per batch, after the passes, not once per draw: BPD / DKL / RECON are one stochastic
+        evaluation per batch either way (get_eval_values reports that of the last draw).
+        The best prediction of every sequence by SSIM is kept on the device; with settings.debug_plot three sheets are
+        written through plot_samples after the loop (error_metrics.py:590-597, pixels only): random_samples_ssim.png
+        (the last batch's last draw), best_samples.png and worst_samples.png (the first and last of the sequences
+        ordered by time-mean SSIM of their best draw, descending), settings.num_samples_to_plot sequences each
+        (default 5, capped at the sequences there are), the first six predicted frames."""
+        from rfn_hip import ops
+        P = int(self.draws_per_pass)
+        if P < 1:
+            raise ValueError("Evaluator: settings.draws_per_pass must be at least 1, got %d" % P)
+        if self.extra_plots and not self._warned_plots:
+            warnings.warn("Evaluator.get_eval_values: extra_plots only draws figures; skipped")
+            self._warned_plots = True
+        loader = loader if loader is not None else self.test_loader
+        start, n_frames, R = self.start_predictions, self.n_frames, self.resample
+        n_pass = -(-R // P)
+        lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
+        names = ("mse", "psnr", "ssim") + (("lpips",) if lpips_w is not None else ())
+        lower_is_better = {"mse": True, "psnr": False, "ssim": False, "lpips": True}
+        best_values = {k: [] for k in names}
+        mean_values = {k: [] for k in names}
+        bpd_list, dkl_list, recon_list = [], [], []
+        best_preds, gts = [], []
+        batch_size, last_pred = None, None
+        with torch.no_grad():
+            self.model.eval()
+            for batch_i, true_image in enumerate(loader):
+                if max_batches is not None and batch_i >= max_batches:
+                    break
+                image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
+                image = self.solver.preprocess(image.to(self.device))
+                imageloss = image[:, :self.n_trained] if self.n_trained else image
+                B = int(image.shape[0])
+                batch_size = batch_size or B
+                gt_u8 = self.solver.preprocess(image, reverse=True)[:, start:n_frames].contiguous()
+                gt_rep = gt_u8.unsqueeze(0).expand(P, *gt_u8.shape)
+                gt_feats = None
+                best, draws, best_pred = {}, {k: [] for k in names}, None
+                for ps in range(n_pass):
+                    _, predictions = self.model._predict_draws_device(image, n_frames - start, start, P, self.seed,
+                                                                      first_seq=batch_i * batch_size, first_draw=ps * P)
+                    # [n_pred, P, B, C, H, W] -> [P, B, n_pred, C, H, W]
+                    pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 2, 0, 3, 4, 5).contiguous()
+                    scores = dict(zip(("mse", "psnr", "ssim"), ops.frame_quality(gt_rep, pred_u8)))
+                    if lpips_w is not None:
+                        if gt_feats is None:
+                            f = ops.lpips_alex_features(lpips_w, gt_u8)
+                            gt_feats = ops.LpipsFeatures(f.data.repeat(P, 1), (P,) + f.lead, f.H, f.W)
+                        scores["lpips"] = ops.lpips_alex_distance(lpips_w, ops.lpips_alex_features(lpips_w, pred_u8),
+                                                                  gt_feats)
+                    host = torch.stack([scores[k] for k in names]).cpu()   # [metrics, P, B, n_pred]: the pass's one copy
+                    for d in range(min(P, R - ps * P)):
+                        for m, k in enumerate(names):
+                            v = host[m, d].clone()
+                            if ps == 0 and d == 0:
+                                best[k] = v   # aliased with the first entry of draws[k], as in the reference
+                                better = None
+                            else:
+                                if lower_is_better[k]:
+                                    better = best[k].mean(-1) > v.mean(-1)
+                                else:
+                                    better = best[k].mean(-1) < v.mean(-1)
+                                best[k][better, :] = v[better, :]
+                            draws[k].append(v)
+                            if k == "ssim":
+                                if better is None:
+                                    best_pred = pred_u8[d].clone()
+                                elif bool(better.any()):
+                                    sel = better.to(self.device)
+                                    best_pred[sel] = pred_u8[d][sel]
+                        last_pred = pred_u8[d]
+                _, kl, nll = self.model.loss(imageloss, 0)
+                bpd, kl_loss, recon_loss = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:],
+                                                             t=imageloss.shape[1] - 1)
+                for k in names:
+                    mean_values[k].append(torch.stack(draws[k]).mean(0))
+                    best_values[k].append(best[k])
+                bpd_list.append(bpd)
+                dkl_list.append(kl_loss)
+                recon_list.append(recon_loss)
+                best_preds.append(best_pred)
+                gts.append(gt_u8)
+                last_gt = gt_u8
+        ssim_all = torch.cat(best_values["ssim"])
+        # best_preds_ssim of the reference: every sequence's best draw by SSIM, on the device
+        self.best_preds_ssim = torch.cat(best_preds)
+        if self.debug_plot:
+            ns, nf = self.num_samples_to_plot, 6
+            ordered = torch.argsort(ssim_all.mean(-1), descending=True).to(self.device)
+            preds, gt = self.best_preds_ssim[ordered], torch.cat(gts)[ordered]
+            n = min(ns, int(last_pred.shape[0]))
+            self.plot_samples(last_pred[:n, :nf], last_gt[:n, :nf], name="random_samples_ssim")
+            n = min(ns, int(preds.shape[0]))
+            self.plot_samples(preds[:n, :nf], gt[:n, :nf], name="best_samples")
+            self.plot_samples(preds[-n:, :nf], gt[-n:, :nf], name="worst_samples")
+        return (torch.cat(best_values["mse"]), torch.cat(best_values["psnr"]), ssim_all,
+                torch.cat(best_values["lpips"]) if lpips_w is not None else None,
+                torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
+                torch.cat(mean_values["ssim"]), torch.cat(mean_values["psnr"]),
+                torch.cat(mean_values["lpips"]) if lpips_w is not None else None)
 
     # ---- the analyses the reference's evaluator drives (error_metrics.py: plot_elbo_gap, plot_prob_of_t, param_plots)
     def elbo_gap(self, image, sample=False):

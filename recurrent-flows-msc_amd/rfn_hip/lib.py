@@ -143,6 +143,7 @@ SIGNATURES = {
     "rfn_frame_quality_u8": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_moving_mnist_render_f32": [ctypes.c_void_p, _c_i, _c_f, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
                                     _c_l, _c_l, _c_l, _c_s],
+    "rfn_keyed_normal_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_l, _c_i, _c_l, _c_l, _c_s],
     "rfn_clip_gather_u8_f32": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_sheet_max_rows": [],
     "rfn_sheet_compose_u8": [ctypes.c_void_p] + [_c_i] * 10 + [_c_l, _c_s],

@@ -1859,6 +1859,80 @@ def clip_gather(store, first, T, C):
     return out
 
 
+KEYED_NORMAL_MAX_SLOTS = 8
+
+
+def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=None, device=None):
+    """Addressed N(0,1) noise (rfn_keyed_normal_f32; include/rfn_hip.h and DESIGN section 16 hold the definition): a list
+    of float32 tensors [n_draws*B, *shape_j], slot j being the list position (at most 8).  Row r*B + b of every tensor
+    stands for draw first_draw + r of sequence first_seq + b, and a value depends only on (seed, step, slot, sequence,
+    draw, position in the row): the same on any grid, for any B, n_draws and split of the draws into calls.  An entry
+    None of `shapes` skips that slot (None in the result).  out: tensors to fill in place instead of fresh ones (None
+    where the slot is skipped), each contiguous float32 of n_draws*B rows on one device; with out, `shapes` may be None.
+    device: where fresh tensors go (default: the current GPU).  One launch on the current stream; no CPU fallback."""
+    B, n_draws, seed, step, first_seq, first_draw = (int(v) for v in (B, n_draws, seed, step, first_seq, first_draw))
+    if B < 1 or n_draws < 0:
+        raise ValueError("keyed_normal: need B >= 1 and n_draws >= 0 (got %d, %d)" % (B, n_draws))
+    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
+        if not 0 <= v < 1 << 63:
+            raise ValueError("keyed_normal: %s %d not in [0, 2^63)" % (nm, v))
+    if not 0 <= step < 1 << 31:
+        raise ValueError("keyed_normal: step %d not in [0, 2^31)" % step)
+    rows = n_draws * B
+    if rows > 0x7fffffff:
+        raise ValueError("keyed_normal: %d rows exceed one launch" % rows)
+    if out is None:
+        if shapes is None:
+            raise TypeError("keyed_normal: give shapes or out")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("rfn_hip kernels need device tensors; keyed_normal was asked for %s (no CPU fallback)" %
+                               device)
+        out = [None if sh is None else torch.empty((rows,) + tuple(int(d) for d in sh), device=device,
+                                                   dtype=torch.float32) for sh in shapes]
+    else:
+        out = list(out)
+        if shapes is not None and len(shapes) != len(out):
+            raise ValueError("keyed_normal: %d shapes for %d out tensors" % (len(shapes), len(out)))
+        for j, t in enumerate(out):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError("keyed_normal: out[%d] must be a tensor, got %s" % (j, type(t).__name__))
+            if t.dim() < 1 or int(t.shape[0]) != rows:
+                raise ValueError("keyed_normal: out[%d] must have %d rows, got shape %s" % (j, rows, tuple(t.shape)))
+            if shapes is not None and shapes[j] is not None and tuple(t.shape[1:]) != tuple(int(d) for d in shapes[j]):
+                raise ValueError("keyed_normal: out[%d] has rows %s, shapes[%d] is %s" %
+                                 (j, tuple(t.shape[1:]), j, tuple(shapes[j])))
+    if not 1 <= len(out) <= KEYED_NORMAL_MAX_SLOTS:
+        raise ValueError("keyed_normal: %d slots, one launch fills 1 to %d" % (len(out), KEYED_NORMAL_MAX_SLOTS))
+    live = [t for t in out if t is not None]
+    for t in live:
+        if t.device != live[0].device:
+            raise ValueError("keyed_normal: the tensors are on %s and %s" % (live[0].device, t.device))
+    ptrs = (ctypes.c_void_p * len(out))()
+    numels = (ctypes.c_int * len(out))()
+    total = 0
+    for j, t in enumerate(out):
+        if t is None or rows == 0:
+            continue
+        n = t.numel() // rows
+        if n > 0x7fffffff:
+            raise ValueError("keyed_normal: rows of %d values exceed one launch" % n)
+        if n:
+            ptrs[j] = L.dev(t, "out[%d]" % j).value
+        numels[j] = n
+        total += t.numel()
+    if total:
+        with torch.cuda.device(live[0].device):
+            L.call("rfn_keyed_normal_f32", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(numels, ctypes.c_void_p),
+                   _i(len(out)), _i(rows), _i(B), _l(seed), _i(step), _l(first_seq), _l(first_draw),
+                   meta=("shell", "keyed_normal", 0.0, "%dx%d" % (rows, total // rows), 4.0 * total))
+    return out
+
+
 class _SheetRow(ctypes.Structure):
     """rfn_sheet_row of include/rfn_hip.h"""
     _fields_ = [("ptr", ctypes.c_void_p), ("step", ctypes.c_long), ("kind", ctypes.c_int), ("count", ctypes.c_int)]
