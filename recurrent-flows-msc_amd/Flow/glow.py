@@ -93,6 +93,32 @@ class GlowStep(nn.Module):
         return out, logdet
 
 
+def plan_packs(N, C, H, W, levels, grad):
+    """The weight packs ListGlow keeps fresh for N frames of a C x H x W input; needs no device.  `levels`: per flow level
+    (condition channels, a Split2d follows, [(Hd, k1, k2, k3, activation code, runs as a rfn_hip.ops node) per step]).
+    Returns conv [(step, StepPacks field, PackPlan mode)], nets [step] (the fused kernels' streams: POPackPlan) and
+    dense [(step, StepPacks field, (H, W, transpose))], each in launch order, step = (level, k): a superset of what the
+    steps' routes read (CouplingRoute.packs; DESIGN.md lists the difference)."""
+    conv, nets, dense = [], [], []
+    for l, (Cc, split, steps) in enumerate(levels):
+        C, H, W = C * 4, H // 2, W // 2
+        for k, (Hd, k1, k2, k3, act, node) in enumerate(steps):
+            r = K.coupling_route(N, C, Cc, Hd, H, W, k1, k2, k3, act, grad)
+            fused = node and r.fwd == "po"
+            x6 = 4 if r.fwd_prec == "bf16x6" else 0   # forward packs in three planes where bf16x6 is the forward arithmetic
+            for w, mode in (("w1", 0), ("w2", 0), ("w3", 2 if r.conv3 == "taps" else 0)):
+                if not fused and r.fwd_prec != "f32":
+                    conv.append(((l, k), w + "_fwd", mode + x6))
+                conv.append(((l, k), w + "_dgrad", 1))
+            if fused:
+                nets.append((l, k))
+            dense += [((l, k), field, (H, W, t)) for field, t, on in (   # (H*W <= 16: level 4 of the canonical flow)
+                ("w1_dense_fwd", False, r.conv1 == "dense"), ("w3_dense_fwd", False, r.conv3 == "dense"),
+                ("w1_dense_dgrad", True, r.dgrad1 == "dense")) if on]
+        C = C // 2 if split else C
+    return conv, nets, dense
+
+
 class ListGlow(nn.Module):
     """Flow/glow.py:43-160."""
 
@@ -183,71 +209,38 @@ class ListGlow(nn.Module):
         return True
 
     def _packed_weights(self, x_shape, condition):
-        """re-pack every coupling-net weight of the flow, one launch per kind: the dense small-map packs of the deepest
-        levels, the split-precision packs of the data-gradient convolutions -- and of the forward convolutions where a
-        split arithmetic is the forward arithmetic -- and the fragment streams of the fused kernels (shallow levels,
-        'mixed' arithmetic).  Re-packed on every call: a captured training step must contain the launches (a
-        version-keyed cache would be hit during capture and the replays would run on stale packs).
-        Returns {GlowStep: rfn_hip.ops.StepPacks} or None."""
-        if not K.bwd_b3():
-            return None
+        """re-pack every coupling-net weight of the flow as plan_packs lists them, one launch per kind.  Re-packed on
+        every call: a captured training step must contain the launches (a version-keyed cache would be hit during
+        capture and the replays would run on stale packs).  Returns {GlowStep: rfn_hip.ops.StepPacks} or None."""
         levels = self._level_steps()
-        if not levels or not levels[0][1] or not levels[0][1][0].affine.net[0].conv.weight.is_cuda:
+        if not K.bwd_b3() or not levels or not levels[0][1] or not levels[0][1][0].affine.net[0].conv.weight.is_cuda:
             return None
-        N, C, H, W = (int(v) for v in x_shape)
-        items, nets, slots, dense = [], [], {}, {}
+        wts, shapes = {}, []   # {(level, k): (w1, w2, w3)}, plan_packs' `levels`
+        for l, (_, steps, split) in enumerate(levels):
+            shapes.append((int(condition[l].shape[1]), split is not None, []))
+            for k, s in enumerate(steps):
+                w1, w2, w3 = wts[l, k] = tuple(s.affine.net[i].conv.weight for i in (0, 2, 4))
+                shapes[l][2].append((int(w1.shape[0]), int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2]),
+                                     K.ACT[s.affine.non_lin], s.flow_norm != "batchnorm"))
+        conv, nets, dense = plan_packs(*(int(v) for v in x_shape), shapes, torch.is_grad_enabled())
         with K.PackBatch() as pb:
-            for l, (_, steps, split) in enumerate(levels):
-                C, H, W = C * 4, H // 2, W // 2
-                Cc = int(condition[l].shape[1])
-                for s in steps:
-                    n0, n2, n4 = s.affine.net[0], s.affine.net[2], s.affine.net[4]
-                    w1, w2, w3 = n0.conv.weight, n2.conv.weight, n4.conv.weight
-                    Hd = int(w1.shape[0])
-                    fused = s.flow_norm != "batchnorm" and int(w2.shape[2]) == 1 and \
-                        K.coupling_po_ok(N, C, Cc, Hd, H, W, w1, w3)
-                    fp = K.fwd_prec(H, W)
-                    b3fwd = not fused and fp in ("bf16x3", "bf16x6")
-                    x6 = 4 if fp == "bf16x6" else 0   # forward packs in three planes where bf16x6 is the forward arithmetic
-                    slot = {}
-                    for name, w, mode in (("w1_fwd", w1, 0), ("w1_dgrad", w1, 1), ("w2_fwd", w2, 0), ("w2_dgrad", w2, 1),
-                                          ("w3_fwd", w3, 2 if K.zeros_conv_uses_taps(w3) else 0), ("w3_dgrad", w3, 1)):
-                        if mode == 1 or b3fwd:
-                            slot[name] = len(items)
-                            items.append((w, mode if mode == 1 else mode + x6))
-                    if fused:
-                        slot["po"] = len(nets)
-                        nets.append((w1, w2, w3))
-                    slots[s] = slot
-                    # the dense packs of the small-map levels (H*W <= 16: level 4 of the canonical flow), forward and --
-                    # when a gradient will be asked for -- data-gradient orientation
-                    k33 = int(w1.shape[2]) == 3 and int(w3.shape[2]) == 3
-                    d = dense[s] = {}
-                    if k33 and K.smallmap_conv_ok(H, W, C // 2, Cc, Hd, N):
-                        d["w1_dense_fwd"] = pb.dense(w1, H, W, False)
-                    if k33 and K.smallmap_conv_ok(H, W, Hd, 0, C, N) and not K.zeros_conv_uses_taps(w3):
-                        d["w3_dense_fwd"] = pb.dense(w3, H, W, False)
-                    if torch.is_grad_enabled() and k33 and K.smallmap_conv_ok(H, W, Hd, 0, C // 2 + Cc, N, bwd=True):
-                        d["w1_dense_dgrad"] = pb.dense(w1, H, W, True)
-                if split is not None:
-                    C = C // 2
+            dbufs = [pb.dense(wts[step][int(field[1]) - 1], *how) for step, field, how in dense]
+        items = [(wts[step][int(field[1]) - 1], mode) for step, field, mode in conv]
         plan = getattr(self, "_pack_plan", None)
         if plan is None or not plan.valid_for(items):
             plan = self._pack_plan = K.PackPlan(items)
         plan.run()
-        po = None
+        kw = {step: {} for step in wts}
         if nets:
             po = getattr(self, "_po_plan", None)
-            if po is None or not po.valid_for(nets):
-                po = self._po_plan = K.POPackPlan(nets)
+            if po is None or not po.valid_for([wts[step] for step in nets]):
+                po = self._po_plan = K.POPackPlan([wts[step] for step in nets])
             po.run(bwd=torch.is_grad_enabled())
-        out = {}
-        for s, slot in slots.items():
-            kw = {name: plan.bufs[i] for name, i in slot.items() if name != "po"}
-            if "po" in slot:
-                kw.update(po_fwd=po.bufs[slot["po"]], po_bwd=po.bwd_bufs[slot["po"]])
-            out[s] = K.StepPacks(**kw, **dense[s])
-        return out
+            for i, step in enumerate(nets):
+                kw[step].update(po_fwd=po.bufs[i], po_bwd=po.bwd_bufs[i])
+        for (step, field, _), buf in zip(conv + dense, plan.bufs + dbufs):
+            kw[step][field] = buf
+        return {levels[l][1][k]: K.StepPacks(**kw[l, k]) for l, k in wts}
 
     def f(self, x, condition, logdet):
         """Flow/glow.py:105-117 (same order of operations; per-level batching of the tiny parameter algebra)."""

@@ -612,18 +612,22 @@ def zeros_conv_uses_taps(w):
     return int(w.shape[2]) == 3 and int(w.shape[0]) <= TAP_MAX_COUT
 
 
-def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None):
-    """Conv2dZeros forward (glow_modules.py:119-121): (conv3x3(x) + b) * exp(3 logs).  Tiny Cout -> tap-expanded.
-    `wpk` (optional): pre-packed weight (mode 2 = tap-expanded when zeros_conv_uses_taps(w), else mode 0), packed for
-    `prec` (default: this map's forward arithmetic)."""
-    C, Cin, ks = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+def _tap_expanded(w):   # w [C, Cin, 3, 3] as the 1x1 weight [tap * C + co][ci]
+    return w.detach().permute(2, 3, 0, 1).reshape(9 * int(w.shape[0]), int(w.shape[1]), 1, 1).contiguous()
+
+
+def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None, taps=None):
+    """Conv2dZeros forward (glow_modules.py:119-121): (conv3x3(x) + b) * exp(3 logs).  Tiny Cout -> tap-expanded
+    (`taps`; default zeros_conv_uses_taps(w)).  `wpk` (optional): pre-packed weight (mode 2 = tap-expanded with `taps`,
+    else mode 0), packed for `prec` (default: this map's forward arithmetic)."""
+    C, ks = int(w.shape[0]), int(w.shape[2])
     N, _, H, W = x.shape
     if prec is None:
         prec = fwd_prec(H, W)
-    if not zeros_conv_uses_taps(w):
+    if not (zeros_conv_uses_taps(w) if taps is None else taps):
         return conv2d_raw(x, None, wpk if wpk is not None else pack_weight(w, prec=prec), C, ks, 2, b, logs, 0, prec=prec)
     if wpk is None:
-        wpk = pack_weight(w.detach().permute(2, 3, 0, 1).reshape(9 * C, Cin, 1, 1).contiguous(), prec=prec)  # [tap*C + co][ci]
+        wpk = pack_weight(_tap_expanded(w), prec=prec)
     P = conv2d_raw(x, None, wpk, 9 * C, 1, prec=prec)
     o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
     L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b), L.dev(logs), L.dev(o), _i(N), _i(C), _i(H), _i(W),
@@ -810,13 +814,20 @@ def _f(t):
     return None if t is None else t.detach().reshape(-1).contiguous()
 
 
-# the packed weights of one Glow step's coupling net, kept fresh by the caller (Flow/glow.py ListGlow._packed_weights);
-# a field left None is packed where it is needed.  *_fwd / *_dgrad: split-precision conv packs of the forward (in the
-# map's forward arithmetic) / data-gradient convolutions; po_fwd / po_bwd: the fused kernels' weight streams
-# (POPackPlan); *_dense_*: dense small-map packs (smallmap_conv).
+# the packed weights of one Glow step's coupling net, kept fresh by the caller (Flow/glow.py ListGlow._packed_weights).
+# *_fwd / *_dgrad: conv packs of the forward (in the map's split forward arithmetic) / data-gradient convolutions;
+# po_fwd / po_bwd: the fused kernels' weight streams (POPackPlan); *_dense_*: dense small-map packs (smallmap_conv).
+# CouplingRoute.packs names the fields a step reads; one that is read and left None is packed on the spot (_pack).
 StepPacks = collections.namedtuple("StepPacks", ["w1_fwd", "w1_dgrad", "w2_fwd", "w2_dgrad", "w3_fwd", "w3_dgrad",
                                                  "po_fwd", "po_bwd", "w1_dense_fwd", "w3_dense_fwd", "w1_dense_dgrad"],
                                    defaults=(None,) * 11)
+
+
+def _pack(pk, name, make):
+    """the pack `name` of a step from `pk` (a dict of StepPacks fields); one not given is packed now and kept there"""
+    if pk.get(name) is None:
+        pk[name] = make()
+    return pk[name]
 
 
 def dgrad_small_ok(N, Cin, Cout, H, W, ks):
@@ -841,82 +852,107 @@ def conv3x3_smallcout(x, wpk, Cout, out1, out2=None, cout_split=None, acc1=False
     return out1
 
 
-def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk, want_masks=False):
-    """coupling network of one Glow step (glow_modules.py:232-238) on z's first channel half and `cond`.
-    Returns (h1, h2, o, P, masks): either o (finished Conv2dZeros output) or P (its tap-expanded pre-gather form, fused
-    forward kernel) is None; masks: the fused kernel's activation masks for the fused backward kernel (or None).
-    `pk`: the step's StepPacks."""
+CouplingRoute = collections.namedtuple("CouplingRoute", "fwd fwd_prec conv1 conv3 masks bwd_chain dgrad1 defer_wgrad packs")
+_WeightShape = collections.namedtuple("_WeightShape", "shape")   # all that the predicates read of a weight
+
+
+def coupling_route(N, C, Cc, Hd, H, W, k1, k2, k3, act, grad, reverse=False):
+    """The kernels that serve the net C/2 + Cc -> Hd -> Hd -> C (kernel sizes k1, k2, k3, activation code `act`) of a Glow
+    step on N frames of H x W, and the StepPacks fields they read: a function of the shape, CONV_PRECISION and the RFN_*
+    knobs, all read on every call.  The coupling path asks the predicates here and nowhere else; DESIGN.md ("Where the
+    labels come from") lists the fields.  The backward fields are None / False unless `grad` (a backward may follow).
+    `reverse`: generation, which has no backward, keeps to the conv kernels and keeps forward packs in any arithmetic."""
+    Ch, back = C // 2, grad and not reverse
+    w1, w3 = _WeightShape((Hd, Ch + Cc, k1, k1)), _WeightShape((C, Hd, k3, k3))
+    k33, b3, fp = k1 == 3 and k3 == 3, bwd_b3() and Hd % 64 == 0, fwd_prec(H, W)
+    po = k2 == 1 and coupling_po_ok(N, C, Cc, Hd, H, W, w1, w3)
+    conv1 = "dense" if k33 and not reverse and smallmap_conv_ok(H, W, Ch, Cc, Hd, N) else "conv"
+    conv3 = ("taps" if zeros_conv_uses_taps(w3) else
+             "dense" if k33 and not reverse and smallmap_conv_ok(H, W, Hd, 0, C, N) else "conv")
+    packs = (("po_fwd",) if po else () if fp == "f32" and not reverse else   # (a step's forward packs are split ones)
+             ("w1_dense_fwd" if conv1 == "dense" else "w1_fwd", "w2_fwd", "w3_dense_fwd" if conv3 == "dense" else "w3_fwd"))
+    po_bwd = back and coupling_po_bwd_ok(N, C, H, W)
+    chain = dgrad1 = None
+    if back:
+        chain = "po" if po_bwd and k33 and k2 == 1 and Hd == 256 else "dgrad_act" if b3 else "epilogue"
+        dgrad1 = ("dense" if k33 and smallmap_conv_ok(H, W, Hd, 0, Ch + Cc, N, bwd=True) else
+                  "small" if dgrad_small_ok(N, Hd, Ch + Cc, H, W, k1) else "conv")
+        packs += (("po_bwd",) if chain == "po" else ("w3_dgrad", "w2_dgrad")) + (
+            "w1_dense_dgrad" if dgrad1 == "dense" else "w1_dgrad",)
+    return CouplingRoute("po" if po else "convs", fp, conv1, conv3, bool(po and po_bwd and act != 0), chain, dgrad1,
+                         bool(back and b3 and H * W % 4 == 0), packs)
+
+
+def _step_route(x, cond, w1, w2, w3, act, grad, reverse=False):
+    (N, C, H, W), ks = x.shape, (int(w.shape[2]) for w in (w1, w2, w3))
+    return coupling_route(N, C, int(cond.shape[1]), int(w1.shape[0]), H, W, *ks, act, grad, reverse)
+
+
+def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk):
+    """coupling network of one Glow step (glow_modules.py:232-238) on z's first channel half and `cond`, as `route`
+    says.  Returns (h1, h2, o, P, masks): either o (finished Conv2dZeros output) or P (its tap-expanded pre-gather form,
+    fused kernel) is None; masks: the fused kernel's activation masks (or None).  `pk`: see _pack."""
     N, C, H, W = z.shape
-    Ch = C // 2
-    Hd = int(w1.shape[0])
-    z1 = z[:, :Ch]
-    cin2 = cond if cond.shape[1] > 0 else None
-    Cc_ = 0 if cin2 is None else int(cin2.shape[1])
-    k33 = int(w1.shape[2]) == 3 and int(w3.shape[2]) == 3
-    fp = fwd_prec(H, W)
-    if coupling_po_ok(N, C, Cc_, Hd, H, W, w1, w3) and int(w2.shape[2]) == 1:
-        # shallow levels: the whole coupling net in one kernel (csrc/coupling_po.hip), h1 / h2 written once
-        po = pk.po_fwd
-        if po is None:
+    Hd, fp = int(w1.shape[0]), route.fwd_prec
+    z1, cin2 = z[:, :C // 2], (cond if cond.shape[1] > 0 else None)
+    if route.fwd == "po":
+        def stream():
             plan = POPackPlan([(w1.detach(), w2.detach(), w3.detach())])
             plan.run()
-            po = plan.bufs[0]
-        want = want_masks and pk.po_bwd is not None and coupling_po_bwd_ok(N, C, H, W)
-        h1, h2, P, masks = coupling_po_fwd(z, cin2, po, _f(n1b), _f(n1l), _f(n2b), _f(n2l), C, act, want_masks=want)
+            return plan.bufs[0]
+        # (the masks serve the backward stream only, which POPackPlan builds for at most 16 channels)
+        h1, h2, P, masks = coupling_po_fwd(z, cin2, _pack(pk, "po_fwd", stream), _f(n1b), _f(n1l), _f(n2b), _f(n2l), C, act,
+                                           want_masks=route.masks and pk.get("po_bwd") is not None)
         return h1, h2, None, P, masks
-    # the two deepest levels (H*W <= 16): a launch is a few thousand pixels against megabytes of weights, the
-    # 3x3 convolutions go through the dense small-map kernels (bf16x3 arithmetic: only where that is allowed)
-    dense = k33 and smallmap_conv_ok(H, W, Ch, Cc_, Hd, N)
-    dense3 = k33 and smallmap_conv_ok(H, W, Hd, 0, C, N) and not zeros_conv_uses_taps(w3)
-    b3fwd = fp in ("bf16x3", "bf16x6")  # the caller's pack plan holds forward packs in this map's split arithmetic
-    if dense:
-        h1 = smallmap_conv(z1, cin2, pk.w1_dense_fwd if pk.w1_dense_fwd is not None else smallmap_pack(w1, H, W, False),
-                           Hd, 1, _f(n1b), _f(n1l), act)
+    if "w2_fwd" not in route.packs:
+        pk = {}   # (fp32 forward convs: a step's forward conv packs are split-precision ones)
+    if route.conv1 == "dense":
+        h1 = smallmap_conv(z1, cin2, _pack(pk, "w1_dense_fwd", lambda: smallmap_pack(w1, H, W, False)), Hd, 1, _f(n1b),
+                           _f(n1l), act)
     else:
-        h1 = conv2d_raw(z1, cin2, pk.w1_fwd if (pk.w1_fwd is not None and b3fwd) else pack_weight(w1, prec=fp), Hd,
-                        int(w1.shape[2]), 1, _f(n1b), _f(n1l), act, prec=fp)
-    h2 = conv2d_raw(h1, None, pk.w2_fwd if (pk.w2_fwd is not None and b3fwd) else pack_weight(w2, prec=fp), Hd,
-                    int(w2.shape[2]), 1, _f(n2b), _f(n2l), act, prec=fp)
-    if dense3:
-        o = smallmap_conv(h2, None, pk.w3_dense_fwd if pk.w3_dense_fwd is not None else smallmap_pack(w3, H, W, False), C, 2,
-                          _f(b3), _f(l3), 0)
+        h1 = conv2d_raw(z1, cin2, _pack(pk, "w1_fwd", lambda: pack_weight(w1, prec=fp)), Hd, int(w1.shape[2]), 1,
+                        _f(n1b), _f(n1l), act, prec=fp)
+    h2 = conv2d_raw(h1, None, _pack(pk, "w2_fwd", lambda: pack_weight(w2, prec=fp)), Hd, int(w2.shape[2]), 1, _f(n2b),
+                    _f(n2l), act, prec=fp)
+    if route.conv3 == "dense":
+        o = smallmap_conv(h2, None, _pack(pk, "w3_dense_fwd", lambda: smallmap_pack(w3, H, W, False)), C, 2, _f(b3),
+                          _f(l3), 0)
     else:
-        o = zeros_conv_fwd(h2, w3, _f(b3), _f(l3), pk.w3_fwd if b3fwd else None, prec=fp)
+        taps = route.conv3 == "taps"
+        w3p = _pack(pk, "w3_fwd", lambda: pack_weight(_tap_expanded(w3) if taps else w3, prec=fp))
+        o = zeros_conv_fwd(h2, w3, _f(b3), _f(l3), w3p, prec=fp, taps=taps)
     return h1, h2, o, None, None
 
 
-def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gcond, acc_cond, defer=None,
-             n1b=None, n2b=None, masks=None, fin=None):
-    """backward of the coupling network from `go` = gradient at conv3's output: returns the parameter gradients
-    (gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3); the data gradient of conv1 is ADDED to gz[:, :C/2] and written (acc_cond:
-    added) to gcond.  With `defer` (a dict of three lists) the weight gradients are NOT computed: their operands are
-    appended to defer["w1" | "w2" | "w3"] and None is returned in their place (grouped launch by the caller).
-    With `masks` (the fused forward kernel's activation masks; needs n1b, n2b and the step's backward stream pk.po_bwd) the
-    data-gradient chain conv3^T -> act' -> conv2^T -> act' is ONE kernel (rfn_coupling_po_bwd) that reads no
-    activation; the four ActNorm gradients then come from the weight gradients (rfn_coupling_po_bwd_finish): a ticket
-    is appended to `fin` (the caller runs coupling_po_bwd_finish once its weight gradients exist; ticket[2] / [5] = gw1 /
-    gw2 are filled in by the caller when deferred) or, without `fin`, finished here."""
+def _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act, route, pk, arena, gz, gcond, acc_cond,
+             defer=None, masks=None, fin=None):
+    """backward of the coupling network from `go` = gradient at conv3's output, as `route` says: returns the parameter
+    gradients (gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3); the data gradient of conv1 is ADDED to gz[:, :C/2] and written
+    (acc_cond: added) to gcond.  With `defer` (a dict of three lists) and route.defer_wgrad the weight gradients are NOT
+    computed: their operands are appended to defer["w1" | "w2" | "w3"] and None is returned in their place (grouped
+    launch by the caller).  The "po" chain reads `masks` (the fused forward kernel's) and no activation; it leaves the
+    four ActNorm gradients to rfn_coupling_po_bwd_finish, which needs the weight gradients: a ticket is appended to
+    `fin` (ticket[2] / [5] = gw1 / gw2 are filled in by the caller when deferred) or, without `fin`, finished here."""
     N, C, H, W = out.shape
-    Ch = C // 2
-    Hd = int(w1.shape[0])
-    Cc = int(cond.shape[1])
+    Ch, Hd, Cc = C // 2, int(w1.shape[0]), int(cond.shape[1])
     k1, k2, k3 = int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2])
-    dfr = defer is not None and bwd_b3() and Hd % 64 == 0 and _hw(h2) % 4 == 0
+    dfr = defer is not None and route.defer_wgrad
     gw3 = None if dfr else zeros_conv_wgrad(h2, go, C, k3, arena)
-    fused = (pk.po_bwd is not None and (masks is not None or act == 0) and n1b is not None and n2b is not None
-             and k2 == 1 and k1 == 3 and k3 == 3 and Hd == 256 and coupling_po_bwd_ok(N, C, H, W))
-    w3f, w2f = pk.w3_dgrad, pk.w2_dgrad
-    if not fused and (w3f is None or w2f is None):
+    # the fused kernel needs the step's backward stream (POPackPlan: at most 16 channels) and, past an activation, the
+    # forward's masks; what admits "po" ('mixed' arithmetic, Hd = 256) admits "dgrad_act" in its place
+    chain = route.bwd_chain
+    if chain == "po" and (pk.get("po_bwd") is None or (masks is None and act != 0)):
+        chain = "dgrad_act"
+    if chain != "po":
         with PackBatch() as b:
-            w3f = w3f if w3f is not None else b.conv(w3, True)
-            w2f = w2f if w2f is not None else b.conv(w2, True)
-    if fused:
-        gh2, gh1, part = coupling_po_bwd(go.contiguous(), pk.po_bwd, _f(n1l), _f(n2l), masks, act)
+            w3f = _pack(pk, "w3_dgrad", lambda: b.conv(w3, True))
+            w2f = _pack(pk, "w2_dgrad", lambda: b.conv(w2, True))
+    if chain == "po":
+        gh2, gh1, part = coupling_po_bwd(go.contiguous(), pk["po_bwd"], _f(n1l), _f(n2l), masks, act)
         gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
         o4 = torch.empty((4, 256), device=go.device, dtype=torch.float32)
         gn1b, gn1l, gn2b, gn2l = o4[0], o4[1], o4[2], o4[3]
-    elif bwd_b3() and Hd % 64 == 0:
-        # data-gradient convs with the backward of the producer's ActNorm+activation fused into their epilogue
+    elif chain == "dgrad_act":
         gh2, gn2b, gn2l = conv2d_dgrad_act(go, w3f, h2, _f(n2l), act, Hd, k3, arena)
         gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
         gh1, gn1b, gn1l = conv2d_dgrad_act(gh2, w2f, h1, _f(n1l), act, Hd, k2, arena)
@@ -928,10 +964,9 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gc
         gh1 = conv2d_raw(gh2, None, w2f, Hd, k2)
         # ---- actnorm1 + act bwd, conv1 bwd (grad flows to z1 (accumulated into gz's first half) and to cond)
         gh1, gn1b, gn1l = conv_epilogue_bwd(h1, gh1, _f(n1l), 1, act, arena=arena)
-    z1 = out[:, :Ch]
-    has_cond = Cc > 0
-    gw1 = None if dfr else conv2d_wgrad(z1, cond if has_cond else None, gh1, Hd, k1, arena)
-    if fused:
+    z1, c2 = out[:, :Ch], (cond if Cc > 0 else None)
+    gw1 = None if dfr else conv2d_wgrad(z1, c2, gh1, Hd, k1, arena)
+    if chain == "po":
         ticket = [part, w1, gw1, _f(n1b), w2, gw2, _f(n2b), o4]
         if fin is not None:
             fin.append(ticket)
@@ -941,18 +976,16 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, pk, arena, gz, gc
     if dfr:
         defer["w3"].append((h2, go))
         defer["w2"].append((h1, gh2))
-        defer["w1"].append((z1, cond if has_cond else None, gh1))
-    if k1 == 3 and k3 == 3 and smallmap_conv_ok(H, W, Hd, 0, Ch + Cc, N, bwd=True):
-        smallmap_conv(gh1, None, pk.w1_dense_dgrad if pk.w1_dense_dgrad is not None else smallmap_pack(w1, H, W, True),
-                      Ch + Cc, 0, out1=gz[:, :Ch], out2=gcond if has_cond else None, cout_split=Ch, acc1=True,
-                      acc2=acc_cond)
-    elif dgrad_small_ok(N, Hd, Ch + Cc, H, W, k1):
-        conv3x3_smallcout(gh1, pk.w1_dgrad if pk.w1_dgrad is not None else pack_weight(w1, True), Ch + Cc, gz[:, :Ch],
-                          gcond if has_cond else None, Ch, True, acc_cond)
+        defer["w1"].append((z1, c2, gh1))
+    g1, g2 = gz[:, :Ch], (gcond if Cc > 0 else None)
+    if route.dgrad1 == "dense":
+        smallmap_conv(gh1, None, _pack(pk, "w1_dense_dgrad", lambda: smallmap_pack(w1, H, W, True)), Ch + Cc, 0, out1=g1,
+                      out2=g2, cout_split=Ch, acc1=True, acc2=acc_cond)
+    elif route.dgrad1 == "small":
+        conv3x3_smallcout(gh1, _pack(pk, "w1_dgrad", lambda: pack_weight(w1, True)), Ch + Cc, g1, g2, Ch, True, acc_cond)
     else:
-        conv2d_raw(gh1, None, pk.w1_dgrad if pk.w1_dgrad is not None else pack_weight(w1, True), Ch + Cc, k1, 0,
-                   None, None, 0, out1=gz[:, :Ch], out2=gcond if has_cond else None, cout_split=Ch, acc1=True,
-                   acc2=acc_cond)
+        conv2d_raw(gh1, None, _pack(pk, "w1_dgrad", lambda: pack_weight(w1, True)), Ch + Cc, k1, 0, None, None, 0,
+                   out1=g1, out2=g2, cout_split=Ch, acc1=True, acc2=acc_cond)
     return gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3
 
 
@@ -1004,13 +1037,11 @@ class GlowStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cond, Wm, an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift,
                 act, clamp_type, packs=None):
-        """`packs` (optional): the step's StepPacks (or a sequence in its field order); the forward conv packs are only
-        used where their split arithmetic is the forward arithmetic."""
+        """`packs` (optional): the step's StepPacks (or a sequence in its field order)"""
         out = actnorm_invconv_fwd(x, _f(an_bias), _f(an_logs), Wm.detach())
-        pk = StepPacks(*packs) if packs is not None else StepPacks()
-        ctx.packs = pk
-        h1, h2, o, P, masks = _net_fwd(out, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pk,
-                                       want_masks=any(ctx.needs_input_grad))
+        ctx.packs = pk = StepPacks(*packs)._asdict() if packs is not None else {}
+        ctx.route = route = _step_route(x, cond, w1, w2, w3, act, any(ctx.needs_input_grad))
+        h1, h2, o, P, masks = _net_fwd(out, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk)
         o, dlogdet = gather_affine_(out, o, P, _f(b3), _f(l3), _f(scale), _f(scale_shift), clamp_type)
         ctx.save_for_backward(x, cond, Wm, an_bias, an_logs, w1, n1l, w2, n2l, w3, l3, scale, scale_shift, out, h1, h2, o,
                               n1b, n2b, *(masks if masks is not None else ()))
@@ -1032,8 +1063,8 @@ class GlowStepFn(torch.autograd.Function):
         # ---- affine coupling bwd + Conv2dZeros epilogue bwd in one launch: gz (whole tensor), go = grad at conv3's output
         gz, go, gscale, gshift, gb3, gl3 = _affine_zeros_bwd(out, o, gout, gdl, scale, scale_shift, l3, clamp_type, arena)
         gcond = torch.empty_like(cond) if Cc > 0 else torch.zeros_like(cond)
-        gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, out, cond, h1, h2, w1, n1l, w2, n2l, w3, act, ctx.packs,
-                                                         arena, gz, gcond, False, n1b=n1b, n2b=n2b, masks=masks)
+        gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act,
+                                                         ctx.route, ctx.packs, arena, gz, gcond, False, masks=masks)
         # ---- invconv + actnorm bwd
         gx, gW, gab, gal = actnorm_invconv_bwd(x, _f(an_bias), _f(an_logs), Wm.detach(), gz, arena)
         return (gx, gcond, gW, gab.view(an_bias.shape), gal.view(an_logs.shape), gw1, gn1b.view(1, -1, 1, 1),
@@ -1065,8 +1096,8 @@ class GlowLevelFn(torch.autograd.Function):
             raise RuntimeError("GlowLevelFn: a flow level of C=%d channels on %dx%d maps does not fit the shell kernels "
                                "(C must be even and at most 144: rfn_glow_shell_supported)" % (C, H, W))
         prm = [flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)] for k in range(Kn)]
-        pks = [StepPacks(*packs[k]) if packs is not None and packs[k] is not None else StepPacks() for k in range(Kn)]
-        want_masks = any(ctx.needs_input_grad)
+        pks = [StepPacks(*packs[k])._asdict() if packs is not None and packs[k] is not None else {} for k in range(Kn)]
+        route = _step_route(x, cond, prm[0][2], prm[0][5], prm[0][8], act, any(ctx.needs_input_grad))   # of all K steps
         Wd = Wst.detach().contiguous()
         # log-det: every shell launch WRITES its per-block partial sums into its own slice; one reduce launch adds them
         # per frame in a fixed order (no float atomics anywhere in the forward pass: bit-reproducible)
@@ -1083,7 +1114,7 @@ class GlowLevelFn(torch.autograd.Function):
         outs, h1s, h2s, os_, mks = [], [], [], [], []
         for k in range(Kn):
             (_, _, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift) = prm[k]
-            h1, h2, o, P, masks = _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, pks[k], want_masks)
+            h1, h2, o, P, masks = _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pks[k])
             mks.append(masks)
             last = k == Kn - 1
             zn = None if last else torch.empty_like(z)
@@ -1111,12 +1142,12 @@ class GlowLevelFn(torch.autograd.Function):
         has_masks = all(m is not None for m in mks)
         ctx.save_for_backward(x, cond, Wst, *flat, *outs, *h1s, *h2s, *os_,
                               *([m[0] for m in mks] + [m[1] for m in mks] if has_masks else []))
-        ctx.cfg = (act, clamp_type, Kn, pks, has_masks)
+        ctx.cfg = (act, clamp_type, Kn, pks, has_masks, route)
         return outs[-1], dl
 
     @staticmethod
     def backward(ctx, gout, gdl):
-        act, clamp_type, Kn, pks, has_masks = ctx.cfg
+        act, clamp_type, Kn, pks, has_masks, route = ctx.cfg
         sv = ctx.saved_tensors
         x, cond, Wst = sv[0], sv[1], sv[2]
         nf = STEP_NPARAM * Kn
@@ -1153,9 +1184,9 @@ class GlowLevelFn(torch.autograd.Function):
         for k in range(Kn - 1, -1, -1):
             (an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift) = prm[k]
             nfin = len(fin)
-            gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, outs[k], cond, h1s[k], h2s[k], w1, n1l, w2, n2l, w3, act,
-                                                             pks[k], arena, gz, gcond, k != Kn - 1, defer,
-                                                             n1b=n1b, n2b=n2b, masks=mks[k], fin=fin)
+            gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, outs[k], cond, h1s[k], h2s[k], w1, n1b, n1l, w2, n2b, n2l,
+                                                             w3, act, route, pks[k], arena, gz, gcond, k != Kn - 1, defer,
+                                                             masks=mks[k], fin=fin)
             if len(fin) > nfin:
                 fin[-1].append(k)   # the step whose (possibly deferred) weight gradients the ticket needs
             base = STEP_NPARAM * k
@@ -1225,43 +1256,18 @@ class GlowStepRevFn(torch.autograd.Function):
         """`pkcache` (optional dict, owned by the caller): packed weights of this step, filled on first use and reused
         while the caller keeps it -- autoregressive generation runs the same step once per frame on unchanged weights."""
         N, C, H, W = x.shape
-        Ch = C // 2
-        Hd = int(w1.shape[0])
-        f = lambda t: None if t is None else t.detach().reshape(-1).contiguous()
         z = x.detach().clone()
-        cin2 = cond if cond.shape[1] > 0 else None
-        fp = fwd_prec(H, W)
-        Cc_ = 0 if cin2 is None else int(cin2.shape[1])
-        pkc = pkcache if pkcache is not None else {}
-
-        def cached(key, make):
-            if key not in pkc:
-                pkc[key] = make()
-            return pkc[key]
-        if coupling_po_ok(N, C, Cc_, Hd, H, W, w1, w3) and int(w2.shape[2]) == 1:
-            def make_po():
-                plan = POPackPlan([(w1.detach(), w2.detach(), w3.detach())])
-                plan.run()
-                return plan.bufs[0]
-            _, _, P, _ = coupling_po_fwd(z, cin2, cached("po", make_po), f(n1b), f(n1l), f(n2b), f(n2l), C, act)
+        route = _step_route(x, cond, w1, w2, w3, act, False, reverse=True)
+        # (one set of packs per forward arithmetic: CONV_PRECISION may change while the caller keeps the dict)
+        pk = (pkcache if pkcache is not None else {}).setdefault(route.fwd_prec, {})
+        _, _, o, P, _ = _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk)
+        if P is not None:
             o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
-            b3f, l3f = f(b3), f(l3)
+            b3f, l3f = _f(b3), _f(l3)
             L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b3f), L.dev(l3f), L.dev(o), _i(N), _i(C), _i(H), _i(W))
-        else:
-            h1 = conv2d_raw(z[:, :Ch], cin2, cached(("w1", fp), lambda: pack_weight(w1, prec=fp)), Hd, int(w1.shape[2]), 1,
-                            f(n1b), f(n1l), act, prec=fp)
-            h2 = conv2d_raw(h1, None, cached(("w2", fp), lambda: pack_weight(w2, prec=fp)), Hd, int(w2.shape[2]), 1,
-                            f(n2b), f(n2l), act, prec=fp)
-            if zeros_conv_uses_taps(w3):
-                C3, Cin3 = int(w3.shape[0]), int(w3.shape[1])
-                pk3 = cached(("w3t", fp), lambda: pack_weight(
-                    w3.detach().permute(2, 3, 0, 1).reshape(9 * C3, Cin3, 1, 1).contiguous(), prec=fp))
-            else:
-                pk3 = cached(("w3", fp), lambda: pack_weight(w3, prec=fp))
-            o = zeros_conv_fwd(h2, w3, f(b3), f(l3), pk3, prec=fp)
         dlogdet = torch.zeros(N, device=x.device, dtype=torch.float32)
-        affine_coupling_(z, o, f(scale), f(scale_shift), dlogdet, clamp_type, True)
-        out = invconv_actnorm_rev(z, f(an_bias), f(an_logs), Winv.detach())
+        affine_coupling_(z, o, _f(scale), _f(scale_shift), dlogdet, clamp_type, True)
+        out = invconv_actnorm_rev(z, _f(an_bias), _f(an_logs), Winv.detach())
         ctx.mark_non_differentiable(out, dlogdet)
         return out, dlogdet
 
