@@ -17,10 +17,11 @@
  *     being captured into a hipGraph: run the shape eagerly once first) and serves every stream of the device, so
  *     split-K convolutions on DIFFERENT streams of one device must not overlap in time;
  *   - return value: 0 on success, otherwise a hipError_t / negative argument-check code; rfn_last_error() gives text;
- *   - global state: the (thread-local) last-error string, and six developer knobs that the kernel selectors read ONCE
+ *   - global state: the (thread-local) last-error string, and seven developer knobs that the kernel selectors read ONCE
  *     from the environment at their first call and then keep for the life of the process: RFN_CONV_WS (0: no
  *     weight-stationary kernels), RFN_WGRAD_DMA (0: no LDS-DMA ring kernels), RFN_CONV_VARIANT, RFN_WGRAD_VARIANT,
- *     RFN_WGRAD_SPLIT, RFN_WGRAD_BPX128 (tile / split-K experiments; unset = production choice).  They pick between
+ *     RFN_WGRAD_SPLIT, RFN_WGRAD_BPX128, RFN_WGRAD_NARROW_PER_CU (tile / split-K experiments; unset = production choice).
+ *     They pick between
  *     kernels that compute the same result; nothing else is cached between calls, and the library is safe to call from
  *     several host threads on distinct streams.  The *_kernel_label_* queries answer with the same knobs applied, so a
  *     caller may cache their answers for the life of the process.
@@ -318,6 +319,18 @@ int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, long g_ns, 
                                               float* const* gw, int G, int F, int H, int W, rfn_stream_t stream);
 /* label query for both (G = 0: the ungrouped entry point) */
 const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W);
+/* The same for a 3x3 conv with FEW outputs (Cin -> C, the last conv of a coupling net), roles swapped and taps mirrored:
+ * the Cin rows of the conv's input h are the big operand, the C gradient planes g are shifted while staging -- no
+ * tap-scattered copy of g in memory.  gwT[Cin][C*9] += sum over frames and pixels of h[ci][q] * g[co][q - tap], column
+ * index co*9 + tap: gwT is the TRANSPOSE [Cin][C][3][3] of the torch layout; zeroed by the caller.  W % 8 == 0; code -5
+ * when the shape has no mirrored route.  (The narrow column tiles of the ring kernel start
+ * rfn_wgrad_split_workgroups' count with 512 in place of 256: two workgroups per CU.) */
+int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C, float* gwT,
+                                      int F, int H, int W, rfn_stream_t stream);
+int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, long h_ns, int Cin, const float* const* g, long g_ns,
+                                              int C, float* const* gwT, int G, int F, int H, int W, rfn_stream_t stream);
+/* label query for both (G = 0: the ungrouped entry point); "" when the shape has no mirrored route */
+const char* rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H, int W);
 /* K split of a GROUPED launch of the LDS-DMA ring kernels (gemm_wgrad_dma_kernel, gemm_wgrad_dma_impl_kernel), as
  * host-only queries that launch nothing and run the very functions the kernels and launchers run.  The unit of work is
  * the flat stage space of one output tile: G * n_stages stages (n_stages = F * HW / 32), group g owning

@@ -4,6 +4,9 @@
 //   * 1x1 conv:                 A = grad [M = Cout],       B = input [N = Cin]
 //   * 3x3 conv, Cin <= Cout:    A = grad,                  B = im2col3x3(input) [N = 9*Cin]   (rfn_im2col3x3_f32)
 //   * 3x3 conv, Cout <  Cin:    A = tap_scatter(grad) [M = 9*Cout] (rfn_tap_scatter_f32),     B = input
+// (the two 3x3 forms on maps whose rows are a multiple of 8 pixels skip the expansion: the implicit kernels build the
+// shifted planes of the small operand while staging -- the input's for Cin <= Cout, the gradient's, taps mirrored and
+// roles swapped, for the few-output conv behind rfn_conv3x3_wgrad_mirrored_bf16x3)
 // so the shifted-window reads of a 3x3 weight gradient never reach this kernel and the 8 consecutive k (pixels) an
 // MFMA operand lane needs are 8 consecutive fp32 of one channel plane in NCHW: staged with 16-byte loads, split into
 // bf16 hi/lo (see conv_bf16x3.hip) and stored as [row][k-group] 16-byte units with an odd row stride, so both fragment
@@ -27,6 +30,10 @@ struct GemmWgradParams {
     const float* b2;
     long b2_ns;
     int C1, C2, H, W;
+    // mirrored taps (implicit mode): row n = ci*9 + tap takes the plane shifted by the OPPOSITE tap, (1 - tap/3,
+    // 1 - tap%3) -- the weight gradient of a convolution whose GRADIENT is the small operand B and whose input is A:
+    // gw[co][ci][t] = sum_p g[co][p] in[ci][p + t] = sum_q in[ci][q] g[co][q - t], stored [Cin][Cout * 9]
+    int mirror;
     // grouped launch (G > 0): G independent gradients of the SAME shape in one launch -- the K steps of a flow level, one
     // atomic tail instead of K.  gemm_wgrad_b3_kernel: blockIdx.z = grp * mtiles + mt, a K split per group; the ring
     // kernels: no grid dimension carries the group, the workgroups of a tile split the groups' flat stage range
@@ -99,8 +106,9 @@ __host__ __device__ inline bool wg_split_part(int G, int n_stages, int Wt, int w
     return true;
 }
 // workgroups per output tile of a grouped ring launch: the chip's 256 CUs over the tiles, at least 8 stages each
-__host__ __device__ inline int wg_split_workgroups(int tiles, int G, int n_stages) {
-    long Wt = 256 / tiles, cap = (long)G * n_stages / 8;
+// (`slots`: workgroups the chip holds at once -- 512 for the tiles of which two fit a CU)
+__host__ __device__ inline int wg_split_workgroups(int tiles, int G, int n_stages, int slots = 256) {
+    long Wt = slots / tiles, cap = (long)G * n_stages / 8;
     if (Wt > cap) Wt = cap;
     return Wt < 1 ? 1 : (int)Wt;
 }
@@ -168,8 +176,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
             if (row >= p.N) row = 0;
             // row = ci*9 + tap: the output [Cout][9*Cin] IS the torch weight layout [Cout][Cin][3][3]
             const int ci = row / 9, tap = row - ci * 9;
-            udy[u] = tap / 3 - 1;
-            udx[u] = tap % 3 - 1;
+            udy[u] = p.mirror ? 1 - tap / 3 : tap / 3 - 1;
+            udx[u] = p.mirror ? 1 - tap % 3 : tap % 3 - 1;
             const bool first = ci < p.C1;
             uplane[u] = first ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
             uns[u] = first ? p.b_ns : p.b2_ns;
@@ -613,13 +621,25 @@ static void launch_gemm_wgrad_dma(GemmWgradParams& p, hipStream_t s) {
 // planes with the shift and the (hi, lo) split, into a double buffer of bf16 planes: the loads of stage t + 1 are issued
 // at the top of stage t, committed at its end (which also certifies that the DMA pieces issued before them have landed:
 // vector-memory operations complete in order), and the barrier at the top of stage t + 1 publishes both.
+//
+// Narrow column tiles (BN <= 64: the mirrored conv3 gradient of flow level 0, 36 columns) do a few hundred cycles of
+// MFMAs per stage against some thousand of DMA, so one workgroup per CU -- one stage in flight -- is bound by latency.
+// Two workgroups share a CU instead: 128 registers per lane (the second launch bound: 4 waves per SIMD) and 80 KB of
+// LDS each, which the B planes reach without the pad unit -- their rows are 4 units (64 B) and the unit order inside a
+// row is XOR-swizzled with (row / 4) & 3, conflict-free for the 16-lane groups of the fragment reads and 256 contiguous
+// bytes per 16 lanes for the commit's stores.
+constexpr int wg_impl_waves_per_simd(int NW, int BN) { return NW == 8 && BN <= 64 ? 4 : NW / 4; }
+constexpr size_t wg_impl_lds(int BM, int BN) { return (size_t)2 * BM * 128 + (size_t)2 * 2 * BN * (BN <= 64 ? 4 : 5) * 16; }
+
 template <int WM, int WN, int TM, int TN>
-__global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
+__global__ __launch_bounds__(64 * WM * WN, wg_impl_waves_per_simd(WM * WN, 32 * TN * WN))
+void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
     constexpr int NW = WM * WN, NT = 64 * NW, KP = 32, NK = KP / 16;
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     constexpr int PIECES = BM / 8, PPW = PIECES / NW;   // 1-KB DMA pieces (8 rows x 128 B) of the A rows per stage / wave
     constexpr int ASLOT = BM * 128;
-    constexpr int NU = KP / 8, RS = NU + 1;             // B planes: 16-byte units per row, row stride (conflict-free)
+    constexpr bool SWZB = BN <= 64;                     // B planes without the pad unit, swizzled (see above)
+    constexpr int NU = KP / 8, RS = SWZB ? NU : NU + 1; // B planes: 16-byte units per row, row stride (conflict-free)
     constexpr int BU = (BN * NU + NT - 1) / NT;         // B units staged per thread
     constexpr int BPLANE = BN * RS;                     // units per plane
     static_assert(PIECES % NW == 0 && NT % NU == 0 && TM % 2 == 0, "shares / parities");
@@ -665,8 +685,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
         int row = n0 + r0 + u * (NT / NU);
         if (row >= p.N) row = 0;
         const int ci = row / 9, tap = row - ci * 9;
-        udy[u] = tap / 3 - 1;
-        udx[u] = tap % 3 - 1;
+        udy[u] = p.mirror ? 1 - tap / 3 : tap / 3 - 1;
+        udx[u] = p.mirror ? 1 - tap % 3 : tap % 3 - 1;
         uin1[u] = ci < p.C1;
         uplane[u] = uin1[u] ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
         uns[u] = uin1[u] ? p.b_ns : p.b2_ns;
@@ -728,8 +748,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
                     hi[c] = h;
                     lo[c] = (__bf16)(x - (float)h);
                 }
-                Bh[row * RS + kg] = hi;
-                Bl[row * RS + kg] = lo;
+                const int o = row * RS + (SWZB ? kg ^ ((row >> 2) & 3) : kg);
+                Bh[o] = hi;
+                Bl[o] = lo;
             }
         }
     };
@@ -738,7 +759,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
         r[0] = *reinterpret_cast<const f32x4*>(sb + o);
         r[1] = *reinterpret_cast<const f32x4*>(sb + (o ^ 16));
     };
-    const int brow = (wn * TN * 32 + l31) * RS + kk;
+    const int brow = (wn * TN * 32 + l31) * RS + (SWZB ? kk ^ ((l31 >> 2) & 3) : kk);   // unit kk + 2 s = kk ^ 2 s
 
     // one pass per part (see gemm_wgrad_dma_kernel)
     WgPart part;
@@ -800,8 +821,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_impl_kernel(const
                 bf16x8 bh[TN], bl[TN];
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    bh[j] = Bh[brow + j * 32 * RS + 2 * s_];
-                    bl[j] = Bl[brow + j * 32 * RS + 2 * s_];
+                    const int o = SWZB ? (brow + j * 32 * RS) ^ (2 * s_) : brow + j * 32 * RS + 2 * s_;
+                    bh[j] = Bh[o];
+                    bl[j] = Bl[o];
                 }
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -840,9 +862,12 @@ template <int WM, int WN, int TM, int TN>
 static void launch_gemm_wgrad_dma_impl(GemmWgradParams& p, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     p.n_stages = (int)(p.total / 32);
-    const size_t lds = (size_t)2 * BM * 128 + (size_t)2 * 2 * BN * 5 * 16;
+    const size_t lds = wg_impl_lds(BM, BN);
     const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages);   // (see launch_gemm_wgrad_dma)
+    // (see launch_gemm_wgrad_dma); the narrow tiles at two workgroups per CU.  RFN_WGRAD_NARROW_PER_CU=1: one
+    static const int narrow_per_cu = getenv("RFN_WGRAD_NARROW_PER_CU") ? atoi(getenv("RFN_WGRAD_NARROW_PER_CU")) : 2;
+    const int per_cu = 2 * lds <= 160 * 1024 && narrow_per_cu == 2 ? 2 : 1;
+    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages, 256 * per_cu);
     auto kern = gemm_wgrad_dma_impl_kernel<WM, WN, TM, TN>;
     static_assert(wg_sole_argument(decltype(kern){}), "wg_operands_kernarg reads p from the kernel-argument segment");
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -876,7 +901,8 @@ static void launch_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
 // launch_wgrad_route is the only place a route is mapped to a launch, the label queries of the C ABI read the same table.
 // Instantiations: gemm_wgrad_dma_kernel<WM,WN,TM,TN,KP,NST>, gemm_wgrad_b3_kernel<WM,WN,TM,TN,KP[,IMPL]>.
 enum WgradB3Route { DMA_256x256, DMA_64x256, R_256x192, R_256x192_KP32, R_256x256, R_256x256_KP32, R_64x256, R_256x64,
-                    R_128x128, IMPL_DMA_256x192, IMPL_256x192, IMPL_32x256, IMPL_128x128 };
+                    R_128x128, IMPL_DMA_256x192, IMPL_256x192, IMPL_32x256, IMPL_128x128, IMPL_DMA_256x64,
+                    IMPL_DMA_256x128 };
 static const char* const kWgradB3Labels[] = {
     "gemm_wgrad_dma_kernel<2,4,4,2,32,2>",   // 256 x 256, two slots of 64 KB
     "gemm_wgrad_dma_kernel<1,8,2,1,32,3>",   // 64 x 256, ring of 3 x 40 KB
@@ -891,8 +917,10 @@ static const char* const kWgradB3Labels[] = {
     "gemm_wgrad_b3_kernel<4,2,2,3,64,1>",    // 256 x 192, 8 waves
     "gemm_wgrad_b3_kernel<1,4,1,2,32,1>",    // 32 x 256
     "gemm_wgrad_b3_kernel<2,2,2,2,64,1>",    // 128 x 128
+    "gemm_wgrad_dma_impl_kernel<4,2,2,1>",   // implicit 3x3, narrow: 256 x 64, two workgroups per CU (mirrored conv3, C = 4)
+    "gemm_wgrad_dma_impl_kernel<4,2,2,2>",   // 256 x 128 (mirrored conv3, C = 8)
 };
-static_assert(sizeof(kWgradB3Labels) / sizeof(kWgradB3Labels[0]) == IMPL_128x128 + 1, "one label per route");
+static_assert(sizeof(kWgradB3Labels) / sizeof(kWgradB3Labels[0]) == IMPL_DMA_256x128 + 1, "one label per route");
 static bool wgrad_dma_off() {
     static const int off = getenv("RFN_WGRAD_DMA") ? atoi(getenv("RFN_WGRAD_DMA")) == 0 : 0;
     return off;
@@ -940,6 +968,29 @@ extern "C" const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, 
     return kWgradB3Labels[choose_wgrad_implicit(wgrad_shape(Cout, 0, g_ns, 0, G, F, H * W))];
 }
 
+// Mirrored form (rfn_conv3x3_wgrad_mirrored_bf16x3 below): the weight gradient of a 3x3 conv with FEW outputs (the last
+// conv of a coupling net, 256 -> C): M = Cin rows of the conv's input h through the ring, the C gradient planes as the
+// shifted operand, 9 C columns.  false: the shape has no mirrored route (rows of the map that are no multiple of 8
+// pixels) and the caller expands the gradient in HBM as before.
+static bool choose_wgrad_implicit_mirrored(const GemmWgradParams& p, WgradB3Route& r) {
+    if (p.W % 8 != 0) return false;
+    if (p.M > 128 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 && !wgrad_dma_off() && p.HW % 32 == 0 &&
+        p.a_ns % 4 == 0) {
+        // a column tile that fits 9 C: 36 -> 64, 72 -> 128 (8 waves; a 4-wave 256 x 96 tile was 5 % slower), 144 -> 192
+        r = p.N <= 64 ? IMPL_DMA_256x64 : (p.N <= 128 ? IMPL_DMA_256x128 : IMPL_DMA_256x192);
+        return true;
+    }
+    r = p.M > 128 && p.total >= 100000 ? IMPL_256x192 : IMPL_128x128;
+    return true;
+}
+extern "C" const char* rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H,
+                                                                      int W) {
+    GemmWgradParams p = wgrad_shape(Cin, 9 * C, h_ns, 0, G, F, H * W);
+    p.H = H; p.W = W;
+    WgradB3Route r;
+    return choose_wgrad_implicit_mirrored(p, r) ? kWgradB3Labels[r] : "";
+}
+
 // K split of the grouped ring launches, as queries that launch nothing: the workgroups per output tile the launchers
 // start, and the parts (group, first stage, count) of workgroup w of Wt -- the very functions the kernels run
 extern "C" int rfn_wgrad_split_workgroups(int tiles, int G, int n_stages) {
@@ -974,6 +1025,8 @@ static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s
         case IMPL_256x192:     return launch_gemm_wgrad<4, 2, 2, 3, 64, 1>(p, s);
         case IMPL_32x256:      return launch_gemm_wgrad<1, 4, 1, 2, 32, 1>(p, s);
         case IMPL_128x128:     return launch_gemm_wgrad<2, 2, 2, 2, 64, 1>(p, s);
+        case IMPL_DMA_256x64:  return launch_gemm_wgrad_dma_impl<4, 2, 2, 1>(p, s);
+        case IMPL_DMA_256x128: return launch_gemm_wgrad_dma_impl<4, 2, 2, 2>(p, s);
     }
 }
 
@@ -1056,6 +1109,55 @@ extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, 
     p.C1 = C1; p.C2 = C2; p.H = H; p.W = W; p.N = 9 * (C1 + C2); p.F = F; p.HW = H * W;
     p.total = (long)F * H * W;
     launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+// 3x3 weight gradient of a conv with few outputs, without the tap-scattered gradient buffer: the roles of the implicit
+// form swapped and the taps mirrored (GemmWgradParams::mirror).  gwT[ci][co][tap] = sum_{frames,pixels} h[ci][q] *
+// g[co][q - tap] = gw[co][ci][tap]: the TRANSPOSE of the torch layout, [Cin][C][3][3].  -5: the shape has no mirrored
+// route (rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3 returns "").
+extern "C" int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C,
+                                                 float* gwT, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(h && g && gwT && Cin > 0 && C > 0 && F >= 0 && H > 0 && W > 0, -1);
+    RFN_CHECK_ARG(W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
+    RFN_CHECK_ARG((((uintptr_t)h | (uintptr_t)g) & 15) == 0, -3);
+    RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
+    if (F == 0) return 0;
+    GemmWgradParams p;
+    memset(&p, 0, sizeof(p));
+    p.a = h; p.a_ns = h_ns; p.M = Cin; p.b = g; p.b_ns = g_ns; p.b2 = g; p.b2_ns = g_ns;
+    p.C1 = C; p.C2 = 0; p.H = H; p.W = W; p.N = 9 * C; p.gw = gwT; p.F = F; p.HW = H * W; p.mirror = 1;
+    p.total = (long)F * H * W;
+    WgradB3Route r;
+    RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
+    launch_wgrad_route(p, r, (hipStream_t)stream);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+// grouped form: G gradients of one shape (per group: h, g, gwT)
+extern "C" int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, long h_ns, int Cin, const float* const* g,
+                                                         long g_ns, int C, float* const* gwT, int G, int F, int H, int W,
+                                                         rfn_stream_t stream) {
+    RFN_CHECK_ARG(h && g && gwT && G >= 1 && G <= 16 && Cin > 0 && C > 0 && F >= 0, -1);
+    RFN_CHECK_ARG(H > 0 && W > 0 && W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
+    RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
+    if (F == 0) return 0;
+    GemmWgradParams p;
+    memset(&p, 0, sizeof(p));
+    for (int i = 0; i < G; ++i) {
+        RFN_CHECK_ARG(h[i] && g[i] && gwT[i], -3);
+        RFN_CHECK_ARG((((uintptr_t)h[i] | (uintptr_t)g[i]) & 15) == 0, -3);
+        p.ga[i] = h[i]; p.gb[i] = g[i]; p.gb2[i] = g[i]; p.ggw[i] = gwT[i];
+    }
+    p.G = G; p.a = h[0]; p.b = g[0]; p.b2 = g[0]; p.gw = gwT[0];
+    p.a_ns = h_ns; p.M = Cin; p.b_ns = g_ns; p.b2_ns = g_ns;
+    p.C1 = C; p.C2 = 0; p.H = H; p.W = W; p.N = 9 * C; p.F = F; p.HW = H * W; p.mirror = 1;
+    p.total = (long)F * H * W;
+    WgradB3Route r;
+    RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
+    launch_wgrad_route(p, r, (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }

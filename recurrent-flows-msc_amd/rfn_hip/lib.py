@@ -83,6 +83,9 @@ SIGNATURES = {
                                           _c_s],
     "rfn_gemm_wgrad_kernel_label_bf16x3": [_c_i, _c_i, _c_l, _c_l, _c_i, _c_i, _c_i],
     "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i],
+    "rfn_conv3x3_wgrad_mirrored_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
+    "rfn_conv3x3_wgrad_mirrored_grouped_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i],
     "rfn_wgrad_split_workgroups": [_c_i, _c_i, _c_i],
     "rfn_wgrad_split_parts": [_c_i, _c_i, _c_i, _c_i, ctypes.c_void_p, _c_i],
     "rfn_im2col3x3_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
@@ -163,6 +166,7 @@ _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": c
              "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,
              "rfn_gemm_wgrad_kernel_label_bf16x3": ctypes.c_char_p,
              "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": ctypes.c_char_p,
+             "rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3": ctypes.c_char_p,
              "rfn_glow_shell_fwd_kernel_label": ctypes.c_char_p, "rfn_glow_shell_bwd_kernel_label": ctypes.c_char_p,
              "rfn_stepbn_kernel_label": ctypes.c_char_p, "rfn_convlstm_gates_kernel_label": ctypes.c_char_p,
              "rfn_latent_step_kernel_label": ctypes.c_char_p,

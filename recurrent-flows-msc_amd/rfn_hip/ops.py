@@ -635,8 +635,35 @@ def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None, taps=None):
     return o
 
 
+def _mirrored_wgrad_label(x, C, ks, G):
+    """label of the mirrored 3x3 weight-gradient launch (rfn_conv3x3_wgrad_mirrored[_grouped]_bf16x3: the conv's input
+    x [N, Cin, H, W] through the ring, the C gradient planes shifted while staging, no tap-scattered copy) for G groups
+    (0: the single form), or '' when the gradient takes conv2d_wgrad's routes: another arithmetic, Cin <= C (the
+    implicit form proper), RFN_WGRAD_MIRRORED=0, or a shape for which the library names no mirrored kernel."""
+    N, Cin, H, W = x.shape
+    if ks != 3 or Cin <= C or not bwd_b3() or (H * W) % 4 != 0 or os.environ.get("RFN_WGRAD_MIRRORED") == "0":
+        return ""
+    return kernel_label("rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3", int(Cin), L.frames(x, "x")[1], int(C), G, int(N),
+                        int(H), int(W))
+
+
+def _mirrored_wgrad_meta(label, G, N, Cin, C, HW):
+    return ("wgrad", label, 2.0 * max(G, 1) * N * HW * Cin * 9 * C,
+            "%sF%d %dx%d HW%d mirrored3x3" % ("G%d " % G if G else "", N, Cin, 9 * C, HW),
+            4.0 * max(G, 1) * (N * HW * (Cin + C) + Cin * 9 * C))
+
+
 def zeros_conv_wgrad(x, g_pre, C, ks, arena=None):
     """weight gradient of the conv inside Conv2dZeros given g_pre = grad wrt (conv + b); same switch as the forward."""
+    label = _mirrored_wgrad_label(x, C, ks, 0)
+    if label:
+        N, Cin, H, W = x.shape
+        xp, xns = L.frames(x, "x")
+        gp, gns = L.frames(g_pre.contiguous(), "g")
+        gwT = _zeros(arena, Cin, C, 3, 3, device=x.device)
+        L.call("rfn_conv3x3_wgrad_mirrored_bf16x3", xp, _l(xns), _i(Cin), gp, _l(gns), _i(C), L.dev(gwT), _i(N), _i(H),
+               _i(W), meta=_mirrored_wgrad_meta(label, 0, N, Cin, C, H * W))
+        return gwT.permute(1, 0, 2, 3).contiguous()
     if ks != 3 or C > TAP_MAX_COUT or (bwd_b3() and _hw(x) % 4 == 0):
         return conv2d_wgrad(x, None, g_pre, C, ks, arena)
     N, Cin, H, W = x.shape
@@ -645,6 +672,40 @@ def zeros_conv_wgrad(x, g_pre, C, ks, arena=None):
            meta=_shell("tap_scatter", Gs, 10.0 / 9.0))
     gw = conv2d_wgrad(x, None, Gs, 9 * C, 1, arena)  # [9C, Cin, 1, 1]
     return gw.view(3, 3, C, Cin).permute(2, 3, 0, 1).contiguous()
+
+
+LEVEL_MIRRORED_MIN_PIXELS = 1 << 17
+
+
+def level_mirrored_min_pixels():
+    """fewest pixels G * N * H * W of a flow level's K conv3 gradients at which the level node takes the mirrored launch:
+    RFN_WGRAD_MIRRORED_MIN_PIXELS, or 2^17.  Smaller levels keep tap scatter + GEMM, the route they had: just above the
+    ring threshold (100 000 pixels) the two routes are within 8 us of each other either way."""
+    env = os.environ.get("RFN_WGRAD_MIRRORED_MIN_PIXELS")
+    return int(env) if env is not None else LEVEL_MIRRORED_MIN_PIXELS
+
+
+def zeros_conv_wgrad_grouped(h2_list, go_list, C, arena=None, g_stacked=None, ks=3, min_pixels=0):
+    """zeros_conv_wgrad for the G convolutions of one shape of a flow level: list of G tensors [C, Cin, ks, ks].  One
+    mirrored launch and one transposing copy for all groups where the library names a mirrored kernel (and the G groups
+    have `min_pixels` pixels together), else conv2d_wgrad_grouped (which expands the gradients -- the slices of
+    `g_stacked` in one launch -- in memory)."""
+    G = len(go_list)
+    label = _mirrored_wgrad_label(h2_list[0], C, ks, G)
+    if label and G * int(h2_list[0].shape[0]) * _hw(h2_list[0]) < min_pixels:
+        label = ""
+    if not label:
+        return conv2d_wgrad_grouped(h2_list, None, go_list, C, ks, arena, g_stacked=g_stacked)
+    N, Cin, H, W = h2_list[0].shape
+    go_list = [g.contiguous() for g in go_list]
+    gwT = _zeros(arena, G, Cin, C, 3, 3, device=h2_list[0].device)
+    xns, gns = L.frames(h2_list[0], "x")[1], L.frames(go_list[0], "g")[1]
+    px, pg = L.ptr_array(h2_list, "x"), L.ptr_array(go_list, "g")
+    pw = L.ptr_array([gwT[i] for i in range(G)], "gw")
+    L.call("rfn_conv3x3_wgrad_mirrored_grouped_bf16x3", px, _l(xns), _i(Cin), pg, _l(gns), _i(C), pw, _i(G), _i(N),
+           _i(H), _i(W), meta=_mirrored_wgrad_meta(label.replace("<", "<grouped "), G, N, Cin, C, H * W))
+    gw = gwT.permute(0, 2, 1, 3, 4).contiguous()   # one copy for all groups
+    return [gw[i] for i in range(G)]
 
 
 def conv_epilogue_bwd(y, gy, logs, ep_mode, act, want_gl=True, arena=None, inplace=True):
@@ -1234,8 +1295,8 @@ class GlowLevelFn(torch.autograd.Function):
                                       None if defer["w1"][0][1] is None else [t[1] for t in defer["w1"]],
                                       [t[2] for t in defer["w1"]], Hd_, k1, arena)
             g2 = conv2d_wgrad_grouped([t[0] for t in defer["w2"]], None, [t[1] for t in defer["w2"]], Hd_, k2, arena)
-            g3 = conv2d_wgrad_grouped([t[0] for t in defer["w3"]], None, [t[1] for t in defer["w3"]], C, k3, arena,
-                                      g_stacked=go_all)
+            g3 = zeros_conv_wgrad_grouped([t[0] for t in defer["w3"]], [t[1] for t in defer["w3"]], C, arena,
+                                          g_stacked=go_all, ks=k3, min_pixels=level_mirrored_min_pixels())
             for k in range(Kn):
                 base = STEP_NPARAM * k
                 grads[base + 2], grads[base + 5], grads[base + 8] = g1[k], g2[k], g3[k]

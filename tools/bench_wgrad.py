@@ -2,6 +2,8 @@
 against the register-staged one.  python tools/bench_wgrad.py   (RFN_WGRAD_DMA=0 for the register-staged kernel)
 python tools/bench_wgrad.py level [frames ...]: the three weight gradients of a Glow step at flow levels 0 - 2 (K = 10
 steps per level), as ten single launches and as one grouped launch, GEMM launches only (HIP events of rfn_hip.lib.PROFILE).
+conv3 gets a second row, `mirrored`: tap scatter + GEMM (both launches counted) beside the one mirrored launch that shifts
+the gradient while staging.  python tools/bench_wgrad.py conv3 [frames ...]: the conv3 rows only.
 RFN_PKG_DIR selects another build of the package (A/B on the same box, as bench.py)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -46,9 +48,9 @@ def run_implicit(F_, C1, C2, S, reps=10):
     print("F%d 256x%d %dx%d implicit3x3  %.3f ms  %.2f TB/s" % (F_, 9 * (C1 + C2), S, S, dt * 1e3, by / dt / 1e12), flush=True)
 
 
-def _wgrad_ms(fn, reps=5):
+def _wgrad_ms(fn, reps=5, also=()):
     """fn() reps times after one warm-up: (median over the reps of the summed weight-gradient GEMM time in ms, launches
-    per call, label of the first)"""
+    per call, label of the first); `also`: shell launches (by name) that count as well"""
     fn()
     torch.cuda.synchronize()
     sums = []
@@ -56,14 +58,14 @@ def _wgrad_ms(fn, reps=5):
         L.PROFILE = []
         fn()
         torch.cuda.synchronize()
-        ev = [(m[1], e0.elapsed_time(e1)) for (_, m, e0, e1) in L.PROFILE if m is not None and m[0] == "wgrad"]
+        ev = [(m[1], e0.elapsed_time(e1)) for (_, m, e0, e1) in L.PROFILE if m is not None and (m[0] == "wgrad" or m[1] in also)]
         L.PROFILE = None
         sums.append(sum(t for _, t in ev))
     sums.sort()
     return sums[len(sums) // 2], len(ev), ev[0][0]
 
 
-def level(F_, G=10):
+def level(F_, G=10, only=None):
     """conv1 (3x3, C/2 + cond -> 256), conv2 (1x1, 256 -> 256), conv3 (3x3, 256 -> C) of levels 0 - 2"""
     torch.manual_seed(0)
     rn = lambda *shape: torch.randn(*shape, device="cuda")
@@ -77,19 +79,28 @@ def level(F_, G=10):
                  ("conv2 256x256", h, None, gh, 256, 1, None),
                  ("conv3 %dx256" % (9 * C), h, None, [go[i] for i in range(G)], C, 3, go)]
         for name, in1, in2, gl, Cout, ks, stacked in cases:
+            if only is not None and not name.startswith(only):
+                continue
             one = lambda: [K.conv2d_wgrad(in1[i], None if in2 is None else in2[i], gl[i], Cout, ks) for i in range(G)]
             grp = lambda: K.conv2d_wgrad_grouped(in1, in2, gl, Cout, ks, g_stacked=stacked)
             t1, n1, l1 = _wgrad_ms(one)
             tg, ng, lg = _wgrad_ms(grp)
             print("F%d level %d %-14s  %d singles %7.3f ms (%s)   grouped G%d %7.3f ms in %d launch (%s)" % (
                 F_, lvl, name, n1, t1, l1, G, tg, ng, lg), flush=True)
+            if stacked is not None:
+                ts, ns, _ = _wgrad_ms(grp, also=("tap_scatter",))
+                row = "F%d level %d %-14s  scatter + GEMM %7.3f ms in %d launches" % (F_, lvl, "mirrored", ts, ns)
+                if hasattr(K, "zeros_conv_wgrad_grouped"):
+                    tm, nm, lm = _wgrad_ms(lambda: K.zeros_conv_wgrad_grouped(in1, gl, Cout, g_stacked=stacked))
+                    row += "   mirrored G%d %7.3f ms in %d launch (%s)" % (G, tm, nm, lm)
+                print(row, flush=True)
         del h, gh, z, cond, go
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "level":
+    if len(sys.argv) > 1 and sys.argv[1] in ("level", "conv3"):
         for F_ in [int(v) for v in sys.argv[2:]] or [608, 76]:
-            level(F_)
+            level(F_, only="conv3" if sys.argv[1] == "conv3" else None)
         sys.exit(0)
     run_implicit(608, 2, 16, 32)
     run_implicit(608, 4, 32, 16)
