@@ -408,6 +408,12 @@ int rfn_gauss_logp_bwd_f32(const float* z, long z_ns, const float* o, long o_ns,
 /* reverse / sampling (glow_modules.py:366-369, glow.py:153-154): z = mean + std*temperature*eps. */
 int rfn_gauss_sample_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns, float temperature, int layout,
                          int std_mode, int N, int Cz, int HW, rfn_stream_t stream);
+/* the same with one temperature per frame: z[n] = mean + std*temperature_rows[n]*eps, temperature_rows a device array of
+ * N floats.  The same kernel as rfn_gauss_sample_f32 (the pointer selects the row's value, uniform per block), so rows
+ * that hold the scalar's value give the scalar call's bits. */
+int rfn_gauss_sample_rows_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns,
+                              const float* temperature_rows, int layout, int std_mode, int N, int Cz, int HW,
+                              rfn_stream_t stream);
 
 /* ---- a10  SRNN latent step of RFN.loss (RFN/RFN_new.py:167-184,206-207 with SimpleParamNet's chunk + softplus,
  * Utils/modules.py:240-244): enc, pri = [B, 2*Z*HW] outputs of the encoder / prior parameter convs (loc half | raw scale
@@ -619,6 +625,12 @@ int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long
  * (none when nothing is to be written). */
 int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, long seed, int step,
                          long first_seq, long first_draw, rfn_stream_t stream);
+/* the same values `tiles` >= 1 times (common random numbers for a temperature sweep): every tensor
+ * is [tiles * rows, numel_j] and row k * rows + i holds exactly what row i holds above, for every tile k.  Still one
+ * launch of the untiled grid: a lane computes its eight values once and stores them `tiles` times.  tiles * rows must
+ * fit an int.  tiles == 1 is rfn_keyed_normal_f32. */
+int rfn_keyed_normal_tiled_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, int tiles, long seed,
+                               int step, long first_seq, long first_draw, rfn_stream_t stream);
 
 /* ---- clips of a device-resident frame store as float32 batches  (the per-item work of the file-backed datasets,
  * data_generators/bair_push.py:66-109 and data_generators/kth.py:34-65, and the DataLoader collation of

@@ -265,9 +265,11 @@ class RFN(nn.Module):
 
     # ------------------------------------------------------------------------------------------------ generation
     # `draws` (optional, tests): the noise in the reference's draw order, see each method.
-    def _gen_step(self, prediction, hprev, cprev, zprev, eps, kl_temp):
+    def _gen_step(self, prediction, hprev, cprev, zprev, eps, kl_temp, temperature=None):
         """one autoregressive generation step (RFN_new.py:331-356 / :480-491): frame t-1 -> frame t.
-        eps: [prior eps, flow base eps, Split2d eps (coarsest first) ...].  Returns (frame, ht, ct, zt)."""
+        eps: [prior eps, flow base eps, Split2d eps (coarsest first) ...].  Returns (frame, ht, ct, zt).
+        kl_temp: a number, or a [N, 1, 1, 1] tensor with one value per row; temperature: the flow's sampling
+        temperature, None for self.temperature, or an N-element device tensor with one value per row."""
         eps = list(eps)
         take = lambda ref=None: eps.pop(0)
         condition_list = self.extractor(prediction)
@@ -276,7 +278,7 @@ class RFN(nn.Module):
         zt = pm + ps * kl_temp * take(pm)
         hz = torch.cat((ht, zt), dim=1)
         fc = self._flow_conditions(hz, condition_list)
-        frame = self._flow_sample(fc, hz, take, True)
+        frame = self._flow_sample(fc, hz, take, True, temperature=temperature)
         return frame, ht, ct, zt
 
     def _gen_eps_shapes(self, B):
@@ -295,7 +297,7 @@ class RFN(nn.Module):
 
     _GEN_GRAPHS_KEPT = 4   # captured generation graphs kept per model, one per batch shape
 
-    def _gen_step_graphed(self, prediction, hprev, cprev, zprev, kl_temp, eps_fill=None):
+    def _gen_step_graphed(self, prediction, hprev, cprev, zprev, kl_temp, eps_fill=None, temp_rows=None):
         """_gen_step with fresh N(0,1) draws, replayed from a hipGraph: generation is one frame at a time, a few hundred
         launches of a few microseconds each, i.e. bound by the host's launch rate when launched eagerly (38 ms per frame at
         B = 32 against ~6 ms of GPU work).  A graph is rebuilt whenever a parameter changed (the inverse matrices and
@@ -304,7 +306,11 @@ class RFN(nn.Module):
         P*B alternate without a rebuild; `_gen_graph` is the one used last.
         eps_fill (optional): a callable that writes the draws into the list of eps tensors it is given, in place
         (predict_draws: addressed noise, written straight into the graph's inputs); without it the draws come from
-        torch's generator, L + 1 launches."""
+        torch's generator, L + 1 launches.
+        temp_rows (optional, predict_draws with per-row temperatures): (temperature [N], kl temperature [N]) device
+        tensors; kl_temp is then ignored and self.temperature is not read.  The two vectors are static inputs of the
+        graph, copied in before each replay like the state, and the graph's key holds the fact that the mode is
+        per-row, not the values: another list of temperatures at the same shapes and weights replays the same graph."""
         import rfn_hip
         dev = prediction.device
         shapes = self._gen_eps_shapes(prediction.shape[0])
@@ -318,11 +324,22 @@ class RFN(nn.Module):
         else:
             eps = None   # written into the graph's inputs below
         state = [prediction, hprev, cprev, zprev]
+        n_eps = len(shapes)
+
+        def step(ins):   # ins: the state, the draws [, temperature rows, kl temperature rows]
+            if temp_rows is None:
+                return self._gen_step(*ins[:4], ins[4:4 + n_eps], kl_temp)
+            return self._gen_step(*ins[:4], ins[4:4 + n_eps], ins[5 + n_eps].view(-1, 1, 1, 1), ins[4 + n_eps])
+
         if not ok:
-            return self._gen_step(prediction, hprev, cprev, zprev, eps, kl_temp)
+            return step(state + list(eps) + list(temp_rows or ()))
         shape_key = tuple(tuple(a.shape) for a in state) + tuple(shapes)
-        key = (tuple((p._version, p.data_ptr()) for p in self.parameters()), shape_key,
-               float(kl_temp), float(self.temperature))
+        if temp_rows is None:
+            key = (tuple((p._version, p.data_ptr()) for p in self.parameters()), shape_key,
+                   float(kl_temp), float(self.temperature))
+        else:
+            shape_key += ("rows",)   # its own entry: a scalar-mode graph of the same shapes is kept beside it
+            key = (tuple((p._version, p.data_ptr()) for p in self.parameters()), shape_key, "rows")
         graphs = self.__dict__.setdefault("_gen_graphs", {})
         g = graphs.pop(shape_key, None)
         if g is None or g[0] != key:
@@ -332,15 +349,17 @@ class RFN(nn.Module):
             else:
                 static_in += [torch.empty(sh, device=dev) for sh in shapes]
                 eps_fill(static_in[4:])
+            if temp_rows is not None:
+                static_in += [a.clone() for a in temp_rows]
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
                 for _ in range(2):  # warm-up on the capture path (lazy per-stream state, generation cache, MIOpen)
-                    self._gen_step(*static_in[:4], static_in[4:], kl_temp)
+                    step(static_in)
             torch.cuda.current_stream().wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = self._gen_step(*static_in[:4], static_in[4:], kl_temp)
+                static_out = step(static_in)
             g = (key, graph, static_in, static_out)
             self._gen_graph_builds = getattr(self, "_gen_graph_builds", 0) + 1
         graphs[shape_key] = g          # most recently used last
@@ -354,15 +373,20 @@ class RFN(nn.Module):
             for s_, a in zip(static_in[4:], eps):
                 s_.copy_(a)
         else:
-            eps_fill(static_in[4:])
+            eps_fill(static_in[4:4 + n_eps])
+        if temp_rows is not None:
+            for s_, a in zip(static_in[4 + n_eps:], temp_rows):
+                s_.copy_(a)
         graph.replay()
         return tuple(o.clone() for o in static_out)
 
-    def _flow_sample(self, fc, hz, take, pinned, z=None):
-        """flow.sample with pinned draws: base eps (only when z is None), then the Split2d eps list, coarsest first"""
+    def _flow_sample(self, fc, hz, take, pinned, z=None, temperature=None):
+        """flow.sample with pinned draws: base eps (only when z is None), then the Split2d eps list, coarsest first.
+        temperature: None for self.temperature, or a number, or one value per row as a device tensor"""
         eb = take() if (pinned and z is None) else None
         el = [take() for _ in range(self.L - 1)] if pinned else None
-        return self.flow.sample(z, fc, hz, temperature=self.temperature, eps_base=eb, eps_list=el)
+        return self.flow.sample(z, fc, hz, temperature=self.temperature if temperature is None else temperature,
+                                eps_base=eb, eps_list=el)
 
     # predict / reconstruct / sample end in `.cpu()`, as the reference's do; the `_*_device` bodies return the same
     # tensors where they were computed (Solver.plotter composes its sheet from them without a host round trip).
@@ -406,7 +430,8 @@ class RFN(nn.Module):
             predictions = torch.stack(frames, 0) if frames else torch.zeros((0, *x[:, 0].shape), device=x.device)
         return true_x, predictions
 
-    def predict_draws(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+    def predict_draws(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0,
+                      temperatures=None, kl_temperatures=None):
         """`predict` for n_draws independent draws of every sequence in one pass, with addressed noise: returns
         (true_x, predictions), predictions [n_predictions, n_draws, B, C, H, W] on the CPU (`_predict_draws_device`: the
         same on the device).  The extractor and the ConvLSTM run once over the conditioning frames of the B sequences;
@@ -417,12 +442,48 @@ class RFN(nn.Module):
         eps, slot 2 the flow's base eps, slots 3.. the Split2d eps list, coarsest first (the order of _gen_eps_shapes).
         A frame therefore depends on (seed, sequence id, draw id) and the data alone: not on B, on n_draws, on how the
         draws are split into calls, or on torch's generator, which is left untouched.  Eval mode only: batch statistics
-        would couple the draws."""
+        would couple the draws.
+        temperatures / kl_temperatures (each a sequence of K numbers, or None): a sweep over K (temperature, kl
+        temperature) pairs in the same pass; None stands for K copies of self.temperature / self.kl_temperature, and
+        two lists have the same length.  With either given, predictions are [n_predictions, K, n_draws, B, C, H, W]:
+        the batch is temperature-major, then draw-major (row (k*n_draws + r)*B + b), the conditioning frames are
+        encoded once for all K*n_draws*B rows, and every place a temperature enters -- the prior samples of the
+        warm-up steps and of generation, the flow's base and Split2d samples -- takes its row's value from a device
+        vector.  The noise is tiled (keyed_normal(tiles=K)): block k uses exactly the numbers the call without
+        temperatures uses, so a block does not depend on which other temperatures are swept with it.  In this mode
+        the model's temperature / kl_temperature attributes are neither read (for the given lists) nor written."""
         true_x, predictions = self._predict_draws_device(x, n_predictions, n_conditions, n_draws, seed, first_seq,
-                                                         first_draw)
+                                                         first_draw, temperatures, kl_temperatures)
         return true_x.cpu(), predictions.cpu()
 
-    def _predict_draws_device(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+    def _temperature_lists(self, temperatures, kl_temperatures):
+        """the two lists of K floats of a per-row call (None: K copies of the model's value, the only case in which an
+        attribute is read)"""
+        lists = []
+        for v, nm in ((temperatures, "temperatures"), (kl_temperatures, "kl_temperatures")):
+            if v is None:
+                lists.append(None)
+                continue
+            if isinstance(v, (str, bytes, torch.Tensor)) or not hasattr(v, "__len__"):
+                raise TypeError("RFN.predict_draws: %s must be a sequence of numbers, got %s" % (nm, type(v).__name__))
+            v = [float(t) for t in v]
+            if not v:
+                raise ValueError("RFN.predict_draws: %s is empty" % nm)
+            lists.append(v)
+        t, kl = lists
+        if t is not None and kl is not None and len(t) != len(kl):
+            raise ValueError("RFN.predict_draws: %d temperatures and %d kl_temperatures" % (len(t), len(kl)))
+        K_ = len(t if t is not None else kl)
+        return (t if t is not None else [float(self.temperature)] * K_,
+                kl if kl is not None else [float(self.kl_temperature)] * K_)
+
+    @staticmethod
+    def _temperature_rows(values, P, B, device):
+        """float32 [K*P*B] on `device`: row rfn_hip.ops.keyed_normal_tiled_row(k, r, b, P, B) holds values[k]"""
+        return torch.tensor(values, dtype=torch.float32).repeat_interleave(P * B).to(device)
+
+    def _predict_draws_device(self, x, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0,
+                              temperatures=None, kl_temperatures=None):
         assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
         if self.training:
             raise RuntimeError("RFN.predict_draws needs eval mode: in training mode the batch statistics of the "
@@ -434,8 +495,19 @@ class RFN(nn.Module):
             raise ValueError("RFN.predict_draws: L = %d needs %d noise slots, one launch fills %d" %
                              (self.L, self.L + 2, K.KEYED_NORMAL_MAX_SLOTS))
 
-        def rep(t):   # draw-major: row r*B + b is sequence b
-            return t.repeat((P,) + (1,) * (t.dim() - 1))
+        per_row = temperatures is not None or kl_temperatures is not None
+        Kt, temp_rows, kl_temp = 1, None, None
+        if per_row:
+            t_list, kl_list = self._temperature_lists(temperatures, kl_temperatures)
+            Kt = len(t_list)
+            # temperature-major: row (k*P + r)*B + b takes entry k
+            temp_rows = tuple(self._temperature_rows(v, P, B, x.device) for v in (t_list, kl_list))
+            kl_temp = temp_rows[1].view(-1, 1, 1, 1)
+        else:
+            kl_temp = self.kl_temperature
+
+        def rep(t):   # (temperature-major, then) draw-major: row (k*P + r)*B + b is sequence b
+            return t.repeat((Kt * P,) + (1,) * (t.dim() - 1))
 
         with torch.no_grad():
             hprev, cprev, aprev, caprev, zprev, zxprev, _, _, _ = self.get_inits()
@@ -444,7 +516,8 @@ class RFN(nn.Module):
             zprev, zxprev = rep(zprev), rep(zxprev)
             zshape = tuple(zprev.shape[1:])
             for i in range(1, n_conditions):
-                eps_p, eps_q = K.keyed_normal([zshape, zshape], B, P, seed, i, first_seq, first_draw, device=x.device)
+                eps_p, eps_q = K.keyed_normal([zshape, zshape], B, P, seed, i, first_seq, first_draw, device=x.device,
+                                              tiles=Kt)
                 ht = rep(store_ht[i - 1])
                 if self.enable_smoothing:
                     enc_mean, enc_std = self.encoder(torch.cat((rep(store_at[i - 1]), zxprev), dim=1))
@@ -455,22 +528,25 @@ class RFN(nn.Module):
                     enc_mean = prior_mean + enc_mean
                 else:
                     prior_mean, prior_std = self.prior(torch.cat((ht, zprev), dim=1))
-                zprev = prior_mean + prior_std * self.kl_temperature * eps_p
+                zprev = prior_mean + prior_std * kl_temp * eps_p
                 zxprev = enc_mean + enc_std * eps_q
             true_x = x[:, :n_conditions].transpose(0, 1).detach().clone()
             frames = []
             prediction, hprev, cprev = rep(x[:, n_conditions - 1]), rep(hprev), rep(cprev)
             for i in range(n_predictions):
                 def fill(eps, t=n_conditions + i):   # slot 1 (the encoder eps) is not drawn while generating
-                    K.keyed_normal(None, B, P, seed, t, first_seq, first_draw, out=[eps[0], None] + list(eps[1:]))
-                prediction, ht, ct, zt = self._gen_step_graphed(prediction, hprev, cprev, zprev, self.kl_temperature,
-                                                                eps_fill=fill)
+                    K.keyed_normal(None, B, P, seed, t, first_seq, first_draw, out=[eps[0], None] + list(eps[1:]),
+                                   tiles=Kt)
+                prediction, ht, ct, zt = self._gen_step_graphed(prediction, hprev, cprev, zprev,
+                                                                None if per_row else kl_temp, eps_fill=fill,
+                                                                temp_rows=temp_rows)
                 frames.append(prediction.detach())
                 hprev, cprev, zprev = ht, ct, zt
+            lead = (Kt, P, B) if per_row else (P, B)
             if frames:
-                predictions = torch.stack(frames, 0).view(n_predictions, P, B, *x.shape[2:])
+                predictions = torch.stack(frames, 0).view(n_predictions, *lead, *x.shape[2:])
             else:
-                predictions = torch.zeros((0, P, B, *x.shape[2:]), device=x.device)
+                predictions = torch.zeros((0, *lead, *x.shape[2:]), device=x.device)
         return true_x, predictions
 
     def reconstruct(self, x, draws=None):

@@ -17,6 +17,12 @@
 // 16-byte aligned (then every row base is), single stores for a tail block and for unaligned slots.  The slot is
 // blockIdx.z; its pointer and length are selected from the by-value tables with compile-time indices (a run-time index
 // would put the whole struct in scratch memory).  A pure store stream: no atomics, no LDS.
+//
+// Tiled launches (rfn_keyed_normal_tiled_f32, a temperature sweep's common random numbers): the tensors hold `tiles`
+// copies of the rows*numel_j block one after the other.  A lane computes its eight values once and stores them `tiles`
+// times, numel_j * rows floats apart: the grid, the Philox blocks and the transcendental work are those of the untiled
+// launch, only the stores multiply.  (A step's launch takes ~17 us from 0.55 MB to 4.4 MB -- it is bound by launch
+// latency, not by ALU work or stores -- so recomputing would buy nothing and cost tiles x the arithmetic.)
 #include "common.h"
 #include "philox.h"
 #include "../../include/rfn_hip.h"
@@ -31,6 +37,7 @@ struct KeyedNormalParams {
     int numel[KN_MAX_SLOTS];
     unsigned vec_mask;   // bit j: slot j takes the 16-byte stores
     int rows, B;
+    int tiles;           // copies of the [rows, numel] block per tensor, >= 1
     uint64_t seed, first_seq, first_draw;
     uint32_t step;
 };
@@ -69,25 +76,31 @@ __global__ __launch_bounds__(KN_THREADS) void keyed_normal_kernel(const KeyedNor
     kn_pair(w.w2, v[4], v[5]);
     kn_pair(w.w3, v[6], v[7]);
     float* dst = base + row * (long)numel + 8 * q;
+    const long tile_step = (long)p.rows * numel;   // a multiple of 8 floats where the slot takes 16-byte stores
     if ((p.vec_mask >> j) & 1u) {   // numel % 8 == 0: no tail block
-        reinterpret_cast<float4*>(dst)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4*>(dst)[1] = make_float4(v[4], v[5], v[6], v[7]);
+        for (int k = 0; k < p.tiles; ++k, dst += tile_step) {
+            reinterpret_cast<float4*>(dst)[0] = make_float4(v[0], v[1], v[2], v[3]);
+            reinterpret_cast<float4*>(dst)[1] = make_float4(v[4], v[5], v[6], v[7]);
+        }
     } else {
         const int left = numel - (int)(8 * q);   // >= 1
+        for (int k = 0; k < p.tiles; ++k, dst += tile_step) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-            if (e < left) dst[e] = v[e];
+            for (int e = 0; e < 8; ++e)
+                if (e < left) dst[e] = v[e];
+        }
     }
 }
 
 }  // namespace
 
-extern "C" int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, long seed,
-                                    int step, long first_seq, long first_draw, rfn_stream_t stream) {
+static int keyed_normal_launch(float* const* outs, const int* numels, int n_slots, int rows, int B, int tiles,
+                               long seed, int step, long first_seq, long first_draw, rfn_stream_t stream) {
     RFN_CHECK_ARG(n_slots >= 1 && n_slots <= KN_MAX_SLOTS, -1);
     RFN_CHECK_ARG(outs && numels, -2);
     RFN_CHECK_ARG(rows >= 0 && B >= 1 && rows % B == 0, -3);
     RFN_CHECK_ARG(seed >= 0 && first_seq >= 0 && first_draw >= 0 && step >= 0, -4);
+    RFN_CHECK_ARG(tiles >= 1 && (long)tiles * rows <= 0x7fffffffL, -8);
     KeyedNormalParams p;
     memset(&p, 0, sizeof(p));
     long most = 0;
@@ -106,6 +119,7 @@ extern "C" int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n
     RFN_CHECK_ARG(blocks <= 0x7fffffffL, -7);
     p.rows = rows;
     p.B = B;
+    p.tiles = tiles;
     p.seed = (uint64_t)seed;
     p.first_seq = (uint64_t)first_seq;
     p.first_draw = (uint64_t)first_draw;
@@ -114,4 +128,15 @@ extern "C" int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n
                        (hipStream_t)stream, p);
     RFN_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, long seed,
+                                    int step, long first_seq, long first_draw, rfn_stream_t stream) {
+    return keyed_normal_launch(outs, numels, n_slots, rows, B, 1, seed, step, first_seq, first_draw, stream);
+}
+
+extern "C" int rfn_keyed_normal_tiled_f32(float* const* outs, const int* numels, int n_slots, int rows, int B,
+                                          int tiles, long seed, int step, long first_seq, long first_draw,
+                                          rfn_stream_t stream) {
+    return keyed_normal_launch(outs, numels, n_slots, rows, B, tiles, seed, step, first_seq, first_draw, stream);
 }

@@ -1476,18 +1476,22 @@ extern "C" int rfn_gauss_logp_bwd_f32(const float* z, long z_ns, const float* o,
     return 0;
 }
 
+// temperature_rows (may be null): one temperature per frame, uniform per block; null: the scalar for every frame.  One
+// kernel for both, so a vector filled with the scalar's value gives the scalar call's bits.
 __global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restrict__ o, long o_ns,
                                                            const float* __restrict__ eps, float* __restrict__ z,
-                                                           long z_ns, float temperature, int layout, int std_mode,
-                                                           int Cz, int HW) {
+                                                           long z_ns, float temperature,
+                                                           const float* __restrict__ temperature_rows, int layout,
+                                                           int std_mode, int Cz, int HW) {
     const int n = blockIdx.x;
     const float* on = o + n * o_ns;
+    const float t = temperature_rows ? temperature_rows[n] : temperature;
     for (int e = threadIdx.x; e < Cz * HW; e += 256) {
         int c = e / HW, p = e - c * HW;
         float mean, raw;
         gauss_params(on, layout, c, Cz, HW, p, mean, raw);
         float std = std_mode == 0 ? softplusf_(raw) + 1e-8f : expf(raw);
-        z[n * z_ns + e] = mean + std * temperature * eps[(long)n * Cz * HW + e];
+        z[n * z_ns + e] = mean + std * t * eps[(long)n * Cz * HW + e];
     }
 }
 extern "C" int rfn_gauss_sample_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns, float temperature,
@@ -1495,7 +1499,17 @@ extern "C" int rfn_gauss_sample_f32(const float* o, long o_ns, const float* eps,
     RFN_CHECK_ARG(o && eps && z && N >= 0 && Cz > 0 && HW > 0, -1);
     if (N == 0) return 0;
     hipLaunchKernelGGL(gauss_sample_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, o, o_ns, eps, z, z_ns,
-                       temperature, layout, std_mode, Cz, HW);
+                       temperature, (const float*)nullptr, layout, std_mode, Cz, HW);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int rfn_gauss_sample_rows_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns,
+                                         const float* temperature_rows, int layout, int std_mode, int N, int Cz,
+                                         int HW, rfn_stream_t stream) {
+    RFN_CHECK_ARG(o && eps && z && temperature_rows && N >= 0 && Cz > 0 && HW > 0, -1);
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(gauss_sample_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, o, o_ns, eps, z, z_ns, 0.0f,
+                       temperature_rows, layout, std_mode, Cz, HW);
     RFN_LAUNCH_CHECK();
     return 0;
 }

@@ -12,12 +12,74 @@ the lpips package's alex.pth; nothing is downloaded); without that setting LPIPS
 `get_fvd_values` (:1006-1063) is the Frechet Video Distance on the logits of the I3D network (Kinetics-400, RGB stream;
 the definition is pinned in rfn_hip/i3d.py), the trunk on the GPU, once `settings.fvd_weights` names local files with
 the I3D weights (a PyTorch state dict or an .npz of the TF variables; nothing is downloaded); without that setting it
-raises.  The other plots are not drawn."""
+raises.
+`get_eval_values_temperatures` is the temperature study (eval_settings.py:110-126) as one pass: best-of-N at K sampling
+temperatures from one RFN.predict_draws call per pass, the temperatures being per-row inputs of generation.
+`plot_long_t`, `plot_diversity`, `plot_random_samples` and `plot_temp` (:1220-1415) are written as PNG sheets of pixels
+like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  The other plots -- the curve figures
+`plot_eval_values` / `test_temp_values`, `param_plots`, `plot_elbo_gap`, `plot_prob_of_t` -- are not drawn."""
 import os
 import warnings
 
 import numpy as np
 import torch
+
+
+class _BestOfN(object):
+    """The best-of-N bookkeeping of one block of draws (one temperature), shared by Evaluator._get_eval_values_draws
+    and .get_eval_values_temperatures.  Per batch: start_batch(), add(scores, pred) once per draw in ascending draw id,
+    end_batch().  The rules are the reference's (error_metrics.py:500-530): the time-means are compared strictly (ties
+    keep the earlier draw), and draw 0's tensors ARE the best-so-far tensors (aliased), so that the "mean over draws"
+    averages the final best values in place of draw 0.  The best prediction of every sequence by SSIM stays on the
+    device."""
+    LOWER_IS_BETTER = {"mse": True, "psnr": False, "ssim": False, "lpips": True}
+
+    def __init__(self, names, device):
+        self.names, self.device = tuple(names), device
+        self.best_values = {k: [] for k in self.names}
+        self.mean_values = {k: [] for k in self.names}
+        self.best_preds, self.last_pred = [], None
+
+    def start_batch(self):
+        self.best, self.draws, self.best_pred = {}, {k: [] for k in self.names}, None
+
+    def add(self, scores, pred):
+        """scores: host tensor [metrics, B, n_pred] in the order of `names`; pred: uint8 [B, n_pred, C, H, W] on the
+        device"""
+        first = not self.draws[self.names[0]]
+        for m, k in enumerate(self.names):
+            v = scores[m].clone()
+            if first:
+                self.best[k] = v   # aliased with the first entry of draws[k], as in the reference
+                better = None
+            else:
+                if self.LOWER_IS_BETTER[k]:
+                    better = self.best[k].mean(-1) > v.mean(-1)
+                else:
+                    better = self.best[k].mean(-1) < v.mean(-1)
+                self.best[k][better, :] = v[better, :]
+            self.draws[k].append(v)
+            if k == "ssim":
+                if better is None:
+                    self.best_pred = pred.clone()
+                elif bool(better.any()):
+                    sel = better.to(self.device)
+                    self.best_pred[sel] = pred[sel]
+        self.last_pred = pred
+
+    def end_batch(self):
+        for k in self.names:
+            self.mean_values[k].append(torch.stack(self.draws[k]).mean(0))
+            self.best_values[k].append(self.best[k])
+        self.best_preds.append(self.best_pred)
+
+    def result(self, bpd, dkl, recon):
+        """the ten-element tuple of get_eval_values; bpd, dkl, recon: CPU tensors, one value per batch"""
+        lp = "lpips" in self.names
+        cat = lambda d, k: torch.cat(d[k])
+        return (cat(self.best_values, "mse"), cat(self.best_values, "psnr"), cat(self.best_values, "ssim"),
+                cat(self.best_values, "lpips") if lp else None, bpd, dkl, recon,
+                cat(self.mean_values, "ssim"), cat(self.mean_values, "psnr"), cat(self.mean_values, "lpips") if lp else None)
 
 
 class Evaluator(object):
@@ -337,7 +399,6 @@ class Evaluator(object):
         (the last batch's last draw), best_samples.png and worst_samples.png (the first and last of the sequences
         ordered by time-mean SSIM of their best draw, descending), settings.num_samples_to_plot sequences each
         (default 5, capped at the sequences there are), the first six predicted frames."""
-        from rfn_hip import ops
         P = int(self.draws_per_pass)
         if P < 1:
             raise ValueError("Evaluator: settings.draws_per_pass must be at least 1, got %d" % P)
@@ -349,12 +410,10 @@ class Evaluator(object):
         n_pass = -(-R // P)
         lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
         names = ("mse", "psnr", "ssim") + (("lpips",) if lpips_w is not None else ())
-        lower_is_better = {"mse": True, "psnr": False, "ssim": False, "lpips": True}
-        best_values = {k: [] for k in names}
-        mean_values = {k: [] for k in names}
+        book = _BestOfN(names, self.device)
         bpd_list, dkl_list, recon_list = [], [], []
-        best_preds, gts = [], []
-        batch_size, last_pred = None, None
+        gts = []
+        batch_size = None
         with torch.no_grad():
             self.model.eval()
             for batch_i, true_image in enumerate(loader):
@@ -366,57 +425,27 @@ class Evaluator(object):
                 B = int(image.shape[0])
                 batch_size = batch_size or B
                 gt_u8 = self.solver.preprocess(image, reverse=True)[:, start:n_frames].contiguous()
-                gt_rep = gt_u8.unsqueeze(0).expand(P, *gt_u8.shape)
                 gt_feats = None
-                best, draws, best_pred = {}, {k: [] for k in names}, None
+                book.start_batch()
                 for ps in range(n_pass):
                     _, predictions = self.model._predict_draws_device(image, n_frames - start, start, P, self.seed,
                                                                       first_seq=batch_i * batch_size, first_draw=ps * P)
                     # [n_pred, P, B, C, H, W] -> [P, B, n_pred, C, H, W]
                     pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 2, 0, 3, 4, 5).contiguous()
-                    scores = dict(zip(("mse", "psnr", "ssim"), ops.frame_quality(gt_rep, pred_u8)))
-                    if lpips_w is not None:
-                        if gt_feats is None:
-                            f = ops.lpips_alex_features(lpips_w, gt_u8)
-                            gt_feats = ops.LpipsFeatures(f.data.repeat(P, 1), (P,) + f.lead, f.H, f.W)
-                        scores["lpips"] = ops.lpips_alex_distance(lpips_w, ops.lpips_alex_features(lpips_w, pred_u8),
-                                                                  gt_feats)
-                    host = torch.stack([scores[k] for k in names]).cpu()   # [metrics, P, B, n_pred]: the pass's one copy
+                    host, gt_feats = self._score_pass(gt_u8, pred_u8, names, lpips_w, gt_feats)
                     for d in range(min(P, R - ps * P)):
-                        for m, k in enumerate(names):
-                            v = host[m, d].clone()
-                            if ps == 0 and d == 0:
-                                best[k] = v   # aliased with the first entry of draws[k], as in the reference
-                                better = None
-                            else:
-                                if lower_is_better[k]:
-                                    better = best[k].mean(-1) > v.mean(-1)
-                                else:
-                                    better = best[k].mean(-1) < v.mean(-1)
-                                best[k][better, :] = v[better, :]
-                            draws[k].append(v)
-                            if k == "ssim":
-                                if better is None:
-                                    best_pred = pred_u8[d].clone()
-                                elif bool(better.any()):
-                                    sel = better.to(self.device)
-                                    best_pred[sel] = pred_u8[d][sel]
-                        last_pred = pred_u8[d]
-                _, kl, nll = self.model.loss(imageloss, 0)
-                bpd, kl_loss, recon_loss = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:],
-                                                             t=imageloss.shape[1] - 1)
-                for k in names:
-                    mean_values[k].append(torch.stack(draws[k]).mean(0))
-                    best_values[k].append(best[k])
+                        book.add(host[:, d], pred_u8[d])
+                bpd, kl_loss, recon_loss = self._batch_loss(imageloss)
+                book.end_batch()
                 bpd_list.append(bpd)
                 dkl_list.append(kl_loss)
                 recon_list.append(recon_loss)
-                best_preds.append(best_pred)
                 gts.append(gt_u8)
                 last_gt = gt_u8
-        ssim_all = torch.cat(best_values["ssim"])
+        out = book.result(torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list))
+        ssim_all, last_pred = out[2], book.last_pred
         # best_preds_ssim of the reference: every sequence's best draw by SSIM, on the device
-        self.best_preds_ssim = torch.cat(best_preds)
+        self.best_preds_ssim = torch.cat(book.best_preds)
         if self.debug_plot:
             ns, nf = self.num_samples_to_plot, 6
             ordered = torch.argsort(ssim_all.mean(-1), descending=True).to(self.device)
@@ -426,11 +455,235 @@ class Evaluator(object):
             n = min(ns, int(preds.shape[0]))
             self.plot_samples(preds[:n, :nf], gt[:n, :nf], name="best_samples")
             self.plot_samples(preds[-n:, :nf], gt[-n:, :nf], name="worst_samples")
-        return (torch.cat(best_values["mse"]), torch.cat(best_values["psnr"]), ssim_all,
-                torch.cat(best_values["lpips"]) if lpips_w is not None else None,
-                torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
-                torch.cat(mean_values["ssim"]), torch.cat(mean_values["psnr"]),
-                torch.cat(mean_values["lpips"]) if lpips_w is not None else None)
+        return out
+
+    def _score_pass(self, gt_u8, pred_u8, names, lpips_w, gt_feats):
+        """the scores of one generation pass: gt_u8 uint8 [B, n_pred, C, H, W], pred_u8 uint8 [M, B, n_pred, C, H, W]
+        (M draws, or temperatures x draws) -> (host tensor [metrics, M, B, n_pred] in the order of `names`, the ground
+        truth's LPIPS features repeated M times, for the batch's next pass).  One frame_quality launch, with lpips_w
+        one trunk pass over the predicted frames, one device-to-host copy."""
+        from rfn_hip import ops
+        M = int(pred_u8.shape[0])
+        gt_rep = gt_u8.unsqueeze(0).expand(M, *gt_u8.shape)
+        scores = dict(zip(("mse", "psnr", "ssim"), ops.frame_quality(gt_rep, pred_u8)))
+        if lpips_w is not None:
+            if gt_feats is None:
+                f = ops.lpips_alex_features(lpips_w, gt_u8)
+                gt_feats = ops.LpipsFeatures(f.data.repeat(M, 1), (M,) + f.lead, f.H, f.W)
+            scores["lpips"] = ops.lpips_alex_distance(lpips_w, ops.lpips_alex_features(lpips_w, pred_u8), gt_feats)
+        return torch.stack([scores[k] for k in names]).cpu(), gt_feats   # the pass's one copy
+
+    def _batch_loss(self, imageloss):
+        """(bits/dim, kl / t, nll / t) of one model.loss evaluation of a batch"""
+        _, kl, nll = self.model.loss(imageloss, 0)
+        return self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:], t=imageloss.shape[1] - 1)
+
+    def get_eval_values_temperatures(self, temperatures, model_name="rfn.pt", loader=None, max_batches=None):
+        """The temperature study (eval_settings.py:110-126: get_eval_values once per value of --temperatures) as one
+        pass over the test set: returns {T: tuple}, each tuple the ten-element tuple of get_eval_values computed for
+        that sampling temperature (the kl temperature is the model's, as in the reference's loop).  Needs
+        settings.draws_per_pass; with K temperatures a pass generates P = max(1, draws_per_pass // K) draws of the B
+        sequences at all K temperatures as K*P*B rows of one RFN._predict_draws_device call (about draws_per_pass * B
+        rows, the memory of that setting), ceil(resample / P) passes per batch.  The conditioning frames are encoded
+        once per pass, the temperatures are per-row inputs of generation (one hipGraph whatever the values) and all K
+        blocks use the same addressed noise, draw r of sequence batch_i * B + b under settings.seed: the figures for
+        one temperature do not depend on which other temperatures are swept with it, nor on P.  Per pass one
+        frame_quality launch scores the K*P*B sequences (with lpips_weights: one trunk pass) and the scores come to
+        the host in one copy.  Per temperature the rules are those of _get_eval_values_draws (the same bookkeeping
+        code): ascending draw id, strict comparisons of time-means, the draw-0 aliasing, draws >= resample of a padded
+        last pass ignored.  model.loss runs once per batch: BPD / DKL / RECON do not depend on the sampling temperature
+        and the K tuples share them.  self.best_preds_ssim becomes a dict {T: uint8 tensor on the device} in this call
+        only.  The debug_plot sheets are not written here (they would overwrite one another per temperature)."""
+        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        temps = [float(t) for t in temperatures]
+        if not temps or len(set(temps)) != len(temps):
+            raise ValueError("Evaluator.get_eval_values_temperatures: need at least one temperature and no duplicates, "
+                             "got %s" % (temps,))
+        if self.draws_per_pass is None:
+            raise ValueError("Evaluator.get_eval_values_temperatures needs settings.draws_per_pass (without it, call "
+                             "get_eval_values once per temperature)")
+        K = len(temps)
+        P = self.draws_per_temperature(self.draws_per_pass, K)
+        if self.extra_plots and not self._warned_plots:
+            warnings.warn("Evaluator.get_eval_values: extra_plots only draws figures; skipped")
+            self._warned_plots = True
+        loader = loader if loader is not None else self.test_loader
+        start, n_frames, R = self.start_predictions, self.n_frames, self.resample
+        n_pass = -(-R // P)
+        lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
+        names = ("mse", "psnr", "ssim") + (("lpips",) if lpips_w is not None else ())
+        books = [_BestOfN(names, self.device) for _ in temps]
+        bpd_list, dkl_list, recon_list = [], [], []
+        batch_size = None
+        with torch.no_grad():
+            self.model.eval()
+            for batch_i, true_image in enumerate(loader):
+                if max_batches is not None and batch_i >= max_batches:
+                    break
+                image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
+                image = self.solver.preprocess(image.to(self.device))
+                imageloss = image[:, :self.n_trained] if self.n_trained else image
+                B = int(image.shape[0])
+                batch_size = batch_size or B
+                gt_u8 = self.solver.preprocess(image, reverse=True)[:, start:n_frames].contiguous()
+                gt_feats = None
+                for book in books:
+                    book.start_batch()
+                for ps in range(n_pass):
+                    _, predictions = self.model._predict_draws_device(image, n_frames - start, start, P, self.seed,
+                                                                      first_seq=batch_i * batch_size, first_draw=ps * P,
+                                                                      temperatures=temps)
+                    # [n_pred, K, P, B, C, H, W] -> [K*P, B, n_pred, C, H, W]
+                    pred_u8 = self.solver.preprocess(predictions, reverse=True)
+                    pred_u8 = pred_u8.reshape(pred_u8.shape[0], K * P, *pred_u8.shape[3:]).permute(1, 2, 0, 3, 4, 5)
+                    pred_u8 = pred_u8.contiguous()
+                    host, gt_feats = self._score_pass(gt_u8, pred_u8, names, lpips_w, gt_feats)
+                    for k, book in enumerate(books):
+                        for d in range(min(P, R - ps * P)):
+                            book.add(host[:, k * P + d], pred_u8[k * P + d])
+                bpd, kl_loss, recon_loss = self._batch_loss(imageloss)
+                for book in books:
+                    book.end_batch()
+                bpd_list.append(bpd)
+                dkl_list.append(kl_loss)
+                recon_list.append(recon_loss)
+        shared = (torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list))
+        self.best_preds_ssim = {t: torch.cat(book.best_preds) for t, book in zip(temps, books)}
+        return {t: book.result(*shared) for t, book in zip(temps, books)}
+
+    @staticmethod
+    def draws_per_temperature(draws_per_pass, n_temperatures):
+        """P = max(1, draws_per_pass // K): the draws per pass of a sweep over K temperatures, so that a pass holds about
+        draws_per_pass * B rows"""
+        draws_per_pass, n_temperatures = int(draws_per_pass), int(n_temperatures)
+        if draws_per_pass < 1 or n_temperatures < 1:
+            raise ValueError("Evaluator: need draws_per_pass >= 1 and at least one temperature (got %d, %d)" %
+                             (draws_per_pass, n_temperatures))
+        return max(1, draws_per_pass // n_temperatures)
+
+    # ---- the four RFN-only figures of eval_settings.py (error_metrics.py:1220-1415) as sheets of pixels
+    def _sheet_batch(self):
+        """the first test batch in model space on the device; torch's generators are restored by the caller"""
+        image = next(iter(self.test_loader))
+        image = image[0] if self.choose_data == "bair" and isinstance(image, (list, tuple)) else image
+        return self.solver.preprocess(image.to(self.device))
+
+    def _write_sheet(self, rows, n_cols, name):
+        from rfn_hip import ops
+        from Utils.png import write_png
+        sheet = ops.compose_sheet(rows, n_cols, n_bits=int(getattr(self.solver, "n_bits", 8)),
+                                  preprocess_range=getattr(self.solver, "preprocess_range", "0.5"), scanlines=True)
+        folder = self.solver.path + "eval_folder"
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, name + ".png")
+        write_png(path, sheet)
+        return path
+
+    def _sheet(self, model_name, draw):
+        """run `draw(image)` -> [(rows, n_cols, name), ...] on the first test batch in eval mode and write the sheets;
+        torch's CPU and GPU generator states and model.training are what they were afterwards (the loader may shuffle
+        with torch's generator; the frames themselves are drawn with addressed noise under settings.seed)"""
+        if model_name != "rfn.pt":
+            raise ValueError("Evaluator: the sheets need an RFN model (rfn.pt), got %s" % model_name)
+        was_training = self.model.training
+        on_gpu = self.device.type == "cuda"
+        cpu_rng = torch.get_rng_state()
+        gpu_rng = torch.cuda.get_rng_state(self.device) if on_gpu else None
+        try:
+            with torch.no_grad():
+                self.model.eval()
+                paths = [self._write_sheet(*sheet) for sheet in draw(self._sheet_batch())]
+        finally:
+            self.model.train(was_training)
+            torch.set_rng_state(cpu_rng)
+            if on_gpu:
+                torch.cuda.set_rng_state(gpu_rng, self.device)
+        return paths
+
+    def _rollout_sheet(self, model_name, name, n_predictions, n_conditions, t_list, n_sequences):
+        t_list = [int(t) for t in t_list]
+        if not t_list or min(t_list) < 0 or max(t_list) >= n_conditions + n_predictions:
+            raise ValueError("Evaluator.%s: t_list %s outside the %d frames of cat(conditions, predictions)" %
+                             (name, t_list, n_conditions + n_predictions))
+
+        def draw(image):
+            conditions, predictions = self.model._predict_draws_device(image, n_predictions, n_conditions, 1, self.seed)
+            t_seq = torch.cat((conditions, predictions[:, 0]), 0)           # [T, B, C, H, W]
+            n = min(int(n_sequences), int(image.shape[0]))
+            return [([t_seq[t_list, k] for k in range(n)], len(t_list), name)]
+        return self._sheet(model_name, draw)[0]
+
+    def plot_long_t(self, model_name="rfn.pt", n_predictions=80, n_conditions=5, t_list=(3, 4, 9, 19, 39, 59, 69),
+                    n_sequences=4):
+        """error_metrics.py:1220-1258 as pixels: `eval_folder/plot_long_t.png`, one row per sequence (the first
+        n_sequences of the first test batch, capped at the batch), the columns being frames t_list of
+        cat(conditions, predictions) of one rollout of n_predictions frames after n_conditions given ones, at the
+        model's temperatures.  No titles and no red / green cell borders.  The noise is addressed noise under
+        settings.seed (draw 0); torch's generators and the model's attributes are left as they were.  Returns the
+        path."""
+        return self._rollout_sheet(model_name, "plot_long_t", n_predictions, n_conditions, t_list, n_sequences)
+
+    def plot_random_samples(self, model_name="rfn.pt", n_predictions=10, n_conditions=3, t_list=(1, 2, 3, 4, 5, 6, 7),
+                            n_sequences=5):
+        """error_metrics.py:1378-1415 as pixels: `eval_folder/plot_rollouts.png`, the layout of plot_long_t.  Returns
+        the path."""
+        return self._rollout_sheet(model_name, "plot_rollouts", n_predictions, n_conditions, t_list, n_sequences)
+
+    def plot_diversity(self, model_name="rfn.pt", n_resamples=3, n_predictions=25, n_conditions=5, t_list=(3, 7, 12, 20)):
+        """error_metrics.py:1328-1376 as pixels: `eval_folder/plot_diversity_1.png` (sequence 1 of the first test batch)
+        and `plot_diversity_2.png` (sequence 0), one row per draw, the columns being predicted frames t_list.  All
+        n_resamples draws come from one RFN.predict_draws call (addressed noise under settings.seed, draws
+        0 .. n_resamples - 1).  Returns the two paths."""
+        t_list = [int(t) for t in t_list]
+        if not t_list or min(t_list) < 0 or max(t_list) >= n_predictions:
+            raise ValueError("Evaluator.plot_diversity: t_list %s outside the %d predicted frames" % (t_list, n_predictions))
+
+        def draw(image):
+            if int(image.shape[0]) < 2:
+                raise ValueError("Evaluator.plot_diversity shows sequences 0 and 1; the batch holds %d" % image.shape[0])
+            _, predictions = self.model._predict_draws_device(image, n_predictions, n_conditions, int(n_resamples),
+                                                              self.seed)                 # [n_pred, R, B, C, H, W]
+            return [([predictions[t_list, r, seq] for r in range(int(n_resamples))], len(t_list), name)
+                    for name, seq in (("plot_diversity_1", 1), ("plot_diversity_2", 0))]
+        return tuple(self._sheet(model_name, draw))
+
+    def plot_temp(self, model_name="rfn.pt", orig_temps=None, kl_analysis=False, duplicate_samples=False,
+                  t_list=(0, 1, 2, 9, 19, 39), temperatures=(0.001, 0.3, 0.5, 0.7, 1, 2), n_conditions=5):
+        """error_metrics.py:1260-1325 as pixels: one row per temperature, showing sequence 0 of the first test batch,
+        written to `eval_folder/plot_temp_samples.png`, `plot_temp_samples_kl.png` (kl_analysis),
+        `plot_temp_samples_dup.png` (duplicate_samples) or `plot_temp_dup_kl.png` (both).  The swept temperature is the
+        flow's sampling temperature, with kl_analysis the prior's (kl) temperature; the other one is 1e-9 in every row.
+        Without duplicate_samples the rows are one rollout of max(t_list) + 1 predicted frames (the reference always
+        rolls 50) and column i shows frame t_list[i]; with it, column i shows frame t_list[i] of draw i of a 5-frame
+        rollout, so t_list = [0] * 8 is eight independent first frames.  Either way all rows come from ONE
+        RFN.predict_draws call with len(temperatures) per-row temperatures, and all rows share their noise (addressed
+        noise under settings.seed): a row is the same draw as the row above it at another temperature, which is the
+        comparison the figure is for (the reference draws every row afresh).  orig_temps (the reference restores the
+        model's attributes from it) is accepted and ignored: the attributes are never changed.  Returns the path."""
+        t_list = [int(t) for t in t_list]
+        swept = [float(t) for t in temperatures]
+        if not swept:
+            raise ValueError("Evaluator.plot_temp: no temperatures")
+        n_pred = 5 if duplicate_samples else (max(t_list) + 1 if t_list else 0)
+        if not t_list or min(t_list) < 0 or max(t_list) >= n_pred:
+            raise ValueError("Evaluator.plot_temp: t_list %s outside the %d predicted frames" % (t_list, n_pred))
+        name = {(False, False): "plot_temp_samples", (True, False): "plot_temp_samples_kl",
+                (False, True): "plot_temp_samples_dup", (True, True): "plot_temp_dup_kl"}[(bool(kl_analysis),
+                                                                                          bool(duplicate_samples))]
+        other = [1e-9] * len(swept)
+        kw = dict(temperatures=other, kl_temperatures=swept) if kl_analysis else dict(temperatures=swept,
+                                                                                      kl_temperatures=other)
+
+        def draw(image):
+            n_draws = len(t_list) if duplicate_samples else 1
+            _, preds = self.model._predict_draws_device(image, n_pred, n_conditions, n_draws, self.seed, **kw)
+            # [n_pred, K, n_draws, B, C, H, W]
+            if duplicate_samples:
+                rows = [torch.stack([preds[t, k, i, 0] for i, t in enumerate(t_list)]) for k in range(len(swept))]
+            else:
+                rows = [preds[t_list, k, 0, 0] for k in range(len(swept))]
+            return [(rows, len(t_list), name)]
+        return self._sheet(model_name, draw)[0]
 
     # ---- the analyses the reference's evaluator drives (error_metrics.py: plot_elbo_gap, plot_prob_of_t, param_plots)
     def elbo_gap(self, image, sample=False):

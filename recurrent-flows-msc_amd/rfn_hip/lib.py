@@ -105,6 +105,7 @@ SIGNATURES = {
     "rfn_gauss_logp_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i,
                                _c_s],
     "rfn_gauss_sample_f32": [_c_f, _c_l, _c_f, _c_f, _c_l, ctypes.c_float, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_gauss_sample_rows_f32": [_c_f, _c_l, _c_f, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_latent_step_fwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_s],
     "rfn_latent_step_bwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i,
                                 _c_s],
@@ -147,6 +148,7 @@ SIGNATURES = {
     "rfn_moving_mnist_render_f32": [ctypes.c_void_p, _c_i, _c_f, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
                                     _c_l, _c_l, _c_l, _c_s],
     "rfn_keyed_normal_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_l, _c_i, _c_l, _c_l, _c_s],
+    "rfn_keyed_normal_tiled_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_l, _c_i, _c_l, _c_l, _c_s],
     "rfn_clip_gather_u8_f32": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_sheet_max_rows": [],
     "rfn_sheet_compose_u8": [ctypes.c_void_p] + [_c_i] * 10 + [_c_l, _c_s],

@@ -763,13 +763,31 @@ def gauss_logp(z, o, layout, std_mode):
 
 
 def gauss_sample(o, eps, layout, std_mode, temperature):
+    """z = mean + std * temperature * eps (rfn_gauss_sample_f32).  temperature: a number, or a float32 device tensor of N
+    elements, one temperature per frame (rfn_gauss_sample_rows_f32: the same kernel, so rows holding a number's value
+    give that number's bits)."""
     N, C2 = o.shape[0], o.shape[1]
     Cz = C2 // 2
+    if isinstance(temperature, torch.Tensor):
+        if temperature.dtype != torch.float32:
+            raise TypeError("gauss_sample: a temperature tensor must be float32, got %s" % temperature.dtype)
+        if temperature.device != o.device:
+            raise ValueError("gauss_sample: temperature is on %s, o on %s" % (temperature.device, o.device))
+        if temperature.numel() != N:
+            raise ValueError("gauss_sample: temperature holds %d values for %d frames" % (temperature.numel(), N))
+        temperature = temperature.contiguous()
+    elif isinstance(temperature, bool) or not isinstance(temperature, (int, float)):
+        raise TypeError("gauss_sample: temperature must be a number or a float32 tensor, got %s" %
+                        type(temperature).__name__)
     z = torch.empty((N, Cz) + tuple(o.shape[2:]), device=o.device, dtype=torch.float32)
     op, ons = L.frames(o, "o")
     zp, zns = L.frames(z, "z")
-    L.call("rfn_gauss_sample_f32", op, _l(ons), L.dev(eps.contiguous(), "eps"), zp, _l(zns),
-           ctypes.c_float(float(temperature)), _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(o)))
+    if isinstance(temperature, torch.Tensor):
+        L.call("rfn_gauss_sample_rows_f32", op, _l(ons), L.dev(eps.contiguous(), "eps"), zp, _l(zns),
+               L.dev(temperature, "temperature"), _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(o)))
+    else:
+        L.call("rfn_gauss_sample_f32", op, _l(ons), L.dev(eps.contiguous(), "eps"), zp, _l(zns),
+               ctypes.c_float(float(temperature)), _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(o)))
     return z
 
 
@@ -1929,15 +1947,29 @@ def clip_gather(store, first, T, C):
 KEYED_NORMAL_MAX_SLOTS = 8
 
 
-def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=None, device=None):
+def keyed_normal_tiled_row(k, r, b, n_draws, B):
+    """the row of tile k, draw r (local to the call), sequence b (local to the batch) in a tensor of keyed_normal(...,
+    tiles=K): tile-major, then draw-major.  It holds what row r*B + b holds with tiles = 1.  The batch of a
+    temperature sweep (RFN.predict_draws(temperatures=...)) has the same layout, k being the temperature."""
+    return (k * n_draws + r) * B + b
+
+
+def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=None, device=None, tiles=1):
     """Addressed N(0,1) noise (rfn_keyed_normal_f32; include/rfn_hip.h and DESIGN section 16 hold the definition): a list
     of float32 tensors [n_draws*B, *shape_j], slot j being the list position (at most 8).  Row r*B + b of every tensor
     stands for draw first_draw + r of sequence first_seq + b, and a value depends only on (seed, step, slot, sequence,
     draw, position in the row): the same on any grid, for any B, n_draws and split of the draws into calls.  An entry
     None of `shapes` skips that slot (None in the result).  out: tensors to fill in place instead of fresh ones (None
     where the slot is skipped), each contiguous float32 of n_draws*B rows on one device; with out, `shapes` may be None.
-    device: where fresh tensors go (default: the current GPU).  One launch on the current stream; no CPU fallback."""
+    device: where fresh tensors go (default: the current GPU).  One launch on the current stream; no CPU fallback.
+    tiles = K > 1 (rfn_keyed_normal_tiled_f32): every tensor has K*n_draws*B rows and row (k*n_draws + r)*B + b holds
+    exactly what row r*B + b holds with tiles = 1, for every k (the blocks of a temperature sweep share their noise);
+    still one launch.  tiles = 1 is the untiled entry point."""
     B, n_draws, seed, step, first_seq, first_draw = (int(v) for v in (B, n_draws, seed, step, first_seq, first_draw))
+    if isinstance(tiles, bool) or not isinstance(tiles, int):
+        raise TypeError("keyed_normal: tiles must be an int, got %s" % type(tiles).__name__)
+    if tiles < 1:
+        raise ValueError("keyed_normal: tiles must be at least 1, got %d" % tiles)
     if B < 1 or n_draws < 0:
         raise ValueError("keyed_normal: need B >= 1 and n_draws >= 0 (got %d, %d)" % (B, n_draws))
     for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
@@ -1945,7 +1977,8 @@ def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=
             raise ValueError("keyed_normal: %s %d not in [0, 2^63)" % (nm, v))
     if not 0 <= step < 1 << 31:
         raise ValueError("keyed_normal: step %d not in [0, 2^31)" % step)
-    rows = n_draws * B
+    tile_rows = n_draws * B          # the rows that are computed; every tensor holds them `tiles` times
+    rows = tiles * tile_rows
     if rows > 0x7fffffff:
         raise ValueError("keyed_normal: %d rows exceed one launch" % rows)
     if out is None:
@@ -1994,9 +2027,15 @@ def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=
         total += t.numel()
     if total:
         with torch.cuda.device(live[0].device):
-            L.call("rfn_keyed_normal_f32", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(numels, ctypes.c_void_p),
-                   _i(len(out)), _i(rows), _i(B), _l(seed), _i(step), _l(first_seq), _l(first_draw),
-                   meta=("shell", "keyed_normal", 0.0, "%dx%d" % (rows, total // rows), 4.0 * total))
+            if tiles == 1:
+                L.call("rfn_keyed_normal_f32", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(numels, ctypes.c_void_p),
+                       _i(len(out)), _i(rows), _i(B), _l(seed), _i(step), _l(first_seq), _l(first_draw),
+                       meta=("shell", "keyed_normal", 0.0, "%dx%d" % (rows, total // rows), 4.0 * total))
+            else:
+                L.call("rfn_keyed_normal_tiled_f32", ctypes.cast(ptrs, ctypes.c_void_p),
+                       ctypes.cast(numels, ctypes.c_void_p), _i(len(out)), _i(tile_rows), _i(B), _i(tiles), _l(seed),
+                       _i(step), _l(first_seq), _l(first_draw),
+                       meta=("shell", "keyed_normal", 0.0, "%dx%dx%d" % (tiles, tile_rows, total // rows), 4.0 * total))
     return out
 
 
