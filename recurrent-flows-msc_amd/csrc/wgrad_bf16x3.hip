@@ -1,13 +1,15 @@
 // Weight gradients as one split-precision GEMM:  gw[m][n] += Σ_{frames, pixels} A[f][m][p] * B[f][n][p].
 //
-// Every weight gradient of the path is brought to this 1x1 form by expanding the SMALL operand in HBM:
-//   * 1x1 conv:                 A = grad [M = Cout],       B = input [N = Cin]
-//   * 3x3 conv, Cin <= Cout:    A = grad,                  B = im2col3x3(input) [N = 9*Cin]   (rfn_im2col3x3_f32)
-//   * 3x3 conv, Cout <  Cin:    A = tap_scatter(grad) [M = 9*Cout] (rfn_tap_scatter_f32),     B = input
-// (the two 3x3 forms on maps whose rows are a multiple of 8 pixels skip the expansion: the implicit kernels build the
-// shifted planes of the small operand while staging -- the input's for Cin <= Cout, the gradient's, taps mirrored and
-// roles swapped, for the few-output conv behind rfn_conv3x3_wgrad_mirrored_bf16x3)
-// so the shifted-window reads of a 3x3 weight gradient never reach this kernel and the 8 consecutive k (pixels) an
+// Every split-precision weight gradient is brought to this 1x1 form; rfn_hip.ops.wgrad_plan names the forms:
+//   * gemm      1x1 conv:               A = grad [M = Cout],       B = input [N = Cin]
+//   * im2col    3x3 conv, Cin <= Cout:  A = grad,                  B = im2col3x3(input) [N = 9*Cin]   (rfn_im2col3x3_f32)
+//   * scatter   3x3 conv, Cout <  Cin:  A = tap_scatter(grad) [M = 9*Cout] (rfn_tap_scatter_f32),     B = input
+//   * implicit  3x3, Cin <= Cout, rows of a multiple of 8 pixels: no expansion in HBM, the kernel builds the shifted
+//               planes of the input while staging (rfn_conv3x3_wgrad_implicit_bf16x3)
+//   * mirrored  the same for the few-output conv, Cout < Cin: the gradient's planes, taps mirrored and roles swapped
+//               (rfn_conv3x3_wgrad_mirrored_bf16x3)
+// (its other two forms, f32 and scatter_f32, are the fp32 kernel of conv.hip).  The first three expand the SMALL operand
+// in HBM, so the shifted-window reads of a 3x3 weight gradient never reach their kernel and the 8 consecutive k (pixels) an
 // MFMA operand lane needs are 8 consecutive fp32 of one channel plane in NCHW: staged with 16-byte loads, split into
 // bf16 hi/lo (see conv_bf16x3.hip) and stored as [row][k-group] 16-byte units with an odd row stride, so both fragment
 // reads are conflict-free ds_read_b128.  K (all pixels of all frames) is split over gridDim.x; a workgroup sweeps its
@@ -1030,6 +1032,20 @@ static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s
     }
 }
 
+// The parameter block of every entry point below: wgrad_shape plus the operands of the max(G, 1) gradients, as the group
+// tables and their group-0 mirrors p.a / p.b / p.b2 / p.gw -- which are all a kernel reads when G == 0 (the single forms
+// pass the address of their one pointer).  b2: second source of an implicit B operand; nullptr = b (the GEMM kernels
+// never read it).  The implicit forms add b2_ns, C1, C2, H, W and `mirror` themselves.
+static GemmWgradParams wgrad_params(int G, const float* const* a, long a_ns, int M, const float* const* b, long b_ns,
+                                    const float* const* b2, int Nc, float* const* gw, int F, int HW) {
+    GemmWgradParams p = wgrad_shape(M, Nc, a_ns, b_ns, G, F, HW);
+    for (int g = 0; g < (G > 0 ? G : 1); ++g) {
+        p.ga[g] = a[g]; p.gb[g] = b[g]; p.gb2[g] = b2 ? b2[g] : b[g]; p.ggw[g] = gw[g];
+    }
+    p.a = p.ga[0]; p.b = p.gb[0]; p.b2 = p.gb2[0]; p.gw = p.ggw[0];
+    return p;
+}
+
 extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw,
                                      int F, int HW, rfn_stream_t stream) {
     RFN_CHECK_ARG(a && b && gw && M > 0 && Nc > 0 && F >= 0 && HW > 0, -1);
@@ -1037,10 +1053,7 @@ extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const flo
     RFN_CHECK_ARG((((uintptr_t)a | (uintptr_t)b) & 15) == 0, -3);
     RFN_CHECK_ARG((long)F * HW < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.a = a; p.b = b; p.a_ns = a_ns; p.b_ns = b_ns; p.M = M; p.N = Nc; p.gw = gw; p.F = F; p.HW = HW;
-    p.total = (long)F * HW;
+    GemmWgradParams p = wgrad_params(0, &a, a_ns, M, &b, b_ns, nullptr, Nc, &gw, F, HW);
     launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
@@ -1053,15 +1066,9 @@ extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, i
     RFN_CHECK_ARG(HW % 4 == 0 && a_ns % 4 == 0 && b_ns % 4 == 0, -2);
     RFN_CHECK_ARG((long)F * HW < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < G; ++g)
         RFN_CHECK_ARG(a[g] && b[g] && gw[g] && (((uintptr_t)a[g] | (uintptr_t)b[g]) & 15) == 0, -3);
-        p.ga[g] = a[g]; p.gb[g] = b[g]; p.gb2[g] = b[g]; p.ggw[g] = gw[g];
-    }
-    p.G = G; p.a = a[0]; p.b = b[0]; p.gw = gw[0];
-    p.a_ns = a_ns; p.b_ns = b_ns; p.M = M; p.N = Nc; p.F = F; p.HW = HW;
-    p.total = (long)F * HW;
+    GemmWgradParams p = wgrad_params(G, a, a_ns, M, b, b_ns, nullptr, Nc, gw, F, HW);
     launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
@@ -1078,11 +1085,8 @@ extern "C" int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int 
     RFN_CHECK_ARG((((uintptr_t)g | (uintptr_t)in1 | (uintptr_t)(C2 ? in2 : in1)) & 15) == 0, -3);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.a = g; p.a_ns = g_ns; p.M = Cout; p.b = in1; p.b_ns = in1_ns; p.b2 = C2 ? in2 : in1; p.b2_ns = C2 ? in2_ns : in1_ns;
-    p.C1 = C1; p.C2 = C2; p.H = H; p.W = W; p.N = 9 * (C1 + C2); p.gw = gw; p.F = F; p.HW = H * W;
-    p.total = (long)F * H * W;
+    GemmWgradParams p = wgrad_params(0, &g, g_ns, Cout, &in1, in1_ns, C2 ? &in2 : nullptr, 9 * (C1 + C2), &gw, F, H * W);
+    p.b2_ns = C2 ? in2_ns : in1_ns; p.C1 = C1; p.C2 = C2; p.H = H; p.W = W;
     launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
@@ -1097,17 +1101,12 @@ extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, 
     RFN_CHECK_ARG(H > 0 && W > 0 && W % 8 == 0 && g_ns % 4 == 0 && in1_ns % 4 == 0 && (C2 == 0 || in2_ns % 4 == 0), -2);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
     for (int i = 0; i < G; ++i) {
         RFN_CHECK_ARG(g[i] && in1[i] && gw[i] && (C2 == 0 || in2[i]), -3);
         RFN_CHECK_ARG((((uintptr_t)g[i] | (uintptr_t)in1[i] | (uintptr_t)(C2 ? in2[i] : in1[i])) & 15) == 0, -3);
-        p.ga[i] = g[i]; p.gb[i] = in1[i]; p.gb2[i] = C2 ? in2[i] : in1[i]; p.ggw[i] = gw[i];
     }
-    p.G = G; p.a = g[0]; p.b = in1[0]; p.b2 = p.gb2[0]; p.gw = gw[0];
-    p.a_ns = g_ns; p.M = Cout; p.b_ns = in1_ns; p.b2_ns = C2 ? in2_ns : in1_ns;
-    p.C1 = C1; p.C2 = C2; p.H = H; p.W = W; p.N = 9 * (C1 + C2); p.F = F; p.HW = H * W;
-    p.total = (long)F * H * W;
+    GemmWgradParams p = wgrad_params(G, g, g_ns, Cout, in1, in1_ns, C2 ? in2 : nullptr, 9 * (C1 + C2), gw, F, H * W);
+    p.b2_ns = C2 ? in2_ns : in1_ns; p.C1 = C1; p.C2 = C2; p.H = H; p.W = W;
     launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
@@ -1124,11 +1123,8 @@ extern "C" int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int 
     RFN_CHECK_ARG((((uintptr_t)h | (uintptr_t)g) & 15) == 0, -3);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
-    p.a = h; p.a_ns = h_ns; p.M = Cin; p.b = g; p.b_ns = g_ns; p.b2 = g; p.b2_ns = g_ns;
-    p.C1 = C; p.C2 = 0; p.H = H; p.W = W; p.N = 9 * C; p.gw = gwT; p.F = F; p.HW = H * W; p.mirror = 1;
-    p.total = (long)F * H * W;
+    GemmWgradParams p = wgrad_params(0, &h, h_ns, Cin, &g, g_ns, nullptr, 9 * C, &gwT, F, H * W);
+    p.b2_ns = g_ns; p.C1 = C; p.H = H; p.W = W; p.mirror = 1;
     WgradB3Route r;
     RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
     launch_wgrad_route(p, r, (hipStream_t)stream);
@@ -1144,17 +1140,12 @@ extern "C" int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, 
     RFN_CHECK_ARG(H > 0 && W > 0 && W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p;
-    memset(&p, 0, sizeof(p));
     for (int i = 0; i < G; ++i) {
         RFN_CHECK_ARG(h[i] && g[i] && gwT[i], -3);
         RFN_CHECK_ARG((((uintptr_t)h[i] | (uintptr_t)g[i]) & 15) == 0, -3);
-        p.ga[i] = h[i]; p.gb[i] = g[i]; p.gb2[i] = g[i]; p.ggw[i] = gwT[i];
     }
-    p.G = G; p.a = h[0]; p.b = g[0]; p.b2 = g[0]; p.gw = gwT[0];
-    p.a_ns = h_ns; p.M = Cin; p.b_ns = g_ns; p.b2_ns = g_ns;
-    p.C1 = C; p.C2 = 0; p.H = H; p.W = W; p.N = 9 * C; p.F = F; p.HW = H * W; p.mirror = 1;
-    p.total = (long)F * H * W;
+    GemmWgradParams p = wgrad_params(G, h, h_ns, Cin, g, g_ns, nullptr, 9 * C, gwT, F, H * W);
+    p.b2_ns = g_ns; p.C1 = C; p.H = H; p.W = W; p.mirror = 1;
     WgradB3Route r;
     RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
     launch_wgrad_route(p, r, (hipStream_t)stream);

@@ -426,69 +426,59 @@ def conv2d_raw(in1, in2, wpk, Cout, ks, ep_mode=0, p0=None, p1=None, act=0, out1
     return out1
 
 
-def gemm_wgrad(a, b, M, Nc, arena=None):
-    """gw[M][Nc] = Σ_{frames,pixels} a[f,m,p] b[f,n,p] on the split-precision MFMA GEMM (rfn_gemm_wgrad_bf16x3)."""
-    F_, HW = int(a.shape[0]), _hw(a)
-    ap, ans = L.frames(a, "a")
-    bp, bns = L.frames(b, "b")
-    gw = _zeros(arena, M, Nc, device=a.device)
-    L.call("rfn_gemm_wgrad_bf16x3", ap, _l(ans), _i(M), bp, _l(bns), _i(Nc), L.dev(gw), _i(F_), _i(HW),
-           meta=("wgrad", kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, ans, bns, 0, F_, HW),
-                 2.0 * F_ * HW * M * Nc, "F%d %dx%d HW%d" % (F_, M, Nc, HW), 4.0 * (F_ * HW * (M + Nc) + M * Nc)))
+def wgrad_b3(H, W):
+    """weight gradients on an H x W map run split precision: the gradient arithmetic, and whole 4-pixel groups for the
+    GEMM forms (wgrad_plan; coupling_route defers a level's gradients to grouped launches only then)"""
+    return bwd_b3() and H * W % 4 == 0
+
+
+def _frame_stride(t):   # (as L.frames, layout unchecked)
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]) * _hw(t)
+
+
+def _b3_launch(G, entry, *args):
+    """(entry point, label) of a split-precision weight-gradient launch for G groups (0: the single form `entry`; else its
+    _grouped form and the 'grouped' decoration): the label is the library's answer to `entry`'s query for `args`"""
+    label = kernel_label(entry.replace("_bf16x3", "_kernel_label_bf16x3"), *args)
+    return (entry.replace("_bf16x3", "_grouped_bf16x3"), label.replace("<", "<grouped ")) if G else (entry, label)
+
+
+def _b3_wgrad(launch, G, operands, M, Nc, dims, arena, tag=""):
+    """ONE launch of a GEMM-form entry point, `launch` = (entry point, label), single (G = 0) or grouped: returns the zeroed
+    and accumulated gw [max(G, 1), M, Nc].  operands: (the groups' tensors or None, name, channels) in the entry point's
+    order, each passed as pointer (G: host array of the groups' pointers), frame stride (the first tensor's, whose layout
+    is checked), channels; dims: its last arguments, (frames, pixels) or (frames, H, W).  `tag` names a 3x3 form, whose
+    Nc = 9 x channels columns are planes shifted while staging."""
+    args = []
+    for ts, name, C in operands:
+        p, ns = (None, 0) if ts is None else L.frames(ts[0], name)
+        args += [L.ptr_array(ts, name) if G and ts is not None else p, _l(ns), _i(C)]
+    n, F_, HW = max(G, 1), dims[0], dims[1] * (dims[2] if len(dims) > 2 else 1)
+    gw = _zeros(arena, n, M, Nc, device=operands[0][0][0].device)
+    L.call(launch[0], *args, L.ptr_array(gw.unbind(0), "gw") if G else L.dev(gw), *((_i(G),) if G else ()),
+           *[_i(d) for d in dims],
+           meta=("wgrad", launch[1], 2.0 * n * F_ * HW * M * Nc,
+                 "%sF%d %dx%d HW%d%s" % ("G%d " % G if G else "", F_, M, Nc, HW, tag),
+                 4.0 * n * (F_ * HW * (M + (Nc // 9 if tag else Nc)) + M * Nc)))
     return gw
 
 
-def conv2d_wgrad_b3(in1, in2, g, Cout, ks, arena=None):
-    """weight gradient through the split-precision GEMM: 3x3 convs expand their smaller operand in HBM first
-    (im2col of the input when Cin <= Cout, tap-scatter of the gradient otherwise)."""
-    N, C1, H, W = in1.shape
-    C2 = 0 if in2 is None else int(in2.shape[1])
-    Cin = C1 + C2
-    if ks == 1:
-        x = in1 if in2 is None else torch.cat((in1, in2), 1)
-        return gemm_wgrad(g, x, Cout, Cin, arena).view(Cout, Cin, 1, 1)
-    if Cin <= Cout and W % 8 == 0 and os.environ.get("RFN_WGRAD_IMPLICIT") != "0":
-        # shifted input planes are built while staging: no im2col buffer (rfn_conv3x3_wgrad_implicit_bf16x3)
-        i1p, i1ns = L.frames(in1, "in1")
-        i2p, i2ns = (None, 0) if in2 is None else L.frames(in2, "in2")
-        gp, gns = L.frames(g, "g")
-        gw = _zeros(arena, Cout, 9 * Cin, device=in1.device)
-        L.call("rfn_conv3x3_wgrad_implicit_bf16x3", gp, _l(gns), _i(Cout), i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2),
-               L.dev(gw), _i(N), _i(H), _i(W),
-               meta=("wgrad", kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, gns, 0, N, H, W),
-                     2.0 * N * H * W * Cout * 9 * Cin, "F%d %dx%d HW%d implicit3x3" % (N, Cout, 9 * Cin, H * W),
-                     4.0 * (N * H * W * (Cout + Cin) + Cout * 9 * Cin)))
-        return gw.view(Cout, Cin, 3, 3)  # rows of the implicit operand are (ci, tap): already the torch layout
-    if Cin <= Cout:
-        i1p, i1ns = L.frames(in1, "in1")
-        i2p, i2ns = (None, 0) if in2 is None else L.frames(in2, "in2")
-        x9 = torch.empty((N, 9 * Cin, H, W), device=in1.device, dtype=torch.float32)
-        L.call("rfn_im2col3x3_f32", i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), L.dev(x9), _i(N), _i(H), _i(W),
-               meta=_shell("im2col3x3", x9, 10.0 / 9.0))
-        gw = gemm_wgrad(g, x9, Cout, 9 * Cin, arena)  # [co][tap*Cin + ci]
-        return gw.view(Cout, 9, Cin).permute(0, 2, 1).reshape(Cout, Cin, 3, 3)
-    x = in1 if in2 is None else torch.cat((in1, in2), 1)
-    gs = torch.empty((N, 9 * Cout, H, W), device=in1.device, dtype=torch.float32)
-    L.call("rfn_tap_scatter_f32", L.dev(g.contiguous()), L.dev(gs), _i(N), _i(Cout), _i(H), _i(W),
-           meta=_shell("tap_scatter", gs, 10.0 / 9.0))
-    gw = gemm_wgrad(gs, x, 9 * Cout, Cin, arena)  # [tap*Cout + co][ci]
-    return gw.view(3, 3, Cout, Cin).permute(2, 3, 0, 1).contiguous()
+def _gemm_wgrad(G, a_list, b_list, M, Nc, arena, launch=None):
+    """gw [max(G, 1), M, Nc], gw[g] = Σ_{frames,pixels} a_g[f,m,p] b_g[f,n,p] on the split-precision MFMA GEMM
+    (rfn_gemm_wgrad[_grouped]_bf16x3): one launch.  `launch`: as a WgradPlan names it, where one does."""
+    F_, HW = int(a_list[0].shape[0]), _hw(a_list[0])
+    launch = launch or _b3_launch(G, "rfn_gemm_wgrad_bf16x3", M, Nc, _frame_stride(a_list[0]), _frame_stride(b_list[0]), G,
+                                  F_, HW)
+    return _b3_wgrad(launch, G, [(a_list, "a", M), (b_list, "b", Nc)], M, Nc, (F_, HW), arena)
+
+
+def gemm_wgrad(a, b, M, Nc, arena=None):
+    return _gemm_wgrad(0, [a], [b], M, Nc, arena)[0]
 
 
 def gemm_wgrad_grouped(a_list, b_list, M, Nc, arena=None):
-    """G gradients gw[g][M][Nc] = Σ a_g b_g^T of one shape in ONE launch (rfn_gemm_wgrad_grouped_bf16x3)."""
-    G = len(a_list)
-    F_, HW = int(a_list[0].shape[0]), _hw(a_list[0])
-    ans, bns = L.frames(a_list[0], "a")[1], L.frames(b_list[0], "b")[1]
-    gw = _zeros(arena, G, M, Nc, device=a_list[0].device)
-    pa, pb = L.ptr_array(a_list, "a"), L.ptr_array(b_list, "b")
-    pg = L.ptr_array([gw[g] for g in range(G)], "gw")
-    L.call("rfn_gemm_wgrad_grouped_bf16x3", pa, _l(ans), _i(M), pb, _l(bns), _i(Nc), pg, _i(G), _i(F_), _i(HW),
-           meta=("wgrad", kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, ans, bns, G, F_,
-                                       HW).replace("<", "<grouped "),
-                 2.0 * G * F_ * HW * M * Nc, "G%d F%d %dx%d HW%d" % (G, F_, M, Nc, HW),
-                 4.0 * G * (F_ * HW * (M + Nc) + M * Nc)))
-    return gw
+    """G gradients of one shape (at most 16) in ONE launch"""
+    return _gemm_wgrad(len(a_list), a_list, b_list, M, Nc, arena)
 
 
 _grouped_wgrad_budget = {}  # device index -> bytes
@@ -520,89 +510,148 @@ def group_level_wgrad(Kn, N, Hd, HW, o_numel, device):
             grouped_wgrad_retained_bytes(Kn, N, Hd, HW, o_numel) <= grouped_wgrad_budget(device))
 
 
-def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_stacked=None):
-    """the weight gradients of G convolutions of ONE shape (the K steps of a flow level) in one GEMM launch: list of G
-    tensors [Cout, Cin, ks, ks].  Same operand choices as conv2d_wgrad_b3 (the small operand of a 3x3 gradient is
-    expanded per step -- in one launch when the gradients are the slices of `g_stacked` -- and the layout fix-up is one
-    copy for all groups)."""
-    G = len(g_list)
-    N, C1, H, W = in1_list[0].shape
-    has2 = in2_list is not None and in2_list[0] is not None
-    C2 = int(in2_list[0].shape[1]) if has2 else 0
-    Cin = C1 + C2
-    dev_ = in1_list[0].device
+WgradPlan = collections.namedtuple("WgradPlan", "form G M Nc launches")
+_TAP_SCATTER, _IM2COL = ("rfn_tap_scatter_f32", "tap_scatter"), ("rfn_im2col3x3_f32", "im2col3x3")
+
+
+def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=False, min_pixels=0, stacked=False):
+    """How the weight gradient(s) [Cout, C1 + C2, ks, ks] of a convolution on N frames of H x W are computed, from shapes,
+    strides and options alone (no tensor, no device): the one decision of the path, which _wgrad_run executes and the
+    host tests query.  G = 0: one gradient; G >= 1: G of one shape in grouped launches.  g_ns / in1_ns: frame strides
+    of the output gradient and of the first input source (default: dense).  few_out: the caller is a Conv2dZeros
+    (one-source input), which alone may take the mirrored kernel (from `min_pixels` pixels G * N * H * W) or the fp32
+    tap route.  stacked: the G output gradients are the slices of one contiguous [G, N, Cout, H, W] buffer.
+    Returns WgradPlan(form, G, M, Nc, launches): the form (table in DESIGN.md, "Where the labels come from"), the GEMM
+    dimensions gw[M][Nc] and, in order, the (entry point, label) of every library launch.  CONV_PRECISION,
+    RFN_WGRAD_IMPLICIT, RFN_WGRAD_MIRRORED and the label queries are read on every call."""
+    Cin, HW, n = C1 + C2, H * W, max(G, 1)
+    g_ns = Cout * HW if g_ns is None else g_ns
+    in1_ns = C1 * HW if in1_ns is None else in1_ns
+    x_ns = in1_ns if C2 == 0 else Cin * HW   # the input as ONE GEMM operand: in1 itself, or cat(in1, in2)
+    b3 = wgrad_b3(H, W)
+    scatter = [_TAP_SCATTER] * (1 if stacked else n)   # a launch per gradient, or one over the stacked G * N frames
+    assert not (few_out and C2)
+
+    def plan(form, M, Nc, *launches):
+        return WgradPlan(form, G, M, Nc, list(launches))
+
+    def gemm(M, Nc, a_ns, b_ns):
+        return _b3_launch(G, "rfn_gemm_wgrad_bf16x3", M, Nc, a_ns, b_ns, G, N, HW)
+
+    def f32(k, Co):
+        return ("rfn_conv2d_wgrad_f32", kernel_label("rfn_conv2d_wgrad_kernel_label_f32", k, Cin, Co, H, W))
+
+    if not b3 and not G:   # the fp32-MFMA kernel (a group is always split precision: CouplingRoute.defer_wgrad)
+        if few_out and ks == 3 and Cout <= TAP_MAX_COUT:   # as a 1x1 conv to the 9 Cout tap-scattered channels
+            return plan("scatter_f32", 9 * Cout, Cin, *scatter, f32(1, 9 * Cout))
+        return plan("f32", Cout, ks * ks * Cin, f32(ks, Cout), *([("rfn_wgrad_finish_f32", "wgrad_finish")] if ks > 1 else []))
     if ks == 1:
-        xs = in1_list if not has2 else [torch.cat((a, b), 1) for a, b in zip(in1_list, in2_list)]
-        gw = gemm_wgrad_grouped(g_list, xs, Cout, Cin, arena)
-        return [gw[i].view(Cout, Cin, 1, 1) for i in range(G)]
-    if Cin <= Cout and W % 8 == 0 and os.environ.get("RFN_WGRAD_IMPLICIT") != "0":
-        gw = _zeros(arena, G, Cout, 9 * Cin, device=dev_)
-        gns, i1ns = L.frames(g_list[0], "g")[1], L.frames(in1_list[0], "in1")[1]
-        i2ns = L.frames(in2_list[0], "in2")[1] if has2 else 0
-        pg, p1 = L.ptr_array(g_list, "g"), L.ptr_array(in1_list, "in1")
-        p2 = L.ptr_array(in2_list, "in2") if has2 else None
-        pw = L.ptr_array([gw[i] for i in range(G)], "gw")
-        L.call("rfn_conv3x3_wgrad_implicit_grouped_bf16x3", pg, _l(gns), _i(Cout), p1, _l(i1ns), _i(C1), p2, _l(i2ns),
-               _i(C2), pw, _i(G), _i(N), _i(H), _i(W),
-               meta=("wgrad", kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, gns, G, N, H,
-                                           W).replace("<", "<grouped "),
-                     2.0 * G * N * H * W * Cout * 9 * Cin,
-                     "G%d F%d %dx%d HW%d implicit3x3" % (G, N, Cout, 9 * Cin, H * W),
-                     4.0 * G * (N * H * W * (Cout + Cin) + Cout * 9 * Cin)))
-        return [gw[i].view(Cout, Cin, 3, 3) for i in range(G)]
-    if Cin <= Cout:
-        x9s = []
-        for i in range(G):
-            i1p, i1ns = L.frames(in1_list[i], "in1")
-            i2p, i2ns = (None, 0) if not has2 else L.frames(in2_list[i], "in2")
-            x9 = torch.empty((N, 9 * Cin, H, W), device=dev_, dtype=torch.float32)
-            L.call("rfn_im2col3x3_f32", i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), L.dev(x9), _i(N), _i(H), _i(W),
-                   meta=_shell("im2col3x3", x9, 10.0 / 9.0))
-            x9s.append(x9)
-        gw = gemm_wgrad_grouped(g_list, x9s, Cout, 9 * Cin, arena)  # [g][co][tap*Cin + ci]
-        gwt = gw.view(G, Cout, 9, Cin).permute(0, 1, 3, 2).reshape(G, Cout, Cin, 3, 3)  # one copy for all groups
-        return [gwt[i] for i in range(G)]
-    xs = in1_list if not has2 else [torch.cat((a, b), 1) for a, b in zip(in1_list, in2_list)]
-    gss = []
-    if g_stacked is not None and g_stacked.is_contiguous() and tuple(g_stacked.shape) == (G, N, Cout, H, W):
-        # the G gradients are slices of one [G, N, Cout, H, W] buffer (in list order): one scatter launch over G*N frames
-        gs_all = torch.empty((G, N, 9 * Cout, H, W), device=dev_, dtype=torch.float32)
-        L.call("rfn_tap_scatter_f32", L.dev(g_stacked), L.dev(gs_all), _i(G * N), _i(Cout), _i(H), _i(W),
-               meta=_shell("tap_scatter", gs_all, 10.0 / 9.0))
-        gss = [gs_all[i] for i in range(G)]
-    else:
-        for i in range(G):
-            gs = torch.empty((N, 9 * Cout, H, W), device=dev_, dtype=torch.float32)
-            gi = g_list[i].contiguous()
-            L.call("rfn_tap_scatter_f32", L.dev(gi), L.dev(gs), _i(N), _i(Cout), _i(H), _i(W),
-                   meta=_shell("tap_scatter", gs, 10.0 / 9.0))
-            gss.append(gs)
-    gw = gemm_wgrad_grouped(gss, xs, 9 * Cout, Cin, arena)  # [g][tap*Cout + co][ci]
-    gwt = gw.view(G, 3, 3, Cout, Cin).permute(0, 3, 4, 1, 2).contiguous()
-    return [gwt[i] for i in range(G)]
+        return plan("gemm", Cout, Cin, gemm(Cout, Cin, g_ns, x_ns))
+    if Cin <= Cout:   # the input is the small operand: its shifted planes built while staging, or expanded in memory
+        if W % 8 == 0 and os.environ.get("RFN_WGRAD_IMPLICIT") != "0":
+            return plan("implicit", Cout, 9 * Cin,
+                        _b3_launch(G, "rfn_conv3x3_wgrad_implicit_bf16x3", Cout, g_ns, G, N, H, W))
+        return plan("im2col", Cout, 9 * Cin, *[_IM2COL] * n, gemm(Cout, 9 * Cin, g_ns, 9 * Cin * HW))
+    if few_out and ks == 3 and b3 and os.environ.get("RFN_WGRAD_MIRRORED") != "0" and n * N * HW >= min_pixels:
+        launch = _b3_launch(G, "rfn_conv3x3_wgrad_mirrored_bf16x3", Cin, in1_ns, Cout, G, N, H, W)
+        if launch[1]:   # ('': the library names no mirrored kernel for this shape)
+            return plan("mirrored", Cin, 9 * Cout, launch)
+    return plan("scatter", 9 * Cout, Cin, *scatter, gemm(9 * Cout, Cin, 9 * Cout * HW, x_ns))
+
+
+def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
+    """The launches of `plan` and the layout fix-up: the n = max(plan.G, 1) weight gradients (list of contiguous tensors or
+    views [Cout, Cin, ks, ks]) of the convolutions of cat(in1s[i], in2s[i]) -- in2s None: one source -- with output
+    gradients gs[i].  `plan` is wgrad_plan of these operands; every launch takes its entry point and label from
+    plan.launches, in order.  g_stacked: the gradients as one buffer, iff the plan was made with `stacked`.  Strided
+    frames go to the implicit and GEMM forms as they are; the scatter and mirrored forms make their gradient dense.
+    One arena take and one transposing copy per call, whatever G."""
+    G, n, form = plan.G, max(plan.G, 1), plan.form
+    N, C1, H, W = in1s[0].shape
+    C2 = 0 if in2s is None else int(in2s[0].shape[1])
+    Cin, Cout, dev_ = C1 + C2, int(gs[0].shape[1]), in1s[0].device
+    todo = iter(plan.launches)
+
+    def cat():
+        return in1s if in2s is None else [torch.cat((a, b), 1) for a, b in zip(in1s, in2s)]
+
+    def tap_scatter():
+        """the gradients' tap-scattered copies [N, 9 Cout, H, W]: a launch each, or one over the n * N frames of g_stacked"""
+        srcs = gs if g_stacked is None else [g_stacked]
+        outs = [torch.empty(tuple(s.shape[:-3]) + (9 * Cout, H, W), device=dev_, dtype=torch.float32) for s in srcs]
+        for s, o in zip(srcs, outs):
+            entry, label = next(todo)
+            L.call(entry, L.dev(s.contiguous()), L.dev(o), _i(o.numel() // (9 * Cout * H * W)), _i(Cout), _i(H), _i(W),
+                   meta=_shell(label, o, 10.0 / 9.0))
+        return outs if g_stacked is None else list(outs[0].unbind(0))
+
+    if form in ("f32", "scatter_f32"):
+        g, Co, k = (gs[0], Cout, ks) if form == "f32" else (tap_scatter()[0], 9 * Cout, 1)
+        i1p, i1ns = L.frames(in1s[0], "in1")
+        i2p, i2ns = (None, 0) if in2s is None else L.frames(in2s[0], "in2")
+        gp, gns = L.frames(g, "g")
+        gwt = _zeros(arena, k * k, Co, Cin, device=dev_)
+        entry, label = next(todo)
+        L.call(entry, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), gp, _l(gns), _i(Co), L.dev(gwt), _i(N), _i(H), _i(W),
+               _i(k), meta=("wgrad", label, 2.0 * N * H * W * Cin * Co * k * k, "N%d %d->%d %dx%d k%d" % (N, Cin, Co, H, W, k),
+                            4.0 * (N * H * W * (Cin + Co) + Cin * Co * k * k)))
+        if form == "scatter_f32":
+            out = [gwt.view(3, 3, Cout, Cin).permute(2, 3, 0, 1).contiguous()]   # from [tap * Cout + co][ci]
+        elif ks == 1:
+            out = [gwt.view(Cout, Cin, 1, 1)]  # tap-major == torch layout when there is a single tap
+        else:
+            out = [torch.empty((Cout, Cin, ks, ks), device=dev_, dtype=torch.float32)]
+            entry, label = next(todo)
+            L.call(entry, L.dev(gwt), L.dev(out[0]), _i(Cout), _i(Cin), _i(ks), _i(0), meta=_shell(label, out[0], 2))
+    elif form == "gemm":
+        out = [t.view(Cout, Cin, 1, 1) for t in _gemm_wgrad(G, gs, cat(), Cout, Cin, arena, next(todo))]
+    elif form == "implicit":   # rows (ci, tap) of the implicit operand: already the torch layout
+        gw = _b3_wgrad(next(todo), G, [(gs, "g", Cout), (in1s, "in1", C1), (in2s, "in2", C2)], Cout, 9 * Cin, (N, H, W), arena,
+                       " implicit3x3")
+        out = [t.view(Cout, Cin, 3, 3) for t in gw]
+    elif form == "im2col":
+        x9s = [torch.empty((N, 9 * Cin, H, W), device=dev_, dtype=torch.float32) for _ in range(n)]
+        for i, x9 in enumerate(x9s):
+            i1p, i1ns = L.frames(in1s[i], "in1")
+            i2p, i2ns = (None, 0) if in2s is None else L.frames(in2s[i], "in2")
+            entry, label = next(todo)
+            L.call(entry, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), L.dev(x9), _i(N), _i(H), _i(W),
+                   meta=_shell(label, x9, 10.0 / 9.0))
+        gw = _gemm_wgrad(G, gs, x9s, Cout, 9 * Cin, arena, next(todo))  # [g][co][tap*Cin + ci]
+        out = list(gw.view(n, Cout, 9, Cin).permute(0, 1, 3, 2).reshape(n, Cout, Cin, 3, 3))  # one copy for all groups
+    elif form == "scatter":
+        xs, gss = cat(), tap_scatter()
+        gw = _gemm_wgrad(G, gss, xs, 9 * Cout, Cin, arena, next(todo))  # [g][tap*Cout + co][ci]
+        out = list(gw.view(n, 3, 3, Cout, Cin).permute(0, 3, 4, 1, 2).contiguous())
+    else:   # mirrored: the input through the ring, the (dense) gradient shifted while staging; gw is [g][ci][co][tap]
+        gw = _b3_wgrad(next(todo), G, [(in1s, "x", Cin), ([g.contiguous() for g in gs], "g", Cout)], Cin, 9 * Cout, (N, H, W),
+                       arena, " mirrored3x3")
+        out = list(gw.view(n, Cin, Cout, 3, 3).permute(0, 2, 1, 3, 4).contiguous())
+    assert next(todo, None) is None, plan
+    return out
+
+
+def _conv_wgrad(G, in1s, in2s, gs, Cout, ks, arena, g_stacked=None, few_out=False, min_pixels=0):
+    """wgrad_plan of the operands, executed: what every public weight-gradient function of a convolution is"""
+    N, C1, H, W = in1s[0].shape
+    if in2s is not None and in2s[0] is None:
+        in2s = None
+    if not (G and g_stacked is not None and g_stacked.is_contiguous() and tuple(g_stacked.shape) == (G, N, Cout, H, W)):
+        g_stacked = None   # (else the G gradients are its slices, in list order)
+    plan = wgrad_plan(G, N, C1, 0 if in2s is None else int(in2s[0].shape[1]), Cout, H, W, ks, _frame_stride(gs[0]),
+                      _frame_stride(in1s[0]), few_out, min_pixels, g_stacked is not None)
+    return _wgrad_run(plan, in1s, in2s, gs, ks, arena, g_stacked)
+
+
+def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_stacked=None):
+    """the weight gradients of G convolutions of ONE shape (the K steps of a flow level) in grouped launches: list of G
+    tensors [Cout, Cin, ks, ks].  g_stacked: the buffer the G gradients are slices of, if they are."""
+    return _conv_wgrad(len(g_list), in1_list, in2_list, g_list, Cout, ks, arena, g_stacked)
 
 
 def conv2d_wgrad(in1, in2, g, Cout, ks, arena=None):
     """returns gw [Cout, Cin, ks, ks]"""
-    N, C1, H, W = in1.shape
-    C2 = 0 if in2 is None else int(in2.shape[1])
-    Cin = C1 + C2
-    if bwd_b3() and (H * W) % 4 == 0:
-        return conv2d_wgrad_b3(in1, in2, g, Cout, ks, arena)
-    i1p, i1ns = L.frames(in1, "in1")
-    i2p, i2ns = (None, 0) if in2 is None else L.frames(in2, "in2")
-    gp, gns = L.frames(g, "g")
-    gwt = _zeros(arena, ks * ks, Cout, Cin, device=in1.device)
-    L.call("rfn_conv2d_wgrad_f32", i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), gp, _l(gns), _i(Cout), L.dev(gwt),
-           _i(N), _i(H), _i(W), _i(ks),
-           meta=("wgrad", kernel_label("rfn_conv2d_wgrad_kernel_label_f32", ks, Cin, Cout, H, W),
-                 2.0 * N * H * W * Cin * Cout * ks * ks,
-                 "N%d %d->%d %dx%d k%d" % (N, Cin, Cout, H, W, ks), 4.0 * (N * H * W * (Cin + Cout) + Cin * Cout * ks * ks)))
-    if ks == 1:
-        return gwt.view(Cout, Cin, 1, 1)  # tap-major == torch layout when there is a single tap
-    gw = torch.empty((Cout, Cin, ks, ks), device=in1.device, dtype=torch.float32)
-    L.call("rfn_wgrad_finish_f32", L.dev(gwt), L.dev(gw), _i(Cout), _i(Cin), _i(ks), _i(0), meta=_shell("wgrad_finish", gw, 2))
-    return gw
+    return _conv_wgrad(0, [in1], None if in2 is None else [in2], [g], Cout, ks, arena)[0]
 
 
 TAP_MAX_COUT = 8  # 3x3 convs with at most this many outputs run tap-expanded (1x1 to 9*C channels + shift-add)
@@ -635,43 +684,9 @@ def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None, taps=None):
     return o
 
 
-def _mirrored_wgrad_label(x, C, ks, G):
-    """label of the mirrored 3x3 weight-gradient launch (rfn_conv3x3_wgrad_mirrored[_grouped]_bf16x3: the conv's input
-    x [N, Cin, H, W] through the ring, the C gradient planes shifted while staging, no tap-scattered copy) for G groups
-    (0: the single form), or '' when the gradient takes conv2d_wgrad's routes: another arithmetic, Cin <= C (the
-    implicit form proper), RFN_WGRAD_MIRRORED=0, or a shape for which the library names no mirrored kernel."""
-    N, Cin, H, W = x.shape
-    if ks != 3 or Cin <= C or not bwd_b3() or (H * W) % 4 != 0 or os.environ.get("RFN_WGRAD_MIRRORED") == "0":
-        return ""
-    return kernel_label("rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3", int(Cin), L.frames(x, "x")[1], int(C), G, int(N),
-                        int(H), int(W))
-
-
-def _mirrored_wgrad_meta(label, G, N, Cin, C, HW):
-    return ("wgrad", label, 2.0 * max(G, 1) * N * HW * Cin * 9 * C,
-            "%sF%d %dx%d HW%d mirrored3x3" % ("G%d " % G if G else "", N, Cin, 9 * C, HW),
-            4.0 * max(G, 1) * (N * HW * (Cin + C) + Cin * 9 * C))
-
-
 def zeros_conv_wgrad(x, g_pre, C, ks, arena=None):
-    """weight gradient of the conv inside Conv2dZeros given g_pre = grad wrt (conv + b); same switch as the forward."""
-    label = _mirrored_wgrad_label(x, C, ks, 0)
-    if label:
-        N, Cin, H, W = x.shape
-        xp, xns = L.frames(x, "x")
-        gp, gns = L.frames(g_pre.contiguous(), "g")
-        gwT = _zeros(arena, Cin, C, 3, 3, device=x.device)
-        L.call("rfn_conv3x3_wgrad_mirrored_bf16x3", xp, _l(xns), _i(Cin), gp, _l(gns), _i(C), L.dev(gwT), _i(N), _i(H),
-               _i(W), meta=_mirrored_wgrad_meta(label, 0, N, Cin, C, H * W))
-        return gwT.permute(1, 0, 2, 3).contiguous()
-    if ks != 3 or C > TAP_MAX_COUT or (bwd_b3() and _hw(x) % 4 == 0):
-        return conv2d_wgrad(x, None, g_pre, C, ks, arena)
-    N, Cin, H, W = x.shape
-    Gs = torch.empty((N, 9 * C, H, W), device=x.device, dtype=torch.float32)
-    L.call("rfn_tap_scatter_f32", L.dev(g_pre.contiguous()), L.dev(Gs), _i(N), _i(C), _i(H), _i(W),
-           meta=_shell("tap_scatter", Gs, 10.0 / 9.0))
-    gw = conv2d_wgrad(x, None, Gs, 9 * C, 1, arena)  # [9C, Cin, 1, 1]
-    return gw.view(3, 3, C, Cin).permute(2, 3, 0, 1).contiguous()
+    """weight gradient of the conv inside Conv2dZeros given g_pre = grad wrt (conv + b): wgrad_plan with few_out"""
+    return _conv_wgrad(0, [x], None, [g_pre], C, ks, arena, few_out=True)[0]
 
 
 LEVEL_MIRRORED_MIN_PIXELS = 1 << 17
@@ -686,26 +701,9 @@ def level_mirrored_min_pixels():
 
 
 def zeros_conv_wgrad_grouped(h2_list, go_list, C, arena=None, g_stacked=None, ks=3, min_pixels=0):
-    """zeros_conv_wgrad for the G convolutions of one shape of a flow level: list of G tensors [C, Cin, ks, ks].  One
-    mirrored launch and one transposing copy for all groups where the library names a mirrored kernel (and the G groups
-    have `min_pixels` pixels together), else conv2d_wgrad_grouped (which expands the gradients -- the slices of
-    `g_stacked` in one launch -- in memory)."""
-    G = len(go_list)
-    label = _mirrored_wgrad_label(h2_list[0], C, ks, G)
-    if label and G * int(h2_list[0].shape[0]) * _hw(h2_list[0]) < min_pixels:
-        label = ""
-    if not label:
-        return conv2d_wgrad_grouped(h2_list, None, go_list, C, ks, arena, g_stacked=g_stacked)
-    N, Cin, H, W = h2_list[0].shape
-    go_list = [g.contiguous() for g in go_list]
-    gwT = _zeros(arena, G, Cin, C, 3, 3, device=h2_list[0].device)
-    xns, gns = L.frames(h2_list[0], "x")[1], L.frames(go_list[0], "g")[1]
-    px, pg = L.ptr_array(h2_list, "x"), L.ptr_array(go_list, "g")
-    pw = L.ptr_array([gwT[i] for i in range(G)], "gw")
-    L.call("rfn_conv3x3_wgrad_mirrored_grouped_bf16x3", px, _l(xns), _i(Cin), pg, _l(gns), _i(C), pw, _i(G), _i(N),
-           _i(H), _i(W), meta=_mirrored_wgrad_meta(label.replace("<", "<grouped "), G, N, Cin, C, H * W))
-    gw = gwT.permute(0, 2, 1, 3, 4).contiguous()   # one copy for all groups
-    return [gw[i] for i in range(G)]
+    """zeros_conv_wgrad for the G convolutions of one shape of a flow level: list of G tensors [C, Cin, ks, ks]; the
+    mirrored launch only where the G groups have `min_pixels` pixels together"""
+    return _conv_wgrad(len(go_list), h2_list, None, go_list, C, ks, arena, g_stacked, True, min_pixels)
 
 
 def conv_epilogue_bwd(y, gy, logs, ep_mode, act, want_gl=True, arena=None, inplace=True):
@@ -959,7 +957,7 @@ def coupling_route(N, C, Cc, Hd, H, W, k1, k2, k3, act, grad, reverse=False):
         packs += (("po_bwd",) if chain == "po" else ("w3_dgrad", "w2_dgrad")) + (
             "w1_dense_dgrad" if dgrad1 == "dense" else "w1_dgrad",)
     return CouplingRoute("po" if po else "convs", fp, conv1, conv3, bool(po and po_bwd and act != 0), chain, dgrad1,
-                         bool(back and b3 and H * W % 4 == 0), packs)
+                         bool(back and Hd % 64 == 0 and wgrad_b3(H, W)), packs)
 
 
 def _step_route(x, cond, w1, w2, w3, act, grad, reverse=False):

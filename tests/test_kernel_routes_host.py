@@ -69,33 +69,13 @@ def test_gemm_cases_take_their_table_route(K, name):
     assert (label.replace("<", "<grouped ") if G else label) == tile
 
 
-def _wgrad_labels(K, G, N, C1, C2, Cout, H, W, ks):
-    """the labelled launches of K.conv2d_wgrad / K.conv2d_wgrad_grouped for one case: its operand choices, then the
-    queries (dense gradient; the GEMM operands of the 3x3 forms are dense expansions)"""
-    Cin, HW = C1 + C2, H * W
-    grouped = (lambda s: s.replace("<", "<grouped ")) if G else (lambda s: s)
-    gemm = "rfn_gemm_wgrad_grouped_bf16x3" if G else "rfn_gemm_wgrad_bf16x3"
-    if HW % 4 != 0:
-        assert not G
-        return [("rfn_conv2d_wgrad_f32", K.kernel_label("rfn_conv2d_wgrad_kernel_label_f32", ks, Cin, Cout, H, W)),
-                ("rfn_wgrad_finish_f32", "wgrad_finish")]
-    if ks == 3 and Cin <= Cout and W % 8 == 0:
-        impl = "rfn_conv3x3_wgrad_implicit_grouped_bf16x3" if G else "rfn_conv3x3_wgrad_implicit_bf16x3"
-        return [(impl, grouped(K.kernel_label("rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3", Cout, Cout * HW, G, N, H, W)))]
-    if ks == 1:      # a = the gradient, b = the input (C2 == 0 in the table: in1 itself, a slice when `view`)
-        M, Nc, pre = Cout, Cin, []
-    elif Cin <= Cout:
-        M, Nc, pre = Cout, 9 * Cin, [("rfn_im2col3x3_f32", "im2col3x3")] * max(G, 1)
-    else:
-        M, Nc, pre = 9 * Cout, Cin, [("rfn_tap_scatter_f32", "tap_scatter")]
-    return pre + [(gemm, grouped(K.kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", M, Nc, M * HW, Nc * HW, G, N, HW)))]
-
-
 @pytest.mark.parametrize("name", list(WGRAD_CASES))
 def test_wgrad_cases_take_their_table_routes(K, name):
+    """the launches K.conv2d_wgrad / K.conv2d_wgrad_grouped make are those of K.wgrad_plan, which needs no device (`view`:
+    in1 is the channel slice z[:, :C1] of a tensor twice as wide -- its frame stride)"""
     G, N, C1, C2, Cout, H, W, ks, view, want = WGRAD_CASES[name]
-    assert ks == 3 and C1 + C2 <= Cout or not (view and C2 == 0)   # (_wgrad_labels: no sliced GEMM operand in the table)
-    assert _wgrad_labels(K, G, N, C1, C2, Cout, H, W, ks) == want
+    plan = K.wgrad_plan(G, N, C1, C2, Cout, H, W, ks, in1_ns=2 * C1 * H * W if view else None, stacked=bool(G))
+    assert plan.launches == want
 
 
 def test_fp32_1x1_between_65_and_128_outputs_takes_the_128_row_block(K):

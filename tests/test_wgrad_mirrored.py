@@ -226,6 +226,45 @@ def test_4x4_map_keeps_scatter_and_gemm(K):
     assert e_new < 2e-5 and e_old < 2e-5, (e_new, e_old)
 
 
+@gpu
+def test_plan_is_what_runs_fp32_taps_and_unstacked_group(K, monkeypatch):
+    """ops.wgrad_plan against execution on the two forms no other test pins launch by launch.  fp32 arithmetic,
+    x [3, 16, 6, 6], C = 4: tap scatter + the fp32 kernel as a 1x1 conv to 36 channels, within 1e-4 of fp64 F.conv2d (the
+    bound of test_tap_expanded_zeros_conv_fwd_wgrad).  Split precision, G = 2 gradients 20 -> 4 on 3 frames of 4x4 given
+    as a list with no stacked buffer: a tap scatter each and one grouped GEMM, relerr < 2e-5."""
+    def case(G, N, Cin, C, H, W, seed):
+        g = torch.Generator().manual_seed(seed)
+        n = max(G, 1)
+        x, go = torch.randn(n, N, Cin, H, W, generator=g), torch.randn(n, N, C, H, W, generator=g)
+        refs = []
+        for i in range(n):
+            w = torch.zeros(C, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+            F.conv2d(x[i].double(), w, padding=1).backward(go[i].double())
+            refs.append(w.grad)
+        xs, gos = [t.cuda() for t in x], [t.cuda() for t in go]   # separate allocations: nothing stacked
+        plan = K.wgrad_plan(G, N, Cin, 0, C, H, W, 3, few_out=True)
+        if G:
+            got, calls = _profiled(lambda: K.zeros_conv_wgrad_grouped(xs, gos, C))
+        else:
+            got, calls = _profiled(lambda: [K.zeros_conv_wgrad(xs[0], gos[0], C, 3)])
+        assert calls == plan.launches, (calls, plan)
+        for t in got:
+            assert tuple(t.shape) == (C, Cin, 3, 3) and t.is_contiguous()
+        e = max(relerr(got[i], refs[i]) for i in range(n))
+        print("G%d N%d %d->%d %dx%d: %s %s relerr %.3g" % (G, N, Cin, C, H, W, plan.form, calls, e))
+        return plan, e
+
+    plan, e = case(2, 3, 20, 4, 4, 4, 7100)
+    assert plan.form == "scatter" and [name for name, _ in plan.launches] == [
+        "rfn_tap_scatter_f32", "rfn_tap_scatter_f32", "rfn_gemm_wgrad_grouped_bf16x3"], plan
+    assert e < 2e-5, e
+    monkeypatch.setattr(K, "CONV_PRECISION", "f32")
+    plan, e = case(0, 3, 16, 4, 6, 6, 7101)
+    assert plan.form == "scatter_f32" and [name for name, _ in plan.launches] == [
+        "rfn_tap_scatter_f32", "rfn_conv2d_wgrad_f32"], plan
+    assert e < 1e-4, e
+
+
 # ---- one level node end to end: the mirrored route against RFN_WGRAD_MIRRORED=0 (fresh child process)
 LEVEL = dict(N=200, C=8, Cc=32, S=16, Kn=2, Hd=256)
 
