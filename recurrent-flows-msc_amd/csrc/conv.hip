@@ -74,13 +74,16 @@ extern "C" int rfn_pack_conv_weight_f32(const float* w, float* wpk, int Cout, in
 }
 
 // ------------------------------------------------------------------------------------------------ forward / dgrad
+// Image slots per staging thread (HaloSlots): 4 cover the 256-pixel 3x3 tiles, 2 everything smaller.  The split-
+// precision kernel (conv_b3_npos, conv_bf16x3.hip) drops to 1 below 128 pixels, where a slot costs it eight staging
+// registers per channel group; here a slot costs one, and with 2 the 32-pixel tile still takes 1x1 maps (32 frames x
+// 9 = 288 slots).  The difference is historical; nobody measured either kernel at the other's value.
+static constexpr int conv_f32_npos(int KS, int BPX) { return KS == 1 ? 1 : (BPX >= 256 ? 4 : 2); }
+
 template <int KS, int WCO, int WPX, int TCO, int TPX, int KC>
-#ifndef RFN_CONV_WAVES
-#define RFN_CONV_WAVES 1
-#endif
-__global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const ConvParams p) {
+__global__ __launch_bounds__(256, 1) void conv_mfma_kernel(const ConvParams p) {
     constexpr int T = KS * KS, PAD = KS / 2;
-    constexpr int BCO = 32 * TCO * WCO;
+    constexpr int BCO = 32 * TCO * WCO, BPX = 32 * TPX * WPX;
     static_assert(WCO * WPX == 4, "4 waves");
     extern __shared__ float lds[];  // [KC][IMG]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -89,29 +92,15 @@ __global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const Co
     const int HW = p.H * p.W;
     const int Cin = p.C1 + p.C2;
 
-    int pt = blockIdx.x;
-    const int wt = pt % p.n_wtiles;
-    pt /= p.n_wtiles;
-    const int ht = pt % p.n_htiles;
-    const int ft = pt / p.n_htiles;
-    const int x0 = wt * p.TWp, y0 = ht * p.TH, f0 = ft * p.TF;
-    const int RW = p.TWp + 2 * PAD, RH = p.TH + 2 * PAD;
-    const int FRM = RH * RW;       // one frame's padded image
-    const int IMG = p.TF * FRM;    // per channel
+    const ConvTile tl = conv_tile_origin<PAD>(p);
+    const int RW = tl.RW, IMG = tl.IMG;
     const int co_base = blockIdx.y * BCO + wco * (32 * TCO);
-
     int lds_off[TPX], pn[TPX], ppix[TPX];
     bool pvalid[TPX];
 #pragma unroll
     for (int t = 0; t < TPX; ++t) {
-        int q = (wpx * TPX + t) * 32 + l31;
-        int col = q & (p.TWp - 1);
-        int row = (q >> p.tw_shift) & (p.TH - 1);
-        int f = q >> (p.tw_shift + p.th_shift);
-        lds_off[t] = f * FRM + row * RW + col;
-        pvalid[t] = (x0 + col < p.W) && (y0 + row < p.H) && (f0 + f < p.N);
-        pn[t] = f0 + f;
-        ppix[t] = (y0 + row) * p.W + x0 + col;
+        const ConvPixel px = conv_pixel(p, tl, (wpx * TPX + t) * 32 + l31);
+        lds_off[t] = px.lds_off, pn[t] = px.n, ppix[t] = px.pix, pvalid[t] = px.valid;
     }
 
     f32x16 acc[TCO][TPX];
@@ -122,36 +111,17 @@ __global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const Co
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][t][r] = 0.f;
 
-    // ---- staging descriptors, computed ONCE per workgroup (the integer divisions live here, not in the K loop):
-    // thread -> image slot(s) r = slot + P2*j and channel phase; per chunk it then only adds a channel offset.
-    // P2 = slots per pass (compile time): a 1x1 tile of 128 pixels is covered by half the block, so the two halves
-    // take alternate channels (GROUPS = 2); every other case has IMG > 128 and uses all 256 threads as slots.
-    constexpr int BPX = 32 * TPX * WPX;
-    constexpr int NPOS = (KS == 1) ? 1 : (BPX >= 256 ? 4 : 2);
-    // (P2 >= 64 keeps `phase` wave-uniform)
-    constexpr int GROUPS = (KS == 1 && BPX < 256) ? (BPX >= 64 ? 256 / BPX : 4) : 1;
-    constexpr int P2 = 256 / GROUPS;
+    // ---- activations: one float per (channel, slot) in registers, stored as is -> lds[channel][slot]
+    constexpr int NPOS = conv_f32_npos(KS, BPX);
+    typedef HaloSlots<KS, BPX, NPOS> Halo;
+    constexpr int GROUPS = Halo::GROUPS, P2 = Halo::P2;
     const int slot = tid & (P2 - 1);
     const int phase = __builtin_amdgcn_readfirstlane(tid / P2);  // wave-uniform: keeps channel math scalar
     int soff1[NPOS], soff2[NPOS];
     bool sok[NPOS], sin[NPOS];
-#pragma unroll
-    for (int j = 0; j < NPOS; ++j) {
-        const int r = slot + P2 * j;
-        sin[j] = r < IMG;
-        const int f = r / FRM;
-        const int rr = r - f * FRM;
-        const int yy = rr / RW;
-        const int xx = rr - yy * RW;
-        const int gy = y0 + yy - PAD, gx = x0 + xx - PAD;
-        sok[j] = sin[j] && (f0 + f < p.N) && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-        // invalid slots read element 0 of the channel plane (always mapped) and are zeroed after the load, so the
-        // loads below are unconditional and the compiler can keep all of them in flight (no per-load branch/wait)
-        soff1[j] = sok[j] ? (int)(f * p.in1_ns) + gy * p.W + gx : 0;
-        soff2[j] = sok[j] ? (int)(f * p.in2_ns) + gy * p.W + gx : 0;
-    }
-    const float* in1b = p.in1 + (long)f0 * p.in1_ns;
-    const float* in2b = p.in2 ? p.in2 + (long)f0 * p.in2_ns : p.in1;
+    Halo::fill(p, tl, slot, soff1, soff2, sok, sin);
+    const float* in1b = p.in1 + (long)tl.f0 * p.in1_ns;
+    const float* in2b = p.in2 ? p.in2 + (long)tl.f0 * p.in2_ns : p.in1;
     float stg[KC / GROUPS][NPOS];
     auto prefetch = [&](int chunk) {
 #pragma unroll
@@ -162,10 +132,8 @@ __global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const Co
             const bool first = chc < p.C1;
             const float* src = first ? in1b + (long)chc * HW : in2b + (long)(chc - p.C1) * HW;
 #pragma unroll
-            for (int j = 0; j < NPOS; ++j) {
-                const float v = src[first ? soff1[j] : soff2[j]];
-                stg[i][j] = (sok[j] && chv) ? v : 0.f;
-            }
+            for (int j = 0; j < NPOS; ++j)
+                stg[i][j] = Halo::load(src, first ? soff1[j] : soff2[j], sok[j] && chv);
         }
     };
     auto commit = [&]() {
@@ -183,64 +151,28 @@ __global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const Co
     // chunk and stalled the wave for a full HBM round trip per chunk.)  The packed layout is linear per (iteration,
     // k-parity): runs of BCO float4, copied verbatim -> Ws4[(it_local*2 + kk)*BCO + cout_local].
     const int total_it = p.Cin8 * T;
-    const f32x4* wp4 = reinterpret_cast<const f32x4*>(p.wpk);
-    constexpr int ITC = (KC / 8) * T;               // iterations (8-channel group x tap) per chunk
-    constexpr int WRUNS = ITC * 2;                  // runs of BCO float4 per chunk
-    constexpr int WPT = (WRUNS * BCO + 255) / 256;  // float4 per thread per chunk
-    f32x4* Ws4 = reinterpret_cast<f32x4*>(lds + p.w_lds_off);
-    const long wblk = (long)blockIdx.y * BCO;
-    f32x4 wstg[WPT];
-    auto wprefetch = [&](int chunk) {
-        const int it0 = chunk * ITC;
-#pragma unroll
-        for (int j = 0; j < WPT; ++j) {
-            const int e = tid + 256 * j;
-            const int run = e / BCO, col = e % BCO;  // BCO is a power of two
-            const int itg = it0 + (run >> 1);
-            const bool ok = (WRUNS * BCO % 256 == 0 || e < WRUNS * BCO) && itg < total_it;
-            const f32x4 v = wp4[((long)(ok ? itg : 0) * 2 + (run & 1)) * p.CoutP + wblk + col];
-            wstg[j] = ok ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto wcommit = [&]() {
-#pragma unroll
-        for (int j = 0; j < WPT; ++j) {
-            const int e = tid + 256 * j;
-            if (WRUNS * BCO % 256 == 0 || e < WRUNS * BCO) Ws4[e] = wstg[j];
-        }
-    };
+    constexpr int ITC = (KC / 8) * T;  // iterations (8-channel group x tap) per chunk
+    WeightTileCopy<2, ITC, BCO> wtile;
+    u32x4* Ws4 = reinterpret_cast<u32x4*>(lds + p.w_lds_off);
+    auto wprefetch = [&](int chunk) { wtile.prefetch(p, chunk, total_it, tid); };
+    auto wcommit = [&]() { wtile.commit(Ws4, tid); };
 
-    // epilogue parameters of this block's BCO channels -> LDS (read after the K loop; its barriers order the write)
     float* ep = lds + KC * IMG;  // [2][BCO]
-    if (p.ep_mode != 0) {
-        for (int c = tid; c < BCO; c += 256) {
-            const int co = blockIdx.y * BCO + c;
-            float e0 = 0.f, e1 = 1.f;
-            if (co < p.Cout) {
-                if (p.ep_mode != 4) e0 = p.p0[co];
-                if (p.ep_mode == 1 || p.ep_mode == 4) e1 = expf(p.p1[co]);
-                if (p.ep_mode == 2) e1 = expf(3.f * p.p1[co]);
-            }
-            ep[c] = e0;
-            ep[BCO + c] = e1;
-        }
-    }
+    load_epilogue_params<BCO>(p, ep);
 
-    const int nchunks_all = (p.Cin8 * 8 + KC - 1) / KC;
-    const int cps = (nchunks_all + p.ksplit - 1) / p.ksplit;  // chunks per K split
-    const int chunk0 = blockIdx.z * cps;
-    const int nchunks = chunk0 + cps < nchunks_all ? chunk0 + cps : nchunks_all;
-    if (chunk0 < nchunks) {
-        prefetch(chunk0);
-        wprefetch(chunk0);
+    const ChunkRange kr = chunk_range(p, 8, KC);
+    if (kr.begin < kr.end) {
+        prefetch(kr.begin);
+        wprefetch(kr.begin);
     }
-    const f32x4* wa = Ws4 + kk * BCO + wco * (32 * TCO) + l31;  // + it_local*2*BCO + a*32
-    for (int chunk = chunk0; chunk < nchunks; ++chunk) {
+    // + it_local*2*BCO + a*32
+    const f32x4* wa = reinterpret_cast<const f32x4*>(Ws4) + kk * BCO + wco * (32 * TCO) + l31;
+    for (int chunk = kr.begin; chunk < kr.end; ++chunk) {
         __syncthreads();  // every wave is done reading the previous chunk
         commit();
         wcommit();
         __syncthreads();
-        if (chunk + 1 < nchunks) {  // global loads of the next chunk stay in flight under the MFMAs below
+        if (chunk + 1 < kr.end) {  // global loads of the next chunk stay in flight under the MFMAs below
             prefetch(chunk + 1);
             wprefetch(chunk + 1);
         }
@@ -273,52 +205,22 @@ __global__ __launch_bounds__(256, RFN_CONV_WAVES) void conv_mfma_kernel(const Co
 
     // ---- epilogue
     __syncthreads();  // ep[] visible even when the K loop ran zero chunks
-    conv_epilogue<TCO, TPX, BCO>(p, acc, ep, co_base, wco, kk, HW, pn, ppix, pvalid);
+    // (no partial sums: rfn_conv2d_fwd_f32 refuses ep_mode 4, the only mode that writes them)
+    conv_epilogue<TCO, TPX, BCO>(p, acc, ep, co_base, wco, kk, HW, pn, ppix, pvalid, nullptr, false);
 }
 
 template <int KS, int WCO, int WPX, int TCO, int TPX, int KC>
 static int launch_conv(ConvParams& p, hipStream_t s) {
-    constexpr int BCO = 32 * TCO * WCO, BPX = 32 * TPX * WPX, PAD = KS / 2;
-    tile_geometry(p.H, p.W, BPX, &p.TWp, &p.TH, &p.TF);
-    p.tw_shift = ilog2(p.TWp);
-    p.th_shift = ilog2(p.TH);
-    p.n_wtiles = ceil_div(p.W, p.TWp);
-    p.n_htiles = ceil_div(p.H, p.TH);
-    p.n_ftiles = ceil_div(p.N, p.TF);
-    const int IMG = p.TF * (p.TH + 2 * PAD) * (p.TWp + 2 * PAD);
-    constexpr int NPOS = (KS == 1) ? 1 : (BPX >= 256 ? 4 : 2);
-    constexpr int P2 = (KS == 1 && BPX < 256) ? (BPX >= 64 ? BPX : 64) : 256;
-    if (IMG > P2 * NPOS) {
-        rfn_set_error("conv2d: map %dx%d needs an LDS image of %d slots (> %d supported)", p.H, p.W, IMG, P2 * NPOS);
+    constexpr int BCO = 32 * TCO * WCO, BPX = 32 * TPX * WPX;
+    const int IMG = conv_tile_setup(p, BPX, KS / 2);
+    constexpr int SLOTS = HaloSlots<KS, BPX, conv_f32_npos(KS, BPX)>::P2 * conv_f32_npos(KS, BPX);
+    if (IMG > SLOTS) {
+        rfn_set_error("conv2d: map %dx%d needs an LDS image of %d slots (> %d supported)", p.H, p.W, IMG, SLOTS);
         return -7;
     }
     p.w_lds_off = ((KC * IMG + 2 * BCO + 3) / 4) * 4;
-    size_t lds = ((size_t)p.w_lds_off + (size_t)(KC / 8) * KS * KS * 2 * BCO * 4) * 4;
-    auto kern = conv_mfma_kernel<KS, WCO, WPX, TCO, TPX, KC>;
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    dim3 grid(p.n_wtiles * p.n_htiles * p.n_ftiles, ceil_div(p.Cout, BCO));
-    // Split K over gridDim.z when the (pixel, cout) grid alone cannot fill 256 CUs (ConvLSTM: 128 pixels x 800
-    // couts x K = 6408).  Needs a linear epilogue, dense zero-initialisable outputs and no accumulate flag.
-    p.ksplit = 1;
-    const int wgs = grid.x * grid.y;
-    const int nchunks = (p.Cin8 * 8 + KC - 1) / KC;
-    const int HW = p.H * p.W;
-    const bool dense = p.out1_ns == (long)p.cout_split * HW &&
-                       (p.cout_split == p.Cout || p.out2_ns == (long)(p.Cout - p.cout_split) * HW);
-    if (wgs < 128 && nchunks >= 8 && p.ep_mode != 1 && !p.acc1 && !p.acc2 && dense) {
-        int ks_ = 512 / wgs;
-        if (ks_ > nchunks / 2) ks_ = nchunks / 2;
-        if (ks_ > 1) {
-            p.ksplit = ks_;
-            p.ws_stride = (long)p.N * p.Cout * HW;
-            p.ws = rfn_workspace(s, (size_t)ks_ * (size_t)p.ws_stride);
-            if (!p.ws) return -8;
-        }
-    }
-    grid.z = p.ksplit;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-    if (p.ksplit > 1) splitk_reduce(p, s);   // slices added in order: deterministic
-    return 0;
+    const size_t lds = ((size_t)p.w_lds_off + (size_t)(KC / 8) * KS * KS * 2 * BCO * 4) * 4;
+    return conv_tile_launch(conv_mfma_kernel<KS, WCO, WPX, TCO, TPX, KC>, p, BCO, (p.Cin8 * 8 + KC - 1) / KC, lds, s);
 }
 
 // ---- kernel choice: choose_conv_f32 maps a shape to a route (and launches nothing), rfn_conv2d_fwd_f32 switches over
@@ -361,23 +263,13 @@ extern "C" int rfn_conv2d_fwd_f32(const float* in1, long in1_ns, int C1, const f
                                   const float* wpk, float* out1, long out1_ns, float* out2, long out2_ns, int Cout,
                                   int cout_split, int acc1, int acc2, int N, int H, int W, int ks, int ep_mode,
                                   const float* p0, const float* p1, int act, rfn_stream_t stream) {
-    RFN_CHECK_ARG(in1 && wpk && out1 && C1 > 0 && C2 >= 0 && Cout > 0 && N >= 0 && H > 0 && W > 0, -1);
-    RFN_CHECK_ARG(ks == 1 || ks == 3, -2);
-    RFN_CHECK_ARG(C2 == 0 || in2, -3);
-    RFN_CHECK_ARG(cout_split >= 0 && cout_split <= Cout && (cout_split == Cout || out2), -4);
-    RFN_CHECK_ARG(ep_mode >= 0 && ep_mode <= 3 && (ep_mode == 0 || p0) && ((ep_mode != 1 && ep_mode != 2) || p1), -5);
-    RFN_CHECK_ARG(((uintptr_t)wpk & 15) == 0, -6);
-    if (N == 0) return 0;
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.in1 = in1; p.in2 = in2; p.in1_ns = in1_ns; p.in2_ns = in2_ns; p.C1 = C1; p.C2 = C2;
-    p.wpk = wpk; p.out1 = out1; p.out2 = out2; p.out1_ns = out1_ns; p.out2_ns = out2_ns;
-    p.Cout = Cout; p.cout_split = cout_split; p.acc1 = acc1; p.acc2 = acc2;
-    p.N = N; p.H = H; p.W = W;
+    int rc = conv_fwd_params(p, __func__, in1, in1_ns, C1, in2, in2_ns, C2, wpk, out1, out1_ns, out2, out2_ns, Cout,
+                             cout_split, acc1, acc2, N, H, W, ks, ep_mode, p0, p1, act);
+    if (rc || N == 0) return rc;
     packed_dims(Cout, C1 + C2, &p.CoutP, &p.Cin8);
-    p.ep_mode = ep_mode; p.act = act; p.p0 = p0; p.p1 = p1;
     hipStream_t s = (hipStream_t)stream;
-    int rc = -9;
+    rc = -9;
     switch (choose_conv_f32(ks, Cout, N, H, W)) {
         case F3_COUT32:  rc = launch_conv<3, 1, 4, 1, 2, 8>(p, s); break;
         case F3_COUT64:  rc = launch_conv<3, 1, 4, 2, 1, 8>(p, s); break;
@@ -561,14 +453,8 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(const WgradParams p) {
 template <int KS, int WCO, int WCI, int TCO, int TCI, int BPX>
 static void launch_wgrad_bpx(WgradParams& p, hipStream_t s) {
     constexpr int BCO = 32 * TCO * WCO, BCI = 32 * TCI * WCI, PAD = KS / 2;
-    tile_geometry(p.H, p.W, BPX, &p.TWp, &p.TH, &p.TF);
-    p.tw_shift = ilog2(p.TWp);
-    p.th_shift = ilog2(p.TH);
-    p.n_wtiles = ceil_div(p.W, p.TWp);
-    p.n_htiles = ceil_div(p.H, p.TH);
-    p.n_ftiles = ceil_div(p.N, p.TF);
+    const int IMG = conv_tile_setup(p, BPX, PAD);
     p.n_pix_tiles = p.n_wtiles * p.n_htiles * p.n_ftiles;
-    int IMG = p.TF * (p.TH + 2 * PAD) * (p.TWp + 2 * PAD);
     p.P2 = next_pow2(IMG) < 256 ? next_pow2(IMG) : 256;
     p.P2_shift = ilog2(p.P2);
     size_t lds = ((size_t)BCO * (BPX + 1) + (size_t)BCI * (IMG | 1)) * 4;

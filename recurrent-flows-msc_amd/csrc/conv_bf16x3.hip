@@ -7,15 +7,14 @@
 // bits-per-dim error against an fp64 reference is ~1e-5 relative — ten times the plain fp32 error and a tenth of the
 // 1e-4 budget — for 3/16 of the fp32-MFMA cycles.
 //
-// Same GEMM orientation, pixel tiling, halo staging, descriptors, register prefetch, split-K and epilogue as conv.hip
-// (D[cout][pixel], C/D register layout is dtype independent).  What differs is the LDS image: an MFMA operand lane
-// needs 8 consecutive k (channels) of one row/column in one 16-byte register quad, so activations are stored as
-// [plane hi|lo][8-channel group][slot][8 x bf16] and weights (pre-split on the device by the pack kernel) as
-// [iteration][plane][k-group][cout][8 x bf16]; both fragments are single ds_read_b128.
+// Same GEMM orientation, pixel tiling, halo staging, descriptors, register prefetch, split-K and epilogue as conv.hip,
+// shared through conv_common.h (D[cout][pixel], C/D register layout is dtype independent).  What differs is the LDS
+// image: an MFMA operand lane needs 8 consecutive k (channels) of one row/column in one 16-byte register quad, so
+// activations are stored as [plane hi|lo][8-channel group][slot][8 x bf16] and weights (pre-split on the device by the
+// pack kernel) as [iteration][plane][k-group][cout][8 x bf16]; both fragments are single ds_read_b128.
 #include "conv_common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 static inline void packed_dims_b3(int Cout_l, int Cin_l, int* CoutP, int* Cin16) {
     *CoutP = ((Cout_l + 255) / 256) * 256;
@@ -78,12 +77,10 @@ __global__ void pack_weights_table_b3_kernel(const PackTable t) {
                 else
                     v = d.w[((long)(co % d.Cout) * d.Cin + ci) * T_src + co / d.Cout];
             }
-            const __bf16 h = (__bf16)v;
-            const float r1 = v - (float)h;
-            const __bf16 m = (__bf16)r1;
-            hi[j] = h;
-            lo[j] = m;
-            l3[j] = (__bf16)(r1 - (float)m);
+            const Bf16Split sp = split_bf16<3>(v);
+            hi[j] = sp.hi;
+            lo[j] = sp.mid;
+            l3[j] = sp.lo;
         }
         const long base = ((long)(c16 * T + tap) * NPL) * 2 * CoutP;
         wpk[base + (long)(0 * 2 + g) * CoutP + co] = hi;
@@ -131,6 +128,12 @@ extern "C" int rfn_pack_conv_weight_bf16x6(const float* w, float* wpk, int Cout,
     return rfn_pack_conv_weights_hostdescs_bf16x3(&d, 1, stream);
 }
 
+// Image slots per staging thread (HaloSlots): a slot holds eight floats per channel group here (one in conv.hip), so
+// the 64-pixel 3x3 tile stages a single slot -- its image has at most 256 slots down to 2x2 maps (16 frames x 16);
+// smaller maps are refused (-7) and belong to the small-map kernels.  conv_f32_npos (conv.hip) keeps 2 below 128
+// pixels; the difference is historical.
+static constexpr int conv_b3_npos(int KS, int BPX) { return KS == 1 ? 1 : (BPX >= 256 ? 4 : (BPX >= 128 ? 2 : 1)); }
+
 // NPL = 2: two bf16 pieces per operand, three products (bf16x3); NPL = 3: three pieces, six products ("bf16x6", 24
 // significant bits: the fp32-grade arithmetic of the forward convolutions at the levels the fused kernel does not take)
 template <int KS, int WCO, int WPX, int TCO, int TPX, int KC, int NPL = 2>
@@ -147,14 +150,8 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
     const int HW = p.H * p.W;
     const int Cin = p.C1 + p.C2;
 
-    int pt = blockIdx.x;
-    const int wt = pt % p.n_wtiles;
-    pt /= p.n_wtiles;
-    const int ht = pt % p.n_htiles;
-    const int ft = pt / p.n_htiles;
-    const int x0 = wt * p.TWp, y0 = ht * p.TH, f0 = ft * p.TF;
-    const int RW = p.TWp + 2 * PAD, RH = p.TH + 2 * PAD;
-    const int FRM = RH * RW, IMG = p.TF * FRM;
+    const ConvTile tl = conv_tile_origin<PAD>(p);
+    const int RW = tl.RW, IMG = tl.IMG;
     const int co_base = blockIdx.y * BCO + wco * (32 * TCO);
 
     // LDS: Bs[plane][NG][IMG] units | Ws[NS*T][plane][2][BCO] units | ep[2][BCO] floats
@@ -166,14 +163,8 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
     bool pvalid[TPX];
 #pragma unroll
     for (int t = 0; t < TPX; ++t) {
-        const int q = (wpx * TPX + t) * 32 + l31;
-        const int col = q & (p.TWp - 1);
-        const int row = (q >> p.tw_shift) & (p.TH - 1);
-        const int f = q >> (p.tw_shift + p.th_shift);
-        lds_off[t] = f * FRM + row * RW + col;
-        pvalid[t] = (x0 + col < p.W) && (y0 + row < p.H) && (f0 + f < p.N);
-        pn[t] = f0 + f;
-        ppix[t] = (y0 + row) * p.W + x0 + col;
+        const ConvPixel px = conv_pixel(p, tl, (wpx * TPX + t) * 32 + l31);
+        lds_off[t] = px.lds_off, pn[t] = px.n, ppix[t] = px.pix, pvalid[t] = px.valid;
     }
 
     f32x16 acc[TCO][TPX];
@@ -190,30 +181,18 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
         for (int r = 0; r < 16; ++r) accx[0][r] = accx[1][r] = 0.f;
     }
 
-    // ---- activation staging descriptors (as in conv.hip): thread -> image slot(s), 8-channel group phase
-    constexpr int NPOS = (KS == 1) ? 1 : (BPX >= 256 ? 4 : (BPX >= 128 ? 2 : 1));
-    constexpr int GROUPS = (KS == 1 && BPX < 256) ? (BPX >= 64 ? 256 / BPX : 4) : 1;
-    constexpr int P2 = 256 / GROUPS;
-    constexpr int NGT = (NG + GROUPS - 1) / GROUPS;  // channel groups per thread
+    // ---- activations: eight channels (one group) per slot in registers, split into planes on the way into LDS
+    constexpr int NPOS = conv_b3_npos(KS, BPX);
+    typedef HaloSlots<KS, BPX, NPOS> Halo;
+    constexpr int GROUPS = Halo::GROUPS, P2 = Halo::P2;
     const int slot = tid & (P2 - 1);
-    const int phase = __builtin_amdgcn_readfirstlane(tid / P2);
+    const int phase = __builtin_amdgcn_readfirstlane(tid / P2);  // wave-uniform: keeps channel math scalar
     int soff1[NPOS], soff2[NPOS];
     bool sok[NPOS], sin[NPOS];
-#pragma unroll
-    for (int j = 0; j < NPOS; ++j) {
-        const int r = slot + P2 * j;
-        sin[j] = r < IMG;
-        const int f = r / FRM;
-        const int rr = r - f * FRM;
-        const int yy = rr / RW;
-        const int xx = rr - yy * RW;
-        const int gy = y0 + yy - PAD, gx = x0 + xx - PAD;
-        sok[j] = sin[j] && (f0 + f < p.N) && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
-        soff1[j] = sok[j] ? (int)(f * p.in1_ns) + gy * p.W + gx : 0;
-        soff2[j] = sok[j] ? (int)(f * p.in2_ns) + gy * p.W + gx : 0;
-    }
-    const float* in1b = p.in1 + (long)f0 * p.in1_ns;
-    const float* in2b = p.in2 ? p.in2 + (long)f0 * p.in2_ns : p.in1;
+    Halo::fill(p, tl, slot, soff1, soff2, sok, sin);
+    const float* in1b = p.in1 + (long)tl.f0 * p.in1_ns;
+    const float* in2b = p.in2 ? p.in2 + (long)tl.f0 * p.in2_ns : p.in1;
+    constexpr int NGT = (NG + GROUPS - 1) / GROUPS;  // channel groups per thread
     float stg[NGT][NPOS][8];
     auto prefetch = [&](int chunk) {
 #pragma unroll
@@ -227,14 +206,12 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
                 const bool first = chc < p.C1;
                 const float* src = first ? in1b + (long)chc * HW : in2b + (long)(chc - p.C1) * HW;
 #pragma unroll
-                for (int j = 0; j < NPOS; ++j) {
-                    const float v = src[first ? soff1[j] : soff2[j]];
-                    stg[i][j][c] = (sok[j] && chv) ? v : 0.f;
-                }
+                for (int j = 0; j < NPOS; ++j)
+                    stg[i][j][c] = Halo::load(src, first ? soff1[j] : soff2[j], sok[j] && chv);
             }
         }
     };
-    auto commit = [&]() {  // split to (hi, lo) and store the two 16-byte units
+    auto commit = [&]() {  // split to (hi, mid[, lo]) and store the 16-byte units
 #pragma unroll
         for (int i = 0; i < NGT; ++i) {
             const int gi = phase + GROUPS * i;
@@ -245,13 +222,10 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
                         bf16x8 hi, lo, l3;
 #pragma unroll
                         for (int c = 0; c < 8; ++c) {
-                            const float v = stg[i][j][c];
-                            const __bf16 h = (__bf16)v;
-                            const float r1 = v - (float)h;
-                            const __bf16 m = (__bf16)r1;
-                            hi[c] = h;
-                            lo[c] = m;
-                            if (NPL == 3) l3[c] = (__bf16)(r1 - (float)m);
+                            const Bf16Split sp = split_bf16<NPL>(stg[i][j][c]);
+                            hi[c] = sp.hi;
+                            lo[c] = sp.mid;
+                            if (NPL == 3) l3[c] = sp.lo;
                         }
                         const int r = slot + P2 * j;
                         Bs[(0 * NG + gi) * IMG + r] = hi;
@@ -263,63 +237,27 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
         }
     };
 
-    // ---- weight tile of a chunk: verbatim copy of NS*T*4 runs of BCO units from the packed buffer
+    // ---- weight tile of a chunk: NS*T iterations of NPL*2 runs (plane, k-group) of BCO units
     const int total_it = p.Cin8 * T;  // Cin8 holds Cin16 for this kernel
-    const u32x4* wp4 = reinterpret_cast<const u32x4*>(p.wpk);
-    constexpr int WRUNS = NS * T * NPL * 2;
-    constexpr int WPT = (WRUNS * BCO + 255) / 256;
+    WeightTileCopy<NPL * 2, NS * T, BCO> wtile;
     u32x4* Ws4 = reinterpret_cast<u32x4*>(Ws);
-    const long wblk = (long)blockIdx.y * BCO;
-    u32x4 wstg[WPT];
-    auto wprefetch = [&](int chunk) {
-        const int it0 = chunk * NS * T;
-#pragma unroll
-        for (int j = 0; j < WPT; ++j) {
-            const int e = tid + 256 * j;
-            const int run = e / BCO, col = e % BCO;
-            const int itg = it0 + run / (NPL * 2);
-            const bool ok = (WRUNS * BCO % 256 == 0 || e < WRUNS * BCO) && itg < total_it;
-            const u32x4 v = wp4[((long)(ok ? itg : 0) * (NPL * 2) + run % (NPL * 2)) * p.CoutP + wblk + col];
-            wstg[j] = ok ? v : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    auto wcommit = [&]() {
-#pragma unroll
-        for (int j = 0; j < WPT; ++j) {
-            const int e = tid + 256 * j;
-            if (WRUNS * BCO % 256 == 0 || e < WRUNS * BCO) Ws4[e] = wstg[j];
-        }
-    };
+    auto wprefetch = [&](int chunk) { wtile.prefetch(p, chunk, total_it, tid); };
+    auto wcommit = [&]() { wtile.commit(Ws4, tid); };
 
-    if (p.ep_mode != 0) {
-        for (int c = tid; c < BCO; c += 256) {
-            const int co = blockIdx.y * BCO + c;
-            float e0 = 0.f, e1 = 1.f;
-            if (co < p.Cout) {
-                if (p.ep_mode != 4) e0 = p.p0[co];
-                if (p.ep_mode == 1 || p.ep_mode == 4) e1 = expf(p.p1[co]);
-                if (p.ep_mode == 2) e1 = expf(3.f * p.p1[co]);
-            }
-            ep[c] = e0;
-            ep[BCO + c] = e1;
-        }
-    }
+    load_epilogue_params<BCO>(p, ep);
 
-    const int nchunks_all = (p.Cin8 * 16 + KC - 1) / KC;
-    const int cps = (nchunks_all + p.ksplit - 1) / p.ksplit;
-    const int chunk0 = blockIdx.z * cps;
-    const int nchunks = chunk0 + cps < nchunks_all ? chunk0 + cps : nchunks_all;
-    if (chunk0 < nchunks) {
-        prefetch(chunk0);
-        wprefetch(chunk0);
+    const ChunkRange kr = chunk_range(p, 16, KC);
+    if (kr.begin < kr.end) {
+        prefetch(kr.begin);
+        wprefetch(kr.begin);
     }
     const bf16x8* wa = Ws + kk * BCO + wco * (32 * TCO) + l31;  // + ((itl*2 + plane)*2)*BCO + a*32
-    for (int chunk = chunk0; chunk < nchunks; ++chunk) {
+    for (int chunk = kr.begin; chunk < kr.end; ++chunk) {
         __syncthreads();
         commit();
         wcommit();
         __syncthreads();
-        if (chunk + 1 < nchunks) {
+        if (chunk + 1 < kr.end) {
             prefetch(chunk + 1);
             wprefetch(chunk + 1);
         }
@@ -388,8 +326,7 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
     if (p.ep_mode == 4)
         for (int c = tid; c < 2 * BCO; c += 256) psum[c] = 0.f;
     __syncthreads();
-    conv_epilogue<TCO, TPX, BCO>(p, acc, ep, co_base, wco, kk, HW, pn, ppix, pvalid, blockIdx.x * WPX + wpx,
-                                 p.ep_mode == 4 ? psum : nullptr, true);
+    conv_epilogue<TCO, TPX, BCO>(p, acc, ep, co_base, wco, kk, HW, pn, ppix, pvalid, psum, true);
     if (p.ep_mode == 4) {
         __syncthreads();
         for (int c = tid; c < 2 * BCO; c += 256) {
@@ -401,44 +338,17 @@ __global__ __launch_bounds__(256) void conv_b3_kernel(const ConvParams p) {
 
 template <int KS, int WCO, int WPX, int TCO, int TPX, int KC, int NPL = 2>
 static int launch_conv_b3(ConvParams& p, hipStream_t s) {
-    constexpr int BCO = 32 * TCO * WCO, BPX = 32 * TPX * WPX, PAD = KS / 2;
-    tile_geometry(p.H, p.W, BPX, &p.TWp, &p.TH, &p.TF);
-    p.tw_shift = ilog2(p.TWp);
-    p.th_shift = ilog2(p.TH);
-    p.n_wtiles = ceil_div(p.W, p.TWp);
-    p.n_htiles = ceil_div(p.H, p.TH);
-    p.n_ftiles = ceil_div(p.N, p.TF);
-    const int IMG = p.TF * (p.TH + 2 * PAD) * (p.TWp + 2 * PAD);
-    constexpr int NPOS = (KS == 1) ? 1 : (BPX >= 256 ? 4 : (BPX >= 128 ? 2 : 1));
-    constexpr int P2 = (KS == 1 && BPX < 256) ? (BPX >= 64 ? BPX : 64) : 256;
-    if (IMG > P2 * NPOS) {
-        rfn_set_error("conv2d(bf16x3): map %dx%d needs %d LDS slots (> %d supported)", p.H, p.W, IMG, P2 * NPOS);
+    constexpr int BCO = 32 * TCO * WCO, BPX = 32 * TPX * WPX;
+    const int IMG = conv_tile_setup(p, BPX, KS / 2);
+    constexpr int SLOTS = HaloSlots<KS, BPX, conv_b3_npos(KS, BPX)>::P2 * conv_b3_npos(KS, BPX);
+    if (IMG > SLOTS) {
+        rfn_set_error("conv2d(bf16x3): map %dx%d needs %d LDS slots (> %d supported)", p.H, p.W, IMG, SLOTS);
         return -7;
     }
-    size_t lds = (size_t)NPL * (KC / 8) * IMG * 16 + (size_t)(KC / 16) * KS * KS * NPL * 2 * BCO * 16 + 4 * BCO * 4;
-    auto kern = conv_b3_kernel<KS, WCO, WPX, TCO, TPX, KC, NPL>;
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    dim3 grid(p.n_wtiles * p.n_htiles * p.n_ftiles, ceil_div(p.Cout, BCO));
-    p.ksplit = 1;
-    const int wgs = grid.x * grid.y;
+    const size_t lds =
+        (size_t)NPL * (KC / 8) * IMG * 16 + (size_t)(KC / 16) * KS * KS * NPL * 2 * BCO * 16 + 4 * BCO * 4;
     const int nchunks = (p.Cin8 * 16 + KC - 1) / KC;
-    const int HW = p.H * p.W;
-    const bool dense = p.out1_ns == (long)p.cout_split * HW &&
-                       (p.cout_split == p.Cout || p.out2_ns == (long)(p.Cout - p.cout_split) * HW);
-    if (wgs < 128 && nchunks >= 8 && p.ep_mode != 1 && p.ep_mode != 4 && !p.acc1 && !p.acc2 && dense) {
-        int ks_ = 512 / wgs;
-        if (ks_ > nchunks / 2) ks_ = nchunks / 2;
-        if (ks_ > 1) {
-            p.ksplit = ks_;
-            p.ws_stride = (long)p.N * p.Cout * HW;
-            p.ws = rfn_workspace(s, (size_t)ks_ * (size_t)p.ws_stride);
-            if (!p.ws) return -8;
-        }
-    }
-    grid.z = p.ksplit;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p);
-    if (p.ksplit > 1) splitk_reduce(p, s);   // slices added in order: deterministic
-    return 0;
+    return conv_tile_launch(conv_b3_kernel<KS, WCO, WPX, TCO, TPX, KC, NPL>, p, BCO, nchunks, lds, s);
 }
 
 // ------------------------------------------------------------------------------------------------ kernel choice
@@ -543,23 +453,13 @@ static int conv2d_fwd_split(const float* in1, long in1_ns, int C1, const float* 
                             const float* wpk, float* out1, long out1_ns, float* out2, long out2_ns, int Cout,
                             int cout_split, int acc1, int acc2, int N, int H, int W, int ks, int ep_mode,
                             const float* p0, const float* p1, int act, int npl, rfn_stream_t stream) {
-    RFN_CHECK_ARG(in1 && wpk && out1 && C1 > 0 && C2 >= 0 && Cout > 0 && N >= 0 && H > 0 && W > 0, -1);
-    RFN_CHECK_ARG(ks == 1 || ks == 3, -2);
-    RFN_CHECK_ARG(C2 == 0 || in2, -3);
-    RFN_CHECK_ARG(cout_split >= 0 && cout_split <= Cout && (cout_split == Cout || out2), -4);
-    RFN_CHECK_ARG(ep_mode >= 0 && ep_mode <= 3 && (ep_mode == 0 || p0) && ((ep_mode != 1 && ep_mode != 2) || p1), -5);
-    RFN_CHECK_ARG(((uintptr_t)wpk & 15) == 0, -6);
-    if (N == 0) return 0;
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    p.in1 = in1; p.in2 = in2; p.in1_ns = in1_ns; p.in2_ns = in2_ns; p.C1 = C1; p.C2 = C2;
-    p.wpk = wpk; p.out1 = out1; p.out2 = out2; p.out1_ns = out1_ns; p.out2_ns = out2_ns;
-    p.Cout = Cout; p.cout_split = cout_split; p.acc1 = acc1; p.acc2 = acc2;
-    p.N = N; p.H = H; p.W = W;
+    int rc = conv_fwd_params(p, __func__, in1, in1_ns, C1, in2, in2_ns, C2, wpk, out1, out1_ns, out2, out2_ns, Cout,
+                             cout_split, acc1, acc2, N, H, W, ks, ep_mode, p0, p1, act);
+    if (rc || N == 0) return rc;
     packed_dims_b3(Cout, C1 + C2, &p.CoutP, &p.Cin8);
-    p.ep_mode = ep_mode; p.act = act; p.p0 = p0; p.p1 = p1;
     p.npl = npl;
-    int rc = dispatch_conv_b3(p, ks, (hipStream_t)stream);
+    rc = dispatch_conv_b3(p, ks, (hipStream_t)stream);
     if (rc) return rc;
     RFN_LAUNCH_CHECK();
     return 0;
@@ -622,19 +522,7 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p, con
             wl[s] = ok ? l : z;
         }
     }
-    if (p.ep_mode != 0) {
-        for (int c = tid; c < 256; c += 512) {
-            const int co = blockIdx.y * 256 + c;
-            float e0 = 0.f, e1 = 1.f;
-            if (co < p.Cout) {
-                if (p.ep_mode != 4) e0 = p.p0[co];
-                if (p.ep_mode == 1 || p.ep_mode == 4) e1 = expf(p.p1[co]);
-                if (p.ep_mode == 2) e1 = expf(3.f * p.p1[co]);
-            }
-            ep[c] = e0;
-            ep[256 + c] = e1;
-        }
-    }
+    load_epilogue_params<256, 512>(p, ep);
 
     // Staging role: pixel l31 of the tile, channel units 2*wave + kk + 16*i (i < NG/16).  Loads go through one buffer
     // descriptor: a per-lane 32-bit byte offset (frame, pixel, kk) plus a scalar channel offset, so the loads of a tile
@@ -678,10 +566,9 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p, con
             bf16x8 hi, lo;
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
-                const float v = (sval && g * 8 + c < Cin) ? stg[i][c] : 0.f;
-                const __bf16 h = (__bf16)v;
-                hi[c] = h;
-                lo[c] = (__bf16)(v - (float)h);
+                const Bf16Split sp = split_bf16<2>((sval && g * 8 + c < Cin) ? stg[i][c] : 0.f);
+                hi[c] = sp.hi;
+                lo[c] = sp.mid;
             }
             dst[(0 * NG + g) * TP] = hi;
             dst[(1 * NG + g) * TP] = lo;
@@ -712,7 +599,7 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p, con
         const long q = (long)tile * TP + l31;
         pvalid[0] = q < total;
         split_q(pvalid[0] ? q : 0, pn[0], ppix[0]);
-        conv_epilogue<1, 1, 256>(p, acc, ep, co_base, wave, kk, HW, pn, ppix, pvalid, tile, psum);
+        conv_epilogue<1, 1, 256>(p, acc, ep, co_base, wave, kk, HW, pn, ppix, pvalid, psum, false);
     }
     if (p.ep_mode == 4) {  // the workgroup's partial sums: one atomic per (sum, channel)
         __syncthreads();
@@ -766,19 +653,7 @@ __global__ __launch_bounds__(512) void conv3x3_ws_kernel(const ConvParams p, con
             wl[s] = ok ? l : z;
         }
     }
-    if (p.ep_mode != 0) {
-        for (int c = tid; c < 256; c += 512) {
-            const int co = blockIdx.y * 256 + c;
-            float e0 = 0.f, e1 = 1.f;
-            if (co < p.Cout) {
-                if (p.ep_mode != 4) e0 = p.p0[co];
-                if (p.ep_mode == 1 || p.ep_mode == 4) e1 = expf(p.p1[co]);
-                if (p.ep_mode == 2) e1 = expf(3.f * p.p1[co]);
-            }
-            ep[c] = e0;
-            ep[256 + c] = e1;
-        }
-    }
+    load_epilogue_params<256, 512>(p, ep);
 
     // staging role: one (unit, image position) pair per thread (NG * IMG <= 512)
     const bool srole = tid < NG * IMG;
@@ -812,10 +687,9 @@ __global__ __launch_bounds__(512) void conv3x3_ws_kernel(const ConvParams p, con
         bf16x8 hi, lo;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            const float v = (sval && sg * 8 + c < Cin) ? stg[c] : 0.f;
-            const __bf16 h = (__bf16)v;
-            hi[c] = h;
-            lo[c] = (__bf16)(v - (float)h);
+            const Bf16Split sp = split_bf16<2>((sval && sg * 8 + c < Cin) ? stg[c] : 0.f);
+            hi[c] = sp.hi;
+            lo[c] = sp.mid;
         }
         bf16x8* dst = Bs + (long)buf * 2 * NG * IMGP + spos;
         dst[(0 * NG + sg) * IMGP] = hi;
@@ -870,7 +744,7 @@ __global__ __launch_bounds__(512) void conv3x3_ws_kernel(const ConvParams p, con
             ppix[t] = (y0 + prow[t]) * p.W + x0 + pcol[t];
             pvalid[t] = true;
         }
-        conv_epilogue<1, PT, 256, FASTEP>(p, acc, ep, co_base, wave, kk, HW, pn, ppix, pvalid, tile, psum);
+        conv_epilogue<1, PT, 256, FASTEP>(p, acc, ep, co_base, wave, kk, HW, pn, ppix, pvalid, psum, false);
     }
     if (!FASTEP && p.ep_mode == 4) {  // the workgroup's partial sums: one atomic per (sum, channel)
         __syncthreads();

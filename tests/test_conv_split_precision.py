@@ -12,6 +12,7 @@
      K=72   (3+5 -> 40, 6x6)          1.7e-7 / 9.3e-8 / 4.1e-6   ratio 42
      K=144  (16->16, 64x64)           3.2e-7 / 1.4e-7 / 3.6e-6   ratio 25
      K=144  (16->64, 64x64, 9 frames) 3.6e-7 / 3.2e-7 / 3.9e-6   ratio 10.7 (the smallest)
+     K=216  (24->96, 32x32, 36 frames) 2.8e-7 / 2.8e-7 / 2.8e-6
      K=256  (1x1 256->288, 4x4)       2.7e-7 / 1.9e-7 / 1.8e-6
      K=2304 (split-K 256->512, 4x4)   4.1e-8 / 3.4e-8 / 8.0e-7
      K=4608 (split-K 300+212->96)     2.7e-8 / 2.1e-8 / 6.2e-7
@@ -101,6 +102,7 @@ FWD_CASES = [
     (800, 256, 0, 288, 4, 4, 1),    # level-3 tap-expanded Conv2dZeros: 9 * 32 outputs, second 256 block mostly padding
     (4, 256, 0, 512, 4, 4, 3),      # split-K (8 workgroups, 16 chunks), K = 2304
     (3, 300, 212, 96, 4, 4, 3),     # split-K with two sources, K = 4608
+    (36, 24, 0, 96, 32, 32, 3),     # many pixels (36864), more than 64 outputs: the fp32 kernel's 128 co x 128 px tile
 ]
 
 
@@ -111,6 +113,17 @@ def _x6_label(K, case):
 
 def test_forward_cases_reach_every_bf16x6_instantiation(K):
     assert {_x6_label(K, c) for c in FWD_CASES} == X6_KERNELS
+
+
+# the nine production routes of choose_conv_f32 (csrc/conv.hip), F3_COUT32 to F1_256x64; the RFN_CONV_VARIANT ones are not
+F32_KERNELS = {"conv_mfma_kernel<3,1,4,1,2,8>", "conv_mfma_kernel<3,1,4,2,1,8>", "conv_mfma_kernel<3,4,1,1,1,8>",
+               "conv_mfma_kernel<3,2,2,2,2,8>", "conv_mfma_kernel<1,1,4,1,2,32>", "conv_mfma_kernel<1,1,4,2,1,32>",
+               "conv_mfma_kernel<1,4,1,1,1,32>", "conv_mfma_kernel<1,2,2,2,2,32>", "conv_mfma_kernel<1,4,1,2,2,32>"}
+
+
+def test_forward_cases_reach_every_fp32_route(K):
+    labels = {K.kernel_label("rfn_conv2d_kernel_label_f32", ks, Cout, N, H, W) for N, _, _, Cout, H, W, ks in FWD_CASES}
+    assert labels == F32_KERNELS
 
 
 def _inputs(case, seed):
