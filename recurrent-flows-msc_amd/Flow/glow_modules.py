@@ -238,6 +238,7 @@ class AffineCoupling(nn.Module):
         return s
 
     def nn_params(self):
+        """the fields w1 .. scale_shift of rfn_hip.ops.StepParams, in its order (the Glow nodes take them positionally)"""
         n0, n2, n4 = self.net[0], self.net[2], self.net[4]
         sc = getattr(self, "scale", None)
         sh = getattr(self, "scale_shift", None)

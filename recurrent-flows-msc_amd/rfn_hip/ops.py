@@ -7,6 +7,7 @@ time-batches B*(T-1) frames into one call).
 import collections
 import ctypes
 import functools
+import itertools
 
 import torch
 
@@ -123,18 +124,20 @@ def _zeros(arena, *shape, device=None):
     return arena.take(*shape) if arena is not None else torch.zeros(shape, device=device, dtype=torch.float32)
 
 
-def actnorm_invconv_bwd(x, bias, logs, Wm, gz, arena=None):
+def actnorm_invconv_bwd(x, bias, logs, Wm, gz, arena=None, acc=None, glogdet=None):
+    """returns (gx, gW, gb, gl).  `acc` (optional): zero-filled (gW, gb, gl) of the caller's to accumulate into.
+    `glogdet` [N] (optional): the gradient of a per-frame log-det that includes this ActNorm's term H*W * sum logs, which
+    the kernel then adds to gl (rfn_actnorm_invconv_bwd_ld_f32: the first step of a level node)."""
     N, C = x.shape[0], x.shape[1]
     xp, xns = L.frames(x, "x")
     gzp, gzns = L.frames(gz, "gz")
     gx = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     gxp, gxns = L.frames(gx, "gx")
-    gW = _zeros(arena, C, C, device=x.device)
-    gb = _zeros(arena, C, device=x.device)
-    gl = _zeros(arena, C, device=x.device)
+    gW, gb, gl = acc if acc is not None else [_zeros(arena, *s, device=x.device) for s in ((C, C), (C,), (C,))]
     bias, logs, Wm = bias.contiguous(), logs.contiguous(), Wm.contiguous()  # held until the launch is enqueued
-    L.call("rfn_actnorm_invconv_bwd_f32", xp, _l(xns), L.dev(bias), L.dev(logs), L.dev(Wm), gzp, _l(gzns), gxp, _l(gxns), L.dev(gW), L.dev(gb), L.dev(gl), _i(N), _i(C),
-           _i(_hw(x)), meta=_shell("actnorm_invconv_bwd", x, 3))
+    entry, ld = ("rfn_actnorm_invconv_bwd_f32", ()) if glogdet is None else ("rfn_actnorm_invconv_bwd_ld_f32", (L.dev(glogdet),))
+    L.call(entry, xp, _l(xns), L.dev(bias), L.dev(logs), L.dev(Wm), gzp, _l(gzns), gxp, _l(gxns), L.dev(gW), L.dev(gb),
+           L.dev(gl), *ld, _i(N), _i(C), _i(_hw(x)), meta=_shell("actnorm_invconv_bwd", x, 3))
     return gx, gW, gb, gl
 
 
@@ -379,9 +382,14 @@ def coupling_po_bwd(go, wpk_bwd, n1l, n2l, masks, act):
     return ga2, ga1, part
 
 
+# what rfn_coupling_po_bwd_finish reads of one net, in the order of its arguments, and `step`: the step of a level node
+# whose weight gradients gw1 / gw2 the ticket waits for (_net_bwd leaves them None when they are computed later)
+FinishTicket = collections.namedtuple("FinishTicket", "part w1 gw1 n1b w2 gw2 n2b out step", defaults=(None,))
+
+
 def coupling_po_bwd_finish(tickets):
-    """ActNorm gradients of the hidden layers of up to 16 nets per launch (rfn_coupling_po_bwd_finish); a ticket is
-    (part, w1, gw1, n1b, w2, gw2, n2b, out[4,256]); `out` is written."""
+    """ActNorm gradients of the hidden layers of up to 16 nets per launch (rfn_coupling_po_bwd_finish); a ticket is a
+    FinishTicket or any sequence (part, w1, gw1, n1b, w2, gw2, n2b, out[4,256]); `out` is written."""
     for i0 in range(0, len(tickets), 16):
         tk = tickets[i0:i0 + 16]
         cols = [L.ptr_array([t[j].detach() for t in tk], "finish") for j in range(8)]
@@ -960,60 +968,78 @@ def coupling_route(N, C, Cc, Hd, H, W, k1, k2, k3, act, grad, reverse=False):
                          bool(back and Hd % 64 == 0 and wgrad_b3(H, W)), packs)
 
 
-def _step_route(x, cond, w1, w2, w3, act, grad, reverse=False):
-    (N, C, H, W), ks = x.shape, (int(w.shape[2]) for w in (w1, w2, w3))
-    return coupling_route(N, C, int(cond.shape[1]), int(w1.shape[0]), H, W, *ks, act, grad, reverse)
+# The parameters of one Glow step, in the order in which the three nodes' apply() takes them and their backward returns
+# the gradients: the step's ActNorm, then what AffineCoupling.nn_params() (Flow/glow_modules.py) returns -- conv1 with
+# its ActNorm, conv2 with its ActNorm, Conv2dZeros (weight, bias, logs), the realnvp clamp's scale and shift (or None).
+StepParams = collections.namedtuple("StepParams", "an_bias an_logs w1 n1b n1l w2 n2b n2l w3 b3 l3 scale scale_shift")
+STEP_NPARAM = len(StepParams._fields)
 
 
-def _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk):
-    """coupling network of one Glow step (glow_modules.py:232-238) on z's first channel half and `cond`, as `route`
+def _net_dims(p, cond):
+    """(Hd, Cc, k1, k2, k3): hidden width, condition channels and kernel sizes of the coupling net of the step `p`"""
+    return (int(p.w1.shape[0]), int(cond.shape[1]), *(int(w.shape[2]) for w in (p.w1, p.w2, p.w3)))
+
+
+def _step_route(x, cond, p, act, grad, reverse=False):
+    (N, C, H, W), (Hd, Cc, k1, k2, k3) = x.shape, _net_dims(p, cond)
+    return coupling_route(N, C, Cc, Hd, H, W, k1, k2, k3, act, grad, reverse)
+
+
+def _net_fwd(z, cond, p, act, route, pk):
+    """coupling network of one Glow step `p` (glow_modules.py:232-238) on z's first channel half and `cond`, as `route`
     says.  Returns (h1, h2, o, P, masks): either o (finished Conv2dZeros output) or P (its tap-expanded pre-gather form,
     fused kernel) is None; masks: the fused kernel's activation masks (or None).  `pk`: see _pack."""
     N, C, H, W = z.shape
-    Hd, fp = int(w1.shape[0]), route.fwd_prec
-    z1, cin2 = z[:, :C // 2], (cond if cond.shape[1] > 0 else None)
+    (Hd, Cc, k1, k2, _), fp = _net_dims(p, cond), route.fwd_prec
+    z1, cin2 = z[:, :C // 2], (cond if Cc > 0 else None)
     if route.fwd == "po":
         def stream():
-            plan = POPackPlan([(w1.detach(), w2.detach(), w3.detach())])
+            plan = POPackPlan([(p.w1.detach(), p.w2.detach(), p.w3.detach())])
             plan.run()
             return plan.bufs[0]
         # (the masks serve the backward stream only, which POPackPlan builds for at most 16 channels)
-        h1, h2, P, masks = coupling_po_fwd(z, cin2, _pack(pk, "po_fwd", stream), _f(n1b), _f(n1l), _f(n2b), _f(n2l), C, act,
-                                           want_masks=route.masks and pk.get("po_bwd") is not None)
+        h1, h2, P, masks = coupling_po_fwd(z, cin2, _pack(pk, "po_fwd", stream), _f(p.n1b), _f(p.n1l), _f(p.n2b),
+                                           _f(p.n2l), C, act, want_masks=route.masks and pk.get("po_bwd") is not None)
         return h1, h2, None, P, masks
     if "w2_fwd" not in route.packs:
         pk = {}   # (fp32 forward convs: a step's forward conv packs are split-precision ones)
     if route.conv1 == "dense":
-        h1 = smallmap_conv(z1, cin2, _pack(pk, "w1_dense_fwd", lambda: smallmap_pack(w1, H, W, False)), Hd, 1, _f(n1b),
-                           _f(n1l), act)
+        h1 = smallmap_conv(z1, cin2, _pack(pk, "w1_dense_fwd", lambda: smallmap_pack(p.w1, H, W, False)), Hd, 1,
+                           _f(p.n1b), _f(p.n1l), act)
     else:
-        h1 = conv2d_raw(z1, cin2, _pack(pk, "w1_fwd", lambda: pack_weight(w1, prec=fp)), Hd, int(w1.shape[2]), 1,
-                        _f(n1b), _f(n1l), act, prec=fp)
-    h2 = conv2d_raw(h1, None, _pack(pk, "w2_fwd", lambda: pack_weight(w2, prec=fp)), Hd, int(w2.shape[2]), 1, _f(n2b),
-                    _f(n2l), act, prec=fp)
+        h1 = conv2d_raw(z1, cin2, _pack(pk, "w1_fwd", lambda: pack_weight(p.w1, prec=fp)), Hd, k1, 1, _f(p.n1b),
+                        _f(p.n1l), act, prec=fp)
+    h2 = conv2d_raw(h1, None, _pack(pk, "w2_fwd", lambda: pack_weight(p.w2, prec=fp)), Hd, k2, 1, _f(p.n2b),
+                    _f(p.n2l), act, prec=fp)
     if route.conv3 == "dense":
-        o = smallmap_conv(h2, None, _pack(pk, "w3_dense_fwd", lambda: smallmap_pack(w3, H, W, False)), C, 2, _f(b3),
-                          _f(l3), 0)
+        o = smallmap_conv(h2, None, _pack(pk, "w3_dense_fwd", lambda: smallmap_pack(p.w3, H, W, False)), C, 2, _f(p.b3),
+                          _f(p.l3), 0)
     else:
         taps = route.conv3 == "taps"
-        w3p = _pack(pk, "w3_fwd", lambda: pack_weight(_tap_expanded(w3) if taps else w3, prec=fp))
-        o = zeros_conv_fwd(h2, w3, _f(b3), _f(l3), w3p, prec=fp, taps=taps)
+        w3p = _pack(pk, "w3_fwd", lambda: pack_weight(_tap_expanded(p.w3) if taps else p.w3, prec=fp))
+        o = zeros_conv_fwd(h2, p.w3, _f(p.b3), _f(p.l3), w3p, prec=fp, taps=taps)
     return h1, h2, o, None, None
 
 
-def _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act, route, pk, arena, gz, gcond, acc_cond,
-             defer=None, masks=None, fin=None):
-    """backward of the coupling network from `go` = gradient at conv3's output, as `route` says: returns the parameter
-    gradients (gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3); the data gradient of conv1 is ADDED to gz[:, :C/2] and written
-    (acc_cond: added) to gcond.  With `defer` (a dict of three lists) and route.defer_wgrad the weight gradients are NOT
-    computed: their operands are appended to defer["w1" | "w2" | "w3"] and None is returned in their place (grouped
-    launch by the caller).  The "po" chain reads `masks` (the fused forward kernel's) and no activation; it leaves the
-    four ActNorm gradients to rfn_coupling_po_bwd_finish, which needs the weight gradients: a ticket is appended to
-    `fin` (ticket[2] / [5] = gw1 / gw2 are filled in by the caller when deferred) or, without `fin`, finished here."""
+NetGrads = collections.namedtuple("NetGrads", "w1 n1b n1l w2 n2b n2l w3")   # of a coupling net, flat as the kernels write
+# the operands of a level's 3 K weight gradients, computed at the end K of one shape per launch: one list per operand,
+# indexed by step (conv1: z1, c2, gh1; conv2: h1, gh2; conv3: h2, go)
+WgradOperands = collections.namedtuple("WgradOperands", "z1 c2 gh1 h1 gh2 h2 go")
+
+
+def _net_bwd(go, out, cond, h1, h2, p, act, route, pk, arena, gz, gcond, acc_cond, defer=None, masks=None, fin=None,
+             step=None):
+    """backward of the coupling network of the step `p` from `go` = gradient at conv3's output, as `route` says: returns
+    the parameter gradients (NetGrads); the data gradient of conv1 is ADDED to gz[:, :C/2] and written (acc_cond: added)
+    to gcond.  With `defer` (a WgradOperands) the weight gradients are NOT computed: their operands are stored at
+    defer.*[step] and None is returned in their place (grouped launch by the caller).  The "po" chain reads `masks` (the
+    fused forward kernel's) and no activation; it leaves the four ActNorm gradients to rfn_coupling_po_bwd_finish, which
+    needs the weight gradients: a FinishTicket of `step` is appended to `fin` (the caller fills in gw1 / gw2 when they
+    are deferred) or, without `fin`, finished here."""
     N, C, H, W = out.shape
-    Ch, Hd, Cc = C // 2, int(w1.shape[0]), int(cond.shape[1])
-    k1, k2, k3 = int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2])
-    dfr = defer is not None and route.defer_wgrad
+    w1, n1b, n1l, w2, n2b, n2l, w3 = p.w1, p.n1b, p.n1l, p.w2, p.n2b, p.n2l, p.w3
+    Ch, (Hd, Cc, k1, k2, k3) = C // 2, _net_dims(p, cond)
+    dfr = defer is not None
     gw3 = None if dfr else zeros_conv_wgrad(h2, go, C, k3, arena)
     # the fused kernel needs the step's backward stream (POPackPlan: at most 16 channels) and, past an activation, the
     # forward's masks; what admits "po" ('mixed' arithmetic, Hd = 256) admits "dgrad_act" in its place
@@ -1044,16 +1070,16 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act, route, 
     z1, c2 = out[:, :Ch], (cond if Cc > 0 else None)
     gw1 = None if dfr else conv2d_wgrad(z1, c2, gh1, Hd, k1, arena)
     if chain == "po":
-        ticket = [part, w1, gw1, _f(n1b), w2, gw2, _f(n2b), o4]
+        ticket = FinishTicket(part, w1, gw1, _f(n1b), w2, gw2, _f(n2b), o4, step)
         if fin is not None:
             fin.append(ticket)
         else:
             assert not dfr
             coupling_po_bwd_finish([ticket])
     if dfr:
-        defer["w3"].append((h2, go))
-        defer["w2"].append((h1, gh2))
-        defer["w1"].append((z1, c2, gh1))
+        defer.z1[step], defer.c2[step], defer.gh1[step] = z1, c2, gh1
+        defer.h1[step], defer.gh2[step] = h1, gh2
+        defer.h2[step], defer.go[step] = h2, go
     g1, g2 = gz[:, :Ch], (gcond if Cc > 0 else None)
     if route.dgrad1 == "dense":
         smallmap_conv(gh1, None, _pack(pk, "w1_dense_dgrad", lambda: smallmap_pack(w1, H, W, True)), Ch + Cc, 0, out1=g1,
@@ -1063,38 +1089,101 @@ def _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act, route, 
     else:
         conv2d_raw(gh1, None, _pack(pk, "w1_dgrad", lambda: pack_weight(w1, True)), Ch + Cc, k1, 0, None, None, 0,
                    out1=g1, out2=g2, cout_split=Ch, acc1=True, acc2=acc_cond)
-    return gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3
+    return NetGrads(gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3)
 
 
-def _net_arena_numel(C, Cc, Hd, k1, k2, k3):
-    Ch = C // 2
+def _net_arena_numel(C, p, cond):
+    """floats of zero-filled arena that one step's backward takes: _net_bwd, a shell tail and an ActNorm / InvConv head"""
+    Ch, (Hd, Cc, k1, k2, k3) = C // 2, _net_dims(p, cond)
     return (2 * Ch + 8 + 3 * 2 * (Hd + 4) + 2 * (C + 4) + k1 * k1 * Hd * (Ch + Cc) + k2 * k2 * Hd * Hd
             + max(k3 * k3 * C * Hd, 9 * C * Hd) + C * C + 2 * C + 64)
 
 
-def _affine_zeros_bwd(out, o, gout, gdl, scale, scale_shift, l3, clamp_type, arena, go=None):
-    """rfn_affine_zeros_bwd_f32: returns (gz, go, gscale, gshift, gb3, gl3)"""
+def _step_grads(p, net, tail, gab, gal):
+    """the 13 gradients of the step `p` in StepParams order, shaped like the parameters, from its NetGrads, the TailGrads
+    of its coupling tail and its ActNorm's gab / gal (scale / scale_shift: None unless the clamp is realnvp)"""
+    def like(g, t):
+        return None if g is None else g.view(t.shape)
+    return StepParams(like(gab, p.an_bias), like(gal, p.an_logs), net.w1, net.n1b.view(1, -1, 1, 1), like(net.n1l, p.n1l),
+                      net.w2, net.n2b.view(1, -1, 1, 1), like(net.n2l, p.n2l), net.w3, tail.gb3, like(tail.gl3, p.l3),
+                      like(tail.gscale, p.scale), like(tail.gshift, p.scale_shift))
+
+
+# ---- the shell launches of the Glow nodes, one wrapper per entry point
+# what a backward coupling tail (coupling + Conv2dZeros epilogue) returns: gz = gradient at the step's post-InvConv
+# tensor, go = gradient at conv3's output, and the flat gradients of scale, scale_shift (realnvp only), b3 and l3
+TailGrads = collections.namedtuple("TailGrads", "gz go gscale gshift gb3 gl3")
+
+
+def _tail_grads(gout, o, clamp_type, arena, go=None):
+    """the outputs of a backward coupling tail, to be written (gz, go) or accumulated into (the rest, from `arena`)"""
+    C = int(o.shape[1])
+    gz, go = torch.empty_like(gout), (torch.empty_like(o) if go is None else go)
+    gscale, gshift = (arena.take(C // 2), arena.take(C // 2)) if clamp_type == 0 else (None, None)
+    return TailGrads(gz, go, gscale, gshift, arena.take(C), arena.take(C))
+
+
+def _affine_zeros_bwd(out, o, gout, gdl, p, clamp_type, arena, go=None):
+    """rfn_affine_zeros_bwd_f32, the stand-alone coupling tail of the step `p` backward: returns TailGrads"""
     N, C, H, W = out.shape
-    Ch, HW = C // 2, H * W
-    gz = torch.empty_like(gout)
-    if go is None:
-        go = torch.empty_like(o)
-    gscale = gshift = None
-    if clamp_type == 0:
-        gscale = arena.take(Ch)
-        gshift = arena.take(Ch)
-    gb3 = arena.take(C)
-    gl3 = arena.take(C)
+    t = _tail_grads(gout, o, clamp_type, arena, go)
     op, ons = L.frames(o, "o")
     outp, outns = L.frames(out, "out")
     gop, gons = L.frames(gout, "gout")
-    gzp, gzns = L.frames(gz, "gz")
-    gonp, gonns = L.frames(go, "go")
-    scf, shf, l3f = _f(scale), _f(scale_shift), _f(l3)
+    gzp, gzns = L.frames(t.gz, "gz")
+    gonp, gonns = L.frames(t.go, "go")
+    scf, shf, l3f = _f(p.scale), _f(p.scale_shift), _f(p.l3)
     L.call("rfn_affine_zeros_bwd_f32", outp, _l(outns), op, _l(ons), gop, _l(gons), L.dev(gdl), L.dev(scf),
-           L.dev(shf), L.dev(l3f), gzp, _l(gzns), gonp, _l(gonns), L.dev(gscale), L.dev(gshift), L.dev(gb3),
-           L.dev(gl3), _i(clamp_type), _i(N), _i(C), _i(HW), meta=_shell("affine_zeros_bwd", gout, 4.5))
-    return gz, go, gscale, gshift, gb3, gl3
+           L.dev(shf), L.dev(l3f), gzp, _l(gzns), gonp, _l(gonns), L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3),
+           L.dev(t.gl3), _i(clamp_type), _i(N), _i(C), _i(H * W), meta=_shell("affine_zeros_bwd", gout, 4.5))
+    return t
+
+
+def _glow_shell_bwd(x, head, Wm, gz, gW, gab, gal, o, gdl, tail, clamp_type, arena, go=None):
+    """rfn_glow_shell_bwd_f32: ActNorm / InvConv backward of the step `head` (input x, matrix Wm, gradient gz at its
+    post-InvConv tensor; gW, gab, gal are accumulated into), whose result feeds the coupling tail of the step before it,
+    `tail` (Conv2dZeros output o), from registers.  Returns that tail's TailGrads, as _affine_zeros_bwd."""
+    N, C, H, W = x.shape
+    t = _tail_grads(gz, o, clamp_type, arena, go)
+    xp, xns = L.frames(x, "x")
+    gzp, gzns = L.frames(gz, "gz")
+    op, ons = L.frames(o, "o")
+    gznp, gznns = L.frames(t.gz, "gz_prev")
+    gonp, gonns = L.frames(t.go, "gpre")
+    abf, alf, scf, shf, l3f = (_f(v) for v in (head.an_bias, head.an_logs, tail.scale, tail.scale_shift, tail.l3))
+    L.call("rfn_glow_shell_bwd_f32", xp, _l(xns), L.dev(abf), L.dev(alf), L.dev(Wm), gzp, _l(gzns), L.dev(gW),
+           L.dev(gab), L.dev(gal), op, _l(ons), L.dev(gdl), L.dev(scf), L.dev(shf), L.dev(l3f), gznp, _l(gznns), gonp,
+           _l(gonns), L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3), L.dev(t.gl3), _i(clamp_type), _i(1), _i(N), _i(C),
+           _i(H * W), meta=_shell("glow_shell_bwd", x, 5.5))
+    return t
+
+
+def _glow_shell_fwd(z, ld, clamp_type=0, tail=None, o=None, P=None, head=None, Wm=None):
+    """rfn_glow_shell_fwd_f32: the coupling tail of the step `tail` on z, in place, from the finished Conv2dZeros output
+    `o` or from its tap-expanded form `P` (fused kernel; gathered here into a fresh o), then the ActNorm / InvConv head
+    of the step `head` (matrix Wm) into a new tensor.  Without `tail` only the head runs (first launch of a level),
+    without `head` only the tail (last).  `ld`: the launch's slice of log-det partial sums, written.  Returns (o, znext)."""
+    N, C, H, W = z.shape
+    zp, zns = L.frames(z, "z")
+    zn, znp, znns = None, None, 0
+    hb = hl = sc = sh = b3 = l3 = None   # flat views of the parameters, held until the launch is enqueued
+    if head is not None:
+        zn, hb, hl = torch.empty_like(z), _f(head.an_bias), _f(head.an_logs)
+        znp, znns = L.frames(zn, "znext")
+    if tail is None:
+        src, nt = (None, None, _l(0), None, None, None), 2
+    else:
+        sc, sh = _f(tail.scale), _f(tail.scale_shift)
+        if P is not None:
+            b3, l3, o = _f(tail.b3), _f(tail.l3), torch.empty((N, C, H, W), device=z.device, dtype=torch.float32)
+            src, nt = (L.dev(P), None, _l(0), L.dev(b3), L.dev(l3), L.dev(o)), 12 + (0 if head is None else 1)
+        else:
+            op, ons = L.frames(o, "o")
+            src, nt = (None, op, _l(ons), None, None, None), 2 + (0 if head is None else 1.5)
+    L.call("rfn_glow_shell_fwd_f32", zp, _l(zns), *src, L.dev(sc), L.dev(sh), L.dev(ld), _i(clamp_type), L.dev(hb),
+           L.dev(hl), None if head is None else L.dev(Wm), znp, _l(znns), _i(0 if head is None else 1), _i(N), _i(C),
+           _i(H), _i(W), meta=_shell("glow_shell_fwd", z, nt))
+    return o, zn
 
 
 class GlowStepFn(torch.autograd.Function):
@@ -1107,7 +1196,8 @@ class GlowStepFn(torch.autograd.Function):
          z2 <- (z2 + o[0::2]) * exp(clamp(o[1::2]))              glow_modules.py:276-285
        Returns (out, dlogdet[N]) where dlogdet holds only the data dependent Σ clamp(s) part; the parameter-only
        terms (Σlogs + Σlog_s)·H·W are added by the caller.
-       Saved for backward: x, cond, out, h1, h2, o (activations stay resident in HBM, 288 GB is plenty).
+       apply(x, cond, Wm, *the step's parameters in StepParams order, act, clamp_type, packs).
+       Saved for backward (_save_step): x, cond, out, h1, h2, o (activations stay resident in HBM, 288 GB is plenty).
        (The K steps of a level normally run as ONE node, GlowLevelFn; this one serves the first, data-initialising
        call and stand-alone coupling layers.)"""
 
@@ -1115,42 +1205,58 @@ class GlowStepFn(torch.autograd.Function):
     def forward(ctx, x, cond, Wm, an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift,
                 act, clamp_type, packs=None):
         """`packs` (optional): the step's StepPacks (or a sequence in its field order)"""
+        p = StepParams(an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift)
         out = actnorm_invconv_fwd(x, _f(an_bias), _f(an_logs), Wm.detach())
         ctx.packs = pk = StepPacks(*packs)._asdict() if packs is not None else {}
-        ctx.route = route = _step_route(x, cond, w1, w2, w3, act, any(ctx.needs_input_grad))
-        h1, h2, o, P, masks = _net_fwd(out, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk)
+        ctx.route = route = _step_route(x, cond, p, act, any(ctx.needs_input_grad))
+        h1, h2, o, P, masks = _net_fwd(out, cond, p, act, route, pk)
         o, dlogdet = gather_affine_(out, o, P, _f(b3), _f(l3), _f(scale), _f(scale_shift), clamp_type)
-        ctx.save_for_backward(x, cond, Wm, an_bias, an_logs, w1, n1l, w2, n2l, w3, l3, scale, scale_shift, out, h1, h2, o,
-                              n1b, n2b, *(masks if masks is not None else ()))
+        _save_step(ctx, x, cond, Wm, p, out, h1, h2, o, masks)
         ctx.cfg = (act, clamp_type)
         return out, dlogdet
 
     @staticmethod
     def backward(ctx, gout, gdl):
-        (x, cond, Wm, an_bias, an_logs, w1, n1l, w2, n2l, w3, l3, scale, scale_shift, out, h1, h2, o, n1b, n2b) = ctx.saved_tensors[:19]
-        masks = tuple(ctx.saved_tensors[19:21]) if len(ctx.saved_tensors) > 19 else None
+        x, cond, Wm, p, out, h1, h2, o, masks = _saved_step(ctx.saved_tensors)
         act, clamp_type = ctx.cfg
-        N, C, H, W = x.shape
+        C = int(x.shape[1])
         gout = gout.contiguous()
         gdl = None if gdl is None else gdl.contiguous()
-        Cc = int(cond.shape[1])
-        k1, k2, k3 = int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2])
         # every accumulate-into output of this node lives in one zero-filled arena (1 fill launch instead of 14)
-        arena = ZeroArena(_net_arena_numel(C, Cc, int(w1.shape[0]), k1, k2, k3), x.device)
+        arena = ZeroArena(_net_arena_numel(C, p, cond), x.device)
         # ---- affine coupling bwd + Conv2dZeros epilogue bwd in one launch: gz (whole tensor), go = grad at conv3's output
-        gz, go, gscale, gshift, gb3, gl3 = _affine_zeros_bwd(out, o, gout, gdl, scale, scale_shift, l3, clamp_type, arena)
-        gcond = torch.empty_like(cond) if Cc > 0 else torch.zeros_like(cond)
-        gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, out, cond, h1, h2, w1, n1b, n1l, w2, n2b, n2l, w3, act,
-                                                         ctx.route, ctx.packs, arena, gz, gcond, False, masks=masks)
+        tail = _affine_zeros_bwd(out, o, gout, gdl, p, clamp_type, arena)
+        gcond = torch.empty_like(cond) if cond.shape[1] > 0 else torch.zeros_like(cond)
+        net = _net_bwd(tail.go, out, cond, h1, h2, p, act, ctx.route, ctx.packs, arena, tail.gz, gcond, False, masks=masks)
         # ---- invconv + actnorm bwd
-        gx, gW, gab, gal = actnorm_invconv_bwd(x, _f(an_bias), _f(an_logs), Wm.detach(), gz, arena)
-        return (gx, gcond, gW, gab.view(an_bias.shape), gal.view(an_logs.shape), gw1, gn1b.view(1, -1, 1, 1),
-                gn1l.view(n1l.shape), gw2, gn2b.view(1, -1, 1, 1), gn2l.view(n2l.shape), gw3, gb3, gl3.view(l3.shape),
-                None if gscale is None else gscale.view(scale.shape),
-                None if gshift is None else gshift.view(scale_shift.shape), None, None, None)
+        gx, gW, gab, gal = actnorm_invconv_bwd(x, _f(p.an_bias), _f(p.an_logs), Wm.detach(), tail.gz, arena)
+        return (gx, gcond, gW, *_step_grads(p, net, tail, gab, gal), None, None, None)
 
 
-STEP_NPARAM = 13  # an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift
+# ---- what the two training nodes save for backward, in which order, and how it comes back: (x, cond, W, the
+# StepParams, out, h1, h2, o, masks), for the level node with lists over the K steps from the StepParams on
+def _save_step(ctx, x, cond, Wm, p, out, h1, h2, o, masks):
+    ctx.save_for_backward(x, cond, Wm, p.an_bias, p.an_logs, p.w1, p.n1l, p.w2, p.n2l, p.w3, p.l3, p.scale, p.scale_shift,
+                          out, h1, h2, o, p.n1b, p.n2b, *(masks if masks is not None else ()))
+
+
+def _saved_step(sv):
+    (x, cond, Wm, an_bias, an_logs, w1, n1l, w2, n2l, w3, l3, scale, scale_shift, out, h1, h2, o, n1b, n2b, *masks) = sv
+    p = StepParams(an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, None, l3, scale, scale_shift)   # (b3 is not read)
+    return x, cond, Wm, p, out, h1, h2, o, tuple(masks) if masks else None
+
+
+def _save_level(ctx, x, cond, Wst, flat, outs, h1s, h2s, os_, mks):
+    """x, cond, Wst, the 13 K parameters, then K each of out / h1 / h2 / o and, if every step has them, of the two masks"""
+    m1, m2 = zip(*mks) if all(m is not None for m in mks) else ((), ())
+    ctx.save_for_backward(x, cond, Wst, *flat, *outs, *h1s, *h2s, *os_, *m1, *m2)
+
+
+def _saved_level(sv):
+    Kn, it = int(sv[2].shape[0]), iter(sv)
+    (x, cond, Wst), *steps, outs, h1s, h2s, os_, m1, m2 = (
+        list(itertools.islice(it, n)) for n in [3] + [STEP_NPARAM] * Kn + [Kn] * 6)
+    return x, cond, Wst, [StepParams(*s) for s in steps], outs, h1s, h2s, os_, list(zip(m1, m2)) or [None] * Kn
 
 
 class GlowLevelFn(torch.autograd.Function):
@@ -1159,7 +1265,7 @@ class GlowLevelFn(torch.autograd.Function):
     of step k+1; rfn_glow_shell_bwd_f32: the mirror image); the gradient wrt the shared condition map accumulates
     inside the data-gradient kernels and the per-frame log-det inside the shell kernel, so autograd adds nothing.
     apply(x, cond, Wst[K,C,C], act, clamp_type, packs (None, or a list of K StepPacks or sequences in its field order),
-    *13K step parameters)
+    *the K steps' parameters, step by step, each in StepParams order)
     -> (out, dlogdet[N] = sum over the K steps of the data dependent log-det AND of the ActNorm parameter term
     H*W * sum_c logs[c]; the InvConv term sum log|s| * H*W stays with the caller, who builds the matrices)."""
 
@@ -1172,160 +1278,78 @@ class GlowLevelFn(torch.autograd.Function):
         if not L.load().rfn_glow_shell_supported(N, C, H, W):
             raise RuntimeError("GlowLevelFn: a flow level of C=%d channels on %dx%d maps does not fit the shell kernels "
                                "(C must be even and at most 144: rfn_glow_shell_supported)" % (C, H, W))
-        prm = [flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)] for k in range(Kn)]
+        prm = [StepParams(*flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)]) for k in range(Kn)]
         pks = [StepPacks(*packs[k])._asdict() if packs is not None and packs[k] is not None else {} for k in range(Kn)]
-        route = _step_route(x, cond, prm[0][2], prm[0][5], prm[0][8], act, any(ctx.needs_input_grad))   # of all K steps
+        route = _step_route(x, cond, prm[0], act, any(ctx.needs_input_grad))   # of all K steps
         Wd = Wst.detach().contiguous()
         # log-det: every shell launch WRITES its per-block partial sums into its own slice; one reduce launch adds them
         # per frame in a fixed order (no float atomics anywhere in the forward pass: bit-reproducible)
         ldf = int(L.load().rfn_glow_shell_fwd_ld_floats(N, C, H, W))
         ldp = torch.empty((Kn + 1, ldf), device=x.device, dtype=torch.float32)
         dl = torch.empty(N, device=x.device, dtype=torch.float32)
-        xp, xns = L.frames(x, "x")
-        z = torch.empty_like(x)
-        zp, zns = L.frames(z, "z")
-        ab0, al0 = _f(prm[0][0]), _f(prm[0][1])
-        L.call("rfn_glow_shell_fwd_f32", xp, _l(xns), None, None, _l(0), None, None, None, None, None, L.dev(ldp[0]), _i(0),
-               L.dev(ab0), L.dev(al0), L.dev(Wd[0]), zp, _l(zns), _i(1), _i(N), _i(C), _i(H), _i(W),
-               meta=_shell("glow_shell_fwd", x, 2))
-        outs, h1s, h2s, os_, mks = [], [], [], [], []
+        _, z = _glow_shell_fwd(x, ldp[0], head=prm[0], Wm=Wd[0])
+        kept = []   # per step: out, h1, h2, o, masks
+        heads = [*zip(prm[1:], Wd[1:]), (None, None)]   # the step whose head follows the tail of step k, and its matrix
         for k in range(Kn):
-            (_, _, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift) = prm[k]
-            h1, h2, o, P, masks = _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pks[k])
-            mks.append(masks)
-            last = k == Kn - 1
-            zn = None if last else torch.empty_like(z)
-            znp, znns = (None, 0) if last else L.frames(zn, "znext")
-            hold = [_f(b3), _f(l3), _f(scale), _f(scale_shift)] + ([None, None] if last else [_f(prm[k + 1][0]), _f(prm[k + 1][1])])
-            zp, zns = L.frames(z, "z")
-            if P is not None:
-                o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
-                args = (L.dev(P), None, _l(0), L.dev(hold[0]), L.dev(hold[1]), L.dev(o))
-                nt = 12 + (0 if last else 1)
-            else:
-                op, ons = L.frames(o, "o")
-                args = (None, op, _l(ons), None, None, None)
-                nt = 2 + (0 if last else 1.5)
-            L.call("rfn_glow_shell_fwd_f32", zp, _l(zns), *args, L.dev(hold[2]), L.dev(hold[3]), L.dev(ldp[k + 1]),
-                   _i(clamp_type), L.dev(hold[4]), L.dev(hold[5]), None if last else L.dev(Wd[k + 1]), znp, _l(znns),
-                   _i(0 if last else 1), _i(N), _i(C), _i(H), _i(W), meta=_shell("glow_shell_fwd", z, nt))
-            outs.append(z)
-            h1s.append(h1)
-            h2s.append(h2)
-            os_.append(o)
+            h1, h2, o, P, masks = _net_fwd(z, cond, prm[k], act, route, pks[k])
+            o, zn = _glow_shell_fwd(z, ldp[k + 1], clamp_type, prm[k], o, P, *heads[k])
+            kept.append((z, h1, h2, o, masks))
             z = zn
         L.call("rfn_logdet_reduce_f32", L.dev(ldp), _i(Kn + 1), L.dev(dl), _i(0), _i(N), _i(C), _i(H), _i(W),
                meta=_shell("logdet_reduce", ldp, 1))
-        has_masks = all(m is not None for m in mks)
-        ctx.save_for_backward(x, cond, Wst, *flat, *outs, *h1s, *h2s, *os_,
-                              *([m[0] for m in mks] + [m[1] for m in mks] if has_masks else []))
-        ctx.cfg = (act, clamp_type, Kn, pks, has_masks, route)
-        return outs[-1], dl
+        _save_level(ctx, x, cond, Wst, flat, *zip(*kept))
+        ctx.cfg = (act, clamp_type, pks, route)
+        return kept[-1][0], dl
 
     @staticmethod
     def backward(ctx, gout, gdl):
-        act, clamp_type, Kn, pks, has_masks, route = ctx.cfg
-        sv = ctx.saved_tensors
-        x, cond, Wst = sv[0], sv[1], sv[2]
-        nf = STEP_NPARAM * Kn
-        flat = sv[3:3 + nf]
-        rest = sv[3 + nf:]
-        outs, h1s, h2s, os_ = (rest[i * Kn:(i + 1) * Kn] for i in range(4))
-        mks = [(rest[4 * Kn + k], rest[5 * Kn + k]) for k in range(Kn)] if has_masks else [None] * Kn
-        fin = []   # ActNorm-gradient tickets of the fused backward kernel, finished in one launch at the end
-        prm = [flat[STEP_NPARAM * k:STEP_NPARAM * (k + 1)] for k in range(Kn)]
-        N, C, H, W = x.shape
-        Ch, HW = C // 2, H * W
-        Cc = int(cond.shape[1])
+        act, clamp_type, pks, route = ctx.cfg
+        x, cond, Wst, prm, outs, h1s, h2s, os_, mks = _saved_level(ctx.saved_tensors)
+        Kn, (N, C, H, W), (Hd, Cc, k1, k2, k3) = len(prm), x.shape, _net_dims(prm[0], cond)
         gout = gout.contiguous()
         gdl = None if gdl is None else gdl.contiguous()
         Wd = Wst.detach().contiguous()
-        w1 = prm[0][2]
-        k1, k2, k3 = int(prm[0][2].shape[2]), int(prm[0][5].shape[2]), int(prm[0][8].shape[2])
         # one zero-filled arena for the accumulate-into outputs of all K steps
-        arena = ZeroArena(Kn * _net_arena_numel(C, Cc, int(w1.shape[0]), k1, k2, k3), x.device)
+        arena = ZeroArena(Kn * _net_arena_numel(C, prm[0], cond), x.device)
         gWst = arena.take(Kn, C, C)
         gcond = torch.empty_like(cond) if Cc > 0 else torch.zeros_like(cond)
-        grads = [None] * nf
-        # last step: stand-alone coupling backward; earlier steps get theirs from the fused shell launch below
-        (_, _, _, _, _, _, _, _, _, _, l3, scale, scale_shift) = prm[Kn - 1]
-        # (with deferred weight gradients the K conv3-output gradients live in one buffer: one tap-scatter for all)
-        grouped = group_level_wgrad(Kn, N, int(w1.shape[0]), HW, os_[0].numel(), x.device)
-        go_all = torch.empty((Kn,) + tuple(os_[0].shape), device=x.device, dtype=torch.float32) if grouped else None
-        gz, go, gscale, gshift, gb3, gl3 = _affine_zeros_bwd(outs[Kn - 1], os_[Kn - 1], gout, gdl, scale, scale_shift, l3,
-                                                            clamp_type, arena, None if go_all is None else go_all[Kn - 1])
-        gx = None
         # the 3 K weight gradients are computed at the end, K of one shape per launch (one atomic tail per launch
         # instead of K); their operands stay alive until then, which is what group_level_wgrad budgets
-        defer = {"w1": [], "w2": [], "w3": []} if grouped else None
+        # (the K conv3-output gradients then live in one buffer, go_all: one tap-scatter for all; else each in its own)
+        grouped = group_level_wgrad(Kn, N, Hd, H * W, os_[0].numel(), x.device)
+        go_all = torch.empty((Kn,) + tuple(os_[0].shape), device=x.device, dtype=torch.float32) if grouped else [None] * Kn
+        defer = WgradOperands(*([None] * Kn for _ in WgradOperands._fields)) if grouped and route.defer_wgrad else None
+        fin = []   # ActNorm-gradient tickets of the fused backward kernel, finished in one launch at the end
+        grads = [None] * Kn   # per step, in StepParams order
+        # `tail`: the coupling tail's gradients of the step the loop is about to visit.  They are produced one iteration
+        # before they are consumed: for the last step by the stand-alone launch here, for step k - 1 by the shell launch
+        # of iteration k, which runs the ActNorm / InvConv backward of step k and the tail of step k - 1 in one kernel.
+        tail = _affine_zeros_bwd(outs[-1], os_[-1], gout, gdl, prm[-1], clamp_type, arena, go_all[-1])
         for k in range(Kn - 1, -1, -1):
-            (an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift) = prm[k]
-            nfin = len(fin)
-            gw1, gn1b, gn1l, gw2, gn2b, gn2l, gw3 = _net_bwd(go, outs[k], cond, h1s[k], h2s[k], w1, n1b, n1l, w2, n2b, n2l,
-                                                             w3, act, route, pks[k], arena, gz, gcond, k != Kn - 1, defer,
-                                                             masks=mks[k], fin=fin)
-            if len(fin) > nfin:
-                fin[-1].append(k)   # the step whose (possibly deferred) weight gradients the ticket needs
-            base = STEP_NPARAM * k
-            grads[base + 2:base + 13] = [gw1, gn1b.view(1, -1, 1, 1), gn1l.view(n1l.shape), gw2, gn2b.view(1, -1, 1, 1),
-                                         gn2l.view(n2l.shape), gw3, gb3, gl3.view(l3.shape),
-                                         None if gscale is None else gscale.view(scale.shape),
-                                         None if gshift is None else gshift.view(scale_shift.shape)]
+            net = _net_bwd(tail.go, outs[k], cond, h1s[k], h2s[k], prm[k], act, route, pks[k], arena, tail.gz, gcond,
+                           k != Kn - 1, defer, mks[k], fin, k)
             gab, gal = arena.take(C), arena.take(C)
-            grads[base], grads[base + 1] = gab.view(an_bias.shape), gal.view(an_logs.shape)
-            abf, alf = _f(an_bias), _f(an_logs)
-            gzp, gzns = L.frames(gz, "gz")
+            grads[k] = _step_grads(prm[k], net, tail, gab, gal)
             if k == 0:
-                gx = torch.empty_like(x)
-                xp, xns = L.frames(x, "x")
-                gxp, gxns = L.frames(gx, "gx")
-                L.call("rfn_actnorm_invconv_bwd_ld_f32", xp, _l(xns), L.dev(abf), L.dev(alf), L.dev(Wd[0]), gzp, _l(gzns),
-                       gxp, _l(gxns), L.dev(gWst[0]), L.dev(gab), L.dev(gal), L.dev(gdl), _i(N), _i(C), _i(HW),
-                       meta=_shell("actnorm_invconv_bwd", x, 3))
-                break
-            # fused: ActNorm/InvConv backward of step k, coupling + Conv2dZeros-epilogue backward of step k-1
-            (_, _, _, _, _, _, _, _, _, _, l3p, scalep, shiftp) = prm[k - 1]
-            xin, op_ = outs[k - 1], os_[k - 1]
-            gzn = torch.empty_like(gz)
-            gon = torch.empty_like(op_) if go_all is None else go_all[k - 1]
-            gscale = gshift = None
-            if clamp_type == 0:
-                gscale, gshift = arena.take(Ch), arena.take(Ch)
-            gb3, gl3 = arena.take(C), arena.take(C)
-            xp, xns = L.frames(xin, "x")
-            opp, ons = L.frames(op_, "o")
-            gznp, gznns = L.frames(gzn, "gz_prev")
-            gonp, gonns = L.frames(gon, "gpre")
-            hold = [_f(scalep), _f(shiftp), _f(l3p)]
-            L.call("rfn_glow_shell_bwd_f32", xp, _l(xns), L.dev(abf), L.dev(alf), L.dev(Wd[k]), gzp, _l(gzns),
-                   L.dev(gWst[k]), L.dev(gab), L.dev(gal), opp, _l(ons), L.dev(gdl), L.dev(hold[0]), L.dev(hold[1]),
-                   L.dev(hold[2]), gznp, _l(gznns), gonp, _l(gonns), L.dev(gscale), L.dev(gshift), L.dev(gb3),
-                   L.dev(gl3), _i(clamp_type), _i(1), _i(N), _i(C), _i(HW), meta=_shell("glow_shell_bwd", xin, 5.5))
-            gz, go = gzn, gon
-        if defer is not None and defer["w2"]:
-            # entries were appended for k = Kn-1 .. 0: back to step order
-            for key in ("w1", "w2", "w3"):
-                defer[key].reverse()
-            Hd_ = int(prm[0][2].shape[0])
-            g1 = conv2d_wgrad_grouped([t[0] for t in defer["w1"]],
-                                      None if defer["w1"][0][1] is None else [t[1] for t in defer["w1"]],
-                                      [t[2] for t in defer["w1"]], Hd_, k1, arena)
-            g2 = conv2d_wgrad_grouped([t[0] for t in defer["w2"]], None, [t[1] for t in defer["w2"]], Hd_, k2, arena)
-            g3 = zeros_conv_wgrad_grouped([t[0] for t in defer["w3"]], [t[1] for t in defer["w3"]], C, arena,
-                                          g_stacked=go_all, ks=k3, min_pixels=level_mirrored_min_pixels())
-            for k in range(Kn):
-                base = STEP_NPARAM * k
-                grads[base + 2], grads[base + 5], grads[base + 8] = g1[k], g2[k], g3[k]
+                gx = actnorm_invconv_bwd(x, _f(prm[0].an_bias), _f(prm[0].an_logs), Wd[0], tail.gz, acc=(gWst[0], gab, gal),
+                                         glogdet=gdl)[0]
+            else:
+                tail = _glow_shell_bwd(outs[k - 1], prm[k], Wd[k], tail.gz, gWst[k], gab, gal, os_[k - 1], gdl, prm[k - 1],
+                                       clamp_type, arena, go_all[k - 1])
+        if defer is not None:
+            gw1 = conv2d_wgrad_grouped(defer.z1, None if defer.c2[0] is None else defer.c2, defer.gh1, Hd, k1, arena)
+            gw2 = conv2d_wgrad_grouped(defer.h1, None, defer.gh2, Hd, k2, arena)
+            gw3 = zeros_conv_wgrad_grouped(defer.h2, defer.go, C, arena, g_stacked=go_all, ks=k3,
+                                           min_pixels=level_mirrored_min_pixels())
+            grads = [g._replace(w1=a, w2=b, w3=c) for g, a, b, c in zip(grads, gw1, gw2, gw3)]
         if fin:
-            for t in fin:
-                base = STEP_NPARAM * t.pop()
-                t[2], t[5] = grads[base + 2], grads[base + 5]
-            coupling_po_bwd_finish(fin)
-        return (gx, gcond, gWst, None, None, None) + tuple(grads)
+            coupling_po_bwd_finish([t._replace(gw1=grads[t.step].w1, gw2=grads[t.step].w2) for t in fin])
+        return (gx, gcond, gWst, None, None, None, *(g for step in grads for g in step))
 
 
 class GlowStepRevFn(torch.autograd.Function):
-    """Reverse Glow step (Flow/glow.py:37-41) for generation; no gradient (the reference samples under no_grad)."""
+    """Reverse Glow step (Flow/glow.py:37-41) for generation; no gradient (the reference samples under no_grad).
+    apply(x, cond, Winv, *the step's parameters in StepParams order, act, clamp_type, pkcache)."""
 
     @staticmethod
     def forward(ctx, x, cond, Winv, an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift,
@@ -1333,11 +1357,12 @@ class GlowStepRevFn(torch.autograd.Function):
         """`pkcache` (optional dict, owned by the caller): packed weights of this step, filled on first use and reused
         while the caller keeps it -- autoregressive generation runs the same step once per frame on unchanged weights."""
         N, C, H, W = x.shape
+        p = StepParams(an_bias, an_logs, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, scale, scale_shift)
         z = x.detach().clone()
-        route = _step_route(x, cond, w1, w2, w3, act, False, reverse=True)
+        route = _step_route(x, cond, p, act, False, reverse=True)
         # (one set of packs per forward arithmetic: CONV_PRECISION may change while the caller keeps the dict)
         pk = (pkcache if pkcache is not None else {}).setdefault(route.fwd_prec, {})
-        _, _, o, P, _ = _net_fwd(z, cond, w1, n1b, n1l, w2, n2b, n2l, w3, b3, l3, act, route, pk)
+        _, _, o, P, _ = _net_fwd(z, cond, p, act, route, pk)
         if P is not None:
             o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
             b3f, l3f = _f(b3), _f(l3)

@@ -288,3 +288,26 @@ def test_shell_argument_errors_launch_nothing(lib):
         assert bwd_label(lib, *q) == "unsupported"
     assert bwd_label(lib, 2, 5, 4, 0).startswith("actnorm_invconv_bwd_kernel<0> ")   # without a tail C may be odd
     del keep
+
+
+def test_step_parameters_have_one_stated_order():
+    """rfn_hip.ops.StepParams is the order in which Flow/ hands a step's parameters to the three Glow nodes and in which
+    their backward returns the gradients: the step's ActNorm, then AffineCoupling.nn_params(), tensor by tensor"""
+    from rfn_hip import ops
+    from Flow.glow_modules import AffineCoupling
+    assert ops.StepParams._fields == ("an_bias", "an_logs", "w1", "n1b", "n1l", "w2", "n2b", "n2l", "w3", "b3", "l3",
+                                      "scale", "scale_shift")
+    assert ops.STEP_NPARAM == 13
+    aff = AffineCoupling([2, 4, 4, 4], [2, 3, 4, 4], hidden_units=8, non_lin="relu", clamp_type="realnvp")
+    an_bias, an_logs = object(), object()
+    p = ops.StepParams(an_bias, an_logs, *aff.nn_params())
+    n0, n2, n4 = aff.net[0], aff.net[2], aff.net[4]
+    named = dict(an_bias=an_bias, an_logs=an_logs, w1=n0.conv.weight, n1b=n0.norm_type.bias, n1l=n0.norm_type.logs,
+                 w2=n2.conv.weight, n2b=n2.norm_type.bias, n2l=n2.norm_type.logs, w3=n4.conv.weight, b3=n4.conv.bias,
+                 l3=n4.logs, scale=aff.scale, scale_shift=aff.scale_shift)
+    assert tuple(named) == ops.StepParams._fields
+    for field in ops.StepParams._fields:
+        assert getattr(p, field) is named[field], field
+    # without the realnvp clamp the last two are None, in place
+    p = ops.StepParams(an_bias, an_logs, *AffineCoupling([2, 4, 4, 4], [2, 0, 4, 4], 8, "relu", "glow").nn_params())
+    assert p.scale is None and p.scale_shift is None and p.l3.shape == (4, 1, 1)

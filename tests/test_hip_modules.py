@@ -1368,7 +1368,11 @@ def test_glowstep_bair_channel_counts(conv_precision, C, Cc, S):
 
 @pytest.mark.parametrize("N,C,Cc,S,Hd,Kn,clamp", [(2, 4, 16, 32, 256, 3, "realnvp"), (3, 8, 32, 16, 256, 2, "glow"),
                                                (5, 16, 8, 8, 64, 3, "realnvp"), (4, 32, 16, 4, 64, 2, "softclamp"),
-                                               (6, 64, 32, 2, 64, 3, "realnvp"), (3, 6, 0, 4, 64, 2, "none")])
+                                               (6, 64, 32, 2, 64, 3, "realnvp"), (3, 6, 0, 4, 64, 2, "none"),
+                                               # K = 1: head launch, net, tail launch; backward without a shell launch
+                                               (2, 4, 8, 4, 64, 1, "realnvp"),
+                                               # the carried clamp-parameter gradients without condition channels
+                                               (2, 6, 0, 4, 64, 3, "realnvp")])
 def test_glow_level_node_equals_chain_of_step_nodes(conv_precision, N, C, Cc, S, Hd, Kn, clamp):
     """rfn_hip.ops.GlowLevelFn (the K steps of a level as one autograd node, shell work fused across step boundaries:
     rfn_glow_shell_fwd_f32 / rfn_glow_shell_bwd_f32) against K chained GlowStepFn nodes -- outputs, log-det and every
