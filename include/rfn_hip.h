@@ -508,6 +508,35 @@ int rfn_stepbn_apply_f32(const float* x, const float* gamma, const float* beta, 
  * aligned; bit 1 = the same for the apply kernel (x, y; with bwd x, g, gx). */
 const char* rfn_stepbn_kernel_label(int S, int B, int C, int HW, int aligned, int bwd);
 
+/* ---- BatchNormFlow (Flow/glow_modules.py:56-104), the flow normalisation of --flow_norm batchnorm, on a step-major
+ * time-batched tensor x [S*B, E] with E = C*H*W: log_gamma, beta, run_mean, run_var are [E] (one value per channel AND
+ * pixel), and the statistics of each step's B rows are taken on their own, as the reference's per-timestep calls take
+ * them (glow_modules.py:76-79: mean = mean_b x, var = mean_b (x - mean)^2 + eps, eps INSIDE var also where the log-det
+ * reads it).  Forward, training (glow_modules.py:93-98): z = exp(log_gamma)*(x - mean)/sqrt(var) + beta, dl[s] = sum_e
+ * (log_gamma - 0.5 log var[s]) to be added to the log-det of every row of step s; mean / var [S*E] are kept for the
+ * backward.  run_mean / run_var (both or neither) receive the S updates of glow_modules.py:81-87 in closed form, run <-
+ * decay*run + sum_s coef[s]*stat[s] with coef_mean / coef_var [S] device arrays; the momentum weights the OLD value, so
+ * decay = m^S and coef[s] = (1-m) m^(S-1-s).
+ * Backward, given gz [S*B, E] and gdl [S] (may be NULL = 0), with xhat = (x - mean)/sqrt(var), rstd = 1/sqrt(var),
+ * g' = gz*exp(log_gamma): gx = rstd*(g' - mean_b g' - xhat*mean_b(g' xhat)) - gdl[s]*xhat*rstd/B (the log-det depends on
+ * the data through var), g_log_gamma = sum_{s,b} g' xhat + sum_s gdl[s], g_beta = sum_{s,b} gz.
+ * scratch = rfn_bnflow_scratch_floats(S, B, E, bwd) floats (bwd = 0, the forward: log-det partials, S*ceil(E/64); bwd = 1,
+ * the backward: per-step gradient partials, 2*S*E; no
+ * zeroing needed: no atomics, every sum is taken in a fixed order and the results repeat bit for bit).  Two launches each.
+ * 16-byte accesses when E % 4 == 0 and every tensor pointer is 16-byte aligned, 4-byte accesses otherwise. */
+long rfn_bnflow_scratch_floats(int S, int B, int E, int bwd);
+int rfn_bnflow_fwd_f32(const float* x, const float* log_gamma, const float* beta, float* z, float* mean, float* var,
+                       float* dl, float* scratch, float* run_mean, float* run_var, const float* coef_mean,
+                       const float* coef_var, float decay, int S, int B, int E, float eps, rfn_stream_t stream);
+int rfn_bnflow_bwd_f32(const float* x, const float* log_gamma, const float* gz, const float* gdl, const float* mean,
+                       const float* var, float* gx, float* g_log_gamma, float* g_beta, float* scratch, int S, int B,
+                       int E, rfn_stream_t stream);
+/* The map with GIVEN statistics (glow_modules.py:90-103: eval mode, and the reverse direction in any mode) on N rows, one
+ * launch: forward y = exp(log_gamma)/sqrt(run_var)*(x - run_mean) + beta, dl[0] = sum_e (log_gamma - 0.5 log run_var);
+ * reverse y = (x - beta)*sqrt(run_var)/exp(log_gamma) + run_mean, dl[0] = minus that sum (bit for bit). */
+int rfn_bnflow_apply_f32(const float* x, const float* log_gamma, const float* beta, const float* run_mean,
+                         const float* run_var, float* y, float* dl, int N, int E, int reverse, rfn_stream_t stream);
+
 /* ---- a9  ConvLSTMLayer.forward gate update  (Utils/modules.py:370-377): cc = conv output [N,4*Hc,HW] in gate order
  * i,f,o,g;  i=σ(cc_i+Wci∘c) f=σ(cc_f+Wcf∘c) g=tanh(cc_g) c'=f∘c+i∘g o=σ(cc_o+Wco∘c') h'=o∘tanh(c').
  * Wci/Wcf/Wco [Hc*HW] may be NULL (== 0, which is what the reference trains with).  gates [N,4*Hc,HW] receives the

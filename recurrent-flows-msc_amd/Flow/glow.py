@@ -32,6 +32,8 @@ class GlowStep(nn.Module):
         self.flow_norm = args.flow_norm
         if args.flow_norm == "batchnorm":
             self.norm = BatchNormFlow(x_size, momentum=args.flow_batchnorm_momentum)
+            # the zero ActNorm (bias and logs) the step's fused node runs with; not part of checkpoints
+            self.register_buffer("an_zero", torch.zeros(1, c, 1, 1), persistent=False)
         else:
             self.norm = ActNorm(c)
         self.invconv = InvConv(c, LU_decomposed=args.LU_decomposed)
@@ -39,57 +41,65 @@ class GlowStep(nn.Module):
                                      non_lin=args.non_lin_glow, clamp_type=args.clamp_type)
 
     def _param_logdet(self, x):
-        """(Σ actnorm.logs + Σ log_s)·H·W — the log-det terms that do not depend on the data."""
+        """(Σ actnorm.logs + Σ log_s)·H·W — the log-det terms that do not depend on the data (a batch-norm step has no
+        ActNorm term: its normalisation's log-det comes with the data dependent part)."""
         hw = x.shape[2] * x.shape[3]
         if self.invconv.LU_decomposed:
             ld = torch.sum(self.invconv.log_s)
         else:
             ld = torch.slogdet(self.invconv.weight)[1]
+        if self.flow_norm == "batchnorm":
+            return ld * hw
         return (ld + torch.sum(self.norm.logs)) * hw
 
-    def forward(self, x, condition, logdet, reverse, Wm=None, defer_logdet=None, packs=None):
+    def forward(self, x, condition, logdet, reverse, Wm=None, defer_logdet=None, packs=None, steps=1, update_running=True):
         """`Wm` (optional): this step's C×C matrix when the caller built all matrices of a level in one batched
         computation; `defer_logdet` (optional list): receives the data dependent log-det [N] instead of adding it (the
-        caller sums all steps at once and adds the parameter-only terms per level)."""
-        if self.flow_norm == "batchnorm":  # non-default variant: unfused module chain
-            if not reverse:
-                x, logdet = self.norm(x, logdet, reverse=False)
-                x, logdet = self.invconv(x, logdet, reverse=False)
-                return self.affine(x, condition, logdet, reverse=False)
-            x, logdet = self.affine(x, condition, logdet, reverse=True)
-            x, logdet = self.invconv(x, logdet, reverse=True)
-            return self.norm(x, logdet, reverse=True)
-        aff, an = self.affine, self.norm
+        caller sums all steps at once and adds the parameter-only terms per level).  `steps`, `update_running`: a
+        batch-norm step takes the statistics of each of the `steps` step-major groups of frames (BatchNormFlow.forward).
+
+        A batch-norm step is the BatchNormFlow kernel and then the SAME node as an actnorm step, with a zero ActNorm:
+        InvConv and coupling run fused exactly as on the default path (reverse: in the mirrored order)."""
+        aff, bn = self.affine, self.flow_norm == "batchnorm"
+        an = None if bn else self.norm
+        an_bias, an_logs = (self.an_zero, self.an_zero) if bn else (an.bias, an.logs)
         act, clamp = K.ACT[aff.non_lin], K.CLAMP[aff.clamp_type]
         x = x if x.stride(-1) == 1 and x.stride(1) == x.shape[2] * x.shape[3] else x.contiguous()
         condition = condition.contiguous()
         if not reverse:
-            if an.needs_init():  # data dependent init, first training call (glow_modules.py:22-36)
+            bn_dl = None
+            if bn:
+                x, bn_dl = self.norm(x, 0.0, reverse=False, steps=steps, update_running=update_running)
+            elif an.needs_init():  # data dependent init, first training call (glow_modules.py:22-36)
                 an.initialize(x)
                 an.mark_initialized()
             if Wm is None:
                 Wm, _ = self.invconv.get_weight(x, reverse=False)
             if aff.net[0].norm_type.needs_init() or aff.net[2].norm_type.needs_init():
-                with torch.no_grad():
-                    z = K.actnorm_invconv_fwd(x.detach(), an.bias.detach().reshape(-1), an.logs.detach().reshape(-1),
+                with torch.no_grad():  # (batch-norm: the inner ActNorms see the normalised, InvConv'ed input)
+                    z = K.actnorm_invconv_fwd(x.detach(), an_bias.detach().reshape(-1), an_logs.detach().reshape(-1),
                                               Wm.detach())
                     aff.maybe_init(z[:, : z.shape[1] // 2], condition)
-            out, dl = K.GlowStepFn.apply(x, condition, Wm, an.bias, an.logs, *aff.nn_params(), act, clamp, packs)
+            out, dl = K.GlowStepFn.apply(x, condition, Wm, an_bias, an_logs, *aff.nn_params(), act, clamp, packs)
+            if bn_dl is not None:
+                dl = dl + bn_dl
             if defer_logdet is not None:
                 defer_logdet.append(dl)
             elif logdet is not None:
                 logdet = logdet + dl + self._param_logdet(x)
             return out, logdet
-        if an.needs_init():
+        if an is not None and an.needs_init():
             an.mark_initialized()  # the reference flips the flag on any first call (glow_modules.py:34-36)
         for m in (aff.net[0].norm_type, aff.net[2].norm_type):
             if m.needs_init():
                 m.mark_initialized()
         # `Wm` (optional, reverse): the inverse matrix from the caller's generation cache; `packs`: its packed-weight dict
         Winv = Wm if Wm is not None else self.invconv.get_weight(x, reverse=True)[0]
-        out, dl = K.GlowStepRevFn.apply(x, condition, Winv, an.bias, an.logs, *aff.nn_params(), act, clamp, packs)
+        out, dl = K.GlowStepRevFn.apply(x, condition, Winv, an_bias, an_logs, *aff.nn_params(), act, clamp, packs)
         if logdet is not None:
             logdet = logdet + dl - self._param_logdet(x)
+        if bn:
+            out, logdet = self.norm(out, logdet, reverse=True)
         return out, logdet
 
 
@@ -176,7 +186,7 @@ class ListGlow(nn.Module):
         """All K matrices W = P·L·U of a level in ONE batched computation (glow_modules.py:188-205) plus the level's
         InvConv part of the parameter-only log-det, Σ_k Σ log_s·H·W: a handful of launches per level, not per step."""
         ics = [s.invconv for s in steps]
-        if not all(ic.LU_decomposed for ic in ics) or any(s.flow_norm == "batchnorm" for s in steps):
+        if not all(ic.LU_decomposed for ic in ics):
             return None, None
         if K.invconv_weights_ok(ics):  # one launch each way instead of ~17 + ~20 (rfn_invconv_weights_*_f32)
             return K.InvConvWeightsFn.apply(int(hw), len(ics), *[ic.p for ic in ics], *[ic.sign_s for ic in ics],
@@ -198,6 +208,8 @@ class ListGlow(nn.Module):
         """the one-node-per-level path: device tensors, every ActNorm of the level already initialised (the first,
         data-initialising call walks the steps one by one), one activation / clamp for the whole level"""
         if not z.is_cuda or os.environ.get("RFN_LEVEL_NODE") == "0":
+            return False
+        if any(s_.flow_norm == "batchnorm" for s_ in steps):  # (the level node is actnorm-only: steps run one by one)
             return False
         a0 = steps[0].affine
         for s_ in steps:
@@ -221,7 +233,8 @@ class ListGlow(nn.Module):
             for k, s in enumerate(steps):
                 w1, w2, w3 = wts[l, k] = tuple(s.affine.net[i].conv.weight for i in (0, 2, 4))
                 shapes[l][2].append((int(w1.shape[0]), int(w1.shape[2]), int(w2.shape[2]), int(w3.shape[2]),
-                                     K.ACT[s.affine.non_lin], s.flow_norm != "batchnorm"))
+                                     K.ACT[s.affine.non_lin], True))   # (every GlowStep of the model is an ops
+                # node now, batch-norm steps included; plan_packs keeps the field for a step run as separate modules)
         conv, nets, dense = plan_packs(*(int(v) for v in x_shape), shapes, torch.is_grad_enabled())
         with K.PackBatch() as pb:
             dbufs = [pb.dense(wts[step][int(field[1]) - 1], *how) for step, field, how in dense]
@@ -242,8 +255,10 @@ class ListGlow(nn.Module):
             kw[step][field] = buf
         return {levels[l][1][k]: K.StepPacks(**kw[l, k]) for l, k in wts}
 
-    def f(self, x, condition, logdet):
-        """Flow/glow.py:105-117 (same order of operations; per-level batching of the tiny parameter algebra)."""
+    def f(self, x, condition, logdet, steps=1, update_running=True):
+        """Flow/glow.py:105-117 (same order of operations; per-level batching of the tiny parameter algebra).
+        `steps`, `update_running`: for the batch-norm steps (GlowStep.forward)."""
+        n_steps = steps  # (`steps` below: the GlowSteps of a level)
         z = x
         dls, const = [], 0
         packs = self._packed_weights(x.shape, condition)
@@ -269,9 +284,11 @@ class ListGlow(nn.Module):
             for k, step in enumerate(steps_run):
                 if W is not None:
                     z, _ = step(z, condition[l], logdet=logdet, reverse=False, Wm=Wk[k], defer_logdet=dls,
-                                packs=None if packs is None else packs[step])
+                                packs=None if packs is None else packs[step], steps=n_steps,
+                                update_running=update_running)
                 else:
-                    z, logdet = step(z, condition[l], logdet=logdet, reverse=False)
+                    z, logdet = step(z, condition[l], logdet=logdet, reverse=False, steps=n_steps,
+                                     update_running=update_running)
                 D.check("f.l%d.k%d.z" % (l, k), z)
                 if dls:
                     D.check("f.l%d.k%d.dl" % (l, k), dls[-1])
@@ -279,8 +296,8 @@ class ListGlow(nn.Module):
                 const = const + c  # (the level node adds the ActNorm terms H*W * sum logs itself)
             elif W is not None:
                 # ActNorm logs are read AFTER the steps ran: the first training call initialises them in place
-                logs = torch.stack([s.norm.logs.reshape(-1) for s in steps])
-                const = const + c + logs.sum() * (z.shape[2] * z.shape[3])
+                logs = [s.norm.logs.reshape(-1) for s in steps if s.flow_norm != "batchnorm"]
+                const = const + c + (torch.stack(logs).sum() * (z.shape[2] * z.shape[3]) if logs else 0)
             if split is not None:
                 z, logdet = split(z, condition[l], logdet=logdet, reverse=False)
                 D.check("f.l%d.split.z" % l, z); D.check("f.l%d.split.logdet" % l, logdet)
@@ -303,7 +320,7 @@ class ListGlow(nn.Module):
         with torch.no_grad():
             for _, steps, _ in self._level_steps():
                 ics = [s.invconv for s in steps]
-                if all(ic.LU_decomposed for ic in ics) and not any(s.flow_norm == "batchnorm" for s in steps):
+                if all(ic.LU_decomposed for ic in ics):
                     l_mask, eye = ics[0].l_mask, ics[0].eye
                     Lm = torch.stack([ic.lower for ic in ics]) * l_mask + eye
                     U = torch.stack([ic.upper for ic in ics]) * l_mask.t() + torch.diag_embed(
@@ -343,21 +360,28 @@ class ListGlow(nn.Module):
         objective = torch.full((b,), -np.log(n_bins) * (c * h * w), device=x.device, dtype=torch.float32)
         return x + noise, objective
 
-    def _base_params(self, base_condition, n, device):
+    def _base_params(self, base_condition, n, device, steps=1, update_running=True):
+        """`steps`, `update_running`: for the BatchNorm2d layers of the prior net under --base_norm batchnorm
+        (Conv2dNorm.forward): statistics per step, as the reference's per-timestep calls take them."""
         if self.learn_prior:
-            h = self.prior[0](base_condition.contiguous(), act=self.non_lin_glow)
-            h = self.prior[2](h, act=self.non_lin_glow)
+            h = self.prior[0](base_condition.contiguous(), act=self.non_lin_glow, steps=steps,
+                              update_running=update_running)
+            h = self.prior[2](h, act=self.non_lin_glow, steps=steps, update_running=update_running)
             return self.prior[4](h)  # [n, 2*Cz, h, w]: "split" halves = (mean, log_scale)
         return torch.zeros((n, 2 * self.z_shape[0]) + self.z_shape[1:], device=device)
 
-    def log_prob(self, x, condition, base_condition, logdet=0, noise=None):
-        """Flow/glow.py:128-141.  `noise` optionally pins the dequantisation draw (tests / parity runs)."""
+    def log_prob(self, x, condition, base_condition, logdet=0, noise=None, steps=1, update_running=True):
+        """Flow/glow.py:128-141.  `noise` optionally pins the dequantisation draw (tests / parity runs).
+        `steps`: x holds `steps` step-major groups of frames (the driver's time-batched call); every batch normalisation
+        of the flow and of its prior net (--flow_norm / --base_norm batchnorm) takes its statistics per group and updates
+        its running statistics once per group, as the reference's per-timestep calls do.  `update_running=False` leaves
+        the running statistics alone (the driver's extra data-initialising call)."""
         x, obj_unif = self.uniform_binning_correction(x, noise)
         assert isinstance(condition, list), "Condition is not a list, make sure it fits L"
-        z, obj = self.f(x, condition, logdet)
+        z, obj = self.f(x, condition, logdet, steps, update_running)
         D.check("f.obj", obj)
         obj = obj + obj_unif
-        params = self._base_params(base_condition, x.shape[0], x.device)
+        params = self._base_params(base_condition, x.shape[0], x.device, steps, update_running)
         D.check("base_params", params)
         obj = obj + K.GaussLogpFn.apply(z.contiguous(), params, 1, 1)
         return z, -obj

@@ -18,6 +18,10 @@ def add_logdet(logdet, d, sign=1.0):
     return logdet + d if sign > 0 else logdet - d
 
 
+# (code, slope) of the activations the fused per-step BatchNorm kernels apply (Utils.modules.per_step_batchnorm_act)
+_BN_ACT = {"none": (0, 0.0), "relu": (1, 0.0), "leakyrelu": (2, 0.2)}
+
+
 class ActNorm(nn.Module):
     """Flow/glow_modules.py:10-54 — per-channel affine with data dependent init on the first TRAINING call.
     `initialized` is a uint8 buffer (part of checkpoints); the host mirrors it in `_init_done` to avoid the
@@ -135,13 +139,25 @@ class Conv2dNorm(nn.Module):
             an.set_from_stats(*K.channel_stats(u))
         an.mark_initialized()
 
-    def forward(self, input, input2=None, act="none"):
+    def forward(self, input, input2=None, act="none", steps=1, update_running=True):
+        """`steps` > 1 (batchnorm, training mode): `input` is step-major [steps*B, ...] and the BatchNorm2d takes the
+        statistics of each step's B frames, updating its running statistics once per step, as the reference's per-timestep
+        calls do; `update_running=False`: batch statistics, running statistics left alone."""
         if self.norm == "actnorm":
             self.maybe_init(input, input2)
             return K.conv_ep(input, input2, self.conv.weight, self.norm_type.bias, self.norm_type.logs, 1, K.ACT[act])
         out = K.conv_ep(input, input2, self.conv.weight, self.conv.bias, None, 3, 0)
         if self.norm == "batchnorm":
-            out = self.norm_type(out)
+            bn = self.norm_type
+            if bn.training and not update_running:
+                out = torch.nn.functional.batch_norm(out, None, None, bn.weight, bn.bias, True, 0.0, bn.eps)
+            elif bn.training and steps > 1:
+                from Utils.modules import per_step_batchnorm, per_step_batchnorm_act
+                if out.is_cuda and out.dtype == torch.float32 and act in _BN_ACT:
+                    return per_step_batchnorm_act(bn, out, steps, *_BN_ACT[act])  # the activation is fused
+                out = per_step_batchnorm(bn, out, steps)
+            else:
+                out = bn(out)
         if act == "relu":
             out = torch.relu(out)
         elif act == "leakyrelu":
@@ -326,8 +342,15 @@ class Split2d(nn.Module):
 
 
 class BatchNormFlow(nn.Module):
-    """Flow/glow_modules.py:56-104 — optional (non-default) flow normalisation; plain torch ops as scoped in
-    SURVEY.md §2 row 1."""
+    """Flow/glow_modules.py:56-104 — the flow normalisation of `--flow_norm batchnorm`: per-element (channel AND pixel)
+    batch normalisation over the batch axis whose log-det depends on the data.  `momentum` weights the OLD running value
+    (the opposite of nn.BatchNorm2d; 0.0 = "running = the last call's statistics").
+
+    `forward(input, logdet, reverse, steps=1, update_running=True)`: `input` is step-major [steps*B, C, H, W] and the
+    statistics are those of EACH step's B rows, with the running buffers updated once per step in step order, which is
+    what the reference's `steps` per-timestep calls compute.  `update_running=False` leaves the running buffers alone
+    (the driver's extra data-initialising call).  Device fp32 tensors run on rfn_bnflow_*; the torch expression is the CPU
+    route (and the rare eval-mode call that needs gradients)."""
 
     def __init__(self, x_size, momentum=0.1, eps=1e-5):
         super().__init__()
@@ -338,15 +361,44 @@ class BatchNormFlow(nn.Module):
         self.momentum, self.eps = momentum, eps
         self.register_buffer("running_mean", torch.zeros(size))
         self.register_buffer("running_var", torch.ones(size))
+        self._coef = {}
 
-    def forward(self, input, logdet, reverse):
+    def _running(self, steps, device):
+        """(running_mean, running_var, coef [steps] on the device, decay) for rfn_hip.ops.BatchNormFlowFn"""
+        key = (steps, float(self.momentum), str(device))
+        if key not in self._coef:
+            coef, decay = K.bnflow_coef(steps, self.momentum)
+            self._coef = {key: (coef.to(device=device, dtype=torch.float32), decay)}
+        coef, decay = self._coef[key]
+        return self.running_mean, self.running_var, coef, decay
+
+    def forward(self, input, logdet, reverse, steps=1, update_running=True):
+        hip = input.is_cuda and input.dtype == torch.float32
         if self.training and not reverse:
-            mean = input.mean(0)
-            var = (input - mean).pow(2).mean(0) + self.eps
-            self.running_mean.mul_(self.momentum).add_(mean.data * (1 - self.momentum))
-            self.running_var.mul_(self.momentum).add_(var.data * (1 - self.momentum))
-        else:
-            mean, var = self.running_mean, self.running_var
+            SB = input.shape[0]
+            assert SB % steps == 0, "BatchNormFlow: %d rows are not %d steps" % (SB, steps)
+            B = SB // steps
+            if hip:
+                z, dl = K.BatchNormFlowFn.apply(input, self.log_gamma, self.beta, steps, float(self.eps),
+                                                self._running(steps, input.device) if update_running else None)
+            else:
+                x = input.reshape(steps, B, *input.shape[1:])
+                mean = x.mean(1, keepdim=True)                              # [steps, 1, C, H, W]
+                var = (x - mean).pow(2).mean(1, keepdim=True) + self.eps
+                if update_running:
+                    with torch.no_grad():
+                        for s in range(steps):  # glow_modules.py:81-87, once per step, in step order
+                            self.running_mean.mul_(self.momentum).add_(mean[s] * (1 - self.momentum))
+                            self.running_var.mul_(self.momentum).add_(var[s] * (1 - self.momentum))
+                z = (torch.exp(self.log_gamma) * ((x - mean) / var.sqrt()) + self.beta).reshape(input.shape)
+                dl = torch.sum((self.log_gamma - 0.5 * torch.log(var)).reshape(steps, -1), dim=1)
+            if logdet is None:
+                return z, None
+            return z, logdet + dl.view(steps, 1).expand(steps, B).reshape(SB)  # dl[s] for every row of step s
+        if hip and not (torch.is_grad_enabled() and (input.requires_grad or self.log_gamma.requires_grad)):
+            z, dl = K.bnflow_apply(input, self.log_gamma, self.beta, self.running_mean, self.running_var, reverse)
+            return z, add_logdet(logdet, dl)  # (dl carries the reverse direction's sign)
+        mean, var = self.running_mean, self.running_var
         dlogdet = torch.sum(self.log_gamma - 0.5 * torch.log(var))
         if not reverse:
             z = torch.exp(self.log_gamma) * ((input - mean) / var.sqrt()) + self.beta

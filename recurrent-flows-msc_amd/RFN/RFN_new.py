@@ -232,11 +232,13 @@ class RFN(nn.Module):
         noise = torch.cat(noise_t, dim=0) if noise_t else None
         if self.training and self._flow_needs_init():
             with torch.no_grad():  # data dependent init on the t = 1 batch, as the reference's first call does
+                # (batch-norm flow / prior: the reference updates the running statistics once per timestep, not once more
+                # for this call)
                 self.flow.log_prob(xs[:B], [c[:B] for c in conds], base[:B], 0,
-                                   None if noise is None else noise[:B])
+                                   None if noise is None else noise[:B], update_running=False)
         for j, c in enumerate(conds):
             DBG.check("cond%d" % j, c)
-        _, nll = self.flow.log_prob(xs, conds, base, logdet, noise)
+        _, nll = self.flow.log_prob(xs, conds, base, logdet, noise, steps=T - 1)
         DBG.check("nll", nll)
         nll_loss = nll.view(T - 1, B).sum(0)
         if kl_terms:
