@@ -537,6 +537,31 @@ int rfn_bnflow_bwd_f32(const float* x, const float* log_gamma, const float* gz, 
 int rfn_bnflow_apply_f32(const float* x, const float* log_gamma, const float* beta, const float* run_mean,
                          const float* run_var, float* y, float* dl, int N, int E, int reverse, rfn_stream_t stream);
 
+/* ---- Mixture of discretized logistics, the likelihood of the SRNN baseline (Utils/discretize_logits.py; DESIGN.md
+ * section 19 is the definition).  x [N,C,HW] in [-1,1], C in {1,3}; l [N,Cl,HW] with Cl = M (1 + P C), P = 3 for C = 3
+ * (mean, log-scale, coefficient) and 2 for C = 1; any M >= 1; dense fp32 NCHW.  Channel m is the mixture logit of
+ * component m, channel M + (c P + j) M + m parameter j of colour channel c.  For C = 3 the tanh of the coefficients of
+ * colour rows 0, 1, 2 enter as mean_1 += t0 x_0, mean_2 += t1 x_0 + t2 x_1.
+ * rfn_mol_nll_fwd: nll_pix [N,HW] = -log sum_m softmax(logit)_m prod_c P(x_c | m) with log-scales clamped at -7, bins of
+ *   +-1/255, the edge branches for x < -0.999 and x > 0.999, log(cdf_delta) where cdf_delta > 1e-5 and the mid-bin density
+ *   (log_pdf_mid - log 127.5) otherwise; nll [N] = the sum over a frame's pixels: each workgroup's 256 pixels (all of
+ *   one frame), then the rfn_mol_part_floats(N, HW) / N partials of the frame in index order -- no atomics, and the bits
+ *   of a frame's sum depend on that frame alone.  lse [N,HW] = log sum_m exp(logit_m + sum_c log P(x_c | m)), kept for
+ *   the backward.  part: rfn_mol_part_floats(N, HW) floats of scratch.  Two launches.
+ * rfn_mol_nll_bwd: dl [N,Cl,HW] = up * d nll_pix / d l, up [N] (up_per_pixel = 0) or [N,HW] (1); recomputed from x, l and
+ *   the forward's lse (the responsibility of a component is exp(its term - lse): exactly 1 for M = 1).  A selected branch alone receives gradient; none passes a binding clamp (log-scale < -7).
+ *   One launch; every element of dl is written.
+ * rfn_mol_sample: u_mix [N,HW,M], u_x [N,HW,C] uniforms in (0,1); component argmax_m(logit_m - log(-log u_mix_m)), the
+ *   lowest index on a tie; x_c = clamp(mean_c + exp(max(log-scale_c, -7)) (log u_c - log(1 - u_c)) + the coefficient
+ *   terms on the clamped x_0, x_1, -1, 1); out [N,C,HW], not rounded to 8 bits.  One launch. */
+long rfn_mol_part_floats(int N, int HW);
+int rfn_mol_nll_fwd(const float* x, const float* l, float* nll_pix, float* lse, float* nll, float* part, int N, int C, int M,
+                    int HW, rfn_stream_t stream);
+int rfn_mol_nll_bwd(const float* x, const float* l, const float* lse, const float* up, int up_per_pixel, float* dl, int N,
+                    int C, int M, int HW, rfn_stream_t stream);
+int rfn_mol_sample(const float* l, const float* u_mix, const float* u_x, float* out, int N, int C, int M, int HW,
+                   rfn_stream_t stream);
+
 /* ---- a9  ConvLSTMLayer.forward gate update  (Utils/modules.py:370-377): cc = conv output [N,4*Hc,HW] in gate order
  * i,f,o,g;  i=σ(cc_i+Wci∘c) f=σ(cc_f+Wcf∘c) g=tanh(cc_g) c'=f∘c+i∘g o=σ(cc_o+Wco∘c') h'=o∘tanh(c').
  * Wci/Wcf/Wco [Hc*HW] may be NULL (== 0, which is what the reference trains with).  gates [N,4*Hc,HW] receives the

@@ -43,6 +43,9 @@ class EarlyStopping:
 
 
 class Solver(object):
+    # what a sibling trainer (SRNN/trainer.py) replaces: the checkpoint files of train() and the model of build()
+    checkpoint_names = ("rfn.pt", "rfn_best_model.pt")
+
     def __init__(self, args):
         self.args = args
         for k in ("n_bits", "n_epochs", "learning_rate", "verbose", "batch_size", "patience_lr", "factor_lr", "min_lr",
@@ -80,7 +83,7 @@ class Solver(object):
         if self.rank == 0:
             os.makedirs(self.path + "png_folder", exist_ok=True)
             os.makedirs(self.path + "model_folder", exist_ok=True)
-        self.model = RFN(self.args).to(self.device)
+        self.model = self.make_model().to(self.device)
         rdist.broadcast_module_state(self.model)
         self.reducer = rdist.GradBucketReducer(list(self.model.named_parameters()))
         self.optimizer = self.make_optimizer(self.model.parameters(), self.learning_rate, **self.guard_kwargs())
@@ -88,6 +91,9 @@ class Solver(object):
                                                                     factor=self.factor_lr, min_lr=self.min_lr)
         self.earlystopping = EarlyStopping(min_delta=0, patience=self.patience_es, verbose=self.verbose)
         self.counter, self.stop = 0, False
+
+    def make_model(self):
+        return RFN(self.args)
 
     def guard_kwargs(self):
         """the guard's keywords for `make_optimizer`, from --grad_clip_norm / --skip_nonfinite_steps; the batch-sharded
@@ -404,13 +410,13 @@ class Solver(object):
             # (host scalars: all_reduce_mean_scalars moves them to the GPU when the group is RCCL-only)
             epoch_loss, stop_flag = rdist.all_reduce_mean_scalars(torch.tensor(epoch_loss), torch.tensor(float(self.stop)))
             self.stop = stop_flag > 0.0
-            self.checkpoint("rfn.pt", self.epoch_i, epoch_loss)   # (collective: gathers the sharded initial states)
+            self.checkpoint(self.checkpoint_names[0], self.epoch_i, epoch_loss)   # (collective: gathers the sharded initial states)
             stop = self.earlystopping.step(self.epoch_i, epoch_loss)
             if stop or self.stop:
                 break
             if self.earlystopping.best_loss < self.best_loss and self.epoch_i > 50:
                 self.best_loss = self.earlystopping.best_loss
-                self.checkpoint("rfn_best_model.pt", self.epoch_i, epoch_loss)
+                self.checkpoint(self.checkpoint_names[1], self.epoch_i, epoch_loss)
             if self.scheduler_type == "plateau":
                 self.scheduler.step(epoch_loss)
             if self.verbose:

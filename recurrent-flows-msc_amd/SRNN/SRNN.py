@@ -1,0 +1,322 @@
+"""SRNN baseline — host mirror of the reference's SRNN/SRNN.py: same constructor arguments read from `args`, same
+state_dict keys and shapes, same layer structure, and the reference's behaviour where it differs from its comments
+(`store_ztx` holds zprevx; the non-smoothing encoder runs phi_x_t a second time per step).
+
+On the package's kernels: the two ConvLSTMs (Utils.ConvLSTM) and, for `loss_type == "mol"`, the mixture of discretized
+logistics: the logits of all T-1 frames are collected in the time loop and go through rfn_hip.ops.mol_nll in ONE launch
+after it (the likelihood has no state across steps); the per-frame sums are added over time in step order.  Strided
+convolutions, ConvTranspose2d, Linear and the norm layers are PyTorch modules.
+
+Every method that draws takes `draws=None`: a list of tensors (or (kind, tensor) pairs, as the fixtures store them)
+consumed in the order the reference draws — standard normals of each rsample, the uniforms of the dequantisation and of
+the mixture sampler (u_mix [N,H,W,M], then u_x [N,H,W,C]).  Not here: elbo_importance_weighting."""
+import numpy as np
+import torch
+import torch.distributions as td
+import torch.nn as nn
+
+from Utils import ConvLSTM, NormLayer
+from Utils import DiscretizedMixtureLogits, DiscretizedMixtureLogits_1d
+from Utils import Flatten, UnFlatten, batch_reduce, get_layer_size
+
+
+class _Draws:
+    """the recorded draws in order, or fresh ones"""
+
+    def __init__(self, draws, device):
+        self.q = None if draws is None else [d[1] if isinstance(d, (tuple, list)) else d for d in draws]
+        self.device = device
+
+    def _next(self, shape):
+        t = self.q.pop(0)
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError("recorded draw has shape %s, the model asks for %s" % (tuple(t.shape), tuple(shape)))
+        return t.to(self.device)
+
+    def normal(self, shape):
+        return torch.randn(tuple(shape), device=self.device) if self.q is None else self._next(shape)
+
+    def uniform(self, shape, lo, hi):
+        if self.q is None:
+            return torch.empty(tuple(shape), device=self.device).uniform_(lo, hi)
+        return self._next(shape)
+
+    def rsample(self, dist):
+        return dist.loc + dist.scale * self.normal(dist.loc.shape)
+
+    def done(self):
+        if self.q:
+            raise RuntimeError("%d recorded draws left over" % len(self.q))
+
+
+def _mlp(n_in, z_dim, softplus):
+    layers = [nn.Linear(n_in, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, z_dim)]
+    return nn.Sequential(*(layers + [nn.Softplus()] if softplus else layers))
+
+
+class SRNN(nn.Module):
+    def __init__(self, args):
+        super().__init__()
+        norm_type = args.norm_type
+        self.batch_size = args.batch_size
+        self.u_dim = args.condition_dim
+        self.a_dim = args.a_dim
+        self.x_dim = args.x_dim
+        self.enable_smoothing = args.enable_smoothing
+        self.h_dim, self.z_dim = h_dim, z_dim = args.h_dim, args.z_dim
+        self.loss_type = args.loss_type
+        self.beta = 1
+        bu, cu, hu, wu = self.u_dim
+        bx, cx, hx, wx = self.x_dim
+        self.mse_criterion = nn.MSELoss(reduction="none")
+        self.res_q = args.res_q
+        self.bits = args.n_bits
+        self.dequantize = args.dequantize
+        self.preprocess_range = args.preprocess_range
+        self.n_logistics = args.n_logistics
+
+        def block(conv, c):
+            return [conv, NormLayer(c, norm_type), nn.ReLU()]
+
+        self.phi_x_t_channels = 256
+        self.phi_x_t = nn.Sequential(
+            *block(nn.Conv2d(cx, 64, kernel_size=3, stride=2, padding=1), 64),
+            *block(nn.Conv2d(64, 128, kernel_size=3, stride=2, padding=1), 128),
+            *block(nn.Conv2d(128, 256, kernel_size=3, stride=2, padding=1), 256),
+            *block(nn.Conv2d(256, self.phi_x_t_channels, kernel_size=3, stride=1, padding=1), self.phi_x_t_channels))
+        h, w = get_layer_size([hu, wu], kernels=[3, 3, 3], paddings=[1, 1, 1], strides=[2, 2, 2], dilations=[1, 1, 1])
+        self.h, self.w = h, w
+
+        phi_z_channels = 128
+        self.phi_z = nn.Sequential(
+            nn.Linear(z_dim, phi_z_channels * h * w), nn.ReLU(),
+            nn.Linear(phi_z_channels * h * w, phi_z_channels * h * w), nn.ReLU(),
+            UnFlatten(phi_z_channels, h, w),
+            *block(nn.Conv2d(phi_z_channels, phi_z_channels, kernel_size=3, stride=1, padding=1), phi_z_channels))
+
+        enc_in = phi_z_channels + (self.a_dim if self.enable_smoothing else self.h_dim + self.phi_x_t_channels)
+        self.enc = nn.Sequential(*block(nn.Conv2d(enc_in, 256, kernel_size=3, stride=2, padding=1), 256), Flatten())
+        n_flat = 256 * h // 2 * w // 2
+        self.enc_mean = _mlp(n_flat, z_dim, False)
+        self.enc_std = _mlp(n_flat, z_dim, True)
+
+        self.prior = nn.Sequential(*block(nn.Conv2d(h_dim + phi_z_channels, 256, kernel_size=3, stride=2, padding=1), 256),
+                                   Flatten())
+        self.prior_mean = _mlp(n_flat, z_dim, False)
+        self.prior_std = _mlp(n_flat, z_dim, True)
+
+        def up(cin, cout):
+            return nn.ConvTranspose2d(cin, cout, kernel_size=4, stride=2, padding=1, output_padding=0)
+
+        self.dec = nn.Sequential(
+            *block(up(h_dim + phi_z_channels, 512), 512),
+            *block(nn.Conv2d(512, 256, kernel_size=3, stride=1, padding=1), 256),
+            *block(up(256, 64), 64),
+            *block(nn.Conv2d(64, 64, kernel_size=3, stride=1, padding=1), 64),
+            *block(up(64, 32), 32))
+
+        self.z_0 = nn.Parameter(torch.zeros(self.batch_size, z_dim))
+        self.z_0x = nn.Parameter(torch.zeros(self.batch_size, z_dim))
+        self.h_0 = nn.Parameter(torch.zeros(self.batch_size, self.h_dim, h, w))
+        self.c_0 = nn.Parameter(torch.zeros(self.batch_size, self.h_dim, h, w))
+        self.a_0 = nn.Parameter(torch.zeros(self.batch_size, self.a_dim, h, w))
+        self.ca_0 = nn.Parameter(torch.zeros(self.batch_size, self.a_dim, h, w))
+
+        self.lstm_h = ConvLSTM(in_channels=self.phi_x_t_channels, hidden_channels=self.h_dim, kernel_size=[3, 3],
+                               bias=True, peephole=True)
+        # (hidden_channels = h_dim, as the reference has it: smoothing needs a_dim == h_dim there too)
+        self.lstm_a = ConvLSTM(in_channels=self.phi_x_t_channels + self.h_dim, hidden_channels=self.h_dim,
+                               kernel_size=[3, 3], bias=True, peephole=True)
+        if self.loss_type == "mol":
+            per, lik = (10, DiscretizedMixtureLogits) if cx > 1 else (3, DiscretizedMixtureLogits_1d)
+            self.dec_mean = nn.Sequential(nn.Conv2d(32, self.n_logistics * per, kernel_size=3, stride=1, padding=1))
+            self.likelihood = lik(self.n_logistics)
+        else:
+            self.variance = nn.Parameter(torch.ones([1]))
+            if self.preprocess_range == "0.5":
+                self.dec_mean = nn.Sequential(nn.Conv2d(32, cx, kernel_size=3, stride=1, padding=1), nn.Tanh())
+            elif self.preprocess_range == "1.0":
+                self.dec_mean = nn.Sequential(nn.Conv2d(32, cx, kernel_size=3, stride=1, padding=1), nn.Sigmoid())
+        if self.loss_type == "gaussian" and not self.dequantize:
+            raise ValueError("loss_type 'gaussian' needs --dequantize: the reference's loss reads the dequantisation "
+                             "term it only computes with it")
+        self.D = args.num_shots + 1
+        self.overshot_w = args.overshot_w
+
+    # ------------------------------------------------------------------------------------------------ pieces
+    def get_inits(self):
+        return self.h_0, self.c_0, self.z_0, self.z_0x, self.a_0, self.ca_0, 0, 0, 0
+
+    def uniform_binning_correction(self, x, draws=None):
+        b, c, h, w = x.size()
+        n_bins = 2 ** self.bits
+        d = draws if isinstance(draws, _Draws) else _Draws(draws, x.device)
+        x_noise = x + d.uniform(x.shape, 0, 1.0 / n_bins)
+        objective = -np.log(n_bins) * (c * h * w) * torch.ones(b, device=x.device)
+        return x_noise, objective
+
+    def _prior_dist(self, ht, z):
+        prior_t = self.prior(torch.cat([ht, self.phi_z(z)], 1))
+        return td.Normal(self.prior_mean(prior_t), self.prior_std(prior_t))
+
+    def _decode(self, ht, z):
+        return self.dec_mean(self.dec(torch.cat([ht, self.phi_z(z)], 1)))
+
+    def _generate(self, dec_mean_t, d):
+        """the frame a decoder output stands for: a draw from the mixture, or the output itself"""
+        if self.loss_type != "mol":
+            return dec_mean_t
+        lik = self.likelihood(logits=dec_mean_t)
+        if d.q is None:
+            return lik.sample()
+        N, _, H, W = dec_mean_t.shape
+        u_mix = d.uniform((N, H, W, self.n_logistics), 1e-5, 1. - 1e-5)
+        return lik.sample(u_mix, d.uniform((N, H, W, lik.channels), 1e-5, 1. - 1e-5))
+
+    def _smoothing_states(self, store_ht, feature_of, t, aprev, caprev):
+        store_at = [None] * (t - 1)
+        for i in range(1, t):
+            lstm_a_input = torch.cat([store_ht[t - i - 1], feature_of(t - i)], 1)
+            _, aprev, caprev = self.lstm_a(lstm_a_input.unsqueeze(1), aprev, caprev)
+            store_at[t - i - 1] = aprev
+        return store_at
+
+    # ------------------------------------------------------------------------------------------------ loss
+    def loss(self, xt, draws=None):
+        b, t, c, h, w = xt.shape
+        d = _Draws(draws, xt.device)
+        hprev, cprev, zprev, zprevx, aprev, caprev, _, kl_loss, nll_loss = self.get_inits()
+        feats = [self.phi_x_t(xt[:, i]) for i in range(t)]
+        store_ht = []
+        for i in range(1, t):
+            _, hprev, cprev = self.lstm_h(feats[i - 1].unsqueeze(1), hprev, cprev)
+            store_ht.append(hprev)
+        if self.enable_smoothing:
+            store_at = self._smoothing_states(store_ht, lambda i: feats[i], t, aprev, caprev)
+
+        store_ztx_mean, store_ztx_std, store_ztx, logits = [], [], [], []
+        for i in range(1, t):
+            ht = store_ht[i - 1]
+            if self.enable_smoothing:
+                enc_t = self.enc(torch.cat([store_at[i - 1], self.phi_z(zprevx)], 1))
+            else:
+                enc_t = self.enc(torch.cat([ht, self.phi_z(zprevx), self.phi_x_t(xt[:, i])], 1))
+            enc_std_t = self.enc_std(enc_t)
+            # (res_q: the prior is conditioned on zprevx, as in the reference)
+            prior_dist = self._prior_dist(ht, zprevx if self.res_q else zprev)
+            enc_mean_t = self.enc_mean(enc_t)
+            if self.res_q:
+                enc_mean_t = prior_dist.loc + enc_mean_t
+            enc_dist = td.Normal(enc_mean_t, enc_std_t)
+            z_tx = d.rsample(enc_dist)
+            z_t = d.rsample(prior_dist)
+            store_ztx_mean.append(enc_mean_t)
+            store_ztx_std.append(enc_std_t)
+            store_ztx.append(zprevx)   # (the reference stores z_tx and overwrites it with zprevx)
+            dec_mean_t = self._decode(ht, z_tx)
+            zprevx, zprev = z_tx, z_t
+            if self.D == 1:
+                kl_loss = kl_loss + self.beta * td.kl_divergence(enc_dist, prior_dist)
+            x_i = xt[:, i]
+            if self.loss_type == "bernoulli":
+                nll_loss = nll_loss - batch_reduce(td.Bernoulli(probs=dec_mean_t).log_prob(x_i))
+            elif self.loss_type == "gaussian":
+                x, nll_unif = self.uniform_binning_correction(x_i, d)
+                scale = nn.functional.softplus(self.variance) * torch.ones_like(dec_mean_t)
+                nll_loss = nll_loss - batch_reduce(td.Normal(dec_mean_t, scale).log_prob(x)) - nll_unif
+            elif self.loss_type == "mse":
+                nll_loss = nll_loss + batch_reduce(self.mse_criterion(dec_mean_t, x_i))
+            elif self.loss_type == "mol":
+                logits.append(dec_mean_t)
+            else:
+                raise ValueError("undefined loss %r" % (self.loss_type,))
+        if self.loss_type == "mol":
+            from rfn_hip import ops as K
+            x_all = xt[:, 1:].transpose(0, 1).reshape((t - 1) * b, c, h, w)   # step-major, like the collected logits
+            nll_steps = K.mol_nll(x_all.detach(), torch.cat(logits, 0), reduce="frame").view(t - 1, b)
+            for s in range(t - 1):   # fixed order
+                nll_loss = nll_loss + nll_steps[s]
+
+        if self.D > 1:
+            kl_loss = 0
+            for i in range(1, t):
+                overshot_loss = 0
+                idt = i - 1
+                zprev = store_ztx[idt]
+                D = min(t - i, self.D)
+                for k in range(D):
+                    prior_dist = self._prior_dist(store_ht[idt + k], zprev)
+                    zprev = d.rsample(prior_dist)
+                    enc_mean, enc_std = store_ztx_mean[idt + k], store_ztx_std[idt + k]
+                    if k > 0:   # the encoder is not to conform to the prior beyond the first shot
+                        enc_mean, enc_std = enc_mean.detach(), enc_std.detach()
+                    overshot_loss = overshot_loss + self.overshot_w * td.kl_divergence(td.Normal(enc_mean, enc_std),
+                                                                                        prior_dist)
+                kl_loss = kl_loss + 1 / D * overshot_loss * self.beta
+        d.done()
+        return batch_reduce(kl_loss).mean(), nll_loss.mean()
+
+    # ------------------------------------------------------------------------------------------------ generation
+    def predict(self, xt, n_predictions, n_conditions, draws=None):
+        b, t, c, h, w = xt.shape
+        assert n_conditions <= t, "n_conditions > t, number of conditioned frames is greater than number of frames"
+        d = _Draws(draws, xt.device)
+        hprev, cprev, zprev, zprevx, aprev, caprev, _, _, _ = self.get_inits()
+        true_x = [xt[:, 0].detach()]
+        store_ht = []
+        for i in range(1, n_conditions):
+            _, hprev, cprev = self.lstm_h(self.phi_x_t(xt[:, i - 1]).unsqueeze(1), hprev, cprev)
+            store_ht.append(hprev)
+        for i in range(1, n_conditions):
+            zprev = d.rsample(self._prior_dist(store_ht[i - 1], zprev))
+            true_x.append(xt[:, i].detach())
+        prediction = xt[:, n_conditions - 1]
+        predictions = []
+        for i in range(n_predictions):
+            _, ht, ct = self.lstm_h(self.phi_x_t(prediction).unsqueeze(1), hprev, cprev)
+            z_t = d.rsample(self._prior_dist(ht, zprev))
+            prediction = self._generate(self._decode(ht, z_t), d)
+            zprev, hprev, cprev = z_t, ht, ct
+            predictions.append(prediction.detach())
+        d.done()
+        return torch.stack(true_x, 0).cpu(), torch.stack(predictions, 0).cpu()
+
+    def reconstruct(self, xt, draws=None):
+        b, t, c, h, w = xt.shape
+        d = _Draws(draws, xt.device)
+        hprev, cprev, zprev, zprevx, aprev, caprev, _, _, _ = self.get_inits()
+        store_ht = []
+        for i in range(1, t):
+            _, hprev, cprev = self.lstm_h(self.phi_x_t(xt[:, i - 1]).unsqueeze(1), hprev, cprev)
+            store_ht.append(hprev)
+        if self.enable_smoothing:
+            store_at = self._smoothing_states(store_ht, lambda i: self.phi_x_t(xt[:, i]), t, aprev, caprev)
+        recons = [torch.zeros_like(xt[:, 0])]   # (frame 0 is never reconstructed)
+        for i in range(1, t):
+            ht = store_ht[i - 1]
+            if self.enable_smoothing:
+                enc_t = self.enc(torch.cat([store_at[i - 1], self.phi_z(zprevx)], 1))
+            else:
+                enc_t = self.enc(torch.cat([ht, self.phi_z(zprevx), self.phi_x_t(xt[:, i])], 1))
+            enc_mean_t = self.enc_mean(enc_t)
+            if self.res_q:
+                enc_mean_t = self._prior_dist(ht, zprevx).loc + enc_mean_t
+            z_tx = d.rsample(td.Normal(enc_mean_t, self.enc_std(enc_t)))
+            recons.append(self._generate(self._decode(ht, z_tx), d).detach())
+            zprevx = z_tx
+        d.done()
+        return torch.stack(recons, 0).cpu()
+
+    def sample(self, xt, n_samples, draws=None):
+        d = _Draws(draws, xt.device)
+        hprev, cprev, zprev, zprevx, _, _, _, _, _ = self.get_inits()
+        condition = xt[:, 0]
+        samples = []
+        for i in range(n_samples):
+            _, ht, ct = self.lstm_h(self.phi_x_t(condition).unsqueeze(1), hprev, cprev)
+            z_t = d.rsample(self._prior_dist(ht, zprev))
+            condition = self._generate(self._decode(ht, z_t), d)
+            zprev, hprev, cprev = z_t, ht, ct
+            samples.append(condition.detach())
+        d.done()
+        return torch.stack(samples, 0).cpu()

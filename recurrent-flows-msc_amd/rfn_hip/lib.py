@@ -137,6 +137,10 @@ SIGNATURES = {
     "rfn_bnflow_fwd_f32": [_c_f] * 12 + [ctypes.c_float, _c_i, _c_i, _c_i, ctypes.c_float, _c_s],
     "rfn_bnflow_bwd_f32": [_c_f] * 10 + [_c_i, _c_i, _c_i, _c_s],
     "rfn_bnflow_apply_f32": [_c_f] * 7 + [_c_i, _c_i, _c_i, _c_s],
+    "rfn_mol_part_floats": [_c_i, _c_i],
+    "rfn_mol_nll_fwd": [_c_f] * 6 + [_c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_mol_nll_bwd": [_c_f] * 4 + [_c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
+    "rfn_mol_sample": [_c_f] * 4 + [_c_i, _c_i, _c_i, _c_i, _c_s],
     "rfn_adam_chunk_elems": [],
     "rfn_adam_step_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, ctypes.c_double, _c_i, _c_s],
@@ -177,6 +181,7 @@ _RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": c
              "rfn_stepbn_kernel_label": ctypes.c_char_p, "rfn_convlstm_gates_kernel_label": ctypes.c_char_p,
              "rfn_latent_step_kernel_label": ctypes.c_char_p,
              "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_bnflow_scratch_floats": ctypes.c_long,
+             "rfn_mol_part_floats": ctypes.c_long,
              "rfn_packed_weight_size": ctypes.c_long,
              "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,
              "rfn_smallmap_packed_size": ctypes.c_long,

@@ -1900,6 +1900,101 @@ def bnflow_apply(x, log_gamma, beta, running_mean, running_var, reverse):
     return y, dl
 
 
+# ----------------------------------------------------------------------------------------------- mixture of logistics
+def mol_dims(x, l):
+    """(N, C, M, HW) of a mixture-of-discretized-logistics call, or a RuntimeError naming what does not fit.  x [N,C,H,W]
+    with C in {1, 3}; l [N,Cl,H,W] with Cl = 10 M (C = 3) or 3 M (C = 1).  Needs no device."""
+    if x.dim() != 4 or l.dim() != 4:
+        raise RuntimeError("mol: x and l must be [N,C,H,W], got %s and %s" % (tuple(x.shape), tuple(l.shape)))
+    N, C, H, W = (int(d) for d in x.shape)
+    if C not in (1, 3):
+        raise RuntimeError("mol: x must have 1 or 3 channels, got %d" % C)
+    per = 10 if C == 3 else 3
+    Cl = int(l.shape[1])
+    if (int(l.shape[0]), int(l.shape[2]), int(l.shape[3])) != (N, H, W) or Cl < per or Cl % per:
+        raise RuntimeError("mol: logits %s do not fit x %s: need [%d, %d*M, %d, %d] with M >= 1" %
+                           (tuple(l.shape), tuple(x.shape), N, per, H, W))
+    return N, C, Cl // per, H * W
+
+
+class MolNllFn(torch.autograd.Function):
+    """nll_pix [N,H,W] (reduce = 0) or its per-frame sum nll [N] (reduce = 1) of x under the mixture of discretized
+    logistics with parameters l (rfn_mol_nll_fwd / rfn_mol_nll_bwd).  Gradient into l only."""
+
+    @staticmethod
+    def forward(ctx, x, l, per_frame):
+        N, C, M, HW = mol_dims(x, l)
+        x, l = x.detach().contiguous(), l.contiguous()
+        L.dev(x, "x"), L.dev(l, "l")  # (device fp32 tensors, before anything is allocated or loaded)
+        nll_pix =torch.empty((N, x.shape[2], x.shape[3]), device=l.device, dtype=torch.float32)
+        lse = torch.empty_like(nll_pix)
+        nll = torch.empty((N,), device=l.device, dtype=torch.float32)
+        part = torch.empty((int(L.load().rfn_mol_part_floats(N, HW)),), device=l.device, dtype=torch.float32)
+        L.call("rfn_mol_nll_fwd", L.dev(x, "x"), L.dev(l, "l"), L.dev(nll_pix), L.dev(lse), L.dev(nll), L.dev(part), _i(N), _i(C),
+               _i(M), _i(HW), meta=_shell("mol_nll_fwd", l, 1))
+        ctx.save_for_backward(x, l, lse)
+        ctx.cfg = (N, C, M, HW, per_frame)
+        return nll if per_frame else nll_pix
+
+    @staticmethod
+    def backward(ctx, g):
+        x, l, lse = ctx.saved_tensors
+        N, C, M, HW, per_frame = ctx.cfg
+        g = g.contiguous()
+        dl = torch.empty_like(l)
+        L.call("rfn_mol_nll_bwd", L.dev(x), L.dev(l), L.dev(lse), L.dev(g, "grad"), _i(0 if per_frame else 1), L.dev(dl),
+               _i(N), _i(C), _i(M), _i(HW), meta=_shell("mol_nll_bwd", l, 2))
+        return None, dl, None
+
+
+def mol_nll(x, l, reduce="frame"):
+    """Negative log-likelihood of x [N,C,H,W] in [-1,1] under the mixture of discretized logistics l [N,Cl,H,W]:
+    reduce="pixel" -> [N,H,W], reduce="frame" -> [N], each frame's pixels summed in a fixed order (the bits of a frame do
+    not depend on the other frames of the call).  Differentiable in l; x must not require a gradient."""
+    if reduce not in ("frame", "pixel"):
+        raise ValueError("mol_nll: reduce must be 'frame' or 'pixel', got %r" % (reduce,))
+    if x.requires_grad:
+        raise RuntimeError("mol_nll: no gradient flows into x; pass x.detach()")
+    return MolNllFn.apply(x, l, reduce == "frame")
+
+
+def mol_sample(l, u_mix=None, u_x=None, generator=None, channels=None):
+    """Draw x [N,C,H,W] from the mixture l [N,Cl,H,W] (rfn_mol_sample); no gradient.  u_mix [N,H,W,M] and u_x [N,H,W,C]
+    are the reference's two uniform draws, in (1e-5, 1 - 1e-5); drawn here, in that order, from `generator` when not
+    given.  C is `channels`, else the last extent of u_x, else what Cl allows (10 M: RGB, 3 M: gray); a Cl that allows
+    both (30, 60, ...) needs one of the two."""
+    if l.dim() != 4:
+        raise RuntimeError("mol_sample: l must be [N,Cl,H,W], got %s" % (tuple(l.shape),))
+    N, Cl, H, W = (int(d) for d in l.shape)
+    C = channels
+    if C is None and u_x is not None:
+        C = int(u_x.shape[-1])
+    if C is None:
+        fits = [c for c, per in ((3, 10), (1, 3)) if Cl >= per and Cl % per == 0]
+        if len(fits) != 1:
+            raise RuntimeError("mol_sample: %d logit channels %s; pass channels=1 or 3" %
+                               (Cl, "fit both RGB and gray" if fits else "fit neither 10*M nor 3*M"))
+        C = fits[0]
+    per = 10 if C == 3 else 3
+    if C not in (1, 3) or Cl < per or Cl % per:
+        raise RuntimeError("mol_sample: %d logit channels do not fit %d colour channels (need %d*M)" % (Cl, C, per))
+    M = Cl // per
+    l = l.detach().contiguous()
+    L.dev(l, "l")
+    if u_mix is None:
+        u_mix = torch.empty((N, H, W, M), device=l.device, dtype=torch.float32).uniform_(1e-5, 1. - 1e-5, generator=generator)
+    if u_x is None:
+        u_x = torch.empty((N, H, W, C), device=l.device, dtype=torch.float32).uniform_(1e-5, 1. - 1e-5, generator=generator)
+    if tuple(u_mix.shape) != (N, H, W, M) or tuple(u_x.shape) != (N, H, W, C):
+        raise RuntimeError("mol_sample: uniforms must be [N,H,W,M] = %s and [N,H,W,C] = %s, got %s and %s" %
+                           ((N, H, W, M), (N, H, W, C), tuple(u_mix.shape), tuple(u_x.shape)))
+    u_mix, u_x = u_mix.contiguous(), u_x.contiguous()
+    out = torch.empty((N, C, H, W), device=l.device, dtype=torch.float32)
+    L.call("rfn_mol_sample", L.dev(l), L.dev(u_mix, "u_mix"), L.dev(u_x, "u_x"), L.dev(out), _i(N), _i(C), _i(M),
+           _i(H * W), meta=_shell("mol_sample", l, 1))
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- evaluation metrics
 def _u8_frames(t, C, H, W):
     """(tensor, pointer, frame stride) of a uint8 device tensor [..., C, H, W] seen as [N, C, H, W] frames (lib.dev stays
