@@ -39,11 +39,8 @@ extern "C" long rfn_packed_weight_size_bf16x6(int Cout, int Cin, int ks) {
 // mode + 4: NPL = 3 planes.
 // packed unit (16 bytes = 8 bf16) index: (((c16*T + tap)*NPL + plane)*2 + g)*CoutP + co ; element j <-> cin = c16*16+g*8+j
 // NPL = 2: (hi, lo) -- bf16x3;  NPL = 3: (hi, mid, lo), 24 significant bits -- "bf16x6" (six products per fp32 product)
-struct PackDesc {  // mirrors rfn_pack_desc in include/rfn_hip.h
-    const float* w;
-    float* wpk;
-    int Cout, Cin, ks, mode;
-};
+using PackDesc = rfn_pack_desc;
+static_assert(sizeof(rfn_pack_desc) == 32, "rfn_pack_desc layout is part of the ABI");
 #define PACK_TABLE_MAX 64
 struct PackTable { PackDesc d[PACK_TABLE_MAX]; };
 __global__ void pack_weights_table_b3_kernel(const PackTable t) {

@@ -108,13 +108,8 @@ __host__ __device__ constexpr int po_group_size(int NG, int NP, int idx) {
 //       (the register order of an accumulator tile)                                value w2[row][c1]
 //   conv3 row tile jt, k-step s < 16:  row R = 32jt + r = tap*C + co (zero beyond 9C), element j <-> h2 channel
 //       16s + 8(j>>2) + 4kk + (j&3)                                                 value w3[co][c2][tap]
-struct POPackDesc {   // mirrors rfn_po_pack_desc in include/rfn_hip.h
-    const float* w1;  // [256][Cin][3][3]
-    const float* w2;  // [256][256][1][1]
-    const float* w3;  // [C][256][3][3]
-    float* dst;       // total_frags * 1 KB
-    int Cin, C;
-};
+using POPackDesc = rfn_po_pack_desc;  // dst holds total_frags * 1 KB
+static_assert(sizeof(rfn_po_pack_desc) == 40, "rfn_po_pack_desc layout is part of the ABI");
 
 // exact power-of-two scale that puts m = max|x| into [2^14, 2^15) (fp16: largest finite 65504), and its inverse
 __host__ __device__ static inline void po_scale_for_max(float m, float* sc, float* inv) {

@@ -21,11 +21,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // 2x2 flow level re-pack ~60 matrices per step).  The descriptors travel by value in the kernel arguments; block (x, y)
 // works on matrix y, one fragment pair (hi, lo) per index.
 #define SM_PACK_MAX 64
-struct SmallmapPackDesc {   // mirrors rfn_smallmap_pack_desc in include/rfn_hip.h
-    const float* w;
-    float* packed;
-    int Cout, Cin, H, W, transpose, pad_;
-};
+using SmallmapPackDesc = rfn_smallmap_pack_desc;
+static_assert(sizeof(rfn_smallmap_pack_desc) == 40, "rfn_smallmap_pack_desc layout is part of the ABI");
 struct SmallmapPackTable { SmallmapPackDesc d[SM_PACK_MAX]; };
 __global__ __launch_bounds__(256) void smallmap_pack_batched_kernel(const SmallmapPackTable t) {
     const SmallmapPackDesc d = t.d[blockIdx.y];

@@ -22,8 +22,6 @@ import torch
 
 from . import lib as L
 
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 SIDE = 224                    # the public path resizes every frame to SIDE x SIDE
 MIN_SIDE, MAX_SIDE = 193, 224   # trunk input sides that end in a 7x7 map
@@ -94,14 +92,14 @@ UNITS = _build_units()
 def i3d_same(n, k, s):
     """(output extent, pad before) of one axis under TF "SAME" padding"""
     out = (ctypes.c_longlong * 2)()
-    if L.load().rfn_i3d_same(int(n), int(k), int(s), ctypes.cast(out, ctypes.c_void_p)) != 0:
+    if L.load().rfn_i3d_same(int(n), int(k), int(s), out) != 0:
         raise ValueError("i3d_same: extent, kernel and stride must be at least 1, got %s" % ((n, k, s),))
     return int(out[0]), int(out[1])
 
 
 def _pack_dims(cin, cout, k):
     out = (ctypes.c_longlong * 2)()
-    if L.load().rfn_i3d_conv_pack_dims(int(cin), int(cout), int(k), ctypes.cast(out, ctypes.c_void_p)) != 0:
+    if L.load().rfn_i3d_conv_pack_dims(int(cin), int(cout), int(k), out) != 0:
         raise RuntimeError("rfn_i3d_conv_pack_dims failed: %s" % L.load().rfn_last_error().decode())
     return int(out[0]), int(out[1])
 
@@ -286,9 +284,8 @@ def i3d_unit(w, name, x, out=None, coff=0):
     if N:
         wp, b = w.unit(name)
         with torch.cuda.device(x.device):
-            L.call("rfn_i3d_conv3d_f32", L.dev(x), _l(x.numel()), _i(N), _i(T), _i(H), _i(W), _i(u["cin"]), L.dev(wp),
-                   _l(wp.numel()), L.dev(b), _i(u["cout"]), _i(u["k"]), _i(u["stride"]), _i(1 if u["relu"] else 0),
-                   L.dev(out), _l(out.numel()), _i(coff), _i(o[4]),
+            L.call("rfn_i3d_conv3d_f32", L.dev(x), x.numel(), N, T, H, W, u["cin"], L.dev(wp), wp.numel(), L.dev(b),
+                   u["cout"], u["k"], u["stride"], 1 if u["relu"] else 0, L.dev(out), out.numel(), coff, o[4],
                    meta=("shell", "i3d_conv3d", 2.0 * (out.numel() // o[4]) * u["cout"] * u["cin"] * u["k"] ** 3,
                          "%s %s" % (name, "x".join(map(str, x.shape))), 4.0 * (x.numel() + out.numel())))
     return out
@@ -305,8 +302,8 @@ def i3d_maxpool(x, kt, khw, st, shw, out=None):
         raise ValueError("i3d_maxpool: out must be %s, got %s" % (shape, tuple(out.shape)))
     if N:
         with torch.cuda.device(x.device):
-            L.call("rfn_i3d_maxpool3d_f32", L.dev(x), _l(x.numel()), _i(N), _i(T), _i(H), _i(W), _i(C), _i(kt), _i(khw),
-                   _i(st), _i(shw), L.dev(out), _l(out.numel()),
+            L.call("rfn_i3d_maxpool3d_f32", L.dev(x), x.numel(), N, T, H, W, C, kt, khw,
+                   st, shw, L.dev(out), out.numel(),
                    meta=("shell", "i3d_maxpool3d", 0.0, "x".join(map(str, x.shape)), 4.0 * (x.numel() + out.numel())))
     return out
 
@@ -342,9 +339,8 @@ def i3d_head(w, x):
     if N:
         wp, b = w.unit(LOGITS)
         with torch.cuda.device(x.device):
-            L.call("rfn_i3d_head_f32", L.dev(x), _l(x.numel()), _i(N), _i(Tp), _i(H * W), _i(C), L.dev(wp), _l(wp.numel()),
-                   L.dev(b), _i(N_LOGITS), L.dev(out),
-                   meta=("shell", "i3d_head", 0.0, "x".join(map(str, x.shape)), 4.0 * x.numel()))
+            L.call("rfn_i3d_head_f32", L.dev(x), x.numel(), N, Tp, H * W, C, L.dev(wp), wp.numel(), L.dev(b), N_LOGITS,
+                   L.dev(out), meta=("shell", "i3d_head", 0.0, "x".join(map(str, x.shape)), 4.0 * x.numel()))
     return out
 
 
@@ -372,7 +368,7 @@ def _resize_into(videos, out):
     if N * T:
         v, p, ns = _u8_frames(videos, C, H, W)
         with torch.cuda.device(videos.device):
-            L.call("rfn_i3d_resize_u8", p, _l(ns), _i(N * T), _i(C), _i(H), _i(W), L.dev(out), _l(out.numel()),
+            L.call("rfn_i3d_resize_u8", p, ns, N * T, C, H, W, L.dev(out), out.numel(),
                    meta=("shell", "i3d_resize", 0.0, "x".join(map(str, videos.shape)), 4.0 * out.numel()))
     return out
 

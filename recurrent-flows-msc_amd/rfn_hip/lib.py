@@ -1,216 +1,135 @@
-"""ctypes binding of librfn_hip.so (the C ABI declared in include/rfn_hip.h).
+"""ctypes binding of librfn_hip.so, derived from the C header the library was built from.
 
-The library is built in-tree by `make -C recurrent-flows-msc_amd/csrc` (see __graft_entry__.build) and is the
-ONLY compute backend of this package: if it cannot be loaded, or a tensor is not a contiguous fp32 device tensor,
-the call raises — there is no CPU / eager fallback.
+`make -C recurrent-flows-msc_amd/csrc` (see __graft_entry__.build) builds the library in-tree and copies
+include/rfn_hip.h next to it.  That copy is the one declaration of the ABI on the Python side: SIGNATURES (name ->
+argtypes), RESTYPES (name -> restype) and CONSTANTS (the header's integer `#define RFN_*` limits) are parsed from it,
+and load() sets them on every entry point, so call sites pass plain Python numbers, None and addresses and ctypes
+converts (and refuses a float where the header says int).  A second build of the package carries its own copy.  Only
+the descriptor structs are written out here, because their fields are assigned by name; a host test
+(tests/test_binding_host.py) holds them against the header's typedefs.
+
+The library is the ONLY compute backend of this package: if it cannot be loaded, or a tensor is not a contiguous fp32
+device tensor, the call raises — there is no CPU / eager fallback.
 """
 import ctypes
+import functools
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librfn_hip.so")
-
-_c_f = ctypes.c_void_p  # device float*
-_c_i = ctypes.c_int
-_c_l = ctypes.c_long
-_c_s = ctypes.c_void_p  # hipStream_t
-
-# name -> argtypes (restype is int unless listed in _RESTYPES); order mirrors include/rfn_hip.h
-SIGNATURES = {
-    "rfn_abi_version": [],
-    "rfn_last_error": [],
-    "rfn_squeeze2d_f32": [_c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_channel_stats_f32": [_c_f, _c_l, _c_f, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_actnorm_invconv_fwd_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_i, _c_i, _c_i, _c_s],
-    "rfn_actnorm_invconv_bwd_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f,
-                                    _c_i, _c_i, _c_i, _c_s],
-    "rfn_invconv_weights_fwd_f32": [ctypes.c_void_p] * 5 + [_c_f, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_invconv_weights_bwd_f32": [ctypes.c_void_p] * 5 + [_c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_invconv_actnorm_rev_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv2d_fwd_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
-                           _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
-    "rfn_conv2d_kernel_label_f32": [_c_i] * 5,
-    "rfn_conv2d_fwd_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
-                              _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
-    "rfn_packed_weight_size_bf16x3": [_c_i, _c_i, _c_i],
-    "rfn_pack_conv_weight_bf16x3": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_packed_weight_size_bf16x6": [_c_i, _c_i, _c_i],
-    "rfn_pack_conv_weight_bf16x6": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv2d_fwd_bf16x6": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
-                              _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
-    "rfn_conv2d_kernel_label_bf16x3": [_c_i] * 11,
-    "rfn_conv2d_dgrad_act_rows_bf16x3": [_c_i, _c_i, _c_i, _c_i, _c_i, _c_i],
-    "rfn_conv2d_dgrad_act_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_i, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i,
-                                    _c_i, _c_i, _c_s],
-    "rfn_gather_affine_f32": [_c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i,
-                              _c_i, _c_s],
-    "rfn_affine_zeros_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f,
-                                 _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_glow_shell_fwd_f32": [_c_f, _c_l, _c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_f, _c_f, _c_f,
-                               _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_glow_shell_bwd_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_f, _c_f,
-                               _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_actnorm_invconv_bwd_ld_f32": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_i,
-                                       _c_i, _c_i, _c_s],
-    "rfn_dgrad_small_supported": [_c_i, _c_i, _c_i, _c_i, _c_i],
-    "rfn_conv3x3_smallcout_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
-                                     _c_i, _c_s],
-    "rfn_gemm_wgrad_grouped_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv3x3_wgrad_implicit_grouped_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i,
-                                                  _c_i, _c_i, _c_s],
-    "rfn_coupling_po_supported": [_c_i, _c_i, _c_i, _c_i, _c_i, _c_i],
-    "rfn_coupling_po_packed_bytes": [_c_i, _c_i],
-    "rfn_coupling_po_pack": [_c_f, _c_i, _c_s],
-    "rfn_coupling_po_fwd": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l,
-                            _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_glow_shell_fwd_ld_floats": [_c_i, _c_i, _c_i, _c_i],
-    "rfn_logdet_reduce_f32": [_c_f, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_glow_shell_fwd_kernel_label": [_c_i] * 5,
-    "rfn_glow_shell_bwd_kernel_label": [_c_i] * 4,
-    "rfn_glow_shell_supported": [_c_i] * 4,
-    "rfn_coupling_po_mask_floats": [_c_i, _c_i, _c_i],
-    "rfn_coupling_po_bwd_supported": [_c_i, _c_i, _c_i, _c_i],
-    "rfn_coupling_po_bwd_packed_bytes": [_c_i],
-    "rfn_coupling_po_pack_bwd": [_c_f, _c_i, _c_s],
-    "rfn_coupling_po_bwd_part_floats": [_c_i, _c_i, _c_i],
-    "rfn_coupling_po_bwd": [_c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i,
-                            _c_i, _c_s],
-    "rfn_coupling_po_bwd_finish": [ctypes.c_void_p] * 8 + [_c_i, _c_i, _c_i, _c_s],
-    "rfn_gemm_wgrad_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_s],
-    "rfn_conv3x3_wgrad_implicit_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i,
-                                          _c_s],
-    "rfn_gemm_wgrad_kernel_label_bf16x3": [_c_i, _c_i, _c_l, _c_l, _c_i, _c_i, _c_i],
-    "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i],
-    "rfn_conv3x3_wgrad_mirrored_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv3x3_wgrad_mirrored_grouped_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3": [_c_i, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i],
-    "rfn_wgrad_split_workgroups": [_c_i, _c_i, _c_i],
-    "rfn_wgrad_split_parts": [_c_i, _c_i, _c_i, _c_i, ctypes.c_void_p, _c_i],
-    "rfn_im2col3x3_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_packed_weight_size": [_c_i, _c_i, _c_i],
-    "rfn_pack_conv_weight_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv2d_wgrad_f32": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv2d_wgrad_kernel_label_f32": [_c_i] * 5,
-    "rfn_wgrad_finish_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_tap_gather_f32": [_c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_tap_scatter_f32": [_c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv_epilogue_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i,
-                                  _c_s],
-    "rfn_affine_coupling_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_affine_coupling_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l,
-                                    _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_gauss_logp_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_gauss_logp_bwd_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i,
-                               _c_s],
-    "rfn_gauss_sample_f32": [_c_f, _c_l, _c_f, _c_f, _c_l, ctypes.c_float, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_gauss_sample_rows_f32": [_c_f, _c_l, _c_f, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_latent_step_fwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_latent_step_bwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i,
-                                _c_s],
-    "rfn_conv3x3_fewcin_supported": [_c_i, _c_i],
-    "rfn_conv3x3_fewcin_fwd_f32": [_c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_conv3x3_c1_wgrad16_f32": [_c_f, _c_l, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_s],
-    "rfn_smallmap_packed_size": [_c_i, _c_i, _c_i, _c_i, _c_i],
-    "rfn_smallmap_pack_bf16x3": [_c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_s],
-    "rfn_smallmap_pack_batched_bf16x3": [ctypes.c_void_p, _c_i, _c_s],
-    "rfn_pack_conv_weights_hostdescs_bf16x3": [ctypes.c_void_p, _c_i, _c_s],
-    "rfn_smallmap_dense_bf16x3": [_c_f, _c_f, ctypes.c_float, _c_f, _c_f, _c_f, _c_i, ctypes.c_float, _c_f, _c_f, _c_i,
-                                  _c_i, _c_i, _c_i, _c_s],
-    "rfn_smallmap_dense_pair_bf16x3": [_c_f, _c_f, ctypes.c_float, _c_f, _c_f, _c_f, _c_i, ctypes.c_float, _c_f, _c_f, _c_i,
-                                       _c_i, _c_f, _c_f, ctypes.c_float, _c_f, _c_f, _c_f, _c_i, ctypes.c_float, _c_f, _c_f,
-                                       _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_smallmap_conv_bf16x3": [_c_f, _c_l, _c_i, _c_f, _c_l, _c_i, _c_f, _c_f, _c_l, _c_f, _c_l, _c_i, _c_i, _c_i, _c_i,
-                                 _c_i, _c_i, _c_i, _c_f, _c_f, _c_i, _c_s],
-    "rfn_stepbn_scratch_floats": [_c_i, _c_i, _c_i],
-    "rfn_stepbn_kernel_label": [_c_i] * 6,
-    "rfn_convlstm_gates_kernel_label": [_c_i] * 3,
-    "rfn_latent_step_kernel_label": [_c_i] * 2,
-    "rfn_stepbn_fwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, ctypes.c_float, ctypes.c_void_p,
-                           _c_i, _c_i, _c_i, _c_i, ctypes.c_float, _c_i, ctypes.c_float, _c_s],
-    "rfn_stepbn_bwd_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, ctypes.c_float,
-                           _c_i, ctypes.c_float, _c_i, _c_i, _c_s],
-    "rfn_stepbn_apply_f32": [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, ctypes.c_float, _c_i, ctypes.c_float,
-                             _c_s],
-    "rfn_bnflow_scratch_floats": [_c_i, _c_i, _c_i, _c_i],
-    "rfn_bnflow_fwd_f32": [_c_f] * 12 + [ctypes.c_float, _c_i, _c_i, _c_i, ctypes.c_float, _c_s],
-    "rfn_bnflow_bwd_f32": [_c_f] * 10 + [_c_i, _c_i, _c_i, _c_s],
-    "rfn_bnflow_apply_f32": [_c_f] * 7 + [_c_i, _c_i, _c_i, _c_s],
-    "rfn_mol_part_floats": [_c_i, _c_i],
-    "rfn_mol_nll_fwd": [_c_f] * 6 + [_c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_mol_nll_bwd": [_c_f] * 4 + [_c_i, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_mol_sample": [_c_f] * 4 + [_c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_adam_chunk_elems": [],
-    "rfn_adam_step_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                          ctypes.c_double, ctypes.c_double, _c_i, _c_s],
-    "rfn_grad_sumsq_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_f, _c_f, _c_s],
-    "rfn_grad_guard_f32": [_c_f, ctypes.c_double, _c_i, _c_f, ctypes.c_void_p, _c_s],
-    "rfn_adam_step_guarded_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, ctypes.c_double, ctypes.c_double,
-                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, _c_i, _c_f, ctypes.c_void_p, _c_s],
-    "rfn_convlstm_gates_fwd_f32": [_c_f, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i,
-                                   _c_s],
-    "rfn_convlstm_gates_bwd_f32": [_c_f, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_l, _c_f, _c_f, _c_f, _c_f, _c_f,
-                                   _c_l, _c_i, _c_i, _c_i, _c_s],
-    "rfn_frame_quality_u8": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_l, _c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_moving_mnist_render_f32": [ctypes.c_void_p, _c_i, _c_f, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i,
-                                    _c_l, _c_l, _c_l, _c_s],
-    "rfn_keyed_normal_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_l, _c_i, _c_l, _c_l, _c_s],
-    "rfn_keyed_normal_tiled_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_i, _c_i, _c_i, _c_i, _c_l, _c_i, _c_l, _c_l, _c_s],
-    "rfn_clip_gather_u8_f32": [ctypes.c_void_p, _c_l, ctypes.c_void_p, _c_f, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_s],
-    "rfn_sheet_max_rows": [],
-    "rfn_sheet_compose_u8": [ctypes.c_void_p] + [_c_i] * 10 + [_c_l, _c_s],
-    "rfn_lpips_alex_sizes": [_c_i, _c_i, ctypes.c_void_p],
-    "rfn_lpips_alex_weight_layout": [ctypes.c_void_p],
-    "rfn_lpips_alex_features_u8": [ctypes.c_void_p, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_f, _c_l, _c_s],
-    "rfn_lpips_alex_distance": [_c_f, _c_f, _c_f, _c_i, _c_i, _c_i, _c_f, _c_f, _c_s],
-    "rfn_i3d_same": [_c_i, _c_i, _c_i, ctypes.c_void_p],
-    "rfn_i3d_conv_pack_dims": [_c_i, _c_i, _c_i, ctypes.c_void_p],
-    "rfn_i3d_conv3d_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l,
-                           _c_i, _c_i, _c_s],
-    "rfn_i3d_maxpool3d_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_s],
-    "rfn_i3d_resize_u8": [ctypes.c_void_p, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_s],
-    "rfn_i3d_head_f32": [_c_f, _c_l, _c_i, _c_i, _c_i, _c_i, _c_f, _c_l, _c_f, _c_i, _c_f, _c_s],
-}
-_RESTYPES = {"rfn_last_error": ctypes.c_char_p, "rfn_conv2d_kernel_label_f32": ctypes.c_char_p,
-             "rfn_conv2d_kernel_label_bf16x3": ctypes.c_char_p, "rfn_conv2d_wgrad_kernel_label_f32": ctypes.c_char_p,
-             "rfn_gemm_wgrad_kernel_label_bf16x3": ctypes.c_char_p,
-             "rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3": ctypes.c_char_p,
-             "rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3": ctypes.c_char_p,
-             "rfn_glow_shell_fwd_kernel_label": ctypes.c_char_p, "rfn_glow_shell_bwd_kernel_label": ctypes.c_char_p,
-             "rfn_stepbn_kernel_label": ctypes.c_char_p, "rfn_convlstm_gates_kernel_label": ctypes.c_char_p,
-             "rfn_latent_step_kernel_label": ctypes.c_char_p,
-             "rfn_stepbn_scratch_floats": ctypes.c_long, "rfn_bnflow_scratch_floats": ctypes.c_long,
-             "rfn_mol_part_floats": ctypes.c_long,
-             "rfn_packed_weight_size": ctypes.c_long,
-             "rfn_packed_weight_size_bf16x3": ctypes.c_long, "rfn_packed_weight_size_bf16x6": ctypes.c_long,
-             "rfn_smallmap_packed_size": ctypes.c_long,
-             "rfn_coupling_po_packed_bytes": ctypes.c_long, "rfn_coupling_po_mask_floats": ctypes.c_long, "rfn_glow_shell_fwd_ld_floats": ctypes.c_long,
-             "rfn_coupling_po_bwd_packed_bytes": ctypes.c_long, "rfn_coupling_po_bwd_part_floats": ctypes.c_long}
+HEADER_PATH = os.path.join(_HERE, "rfn_hip.h")   # the build's copy of include/rfn_hip.h
 
 ABI_VERSION = 2  # rfn_abi_version() of the library this binding matches (include/rfn_hip.h)
+
+
+# ---- the descriptor structs of include/rfn_hip.h (same names; the layouts are part of the ABI)
+class rfn_pack_desc(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p), ("wpk", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
+                ("ks", ctypes.c_int), ("mode", ctypes.c_int)]
+
+
+class rfn_po_pack_desc(ctypes.Structure):
+    _fields_ = [("w1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("w3", ctypes.c_void_p), ("dst", ctypes.c_void_p),
+                ("Cin", ctypes.c_int), ("C", ctypes.c_int)]
+
+
+class rfn_smallmap_pack_desc(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("transpose", ctypes.c_int), ("pad_", ctypes.c_int)]
+
+
+class rfn_adam_entry(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("n", ctypes.c_long), ("step_offset", ctypes.c_int), ("flags", ctypes.c_int)]
+
+
+class rfn_sheet_row(ctypes.Structure):
+    _fields_ = [("ptr", ctypes.c_void_p), ("step", ctypes.c_long), ("kind", ctypes.c_int), ("count", ctypes.c_int)]
+
+
+STRUCTS = {s.__name__: s for s in (rfn_pack_desc, rfn_po_pack_desc, rfn_smallmap_pack_desc, rfn_adam_entry,
+                                   rfn_sheet_row)}
+
+# ---- C type -> ctypes.  Values travel as their own type; every pointer travels as an address, whatever it points to.
+_VALUES = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+           "rfn_stream_t": ctypes.c_void_p}
+_POINTEES = {"void", "int", "float", "long long"} | set(STRUCTS)
+_RETURNS = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
+
+
+def _ctype(decl, fn):
+    """ctypes type of one parameter declaration, e.g. `const float* const* w1`; an unknown type is an error"""
+    m = re.fullmatch(r"(.*[\s*])\w+", decl)
+    ty = (m.group(1) if m else decl).replace("*", " * ").split()
+    if "*" in ty:
+        if " ".join(w for w in ty if w not in ("const", "*")) in _POINTEES:
+            return ctypes.c_void_p
+    elif " ".join(ty) in _VALUES:
+        return _VALUES[" ".join(ty)]
+    raise RuntimeError("%s: no ctypes mapping for the C type of `%s`" % (fn, decl))
+
+
+def parse_header(text):
+    """(SIGNATURES, RESTYPES, CONSTANTS) of the text of rfn_hip.h: every `<type> rfn_name(args);` and every
+    `#define RFN_NAME <integer>`"""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    sigs, res = {}, {}
+    for m in re.finditer(r"^([A-Za-z_][\w \t*]*?)\s*\b(rfn_\w+)\s*\(([^;]*?)\)\s*;", text, flags=re.S | re.M):
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        ret = " ".join(ret.replace("*", "* ").split()).replace(" *", "*")   # `const char *` -> `const char*`
+        if ret not in _RETURNS:
+            raise RuntimeError("%s: no ctypes mapping for the C return type `%s`" % (name, ret))
+        res[name] = _RETURNS[ret]
+        sigs[name] = [] if args in ("void", "") else [_ctype(a.strip(), name) for a in args.split(",")]
+    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(RFN_\w+)\s+(-?\d+)\s*$", text, flags=re.M)}
+    return sigs, res, consts
+
+
+_NOT_BUILT = ("%s not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` or `make -C "
+              "recurrent-flows-msc_amd/csrc`. There is no fallback path.")
+
+
+@functools.lru_cache(maxsize=None)
+def _declarations(path):
+    if not os.path.exists(path):
+        raise RuntimeError(_NOT_BUILT % ("rfn_hip.h (the build's copy of include/rfn_hip.h)", path))
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+_DERIVED = ("SIGNATURES", "RESTYPES", "CONSTANTS")
+
+
+def __getattr__(name):   # lib.SIGNATURES, lib.RESTYPES, lib.CONSTANTS: read from the header copy at first use
+    if name in _DERIVED:
+        return _declarations(HEADER_PATH)[_DERIVED.index(name)]
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
 
 _lib = None
 
 
 def load():
-    """Load librfn_hip.so (once).  Raises RuntimeError if the extension has not been built."""
+    """Load librfn_hip.so (once) and set every entry point's argtypes / restype from the header copy beside it.  Raises
+    RuntimeError if the extension has not been built."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
-        raise RuntimeError(
-            "librfn_hip.so not found at %s — build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "or `make -C recurrent-flows-msc_amd/csrc`. There is no fallback path." % LIB_PATH)
+        raise RuntimeError(_NOT_BUILT % ("librfn_hip.so", LIB_PATH))
     lib = ctypes.CDLL(LIB_PATH)
     lib.rfn_abi_version.restype = ctypes.c_int
     if lib.rfn_abi_version() != ABI_VERSION:
         raise RuntimeError("%s has ABI version %d, this package needs %d: rebuild the library (`make -C "
                            "recurrent-flows-msc_amd/csrc`)" % (LIB_PATH, lib.rfn_abi_version(), ABI_VERSION))
-    for name, argtypes in SIGNATURES.items():
+    sigs, res, _ = _declarations(HEADER_PATH)
+    for name, argtypes in sigs.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is missing
         fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, ctypes.c_int)
+        fn.restype = res[name]
     _lib = lib
     return lib
 
@@ -224,7 +143,7 @@ def call(name, *args, meta=None):
     """Invoke an int-returning entry point on the current torch stream; raise on a non-zero code."""
     lib = load()
     cur = torch.cuda.current_stream()
-    stream = ctypes.c_void_p(cur.cuda_stream)
+    stream = cur.cuda_stream
     if PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(cur)

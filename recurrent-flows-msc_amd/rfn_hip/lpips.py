@@ -24,8 +24,6 @@ import torch
 
 from . import lib as L
 
-_i = ctypes.c_int
-_l = ctypes.c_long
 
 MIN_SIDE = 31
 CHANNELS = (64, 192, 384, 256, 256)
@@ -39,7 +37,7 @@ def lpips_alex_sizes(H, W):
     """((rows, columns) of the five taps, floats per frame of the feature pack, workspace floats per frame); ValueError
     for frames under 31x31.  Host only: no GPU needed."""
     out = (ctypes.c_longlong * 12)()
-    if L.load().rfn_lpips_alex_sizes(int(H), int(W), ctypes.cast(out, ctypes.c_void_p)) != 0:
+    if L.load().rfn_lpips_alex_sizes(int(H), int(W), out) != 0:
         raise ValueError("lpips_alex: frames must be at least %dx%d (the second max pool needs a 3x3 map), got %dx%d" %
                          (MIN_SIDE, MIN_SIDE, H, W))
     return tuple((int(out[2 * l]), int(out[2 * l + 1])) for l in range(5)), int(out[10]), int(out[11])
@@ -93,7 +91,7 @@ def lpips_alex_pack(state, device, files=("<state dict>",)):
         return t.detach().to(torch.float32)
 
     lay = (ctypes.c_longlong * 16)()
-    if L.load().rfn_lpips_alex_weight_layout(ctypes.cast(lay, ctypes.c_void_p)) != 0:
+    if L.load().rfn_lpips_alex_weight_layout(lay) != 0:
         raise RuntimeError("rfn_lpips_alex_weight_layout failed")
     trunk = torch.zeros(int(lay[15]), dtype=torch.float32)
     lin = []
@@ -170,8 +168,8 @@ def lpips_alex_features(w, frames, chunk=None):
     with torch.cuda.device(frames.device):
         for n0 in range(0, N, chunk):
             n = min(chunk, N - n0)
-            L.call("rfn_lpips_alex_features_u8", ctypes.c_void_p(v.data_ptr() + n0 * ns), _l(ns), _i(n), _i(C), _i(H),
-                   _i(W), L.dev(w.trunk), _l(w.trunk.numel()), L.dev(data[n0:n0 + n]), L.dev(ws), _l(ws.numel()),
+            L.call("rfn_lpips_alex_features_u8", v.data_ptr() + n0 * ns, ns, n, C, H,
+                   W, L.dev(w.trunk), w.trunk.numel(), L.dev(data[n0:n0 + n]), L.dev(ws), ws.numel(),
                    meta=("shell", "lpips_alex_features", 0.0, "%dx%dx%dx%d" % (n, C, H, W), 4.0 * n * F))
     return LpipsFeatures(data, lead, H, W)
 
@@ -193,7 +191,7 @@ def lpips_alex_distance(w, fa, fb, per_layer=False):
     taps = torch.empty(fa.lead + (5,), device=fa.data.device, dtype=torch.float32)
     if N:
         with torch.cuda.device(fa.data.device):
-            L.call("rfn_lpips_alex_distance", L.dev(fa.data), L.dev(fb.data), L.dev(w.lin), _i(N), _i(fa.H), _i(fa.W),
+            L.call("rfn_lpips_alex_distance", L.dev(fa.data), L.dev(fb.data), L.dev(w.lin), N, fa.H, fa.W,
                    L.dev(taps), L.dev(d),
                    meta=("shell", "lpips_alex_distance", 0.0, "%dx%dx%d" % (N, fa.H, fa.W), 8.0 * fa.data.numel()))
     return (d, taps) if per_layer else d

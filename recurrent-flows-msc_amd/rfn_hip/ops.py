@@ -13,9 +13,6 @@ import torch
 
 from . import lib as L
 
-_i = ctypes.c_int
-_l = ctypes.c_long
-
 import os
 
 # Arithmetic of the MFMA convolutions (RFN_CONV_PRECISION):
@@ -62,8 +59,7 @@ def squeeze2d_raw(x, undo=False):
     else:
         y = torch.empty((N, C // 4, H * 2, W * 2), device=x.device, dtype=x.dtype)
     yp, yns = L.frames(y, "y")
-    L.call("rfn_squeeze2d_f32", xp, _l(xns), yp, _l(yns), _i(N), _i(C), _i(H), _i(W), _i(1 if undo else 0),
-           meta=_shell("squeeze2d", x, 2))
+    L.call("rfn_squeeze2d_f32", xp, xns, yp, yns, N, C, H, W, 1 if undo else 0, meta=_shell("squeeze2d", x, 2))
     return y
 
 
@@ -86,7 +82,7 @@ def channel_stats(x):
     xp, xns = L.frames(x, "x")
     mean = torch.empty(C, device=x.device, dtype=torch.float32)
     var = torch.empty(C, device=x.device, dtype=torch.float32)
-    L.call("rfn_channel_stats_f32", xp, _l(xns), L.dev(mean), L.dev(var), _i(N), _i(C), _i(_hw(x)))
+    L.call("rfn_channel_stats_f32", xp, xns, L.dev(mean), L.dev(var), N, C, _hw(x))
     return mean, var
 
 
@@ -96,8 +92,8 @@ def actnorm_invconv_fwd(x, bias, logs, Wm):
     z = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     zp, zns = L.frames(z, "z")
     bias, logs, Wm = bias.contiguous(), logs.contiguous(), Wm.contiguous()  # held until the launch is enqueued
-    L.call("rfn_actnorm_invconv_fwd_f32", xp, _l(xns), L.dev(bias), L.dev(logs), L.dev(Wm), zp, _l(zns), _i(N), _i(C),
-           _i(_hw(x)), meta=_shell("actnorm_invconv_fwd", x, 2))
+    L.call("rfn_actnorm_invconv_fwd_f32", xp, xns, L.dev(bias), L.dev(logs), L.dev(Wm), zp, zns, N, C,
+           _hw(x), meta=_shell("actnorm_invconv_fwd", x, 2))
     return z
 
 
@@ -136,8 +132,8 @@ def actnorm_invconv_bwd(x, bias, logs, Wm, gz, arena=None, acc=None, glogdet=Non
     gW, gb, gl = acc if acc is not None else [_zeros(arena, *s, device=x.device) for s in ((C, C), (C,), (C,))]
     bias, logs, Wm = bias.contiguous(), logs.contiguous(), Wm.contiguous()  # held until the launch is enqueued
     entry, ld = ("rfn_actnorm_invconv_bwd_f32", ()) if glogdet is None else ("rfn_actnorm_invconv_bwd_ld_f32", (L.dev(glogdet),))
-    L.call(entry, xp, _l(xns), L.dev(bias), L.dev(logs), L.dev(Wm), gzp, _l(gzns), gxp, _l(gxns), L.dev(gW), L.dev(gb),
-           L.dev(gl), *ld, _i(N), _i(C), _i(_hw(x)), meta=_shell("actnorm_invconv_bwd", x, 3))
+    L.call(entry, xp, xns, L.dev(bias), L.dev(logs), L.dev(Wm), gzp, gzns, gxp, gxns, L.dev(gW), L.dev(gb),
+           L.dev(gl), *ld, N, C, _hw(x), meta=_shell("actnorm_invconv_bwd", x, 3))
     return gx, gW, gb, gl
 
 
@@ -147,19 +143,8 @@ def invconv_actnorm_rev(z, bias, logs, Winv):
     x = torch.empty(z.shape, device=z.device, dtype=z.dtype)
     xp, xns = L.frames(x, "x")
     bias, logs, Winv = bias.contiguous(), logs.contiguous(), Winv.contiguous()  # held until the launch is enqueued
-    L.call("rfn_invconv_actnorm_rev_f32", zp, _l(zns), L.dev(bias), L.dev(logs), L.dev(Winv), xp, _l(xns), _i(N), _i(C),
-           _i(_hw(z)))
+    L.call("rfn_invconv_actnorm_rev_f32", zp, zns, L.dev(bias), L.dev(logs), L.dev(Winv), xp, xns, N, C, _hw(z))
     return x
-
-
-class _ConvPackDesc(ctypes.Structure):   # rfn_pack_desc (include/rfn_hip.h)
-    _fields_ = [("w", ctypes.c_void_p), ("wpk", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
-                ("ks", ctypes.c_int), ("mode", ctypes.c_int)]
-
-
-class _SmallmapPackDesc(ctypes.Structure):   # rfn_smallmap_pack_desc (include/rfn_hip.h)
-    _fields_ = [("w", ctypes.c_void_p), ("packed", ctypes.c_void_p), ("Cout", ctypes.c_int), ("Cin", ctypes.c_int),
-                ("H", ctypes.c_int), ("W", ctypes.c_int), ("transpose", ctypes.c_int), ("pad_", ctypes.c_int)]
 
 
 class PackBatch:
@@ -177,11 +162,11 @@ class PackBatch:
     def __exit__(self, exc_type, exc, tb):
         if exc_type is None:
             if self._conv:
-                arr = (_ConvPackDesc * len(self._conv))(*self._conv)
-                L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(arr)))
+                arr = (L.rfn_pack_desc * len(self._conv))(*self._conv)
+                L.call("rfn_pack_conv_weights_hostdescs_bf16x3", arr, len(arr))
             if self._dense:
-                arr = (_SmallmapPackDesc * len(self._dense))(*self._dense)
-                L.call("rfn_smallmap_pack_batched_bf16x3", ctypes.cast(arr, ctypes.c_void_p), _i(len(arr)))
+                arr = (L.rfn_smallmap_pack_desc * len(self._dense))(*self._dense)
+                L.call("rfn_smallmap_pack_batched_bf16x3", arr, len(arr))
         self._conv, self._dense, self._keep = [], [], []   # (the contiguous weights were held until the launch)
 
     def conv(self, w, flip=False, prec=None):
@@ -195,9 +180,9 @@ class PackBatch:
                           dtype=torch.float32)
         wc = w.detach().contiguous()
         if prec == "f32":
-            L.call("rfn_pack_conv_weight_f32", L.dev(wc, "w"), L.dev(wpk), _i(Cout), _i(Cin), _i(ks), _i(1 if flip else 0))
+            L.call("rfn_pack_conv_weight_f32", L.dev(wc, "w"), L.dev(wpk), Cout, Cin, ks, 1 if flip else 0)
             return wpk
-        self._conv.append(_ConvPackDesc(L.dev(wc, "w").value, wpk.data_ptr(), Cout, Cin, ks,
+        self._conv.append(L.rfn_pack_desc(L.dev(wc, "w").value, wpk.data_ptr(), Cout, Cin, ks,
                                         (1 if flip else 0) + (4 if prec == "bf16x6" else 0)))
         self._keep += [wc, wpk]
         return wpk
@@ -208,7 +193,7 @@ class PackBatch:
         nbytes = int(L.load().rfn_smallmap_packed_size(Cout, Cin, H, W, 1 if transpose else 0))
         buf = torch.empty(nbytes // 4, device=w.device, dtype=torch.float32)
         wc = w.detach().contiguous()
-        self._dense.append(_SmallmapPackDesc(L.dev(wc, "w").value, buf.data_ptr(), Cout, Cin, int(H), int(W),
+        self._dense.append(L.rfn_smallmap_pack_desc(L.dev(wc, "w").value, buf.data_ptr(), Cout, Cin, int(H), int(W),
                                              1 if transpose else 0, 0))
         self._keep += [wc, buf]
         return buf
@@ -230,8 +215,8 @@ def conv2d_dgrad_act(gin, wpk_flip, y, logs, act, Cout, ks, arena=None):
     gu = torch.empty((N, Cout, H, W), device=gin.device, dtype=torch.float32)
     up, uns = L.frames(gu, "gu")
     sums = _zeros(arena, 2, Cout, device=gin.device)
-    L.call("rfn_conv2d_dgrad_act_bf16x3", gp, _l(gns), _i(Cin), L.dev(wpk_flip), yp, _l(yns), L.dev(logs), _i(act), up,
-           _l(uns), L.dev(sums), _i(Cout), _i(N), _i(H), _i(W), _i(ks),
+    L.call("rfn_conv2d_dgrad_act_bf16x3", gp, gns, Cin, L.dev(wpk_flip), yp, yns, L.dev(logs), act, up,
+           uns, L.dev(sums), Cout, N, H, W, ks,
            meta=("conv", kernel_label("rfn_conv2d_kernel_label_bf16x3", 2, ks, Cin, 0, Cout, Cout, 0, 4, N, H, W) + "+actbwd",
                  2.0 * N * H * W * Cin * Cout * ks * ks,
                  "N%d %d->%d %dx%d k%d dgrad+actbwd" % (N, Cin, Cout, H, W, ks),
@@ -255,8 +240,8 @@ class PackPlan:
             lc, lk = (9 * Cout, 1) if (mode & 3) == 2 else (Cout, ks)
             size_fn = lib.rfn_packed_weight_size_bf16x6 if (mode & 4) else lib.rfn_packed_weight_size_bf16x3
             self.bufs.append(torch.empty(size_fn(lc, Cin, lk), device=w.device, dtype=torch.float32))
-        self.descs = (_ConvPackDesc * len(self.items))(*[
-            _ConvPackDesc(w.data_ptr(), b.data_ptr(), int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), mode)
+        self.descs = (L.rfn_pack_desc * len(self.items))(*[
+            L.rfn_pack_desc(w.data_ptr(), b.data_ptr(), int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), mode)
             for (w, mode), b in zip(self.items, self.bufs)])
 
     def valid_for(self, items):
@@ -264,7 +249,7 @@ class PackPlan:
                 and all(m == m0 for (_, m), (_, m0) in zip(items, self.items)))
 
     def run(self):
-        L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(self.descs, ctypes.c_void_p), _i(len(self.descs)))
+        L.call("rfn_pack_conv_weights_hostdescs_bf16x3", self.descs, len(self.descs))
 
 
 # ------------------------------------------------------------------------------------------------ fused coupling net
@@ -287,23 +272,21 @@ class POPackPlan:
     refreshes all of them (rfn_coupling_po_pack): weights change every optimizer step."""
 
     def __init__(self, nets):
-        import numpy as np
         self.nets = [tuple(n) for n in nets]
         self.ptrs = [tuple(w.data_ptr() for w in n) for n in self.nets]
         dev = self.nets[0][0].device
         lib = L.load()
-        rec = np.zeros(len(self.nets), dtype=np.dtype([("w1", "<u8"), ("w2", "<u8"), ("w3", "<u8"), ("dst", "<u8"),
-                                                       ("Cin", "<i4"), ("C", "<i4")]))
+        rec = []
         self.bufs = []
-        for i, (w1, w2, w3) in enumerate(self.nets):
+        for w1, w2, w3 in self.nets:
             Cin, C = int(w1.shape[1]), int(w3.shape[0])
             for w in (w1, w2, w3):
                 assert w.is_contiguous() and w.dtype == torch.float32
             assert tuple(w2.shape) == (256, 256, 1, 1) and int(w1.shape[0]) == 256 and int(w3.shape[1]) == 256
             buf = torch.empty(int(lib.rfn_coupling_po_packed_bytes(Cin, C)) // 4, device=dev, dtype=torch.float32)
             self.bufs.append(buf)
-            rec[i] = (w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), buf.data_ptr(), Cin, C)
-        self.table = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+            rec.append((w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), buf.data_ptr(), Cin, C))
+        self.table = torch.frombuffer(self.host_table(rec), dtype=torch.uint8).to(dev)
 
         # the backward kernel's streams (w3 transposed + mirrored, w2 transposed) for the nets whose gradient image has
         # at most 16 channels (two 8-channel groups: rfn_coupling_po_bwd_supported)
@@ -317,19 +300,21 @@ class POPackPlan:
                 recb.append((w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), buf.data_ptr(), int(w1.shape[1]), C))
         self.n_bwd = len(recb)
         if recb:
-            rb = np.zeros(len(recb), dtype=rec.dtype)
-            for i, r in enumerate(recb):
-                rb[i] = r
-            self.table_bwd = torch.from_numpy(rb.view(np.uint8).copy()).to(dev)
+            self.table_bwd = torch.frombuffer(self.host_table(recb), dtype=torch.uint8).to(dev)
+
+    @staticmethod
+    def host_table(rec):
+        """the rfn_po_pack_desc array of rows (w1, w2, w3, dst, Cin, C), addresses as ints"""
+        return (L.rfn_po_pack_desc * len(rec))(*[L.rfn_po_pack_desc(*r) for r in rec])
 
     def valid_for(self, nets):
         return len(nets) == len(self.nets) and all(tuple(w.data_ptr() for w in n) == p for n, p in zip(nets, self.ptrs))
 
     def run(self, bwd=True):
         """`bwd`: also refresh the backward streams (not needed when no gradient will be asked for)"""
-        L.call("rfn_coupling_po_pack", L._c_f(self.table.data_ptr()), _i(len(self.nets)))
+        L.call("rfn_coupling_po_pack", self.table.data_ptr(), len(self.nets))
         if bwd and self.n_bwd:
-            L.call("rfn_coupling_po_pack_bwd", L._c_f(self.table_bwd.data_ptr()), _i(self.n_bwd))
+            L.call("rfn_coupling_po_pack_bwd", self.table_bwd.data_ptr(), self.n_bwd)
 
 
 def coupling_po_fwd(z, cond, wpk, n1b, n1l, n2b, n2l, C, act, want_masks=False):
@@ -349,9 +334,9 @@ def coupling_po_fwd(z, cond, wpk, n1b, n1l, n2b, n2l, C, act, want_masks=False):
         nm = int(L.load().rfn_coupling_po_mask_floats(N, H, W))
         masks = (torch.empty(nm, device=z.device, dtype=torch.float32), torch.empty(nm, device=z.device, dtype=torch.float32))
     m1, m2 = masks if masks is not None else (None, None)
-    L.call("rfn_coupling_po_fwd", zp, _l(zns), cp, _l(cns), L.dev(wpk), L.dev(n1b), L.dev(n1l), L.dev(n2b), L.dev(n2l),
-           L.dev(h1), _l(256 * H * W), L.dev(h2), _l(256 * H * W), L.dev(P), _l(9 * C * H * W), L.dev(m1), L.dev(m2),
-           _i(N), _i(C), _i(Cc), _i(H), _i(W), _i(act),
+    L.call("rfn_coupling_po_fwd", zp, zns, cp, cns, L.dev(wpk), L.dev(n1b), L.dev(n1l), L.dev(n2b), L.dev(n2l),
+           L.dev(h1), 256 * H * W, L.dev(h2), 256 * H * W, L.dev(P), 9 * C * H * W, L.dev(m1), L.dev(m2),
+           N, C, Cc, H, W, act,
            meta=("conv", "coupling_po_fwd_kernel", 2.0 * npx * (9 * Cin * 256 + 256 * 256 + 9 * C * 256),
                  "N%d %d+%d->256->256->9x%d %dx%d" % (N, C // 2, Cc, C, H, W),
                  4.0 * npx * (Cin + 512 + 9 * C + (16 if masks is not None else 0))
@@ -374,8 +359,8 @@ def coupling_po_bwd(go, wpk_bwd, n1l, n2l, masks, act):
     part = torch.empty(int(L.load().rfn_coupling_po_bwd_part_floats(N, H, W)), device=go.device, dtype=torch.float32)
     m1, m2 = masks if masks is not None else (None, None)
     npx = float(N * H * W)
-    L.call("rfn_coupling_po_bwd", gp, _l(gns), L.dev(wpk_bwd), L.dev(n1l), L.dev(n2l), L.dev(m1), L.dev(m2),
-           L.dev(ga2), _l(256 * H * W), L.dev(ga1), _l(256 * H * W), L.dev(part), _i(N), _i(C), _i(H), _i(W), _i(act),
+    L.call("rfn_coupling_po_bwd", gp, gns, L.dev(wpk_bwd), L.dev(n1l), L.dev(n2l), L.dev(m1), L.dev(m2),
+           L.dev(ga2), 256 * H * W, L.dev(ga1), 256 * H * W, L.dev(part), N, C, H, W, act,
            meta=("conv", "coupling_po_bwd_kernel", 2.0 * npx * (9 * C * 256 + 256 * 256),
                  "N%d %d->256->256 %dx%d dgrad chain" % (N, C, H, W),
                  4.0 * npx * (C + 512 + (16 if masks is not None else 0)) + 4.0 * (9 * C * 256 + 65536)))
@@ -398,7 +383,7 @@ def coupling_po_bwd_finish(tickets):
         for t in tk:
             assert t[0].numel() == nblk * 512 and t[1].numel() == K1 * 256 and t[2].numel() == K1 * 256
             assert t[4].numel() == 65536 and t[5].numel() == 65536 and t[2].is_contiguous() and t[5].is_contiguous()
-        L.call("rfn_coupling_po_bwd_finish", *cols, _i(len(tk)), _i(nblk), _i(K1),
+        L.call("rfn_coupling_po_bwd_finish", *cols, len(tk), nblk, K1,
                meta=_shell("po_bwd_finish", tk[0][7], len(tk) * (nblk * 512 + 512 * K1 + 131072 + 1024) / 1024.0))
 
 
@@ -422,10 +407,8 @@ def conv2d_raw(in1, in2, wpk, Cout, ks, ep_mode=0, p0=None, p1=None, act=0, out1
     kname = (kernel_label("rfn_conv2d_kernel_label_f32", ks, Cout, N, H, W) if prec == "f32" else
              kernel_label("rfn_conv2d_kernel_label_bf16x3", 3 if x6 else 2, ks, C1, C2, Cout, cout_split, 1 if acc1 else 0,
                           ep_mode, N, H, W) + (" x6" if x6 else ""))
-    L.call(fn, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2),
-           L.dev(wpk), o1p, _l(o1ns), o2p,
-           _l(o2ns), _i(Cout), _i(cout_split), _i(1 if acc1 else 0), _i(1 if acc2 else 0), _i(N), _i(H), _i(W), _i(ks),
-           _i(ep_mode), L.dev(p0), L.dev(p1), _i(act),
+    L.call(fn, i1p, i1ns, C1, i2p, i2ns, C2, L.dev(wpk), o1p, o1ns, o2p, o2ns, Cout, cout_split, 1 if acc1 else 0,
+           1 if acc2 else 0, N, H, W, ks, ep_mode, L.dev(p0), L.dev(p1), act,
            meta=("conv", kname,
                  2.0 * N * H * W * (C1 + C2) * Cout * ks * ks,
                  "N%d %d+%d->%d %dx%d k%d ep%d%s" % (N, C1, C2, Cout, H, W, ks, ep_mode,
@@ -460,11 +443,10 @@ def _b3_wgrad(launch, G, operands, M, Nc, dims, arena, tag=""):
     args = []
     for ts, name, C in operands:
         p, ns = (None, 0) if ts is None else L.frames(ts[0], name)
-        args += [L.ptr_array(ts, name) if G and ts is not None else p, _l(ns), _i(C)]
+        args += [L.ptr_array(ts, name) if G and ts is not None else p, ns, C]
     n, F_, HW = max(G, 1), dims[0], dims[1] * (dims[2] if len(dims) > 2 else 1)
     gw = _zeros(arena, n, M, Nc, device=operands[0][0][0].device)
-    L.call(launch[0], *args, L.ptr_array(gw.unbind(0), "gw") if G else L.dev(gw), *((_i(G),) if G else ()),
-           *[_i(d) for d in dims],
+    L.call(launch[0], *args, L.ptr_array(gw.unbind(0), "gw") if G else L.dev(gw), *((G,) if G else ()), *dims,
            meta=("wgrad", launch[1], 2.0 * n * F_ * HW * M * Nc,
                  "%sF%d %dx%d HW%d%s" % ("G%d " % G if G else "", F_, M, Nc, HW, tag),
                  4.0 * n * (F_ * HW * (M + (Nc // 9 if tag else Nc)) + M * Nc)))
@@ -589,7 +571,7 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
         outs = [torch.empty(tuple(s.shape[:-3]) + (9 * Cout, H, W), device=dev_, dtype=torch.float32) for s in srcs]
         for s, o in zip(srcs, outs):
             entry, label = next(todo)
-            L.call(entry, L.dev(s.contiguous()), L.dev(o), _i(o.numel() // (9 * Cout * H * W)), _i(Cout), _i(H), _i(W),
+            L.call(entry, L.dev(s.contiguous()), L.dev(o), o.numel() // (9 * Cout * H * W), Cout, H, W,
                    meta=_shell(label, o, 10.0 / 9.0))
         return outs if g_stacked is None else list(outs[0].unbind(0))
 
@@ -600,9 +582,9 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
         gp, gns = L.frames(g, "g")
         gwt = _zeros(arena, k * k, Co, Cin, device=dev_)
         entry, label = next(todo)
-        L.call(entry, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), gp, _l(gns), _i(Co), L.dev(gwt), _i(N), _i(H), _i(W),
-               _i(k), meta=("wgrad", label, 2.0 * N * H * W * Cin * Co * k * k, "N%d %d->%d %dx%d k%d" % (N, Cin, Co, H, W, k),
-                            4.0 * (N * H * W * (Cin + Co) + Cin * Co * k * k)))
+        L.call(entry, i1p, i1ns, C1, i2p, i2ns, C2, gp, gns, Co, L.dev(gwt), N, H, W, k,
+               meta=("wgrad", label, 2.0 * N * H * W * Cin * Co * k * k, "N%d %d->%d %dx%d k%d" % (N, Cin, Co, H, W, k),
+                     4.0 * (N * H * W * (Cin + Co) + Cin * Co * k * k)))
         if form == "scatter_f32":
             out = [gwt.view(3, 3, Cout, Cin).permute(2, 3, 0, 1).contiguous()]   # from [tap * Cout + co][ci]
         elif ks == 1:
@@ -610,7 +592,7 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
         else:
             out = [torch.empty((Cout, Cin, ks, ks), device=dev_, dtype=torch.float32)]
             entry, label = next(todo)
-            L.call(entry, L.dev(gwt), L.dev(out[0]), _i(Cout), _i(Cin), _i(ks), _i(0), meta=_shell(label, out[0], 2))
+            L.call(entry, L.dev(gwt), L.dev(out[0]), Cout, Cin, ks, 0, meta=_shell(label, out[0], 2))
     elif form == "gemm":
         out = [t.view(Cout, Cin, 1, 1) for t in _gemm_wgrad(G, gs, cat(), Cout, Cin, arena, next(todo))]
     elif form == "implicit":   # rows (ci, tap) of the implicit operand: already the torch layout
@@ -623,8 +605,7 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
             i1p, i1ns = L.frames(in1s[i], "in1")
             i2p, i2ns = (None, 0) if in2s is None else L.frames(in2s[i], "in2")
             entry, label = next(todo)
-            L.call(entry, i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), L.dev(x9), _i(N), _i(H), _i(W),
-                   meta=_shell(label, x9, 10.0 / 9.0))
+            L.call(entry, i1p, i1ns, C1, i2p, i2ns, C2, L.dev(x9), N, H, W, meta=_shell(label, x9, 10.0 / 9.0))
         gw = _gemm_wgrad(G, gs, x9s, Cout, 9 * Cin, arena, next(todo))  # [g][co][tap*Cin + ci]
         out = list(gw.view(n, Cout, 9, Cin).permute(0, 1, 3, 2).reshape(n, Cout, Cin, 3, 3))  # one copy for all groups
     elif form == "scatter":
@@ -687,7 +668,7 @@ def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None, taps=None):
         wpk = pack_weight(_tap_expanded(w), prec=prec)
     P = conv2d_raw(x, None, wpk, 9 * C, 1, prec=prec)
     o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
-    L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b), L.dev(logs), L.dev(o), _i(N), _i(C), _i(H), _i(W),
+    L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b), L.dev(logs), L.dev(o), N, C, H, W,
            meta=_shell("tap_gather", P, 10.0 / 9.0))
     return o
 
@@ -724,8 +705,8 @@ def conv_epilogue_bwd(y, gy, logs, ep_mode, act, want_gl=True, arena=None, inpla
     up, uns = L.frames(gu, "gu")
     gbl = _zeros(arena, 2 if want_gl else 1, C, device=gy.device)
     gb, gl = gbl[0], (gbl[1] if want_gl else None)
-    L.call("rfn_conv_epilogue_bwd_f32", yp, _l(yns), gp, _l(gns), up, _l(uns), L.dev(logs), L.dev(gb), L.dev(gl),
-           _i(N), _i(C), _i(_hw(gy)), _i(ep_mode), _i(act), meta=_shell("conv_epilogue_bwd", gy, 3))
+    L.call("rfn_conv_epilogue_bwd_f32", yp, yns, gp, gns, up, uns, L.dev(logs), L.dev(gb), L.dev(gl),
+           N, C, _hw(gy), ep_mode, act, meta=_shell("conv_epilogue_bwd", gy, 3))
     return gu, gb, gl
 
 
@@ -734,8 +715,8 @@ def affine_coupling_(z, o, scale, scale_shift, logdet, clamp_type, reverse):
     N, C = z.shape[0], z.shape[1]
     zp, zns = L.frames(z, "z")
     op, ons = L.frames(o, "o")
-    L.call("rfn_affine_coupling_f32", zp, _l(zns), op, _l(ons), L.dev(scale), L.dev(scale_shift), L.dev(logdet),
-           _i(clamp_type), _i(1 if reverse else 0), _i(N), _i(C), _i(_hw(z)), meta=_shell("affine_coupling", z, 2))
+    L.call("rfn_affine_coupling_f32", zp, zns, op, ons, L.dev(scale), L.dev(scale_shift), L.dev(logdet),
+           clamp_type, 1 if reverse else 0, N, C, _hw(z), meta=_shell("affine_coupling", z, 2))
 
 
 def gather_affine_(z, o, P, b3, l3, scale, scale_shift, clamp_type):
@@ -747,14 +728,13 @@ def gather_affine_(z, o, P, b3, l3, scale, scale_shift, clamp_type):
     dlogdet = torch.empty(N, device=z.device, dtype=torch.float32)
     if P is not None:
         o = torch.empty((N, C, H, W), device=z.device, dtype=torch.float32)
-        L.call("rfn_gather_affine_f32", L.dev(P), None, _l(0), L.dev(b3), L.dev(l3), L.dev(o), zp, _l(zns), L.dev(scale),
-               L.dev(scale_shift), L.dev(dlogdet), _i(clamp_type), _i(N), _i(C), _i(H), _i(W),
+        L.call("rfn_gather_affine_f32", L.dev(P), None, 0, L.dev(b3), L.dev(l3), L.dev(o), zp, zns, L.dev(scale),
+               L.dev(scale_shift), L.dev(dlogdet), clamp_type, N, C, H, W,
                meta=_shell("gather_affine", z, 9 + 1 + 1))  # P read (9x), o written, z2 read + written (2 x 1/2)
     else:
         op, ons = L.frames(o, "o")
-        L.call("rfn_gather_affine_f32", None, op, _l(ons), None, None, None, zp, _l(zns), L.dev(scale),
-               L.dev(scale_shift), L.dev(dlogdet), _i(clamp_type), _i(N), _i(C), _i(H), _i(W),
-               meta=_shell("gather_affine", z, 2))
+        L.call("rfn_gather_affine_f32", None, op, ons, None, None, None, zp, zns, L.dev(scale), L.dev(scale_shift),
+               L.dev(dlogdet), clamp_type, N, C, H, W, meta=_shell("gather_affine", z, 2))
     return o, dlogdet
 
 
@@ -763,8 +743,8 @@ def gauss_logp(z, o, layout, std_mode):
     zp, zns = L.frames(z, "z")
     op, ons = L.frames(o, "o")
     logp = torch.zeros(N, device=z.device, dtype=torch.float32)
-    L.call("rfn_gauss_logp_f32", zp, _l(zns), op, _l(ons), L.dev(logp), _i(layout), _i(std_mode), _i(N), _i(Cz),
-           _i(_hw(z)), meta=_shell("gauss_logp", z, 3))
+    L.call("rfn_gauss_logp_f32", zp, zns, op, ons, L.dev(logp), layout, std_mode, N, Cz,
+           _hw(z), meta=_shell("gauss_logp", z, 3))
     return logp
 
 
@@ -789,11 +769,11 @@ def gauss_sample(o, eps, layout, std_mode, temperature):
     op, ons = L.frames(o, "o")
     zp, zns = L.frames(z, "z")
     if isinstance(temperature, torch.Tensor):
-        L.call("rfn_gauss_sample_rows_f32", op, _l(ons), L.dev(eps.contiguous(), "eps"), zp, _l(zns),
-               L.dev(temperature, "temperature"), _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(o)))
+        L.call("rfn_gauss_sample_rows_f32", op, ons, L.dev(eps.contiguous(), "eps"), zp, zns,
+               L.dev(temperature, "temperature"), layout, std_mode, N, Cz, _hw(o))
     else:
-        L.call("rfn_gauss_sample_f32", op, _l(ons), L.dev(eps.contiguous(), "eps"), zp, _l(zns),
-               ctypes.c_float(float(temperature)), _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(o)))
+        L.call("rfn_gauss_sample_f32", op, ons, L.dev(eps.contiguous(), "eps"), zp, zns,
+               float(temperature), layout, std_mode, N, Cz, _hw(o))
     return z
 
 
@@ -823,8 +803,8 @@ def conv3x3_fewcin(x, w):
     xp, xns = L.frames(x, "x")
     out = torch.empty((N, Cout, H, W), device=x.device, dtype=torch.float32)
     wc = w.detach().contiguous()
-    L.call("rfn_conv3x3_fewcin_fwd_f32", xp, _l(xns), _i(Cin), L.dev(wc), L.dev(out), _l(Cout * H * W), _i(Cout), _i(N),
-           _i(H), _i(W), meta=_shell("conv3x3_fewcin_fwd", out, 1.0 + Cin / Cout))
+    L.call("rfn_conv3x3_fewcin_fwd_f32", xp, xns, Cin, L.dev(wc), L.dev(out), Cout * H * W, Cout, N,
+           H, W, meta=_shell("conv3x3_fewcin_fwd", out, 1.0 + Cin / Cout))
     return out
 
 
@@ -833,7 +813,7 @@ def conv3x3_c1_wgrad16(x, g):
     xp, xns = L.frames(x, "x")
     gp, gns = L.frames(g, "g")
     gw = torch.zeros((16, 1, 3, 3), device=x.device, dtype=torch.float32)
-    L.call("rfn_conv3x3_c1_wgrad16_f32", xp, _l(xns), gp, _l(gns), L.dev(gw), _i(N), _i(H), _i(W),
+    L.call("rfn_conv3x3_c1_wgrad16_f32", xp, xns, gp, gns, L.dev(gw), N, H, W,
            meta=_shell("conv3x3_c1_wgrad", g, 1.0 + 1.0 / 16))
     return gw
 
@@ -930,8 +910,8 @@ def conv3x3_smallcout(x, wpk, Cout, out1, out2=None, cout_split=None, acc1=False
     xp, xns = L.frames(x, "x")
     o1p, o1ns = L.frames(out1, "out1")
     o2p, o2ns = (None, 0) if out2 is None else L.frames(out2, "out2")
-    L.call("rfn_conv3x3_smallcout_bf16x3", xp, _l(xns), _i(Cin), L.dev(wpk), o1p, _l(o1ns), o2p, _l(o2ns), _i(Cout),
-           _i(cout_split), _i(1 if acc1 else 0), _i(1 if acc2 else 0), _i(N), _i(H), _i(W),
+    L.call("rfn_conv3x3_smallcout_bf16x3", xp, xns, Cin, L.dev(wpk), o1p, o1ns, o2p, o2ns, Cout,
+           cout_split, 1 if acc1 else 0, 1 if acc2 else 0, N, H, W,
            meta=("conv", "dgrad_small_kernel", 2.0 * N * H * W * Cin * Cout * 9,
                  "N%d %d->%d %dx%d k3 dgrad" % (N, Cin, Cout, H, W), 4.0 * (N * H * W * (Cin + Cout) + Cin * Cout * 9)))
     return out1
@@ -1133,9 +1113,9 @@ def _affine_zeros_bwd(out, o, gout, gdl, p, clamp_type, arena, go=None):
     gzp, gzns = L.frames(t.gz, "gz")
     gonp, gonns = L.frames(t.go, "go")
     scf, shf, l3f = _f(p.scale), _f(p.scale_shift), _f(p.l3)
-    L.call("rfn_affine_zeros_bwd_f32", outp, _l(outns), op, _l(ons), gop, _l(gons), L.dev(gdl), L.dev(scf),
-           L.dev(shf), L.dev(l3f), gzp, _l(gzns), gonp, _l(gonns), L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3),
-           L.dev(t.gl3), _i(clamp_type), _i(N), _i(C), _i(H * W), meta=_shell("affine_zeros_bwd", gout, 4.5))
+    L.call("rfn_affine_zeros_bwd_f32", outp, outns, op, ons, gop, gons, L.dev(gdl), L.dev(scf),
+           L.dev(shf), L.dev(l3f), gzp, gzns, gonp, gonns, L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3),
+           L.dev(t.gl3), clamp_type, N, C, H * W, meta=_shell("affine_zeros_bwd", gout, 4.5))
     return t
 
 
@@ -1151,10 +1131,10 @@ def _glow_shell_bwd(x, head, Wm, gz, gW, gab, gal, o, gdl, tail, clamp_type, are
     gznp, gznns = L.frames(t.gz, "gz_prev")
     gonp, gonns = L.frames(t.go, "gpre")
     abf, alf, scf, shf, l3f = (_f(v) for v in (head.an_bias, head.an_logs, tail.scale, tail.scale_shift, tail.l3))
-    L.call("rfn_glow_shell_bwd_f32", xp, _l(xns), L.dev(abf), L.dev(alf), L.dev(Wm), gzp, _l(gzns), L.dev(gW),
-           L.dev(gab), L.dev(gal), op, _l(ons), L.dev(gdl), L.dev(scf), L.dev(shf), L.dev(l3f), gznp, _l(gznns), gonp,
-           _l(gonns), L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3), L.dev(t.gl3), _i(clamp_type), _i(1), _i(N), _i(C),
-           _i(H * W), meta=_shell("glow_shell_bwd", x, 5.5))
+    L.call("rfn_glow_shell_bwd_f32", xp, xns, L.dev(abf), L.dev(alf), L.dev(Wm), gzp, gzns, L.dev(gW),
+           L.dev(gab), L.dev(gal), op, ons, L.dev(gdl), L.dev(scf), L.dev(shf), L.dev(l3f), gznp, gznns, gonp,
+           gonns, L.dev(t.gscale), L.dev(t.gshift), L.dev(t.gb3), L.dev(t.gl3), clamp_type, 1, N, C,
+           H * W, meta=_shell("glow_shell_bwd", x, 5.5))
     return t
 
 
@@ -1171,18 +1151,18 @@ def _glow_shell_fwd(z, ld, clamp_type=0, tail=None, o=None, P=None, head=None, W
         zn, hb, hl = torch.empty_like(z), _f(head.an_bias), _f(head.an_logs)
         znp, znns = L.frames(zn, "znext")
     if tail is None:
-        src, nt = (None, None, _l(0), None, None, None), 2
+        src, nt = (None, None, 0, None, None, None), 2
     else:
         sc, sh = _f(tail.scale), _f(tail.scale_shift)
         if P is not None:
             b3, l3, o = _f(tail.b3), _f(tail.l3), torch.empty((N, C, H, W), device=z.device, dtype=torch.float32)
-            src, nt = (L.dev(P), None, _l(0), L.dev(b3), L.dev(l3), L.dev(o)), 12 + (0 if head is None else 1)
+            src, nt = (L.dev(P), None, 0, L.dev(b3), L.dev(l3), L.dev(o)), 12 + (0 if head is None else 1)
         else:
             op, ons = L.frames(o, "o")
-            src, nt = (None, op, _l(ons), None, None, None), 2 + (0 if head is None else 1.5)
-    L.call("rfn_glow_shell_fwd_f32", zp, _l(zns), *src, L.dev(sc), L.dev(sh), L.dev(ld), _i(clamp_type), L.dev(hb),
-           L.dev(hl), None if head is None else L.dev(Wm), znp, _l(znns), _i(0 if head is None else 1), _i(N), _i(C),
-           _i(H), _i(W), meta=_shell("glow_shell_fwd", z, nt))
+            src, nt = (None, op, ons, None, None, None), 2 + (0 if head is None else 1.5)
+    L.call("rfn_glow_shell_fwd_f32", zp, zns, *src, L.dev(sc), L.dev(sh), L.dev(ld), clamp_type, L.dev(hb),
+           L.dev(hl), None if head is None else L.dev(Wm), znp, znns, 0 if head is None else 1, N, C,
+           H, W, meta=_shell("glow_shell_fwd", z, nt))
     return o, zn
 
 
@@ -1295,7 +1275,7 @@ class GlowLevelFn(torch.autograd.Function):
             o, zn = _glow_shell_fwd(z, ldp[k + 1], clamp_type, prm[k], o, P, *heads[k])
             kept.append((z, h1, h2, o, masks))
             z = zn
-        L.call("rfn_logdet_reduce_f32", L.dev(ldp), _i(Kn + 1), L.dev(dl), _i(0), _i(N), _i(C), _i(H), _i(W),
+        L.call("rfn_logdet_reduce_f32", L.dev(ldp), Kn + 1, L.dev(dl), 0, N, C, H, W,
                meta=_shell("logdet_reduce", ldp, 1))
         _save_level(ctx, x, cond, Wst, flat, *zip(*kept))
         ctx.cfg = (act, clamp_type, pks, route)
@@ -1366,7 +1346,7 @@ class GlowStepRevFn(torch.autograd.Function):
         if P is not None:
             o = torch.empty((N, C, H, W), device=x.device, dtype=torch.float32)
             b3f, l3f = _f(b3), _f(l3)
-            L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b3f), L.dev(l3f), L.dev(o), _i(N), _i(C), _i(H), _i(W))
+            L.call("rfn_tap_gather_f32", L.dev(P), L.dev(b3f), L.dev(l3f), L.dev(o), N, C, H, W)
         dlogdet = torch.zeros(N, device=x.device, dtype=torch.float32)
         affine_coupling_(z, o, _f(scale), _f(scale_shift), dlogdet, clamp_type, True)
         out = invconv_actnorm_rev(z, _f(an_bias), _f(an_logs), Winv.detach())
@@ -1394,8 +1374,8 @@ class GaussLogpFn(torch.autograd.Function):
         op, ons = L.frames(o, "o")
         gzp, gzns = L.frames(gz, "gz")
         gop, gons = L.frames(go, "go")
-        L.call("rfn_gauss_logp_bwd_f32", zp, _l(zns), op, _l(ons), L.dev(g.contiguous()), gzp, _l(gzns), gop, _l(gons),
-               _i(layout), _i(std_mode), _i(N), _i(Cz), _i(_hw(z)), meta=_shell("gauss_logp_bwd", z, 6))
+        L.call("rfn_gauss_logp_bwd_f32", zp, zns, op, ons, L.dev(g.contiguous()), gzp, gzns, gop, gons,
+               layout, std_mode, N, Cz, _hw(z), meta=_shell("gauss_logp_bwd", z, 6))
         return gz, go, None, None
 
 
@@ -1430,9 +1410,9 @@ def smallmap_dense(a, packed, n_channels, bias=None, slope_out=None, y=None, slo
     a_out = torch.empty_like(a) if want_a_out else None
     yc = None if y is None else y.contiguous()
     addc = None if add is None else add.contiguous()  # held until the launch is enqueued
-    L.call("rfn_smallmap_dense_bf16x3", L.dev(a), L.dev(yc), ctypes.c_float(slope_in), L.dev(packed), L.dev(bias),
-           L.dev(addc), _i(0 if slope_out is None else 1), ctypes.c_float(0.0 if slope_out is None else slope_out), L.dev(out),
-           L.dev(a_out), _i(B), _i(K), _i(n_channels * HW), _i(HW))
+    L.call("rfn_smallmap_dense_bf16x3", L.dev(a), L.dev(yc), slope_in, L.dev(packed), L.dev(bias),
+           L.dev(addc), 0 if slope_out is None else 1, 0.0 if slope_out is None else slope_out, L.dev(out),
+           L.dev(a_out), B, K, n_channels * HW, HW)
     return (out, a_out) if want_a_out else out
 
 
@@ -1453,12 +1433,11 @@ def smallmap_dense_pair(a0, packed0, n_ch0, a1, packed1, n_ch1, bias0=None, bias
     y1c = None if y1 is None else y1.contiguous()
     ad0 = None if add0 is None else add0.contiguous()
     ad1 = None if add1 is None else add1.contiguous()
-    fl = ctypes.c_float
     L.call("rfn_smallmap_dense_pair_bf16x3",
-           L.dev(a0), L.dev(y0c), fl(slope_in0), L.dev(packed0), L.dev(bias0), L.dev(ad0), _i(0 if slope_out0 is None else 1),
-           fl(0.0 if slope_out0 is None else slope_out0), L.dev(out0), L.dev(ao0), _i(K0), _i(n_ch0 * HW),
-           L.dev(a1), L.dev(y1c), fl(slope_in1), L.dev(packed1), L.dev(bias1), L.dev(ad1), _i(0 if slope_out1 is None else 1),
-           fl(0.0 if slope_out1 is None else slope_out1), L.dev(out1), L.dev(ao1), _i(K1), _i(n_ch1 * HW), _i(B), _i(HW))
+           L.dev(a0), L.dev(y0c), slope_in0, L.dev(packed0), L.dev(bias0), L.dev(ad0), 0 if slope_out0 is None else 1,
+           0.0 if slope_out0 is None else slope_out0, L.dev(out0), L.dev(ao0), K0, n_ch0 * HW,
+           L.dev(a1), L.dev(y1c), slope_in1, L.dev(packed1), L.dev(bias1), L.dev(ad1), 0 if slope_out1 is None else 1,
+           0.0 if slope_out1 is None else slope_out1, L.dev(out1), L.dev(ao1), K1, n_ch1 * HW, B, HW)
     if want_a_out:
         return out0, (ao0 if ao0 is not None else a0), out1, (ao1 if ao1 is not None else a1)
     return out0, out1
@@ -1487,16 +1466,15 @@ def smallmap_conv(in1, in2, packed, Cout, ep_mode=0, p0=None, p1=None, act=0, ou
     i2p, i2ns = (None, 0) if in2 is None else L.frames(in2, "in2")
     o1p, o1ns = L.frames(out1, "out1")
     o2p, o2ns = (None, 0) if out2 is None else L.frames(out2, "out2")
-    L.call("rfn_smallmap_conv_bf16x3", i1p, _l(i1ns), _i(C1), i2p, _l(i2ns), _i(C2), L.dev(packed), o1p, _l(o1ns), o2p,
-           _l(o2ns), _i(Cout), _i(cout_split), _i((1 if acc1 else 0) | (2 if acc2 else 0)), _i(N), _i(H), _i(W), _i(ep_mode), L.dev(p0),
-           L.dev(p1), _i(act),
+    L.call("rfn_smallmap_conv_bf16x3", i1p, i1ns, C1, i2p, i2ns, C2, L.dev(packed), o1p, o1ns, o2p, o2ns, Cout,
+           cout_split, (1 if acc1 else 0) | (2 if acc2 else 0), N, H, W, ep_mode, L.dev(p0), L.dev(p1), act,
            meta=("conv", "smallmap_dense_kernel", 2.0 * N * H * W * (C1 + C2) * Cout * 9,
                  "N%d %d+%d->%d %dx%d k3 ep%d dense" % (N, C1, C2, Cout, H, W, ep_mode),
                  4.0 * (N * H * W * (C1 + C2 + Cout) + (C1 + C2) * Cout * H * W * H * W)))
     return out1
 
 
-INVCONV_MAX_STEPS, INVCONV_MAX_CHANNELS = 32, 96  # RFN_INVCONV_MAX_* of include/rfn_hip.h
+INVCONV_MAX_STEPS, INVCONV_MAX_CHANNELS = L.CONSTANTS["RFN_INVCONV_MAX_STEPS"], L.CONSTANTS["RFN_INVCONV_MAX_CHANNELS"]
 
 
 def invconv_weights_ok(ics):
@@ -1529,7 +1507,7 @@ class InvConvWeightsFn(torch.autograd.Function):
         arrs = InvConvWeightsFn._pointers(P, S, Lw, U, LS)
         W = torch.empty((Kn, C, C), device=Lw[0].device, dtype=torch.float32)
         c = torch.empty((), device=Lw[0].device, dtype=torch.float32)   # written by the kernel
-        L.call("rfn_invconv_weights_fwd_f32", *arrs, L.dev(W), L.dev(c), _i(Kn), _i(C), _i(int(hw)),
+        L.call("rfn_invconv_weights_fwd_f32", *arrs, L.dev(W), L.dev(c), Kn, C, int(hw),
                meta=_shell("invconv_weights_fwd", W, 4))
         ctx.cfg = (int(hw), Kn, C)
         ctx.save_for_backward(*t)
@@ -1549,7 +1527,7 @@ class InvConvWeightsFn(torch.autograd.Function):
         gs = torch.empty((Kn, C), device=dev_, dtype=torch.float32)
         gcc = None if gc is None else gc.contiguous()
         L.call("rfn_invconv_weights_bwd_f32", *arrs, L.dev(gW.contiguous()), L.dev(gcc), L.dev(gl), L.dev(gu), L.dev(gs),
-               _i(Kn), _i(C), _i(hw), meta=_shell("invconv_weights_bwd", gW, 4))
+               Kn, C, hw, meta=_shell("invconv_weights_bwd", gW, 4))
         return (None, None) + (None,) * (2 * Kn) + tuple(gl.unbind(0)) + tuple(gu.unbind(0)) + tuple(gs.unbind(0))
 
 
@@ -1568,7 +1546,7 @@ class LatentStepFn(torch.autograd.Function):
         enc, pri, eps_p, eps_q = enc.contiguous(), pri.contiguous(), eps_p.contiguous(), eps_q.contiguous()
         outs = [torch.empty(shp, device=enc.device, dtype=torch.float32) for _ in range(5)]
         L.call("rfn_latent_step_fwd_f32", L.dev(enc), L.dev(pri), L.dev(eps_p), L.dev(eps_q), *[L.dev(o) for o in outs],
-               _i(B), _i(ZHW), _i(1 if res_q else 0), meta=_shell("latent_step_fwd", enc, 5.5))
+               B, ZHW, 1 if res_q else 0, meta=_shell("latent_step_fwd", enc, 5.5))
         ctx.save_for_backward(enc, pri, eps_p, eps_q)
         ctx.cfg = (B, ZHW, bool(res_q))
         return tuple(outs)
@@ -1581,18 +1559,18 @@ class LatentStepFn(torch.autograd.Function):
         strided, keep = [], []
         for g in (g_zt, g_zxt):
             if g is None:
-                strided += [None, _l(0)]
+                strided += [None, 0]
                 continue
             if B > 0 and (not g[0].is_contiguous() or (B > 1 and g.stride(0) < ZHW)):
                 g = g.contiguous()
             keep.append(g)
             gp, gns = L.frames(g, "g_z")
-            strided += [gp, _l(gns)]
+            strided += [gp, gns]
         # keep the contiguous copies alive until the launch is enqueued (a freed temporary's block would be reused)
         gs = [None if g is None else g.contiguous() for g in (g_kl, g_em, g_es)]
         g_enc, g_pri = torch.empty_like(enc), torch.empty_like(pri)
         L.call("rfn_latent_step_bwd_f32", L.dev(enc), L.dev(pri), L.dev(eps_p), L.dev(eps_q), *strided,
-               *[L.dev(g) for g in gs], L.dev(g_enc), L.dev(g_pri), _i(B), _i(ZHW), _i(1 if res_q else 0))
+               *[L.dev(g) for g in gs], L.dev(g_enc), L.dev(g_pri), B, ZHW, 1 if res_q else 0)
         return g_enc, g_pri, None, None, None
 
 
@@ -1616,8 +1594,8 @@ class ConvLSTMCellFn(torch.autograd.Function):
         hp, hns = L.frames(h_out, "h_out")
         cop, cons = L.frames(c_out, "c_out")
         pe = [None if t is None else t.detach().reshape(-1).contiguous() for t in (wci, wcf, wco)]
-        L.call("rfn_convlstm_gates_fwd_f32", L.dev(cc), cp, _l(cns), L.dev(pe[0]), L.dev(pe[1]), L.dev(pe[2]), hp,
-               _l(hns), cop, _l(cons), L.dev(gates), _i(N), _i(Hc), _i(HW), meta=_shell("convlstm_gates_fwd", gates, 2.75))
+        L.call("rfn_convlstm_gates_fwd_f32", L.dev(cc), cp, cns, L.dev(pe[0]), L.dev(pe[1]), L.dev(pe[2]), hp,
+               hns, cop, cons, L.dev(gates), N, Hc, HW, meta=_shell("convlstm_gates_fwd", gates, 2.75))
         ctx.save_for_backward(x, h, c, w, gates, c_out, *[t for t in pe if t is not None])
         ctx.has_bias = b is not None
         ctx.has_pe = pe[0] is not None
@@ -1639,8 +1617,8 @@ class ConvLSTMCellFn(torch.autograd.Function):
         ghp, ghns = (None, 0) if gh is None else L.frames(gh.contiguous(), "gh")
         gcp, gcns = (None, 0) if gc is None else L.frames(gc.contiguous(), "gc")
         gpp, gpns = L.frames(gc_prev, "gc_prev")
-        L.call("rfn_convlstm_gates_bwd_f32", L.dev(gates), cp, _l(cns), cop, _l(cons), ghp, _l(ghns), gcp, _l(gcns),
-               L.dev(pe[0]), L.dev(pe[1]), L.dev(pe[2]), L.dev(gcc), gpp, _l(gpns), _i(N), _i(Hc), _i(HW),
+        L.call("rfn_convlstm_gates_bwd_f32", L.dev(gates), cp, cns, cop, cons, ghp, ghns, gcp, gcns,
+               L.dev(pe[0]), L.dev(pe[1]), L.dev(pe[2]), L.dev(gcc), gpp, gpns, N, Hc, HW,
                meta=_shell("convlstm_gates_bwd", gates, 3.25))
         gb = conv_epilogue_bwd(None, gcc, None, 3, 0, want_gl=False)[1] if ctx.has_bias else None
         gw = conv2d_wgrad(x, h, gcc, 4 * Hc, ks)
@@ -1682,9 +1660,8 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         ns = Hc * HW
         for t in range(S):
             cc = smallmap_dense(h_prev, pk_hf, 4 * Hc, add=pre[t])
-            L.call("rfn_convlstm_gates_fwd_f32", L.dev(cc), L.dev(c_prev), _l(ns), None, None, None, L.dev(h_all[t]),
-                   _l(ns), L.dev(c_all[t]), _l(ns), L.dev(gates[t]), _i(B), _i(Hc), _i(HW),
-                   meta=_shell("convlstm_gates_fwd", gates[t], 2.75))
+            L.call("rfn_convlstm_gates_fwd_f32", L.dev(cc), L.dev(c_prev), ns, None, None, None, L.dev(h_all[t]), ns,
+                   L.dev(c_all[t]), ns, L.dev(gates[t]), B, Hc, HW, meta=_shell("convlstm_gates_fwd", gates[t], 2.75))
             h_prev, c_prev = h_all[t], c_all[t]
         ctx.save_for_backward(x_all, h0, c0, w, h_all, c_all, gates)
         ctx.has_bias = b is not None
@@ -1712,10 +1689,9 @@ class ConvLSTMSeqFn(torch.autograd.Function):
                 gh = g_hall[t] + gh_rec
             c_prev = c_all[t - 1] if t > 0 else c0
             gc_prev = torch.empty_like(c0)
-            L.call("rfn_convlstm_gates_bwd_f32", L.dev(gates[t]), L.dev(c_prev), _l(ns), L.dev(c_all[t]), _l(ns),
-                   L.dev(gh), _l(ns if gh is not None else 0), L.dev(gc), _l(ns if gc is not None else 0), None, None, None,
-                   L.dev(gcc[t]), L.dev(gc_prev), _l(ns), _i(B), _i(Hc), _i(HW),
-                   meta=_shell("convlstm_gates_bwd", gates[t], 3.25))
+            L.call("rfn_convlstm_gates_bwd_f32", L.dev(gates[t]), L.dev(c_prev), ns, L.dev(c_all[t]), ns, L.dev(gh),
+                   ns if gh is not None else 0, L.dev(gc), ns if gc is not None else 0, None, None, None, L.dev(gcc[t]),
+                   L.dev(gc_prev), ns, B, Hc, HW, meta=_shell("convlstm_gates_bwd", gates[t], 3.25))
             gh_rec = smallmap_dense(gcc[t], pk_hb, Hc)
             gc = gc_prev
         G = gcc.view(S * B, 4 * Hc, H, W)
@@ -1757,9 +1733,8 @@ class StepBatchNormActFn(torch.autograd.Function):
             if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
                 raise RuntimeError("num_batches_tracked must be an int64 device tensor")
         L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), ctypes.c_float(decay),
-               None if nbt is None else ctypes.c_void_p(nbt.data_ptr()), _i(S), _i(B), _i(C), _i(HW), ctypes.c_float(eps),
-               _i(act), ctypes.c_float(slope), meta=_shell("stepbn_fwd", x, 3))
+               L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr(), S, B, C, HW,
+               eps, act, slope, meta=_shell("stepbn_fwd", x, 3))
         ctx.save_for_backward(x, mean, var, gm, bt)
         ctx.cfg = (S, B, C, HW, eps, act, slope, gamma is not None, nscr)
         ctx.mark_non_differentiable(mean, var)
@@ -1783,13 +1758,12 @@ class StepBatchNormActFn(torch.autograd.Function):
         nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))
         acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
         L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               None, None, None, None, ctypes.c_float(1.0), None, _i(S), _i(B), _i(C), _i(HW), ctypes.c_float(eps),
-               _i(act), ctypes.c_float(slope))
+               None, None, None, None, 1.0, None, S, B, C, HW, eps, act, slope)
         st = rdist.all_gather_cat(torch.stack((mean, var)).unsqueeze(0))          # [world, 2, S, C]
         mean = st[:, 0].mean(0).contiguous()
         var = (st[:, 1].mean(0) + (st[:, 0] - mean).pow(2).mean(0)).contiguous()  # equal counts per rank
-        L.call("rfn_stepbn_apply_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), _i(S), _i(B),
-               _i(C), _i(HW), ctypes.c_float(eps), _i(act), ctypes.c_float(slope))
+        L.call("rfn_stepbn_apply_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), S, B,
+               C, HW, eps, act, slope)
         if running is not None:
             rm, rv, cf, cfu, decay, nbt = running
             n = B * HW * world
@@ -1816,14 +1790,14 @@ class StepBatchNormActFn(torch.autograd.Function):
         ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
         gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
         args = (L.dev(x), L.dev(gm), L.dev(bt), L.dev(g), L.dev(mean), L.dev(var), L.dev(sums), L.dev(gx), L.dev(ggamma),
-                L.dev(gbeta), _i(S), _i(B), _i(C), _i(HW), ctypes.c_float(eps), _i(act), ctypes.c_float(slope))
+                L.dev(gbeta), S, B, C, HW, eps, act, slope)
         if ctx.world > 1:   # synchronised: partial sums, added over the ranks, apply
             from . import dist as rdist
-            L.call("rfn_stepbn_bwd_f32", *args, _i(1), _i(ctx.world))
+            L.call("rfn_stepbn_bwd_f32", *args, 1, ctx.world)
             rdist.all_reduce_sum_(sums)
-            L.call("rfn_stepbn_bwd_f32", *args, _i(2), _i(ctx.world))
+            L.call("rfn_stepbn_bwd_f32", *args, 2, ctx.world)
         else:
-            L.call("rfn_stepbn_bwd_f32", *args, _i(0), _i(1))
+            L.call("rfn_stepbn_bwd_f32", *args, 0, 1)
         return gx, ggamma, gbeta, None, None, None, None, None
 
 
@@ -1863,8 +1837,8 @@ class BatchNormFlowFn(torch.autograd.Function):
             if not (rm.is_contiguous() and rv.is_contiguous()) or rm.numel() != E or rv.numel() != E or cf.numel() != S:
                 raise RuntimeError("BatchNormFlowFn: running statistics must be dense [%d] tensors, coef [%d]" % (E, S))
         L.call("rfn_bnflow_fwd_f32", L.dev(x), L.dev(lg), L.dev(bt), L.dev(z), L.dev(mean), L.dev(var), L.dev(dl),
-               L.dev(scr), L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cf), ctypes.c_float(decay), _i(S), _i(B), _i(E),
-               ctypes.c_float(eps), meta=_shell("bnflow_fwd", x, 2))
+               L.dev(scr), L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cf), decay, S, B, E,
+               eps, meta=_shell("bnflow_fwd", x, 2))
         ctx.save_for_backward(x, lg, mean, var)
         ctx.cfg = (S, B, E, log_gamma.shape)
         return z, dl
@@ -1880,7 +1854,7 @@ class BatchNormFlowFn(torch.autograd.Function):
         gbt = torch.empty(pshape, device=x.device, dtype=torch.float32)
         scr = torch.empty((int(L.load().rfn_bnflow_scratch_floats(S, B, E, 1)),), device=x.device, dtype=torch.float32)
         L.call("rfn_bnflow_bwd_f32", L.dev(x), L.dev(lg), L.dev(gz), L.dev(gdl), L.dev(mean), L.dev(var), L.dev(gx),
-               L.dev(glg), L.dev(gbt), L.dev(scr), _i(S), _i(B), _i(E), meta=_shell("bnflow_bwd", x, 3))
+               L.dev(glg), L.dev(gbt), L.dev(scr), S, B, E, meta=_shell("bnflow_bwd", x, 3))
         return gx, glg, gbt, None, None, None
 
 
@@ -1895,8 +1869,8 @@ def bnflow_apply(x, log_gamma, beta, running_mean, running_var, reverse):
     lg, bt, rm, rv = _f(log_gamma), _f(beta), _f(running_mean), _f(running_var)
     if not (lg.numel() == bt.numel() == rm.numel() == rv.numel() == E):
         raise RuntimeError("bnflow_apply: parameters do not match rows of %d elements" % E)
-    L.call("rfn_bnflow_apply_f32", L.dev(x), L.dev(lg), L.dev(bt), L.dev(rm), L.dev(rv), L.dev(y), L.dev(dl), _i(N), _i(E),
-           _i(1 if reverse else 0), meta=_shell("bnflow_apply", x, 2))
+    L.call("rfn_bnflow_apply_f32", L.dev(x), L.dev(lg), L.dev(bt), L.dev(rm), L.dev(rv), L.dev(y), L.dev(dl), N, E,
+           1 if reverse else 0, meta=_shell("bnflow_apply", x, 2))
     return y, dl
 
 
@@ -1930,8 +1904,8 @@ class MolNllFn(torch.autograd.Function):
         lse = torch.empty_like(nll_pix)
         nll = torch.empty((N,), device=l.device, dtype=torch.float32)
         part = torch.empty((int(L.load().rfn_mol_part_floats(N, HW)),), device=l.device, dtype=torch.float32)
-        L.call("rfn_mol_nll_fwd", L.dev(x, "x"), L.dev(l, "l"), L.dev(nll_pix), L.dev(lse), L.dev(nll), L.dev(part), _i(N), _i(C),
-               _i(M), _i(HW), meta=_shell("mol_nll_fwd", l, 1))
+        L.call("rfn_mol_nll_fwd", L.dev(x, "x"), L.dev(l, "l"), L.dev(nll_pix), L.dev(lse), L.dev(nll), L.dev(part), N, C,
+               M, HW, meta=_shell("mol_nll_fwd", l, 1))
         ctx.save_for_backward(x, l, lse)
         ctx.cfg = (N, C, M, HW, per_frame)
         return nll if per_frame else nll_pix
@@ -1942,8 +1916,8 @@ class MolNllFn(torch.autograd.Function):
         N, C, M, HW, per_frame = ctx.cfg
         g = g.contiguous()
         dl = torch.empty_like(l)
-        L.call("rfn_mol_nll_bwd", L.dev(x), L.dev(l), L.dev(lse), L.dev(g, "grad"), _i(0 if per_frame else 1), L.dev(dl),
-               _i(N), _i(C), _i(M), _i(HW), meta=_shell("mol_nll_bwd", l, 2))
+        L.call("rfn_mol_nll_bwd", L.dev(x), L.dev(l), L.dev(lse), L.dev(g, "grad"), 0 if per_frame else 1, L.dev(dl),
+               N, C, M, HW, meta=_shell("mol_nll_bwd", l, 2))
         return None, dl, None
 
 
@@ -1990,8 +1964,8 @@ def mol_sample(l, u_mix=None, u_x=None, generator=None, channels=None):
                            ((N, H, W, M), (N, H, W, C), tuple(u_mix.shape), tuple(u_x.shape)))
     u_mix, u_x = u_mix.contiguous(), u_x.contiguous()
     out = torch.empty((N, C, H, W), device=l.device, dtype=torch.float32)
-    L.call("rfn_mol_sample", L.dev(l), L.dev(u_mix, "u_mix"), L.dev(u_x, "u_x"), L.dev(out), _i(N), _i(C), _i(M),
-           _i(H * W), meta=_shell("mol_sample", l, 1))
+    L.call("rfn_mol_sample", L.dev(l), L.dev(u_mix, "u_mix"), L.dev(u_x, "u_x"), L.dev(out), N, C, M,
+           H * W, meta=_shell("mol_sample", l, 1))
     return out
 
 
@@ -2007,7 +1981,7 @@ def _u8_frames(t, C, H, W):
     if not dense or (v.shape[0] > 1 and s[0] < C * H * W):
         v = v.contiguous()
     ns = v.stride(0) if v.shape[0] > 1 else C * H * W
-    return v, ctypes.c_void_p(v.data_ptr()), int(ns)
+    return v, v.data_ptr(), int(ns)
 
 
 def frame_quality(a, b):
@@ -2044,8 +2018,8 @@ def frame_quality(a, b):
     av, ap, ans = _u8_frames(a, C, H, W)
     bv, bp, bns = _u8_frames(b, C, H, W)
     with torch.cuda.device(a.device):
-        L.call("rfn_frame_quality_u8", ap, _l(ans), bp, _l(bns), L.dev(mse), L.dev(psnr), L.dev(ssim), _i(N), _i(C),
-               _i(H), _i(W), meta=("shell", "frame_quality", 0.0, "x".join(str(int(d)) for d in a.shape),
+        L.call("rfn_frame_quality_u8", ap, ans, bp, bns, L.dev(mse), L.dev(psnr), L.dev(ssim), N, C,
+               H, W, meta=("shell", "frame_quality", 0.0, "x".join(str(int(d)) for d in a.shape),
                                   2.0 * a.numel()))
     return mse, psnr, ssim
 
@@ -2084,9 +2058,9 @@ def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, determinist
     traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
     if B:
         with torch.cuda.device(digits.device):
-            L.call("rfn_moving_mnist_render_f32", ctypes.c_void_p(digits.data_ptr()), _i(int(digits.shape[0])),
-                   L.dev(out), ctypes.c_void_p(traj.data_ptr()) if traj is not None else None, _i(B), _i(T), _i(C),
-                   _i(S), _i(nd), _i(L_), _i(1 if deterministic else 0), _l(seed), _l(split), _l(first_id),
+            L.call("rfn_moving_mnist_render_f32", digits.data_ptr(), int(digits.shape[0]),
+                   L.dev(out), traj.data_ptr() if traj is not None else None, B, T, C,
+                   S, nd, L_, 1 if deterministic else 0, seed, split, first_id,
                    meta=("shell", "moving_mnist", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
     return (out, traj) if trajectories else out
 
@@ -2128,8 +2102,7 @@ def clip_gather(store, first, T, C):
     out = torch.empty((B, T, C, H, W), device=store.device, dtype=torch.float32)
     if B:
         with torch.cuda.device(store.device):
-            L.call("rfn_clip_gather_u8_f32", ctypes.c_void_p(store.data_ptr()), _l(F), ctypes.c_void_p(first.data_ptr()),
-                   L.dev(out), _i(B), _i(T), _i(C), _i(Cs), _i(H), _i(W),
+            L.call("rfn_clip_gather_u8_f32", store.data_ptr(), F, first.data_ptr(), L.dev(out), B, T, C, Cs, H, W,
                    meta=("shell", "clip_gather", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, H, W),
                          4.0 * out.numel() + float(B * T * H * W * Cs)))
     return out
@@ -2219,23 +2192,16 @@ def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=
     if total:
         with torch.cuda.device(live[0].device):
             if tiles == 1:
-                L.call("rfn_keyed_normal_f32", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(numels, ctypes.c_void_p),
-                       _i(len(out)), _i(rows), _i(B), _l(seed), _i(step), _l(first_seq), _l(first_draw),
+                L.call("rfn_keyed_normal_f32", ptrs, numels, len(out), rows, B, seed, step, first_seq, first_draw,
                        meta=("shell", "keyed_normal", 0.0, "%dx%d" % (rows, total // rows), 4.0 * total))
             else:
-                L.call("rfn_keyed_normal_tiled_f32", ctypes.cast(ptrs, ctypes.c_void_p),
-                       ctypes.cast(numels, ctypes.c_void_p), _i(len(out)), _i(tile_rows), _i(B), _i(tiles), _l(seed),
-                       _i(step), _l(first_seq), _l(first_draw),
+                L.call("rfn_keyed_normal_tiled_f32", ptrs, numels, len(out), tile_rows, B, tiles, seed, step, first_seq,
+                       first_draw,
                        meta=("shell", "keyed_normal", 0.0, "%dx%dx%d" % (tiles, tile_rows, total // rows), 4.0 * total))
     return out
 
 
-class _SheetRow(ctypes.Structure):
-    """rfn_sheet_row of include/rfn_hip.h"""
-    _fields_ = [("ptr", ctypes.c_void_p), ("step", ctypes.c_long), ("kind", ctypes.c_int), ("count", ctypes.c_int)]
-
-
-SHEET_MAX_ROWS = 32   # RFN_SHEET_MAX_ROWS: the row descriptors travel in the launch's arguments
+SHEET_MAX_ROWS = L.CONSTANTS["RFN_SHEET_MAX_ROWS"]   # the row descriptors travel in the launch's arguments
 
 
 def sheet_shape(n_rows, n_cols, H, W, gutter):
@@ -2290,7 +2256,7 @@ def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.
     Hs, Ws = sheet_shape(len(rows), n_cols, H, W, gutter)
     if Hs > 0x7fffffff or 3 * Ws + 1 > 0x7fffffff or C * H * W > 0x7fffffff:
         raise ValueError("compose_sheet: a %dx%d sheet of %dx%dx%d frames exceeds one launch" % (Hs, Ws, C, H, W))
-    tab = (_SheetRow * len(rows))()
+    tab = (L.rfn_sheet_row * len(rows))()
     for r, t in enumerate(rows):
         n = int(t.shape[0])
         tab[r].ptr = t.data_ptr() if n else None
@@ -2305,9 +2271,8 @@ def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.
           not out.is_contiguous() or out.device != dev):
         raise ValueError("compose_sheet: out must be a contiguous uint8 tensor %s on %s" % (shape, dev))
     with torch.cuda.device(dev):
-        L.call("rfn_sheet_compose_u8", ctypes.cast(tab, ctypes.c_void_p), _i(len(rows)), _i(n_cols), _i(C), _i(H), _i(W),
-               _i(gutter), _i(bg), _i(n_bits), _i(1 if preprocess_range == "0.5" else 0), _i(1 if scanlines else 0),
-               _l(out.data_ptr()),
+        L.call("rfn_sheet_compose_u8", tab, len(rows), n_cols, C, H, W, gutter, bg, n_bits,
+               1 if preprocess_range == "0.5" else 0, 1 if scanlines else 0, out.data_ptr(),
                meta=("shell", "sheet_compose", 0.0, "%dx%dx%dx%dx%d" % (len(rows), n_cols, C, H, W),
                      float(out.numel()) + sum(float(t.numel() * t.element_size()) for t in rows)))
     return out

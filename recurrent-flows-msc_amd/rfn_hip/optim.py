@@ -16,8 +16,6 @@ rebuild, state_dict(), guard_stats()).  Under data parallelism the squares of th
 batch-sharded initial states; GradBucketReducer.finish() has divided them by the world size) are summed over ranks with
 one scalar all-reduce, which gives every rank the norm of one process on the global batch, bit for bit, and hence the
 same decision."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -102,7 +100,7 @@ class HipAdam(torch.optim.Adam):
             if self._gbuf is None:
                 self._gbuf = torch.zeros(8, dtype=torch.float32, device=dev)
             self._settle_skipped()   # (the previous table's tensors; a read is allowed here)
-        ent = np.zeros((len(params), 6), dtype=np.int64)   # rfn_adam_entry: 4 pointers, long n, (int offset, int pad)
+        ent = (L.rfn_adam_entry * len(params))()
         chunks = []
         for i, p in enumerate(params):
             st = self.state[p]
@@ -125,11 +123,11 @@ class HipAdam(torch.optim.Adam):
             # the guarded kernel subtracts the device's running count of skipped steps as well
             off = self._t - self._steps[id(p)] - self._settled
             flags = 1 if id(p) in self._rank_local else 0
-            ent[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, (off & 0xFFFFFFFF) | (flags << 32))
+            ent[i] = L.rfn_adam_entry(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, off, flags)
             nck = (n + chunk - 1) // chunk
             chunks.append(np.stack([np.full(nck, i, dtype=np.int32), np.arange(nck, dtype=np.int32)], 1))
         chunks = np.concatenate(chunks, 0) if chunks else np.zeros((0, 2), np.int32)
-        tab_d = torch.from_numpy(ent.view(np.uint8).reshape(-1)).to(dev)
+        tab_d = torch.frombuffer(ent, dtype=torch.uint8).to(dev)
         chk_d = torch.from_numpy(np.ascontiguousarray(chunks).reshape(-1)).to(dev)
         self._keep = (tab_d, chk_d, int(chunks.shape[0]), list(params), 28.0 * sum(p.numel() for p in params))
         self._key = key
@@ -172,10 +170,8 @@ class HipAdam(torch.optim.Adam):
             self._guarded_launches(group, beta1, beta2)
             torch.autograd.graph.increment_version(plist)
             return loss
-        L.call("rfn_adam_step_f32", ctypes.c_void_p(tab_d.data_ptr()), ctypes.c_void_p(chk_d.data_ptr()), ctypes.c_int(nck),
-               ctypes.c_double(float(group["lr"])), ctypes.c_double(beta1), ctypes.c_double(beta2),
-               ctypes.c_double(group["eps"]), ctypes.c_double(group["weight_decay"]), ctypes.c_int(self._t),
-               meta=("shell", "adam", 0.0, "%d tensors" % len(plist), nbytes))
+        L.call("rfn_adam_step_f32", tab_d.data_ptr(), chk_d.data_ptr(), nck, float(group["lr"]), beta1, beta2, group["eps"],
+               group["weight_decay"], self._t, meta=("shell", "adam", 0.0, "%d tensors" % len(plist), nbytes))
         # the kernel wrote through raw pointers: tell autograd's version counters, which everything keyed on
         # `p._version` relies on (ListGlow._reverse_cache, RFN._gen_graph: cached inverse matrices / packs / hipGraph)
         torch.autograd.graph.increment_version(plist)
@@ -186,15 +182,13 @@ class HipAdam(torch.optim.Adam):
         from . import dist as rdist
         tab_d, chk_d, nck, plist, nbytes = self._keep
         partials, stats, sumsq, skipped, reduce_local = self._guard
-        tab, chk = ctypes.c_void_p(tab_d.data_ptr()), ctypes.c_void_p(chk_d.data_ptr())
-        L.call("rfn_grad_sumsq_f32", tab, chk, ctypes.c_int(nck), ctypes.c_void_p(partials.data_ptr()),
-               ctypes.c_void_p(sumsq.data_ptr()), meta=("shell", "grad_sumsq", 0.0, "%d tensors" % len(plist), nbytes / 7.0))
+        tab, chk = tab_d.data_ptr(), chk_d.data_ptr()
+        L.call("rfn_grad_sumsq_f32", tab, chk, nck, partials.data_ptr(), sumsq.data_ptr(),
+               meta=("shell", "grad_sumsq", 0.0, "%d tensors" % len(plist), nbytes / 7.0))
         if reduce_local:
             rdist.all_reduce_sum_(sumsq[1:2], group=self._group)
-        L.call("rfn_grad_guard_f32", ctypes.c_void_p(sumsq.data_ptr()), ctypes.c_double(self.max_grad_norm),
-               ctypes.c_int(int(self.skip_nonfinite)), ctypes.c_void_p(stats.data_ptr()),
-               ctypes.c_void_p(skipped.data_ptr()), meta=("shell", "grad_guard", 0.0, "", 0.0))
-        L.call("rfn_adam_step_guarded_f32", tab, chk, ctypes.c_int(nck), ctypes.c_double(float(group["lr"])),
-               ctypes.c_double(beta1), ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
-               ctypes.c_double(group["weight_decay"]), ctypes.c_int(self._t), ctypes.c_void_p(stats.data_ptr()),
-               ctypes.c_void_p(skipped.data_ptr()), meta=("shell", "adam_guarded", 0.0, "%d tensors" % len(plist), nbytes))
+        L.call("rfn_grad_guard_f32", sumsq.data_ptr(), self.max_grad_norm, int(self.skip_nonfinite), stats.data_ptr(),
+               skipped.data_ptr(), meta=("shell", "grad_guard", 0.0, "", 0.0))
+        L.call("rfn_adam_step_guarded_f32", tab, chk, nck, float(group["lr"]), beta1, beta2, group["eps"],
+               group["weight_decay"], self._t, stats.data_ptr(), skipped.data_ptr(),
+               meta=("shell", "adam_guarded", 0.0, "%d tensors" % len(plist), nbytes))

@@ -355,7 +355,7 @@ def test_pack_hostdescs_route_bit_exact(K, n_rep):
     assert (len(items) > 64) == (n_rep > 1)
     wds = {id(w): w.cuda() for w, _ in items}
     bufs = [_sentinel_buf(_mode_size(lib, w, m) + MARGIN) for w, m in items]
-    arr = (K._ConvPackDesc * len(items))(*[K._ConvPackDesc(wds[id(w)].data_ptr(), b.data_ptr(), int(w.shape[0]),
+    arr = (L.rfn_pack_desc * len(items))(*[L.rfn_pack_desc(wds[id(w)].data_ptr(), b.data_ptr(), int(w.shape[0]),
                                                            int(w.shape[1]), int(w.shape[2]), m)
                                            for (w, m), b in zip(items, bufs)])
     L.call("rfn_pack_conv_weights_hostdescs_bf16x3", ctypes.cast(arr, ctypes.c_void_p), ctypes.c_int(len(items)))

@@ -169,7 +169,7 @@ def test_namespace_without_the_guard_flags_builds_and_steps_as_before(tmp_path, 
 
 def test_header_and_binding_declare_the_guard_symbols():
     from rfn_hip import lib
-    protos = _parse_header()
+    protos, _ = _parse_header()
     for name in ("rfn_grad_sumsq_f32", "rfn_grad_guard_f32", "rfn_adam_step_guarded_f32"):
         assert name in protos and name in lib.SIGNATURES
         assert len(protos[name]) == len(lib.SIGNATURES[name])

@@ -18,17 +18,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _parse_header():
     txt = open(os.path.join(ROOT, "include", "rfn_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(?:int|long|const char\*)\s+(rfn_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
+    protos, rets = {}, {}
+    for m in re.finditer(r"(int|long|const char\*)\s+(rfn_\w+)\s*\(([^;]*?)\)\s*;", txt, flags=re.S):
+        name, args = m.group(2), m.group(3).strip()
         protos[name] = [] if args in ("void", "") else [a.strip() for a in args.split(",")]
-    return protos
+        rets[name] = m.group(1)
+    return protos, rets
 
 
 def test_c_abi_exports_every_declared_symbol():
     import ctypes
     from rfn_hip import lib
-    protos = _parse_header()
+    protos, rets = _parse_header()
     assert len(protos) >= 20
     L = lib.load()
     cmap = {"const float*": ctypes.c_void_p, "float*": ctypes.c_void_p, "const void*": ctypes.c_void_p, "long": ctypes.c_long, "int": ctypes.c_int,
@@ -36,6 +37,7 @@ def test_c_abi_exports_every_declared_symbol():
             "const float* const*": ctypes.c_void_p, "float* const*": ctypes.c_void_p,
             "long long*": ctypes.c_void_p, "const rfn_adam_entry*": ctypes.c_void_p, "const int*": ctypes.c_void_p,
             "double": ctypes.c_double}  # host arrays of device pointers
+    rmap = {"int": ctypes.c_int, "long": ctypes.c_long, "const char*": ctypes.c_char_p}
     for name, args in protos.items():
         assert hasattr(L, name), "librfn_hip.so does not export %s" % name
         assert name in lib.SIGNATURES, "ctypes binding lacks %s" % name
@@ -46,7 +48,10 @@ def test_c_abi_exports_every_declared_symbol():
             ty = ty.replace("float *", "float*")
             want.append(cmap[ty])
         assert want == lib.SIGNATURES[name], "%s: header %s vs binding %s" % (name, want, lib.SIGNATURES[name])
-    assert set(lib.SIGNATURES) == set(protos), set(lib.SIGNATURES) ^ set(protos)
+        assert list(getattr(L, name).argtypes) == want and getattr(L, name).restype is lib.RESTYPES[name]
+        assert lib.RESTYPES[name] is rmap[rets[name]], "%s: header returns %s, binding %s" % (name, rets[name],
+                                                                                              lib.RESTYPES[name])
+    assert set(lib.SIGNATURES) == set(lib.RESTYPES) == set(protos), set(lib.SIGNATURES) ^ set(protos)
     assert L.rfn_abi_version() == lib.ABI_VERSION == 2
 
 

@@ -163,11 +163,11 @@ def test_sheet_abi():
     assert lib.SIGNATURES["rfn_sheet_compose_u8"] == [ctypes.c_void_p] + [ctypes.c_int] * 10 + [ctypes.c_long,
                                                                                                  ctypes.c_void_p]
     assert L.rfn_sheet_max_rows() == ops.SHEET_MAX_ROWS
-    assert ctypes.sizeof(ops._SheetRow) == 24
-    assert (ops._SheetRow.ptr.offset, ops._SheetRow.step.offset, ops._SheetRow.kind.offset,
-            ops._SheetRow.count.offset) == (0, 8, 16, 20)
+    assert ctypes.sizeof(lib.rfn_sheet_row) == 24
+    assert (lib.rfn_sheet_row.ptr.offset, lib.rfn_sheet_row.step.offset, lib.rfn_sheet_row.kind.offset,
+            lib.rfn_sheet_row.count.offset) == (0, 8, 16, 20)
     # argument errors are answered before any launch (no GPU needed): a channel count other than 1 / 3, a bad count
-    tab = (ops._SheetRow * 1)()
+    tab = (lib.rfn_sheet_row * 1)()
     tab[0].ptr, tab[0].step, tab[0].kind, tab[0].count = 256, 0, 1, 1
     call = lambda *a: L.rfn_sheet_compose_u8(ctypes.cast(tab, ctypes.c_void_p), *a, 256, None)
     assert call(1, 1, 2, 4, 4, 0, 255, 8, 1, 0) == -2

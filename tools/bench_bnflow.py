@@ -68,12 +68,10 @@ def graphed(fn, reps):
 
 
 def kernels(a):
-    import ctypes
     import torch
     from rfn_hip import lib as L
     from rfn_hip import ops as K
     assert torch.cuda.is_available(), "bench_bnflow.py needs a GPU"
-    _i, _f = ctypes.c_int, ctypes.c_float
     S, B = a.S, a.B
     out = []
     for C, H in LEVELS:
@@ -88,15 +86,15 @@ def kernels(a):
 
         def fwd():
             L.call("rfn_bnflow_fwd_f32", L.dev(x), L.dev(lg), L.dev(beta), L.dev(z), L.dev(mean), L.dev(var), L.dev(dl),
-                   L.dev(scr), L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cf), _f(decay), _i(S), _i(B), _i(E), _f(EPS))
+                   L.dev(scr), L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cf), decay, S, B, E, EPS)
 
         def bwd():
             L.call("rfn_bnflow_bwd_f32", L.dev(x), L.dev(lg), L.dev(gz), L.dev(gdl), L.dev(mean), L.dev(var), L.dev(gx),
-                   L.dev(glg), L.dev(gb), L.dev(scr), _i(S), _i(B), _i(E))
+                   L.dev(glg), L.dev(gb), L.dev(scr), S, B, E)
 
         def apply():
             L.call("rfn_bnflow_apply_f32", L.dev(x), L.dev(lg), L.dev(beta), L.dev(rm), L.dev(rv), L.dev(z), L.dev(dl1),
-                   _i(S * B), _i(E), _i(0))
+                   S * B, E, 0)
 
         # the torch expression of the unfused module (glow_modules.py:76-98 of the reference), one call per step
         lgp, bp = lg.clone().requires_grad_(True), beta.clone().requires_grad_(True)

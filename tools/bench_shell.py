@@ -6,11 +6,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 for p in (ROOT, os.path.join(ROOT, "recurrent-flows-msc_amd")):
     sys.path.insert(0, p)
-import ctypes
 import torch
 from rfn_hip import lib as L
 
-_i, _l = ctypes.c_int, ctypes.c_long
 
 
 def timed(fn, reps=20):
@@ -47,17 +45,17 @@ def run(N, C, S):
     gzp, gpre = torch.empty_like(x), torch.empty_like(x)
 
     def bwd():
-        L.call("rfn_glow_shell_bwd_f32", L.dev(x), _l(C * HW), L.dev(bias), L.dev(logs), L.dev(Wm), L.dev(gz), _l(C * HW),
-               L.dev(gW), L.dev(gab), L.dev(gal), L.dev(o), _l(C * HW), L.dev(gdl), None, None, L.dev(l3), L.dev(gzp),
-               _l(C * HW), L.dev(gpre), _l(C * HW), None, None, L.dev(gb3), L.dev(gl3), _i(1), _i(1), _i(N), _i(C), _i(HW))
+        L.call("rfn_glow_shell_bwd_f32", L.dev(x), C * HW, L.dev(bias), L.dev(logs), L.dev(Wm), L.dev(gz), C * HW,
+               L.dev(gW), L.dev(gab), L.dev(gal), L.dev(o), C * HW, L.dev(gdl), None, None, L.dev(l3), L.dev(gzp),
+               C * HW, L.dev(gpre), C * HW, None, None, L.dev(gb3), L.dev(gl3), 1, 1, N, C, HW)
 
     ldf = int(L.load().rfn_glow_shell_fwd_ld_floats(N, C, S, S))
     ldp = torch.empty(ldf, device=dev)
     z, zn = r(N, C, S, S), torch.empty(N, C, S, S, device=dev)
 
     def fwd():
-        L.call("rfn_glow_shell_fwd_f32", L.dev(z), _l(C * HW), None, L.dev(o), _l(C * HW), None, None, None, None, None,
-               L.dev(ldp), _i(1), L.dev(bias), L.dev(logs), L.dev(Wm), L.dev(zn), _l(C * HW), _i(1), _i(N), _i(C), _i(S), _i(S))
+        L.call("rfn_glow_shell_fwd_f32", L.dev(z), C * HW, None, L.dev(o), C * HW, None, None, None, None, None,
+               L.dev(ldp), 1, L.dev(bias), L.dev(logs), L.dev(Wm), L.dev(zn), C * HW, 1, N, C, S, S)
 
     tb, tf = timed(bwd), timed(fwd)
     by = 4.0 * N * C * HW
