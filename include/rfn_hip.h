@@ -17,10 +17,10 @@
  *     being captured into a hipGraph: run the shape eagerly once first) and serves every stream of the device, so
  *     split-K convolutions on DIFFERENT streams of one device must not overlap in time;
  *   - return value: 0 on success, otherwise a hipError_t / negative argument-check code; rfn_last_error() gives text;
- *   - global state: the (thread-local) last-error string, and seven developer knobs that the kernel selectors read ONCE
+ *   - global state: the (thread-local) last-error string, and four developer knobs that the kernel selectors read ONCE
  *     from the environment at their first call and then keep for the life of the process: RFN_CONV_WS (0: no
- *     weight-stationary kernels), RFN_WGRAD_DMA (0: no LDS-DMA ring kernels), RFN_CONV_VARIANT, RFN_WGRAD_VARIANT,
- *     RFN_WGRAD_SPLIT, RFN_WGRAD_BPX128, RFN_WGRAD_NARROW_PER_CU (tile / split-K experiments; unset = production choice).
+ *     weight-stationary kernels), RFN_WGRAD_DMA (0: no LDS-DMA ring kernels), RFN_CONV_VARIANT, RFN_WGRAD_BPX128
+ *     (tile / split-K experiments; unset = production choice).
  *     They pick between
  *     kernels that compute the same result; nothing else is cached between calls, and the library is safe to call from
  *     several host threads on distinct streams.  The *_kernel_label_* queries answer with the same knobs applied, so a
@@ -297,8 +297,10 @@ int rfn_conv3x3_smallcout_bf16x3(const float* in, long in_ns, int Cin, const flo
  * smaller operand: b = rfn_im2col3x3_f32(input) [9*Cin rows, tap-major] or a = rfn_tap_scatter_f32(grad) [9*Cout rows].
  * Kernel choice (same arithmetic, same result up to summation order): F*HW >= 100000 pixels, HW % 32 == 0 and
  * Nc % 256 == 0 with M >= 192 or M <= 64 (grouped form: G * F*HW >= 100000) -> the LDS-DMA ring kernel (raw fp32 rows HBM -> LDS by global_load_lds, split
- * at the fragment reads; RFN_WGRAD_DMA=0 disables it); otherwise the register-staged tilings (RFN_WGRAD_VARIANT,
- * RFN_WGRAD_SPLIT: tile / K-split experiments). */
+ * at the fragment reads; RFN_WGRAD_DMA=0 disables it); otherwise the register-staged tilings.  Argument checks, here and
+ * in the four 3x3 forms below, run in the order of their codes: -1 null pointer / size <= 0 / G outside 1..16, -2 pixel
+ * counts and strides the 16-byte loads cannot take, -3 a misaligned operand (grouped: a null or misaligned pointer of
+ * any group), -4 F * HW >= 2^31 - 4096; with F == 0 a call that passes them returns 0 and launches nothing. */
 int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw, int F, int HW,
                           rfn_stream_t stream);
 /* G (<= 16) gradients of ONE shape in one launch (the K steps of a flow level: one tail of atomics instead of K): a, b,
@@ -322,8 +324,8 @@ const char* rfn_conv3x3_wgrad_implicit_kernel_label_bf16x3(int Cout, long g_ns, 
 /* The same for a 3x3 conv with FEW outputs (Cin -> C, the last conv of a coupling net), roles swapped and taps mirrored:
  * the Cin rows of the conv's input h are the big operand, the C gradient planes g are shifted while staging -- no
  * tap-scattered copy of g in memory.  gwT[Cin][C*9] += sum over frames and pixels of h[ci][q] * g[co][q - tap], column
- * index co*9 + tap: gwT is the TRANSPOSE [Cin][C][3][3] of the torch layout; zeroed by the caller.  W % 8 == 0; code -5
- * when the shape has no mirrored route.  (The narrow column tiles of the ring kernel start
+ * index co*9 + tap: gwT is the TRANSPOSE [Cin][C][3][3] of the torch layout; zeroed by the caller.  W % 8 == 0.
+ * (The narrow column tiles of the ring kernel start
  * rfn_wgrad_split_workgroups' count with 512 in place of 256: two workgroups per CU.) */
 int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C, float* gwT,
                                       int F, int H, int W, rfn_stream_t stream);

@@ -115,6 +115,138 @@ __host__ __device__ inline int wg_split_workgroups(int tiles, int G, int n_stage
     return Wt < 1 ? 1 : (int)Wt;
 }
 
+// ---- device pieces the three kernels below share
+template <int N_>
+__device__ __forceinline__ void wg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
+template <int TM, int TN>
+__device__ __forceinline__ void wg_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+// one k-step of a 32 x 32 tile: (ah + al)(bh + bl) without al bl, the small products first
+__device__ __forceinline__ void wg_mfma3(f32x16& acc, const bf16x8 ah, const bf16x8 al, const bf16x8 bh, const bf16x8 bl) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+// epilogue: acc of wave (wm, wn) added into gw [M][N], tile origin (m0, n0), with float atomics.
+// D[i = m][j = n]: col = lane&31 = n (32 consecutive floats of a gw row = one 128-byte atomic segment)
+template <int TM, int TN>
+__device__ __forceinline__ void wg_add_tile(const f32x16 (&acc)[TM][TN], float* gw, const int M, const int N, const int m0,
+                                            const int n0, const int wm, const int wn, const int l31, const int kk) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wn * TN + j) * 32 + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                if (m < M && n < N) atomicAdd(&gw[(long)m * N + n], acc[i][j][r]);
+            }
+        }
+}
+// The ring kernels pass wg_add_tile a tile origin made opaque per part: the offsets and bounds masks of the 16 TM TN
+// atomics do not depend on the part, and hoisted out of the part loop they live, and spill, through the stage loop -- 256
+// VGPRs + 92 spilled and 234 spilled SGPRs for the 256 x 256 tile without this, 240 and none with it, as before the part
+// loop.  The empty asm computes nothing; if a compiler stops honouring it, tools/kernel_resources.py shows spills and a
+// ScratchSize above 0 for the three ring kernels.
+__device__ __forceinline__ void wg_opaque_origin(int& m0, int& n0) { asm volatile("" : "+s"(m0), "+s"(n0)); }
+
+// The passes of a ring kernel's workgroup, each ending in an epilogue.  Ungrouped launch: ONE pass over the interleaved
+// stages blockIdx.x, + gridDim.x, ...; grouped (G > 0): one pass per part of my range of the flat stage space
+// (wg_split_part), over consecutive stages of the part's group.  The groups share shapes and strides, so a kernel
+// computes its addresses once and on entering a part only moves their bases to the group's operands (wg_rebase).
+struct WgParts {
+    WgPart part;   // grouped: the part of the current pass
+    long pos;      // where my range goes on
+    int i;         // passes done
+};
+__device__ __forceinline__ WgParts wg_parts_begin(const GemmWgradParams& p) {
+    WgParts ps;
+    ps.pos = p.G > 0 ? wg_split_begin(p.G, p.n_stages, gridDim.x, blockIdx.x) : 0;
+    ps.i = 0;
+    return ps;
+}
+__device__ __forceinline__ bool wg_parts_next(const GemmWgradParams& p, WgParts& ps) {
+    return p.G > 0 ? wg_split_part(p.G, p.n_stages, gridDim.x, blockIdx.x, ps.pos, ps.part) : ps.i == 0;
+}
+// entering part `part`: its stages and its group's operands (the caller rebases its pointers to them)
+__device__ __forceinline__ WgOperands wg_part_enter(const WgPart& part, int& first, int& step, int& nmine) {
+    first = part.s0;
+    step = 1;
+    nmine = part.cnt;
+    return wg_operands_kernarg(part.grp);
+}
+// between two passes: the previous part's atomics have retired (they count in vmcnt like the DMA pieces the kernels'
+// waits count), its fragment reads have returned, and nobody reads the slots and planes the next prologue is about to fill
+__device__ __forceinline__ void wg_parts_drain() {
+    wg_wait_vm<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
+// Staging unit of the shifted operand of the implicit 3x3 forms: row n = ci*9 + tap of B (the output [Cout][9*Cin] IS
+// the torch weight layout [Cout][Cin][3][3]) is plane ci of the two-source input (pb: the first C1 planes, pb2: the
+// rest) shifted by the tap -- by the opposite tap for the mirrored form.  Rows beyond N take row 0 (the caller masks them).
+// (gemm_wgrad_b3_kernel keeps the fields as plain per-unit arrays and gemm_wgrad_dma_impl_kernel as WgTap[]: what the
+// staging lambdas capture decides the register allocation of every instantiation, the non-implicit ones included.)
+struct WgTap {
+    const float* plane;
+    long ns;       // frame stride of the plane's source
+    int dy, dx;
+    bool first;    // the plane is of pb
+};
+__device__ __forceinline__ WgTap wg_tap(int row, const GemmWgradParams& p, const float* pb, const float* pb2) {
+    if (row >= p.N) row = 0;
+    const int ci = row / 9, tap = row - ci * 9;
+    WgTap t;
+    t.dy = p.mirror ? 1 - tap / 3 : tap / 3 - 1;
+    t.dx = p.mirror ? 1 - tap % 3 : tap % 3 - 1;
+    t.first = ci < p.C1;
+    t.plane = t.first ? pb + (long)ci * p.HW : pb2 + (long)(ci - p.C1) * p.HW;
+    t.ns = t.first ? p.b_ns : p.b2_ns;
+    return t;
+}
+// the 8 pixels (y, x0 .. x0 + 7) of frame f lie in one image row (W % 8 == 0); shifted by dx they need one element beyond
+// either end.  Unconditional loads: the row is clamped (rok: inside the image) and so is the edge element (eok)
+struct WgTapRow {
+    float4 v[2];
+    float edge;
+    bool rok, eok;
+};
+__device__ __forceinline__ WgTapRow wg_tap_load(const float* plane, const long ns, const int dy, const int dx,
+                                                const unsigned f, const int y, const int x0, const int H, const int W) {
+    WgTapRow r;
+    const int yy = y + dy;
+    r.rok = yy >= 0 && yy < H;
+    const float* src = plane + (long)f * ns + (r.rok ? yy : y) * W + x0;
+    r.v[0] = *reinterpret_cast<const float4*>(src);
+    r.v[1] = *reinterpret_cast<const float4*>(src + 4);
+    r.eok = dx < 0 ? x0 > 0 : x0 + 8 < W;  // the element beyond the end, inside the row?
+    r.edge = src[r.eok ? (dx < 0 ? -1 : 8) : 0];
+    return r;
+}
+// the loaded row shifted by dx, zeroed unless `ok`, split into bf16 (hi, lo)
+__device__ __forceinline__ void wg_shift_split8(const float4 (&src)[2], const float edge, const int dx, const bool ok,
+                                                const bool eok, bf16x8& hi, bf16x8& lo) {
+    const float v[8] = {src[0].x, src[0].y, src[0].z, src[0].w, src[1].x, src[1].y, src[1].z, src[1].w};
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float left = c == 0 ? (eok ? edge : 0.f) : v[c > 0 ? c - 1 : 0];
+        const float right = c == 7 ? (eok ? edge : 0.f) : v[c < 7 ? c + 1 : 7];
+        float x = dx < 0 ? left : (dx > 0 ? right : v[c]);
+        x = ok ? x : 0.f;
+        const __bf16 h = (__bf16)x;
+        hi[c] = h;
+        lo[c] = (__bf16)(x - (float)h);
+    }
+}
+
 // WM x WN waves (4 or 8) of TM x TN 32x32 tiles each.  The 8-wave 256-row configurations read both operands of the
 // big level-0 / level-1 gradients exactly once (a 128 x 128 tiling of a 256 x 256 gradient reads each of them twice,
 // and those launches sit on the HBM roof).
@@ -145,12 +277,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
     float* const pgw_ = ops_.gw;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    wg_zero(acc);
 
     // staging: unit e = tid + NT*u  ->  row = e / NU, k-group = e % NU   (consecutive threads = consecutive pixels)
     float4 ast[AU][2], bst[BU][2];
@@ -164,8 +291,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
     // commit: unconditional (clamped rows / pixels, no select on a loaded value, no control flow) -- otherwise the
     // compiler waits for HBM right behind the loads and nothing overlaps.  Masks are applied in commit().
     bool okq[2] = {false, false};
-    // implicit mode: per unit (fixed row n = tap*Cin + ci) the plane pointer, frame stride and tap offsets; per stage the
-    // 8 pixels of a unit lie in one image row (W % 8 == 0), shifted by dx they need one element beyond either end
+    // implicit mode: per unit (fixed row n = ci*9 + tap) its tap (wg_tap); per stage the row's edge element and masks
     const float* uplane[IMPL ? BU : 1];
     long uns[IMPL ? BU : 1];
     int udy[IMPL ? BU : 1], udx[IMPL ? BU : 1];
@@ -174,15 +300,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
     if (IMPL) {
 #pragma unroll
         for (int u = 0; u < BU; ++u) {
-            int row = n0 + r0 + u * (NT / NU);
-            if (row >= p.N) row = 0;
-            // row = ci*9 + tap: the output [Cout][9*Cin] IS the torch weight layout [Cout][Cin][3][3]
-            const int ci = row / 9, tap = row - ci * 9;
-            udy[u] = p.mirror ? 1 - tap / 3 : tap / 3 - 1;
-            udx[u] = p.mirror ? 1 - tap % 3 : tap % 3 - 1;
-            const bool first = ci < p.C1;
-            uplane[u] = first ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
-            uns[u] = first ? p.b_ns : p.b2_ns;
+            const WgTap t = wg_tap(n0 + r0 + u * (NT / NU), p, pb_, pb2_);
+            uplane[u] = t.plane;
+            uns[u] = t.ns;
+            udy[u] = t.dy;
+            udx[u] = t.dx;
         }
     }
     auto prefetch = [&](int stage) {
@@ -212,15 +334,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
             edgemask = 0;
 #pragma unroll
             for (int u = 0; u < BU; ++u) {
-                const int yy = y + udy[u];
-                const bool rok = yy >= 0 && yy < p.H;
-                const float* src = uplane[u] + (long)f * uns[u] + (rok ? yy : y) * p.W + x0;
-                bst[u][0] = *reinterpret_cast<const float4*>(src);
-                bst[u][1] = *reinterpret_cast<const float4*>(src + 4);
-                const bool eok = udx[u] < 0 ? x0 > 0 : x0 + 8 < p.W;  // the element beyond the end, inside the row?
-                bedge[u] = src[eok ? (udx[u] < 0 ? -1 : 8) : 0];
-                rowmask |= (rok ? 1u : 0u) << u;
-                edgemask |= (eok ? 1u : 0u) << u;
+                const WgTapRow r = wg_tap_load(uplane[u], uns[u], udy[u], udx[u], f, y, x0, p.H, p.W);
+                bst[u][0] = r.v[0];
+                bst[u][1] = r.v[1];
+                bedge[u] = r.edge;
+                rowmask |= (r.rok ? 1u : 0u) << u;
+                edgemask |= (r.eok ? 1u : 0u) << u;
             }
         } else {
 #pragma unroll
@@ -231,22 +350,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
                 for (int h = 0; h < 2; ++h) bst[u][h] = *reinterpret_cast<const float4*>(base + offb[h]);
             }
         }
-    };
-    auto split_store_shift = [&](const float4 (&src)[2], float edge, int dx, bool okr, bool eok, bf16x8* hi_p, bf16x8* lo_p) {
-        const float v[8] = {src[0].x, src[0].y, src[0].z, src[0].w, src[1].x, src[1].y, src[1].z, src[1].w};
-        bf16x8 hi, lo;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float left = c == 0 ? (eok ? edge : 0.f) : v[c > 0 ? c - 1 : 0];
-            const float right = c == 7 ? (eok ? edge : 0.f) : v[c < 7 ? c + 1 : 7];
-            float x = dx < 0 ? left : (dx > 0 ? right : v[c]);
-            x = (okr && okq[0]) ? x : 0.f;
-            const __bf16 h = (__bf16)x;
-            hi[c] = h;
-            lo[c] = (__bf16)(x - (float)h);
-        }
-        *hi_p = hi;
-        *lo_p = lo;
     };
     auto split_store = [&](const float4 (&src)[2], bool okr, bf16x8* hi_p, bf16x8* lo_p) {
         const float v[8] = {src[0].x, src[0].y, src[0].z, src[0].w, src[1].x, src[1].y, src[1].z, src[1].w};
@@ -272,10 +375,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
             const int o = (r0 + u * (NT / NU)) * RS + kg;
             if (BX || r0 + u * (NT / NU) < BN) {
                 const bool okr = n0 + r0 + u * (NT / NU) < p.N;
-                if (IMPL)
-                    split_store_shift(bst[u], bedge[u], udx[u], okr && ((rowmask >> u) & 1u), (edgemask >> u) & 1u, Bh + o,
-                                      Bl + o);
-                else
+                if (IMPL) {
+                    bf16x8 hi, lo;
+                    wg_shift_split8(bst[u], bedge[u], udx[u], okr && ((rowmask >> u) & 1u) && okq[0],
+                                    (edgemask >> u) & 1u, hi, lo);
+                    Bh[o] = hi;
+                    Bl[o] = lo;
+                } else
                     split_store(bst[u], okr, Bh + o, Bl + o);
             }
         }
@@ -308,25 +414,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) wg_mfma3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
         }
     }
-    // D[i = m][j = n]: col = lane&31 = n (32 consecutive floats of a gw row = one 128-byte atomic segment)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wn * TN + j) * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
-            }
-        }
+    wg_add_tile(acc, pgw_, p.M, p.N, m0, n0, wm, wn, l31, kk);
 }
 
 // ------------------------------------------------------------------------------------------------ LDS-DMA variant
@@ -350,9 +441,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
 //     fragment of unit u + 1 split; the B fragments of the next k-step are read during its unit 0 and split, one tile
 //     per unit, from unit 1 on.
 // K split, epilogue atomics and operand roles are those of gemm_wgrad_b3_kernel (non-implicit, non-grouped).
-template <int N_>
-__device__ __forceinline__ void wg_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
-
 __device__ __forceinline__ void wg_split8(const f32x4 lo4, const f32x4 hi4, bf16x8& hi, bf16x8& lo) {
     const float v[8] = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
 #pragma unroll
@@ -462,35 +550,18 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
         wg_split8(ra[0][0], ra[0][1], ah[0], al[0]);
     };
 
-    // one pass per part: a single pass over the interleaved stages set up above for an ungrouped launch, one pass per
-    // group my range touches for a grouped one
-    WgPart part;
-    long pos = p.G > 0 ? wg_split_begin(p.G, p.n_stages, S, blockIdx.x) : 0;
-    for (int part_i = 0; p.G > 0 ? wg_split_part(p.G, p.n_stages, S, blockIdx.x, pos, part) : part_i == 0; ++part_i) {
+    // one pass per part (WgParts)
+    for (WgParts ps = wg_parts_begin(p); wg_parts_next(p, ps); ++ps.i) {
         if (p.G > 0) {
-            const WgOperands o = wg_operands_kernarg(part.grp);
+            const WgOperands o = wg_part_enter(ps.part, first, step, nmine);
 #pragma unroll
             for (int j = 0; j < PPW; ++j) prow[j] = pisa[j] ? wg_rebase(prow[j], pa_, o.a) : wg_rebase(prow[j], pb_, o.b);
             pa_ = o.a;
             pb_ = o.b;
             pgw_ = o.gw;
-            first = part.s0;
-            step = 1;
-            nmine = part.cnt;
         }
-        if (part_i > 0) {
-            // the previous part's atomics have retired (they count in vmcnt like the pieces the waits below count), its
-            // fragment reads have returned, and nobody reads a slot the prologue is about to fill
-            wg_wait_vm<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        if (ps.i > 0) wg_parts_drain();
+        wg_zero(acc);
 
         // prologue: stages 0 .. NST-2 in flight; (LOOK) stage 0 landed, its first fragments read and split
 #pragma unroll
@@ -544,11 +615,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
                     for (int j = 0; j < PPW; ++j) piece(j, fslot);
                 }
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur], bh[kb][j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bl[kb][j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur], bh[kb][j], acc[i][j], 0, 0, 0);
-                }
+                for (int j = 0; j < TN; ++j) wg_mfma3(acc[i][j], ah[cur], al[cur], bh[kb][j], bl[kb][j]);
                 if (LOOK || u + 1 < NU_) wg_split8(ra[cur ^ 1][0], ra[cur ^ 1][1], ah[cur ^ 1], al[cur ^ 1]);
                 if (i >= 1 && i <= TN && (LOOK || s_ + 1 < NK))
                     wg_split8(rb[i - 1][0], rb[i - 1][1], bh[kb ^ 1][i - 1], bl[kb ^ 1][i - 1]);
@@ -578,42 +645,34 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_dma_kernel(const Gemm
             slot = nslot;
         }
         wg_wait_vm<0>();   // (pieces past the end)
-        // (the tile origin made opaque per part: the offsets and bounds masks of the 16 TM TN atomics do not depend on the
-        // part, and hoisted out of the part loop they live, and spill, through the stage loop -- 256 VGPRs + 92 spilled and
-        // 234 spilled SGPRs for the 256 x 256 tile without this, 240 and none with it, as before the part loop.  The empty
-        // asm computes nothing; if a compiler stops honouring it, tools/kernel_resources.py shows spills and a ScratchSize
-        // above 0 for the three ring kernels)
         int m0e = m0, n0e = n0;
-        asm volatile("" : "+s"(m0e), "+s"(n0e));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0e + (wn * TN + j) * 32 + l31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0e + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                    if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
-                }
-            }
+        wg_opaque_origin(m0e, n0e);
+        wg_add_tile(acc, pgw_, p.M, p.N, m0e, n0e, wm, wn, l31, kk);
     }   // parts
+}
+
+// ---- launchers: each sets p.n_stages for its stage width and decides its LDS size and K split S (gridDim.x);
+// wg_launch is their common tail.  zgroups: groups carried by gridDim.z (gemm_wgrad_b3_kernel), 1 for the ring kernels.
+static int wg_tiles(const GemmWgradParams& p, int BM, int BN) { return ceil_div(p.M, BM) * ceil_div(p.N, BN); }
+template <class Kern>
+static void wg_launch(Kern kern, GemmWgradParams& p, int BM, int BN, int NT, int S, int zgroups, size_t lds,
+                      hipStream_t s) {
+    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    p.mtiles = ceil_div(p.M, BM);
+    dim3 grid(S, ceil_div(p.N, BN), p.mtiles * zgroups);
+    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, s, p);
 }
 
 template <int WM, int WN, int TM, int TN, int KP, int NST>
 static void launch_gemm_wgrad_dma(GemmWgradParams& p, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     p.n_stages = (int)(p.total / KP);
-    const size_t lds = (size_t)NST * (BM + BN) * KP * 4;
-    const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
     // one 8-wave workgroup per CU (see launch_gemm_wgrad), at least 8 stages each; grouped: over the flat stage space
     // of the G groups (wg_split_part), so gridDim.x is the split of a TILE and no grid dimension carries the group
-    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages);
+    const int S = wg_split_workgroups(wg_tiles(p, BM, BN), p.G > 0 ? p.G : 1, p.n_stages);
     auto kern = gemm_wgrad_dma_kernel<WM, WN, TM, TN, KP, NST>;
     static_assert(wg_sole_argument(decltype(kern){}), "wg_operands_kernarg reads p from the kernel-argument segment");
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    p.mtiles = ceil_div(p.M, BM);
-    dim3 grid(S, ceil_div(p.N, BN), p.mtiles);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
+    wg_launch(kern, p, BM, BN, 64 * WM * WN, S, 1, (size_t)NST * (BM + BN) * KP * 4, s);
 }
 
 // Implicit 3x3 form of the ring kernel (conv1's weight gradient at the shallow levels: gw[256][ci*9 + tap], A = the
@@ -676,23 +735,11 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
         const int r = (wm * TM + i) * 32 + l31;
         aoff[i] = r * 128 + (((2 * kk) ^ ((r >> 1) & 7)) << 4);
     }
-    // ---- B: this thread's units (fixed row n = ci * 9 + tap, k-group kg): plane, frame stride, tap
+    // ---- B: this thread's units (fixed row n = ci * 9 + tap, k-group kg): their taps (wg_tap)
     const int kg = tid % NU, r0 = tid / NU;
-    const float* uplane[BU];
-    long uns[BU];
-    int udy[BU], udx[BU];
-    bool uin1[BU];
+    WgTap tap[BU];
 #pragma unroll
-    for (int u = 0; u < BU; ++u) {
-        int row = n0 + r0 + u * (NT / NU);
-        if (row >= p.N) row = 0;
-        const int ci = row / 9, tap = row - ci * 9;
-        udy[u] = p.mirror ? 1 - tap / 3 : tap / 3 - 1;
-        udx[u] = p.mirror ? 1 - tap % 3 : tap % 3 - 1;
-        uin1[u] = ci < p.C1;
-        uplane[u] = uin1[u] ? pb_ + (long)ci * p.HW : pb2_ + (long)(ci - p.C1) * p.HW;
-        uns[u] = uin1[u] ? p.b_ns : p.b2_ns;
-    }
+    for (int u = 0; u < BU; ++u) tap[u] = wg_tap(n0 + r0 + u * (NT / NU), p, pb_, pb2_);
     const unsigned uHW = (unsigned)p.HW;
     const int S = gridDim.x;
     // my stages: first, first + step, ... (ungrouped: blockIdx.x, + S, ...; grouped: one part of my range)
@@ -717,15 +764,12 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
         edgemask = 0;
 #pragma unroll
         for (int u = 0; u < BU; ++u) {
-            const int yy = y + udy[u];
-            const bool rok = yy >= 0 && yy < p.H;
-            const float* src = uplane[u] + (long)f * uns[u] + (rok ? yy : y) * p.W + x0;
-            bst[u][0] = *reinterpret_cast<const float4*>(src);
-            bst[u][1] = *reinterpret_cast<const float4*>(src + 4);
-            const bool eok = udx[u] < 0 ? x0 > 0 : x0 + 8 < p.W;
-            bedge[u] = src[eok ? (udx[u] < 0 ? -1 : 8) : 0];
-            rowmask |= (rok ? 1u : 0u) << u;
-            edgemask |= (eok ? 1u : 0u) << u;
+            const WgTapRow r = wg_tap_load(tap[u].plane, tap[u].ns, tap[u].dy, tap[u].dx, f, y, x0, p.H, p.W);
+            bst[u][0] = r.v[0];
+            bst[u][1] = r.v[1];
+            bedge[u] = r.edge;
+            rowmask |= (r.rok ? 1u : 0u) << u;
+            edgemask |= (r.eok ? 1u : 0u) << u;
         }
     };
     auto commit = [&](const int buf) {
@@ -735,21 +779,9 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
         for (int u = 0; u < BU; ++u) {
             const int row = r0 + u * (NT / NU);
             if (row < BN) {
-                const bool okr = n0 + row < p.N && ((rowmask >> u) & 1u);
-                const bool eok = (edgemask >> u) & 1u;
-                const float v[8] = {bst[u][0].x, bst[u][0].y, bst[u][0].z, bst[u][0].w,
-                                    bst[u][1].x, bst[u][1].y, bst[u][1].z, bst[u][1].w};
                 bf16x8 hi, lo;
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {
-                    const float left = c == 0 ? (eok ? bedge[u] : 0.f) : v[c > 0 ? c - 1 : 0];
-                    const float right = c == 7 ? (eok ? bedge[u] : 0.f) : v[c < 7 ? c + 1 : 7];
-                    float x = udx[u] < 0 ? left : (udx[u] > 0 ? right : v[c]);
-                    x = okr ? x : 0.f;
-                    const __bf16 h = (__bf16)x;
-                    hi[c] = h;
-                    lo[c] = (__bf16)(x - (float)h);
-                }
+                wg_shift_split8(bst[u], bedge[u], tap[u].dx, n0 + row < p.N && ((rowmask >> u) & 1u), (edgemask >> u) & 1u,
+                                hi, lo);
                 const int o = row * RS + (SWZB ? kg ^ ((row >> 2) & 3) : kg);
                 Bh[o] = hi;
                 Bl[o] = lo;
@@ -763,37 +795,22 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
     };
     const int brow = (wn * TN * 32 + l31) * RS + (SWZB ? kk ^ ((l31 >> 2) & 3) : kk);   // unit kk + 2 s = kk ^ 2 s
 
-    // one pass per part (see gemm_wgrad_dma_kernel)
-    WgPart part;
-    long pos = p.G > 0 ? wg_split_begin(p.G, p.n_stages, S, blockIdx.x) : 0;
-    for (int part_i = 0; p.G > 0 ? wg_split_part(p.G, p.n_stages, S, blockIdx.x, pos, part) : part_i == 0; ++part_i) {
+    // one pass per part (WgParts)
+    for (WgParts ps = wg_parts_begin(p); wg_parts_next(p, ps); ++ps.i) {
         if (p.G > 0) {
-            const WgOperands o = wg_operands_kernarg(part.grp);
+            const WgOperands o = wg_part_enter(ps.part, first, step, nmine);
 #pragma unroll
             for (int j = 0; j < PPW; ++j) prow[j] = wg_rebase(prow[j], pa_, o.a);
 #pragma unroll
-            for (int u = 0; u < BU; ++u) uplane[u] = uin1[u] ? wg_rebase(uplane[u], pb_, o.b) : wg_rebase(uplane[u], pb2_, o.b2);
+            for (int u = 0; u < BU; ++u)
+                tap[u].plane = tap[u].first ? wg_rebase(tap[u].plane, pb_, o.b) : wg_rebase(tap[u].plane, pb2_, o.b2);
             pa_ = o.a;
             pb_ = o.b;
             pb2_ = o.b2;
             pgw_ = o.gw;
-            first = part.s0;
-            step = 1;
-            nmine = part.cnt;
         }
-        if (part_i > 0) {
-            // the previous part's atomics have retired, its fragment reads have returned, and nobody reads the slot and the
-            // planes the prologue is about to fill
-            wg_wait_vm<0>();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        if (ps.i > 0) wg_parts_drain();
+        wg_zero(acc);
 
         // prologue: stage 0 loaded and committed
         fetch(0, 0);
@@ -830,11 +847,7 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cur][i], bh[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bl[j], acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cur][i], bh[j], acc[i][j], 0, 0, 0);
-                    }
+                    for (int j = 0; j < TN; ++j) wg_mfma3(acc[i][j], ah[cur][i], al[cur][i], bh[j], bl[j]);
                 if (s_ + 1 < NK) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i) wg_split8(ra[cur ^ 1][i][0], ra[cur ^ 1][i][1], ah[cur ^ 1][i], al[cur ^ 1][i]);
@@ -844,19 +857,9 @@ void gemm_wgrad_dma_impl_kernel(const GemmWgradParams p) {
             slot ^= 1;
         }
         wg_wait_vm<0>();
-        int m0e = m0, n0e = n0;   // (opaque per part: see gemm_wgrad_dma_kernel)
-        asm volatile("" : "+s"(m0e), "+s"(n0e));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int n = n0e + (wn * TN + j) * 32 + l31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0e + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
-                    if (m < p.M && n < p.N) atomicAdd(&pgw_[(long)m * p.N + n], acc[i][j][r]);
-                }
-            }
+        int m0e = m0, n0e = n0;
+        wg_opaque_origin(m0e, n0e);
+        wg_add_tile(acc, pgw_, p.M, p.N, m0e, n0e, wm, wn, l31, kk);
     }   // parts
 }
 
@@ -865,53 +868,39 @@ static void launch_gemm_wgrad_dma_impl(GemmWgradParams& p, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     p.n_stages = (int)(p.total / 32);
     const size_t lds = wg_impl_lds(BM, BN);
-    const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    // (see launch_gemm_wgrad_dma); the narrow tiles at two workgroups per CU.  RFN_WGRAD_NARROW_PER_CU=1: one
-    static const int narrow_per_cu = getenv("RFN_WGRAD_NARROW_PER_CU") ? atoi(getenv("RFN_WGRAD_NARROW_PER_CU")) : 2;
-    const int per_cu = 2 * lds <= 160 * 1024 && narrow_per_cu == 2 ? 2 : 1;
-    const int S = wg_split_workgroups(tiles, p.G > 0 ? p.G : 1, p.n_stages, 256 * per_cu);
+    // (see launch_gemm_wgrad_dma); the narrow tiles, of which two fit a CU, at two workgroups per CU
+    const int per_cu = 2 * lds <= 160 * 1024 ? 2 : 1;
+    const int S = wg_split_workgroups(wg_tiles(p, BM, BN), p.G > 0 ? p.G : 1, p.n_stages, 256 * per_cu);
     auto kern = gemm_wgrad_dma_impl_kernel<WM, WN, TM, TN>;
     static_assert(wg_sole_argument(decltype(kern){}), "wg_operands_kernarg reads p from the kernel-argument segment");
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    p.mtiles = ceil_div(p.M, BM);
-    dim3 grid(S, ceil_div(p.N, BN), p.mtiles);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
+    wg_launch(kern, p, BM, BN, 64 * WM * WN, S, 1, lds, s);
 }
 
 template <int WM, int WN, int TM, int TN, int KP, int IMPL = 0>
 static void launch_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
     constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
     p.n_stages = (int)((p.total + KP - 1) / KP);
-    size_t lds = (size_t)2 * (BM + BN) * (KP / 8 + 1) * 16;
-    int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
     // K split: every workgroup ends with BM x BN float atomics into the SAME gw tile, and the chip retires only ~1.3 TB/s
     // of atomic bytes -- 1024 workgroups x 64 KB is 50 us of atomics on a problem whose GEMM takes 10.  So: as many
     // workgroups as the CUs can hold at once (8-wave tiles: one per CU, 4-wave: two), and at least 4 stages each.
-    static const int sdiv = getenv("RFN_WGRAD_SPLIT") ? atoi(getenv("RFN_WGRAD_SPLIT")) : 0;
     const int G = p.G > 0 ? p.G : 1;
-    int S = (sdiv > 0 ? sdiv : (WM * WN == 8 ? 256 : 512)) / (tiles * G);
+    int S = (WM * WN == 8 ? 256 : 512) / (wg_tiles(p, BM, BN) * G);
     if (S > p.n_stages / 4) S = p.n_stages / 4;
     if (S < 1) S = 1;
-    auto kern = gemm_wgrad_b3_kernel<WM, WN, TM, TN, KP, IMPL>;
-    if (lds > 65536) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    p.mtiles = ceil_div(p.M, BM);
-    dim3 grid(S, ceil_div(p.N, BN), p.mtiles * G);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, p);
+    wg_launch(gemm_wgrad_b3_kernel<WM, WN, TM, TN, KP, IMPL>, p, BM, BN, 64 * WM * WN, S, G,
+              (size_t)2 * (BM + BN) * (KP / 8 + 1) * 16, s);
 }
 
 // ---- kernel choice: choose_gemm_wgrad / choose_wgrad_implicit map a shape to a route (and launch nothing),
 // launch_wgrad_route is the only place a route is mapped to a launch, the label queries of the C ABI read the same table.
 // Instantiations: gemm_wgrad_dma_kernel<WM,WN,TM,TN,KP,NST>, gemm_wgrad_b3_kernel<WM,WN,TM,TN,KP[,IMPL]>.
-enum WgradB3Route { DMA_256x256, DMA_64x256, R_256x192, R_256x192_KP32, R_256x256, R_256x256_KP32, R_64x256, R_256x64,
-                    R_128x128, IMPL_DMA_256x192, IMPL_256x192, IMPL_32x256, IMPL_128x128, IMPL_DMA_256x64,
-                    IMPL_DMA_256x128 };
+enum WgradB3Route { DMA_256x256, DMA_64x256, R_256x192, R_256x256, R_64x256, R_256x64, R_128x128, IMPL_DMA_256x192,
+                    IMPL_256x192, IMPL_32x256, IMPL_128x128, IMPL_DMA_256x64, IMPL_DMA_256x128 };
 static const char* const kWgradB3Labels[] = {
     "gemm_wgrad_dma_kernel<2,4,4,2,32,2>",   // 256 x 256, two slots of 64 KB
     "gemm_wgrad_dma_kernel<1,8,2,1,32,3>",   // 64 x 256, ring of 3 x 40 KB
     "gemm_wgrad_b3_kernel<4,2,2,3,64>",      // 256 x 192, 8 waves, 64-pixel stages
-    "gemm_wgrad_b3_kernel<4,2,2,3,32>",      // (RFN_WGRAD_VARIANT=2: 32-pixel stages)
     "gemm_wgrad_b3_kernel<2,4,4,2,64>",      // 256 x 256, 8 waves, 64-pixel stages
-    "gemm_wgrad_b3_kernel<2,4,4,2,32>",      // (RFN_WGRAD_VARIANT=2)
     "gemm_wgrad_b3_kernel<1,4,2,2,32>",      // 64 x 256
     "gemm_wgrad_b3_kernel<4,1,2,2,32>",      // 256 x 64
     "gemm_wgrad_b3_kernel<2,2,2,2,64>",      // 128 x 128
@@ -937,18 +926,15 @@ static GemmWgradParams wgrad_shape(int M, int Nc, long a_ns, long b_ns, int G, i
 
 static WgradB3Route choose_gemm_wgrad(const GemmWgradParams& p) {
     const int M = p.M, Nc = p.N;
-    static const int variant = getenv("RFN_WGRAD_VARIANT") ? atoi(getenv("RFN_WGRAD_VARIANT")) : 0;
     // the LDS-DMA kernels take a plain (1x1-form) gradient -- or a group of them: the K gradients of a level together are
     // the problem size -- over whole 32-pixel stages
-    if (variant == 0 && !wgrad_dma_off() && p.HW % 32 == 0 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 &&
+    if (!wgrad_dma_off() && p.HW % 32 == 0 && p.total * (p.G > 0 ? p.G : 1) >= 100000 && p.total >= 2048 &&
         p.a_ns % 4 == 0 && p.b_ns % 4 == 0 && Nc > 128 && Nc % 256 == 0) {
         if (M >= 192) return DMA_256x256;
         if (M <= 64) return DMA_64x256;
     }
-    if (variant != 1 && M > 128 && Nc > 128 && p.total >= 100000) {
-        if (ceil_div(Nc, 192) * 192 < ceil_div(Nc, 256) * 256) return variant == 2 ? R_256x192_KP32 : R_256x192;
-        return variant == 2 ? R_256x256_KP32 : R_256x256;
-    }
+    if (M > 128 && Nc > 128 && p.total >= 100000)
+        return ceil_div(Nc, 192) * 192 < ceil_div(Nc, 256) * 256 ? R_256x192 : R_256x256;
     return M <= 64 ? R_64x256 : (Nc <= 64 ? R_256x64 : R_128x128);
 }
 extern "C" const char* rfn_gemm_wgrad_kernel_label_bf16x3(int M, int Nc, long a_ns, long b_ns, int G, int F, int HW) {
@@ -1017,9 +1003,7 @@ static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s
         case DMA_256x256:      return launch_gemm_wgrad_dma<2, 4, 4, 2, 32, 2>(p, s);
         case DMA_64x256:       return launch_gemm_wgrad_dma<1, 8, 2, 1, 32, 3>(p, s);
         case R_256x192:        return launch_gemm_wgrad<4, 2, 2, 3, 64>(p, s);
-        case R_256x192_KP32:   return launch_gemm_wgrad<4, 2, 2, 3, 32>(p, s);
         case R_256x256:        return launch_gemm_wgrad<2, 4, 4, 2, 64>(p, s);
-        case R_256x256_KP32:   return launch_gemm_wgrad<2, 4, 4, 2, 32>(p, s);
         case R_64x256:         return launch_gemm_wgrad<1, 4, 2, 2, 32>(p, s);
         case R_256x64:         return launch_gemm_wgrad<4, 1, 2, 2, 32>(p, s);
         case R_128x128:        return launch_gemm_wgrad<2, 2, 2, 2, 64>(p, s);
@@ -1046,111 +1030,107 @@ static GemmWgradParams wgrad_params(int G, const float* const* a, long a_ns, int
     return p;
 }
 
-extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw,
-                                     int F, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(a && b && gw && M > 0 && Nc > 0 && F >= 0 && HW > 0, -1);
-    RFN_CHECK_ARG(HW % 4 == 0 && a_ns % 4 == 0 && b_ns % 4 == 0, -2);
-    RFN_CHECK_ARG((((uintptr_t)a | (uintptr_t)b) & 15) == 0, -3);
-    RFN_CHECK_ARG((long)F * HW < (1L << 31) - 4096, -4);
-    if (F == 0) return 0;
-    GemmWgradParams p = wgrad_params(0, &a, a_ns, M, &b, b_ns, nullptr, Nc, &gw, F, HW);
-    launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
-    RFN_LAUNCH_CHECK();
-    return 0;
+// ---- entry points.  Each single / grouped pair shares one body: the single form passes G = 0 and the address of its
+// one pointer per operand, after the null check of those pointers (-1; a group's null pointer is a -3 of the grouped
+// form, which checks G itself).  The body's checks run in the order of the codes: -1 sizes and tables, -2 pixel counts
+// and strides the 16-byte loads cannot take, -3 the operands of every group (non-null, inputs 16-byte aligned), -4 the
+// 32-bit pixel index; then F == 0 returns 0 -- all before the kernel choice and the launch.
+static bool wg_aligned16(const float* x, const float* y, const float* z = nullptr) {
+    return (((uintptr_t)x | (uintptr_t)y | (uintptr_t)z) & 15) == 0;
 }
 
-// G (<= 16) weight gradients of one shape in ONE launch: gw[g][M][Nc] += sum a[g] b[g]^T (same strides, F, HW for all).
-extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, int M, const float* const* b, long b_ns,
-                                             int Nc, float* const* gw, int G, int F, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(a && b && gw && G >= 1 && G <= 16 && M > 0 && Nc > 0 && F >= 0 && HW > 0, -1);
+static int rfn_gemm_wgrad_bf16x3_body(int G, const float* const* a, long a_ns, int M, const float* const* b, long b_ns,
+                                      int Nc, float* const* gw, int F, int HW, rfn_stream_t stream) {
+    RFN_CHECK_ARG(a && b && gw && M > 0 && Nc > 0 && F >= 0 && HW > 0, -1);
     RFN_CHECK_ARG(HW % 4 == 0 && a_ns % 4 == 0 && b_ns % 4 == 0, -2);
+    for (int g = 0; g < (G > 0 ? G : 1); ++g) RFN_CHECK_ARG(a[g] && b[g] && gw[g] && wg_aligned16(a[g], b[g]), -3);
     RFN_CHECK_ARG((long)F * HW < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    for (int g = 0; g < G; ++g)
-        RFN_CHECK_ARG(a[g] && b[g] && gw[g] && (((uintptr_t)a[g] | (uintptr_t)b[g]) & 15) == 0, -3);
     GemmWgradParams p = wgrad_params(G, a, a_ns, M, b, b_ns, nullptr, Nc, gw, F, HW);
     launch_wgrad_route(p, choose_gemm_wgrad(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int rfn_gemm_wgrad_bf16x3(const float* a, long a_ns, int M, const float* b, long b_ns, int Nc, float* gw,
+                                     int F, int HW, rfn_stream_t stream) {
+    RFN_CHECK_ARG(a && b && gw, -1);
+    return rfn_gemm_wgrad_bf16x3_body(0, &a, a_ns, M, &b, b_ns, Nc, &gw, F, HW, stream);
+}
+// G (<= 16) weight gradients of one shape in ONE launch: gw[g][M][Nc] += sum a[g] b[g]^T (same strides, F, HW for all).
+extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, int M, const float* const* b, long b_ns,
+                                             int Nc, float* const* gw, int G, int F, int HW, rfn_stream_t stream) {
+    RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
+    return rfn_gemm_wgrad_bf16x3_body(G, a, a_ns, M, b, b_ns, Nc, gw, F, HW, stream);
+}
 
 // 3x3 weight gradient without the im2col buffer: gw[co][ci][tap] = sum_{frames,pixels} g[co][px] * in[ci][px + tap]
 // (pad 1), the shifted planes built while staging (rows of one image row, W % 8 == 0).  The output is the torch weight
-// layout [Cout][Cin][3][3] (the GEMM on rfn_im2col3x3_f32's buffer gives [Cout][tap][Cin] instead).
-extern "C" int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
-                                                 const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
-                                                 rfn_stream_t stream) {
-    RFN_CHECK_ARG(g && in1 && gw && Cout > 0 && C1 > 0 && C2 >= 0 && (C2 == 0 || in2) && F >= 0 && H > 0 && W > 0, -1);
+// layout [Cout][Cin][3][3] (the GEMM on rfn_im2col3x3_f32's buffer gives [Cout][tap][Cin] instead).  Per group: g, in1,
+// in2 (ignored when C2 == 0), gw.  (H <= 0 or W <= 0 alone is a -1 of the single and a -2 of the grouped form.)
+static int rfn_conv3x3_wgrad_implicit_bf16x3_body(int G, const float* const* g, long g_ns, int Cout,
+                                                  const float* const* in1, long in1_ns, int C1, const float* const* in2,
+                                                  long in2_ns, int C2, float* const* gw, int F, int H, int W,
+                                                  rfn_stream_t stream) {
+    RFN_CHECK_ARG(g && in1 && gw && Cout > 0 && C1 > 0 && C2 >= 0 && (C2 == 0 || in2) && F >= 0, -1);
+    RFN_CHECK_ARG(H > 0 && W > 0, G > 0 ? -2 : -1);
     RFN_CHECK_ARG(W % 8 == 0 && g_ns % 4 == 0 && in1_ns % 4 == 0 && (C2 == 0 || in2_ns % 4 == 0), -2);
-    RFN_CHECK_ARG((((uintptr_t)g | (uintptr_t)in1 | (uintptr_t)(C2 ? in2 : in1)) & 15) == 0, -3);
+    for (int i = 0; i < (G > 0 ? G : 1); ++i)
+        RFN_CHECK_ARG(g[i] && in1[i] && gw[i] && (C2 == 0 || in2[i]) && wg_aligned16(g[i], in1[i], C2 ? in2[i] : in1[i]),
+                      -3);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p = wgrad_params(0, &g, g_ns, Cout, &in1, in1_ns, C2 ? &in2 : nullptr, 9 * (C1 + C2), &gw, F, H * W);
-    p.b2_ns = C2 ? in2_ns : in1_ns; p.C1 = C1; p.C2 = C2; p.H = H; p.W = W;
-    launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// grouped form: G gradients of one shape (per group: g, in1, in2 (ignored when C2 == 0), gw)
-extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, long g_ns, int Cout,
-                                                         const float* const* in1, long in1_ns, int C1,
-                                                         const float* const* in2, long in2_ns, int C2, float* const* gw,
-                                                         int G, int F, int H, int W, rfn_stream_t stream) {
-    RFN_CHECK_ARG(g && in1 && gw && G >= 1 && G <= 16 && Cout > 0 && C1 > 0 && C2 >= 0 && (C2 == 0 || in2) && F >= 0, -1);
-    RFN_CHECK_ARG(H > 0 && W > 0 && W % 8 == 0 && g_ns % 4 == 0 && in1_ns % 4 == 0 && (C2 == 0 || in2_ns % 4 == 0), -2);
-    RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
-    if (F == 0) return 0;
-    for (int i = 0; i < G; ++i) {
-        RFN_CHECK_ARG(g[i] && in1[i] && gw[i] && (C2 == 0 || in2[i]), -3);
-        RFN_CHECK_ARG((((uintptr_t)g[i] | (uintptr_t)in1[i] | (uintptr_t)(C2 ? in2[i] : in1[i])) & 15) == 0, -3);
-    }
     GemmWgradParams p = wgrad_params(G, g, g_ns, Cout, in1, in1_ns, C2 ? in2 : nullptr, 9 * (C1 + C2), gw, F, H * W);
     p.b2_ns = C2 ? in2_ns : in1_ns; p.C1 = C1; p.C2 = C2; p.H = H; p.W = W;
     launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
+extern "C" int rfn_conv3x3_wgrad_implicit_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
+                                                 const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
+                                                 rfn_stream_t stream) {
+    RFN_CHECK_ARG(g && in1 && gw && (C2 <= 0 || in2), -1);
+    return rfn_conv3x3_wgrad_implicit_bf16x3_body(0, &g, g_ns, Cout, &in1, in1_ns, C1, &in2, in2_ns, C2, &gw, F, H, W,
+                                                  stream);
+}
+extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, long g_ns, int Cout,
+                                                         const float* const* in1, long in1_ns, int C1,
+                                                         const float* const* in2, long in2_ns, int C2, float* const* gw,
+                                                         int G, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
+    return rfn_conv3x3_wgrad_implicit_bf16x3_body(G, g, g_ns, Cout, in1, in1_ns, C1, in2, in2_ns, C2, gw, F, H, W, stream);
+}
 
 // 3x3 weight gradient of a conv with few outputs, without the tap-scattered gradient buffer: the roles of the implicit
 // form swapped and the taps mirrored (GemmWgradParams::mirror).  gwT[ci][co][tap] = sum_{frames,pixels} h[ci][q] *
-// g[co][q - tap] = gw[co][ci][tap]: the TRANSPOSE of the torch layout, [Cin][C][3][3].  -5: the shape has no mirrored
-// route (rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3 returns "").
-extern "C" int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C,
-                                                 float* gwT, int F, int H, int W, rfn_stream_t stream) {
-    RFN_CHECK_ARG(h && g && gwT && Cin > 0 && C > 0 && F >= 0 && H > 0 && W > 0, -1);
+// g[co][q - tap] = gw[co][ci][tap]: the TRANSPOSE of the torch layout, [Cin][C][3][3].  Per group: h, g, gwT.  Every
+// shape that passes the checks has a mirrored route (choose_wgrad_implicit_mirrored refuses only W % 8 != 0).
+static int rfn_conv3x3_wgrad_mirrored_bf16x3_body(int G, const float* const* h, long h_ns, int Cin,
+                                                  const float* const* g, long g_ns, int C, float* const* gwT, int F, int H,
+                                                  int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(h && g && gwT && Cin > 0 && C > 0 && F >= 0, -1);
+    RFN_CHECK_ARG(H > 0 && W > 0, G > 0 ? -2 : -1);
     RFN_CHECK_ARG(W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
-    RFN_CHECK_ARG((((uintptr_t)h | (uintptr_t)g) & 15) == 0, -3);
+    for (int i = 0; i < (G > 0 ? G : 1); ++i) RFN_CHECK_ARG(h[i] && g[i] && gwT[i] && wg_aligned16(h[i], g[i]), -3);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
-    GemmWgradParams p = wgrad_params(0, &h, h_ns, Cin, &g, g_ns, nullptr, 9 * C, &gwT, F, H * W);
+    GemmWgradParams p = wgrad_params(G, h, h_ns, Cin, g, g_ns, nullptr, 9 * C, gwT, F, H * W);
     p.b2_ns = g_ns; p.C1 = C; p.H = H; p.W = W; p.mirror = 1;
-    WgradB3Route r;
-    RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
+    WgradB3Route r = IMPL_128x128;
+    choose_wgrad_implicit_mirrored(p, r);
     launch_wgrad_route(p, r, (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
-
-// grouped form: G gradients of one shape (per group: h, g, gwT)
+extern "C" int rfn_conv3x3_wgrad_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C,
+                                                 float* gwT, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(h && g && gwT, -1);
+    return rfn_conv3x3_wgrad_mirrored_bf16x3_body(0, &h, h_ns, Cin, &g, g_ns, C, &gwT, F, H, W, stream);
+}
 extern "C" int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, long h_ns, int Cin, const float* const* g,
                                                          long g_ns, int C, float* const* gwT, int G, int F, int H, int W,
                                                          rfn_stream_t stream) {
-    RFN_CHECK_ARG(h && g && gwT && G >= 1 && G <= 16 && Cin > 0 && C > 0 && F >= 0, -1);
-    RFN_CHECK_ARG(H > 0 && W > 0 && W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
-    RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
-    if (F == 0) return 0;
-    for (int i = 0; i < G; ++i) {
-        RFN_CHECK_ARG(h[i] && g[i] && gwT[i], -3);
-        RFN_CHECK_ARG((((uintptr_t)h[i] | (uintptr_t)g[i]) & 15) == 0, -3);
-    }
-    GemmWgradParams p = wgrad_params(G, h, h_ns, Cin, g, g_ns, nullptr, 9 * C, gwT, F, H * W);
-    p.b2_ns = g_ns; p.C1 = C; p.H = H; p.W = W; p.mirror = 1;
-    WgradB3Route r;
-    RFN_CHECK_ARG(choose_wgrad_implicit_mirrored(p, r), -5);
-    launch_wgrad_route(p, r, (hipStream_t)stream);
-    RFN_LAUNCH_CHECK();
-    return 0;
+    RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
+    return rfn_conv3x3_wgrad_mirrored_bf16x3_body(G, h, h_ns, Cin, g, g_ns, C, gwT, F, H, W, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ im2col (3x3, pad 1)

@@ -584,8 +584,7 @@ ROUTES = {
     "conv3x3_ws_kernel<1,2,0>+actbwd", WS1 + "+actbwd", G3 % "2,2,1,1" + "+actbwd", G3 % "2,2,1,2" + "+actbwd",
     G1 % "2,2,1,1" + "+actbwd",
     "dgrad_small_kernel",
-    # choose_gemm_wgrad, single and grouped (the two RFN_WGRAD_VARIANT tilings are read from the environment once per
-    # process and are not selections of the shipped configuration)
+    # choose_gemm_wgrad, single and grouped
     DMA % "2,4,4,2,32,2", DMA % "1,8,2,1,32,3", B3 % "4,2,2,3,64", B3 % "2,4,4,2,64", B3 % "1,4,2,2,32",
     B3 % "4,1,2,2,32", B3 % "2,2,2,2,64",
     DMA % "grouped 2,4,4,2,32,2", DMA % "grouped 1,8,2,1,32,3", B3 % "grouped 4,2,2,3,64", B3 % "grouped 2,4,4,2,64",
