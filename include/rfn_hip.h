@@ -563,6 +563,24 @@ int rfn_mol_nll_bwd(const float* x, const float* l, const float* lse, const floa
                     int C, int M, int HW, rfn_stream_t stream);
 int rfn_mol_sample(const float* l, const float* u_mix, const float* u_x, float* out, int N, int C, int M, int HW,
                    rfn_stream_t stream);
+/* The sampler with addressed uniforms (SRNN.predict_draws; DESIGN.md section 20 is the contract): what rfn_mol_sample
+ * computes, by the same device function, on uniforms made inside the kernel from their address.  l [rows,Cl,HW], out
+ * [rows,C,HW]; row i of a launch is draw first_draw + i / B of sequence first_seq + i % B (draw-major, as
+ * rfn_keyed_normal_f32).  Block j of pixel p (the index inside the frame) is
+ *   Philox4x64-10(key = (seed, (step << 32) | slot), counter = (j, p, seq, draw)),  slot 16 mixture, slot 17 colour
+ * (rfn_keyed_normal_f32 owns slots 0..7, so no address is shared with it).  Uniform e of a pixel (e = m for the mixture,
+ * e = c for the colour) is the 32-bit half e % 8 of block e / 8, the halves in the order high half of w0, low half of
+ * w0, high half of w1, ...:
+ *   u = min(max((2 (half >> 9) + 1) * 2^-24, 1e-5f), 1 - 1e-5f)
+ * The numerator is an odd integer below 2^24: exact in fp32, never 0 or 1.  A value depends on (seed, step, slot,
+ * sequence, draw, pixel, element) and on nothing else: not on rows, B, the grid or the other rows of the launch.
+ * rows is a multiple of B >= 1; seed, step, first_seq, first_draw >= 0.  No atomics, no LDS, no scratch.  One launch.
+ * rfn_mol_keyed_uniforms writes exactly those uniforms as u_mix [rows,HW,M] and u_x [rows,HW,C]:
+ * rfn_mol_sample(l, u_mix, u_x) then equals rfn_mol_sample_keyed(l) bit for bit. */
+int rfn_mol_sample_keyed(const float* l, float* out, int rows, int B, int C, int M, int HW, long seed, int step,
+                         long first_seq, long first_draw, rfn_stream_t stream);
+int rfn_mol_keyed_uniforms(float* u_mix, float* u_x, int rows, int B, int C, int M, int HW, long seed, int step,
+                           long first_seq, long first_draw, rfn_stream_t stream);
 
 /* ---- a9  ConvLSTMLayer.forward gate update  (Utils/modules.py:370-377): cc = conv output [N,4*Hc,HW] in gate order
  * i,f,o,g;  i=σ(cc_i+Wci∘c) f=σ(cc_f+Wcf∘c) g=tanh(cc_g) c'=f∘c+i∘g o=σ(cc_o+Wco∘c') h'=o∘tanh(c').

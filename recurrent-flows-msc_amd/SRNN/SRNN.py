@@ -9,7 +9,10 @@ convolutions, ConvTranspose2d, Linear and the norm layers are PyTorch modules.
 
 Every method that draws takes `draws=None`: a list of tensors (or (kind, tensor) pairs, as the fixtures store them)
 consumed in the order the reference draws — standard normals of each rsample, the uniforms of the dequantisation and of
-the mixture sampler (u_mix [N,H,W,M], then u_x [N,H,W,C]).  Not here: elbo_importance_weighting."""
+the mixture sampler (u_mix [N,H,W,M], then u_x [N,H,W,C]).
+
+`predict_draws` (several draws of every sequence in one pass, with addressed noise) and `elbo_importance_weighting` (the
+bound the reference reports as the baselines' bits/dim) are what the Evaluator drives for srnn.pt; DESIGN.md section 20."""
 import numpy as np
 import torch
 import torch.distributions as td
@@ -257,7 +260,13 @@ class SRNN(nn.Module):
         return batch_reduce(kl_loss).mean(), nll_loss.mean()
 
     # ------------------------------------------------------------------------------------------------ generation
+    # predict ends in `.cpu()`, as the reference's does; `_predict_device` returns the same tensors where they were
+    # computed (the Evaluator's FVD path embeds them without a host round trip).
     def predict(self, xt, n_predictions, n_conditions, draws=None):
+        true_x, predictions = self._predict_device(xt, n_predictions, n_conditions, draws)
+        return true_x.cpu(), predictions.cpu()
+
+    def _predict_device(self, xt, n_predictions, n_conditions, draws=None):
         b, t, c, h, w = xt.shape
         assert n_conditions <= t, "n_conditions > t, number of conditioned frames is greater than number of frames"
         d = _Draws(draws, xt.device)
@@ -279,7 +288,156 @@ class SRNN(nn.Module):
             zprev, hprev, cprev = z_t, ht, ct
             predictions.append(prediction.detach())
         d.done()
-        return torch.stack(true_x, 0).cpu(), torch.stack(predictions, 0).cpu()
+        return torch.stack(true_x, 0), torch.stack(predictions, 0)
+
+    def predict_draws(self, xt, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+        """`predict` for n_draws independent draws of every sequence in one pass, with addressed noise (the counterpart
+        of RFN.predict_draws, without temperatures): returns (true_x, predictions), predictions [n_predictions, n_draws,
+        B, C, H, W] on the CPU (`_predict_draws_device`: the same on the device).  phi_x_t and lstm_h run once over the
+        conditioning frames of the B sequences; from the first prior sample on everything runs on n_draws*B rows,
+        draw-major (row r*B + b: draw first_draw + r of sequence first_seq + b); the [batch_size, ...] initial states
+        are repeated.
+        Noise: conditioning step i (1 .. n_conditions-1) uses t = i, rfn_hip.ops.keyed_normal slot 0 for the prior eps.
+        Generated frame i uses t = n_conditions + i: slot 0 for the prior eps and, for loss_type "mol", the mixture
+        sampler's addressed uniforms at that step (rfn_hip.ops.mol_sample_keyed).  The other loss
+        types have no sampler noise.  A frame therefore depends on (seed, sequence id, draw id) and the data alone: not
+        on B, on n_draws, on how the draws are split into calls, or on torch's generator, which is left untouched.
+        Eval mode only: batch statistics would couple the draws."""
+        true_x, predictions = self._predict_draws_device(xt, n_predictions, n_conditions, n_draws, seed, first_seq,
+                                                         first_draw)
+        return true_x.cpu(), predictions.cpu()
+
+    def _predict_draws_device(self, xt, n_predictions, n_conditions, n_draws, seed, first_seq=0, first_draw=0):
+        from rfn_hip import ops as K
+        assert len(xt.shape) == 5, "xt must be [bs, t, c, h, w]"
+        if self.training:
+            raise RuntimeError("SRNN.predict_draws needs eval mode: in training mode the batch statistics of the "
+                               "normalisation layers would couple the draws (call model.eval() first)")
+        b, t, c, h, w = xt.shape
+        assert n_conditions <= t, "n_conditions > t, number of conditioned frames is greater than number of frames"
+        P, B = int(n_draws), int(b)
+        if P < 1:
+            raise ValueError("SRNN.predict_draws: n_draws must be at least 1, got %d" % P)
+
+        def rep(v):   # draw-major: row r*B + b is sequence b
+            return v.repeat((P,) + (1,) * (v.dim() - 1))
+
+        def prior_sample(ht, zprev, step):
+            dist = self._prior_dist(ht, zprev)
+            eps, = K.keyed_normal([tuple(dist.loc.shape[1:])], B, P, seed, step, first_seq, first_draw, device=xt.device)
+            return dist.loc + dist.scale * eps
+
+        with torch.no_grad():
+            hprev, cprev, zprev, _, _, _, _, _, _ = self.get_inits()
+            store_ht = []
+            for i in range(1, n_conditions):
+                _, hprev, cprev = self.lstm_h(self.phi_x_t(xt[:, i - 1]).unsqueeze(1), hprev, cprev)
+                store_ht.append(hprev)
+            zprev = rep(zprev)
+            for i in range(1, n_conditions):
+                zprev = prior_sample(rep(store_ht[i - 1]), zprev, i)
+            true_x = xt[:, :n_conditions].transpose(0, 1).detach().clone()
+            prediction, hprev, cprev = rep(xt[:, n_conditions - 1]), rep(hprev), rep(cprev)
+            frames = []
+            for i in range(n_predictions):
+                step = n_conditions + i
+                _, ht, ct = self.lstm_h(self.phi_x_t(prediction).unsqueeze(1), hprev, cprev)
+                z_t = prior_sample(ht, zprev, step)
+                prediction = self._decode(ht, z_t)
+                if self.loss_type == "mol":
+                    prediction = self.likelihood(logits=prediction).sample_keyed(B, seed, step, first_seq, first_draw)
+                zprev, hprev, cprev = z_t, ht, ct
+                frames.append(prediction.detach())
+            if frames:
+                predictions = torch.stack(frames, 0).view(n_predictions, P, B, c, h, w)
+            else:
+                predictions = torch.zeros((0, P, B, c, h, w), device=xt.device)
+        return true_x, predictions
+
+    # ------------------------------------------------------------------------------------------------ evaluation
+    def _frame_nll(self, dec_mean_t, x_i, x_noise=None, nll_unif=None):
+        """-log p(x_i | decoder output) per row, as `loss` computes it per step"""
+        if self.loss_type == "bernoulli":
+            return -batch_reduce(td.Bernoulli(probs=dec_mean_t).log_prob(x_i))
+        if self.loss_type == "gaussian":
+            scale = nn.functional.softplus(self.variance) * torch.ones_like(dec_mean_t)
+            return -batch_reduce(td.Normal(dec_mean_t, scale).log_prob(x_noise)) - nll_unif
+        if self.loss_type == "mse":
+            return batch_reduce(self.mse_criterion(dec_mean_t, x_i))
+        if self.loss_type == "mol":
+            from rfn_hip import ops as K
+            return K.mol_nll(x_i.detach(), dec_mean_t, reduce="frame")
+        raise ValueError("undefined loss %r" % (self.loss_type,))
+
+    def elbo_importance_weighting(self, xt, K, draws=None, defer_decoder=None):
+        """The importance-weighted bound the reference reports as its baselines' bits/dim (SRNN/SRNN.py:482-579 of the
+        reference), as that code behaves: zprevx and zprev chain through the K inner samples and on into the next time
+        step; with res_q the prior is taken on zprevx; without smoothing phi_x_t(x_i) belongs to every inner sample; per
+        inner sample the draws are the encoder eps, the prior eps and, for "gaussian", the dequantisation uniforms.
+        Returns sum_t -mean_b(logsumexp_k(log p(x|z_k) + log p(z_k) - log q(z_k|x)) - log K).  The K x B tables stay on
+        the device.
+        The decoder does not feed the recurrence.  In eval mode (defer_decoder None) dec, dec_mean and the likelihood of
+        a time step therefore run ONCE over the K*B rows collected in the k loop (one mol_nll launch per step in place
+        of K), and the deterministic phi_x_t(x_i) is taken from the pass over the frames; in training mode every inner
+        sample makes its own calls, because the batch statistics of the norm layers are per call in the reference.
+        defer_decoder = False / True forces either form of the decoder."""
+        b, t, c, h, w = xt.shape
+        K = int(K)
+        if K < 1:
+            raise ValueError("SRNN.elbo_importance_weighting: K must be at least 1, got %d" % K)
+        defer = (not self.training) if defer_decoder is None else bool(defer_decoder)
+        d = _Draws(draws, xt.device)
+        hprev, cprev, zprev, zprevx, aprev, caprev, _, _, _ = self.get_inits()
+        feats = [self.phi_x_t(xt[:, i]) for i in range(t)]
+        store_ht = []
+        for i in range(1, t):
+            _, hprev, cprev = self.lstm_h(feats[i - 1].unsqueeze(1), hprev, cprev)
+            store_ht.append(hprev)
+        if self.enable_smoothing:
+            store_at = self._smoothing_states(store_ht, lambda i: feats[i], t, aprev, caprev)
+        log_k = float(np.log(K))
+        loss = 0
+        for i in range(1, t):
+            ht, x_i = store_ht[i - 1], xt[:, i]
+            logpzs, logqzxs, nlls, ztxs, noisy, unifs = [], [], [], [], [], []
+            for k in range(K):
+                if self.enable_smoothing:
+                    enc_t = self.enc(torch.cat([store_at[i - 1], self.phi_z(zprevx)], 1))
+                else:
+                    feat_i = self.phi_x_t(x_i) if self.training else feats[i]
+                    enc_t = self.enc(torch.cat([ht, self.phi_z(zprevx), feat_i], 1))
+                enc_std_t = self.enc_std(enc_t)
+                prior_dist = self._prior_dist(ht, zprevx if self.res_q else zprev)
+                enc_mean_t = self.enc_mean(enc_t)
+                if self.res_q:
+                    enc_mean_t = prior_dist.loc + enc_mean_t
+                enc_dist = td.Normal(enc_mean_t, enc_std_t)
+                z_tx = d.rsample(enc_dist)
+                z_t = d.rsample(prior_dist)
+                x_noise = nll_unif = None
+                if self.loss_type == "gaussian":
+                    x_noise, nll_unif = self.uniform_binning_correction(x_i, d)
+                if defer:
+                    ztxs.append(z_tx)
+                    noisy.append(x_noise)
+                    unifs.append(nll_unif)
+                else:
+                    nlls.append(self._frame_nll(self._decode(ht, z_tx), x_i, x_noise, nll_unif))
+                logpzs.append(prior_dist.log_prob(z_t).sum([-1]))
+                logqzxs.append(enc_dist.log_prob(z_tx).sum([-1]))
+                zprevx, zprev = z_tx, z_t
+            if defer:   # rows k*B + b
+                gauss = self.loss_type == "gaussian"
+                nll = self._frame_nll(self._decode(ht.repeat(K, 1, 1, 1), torch.cat(ztxs, 0)), x_i.repeat(K, 1, 1, 1),
+                                      torch.cat(noisy, 0) if gauss else None, torch.cat(unifs, 0) if gauss else None)
+                nll = nll.view(K, b)
+            else:
+                nll = torch.stack(nlls, 0)
+            # (the reference adds its "lpx_Gz_obs", which is the NEGATIVE log-likelihood, as it stands: kept)
+            table = nll + torch.stack(logpzs, 0) - torch.stack(logqzxs, 0)
+            loss = loss - torch.mean(torch.logsumexp(table, 0) - log_k)
+        d.done()
+        return loss
 
     def reconstruct(self, xt, draws=None):
         b, t, c, h, w = xt.shape

@@ -1,7 +1,8 @@
 """Mixture of discretized logistics with the reference's names (Utils/discretize_logits.py of the reference, the
 PixelCNN++ likelihood): `DiscretizedMixtureLogits(nr_mix)(logits=l)` gives an object with `.log_prob(value)` ([N,H,W]) and
-`.sample()` ([N,C,H,W]).  Both run on the HIP kernels (rfn_hip.ops.mol_nll / mol_sample): device
-tensors only, gradient into the logits only.  `DiscretizedMixtureLogits` is the RGB form (10 channels per component),
+`.sample()` ([N,C,H,W]), plus `.sample_keyed(...)`, the sampler with addressed uniforms.  All run on the HIP kernels
+(rfn_hip.ops.mol_nll / mol_sample / mol_sample_keyed; DESIGN.md sections 19 and 20): device tensors only, gradient into
+the logits only.  `DiscretizedMixtureLogits` is the RGB form (10 channels per component),
 `DiscretizedMixtureLogits_1d` the one-channel form (3 per component)."""
 from rfn_hip import ops as K
 
@@ -22,6 +23,11 @@ class _MixtureDistribution:
     def sample(self, u_mix=None, u_x=None, generator=None):
         """u_mix [N,H,W,nr_mix], u_x [N,H,W,C]: recorded draws to replay (the reference draws them in this order)"""
         return K.mol_sample(self.logits, u_mix, u_x, generator=generator, channels=self.channels)
+
+    def sample_keyed(self, B, seed, step, first_seq=0, first_draw=0):
+        """`sample` with addressed uniforms (rfn_hip.ops.mol_sample_keyed): row r*B + b of the
+        logits is draw first_draw + r of sequence first_seq + b.  No uniform tensor, torch's generator untouched."""
+        return K.mol_sample_keyed(self.logits, B, seed, step, first_seq, first_draw, channels=self.channels)
 
 
 class DiscretizedMixtureLogitsDistribution(_MixtureDistribution):

@@ -10,6 +10,7 @@
 // and the frame's sum is its workgroups' partials added in index order by a second small launch: no atomics, and the
 // bits of a frame's sum depend on nothing but that frame.
 #include "common.h"
+#include "philox.h"
 #include "../../include/rfn_hip.h"
 
 namespace {
@@ -196,7 +197,106 @@ __global__ __launch_bounds__(256) void mol_nll_bwd_kernel(const float* __restric
     }
 }
 
-// u_mix [N,HW,M], u_x [N,HW,C] (the reference's draw shapes), out [N,C,HW]
+// ---- the sampler.  The arithmetic after the uniforms is ONE device function, mol_sample_pixel; its uniforms come from a
+// source object, eight mixture uniforms (one "block") at a time and the C colour uniforms at once, always through
+// compile-time register indices (a run-time index into u[] would put it in scratch memory):
+//   MolGivenUniforms  reads them from u_mix [N,HW,M] and u_x [N,HW,C] (the reference's draw shapes)   rfn_mol_sample
+//   MolKeyedUniforms  makes them from their address (below)                                            rfn_mol_sample_keyed
+// so the keyed sampler and the sampler fed the emitted uniforms run the same operations on the same numbers.
+struct MolGivenUniforms {
+    const float* um;  // this pixel's M mixture uniforms
+    const float* ux;  // this pixel's C colour uniforms
+    __device__ __forceinline__ void mix_block(int j, int M, float (&u)[8]) const {
+        const int left = M - 8 * j;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) u[e] = e < left ? um[8 * j + e] : 0.5f;
+    }
+    template <int C>
+    __device__ __forceinline__ void colour(float (&u)[C]) const {
+#pragma unroll
+        for (int c = 0; c < C; ++c) u[c] = ux[c];
+    }
+};
+
+// Addressed uniforms (DESIGN.md section 20 is the contract).  Row n of a launch is draw first_draw + n / B of sequence
+// first_seq + n % B (draw-major, as csrc/keyed_normal.hip).  Block j of pixel p:
+//   Philox4x64-10(key = (seed, (step << 32) | slot), counter = (j, p, seq, draw)),  slot 16 mixture, 17 colour
+//   (keyed_normal owns slots 0..7: another key, so no address is shared with it).
+// Uniform e (e = m for the mixture, e = c for the colour) is the 32-bit half e % 8 of block e / 8, the halves in
+// keyed_normal's order (high half of w0, low half of w0, high half of w1, ...):
+//   u = min(max((2 (half >> 9) + 1) 2^-24, 1e-5f), 1 - 1e-5f)
+// The numerator is an odd integer below 2^24: u is exact, never 0 or 1, and no rounded multiply enters.
+constexpr uint32_t kMolSlotMix = 16, kMolSlotColour = 17;
+constexpr float kMolULo = 1e-5f, kMolUHi = 1.0f - 1e-5f;
+
+__device__ __forceinline__ float mol_uniform(uint32_t half) {
+    const float u = (float)(2u * (half >> 9) + 1u) * 0x1p-24f;
+    return fminf(fmaxf(u, kMolULo), kMolUHi);
+}
+
+struct MolKeyedUniforms {
+    uint64_t seed, step_hi, seq, draw, p;
+    __device__ __forceinline__ void block(uint32_t slot, int j, float (&u)[8]) const {
+        const Philox4x64 w = philox4x64_10((uint64_t)j, p, seq, draw, seed, step_hi | (uint64_t)slot);
+        u[0] = mol_uniform((uint32_t)(w.w0 >> 32));
+        u[1] = mol_uniform((uint32_t)w.w0);
+        u[2] = mol_uniform((uint32_t)(w.w1 >> 32));
+        u[3] = mol_uniform((uint32_t)w.w1);
+        u[4] = mol_uniform((uint32_t)(w.w2 >> 32));
+        u[5] = mol_uniform((uint32_t)w.w2);
+        u[6] = mol_uniform((uint32_t)(w.w3 >> 32));
+        u[7] = mol_uniform((uint32_t)w.w3);
+    }
+    __device__ __forceinline__ void mix_block(int j, int M, float (&u)[8]) const { block(kMolSlotMix, j, u); }
+    template <int C>
+    __device__ __forceinline__ void colour(float (&u)[C]) const {
+        float v[8];
+        block(kMolSlotColour, 0, v);
+#pragma unroll
+        for (int c = 0; c < C; ++c) u[c] = v[c];
+    }
+};
+
+// lp: the pixel's first logit (channel stride HW); op: the pixel's first output (channel stride HW)
+template <int C, class Uniforms>
+__device__ __forceinline__ void mol_sample_pixel(const float* __restrict__ lp, float* __restrict__ op, int M, int HW,
+                                                 const Uniforms& src) {
+    constexpr int P = C == 3 ? 3 : 2;
+    float um[8];
+    src.mix_block(0, M, um);
+    int best = 0;
+    float sc = lp[0] - logf(-logf(um[0]));
+    for (int j = 0; 8 * j < M; ++j) {
+        if (j) src.mix_block(j, M, um);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int m = 8 * j + e;
+            if (m >= 1 && m < M) {
+                const float t = lp[(long)m * HW] - logf(-logf(um[e]));
+                if (t > sc) {  // strict: the lowest index wins a tie
+                    sc = t;
+                    best = m;
+                }
+            }
+        }
+    }
+    float ux[C];
+    src.template colour<C>(ux);
+    float xs[C], th[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float* q = lp + ((long)M + ((long)c * P) * M + best) * HW;
+        const float u = ux[c];
+        float v = q[0] + expf(fmaxf(q[(long)M * HW], kMinLogScale)) * (logf(u) - logf(1.0f - u));
+        if (C == 3) th[c] = tanhf(q[2L * M * HW]);
+        if (C == 3 && c == 1) v += th[0] * xs[0];
+        if (C == 3 && c == 2) v += th[1] * xs[0] + th[2] * xs[1];
+        xs[c] = fminf(fmaxf(v, -1.0f), 1.0f);
+        op[(long)c * HW] = xs[c];
+    }
+}
+
+// u_mix [N,HW,M], u_x [N,HW,C], out [N,C,HW]
 template <int C>
 __global__ __launch_bounds__(256) void mol_sample_kernel(const float* __restrict__ l, const float* __restrict__ u_mix,
                                                          const float* __restrict__ u_x, float* __restrict__ out, int M,
@@ -206,29 +306,54 @@ __global__ __launch_bounds__(256) void mol_sample_kernel(const float* __restrict
     const int p = bx * 256 + threadIdx.x;
     if (p >= HW) return;
     const long Cl = (long)M * (1 + P * C);
-    const float* lp = l + (long)n * Cl * HW + p;
-    const float* um = u_mix + ((long)n * HW + p) * M;
-    int best = 0;
-    float sc = lp[0] - logf(-logf(um[0]));
-    for (int m = 1; m < M; ++m) {
-        const float t = lp[(long)m * HW] - logf(-logf(um[m]));
-        if (t > sc) {  // strict: the lowest index wins a tie
-            sc = t;
-            best = m;
-        }
-    }
-    float xs[C], th[C];
+    const MolGivenUniforms src{u_mix + ((long)n * HW + p) * M, u_x + ((long)n * HW + p) * C};
+    mol_sample_pixel<C>(l + (long)n * Cl * HW + p, out + (long)n * C * HW + p, M, HW, src);
+}
+
+struct MolKeyedParams {
+    int rows, B, M, HW, nbx;
+    uint64_t seed, step_hi, first_seq, first_draw;
+};
+
+__device__ __forceinline__ MolKeyedUniforms mol_keyed_source(const MolKeyedParams& k, int n, int p) {
+    return MolKeyedUniforms{k.seed, k.step_hi, k.first_seq + (uint64_t)(n % k.B), k.first_draw + (uint64_t)(n / k.B),
+                            (uint64_t)p};
+}
+
+// the grid and thread layout of mol_sample_kernel; l [rows,Cl,HW], out [rows,C,HW]
+template <int C>
+__global__ __launch_bounds__(256) void mol_sample_keyed_kernel(const float* __restrict__ l, float* __restrict__ out,
+                                                               const MolKeyedParams k) {
+    constexpr int P = C == 3 ? 3 : 2;
+    const int n = blockIdx.x / k.nbx, bx = blockIdx.x % k.nbx;
+    const int p = bx * 256 + threadIdx.x;
+    if (p >= k.HW) return;
+    const long Cl = (long)k.M * (1 + P * C);
+    const MolKeyedUniforms src = mol_keyed_source(k, n, p);
+    mol_sample_pixel<C>(l + (long)n * Cl * k.HW + p, out + (long)n * C * k.HW + p, k.M, k.HW, src);
+}
+
+// the uniforms mol_sample_keyed_kernel uses, as tensors: u_mix [rows,HW,M], u_x [rows,HW,C]
+template <int C>
+__global__ __launch_bounds__(256) void mol_keyed_uniforms_kernel(float* __restrict__ u_mix, float* __restrict__ u_x,
+                                                                 const MolKeyedParams k) {
+    const int n = blockIdx.x / k.nbx, bx = blockIdx.x % k.nbx;
+    const int p = bx * 256 + threadIdx.x;
+    if (p >= k.HW) return;
+    const MolKeyedUniforms src = mol_keyed_source(k, n, p);
+    float* um = u_mix + ((long)n * k.HW + p) * k.M;
+    float u[8];
+    for (int j = 0; 8 * j < k.M; ++j) {
+        src.mix_block(j, k.M, u);
+        const int left = k.M - 8 * j;
 #pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float* q = lp + ((long)M + ((long)c * P) * M + best) * HW;
-        const float u = u_x[((long)n * HW + p) * C + c];
-        float v = q[0] + expf(fmaxf(q[(long)M * HW], kMinLogScale)) * (logf(u) - logf(1.0f - u));
-        if (C == 3) th[c] = tanhf(q[2L * M * HW]);
-        if (C == 3 && c == 1) v += th[0] * xs[0];
-        if (C == 3 && c == 2) v += th[1] * xs[0] + th[2] * xs[1];
-        xs[c] = fminf(fmaxf(v, -1.0f), 1.0f);
-        out[((long)n * C + c) * HW + p] = xs[c];
+        for (int e = 0; e < 8; ++e)
+            if (e < left) um[8 * j + e] = u[e];
     }
+    float ux[C];
+    src.template colour<C>(ux);
+#pragma unroll
+    for (int c = 0; c < C; ++c) u_x[((long)n * k.HW + p) * C + c] = ux[c];
 }
 
 bool mol_grid(int N, int HW, int* nbx, long* blocks) {
@@ -293,6 +418,48 @@ extern "C" int rfn_mol_sample(const float* l, const float* u_mix, const float* u
         hipLaunchKernelGGL(mol_sample_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, st, l, u_mix, u_x, out, M, HW, nbx);
     else
         hipLaunchKernelGGL(mol_sample_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, l, u_mix, u_x, out, M, HW, nbx);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+static int mol_keyed_params(int rows, int B, int C, int M, int HW, long seed, int step, long first_seq, long first_draw,
+                            MolKeyedParams* k, long* blocks) {
+    RFN_CHECK_ARG(rows > 0 && B >= 1 && rows % B == 0, -2);
+    RFN_CHECK_ARG((C == 1 || C == 3) && M > 0 && HW > 0, -2);
+    RFN_CHECK_ARG(seed >= 0 && first_seq >= 0 && first_draw >= 0 && step >= 0, -4);
+    int nbx;
+    RFN_CHECK_ARG(mol_grid(rows, HW, &nbx, blocks), -3);
+    *k = MolKeyedParams{rows, B, M, HW, nbx, (uint64_t)seed, (uint64_t)(uint32_t)step << 32, (uint64_t)first_seq,
+                        (uint64_t)first_draw};
+    return 0;
+}
+
+extern "C" int rfn_mol_sample_keyed(const float* l, float* out, int rows, int B, int C, int M, int HW, long seed, int step,
+                                    long first_seq, long first_draw, rfn_stream_t stream) {
+    RFN_CHECK_ARG(l && out, -1);
+    MolKeyedParams k;
+    long blocks;
+    if (int rc = mol_keyed_params(rows, B, C, M, HW, seed, step, first_seq, first_draw, &k, &blocks)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 3)
+        hipLaunchKernelGGL(mol_sample_keyed_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, st, l, out, k);
+    else
+        hipLaunchKernelGGL(mol_sample_keyed_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, l, out, k);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rfn_mol_keyed_uniforms(float* u_mix, float* u_x, int rows, int B, int C, int M, int HW, long seed, int step,
+                                      long first_seq, long first_draw, rfn_stream_t stream) {
+    RFN_CHECK_ARG(u_mix && u_x, -1);
+    MolKeyedParams k;
+    long blocks;
+    if (int rc = mol_keyed_params(rows, B, C, M, HW, seed, step, first_seq, first_draw, &k, &blocks)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 3)
+        hipLaunchKernelGGL(mol_keyed_uniforms_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, st, u_mix, u_x, k);
+    else
+        hipLaunchKernelGGL(mol_keyed_uniforms_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, u_mix, u_x, k);
     RFN_LAUNCH_CHECK();
     return 0;
 }

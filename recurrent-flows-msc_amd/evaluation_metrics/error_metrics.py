@@ -82,6 +82,18 @@ class _BestOfN(object):
                 cat(self.mean_values, "ssim"), cat(self.mean_values, "psnr"), cat(self.mean_values, "lpips") if lp else None)
 
 
+MODEL_NAMES = ("rfn.pt", "srnn.pt")   # the checkpoints this package can evaluate
+
+
+def check_model_name(model_name):
+    """the reference's Evaluator branches on the checkpoint's name: "rfn.pt" takes its RFN branches, "srnn.pt" the other
+    ones; its remaining baselines (svg.pt, vrnn.pt) are not part of this package"""
+    if model_name not in MODEL_NAMES:
+        raise ValueError("Evaluator: cannot evaluate %r: of the baseline models (svg.pt, vrnn.pt, srnn.pt) only srnn.pt "
+                         "is part of this package, beside rfn.pt" % (model_name,))
+    return model_name == "rfn.pt"
+
+
 class Evaluator(object):
     def __init__(self, solver, args=None, settings=None):
         self.solver = solver
@@ -104,6 +116,8 @@ class Evaluator(object):
         # RFN.predict call per draw, noise from torch's generator
         self.draws_per_pass = getattr(settings, "draws_per_pass", None)
         self.seed = int(getattr(settings, "seed", None) or 0)
+        # the inner samples of SRNN.elbo_importance_weighting in get_loss("srnn.pt") (the reference's constant: 20)
+        self.iw_samples = int(getattr(settings, "iw_samples", None) or 20)
         self.num_samples_to_plot = int(getattr(settings, "num_samples_to_plot", None) or 5)
         # optional: a directory or a list of files holding the LPIPS-alex weights (rfn_hip.ops.lpips_alex_load); loaded
         # on first use
@@ -122,9 +136,10 @@ class Evaluator(object):
 
     def get_loss(self, model_name="rfn.pt", loss_resamples=1, loader=None, max_batches=None):
         """error_metrics.py:370-417: mean (and, with resampling, standard deviation) of the per-batch bits/dim over the
-        test set, model in eval mode.  Only the RFN branch exists here (the reference's other branch is the
-        importance-weighted bound of its VRNN / SRNN baselines)."""
-        assert model_name == "rfn.pt", "only the RFN loss is on the hot path"
+        test set, model in eval mode.  "rfn.pt": RFN.loss through compute_loss.  "srnn.pt" (the reference's other
+        branch, :396-399): the importance-weighted bound SRNN.elbo_importance_weighting(imageloss, K) / (ln 2 * prod(dims)
+        * t) with K = settings.iw_samples (default 20, the reference's constant)."""
+        rfn = check_model_name(model_name)
         loader = loader if loader is not None else self.test_loader
         with torch.no_grad():
             self.model.eval()
@@ -137,8 +152,13 @@ class Evaluator(object):
                     image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
                     image = self.solver.preprocess(image.to(self.device))
                     imageloss = image[:, :self.n_trained] if self.n_trained else image
-                    _, kl, nll = self.model.loss(imageloss, 0)
-                    b, _, _ = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:], t=imageloss.shape[1] - 1)
+                    if rfn:
+                        _, kl, nll = self.model.loss(imageloss, 0)
+                        b, _, _ = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:], t=imageloss.shape[1] - 1)
+                    else:
+                        loss = self.model.elbo_importance_weighting(imageloss, self.iw_samples)
+                        b = float(loss / (np.log(2.) * torch.prod(torch.tensor(imageloss.shape[2:])) *
+                                          (imageloss.shape[1] - 1)))
                     bpd.append(b)
                 means.append(torch.FloatTensor(bpd))
             means = torch.stack(means)
@@ -225,8 +245,10 @@ class Evaluator(object):
         they are computed in the first pass only.  n_predicts defaults to n_frames - start_predictions and must be at
         least 9; fewer than 16 sequences is a ValueError.  Needs settings.fvd_weights."""
         from rfn_hip import ops
-        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        rfn = check_model_name(model_name)
         w = self._i3d_loaded()
+        # (srnn.pt: the frames stay where they were computed; the embeddings are computed there)
+        predict = self.model.predict if rfn else self.model._predict_device
         loader = loader if loader is not None else self.test_loader
         start = self.start_predictions
         n_predicts = int(n_predicts) if n_predicts is not None else self.n_frames - start
@@ -245,10 +267,10 @@ class Evaluator(object):
                     if cur_bs < batch_size:
                         pad = torch.zeros((batch_size - cur_bs,) + tuple(image.shape[1:]), device=image.device,
                                           dtype=image.dtype)
-                        _, predictions = self.model.predict(torch.cat((image, pad), 0), n_predicts, start)
+                        _, predictions = predict(torch.cat((image, pad), 0), n_predicts, start)
                         predictions = predictions[:, :cur_bs]
                     else:
-                        _, predictions = self.model.predict(image, n_predicts, start)
+                        _, predictions = predict(image, n_predicts, start)
                     pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 0, 2, 3, 4).to(self.device)
                     preds.append(ops.i3d_embed(w, self._as_u8(pred_u8, "pred")))
                     if gt_emb is None:
@@ -306,10 +328,13 @@ class Evaluator(object):
         them in place, so the "mean over draws" averages the final best values in place of draw 0.
 
         With settings.draws_per_pass = P the draws of a batch are generated P at a time with addressed noise
-        (settings.seed) and the figures are reproducible: see _get_eval_values_draws."""
-        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        (settings.seed) and the figures are reproducible: see _get_eval_values_draws.
+
+        "srnn.pt" takes the reference's other branch (:478-483): `kl, nll = model.loss(image)` on the WHOLE sequence,
+        with the dims and t of `image`; everything else is the same code."""
+        rfn = check_model_name(model_name)
         if self.draws_per_pass is not None:
-            return self._get_eval_values_draws(loader, max_batches)
+            return self._get_eval_values_draws(loader, max_batches, rfn)
         if (self.extra_plots or self.debug_plot) and not self._warned_plots:
             warnings.warn("Evaluator.get_eval_values: extra_plots / debug_plot only draw figures; skipped")
             self._warned_plots = True
@@ -334,9 +359,7 @@ class Evaluator(object):
                 gt_feats = None
                 for r in range(self.resample):
                     _, predictions = self.model.predict(image, n_frames - start, start)
-                    _, kl, nll = self.model.loss(imageloss, 0)
-                    bpd, kl_loss, recon_loss = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:],
-                                                                 t=imageloss.shape[1] - 1)
+                    bpd, kl_loss, recon_loss = self._batch_loss(imageloss if rfn else image, rfn)
                     pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 0, 2, 3, 4)
                     pred_u8 = pred_u8.to(self.device)
                     gt_u8 = image_u8[:, start:start + pred_u8.shape[1]]
@@ -380,9 +403,9 @@ class Evaluator(object):
                 torch.cat(ssim_std_values), torch.cat(psnr_std_values),
                 torch.cat(lpips_std_values) if lpips_w is not None else None)
 
-    def _get_eval_values_draws(self, loader=None, max_batches=None):
+    def _get_eval_values_draws(self, loader=None, max_batches=None, rfn=True):
         """get_eval_values with settings.draws_per_pass = P: per batch ceil(resample / P) calls of
-        RFN._predict_draws_device, each generating P draws of the B sequences as P*B rows of one batch (the extractor
+        RFN._predict_draws_device (SRNN._predict_draws_device for srnn.pt), each generating P draws of the B sequences as P*B rows of one batch (the extractor
         and the ConvLSTM over the conditioning frames run once per call, every generated frame is one hipGraph replay
         for all P*B rows).  The noise is addressed (rfn_hip.ops.keyed_normal): draw r of sequence batch_i * B + b under
         settings.seed is the same numbers whatever P, the batch size or anything drawn before, so the result for a
@@ -435,7 +458,7 @@ class Evaluator(object):
                     host, gt_feats = self._score_pass(gt_u8, pred_u8, names, lpips_w, gt_feats)
                     for d in range(min(P, R - ps * P)):
                         book.add(host[:, d], pred_u8[d])
-                bpd, kl_loss, recon_loss = self._batch_loss(imageloss)
+                bpd, kl_loss, recon_loss = self._batch_loss(imageloss if rfn else image, rfn)
                 book.end_batch()
                 bpd_list.append(bpd)
                 dkl_list.append(kl_loss)
@@ -473,9 +496,13 @@ class Evaluator(object):
             scores["lpips"] = ops.lpips_alex_distance(lpips_w, ops.lpips_alex_features(lpips_w, pred_u8), gt_feats)
         return torch.stack([scores[k] for k in names]).cpu(), gt_feats   # the pass's one copy
 
-    def _batch_loss(self, imageloss):
-        """(bits/dim, kl / t, nll / t) of one model.loss evaluation of a batch"""
-        _, kl, nll = self.model.loss(imageloss, 0)
+    def _batch_loss(self, imageloss, rfn=True):
+        """(bits/dim, kl / t, nll / t) of one model.loss evaluation of a batch: RFN.loss(x, logdet) -> (kl with free
+        bits, kl, nll), SRNN.loss(x) -> (kl, nll)"""
+        if rfn:
+            _, kl, nll = self.model.loss(imageloss, 0)
+        else:
+            kl, nll = self.model.loss(imageloss)
         return self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:], t=imageloss.shape[1] - 1)
 
     def get_eval_values_temperatures(self, temperatures, model_name="rfn.pt", loader=None, max_batches=None):
@@ -493,8 +520,11 @@ class Evaluator(object):
         code): ascending draw id, strict comparisons of time-means, the draw-0 aliasing, draws >= resample of a padded
         last pass ignored.  model.loss runs once per batch: BPD / DKL / RECON do not depend on the sampling temperature
         and the K tuples share them.  self.best_preds_ssim becomes a dict {T: uint8 tensor on the device} in this call
-        only.  The debug_plot sheets are not written here (they would overwrite one another per temperature)."""
-        assert model_name == "rfn.pt", "only the RFN evaluation is on the hot path"
+        only.  The debug_plot sheets are not written here (they would overwrite one another per temperature).
+        RFN only: SRNN has no sampling temperature, "srnn.pt" is a ValueError."""
+        if not check_model_name(model_name):
+            raise ValueError("Evaluator.get_eval_values_temperatures: %s has no sampling temperature; the temperature "
+                             "study is for rfn.pt" % model_name)
         temps = [float(t) for t in temperatures]
         if not temps or len(set(temps)) != len(temps):
             raise ValueError("Evaluator.get_eval_values_temperatures: need at least one temperature and no duplicates, "

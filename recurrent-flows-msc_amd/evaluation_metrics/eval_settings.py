@@ -20,8 +20,12 @@ evaluations with the Evaluator (error_metrics.py):
                                generation); without it, one get_eval_values pass per temperature as in the reference.
 
 Flags, defaults and meanings are the reference's; --draws_per_pass, --seed, --lpips_weights, --fvd_weights and
---max_batches are ours.  Deviations: only rfn.pt can be evaluated (the SVG / VRNN / SRNN baselines are not part of this
-package: any other model name is a ValueError); LPIPS entries are None when --lpips_weights is not given (the reference
+--max_batches are ours.  `--model_path srnn.pt` evaluates the SRNN baseline through the reference's
+non-RFN branches: get_eval_values with SRNN.loss on the whole sequence, get_loss as the
+importance-weighted bound (settings.iw_samples inner samples when a caller sets it on the settings object; the parser
+has no flag for it and the default is the reference's 20), get_fvd_values; the RFN-only sheets and analyses are skipped
+with one printed line, and --test_temperature is refused (SRNN has no temperature).  Deviations: the SVG / VRNN
+baselines are not part of this package (any other model name is a ValueError); LPIPS entries are None when --lpips_weights is not given (the reference
 would need the lpips package's download); --debug_mnist / --use_validation_set evaluate the FIRST 1000 test sequences
 (the reference: a random 1000 for --debug_mnist); the curve figures plot_eval_values / test_temp_values and the figure of
 param_plots are not drawn -- one line says so when they would have run -- and --eval_parameters saves the tensors of
@@ -52,12 +56,18 @@ def temperature_file_name(temperature):
     return "t" + str(temperature).replace(".", "") + "evaluations.pt"
 
 
+RFN_ONLY_SHEETS = ("plot_long_t", "plot_diversity", "plot_random_samples", "plot_temp", "param_analysis", "extra_plots")
+
+
 def solver_class(model_name):
-    """eval_settings.py:18-27: the Solver for a checkpoint name; only the RFN is part of this package"""
-    if model_name != "rfn.pt":
-        raise ValueError("eval_settings: cannot evaluate %r: the baseline models (svg.pt, vrnn.pt, srnn.pt) are not "
-                         "part of this package, only rfn.pt is" % (model_name,))
-    from RFN.trainer import Solver
+    """eval_settings.py:18-27: the Solver for a checkpoint name; the RFN and the SRNN baseline are part of this package"""
+    if model_name == "rfn.pt":
+        from RFN.trainer import Solver
+    elif model_name == "srnn.pt":
+        from SRNN.trainer import Solver
+    else:
+        raise ValueError("eval_settings: cannot evaluate %r: of the baseline models (svg.pt, vrnn.pt, srnn.pt) only "
+                         "srnn.pt is part of this package, beside rfn.pt" % (model_name,))
     return Solver
 
 
@@ -121,14 +131,23 @@ def main(settings):
     if not settings.test_temperature and len(settings.temperatures) < len(experiments):
         raise ValueError("eval_settings: %d experiments but %d --temperatures" %
                          (len(experiments), len(settings.temperatures)))
+    for name in settings.model_path[:len(experiments)]:   # before any file is read
+        solver_class(name)
+        if settings.test_temperature and name != "rfn.pt":
+            raise ValueError("eval_settings: --test_temperature with %s: only rfn.pt has a sampling temperature" % name)
     for i in range(len(experiments)):
         model_name = settings.model_path[i]
+        rfn = model_name == "rfn.pt"
         evaluator, args, folder, max_batches = build_evaluator(settings, i)
         if not settings.test_temperature:
             T = settings.temperatures[i]
             evaluator.model.temperature = T
             evaluator.model.kl_temperature = 1
-            if settings.eval_parameters:
+            if not rfn:
+                print("eval_settings: %s: the RFN-only figures and analyses are skipped (%s)" %
+                      (model_name, ", ".join(RFN_ONLY_SHEETS)))
+                evaluator.extra_plots = False
+            if settings.eval_parameters and rfn:
                 image = next(iter(evaluator.test_loader))
                 image = image[0] if args.choose_data == "bair" and isinstance(image, (list, tuple)) else image
                 out = evaluator.param_analysis(image, settings.n_frames - settings.n_conditions, settings.n_conditions)
@@ -140,13 +159,16 @@ def main(settings):
                 print("Done - FVD")
             else:
                 fvd_mean, fvd_std = -1, -1
-            evaluator.plot_long_t(model_name)
-            evaluator.plot_diversity(model_name)
-            evaluator.plot_random_samples(model_name)
-            evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=False)
-            evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=True, duplicate_samples=False)
-            evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=False, duplicate_samples=True, t_list=[0] * 8)
-            evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=True, duplicate_samples=True, t_list=[0] * 8)
+            if rfn:
+                evaluator.plot_long_t(model_name)
+                evaluator.plot_diversity(model_name)
+                evaluator.plot_random_samples(model_name)
+                evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=False)
+                evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=True, duplicate_samples=False)
+                evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=False, duplicate_samples=True,
+                                    t_list=[0] * 8)
+                evaluator.plot_temp(model_name, orig_temps=[T, 1], kl_analysis=True, duplicate_samples=True,
+                                    t_list=[0] * 8)
             if settings.eval_loss:
                 bits_mean, bits_std = evaluator.get_loss(model_name, loss_resamples=2, max_batches=max_batches)
             else:

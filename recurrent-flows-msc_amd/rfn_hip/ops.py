@@ -1969,6 +1969,91 @@ def mol_sample(l, u_mix=None, u_x=None, generator=None, channels=None):
     return out
 
 
+MOL_KEYED_SLOT_MIX, MOL_KEYED_SLOT_COLOUR = 16, 17   # the key's slot word (keyed_normal owns 0 .. 7)
+
+
+def _mol_channels(who, Cl, channels):
+    """(C, M) of Cl logit channels: C is `channels`, else what Cl allows (10 M: RGB, 3 M: gray)"""
+    C = channels
+    if C is None:
+        fits = [c for c, per in ((3, 10), (1, 3)) if Cl >= per and Cl % per == 0]
+        if len(fits) != 1:
+            raise RuntimeError("%s: %d logit channels %s; pass channels=1 or 3" %
+                               (who, Cl, "fit both RGB and gray" if fits else "fit neither 10*M nor 3*M"))
+        C = fits[0]
+    per = 10 if C == 3 else 3
+    if C not in (1, 3) or Cl < per or Cl % per:
+        raise RuntimeError("%s: %d logit channels do not fit %d colour channels (need %d*M)" % (who, Cl, C, per))
+    return C, Cl // per
+
+
+def _mol_keyed_address(who, rows, B, seed, step, first_seq, first_draw):
+    B, seed, step, first_seq, first_draw = (int(v) for v in (B, seed, step, first_seq, first_draw))
+    if B < 1 or rows < 1 or rows % B:
+        raise ValueError("%s: %d rows are no positive multiple of B = %d (row r*B + b is draw first_draw + r of sequence "
+                         "first_seq + b)" % (who, rows, B))
+    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
+        if not 0 <= v < 1 << 63:
+            raise ValueError("%s: %s %d not in [0, 2^63)" % (who, nm, v))
+    if not 0 <= step < 1 << 31:
+        raise ValueError("%s: step %d not in [0, 2^31)" % (who, step))
+    return B, seed, step, first_seq, first_draw
+
+
+def mol_sample_keyed(l, B, seed, step, first_seq=0, first_draw=0, channels=None):
+    """mol_sample with addressed uniforms (rfn_mol_sample_keyed; include/rfn_hip.h and DESIGN section 20 hold the
+    definition): x [rows,C,H,W] from the mixture l [rows,Cl,H,W], rows a multiple of B.  Row r*B + b is draw first_draw +
+    r of sequence first_seq + b, and a pixel's uniforms depend only on (seed, step, sequence, draw, pixel, element): the
+    same for any B, number of draws and split of the draws into calls.  No uniform tensor exists and torch's generator
+    is not touched; mol_keyed_uniforms writes the numbers out.  One launch on the current stream; no CPU fallback."""
+    if l.dim() != 4:
+        raise RuntimeError("mol_sample_keyed: l must be [rows,Cl,H,W], got %s" % (tuple(l.shape),))
+    rows, Cl, H, W = (int(d) for d in l.shape)
+    C, M = _mol_channels("mol_sample_keyed", Cl, channels)
+    B, seed, step, first_seq, first_draw = _mol_keyed_address("mol_sample_keyed", rows, B, seed, step, first_seq,
+                                                              first_draw)
+    l = l.detach().contiguous()
+    L.dev(l, "l")
+    out = torch.empty((rows, C, H, W), device=l.device, dtype=torch.float32)
+    with torch.cuda.device(l.device):
+        L.call("rfn_mol_sample_keyed", L.dev(l), L.dev(out), rows, B, C, M, H * W, seed, step, first_seq, first_draw,
+               meta=_shell("mol_sample_keyed", l, 1))
+    return out
+
+
+def mol_keyed_uniforms(shape_or_l, B, M, channels, seed, step, first_seq=0, first_draw=0, device=None):
+    """(u_mix [rows,H,W,M], u_x [rows,H,W,C]): the uniforms mol_sample_keyed uses at that address
+    (rfn_mol_keyed_uniforms), so that mol_sample(l, u_mix, u_x) replays it bit for bit.  shape_or_l: the logits (their
+    rows, H, W and device are taken) or (rows, H, W); device: where the tensors go for a shape (default: the current
+    GPU)."""
+    if isinstance(shape_or_l, torch.Tensor):
+        if shape_or_l.dim() != 4:
+            raise RuntimeError("mol_keyed_uniforms: l must be [rows,Cl,H,W], got %s" % (tuple(shape_or_l.shape),))
+        rows, _, H, W = (int(d) for d in shape_or_l.shape)
+        device = shape_or_l.device
+    else:
+        if len(shape_or_l) != 3:
+            raise ValueError("mol_keyed_uniforms: give the logits or (rows, H, W), got %s" % (tuple(shape_or_l),))
+        rows, H, W = (int(d) for d in shape_or_l)
+    M, C = int(M), int(channels)
+    if M < 1 or C not in (1, 3) or H < 1 or W < 1:
+        raise ValueError("mol_keyed_uniforms: need M >= 1, channels 1 or 3 and a non-empty frame (got M = %d, channels = "
+                         "%d, %dx%d)" % (M, C, H, W))
+    B, seed, step, first_seq, first_draw = _mol_keyed_address("mol_keyed_uniforms", rows, B, seed, step, first_seq,
+                                                              first_draw)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("rfn_hip kernels need device tensors; mol_keyed_uniforms was asked for %s (no CPU fallback)" %
+                           device)
+    u_mix = torch.empty((rows, H, W, M), device=device, dtype=torch.float32)
+    u_x = torch.empty((rows, H, W, C), device=device, dtype=torch.float32)
+    with torch.cuda.device(device):
+        L.call("rfn_mol_keyed_uniforms", L.dev(u_mix), L.dev(u_x), rows, B, C, M, H * W, seed, step, first_seq,
+               first_draw, meta=("shell", "mol_keyed_uniforms", 0.0, "%dx%dx%d" % (rows, H * W, M + C),
+                                 4.0 * (u_mix.numel() + u_x.numel())))
+    return u_mix, u_x
+
+
 # ----------------------------------------------------------------------------------------------- evaluation metrics
 def _u8_frames(t, C, H, W):
     """(tensor, pointer, frame stride) of a uint8 device tensor [..., C, H, W] seen as [N, C, H, W] frames (lib.dev stays
