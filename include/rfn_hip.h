@@ -509,6 +509,41 @@ int rfn_stepbn_apply_f32(const float* x, const float* gamma, const float* beta, 
  * pointers it will pass: bit 0 = every pointer the stats (x) or, with bwd, the reduce kernel (x, g) tests is 16-byte
  * aligned; bit 1 = the same for the apply kernel (x, y; with bwd x, g, gx). */
 const char* rfn_stepbn_kernel_label(int S, int B, int C, int HW, int aligned, int bwd);
+/* Per-step BatchNorm + activation + MaxPool2d(2, 2) (the extractor's conv -> norm -> act -> pool): x [S*B, C, H, W] with
+ * even H and W (odd: argument error), p / gp [S*B, C, H/2, W/2].  Forward: the statistics launch of rfn_stepbn_fwd_f32,
+ * then ONE apply launch that reads x and writes only p; mean / var / running statistics / num_batches_tracked as there.
+ * A window's winner follows max_pool2d: the ACTIVATED values in the order (0,0), (0,1), (1,0), (1,1), a candidate
+ * replacing the best when it is larger or NaN; p is bit-equal to rfn_stepbn_fwd_f32 followed by max_pool2d.
+ * Backward from the POOLED gradient: the reduce kernel recomputes every winner from x and sums g' = gp act'(u_winner)
+ * and g' xhat_winner into the same [ny][S*C] partial rows (scratch of rfn_stepbn_scratch_floats, no atomics, nothing to
+ * zero); the apply kernel writes gx = gamma rstd (g' [winner] - k1 - xhat k2) at all four positions of a window and the
+ * parameter gradients.  stage / world as rfn_stepbn_bwd_f32.  No index map and no full-resolution gradient exist. */
+int rfn_stepbn_pool_fwd_f32(const float* x, const float* gamma, const float* beta, float* p, float* mean, float* var,
+                            float* acc, float* run_mean, float* run_var, const float* coef, const float* coef_u,
+                            float decay, long long* num_batches_tracked, int S, int B, int C, int H, int W, float eps,
+                            int act, float slope, rfn_stream_t stream);
+int rfn_stepbn_pool_bwd_f32(const float* x, const float* gamma, const float* beta, const float* gp, const float* mean,
+                            const float* var, float* sums, float* gx, float* ggamma, float* gbeta, int S, int B, int C,
+                            int H, int W, float eps, int act, float slope, int stage, int world, rfn_stream_t stream);
+/* Host-only label query: "stepbn_pool ny=.. stats=vec|scalar apply=vec4|vec1 grid=.. sweeps=..".  `aligned` as for
+ * rfn_stepbn_kernel_label: bit 0 = x (the statistics kernel) or, with bwd, x and gp (the reduce kernel) are 16-byte
+ * aligned; bit 1 = the same for the apply kernel (x, p; with bwd x, gp, gx).  The pooled kernels take 16-byte accesses
+ * when W % 4 == 0 as well (a unit = two rows x four columns = two windows), else one window per thread with scalar
+ * accesses; the statistics kernel is the unpooled one (H*W % 4 == 0 always holds here).  "unsupported": odd H or W, a
+ * size < 1, or 2^31 elements and more. */
+const char* rfn_stepbn_pool_kernel_label(int S, int B, int C, int H, int W, int aligned, int bwd);
+
+/* ---- nearest 2x up-sampling + channel concatenation (the upscaler's NearestUp2x -> cat((x, skip), 1)), one launch each
+ * way.  x [N, Cx, h, w] and skip [N, Cs, 2h, 2w] with frame strides x_ns / skip_ns (floats; the per-frame block dense),
+ * out [N, Cx+Cs, 2h, 2w] dense.  Backward: gx [N, Cx, h, w] = the 2x2 block sums of the first Cx channels of
+ * g [N, *, 2h, 2w], read in place through its frame stride g_ns (each sum formed in fp64 and rounded once); the skip's
+ * gradient is the view g[:, Cx:].  16-byte accesses when w is even, every pointer 16-byte aligned and every frame stride
+ * a multiple of 4; else one element per thread.  Label: "up2x_cat[_bwd] access=vec4|vec1 grid=.. sweeps=..", `aligned`
+ * = that condition on pointers and strides. */
+int rfn_up2x_cat_f32(const float* x, long x_ns, const float* skip, long skip_ns, float* out, int N, int Cx, int Cs, int h,
+                     int w, rfn_stream_t stream);
+int rfn_up2x_cat_bwd_f32(const float* g, long g_ns, float* gx, int N, int Cx, int h, int w, rfn_stream_t stream);
+const char* rfn_up2x_cat_kernel_label(int N, int Cx, int Cs, int h, int w, int aligned, int bwd);
 
 /* ---- BatchNormFlow (Flow/glow_modules.py:56-104), the flow normalisation of --flow_norm batchnorm, on a step-major
  * time-batched tensor x [S*B, E] with E = C*H*W: log_gamma, beta, run_mean, run_var are [E] (one value per channel AND

@@ -113,9 +113,28 @@ def _ema_coef(steps, m, n, device):
     return _EMA_COEF[key]
 
 
-def per_step_batchnorm_act(bn, x, steps, act_code, slope):
+def _pool2x2(m):
+    """m is the pool the fused BatchNorm + activation + max-pool kernels implement: MaxPool2d(2, 2), nothing else set"""
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    return (type(m) is nn.MaxPool2d and pair(m.kernel_size) == (2, 2) and pair(m.stride) == (2, 2)
+            and pair(m.padding) == (0, 0) and pair(m.dilation) == (1, 1) and not m.ceil_mode and not m.return_indices)
+
+
+def _pool_fusable(mods, i, x):
+    """mods[i] (a BatchNorm NormLayer on the fused path) is followed by an activation of the kernels and a 2x2 max-pool,
+    x has even sides and the statistics are this process's own: the three modules run as one pair of launches"""
+    if os.environ.get("RFN_STEPBN_POOL") == "0" or i + 2 >= len(mods) or _act_code(mods[i + 1]) is None:
+        return False
+    if not _pool2x2(mods[i + 2]) or x.shape[2] % 2 or x.shape[3] % 2:
+        return False
+    from rfn_hip import dist as rdist
+    return not rdist.sync_batchnorm_on()
+
+
+def per_step_batchnorm_act(bn, x, steps, act_code, slope, pool=False):
     """per_step_batchnorm fused with the following activation on the HIP kernels (rfn_stepbn_*): no permute copies, one
-    statistics pass and one normalise+activate pass forward, one reduction and one apply pass backward."""
+    statistics pass and one normalise+activate pass forward, one reduction and one apply pass backward.  pool: the
+    MaxPool2d(2, 2) that follows the activation too (rfn_stepbn_pool_*): only the pooled map is written."""
     running = None
     if bn.track_running_stats:
         n = (x.shape[0] // steps) * x.shape[2] * x.shape[3]
@@ -124,8 +143,9 @@ def per_step_batchnorm_act(bn, x, steps, act_code, slope):
         # (biased batch variance -> unbiased: the factor is in coef_u)
         coef, coef_u = _ema_coef(steps, m, n, x.device)
         running = (bn.running_mean, bn.running_var, coef, coef_u, (1.0 - m) ** steps, bn.num_batches_tracked)
-    y, _, _ = K.StepBatchNormActFn.apply(x, bn.weight if bn.affine else None, bn.bias if bn.affine else None, steps,
-                                         float(bn.eps), act_code, slope, running)
+    fn = K.StepBatchNormActPoolFn if pool else K.StepBatchNormActFn
+    y, _, _ = fn.apply(x, bn.weight if bn.affine else None, bn.bias if bn.affine else None, steps, float(bn.eps),
+                       act_code, slope, running)
     return y
 
 
@@ -158,8 +178,9 @@ def run_time_batched(seq, x, steps, packs=None):
             fused = x.is_cuda and bn.training and x.dtype == torch.float32 and os.environ.get("RFN_STEPBN") != "0"
             if fused:
                 act = _act_code(mods[i + 1]) if i + 1 < len(mods) else None
-                x = per_step_batchnorm_act(bn, x, steps, act[0] if act else 0, act[1] if act else 0.0)
-                i += 2 if act else 1
+                pool = _pool_fusable(mods, i, x)
+                x = per_step_batchnorm_act(bn, x, steps, act[0] if act else 0, act[1] if act else 0.0, pool)
+                i += 3 if pool else 2 if act else 1
                 continue
             x = per_step_batchnorm(bn, x, steps)
         elif _own_conv(m, x):
@@ -218,6 +239,15 @@ class NearestUp2x(nn.Upsample):
 
     def forward(self, x):
         return _NearestUp2xFn.apply(x)
+
+
+def _up2x_only(seq, x, skip):
+    """the up-sampling stage `seq` is exactly [NearestUp2x()] and (x, skip) can go through rfn_hip.ops.Up2xCatFn
+    (RFN_UP2X_CAT=0: the separate up-sampling and torch.cat, for A/B runs)"""
+    return (len(seq) == 1 and type(seq[0]) is NearestUp2x and x.is_cuda and skip.is_cuda and x.dtype == torch.float32
+            and skip.dtype == torch.float32 and x.dim() == 4 and skip.dim() == 4 and skip.shape[1] > 0
+            and tuple(skip.shape[2:]) == (2 * x.shape[2], 2 * x.shape[3]) and skip.shape[0] == x.shape[0]
+            and os.environ.get("RFN_UP2X_CAT") != "0")
 
 
 class tanh0_5(nn.Module):
@@ -361,10 +391,13 @@ class VGG_upscaler(nn.Module):
         rev = list(reversed(skip_list)) if self.skips else None
         packs = queue_conv_packs(list(self.upscales_nets) + list(self.l_nets), x)
         for i in range(self.L):
-            if i > 0:
-                x = run_time_batched(self.upscales_nets[i - 1], x, steps, packs)
-            if self.skips:
-                x = torch.cat((x, rev[i]), dim=1)
+            if i > 0 and self.skips and _up2x_only(self.upscales_nets[i - 1], x, rev[i]):
+                x = K.Up2xCatFn.apply(x, rev[i])      # up-sampling and concatenation in one launch each way
+            else:
+                if i > 0:
+                    x = run_time_batched(self.upscales_nets[i - 1], x, steps, packs)
+                if self.skips:
+                    x = torch.cat((x, rev[i]), dim=1)
             x = run_time_batched(self.l_nets[i], x, steps, packs)
             outputs.append(x)
         outputs.reverse()

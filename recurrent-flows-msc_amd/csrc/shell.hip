@@ -1768,6 +1768,32 @@ __device__ __forceinline__ void stepbn_moments(const float* __restrict__ x, cons
     const float vv = s2 / n - m1 * m1;
     v = vv > 0.f ? vv : 0.f;
 }
+// the extra first workgroup of a forward apply kernel (pooled or not)
+__device__ __forceinline__ void stepbn_finalise(const float* __restrict__ x, int B, int C, int HW, const StepBnFused& f) {
+    const int SC = f.S * C;
+    if (!f.acc) return;   // given statistics: nothing to finalise
+    for (int sc = threadIdx.x; sc < SC; sc += blockDim.x) {
+        float m, v;
+        stepbn_moments(x, f.acc, sc, sc / C, sc % C, B, C, HW, f.ny, SC, m, v);
+        f.mean_out[sc] = m;
+        f.var_out[sc] = v;
+    }
+    if (f.run_mean) {
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {  // loads only inside the loop: they pipeline
+            float em = 0.f, ev = 0.f;
+#pragma unroll 4
+            for (int s = 0; s < f.S; ++s) {
+                float m, v;
+                stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, v);
+                em = fmaf(f.coef[s], m, em);
+                ev = fmaf(f.coef_u[s], v, ev);
+            }
+            f.run_mean[c] = fmaf(f.decay, f.run_mean[c], em);
+            f.run_var[c] = fmaf(f.decay, f.run_var[c], ev);
+        }
+    }
+    if (f.nbt && threadIdx.x == 0) *f.nbt += f.S;
+}
 template <int VEC>
 __global__ void stepbn_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                     const float* __restrict__ beta, float* __restrict__ y, unsigned total, int B, int C,
@@ -1775,28 +1801,7 @@ __global__ void stepbn_apply_kernel(const float* __restrict__ x, const float* __
     const int SC = f.S * C;
     const unsigned nblk = gridDim.x - 1, bid = blockIdx.x - 1;
     if (blockIdx.x == 0) {
-        if (!f.acc) return;   // given statistics: nothing to finalise
-        for (int sc = threadIdx.x; sc < SC; sc += blockDim.x) {
-            float m, v;
-            stepbn_moments(x, f.acc, sc, sc / C, sc % C, B, C, HW, f.ny, SC, m, v);
-            f.mean_out[sc] = m;
-            f.var_out[sc] = v;
-        }
-        if (f.run_mean) {
-            for (int c = threadIdx.x; c < C; c += blockDim.x) {  // loads only inside the loop: they pipeline
-                float em = 0.f, ev = 0.f;
-#pragma unroll 4
-                for (int s = 0; s < f.S; ++s) {
-                    float m, v;
-                    stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, v);
-                    em = fmaf(f.coef[s], m, em);
-                    ev = fmaf(f.coef_u[s], v, ev);
-                }
-                f.run_mean[c] = fmaf(f.decay, f.run_mean[c], em);
-                f.run_var[c] = fmaf(f.decay, f.run_var[c], ev);
-            }
-        }
-        if (f.nbt && threadIdx.x == 0) *f.nbt += f.S;
+        stepbn_finalise(x, B, C, HW, f);
         return;
     }
     const unsigned nvec = total / VEC;
@@ -1873,6 +1878,22 @@ __global__ __launch_bounds__(256) void stepbn_bwd_reduce_kernel(const float* __r
         sgx[(long)blockIdx.y * gridDim.x + blockIdx.x] = tx;
     }
 }
+// the extra first workgroup of a backward apply kernel (pooled or not): the parameter gradients
+__device__ __forceinline__ void stepbn_param_grads(const float* __restrict__ sg, const float* __restrict__ sgx,
+                                                   float* __restrict__ ggamma, float* __restrict__ gbeta, int C, int S,
+                                                   int ny, int world) {
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float a = 0.f, b = 0.f;
+        for (int i = 0; i < ny * S; ++i) {  // [ny][S][C]: all partials of channel c
+            a += sgx[(long)i * C + c];
+            b += sg[(long)i * C + c];
+        }
+        // (world > 1: the partial sums were added over the ranks for gx; a parameter gradient is this rank's
+        // share of a rank average, so the sum over ranks is divided by their number)
+        ggamma[c] = a / (float)world;
+        gbeta[c] = b / (float)world;
+    }
+}
 template <int VEC>
 __global__ void stepbn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ beta,
                                         const float* __restrict__ g, const float* __restrict__ mean,
@@ -1885,17 +1906,7 @@ __global__ void stepbn_bwd_apply_kernel(const float* __restrict__ x, const float
     const int SC = S * C;
     const unsigned nblk = ggamma ? gridDim.x - 1 : gridDim.x, bid = ggamma ? blockIdx.x - 1 : blockIdx.x;
     if (ggamma && blockIdx.x == 0) {
-        for (int c = threadIdx.x; c < C; c += blockDim.x) {
-            float a = 0.f, b = 0.f;
-            for (int i = 0; i < ny * S; ++i) {  // [ny][S][C]: all partials of channel c
-                a += sgx[(long)i * C + c];
-                b += sg[(long)i * C + c];
-            }
-            // (world > 1: the partial sums were added over the ranks for gx; a parameter gradient is this rank's
-            // share of a rank average, so the sum over ranks is divided by their number)
-            ggamma[c] = a / (float)world;
-            gbeta[c] = b / (float)world;
-        }
+        stepbn_param_grads(sg, sgx, ggamma, gbeta, C, S, ny, world);
         return;
     }
     const float inv_n = 1.f / ((float)(B * HW) * (float)world);
@@ -2063,6 +2074,404 @@ extern "C" int rfn_stepbn_bwd_f32(const float* x, const float* gamma, const floa
     else
         hipLaunchKernelGGL(stepbn_bwd_apply_kernel<1>, dim3(grid + extra), dim3(256), 0, st, x, beta, g, mean, var, gamma,
                            sg, sgx, gx, (unsigned)total, B, C, HW, eps, act, slope, ggamma, gbeta, S, ny, world);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- per-step BatchNorm + 2x2 max-pool
+// conv -> BatchNorm -> activation -> MaxPool2d(2, 2) of the extractor: the apply kernel writes only the pooled map
+// p [S*B, C, H/2, W/2], and the backward recomputes each window's winner from x, so neither the full-resolution
+// activation, nor an index map, nor a full-resolution gradient exists.  The statistics kernel, the moments, the finalising
+// workgroup and the parameter-gradient workgroup are those of the unpooled kernels above.
+// A window's winner by max_pool2d's rule: the ACTIVATED values in the order (0,0), (0,1), (1,0), (1,1); a candidate
+// replaces the best when it is larger or NaN.  xv = the four inputs in that order -> the winner's position (0..3), its
+// activated value, its xhat and its activation input u.
+__device__ __forceinline__ int stepbn_pool_winner(const float xv[4], float m, float rstd, float ga, float be, int act,
+                                                  float slope, float& best, float& xh_w, float& u_w) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float xh = (xv[j] - m) * rstd;
+        const float u = xh * ga + be;
+        const float a = stepbn_act(u, act, slope);
+        if (j == 0 || a > best || isnan(a)) {
+            best = a;
+            xh_w = xh;
+            u_w = u;
+            k = j;
+        }
+    }
+    return k;
+}
+// A thread's unit: VEC == 4: rows 2i, 2i+1 x columns 4j..4j+3 of one plane (two 16-byte loads) = two windows; VEC == 1:
+// one window, scalar accesses.  Unit u of either kind: q = u / (units per pooled row) = plane * H/2 + i, its first input
+// element is q * 2W + (VEC == 4 ? 4 : 2) * (u - q * units per row) and its first pooled element is u * (VEC == 4 ? 2 : 1).
+template <int VEC>
+__device__ __forceinline__ void stepbn_pool_load(const float* __restrict__ x, unsigned in0, int W, float xv[2][4]) {
+    if (VEC == 4) {
+        const float4 r0 = *reinterpret_cast<const float4*>(x + in0);
+        const float4 r1 = *reinterpret_cast<const float4*>(x + in0 + W);
+        xv[0][0] = r0.x; xv[0][1] = r0.y; xv[0][2] = r1.x; xv[0][3] = r1.y;
+        xv[1][0] = r0.z; xv[1][1] = r0.w; xv[1][2] = r1.z; xv[1][3] = r1.w;
+    } else {
+        xv[0][0] = x[in0]; xv[0][1] = x[in0 + 1]; xv[0][2] = x[in0 + W]; xv[0][3] = x[in0 + W + 1];
+    }
+}
+template <int VEC>
+__global__ void stepbn_pool_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
+                                         const float* __restrict__ beta, float* __restrict__ p, unsigned nunits, int B,
+                                         int C, int H, int W, float eps, int act, float slope, StepBnFused f) {
+    constexpr int NW = VEC == 4 ? 2 : 1;  // windows per unit
+    const int SC = f.S * C, HW = H * W;
+    const unsigned nblk = gridDim.x - 1, bid = blockIdx.x - 1;
+    if (blockIdx.x == 0) {
+        stepbn_finalise(x, B, C, HW, f);
+        return;
+    }
+    const unsigned upr = (unsigned)W / (2 * NW), Ho = (unsigned)H / 2;
+    for (unsigned u = bid * blockDim.x + threadIdx.x; u < nunits; u += nblk * blockDim.x) {
+        const unsigned q = u / upr;
+        const unsigned r = q / Ho;  // frame * C + c
+        const int c = (int)(r % (unsigned)C);
+        const int s = (int)(r / (unsigned)C / (unsigned)B);
+        float m = f.acc ? 0.f : f.mean_out[s * C + c], vr = f.acc ? 0.f : f.var_out[s * C + c];
+        stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, vr);
+        const float rstd = rsqrtf(vr + eps);
+        const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
+        float xv[2][4], o[NW];
+        stepbn_pool_load<VEC>(x, q * 2u * (unsigned)W + 2u * NW * (u - q * upr), W, xv);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            float xh, uu;
+            stepbn_pool_winner(xv[w], m, rstd, ga, be, act, slope, o[w], xh, uu);
+        }
+        if (VEC == 4)
+            *reinterpret_cast<float2*>(p + 2u * u) = float2{o[0], o[NW - 1]};
+        else
+            p[u] = o[0];
+    }
+}
+// block (sc, j): partial sums of g' and g' * xhat_winner over the windows of frames j, j+gridDim.y, ... with
+// g' = gp * act'(u_winner), stored like stepbn_bwd_reduce_kernel's (the same terms: a lost position's gradient is zero).
+// A block adds its terms in fp64 and rounds its pair once (a quarter of the unpooled kernel's loads feed the sums, so the
+// adds are hidden behind them): the fp32 partial rows and their consumers are unchanged.
+__device__ __forceinline__ double block_sum_256_f64(double v, double* sm /* >= 4 doubles */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) sm[wave] = v;
+    __syncthreads();
+    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void stepbn_pool_bwd_reduce_kernel(
+    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ gp, const float* __restrict__ mean, const float* __restrict__ var, float* __restrict__ sg,
+    float* __restrict__ sgx, int B, int C, int H, int W, float eps, int act, float slope) {
+    constexpr int NW = VEC == 4 ? 2 : 1;
+    __shared__ double sm[4];
+    const int s = blockIdx.x / C, c = blockIdx.x - s * C;
+    const int HW = H * W, upr = W / (2 * NW), upf = (H / 2) * upr;  // units per pooled row / per plane
+    const unsigned pl0 = (unsigned)(s * B) * C + c;                 // plane of frame 0 of this step
+    const float m = mean[blockIdx.x], rstd = rsqrtf(var[blockIdx.x] + eps);
+    const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
+    double a = 0., ax = 0.;
+    const int nb = (B - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
+    for (int idx = threadIdx.x; idx < nb * upf; idx += 256) {
+        const int bi = idx / upf, t = idx - bi * upf;
+        const unsigned pl = pl0 + (blockIdx.y + (unsigned)bi * gridDim.y) * (unsigned)C;
+        const int i = t / upr, j = t - i * upr;
+        float xv[2][4], gv[NW];
+        stepbn_pool_load<VEC>(x, pl * (unsigned)HW + 2u * i * W + 2u * NW * j, W, xv);
+        const unsigned o0 = pl * (unsigned)(HW / 4) + (unsigned)t * NW;
+        if (VEC == 4) {
+            const float2 g2 = *reinterpret_cast<const float2*>(gp + o0);
+            gv[0] = g2.x; gv[NW - 1] = g2.y;
+        } else {
+            gv[0] = gp[o0];
+        }
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            float best, xh, u;
+            stepbn_pool_winner(xv[w], m, rstd, ga, be, act, slope, best, xh, u);
+            const float g1 = gv[w] * stepbn_dact(u, act, slope);
+            a += (double)g1;
+            ax = fma((double)g1, (double)xh, ax);
+        }
+    }
+    const float ta = (float)block_sum_256_f64(a, sm);
+    const float tx = (float)block_sum_256_f64(ax, sm);
+    if (threadIdx.x == 0) {
+        sg[(long)blockIdx.y * gridDim.x + blockIdx.x] = ta;
+        sgx[(long)blockIdx.y * gridDim.x + blockIdx.x] = tx;
+    }
+}
+// gx = gamma rstd (g' [winner] - k1 - xhat k2) at the four positions of every window
+template <int VEC>
+__global__ void stepbn_pool_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ beta,
+                                             const float* __restrict__ gp, const float* __restrict__ mean,
+                                             const float* __restrict__ var, const float* __restrict__ gamma,
+                                             const float* __restrict__ sg, const float* __restrict__ sgx,
+                                             float* __restrict__ gx, unsigned nunits, int B, int C, int H, int W,
+                                             float eps, int act, float slope, float* __restrict__ ggamma,
+                                             float* __restrict__ gbeta, int S, int ny, int world) {
+    constexpr int NW = VEC == 4 ? 2 : 1;
+    const int SC = S * C, HW = H * W;
+    const unsigned nblk = ggamma ? gridDim.x - 1 : gridDim.x, bid = ggamma ? blockIdx.x - 1 : blockIdx.x;
+    if (ggamma && blockIdx.x == 0) {
+        stepbn_param_grads(sg, sgx, ggamma, gbeta, C, S, ny, world);
+        return;
+    }
+    const float inv_n = 1.f / ((float)(B * HW) * (float)world);
+    const unsigned upr = (unsigned)W / (2 * NW), Ho = (unsigned)H / 2;
+    for (unsigned u = bid * blockDim.x + threadIdx.x; u < nunits; u += nblk * blockDim.x) {
+        const unsigned q = u / upr;
+        const unsigned r = q / Ho;
+        const int c = (int)(r % (unsigned)C);
+        const int s = (int)(r / (unsigned)C / (unsigned)B);
+        const int sc = s * C + c;
+        const float rstd = rsqrtf(var[sc] + eps), m = mean[sc];
+        const float w = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
+        float k1 = 0.f, k2 = 0.f;
+        for (int yy = 0; yy < ny; ++yy) {
+            k1 += sg[(long)yy * SC + sc];
+            k2 += sgx[(long)yy * SC + sc];
+        }
+        k1 *= inv_n;
+        k2 *= inv_n;
+        const unsigned in0 = q * 2u * (unsigned)W + 2u * NW * (u - q * upr);
+        float xv[2][4], gv[NW];
+        stepbn_pool_load<VEC>(x, in0, W, xv);
+        if (VEC == 4) {
+            const float2 g2 = *reinterpret_cast<const float2*>(gp + 2u * u);
+            gv[0] = g2.x; gv[NW - 1] = g2.y;
+        } else {
+            gv[0] = gp[u];
+        }
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) {
+            float best, xhw, uw;
+            const int k = stepbn_pool_winner(xv[ww], m, rstd, w, be, act, slope, best, xhw, uw);
+            const float g1 = gv[ww] * stepbn_dact(uw, act, slope);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float xh = (xv[ww][j] - m) * rstd;
+                const float gpos = j == k ? g1 : 0.f;
+                xv[ww][j] = w * rstd * (gpos - k1 - xh * k2);
+            }
+        }
+        if (VEC == 4) {
+            *reinterpret_cast<float4*>(gx + in0) = float4{xv[0][0], xv[0][1], xv[NW - 1][0], xv[NW - 1][1]};
+            *reinterpret_cast<float4*>(gx + in0 + W) = float4{xv[0][2], xv[0][3], xv[NW - 1][2], xv[NW - 1][3]};
+        } else {
+            gx[in0] = xv[0][0]; gx[in0 + 1] = xv[0][1]; gx[in0 + W] = xv[0][2]; gx[in0 + W + 1] = xv[0][3];
+        }
+    }
+}
+// The launch decisions of the pooled entry points, made once (rfn_stepbn_pool_kernel_label prints them).  `aligned` as for
+// choose_stepbn: bit 0 = the pointers of the statistics kernel (x) or, with bwd, of the reduce kernel (x, gp); bit 1 =
+// those of the apply kernel (x, p; with bwd x, gp, gx).  The statistics kernel is the unpooled one and tests H*W % 4
+// (always 0 here); the pooled kernels read two 16-byte row pieces per unit and need W % 4 == 0.
+constexpr int STEPBN_POOL_GRID_CAP = 8192;
+struct StepBnPoolRoute {
+    int ny;          // workgroups per (step, channel) of the stats / reduce kernel (stepbn_split)
+    bool stats_vec;  // stats kernel (bwd: reduce kernel) on 16-byte loads
+    bool v4;         // apply kernel: stepbn_pool_*apply_kernel<4> (units of two windows); else <1> (one window)
+    long nunits;     // units of the apply kernel
+    int grid;        // its streaming workgroups
+    int sweeps;      // most grid-stride iterations of one
+};
+static StepBnPoolRoute choose_stepbn_pool(int S, int B, int C, int H, int W, int aligned, int bwd) {
+    StepBnPoolRoute r;
+    const long total = (long)S * B * C * H * W;
+    r.ny = stepbn_split(S, B, C);
+    r.stats_vec = (aligned & 1) && (bwd ? W % 4 == 0 : true);
+    r.v4 = W % 4 == 0 && (aligned & 2);
+    r.nunits = r.v4 ? total / 8 : total / 4;
+    const long nb = (r.nunits + 255) / 256;
+    r.grid = (int)(nb < STEPBN_POOL_GRID_CAP ? nb : STEPBN_POOL_GRID_CAP);
+    r.sweeps = (int)((nb + r.grid - 1) / r.grid);
+    return r;
+}
+static bool stepbn_pool_sizes_ok(int S, int B, int C, int H, int W) {
+    return S > 0 && B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0;
+}
+extern "C" const char* rfn_stepbn_pool_kernel_label(int S, int B, int C, int H, int W, int aligned, int bwd) {
+    static thread_local char buf[160];
+    if (!stepbn_pool_sizes_ok(S, B, C, H, W) || (long)S * B * C * H * W >= (1L << 31)) return "unsupported";
+    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, aligned, bwd);
+    snprintf(buf, sizeof(buf), "stepbn_pool ny=%d stats=%s apply=%s grid=%d sweeps=%d", r.ny,
+             r.stats_vec ? "vec" : "scalar", r.v4 ? "vec4" : "vec1", r.grid, r.sweeps);
+    return buf;
+}
+// rfn_stepbn_fwd_f32 with the 2x2 max-pool folded into the apply launch: p [S*B, C, H/2, W/2] is the only map written
+extern "C" int rfn_stepbn_pool_fwd_f32(const float* x, const float* gamma, const float* beta, float* p, float* mean,
+                                       float* var, float* acc, float* run_mean, float* run_var, const float* coef,
+                                       const float* coef_u, float decay, long long* nbt, int S, int B, int C, int H, int W,
+                                       float eps, int act, float slope, rfn_stream_t stream) {
+    RFN_CHECK_ARG(x && p && mean && var && acc && S > 0 && B > 0 && C > 0 && H > 0 && W > 0, -1);
+    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((run_mean && run_var && coef && coef_u) || (!run_mean && !run_var)),
+                  -2);
+    RFN_CHECK_ARG(H % 2 == 0 && W % 2 == 0, -5);
+    const long total = (long)S * B * C * H * W;
+    RFN_CHECK_ARG(total < (1L << 31), -3);
+    hipStream_t st = (hipStream_t)stream;
+    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, stepbn_aligned(x, nullptr, x, p, nullptr), 0);
+    hipLaunchKernelGGL(stepbn_stats_kernel, dim3(S * C, r.ny), dim3(256), 0, st, x, acc, B, C, H * W);
+    StepBnFused f;
+    f.acc = acc; f.mean_out = mean; f.var_out = var; f.run_mean = run_mean; f.run_var = run_var; f.coef = coef;
+    f.coef_u = coef_u; f.decay = decay; f.nbt = nbt; f.S = S; f.ny = r.ny;
+    if (r.v4)
+        hipLaunchKernelGGL(stepbn_pool_apply_kernel<4>, dim3(r.grid + 1), dim3(256), 0, st, x, gamma, beta, p,
+                           (unsigned)r.nunits, B, C, H, W, eps, act, slope, f);
+    else
+        hipLaunchKernelGGL(stepbn_pool_apply_kernel<1>, dim3(r.grid + 1), dim3(256), 0, st, x, gamma, beta, p,
+                           (unsigned)r.nunits, B, C, H, W, eps, act, slope, f);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+// the backward of that layer from the POOLED gradient gp [S*B, C, H/2, W/2]: stage / world as rfn_stepbn_bwd_f32
+extern "C" int rfn_stepbn_pool_bwd_f32(const float* x, const float* gamma, const float* beta, const float* gp,
+                                       const float* mean, const float* var, float* sums, float* gx, float* ggamma,
+                                       float* gbeta, int S, int B, int C, int H, int W, float eps, int act, float slope,
+                                       int stage, int world, rfn_stream_t stream) {
+    RFN_CHECK_ARG(x && gp && mean && var && sums && gx && S > 0 && B > 0 && C > 0 && H > 0 && W > 0, -1);
+    RFN_CHECK_ARG(stage >= 0 && stage <= 2 && world >= 1, -4);
+    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((ggamma && gbeta) || (!ggamma && !gbeta)), -2);
+    RFN_CHECK_ARG(H % 2 == 0 && W % 2 == 0, -5);
+    const long total = (long)S * B * C * H * W;
+    RFN_CHECK_ARG(total < (1L << 31), -3);
+    hipStream_t st = (hipStream_t)stream;
+    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, stepbn_aligned(x, gp, x, gp, gx), 1);
+    const int ny = r.ny;
+    float* sg = sums;
+    float* sgx = sums + (long)ny * S * C;
+    if (stage != 2) {
+        if (r.stats_vec)
+            hipLaunchKernelGGL(stepbn_pool_bwd_reduce_kernel<4>, dim3(S * C, ny), dim3(256), 0, st, x, gamma, beta, gp, mean,
+                               var, sg, sgx, B, C, H, W, eps, act, slope);
+        else
+            hipLaunchKernelGGL(stepbn_pool_bwd_reduce_kernel<1>, dim3(S * C, ny), dim3(256), 0, st, x, gamma, beta, gp, mean,
+                               var, sg, sgx, B, C, H, W, eps, act, slope);
+    }
+    if (stage == 1) {
+        RFN_LAUNCH_CHECK();
+        return 0;
+    }
+    const int extra = ggamma ? 1 : 0;
+    if (r.v4)
+        hipLaunchKernelGGL(stepbn_pool_bwd_apply_kernel<4>, dim3(r.grid + extra), dim3(256), 0, st, x, beta, gp, mean, var,
+                           gamma, sg, sgx, gx, (unsigned)r.nunits, B, C, H, W, eps, act, slope, ggamma, gbeta, S, ny, world);
+    else
+        hipLaunchKernelGGL(stepbn_pool_bwd_apply_kernel<1>, dim3(r.grid + extra), dim3(256), 0, st, x, beta, gp, mean, var,
+                           gamma, sg, sgx, gx, (unsigned)r.nunits, B, C, H, W, eps, act, slope, ggamma, gbeta, S, ny, world);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------- nearest 2x up-sampling + channel cat
+// The upscaler's NearestUp2x -> torch.cat((x, skip), 1) in one launch: out[n, c] = up2x(x[n, c]) for c < Cx, else
+// skip[n, c - Cx].  Backward: gx = the 2x2 block sums of g[:, :Cx], read in place through g's frame stride (each sum is
+// formed in fp64 and rounded once); the skip's gradient is the view g[:, Cx:].  VEC == 4: 16-byte pieces of the 2w-wide
+// rows (w even, aligned pointers and frame strides); VEC == 1: one element per thread.
+constexpr int UP2X_GRID_CAP = 8192;
+template <int VEC>
+__global__ void up2x_cat_kernel(const float* __restrict__ x, long x_ns, const float* __restrict__ skip, long s_ns,
+                                float* __restrict__ out, unsigned nunits, int Cx, int Cs, int h, int w) {
+    const unsigned upr = VEC == 4 ? (unsigned)w / 2 : 2u * w, H2 = 2u * h, Ct = (unsigned)(Cx + Cs);
+    for (unsigned u = blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += gridDim.x * blockDim.x) {
+        const unsigned row = u / upr, k = u - row * upr;  // row = (n * Ct + c) * 2h + Y
+        const unsigned rc = row / H2, Y = row - rc * H2;
+        const unsigned n = rc / Ct, c = rc - n * Ct;
+        if (VEC == 4) {
+            float4 v;
+            if (c < (unsigned)Cx) {
+                const float2 t = *reinterpret_cast<const float2*>(x + n * x_ns + ((long)c * h + Y / 2) * w + 2 * k);
+                v = float4{t.x, t.x, t.y, t.y};
+            } else {
+                v = *reinterpret_cast<const float4*>(skip + n * s_ns + ((long)(c - Cx) * H2 + Y) * (2 * w) + 4 * k);
+            }
+            *reinterpret_cast<float4*>(out + 4ul * u) = v;
+        } else {
+            out[u] = c < (unsigned)Cx ? x[n * x_ns + ((long)c * h + Y / 2) * w + k / 2]
+                                      : skip[n * s_ns + ((long)(c - Cx) * H2 + Y) * (2 * w) + k];
+        }
+    }
+}
+template <int VEC>
+__global__ void up2x_cat_bwd_kernel(const float* __restrict__ g, long g_ns, float* __restrict__ gx, unsigned nunits,
+                                    int Cx, int h, int w) {
+    const unsigned upr = VEC == 4 ? (unsigned)w / 2 : (unsigned)w;
+    for (unsigned u = blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += gridDim.x * blockDim.x) {
+        const unsigned row = u / upr, k = u - row * upr;  // row = (n * Cx + c) * h + i
+        const unsigned rc = row / (unsigned)h, i = row - rc * (unsigned)h;
+        const unsigned n = rc / (unsigned)Cx, c = rc - n * (unsigned)Cx;
+        const float* r0 = g + n * g_ns + ((long)c * 2 * h + 2 * i) * (2 * w) + (VEC == 4 ? 4 : 2) * k;
+        const float* r1 = r0 + 2 * w;
+        if (VEC == 4) {
+            const float4 a = *reinterpret_cast<const float4*>(r0), b = *reinterpret_cast<const float4*>(r1);
+            *reinterpret_cast<float2*>(gx + 2ul * u) = float2{(float)(((double)a.x + a.y) + ((double)b.x + b.y)),
+                                                              (float)(((double)a.z + a.w) + ((double)b.z + b.w))};
+        } else {
+            gx[u] = (float)(((double)r0[0] + r0[1]) + ((double)r1[0] + r1[1]));
+        }
+    }
+}
+struct Up2xRoute {
+    bool v4;
+    long nunits;
+    int grid, sweeps;
+};
+// `aligned`: every pointer is 16-byte aligned and every frame stride a multiple of 4 floats; out_elems = the elements of
+// out (forward) or of gx (backward)
+static Up2xRoute choose_up2x(long out_elems, int w, int aligned, int bwd) {
+    Up2xRoute r;
+    r.v4 = w % 2 == 0 && aligned;
+    r.nunits = r.v4 ? out_elems / (bwd ? 2 : 4) : out_elems;
+    const long nb = (r.nunits + 255) / 256;
+    r.grid = (int)(nb < UP2X_GRID_CAP ? nb : UP2X_GRID_CAP);
+    r.sweeps = (int)((nb + r.grid - 1) / r.grid);
+    return r;
+}
+static bool up2x_sizes_ok(int N, int Cx, int Cs, int h, int w, int bwd) {
+    return N > 0 && Cx > 0 && Cs >= 0 && h > 0 && w > 0 && 4L * N * (bwd ? Cx : Cx + Cs) * h * w < (1L << 31);
+}
+extern "C" const char* rfn_up2x_cat_kernel_label(int N, int Cx, int Cs, int h, int w, int aligned, int bwd) {
+    static thread_local char buf[128];
+    if (!up2x_sizes_ok(N, Cx, Cs, h, w, bwd)) return "unsupported";
+    const Up2xRoute r = choose_up2x(bwd ? (long)N * Cx * h * w : 4L * N * (Cx + Cs) * h * w, w, aligned, bwd);
+    snprintf(buf, sizeof(buf), "up2x_cat%s access=%s grid=%d sweeps=%d", bwd ? "_bwd" : "", r.v4 ? "vec4" : "vec1", r.grid,
+             r.sweeps);
+    return buf;
+}
+extern "C" int rfn_up2x_cat_f32(const float* x, long x_ns, const float* skip, long skip_ns, float* out, int N, int Cx,
+                                int Cs, int h, int w, rfn_stream_t stream) {
+    RFN_CHECK_ARG(x && skip && out && Cs > 0 && up2x_sizes_ok(N, Cx, Cs, h, w, 0), -1);
+    RFN_CHECK_ARG(x_ns >= (long)Cx * h * w && skip_ns >= 4L * Cs * h * w, -2);
+    const int aligned = ((((uintptr_t)x | (uintptr_t)skip | (uintptr_t)out) & 15) == 0 && x_ns % 4 == 0 && skip_ns % 4 == 0);
+    const Up2xRoute r = choose_up2x(4L * N * (Cx + Cs) * h * w, w, aligned, 0);
+    if (r.v4)
+        hipLaunchKernelGGL(up2x_cat_kernel<4>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, x, x_ns, skip, skip_ns, out,
+                           (unsigned)r.nunits, Cx, Cs, h, w);
+    else
+        hipLaunchKernelGGL(up2x_cat_kernel<1>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, x, x_ns, skip, skip_ns, out,
+                           (unsigned)r.nunits, Cx, Cs, h, w);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int rfn_up2x_cat_bwd_f32(const float* g, long g_ns, float* gx, int N, int Cx, int h, int w,
+                                    rfn_stream_t stream) {
+    RFN_CHECK_ARG(g && gx && up2x_sizes_ok(N, Cx, 0, h, w, 1), -1);
+    RFN_CHECK_ARG(g_ns >= 4L * Cx * h * w, -2);
+    const int aligned = ((((uintptr_t)g | (uintptr_t)gx) & 15) == 0 && g_ns % 4 == 0);
+    const Up2xRoute r = choose_up2x((long)N * Cx * h * w, w, aligned, 1);
+    if (r.v4)
+        hipLaunchKernelGGL(up2x_cat_bwd_kernel<4>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, g, g_ns, gx,
+                           (unsigned)r.nunits, Cx, h, w);
+    else
+        hipLaunchKernelGGL(up2x_cat_bwd_kernel<1>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, g, g_ns, gx,
+                           (unsigned)r.nunits, Cx, h, w);
     RFN_LAUNCH_CHECK();
     return 0;
 }

@@ -1801,6 +1801,91 @@ class StepBatchNormActFn(torch.autograd.Function):
         return gx, ggamma, gbeta, None, None, None, None, None
 
 
+class StepBatchNormActPoolFn(torch.autograd.Function):
+    """StepBatchNormActFn followed by MaxPool2d(2, 2) (rfn_stepbn_pool_{fwd,bwd}_f32: two launches each way).  Only the
+    pooled map is written; the backward recomputes every window's winner from x, so no full-resolution activation, index
+    map or full-resolution gradient exists.  Returns (p [S*B, C, H/2, W/2], mean[S, C], biased var[S, C]); arguments as
+    StepBatchNormActFn.  H and W even; not for synchronised BatchNorm (the caller keeps the unfused route there)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, S, eps, act, slope, running=None):
+        ctx.set_materialize_grads(False)
+        x = x.contiguous()
+        SB, C, H, W = (int(v) for v in x.shape)
+        B = SB // S
+        mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
+        var = torch.empty((S, C), device=x.device, dtype=torch.float32)
+        p = torch.empty((SB, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
+        gm = None if gamma is None else gamma.detach().contiguous()
+        bt = None if beta is None else beta.detach().contiguous()
+        nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))
+        acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
+        rm = rv = cf = cfu = nbt = None
+        decay = 1.0
+        if running is not None:
+            rm, rv, cf, cfu, decay, nbt = running
+            if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+                raise RuntimeError("num_batches_tracked must be an int64 device tensor")
+        # x read by the statistics and by the apply launch, a quarter of it written
+        L.call("rfn_stepbn_pool_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(p), L.dev(mean), L.dev(var), L.dev(acc),
+               L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr(), S, B, C, H, W,
+               eps, act, slope, meta=_shell("stepbn_pool_fwd", x, 2.25))
+        ctx.save_for_backward(x, mean, var, gm, bt)
+        ctx.cfg = (S, B, C, H, W, eps, act, slope, gamma is not None, nscr)
+        ctx.mark_non_differentiable(mean, var)
+        return p, mean, var
+
+    @staticmethod
+    def backward(ctx, gp, _gm, _gv):
+        x, mean, var, gm, bt = ctx.saved_tensors
+        S, B, C, H, W, eps, act, slope, affine, nscr = ctx.cfg
+        if gp is None:
+            return (None,) * 8
+        gp = gp.contiguous()
+        sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
+        gx = torch.empty_like(x)
+        ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+        gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+        # x and the pooled gradient read by the reduce and by the apply launch, gx written
+        L.call("rfn_stepbn_pool_bwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(gp), L.dev(mean), L.dev(var), L.dev(sums),
+               L.dev(gx), L.dev(ggamma), L.dev(gbeta), S, B, C, H, W, eps, act, slope, 0, 1,
+               meta=_shell("stepbn_pool_bwd", x, 3.5))
+        return gx, ggamma, gbeta, None, None, None, None, None
+
+
+class Up2xCatFn(torch.autograd.Function):
+    """torch.cat((nearest_up2x(x), skip), 1) in one launch (rfn_up2x_cat_f32); backward: gx = the 2x2 block sums of
+    g[:, :Cx] read in place (rfn_up2x_cat_bwd_f32), the skip's gradient is the view g[:, Cx:]."""
+
+    @staticmethod
+    def forward(ctx, x, skip):
+        N, Cx, h, w = (int(v) for v in x.shape)
+        Cs = int(skip.shape[1])
+        if tuple(skip.shape) != (N, Cs, 2 * h, 2 * w):
+            raise RuntimeError("Up2xCatFn: skip %s does not fit x %s" % (tuple(skip.shape), tuple(x.shape)))
+        dense = lambda t: all(t.shape[d] == 1 or t.stride(d) == e for d, e in
+                              ((3, 1), (2, t.shape[3]), (1, t.shape[2] * t.shape[3])))
+        x, skip = (t if dense(t) else t.contiguous() for t in (x, skip))   # channel-slice views are read in place
+        xp, xns = L.frames(x, "x")
+        sp, sns = L.frames(skip, "skip")
+        out = torch.empty((N, Cx + Cs, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
+        L.call("rfn_up2x_cat_f32", xp, xns, sp, sns, L.dev(out), N, Cx, Cs, h, w,
+               meta=_shell("up2x_cat", out, 1.0 + (0.25 * Cx + Cs) / (Cx + Cs)))
+        ctx.cfg = (N, Cx, h, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        N, Cx, h, w = ctx.cfg
+        g = g.contiguous()
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gp, gns = L.frames(g, "g")
+            gx = torch.empty((N, Cx, h, w), device=g.device, dtype=torch.float32)
+            L.call("rfn_up2x_cat_bwd_f32", gp, gns, L.dev(gx), N, Cx, h, w, meta=_shell("up2x_cat_bwd", gx, 5))
+        return gx, (g[:, Cx:] if ctx.needs_input_grad[1] else None)
+
+
 def bnflow_coef(steps, momentum):
     """(coef [steps] as float64, decay) of the closed form of `steps` running-statistics updates r <- m r + (1 - m) stat_s of
     BatchNormFlow (glow_modules.py:81-87; the momentum weights the OLD value): r <- decay r + sum_s coef[s] stat_s with
