@@ -430,6 +430,34 @@ int rfn_latent_step_bwd_f32(const float* enc, const float* pri, const float* eps
                             const float* g_em, const float* g_es, float* g_enc, float* g_pri, int B, int ZHW, int res_q,
                             rfn_stream_t stream);
 
+/* ---- VRNN baseline: the diagonal Gaussians of one time step, csrc/gauss_heads.hip  (VRNN/VRNN.py:203-213 + :223 in
+ * `loss`, :383-394 + :419-420 in `elbo_importance_weighting`, :265-273 and :290-294 in `predict`: td.Normal of the
+ * encoder and prior MLP outputs, both rsamples, td.kl_divergence, Normal.log_prob of each sample -- about twenty torch
+ * launches per step).  All tensors [B, Z] contiguous; sigma = softplus(raw) as torch.nn.Softplus() computes it (raw itself
+ * where raw > 20, else log1p(exp(raw))); nothing is added to sigma (this is not rfn_gauss_logp's +1e-8, nor
+ * rfn_latent_step's pairing of halves).
+ *   z_q = q_loc + sq*eps_q,  z_p = p_loc + sp*eps_p,  q_scale = sq,  p_scale = sp;
+ *   with a = sq/sp, d = (q_loc - p_loc)/sp:   kl[b] = sum_j  (a^2 + d^2 - 1)/2 - (log sq - log sp);
+ *   logq[b] = sum_j  -eps_q^2/2 - log sq - log(2 pi)/2,  logp[b] the same with p: the density at the OWN sample.
+ * Every output pointer may be NULL.  eps_q NULL: no z_q and no logq; eps_p NULL: no z_p and no logp; q_loc, q_raw and eps_q
+ * all NULL: the prior-only form of generation (z_p, p_scale, logp).  p_loc / p_raw are always needed.  -1: sizes below 1, a
+ * missing p input, one of q_loc / q_raw without the other; -2: an output (backward: an upstream gradient, or eps_q) whose
+ * inputs are missing; -3: a gradient row stride below Z.  Nothing is launched then.
+ * Backward: the gradient of the formulas above, sigma recomputed, sigma'(raw) = logistic(raw) and exactly 1 above the
+ * threshold.  g_zq / g_zp are read with a row stride in floats (>= Z), as rfn_latent_step_bwd_f32 reads its own; g_kl,
+ * g_logq, g_logp are [B]; any upstream pointer may be NULL.  g_q_loc, g_q_raw, g_p_loc, g_p_raw are WRITTEN (g_q_* are NULL
+ * exactly when q_loc is).
+ * One wavefront per row, four rows per workgroup; lane l adds the terms of elements l, l + 64, ... in index order and the
+ * 64 lane sums are combined by a fixed xor butterfly (32, 16, ..., 1): no atomics, no LDS memory, a row's bits depend on
+ * that row alone (not on B or the grid).  Any B >= 1, Z >= 1; one launch, no allocation: capturable. */
+int rfn_gauss_heads_fwd_f32(const float* q_loc, const float* q_raw, const float* p_loc, const float* p_raw,
+                            const float* eps_q, const float* eps_p, float* z_q, float* z_p, float* q_scale,
+                            float* p_scale, float* kl, float* logq, float* logp, int B, int Z, rfn_stream_t stream);
+int rfn_gauss_heads_bwd_f32(const float* q_loc, const float* q_raw, const float* p_loc, const float* p_raw,
+                            const float* eps_q, const float* eps_p, const float* g_zq, long g_zq_ns, const float* g_zp,
+                            long g_zp_ns, const float* g_kl, const float* g_logq, const float* g_logp, float* g_q_loc,
+                            float* g_q_raw, float* g_p_loc, float* g_p_raw, int B, int Z, rfn_stream_t stream);
+
 /* ---- a10  the per-timestep parameter nets (SimpleParamNet, Utils/modules.py:216-244, called once per frame by
  * RFN.loss, RFN/RFN_new.py:167-179) on small maps: a 3x3 / pad 1 convolution on an H x W <= 16 pixel map is the dense
  * product out[b][(co,po)] = bias[co] + sum x[b][(ci,pi)] * w[co][ci][tap(po,pi)] over NCHW-contiguous samples.
