@@ -458,6 +458,32 @@ int rfn_gauss_heads_bwd_f32(const float* q_loc, const float* q_raw, const float*
                             long g_zp_ns, const float* g_kl, const float* g_logq, const float* g_logp, float* g_q_loc,
                             float* g_q_raw, float* g_p_loc, float* g_p_raw, int B, int Z, rfn_stream_t stream);
 
+/* ---- SVG baseline: one torch.nn.LSTMCell call, csrc/lstm_cell.hip  (SVG/SVG.py:131,149 and :163,185 of the reference:
+ * every layer of frame_predictor, posterior and prior).  All tensors contiguous float32: x [B, I], h [B, H], c [B, H],
+ * w_ih [4H, I], w_hh [4H, H], b_ih [4H], b_hh [4H]; rows gH .. gH+H-1 belong to gate g, g = 0..3 = i, f, g, o.
+ *   pre_g[b,j] = sum_k x[b,k] w_ih[gH+j,k] + sum_k h[b,k] w_hh[gH+j,k] + b_ih[gH+j] + b_hh[gH+j]
+ *   i = sigmoid(pre_i), f = sigmoid(pre_f), g = tanh(pre_g), o = sigmoid(pre_o);  c' = f c + i g,  h' = o tanh(c')
+ * fwd WRITES h_out [B, H] = h', c_out [B, H] = c' and gates [B, 4H] = (i | f | g | o), which the backward reads; the
+ * pre-activations never reach memory.  The products run on the float32-input MFMA 16x16x4 (exact float32 products, one
+ * fma chain per output): a workgroup of four waves owns a 16-row x 16-unit tile, the k range is cut into chunks of 16
+ * (those of x first, then those of h), wave w adds the chunks w, w + 4, ... for all four gates, the four partial sums are
+ * added in wave order, then b_ih, then b_hh.  The order of summation of an output depends on I and H alone.  Operands are
+ * read 16 bytes at a time where I (H) is a multiple of 4 and the bases are 16-byte aligned, else as single floats, in the
+ * same order.
+ * bwd, with the upstreams gh = dL/dh' and gc = dL/dc' (either may be NULL = zero) and t = tanh(c'):
+ *   gct = gc + gh o (1 - t^2);  d_i = gct g i(1-i),  d_f = gct c f(1-f),  d_g = gct i (1-g^2),  d_o = gh t o(1-o)
+ * WRITES D [B, 4H] = (d_i | d_f | d_g | d_o), g_c [B, H] = gct f and g_bias [4H] = sum_b D[b,:] (the gradient of b_ih and
+ * of b_hh): thread (unit, row group rg of 16) adds the rows rg, rg + 16, ... in order and the 16 sums are added in
+ * row-group order -- no atomics.  The four matrix products of the backward (D w_ih, D w_hh, D^T x, D^T h) are the
+ * caller's.  Any B, I, H >= 1 (I, H <= 2^28; ceil(B/16) * ceil(H/16) tiles < 2^31, more
+ * than any memory holds); one launch each, no allocation: capturable.  Bad sizes return
+ * -1, a missing required pointer -2; nothing is launched then. */
+int rfn_lstm_cell_fwd_f32(const float* x, const float* h, const float* c, const float* w_ih, const float* w_hh,
+                          const float* b_ih, const float* b_hh, float* h_out, float* c_out, float* gates, int B, int I,
+                          int H, rfn_stream_t stream);
+int rfn_lstm_cell_bwd_f32(const float* gh, const float* gc, const float* gates, const float* c, const float* c_out,
+                          float* D, float* g_c, float* g_bias, int B, int H, rfn_stream_t stream);
+
 /* ---- a10  the per-timestep parameter nets (SimpleParamNet, Utils/modules.py:216-244, called once per frame by
  * RFN.loss, RFN/RFN_new.py:167-179) on small maps: a 3x3 / pad 1 convolution on an H x W <= 16 pixel map is the dense
  * product out[b][(co,po)] = bias[co] + sum x[b][(ci,pi)] * w[co][ci][tap(po,pi)] over NCHW-contiguous samples.
