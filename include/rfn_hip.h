@@ -213,6 +213,22 @@ int rfn_coupling_po_fwd(const float* z, long z_ns, const float* cond, long cond_
                         long h2_ns, float* P, long P_ns, float* m1, float* m2, int N, int C, int Cc, int H, int W, int act,
                         rfn_stream_t stream);
 long rfn_coupling_po_mask_floats(int N, int H, int W);
+/* Host-only queries of the weight streams' layout (the streams stay opaque to callers: sizes come from the
+ * *_packed_bytes functions).  Change note: the first product's K order is dense -- units of 8 K-values, two per k-step;
+ * full units are (tap, 8-channel group) over the 9 real taps, and where the leftover Cin % 8 channels have a narrow
+ * instantiation (forward Cin 17..18 and 35..36, backward C = 4) they are the FIRST channels and form units of 8/r' taps
+ * x r' channels -- instead of 5 tap pairs x ceil(Cin / 8) groups; streams of an older build are not interchangeable.
+ *   rfn_coupling_po_k_order  unit < 0: the number of units of the forward (bwd = 0, Cin = C/2 + Cc) or backward
+ *       (bwd = 1, Cin = C) stream; else the real taps [*tap0, *tap0 + *n_taps) and channels [*ch0, *ch0 + *n_ch) of
+ *       that unit, and its k-step (unit / 2) as the return value; negative on a bad argument;
+ *   rfn_coupling_po_ring_group  idx < 0: the number of LDS-ring groups of a round; else first fragment (1 KB each,
+ *       fragment 0 = header) and fragment count of group idx in consumption order (C is not read with bwd = 1);
+ *       (out-parameters are long long, the one integer pointee the loader's binding check knows);
+ *   rfn_coupling_po_lds_bytes  dynamic LDS of the kernel instantiation that serves the shape (limit: 160 KB). */
+int rfn_coupling_po_k_order(int Cin, int bwd, int unit, long long* tap0, long long* n_taps, long long* ch0,
+                            long long* n_ch);
+int rfn_coupling_po_ring_group(int Cin, int C, int bwd, int idx, long long* first_frag, long long* n_frags);
+long rfn_coupling_po_lds_bytes(int Cin, int C, int W, int bwd);
 int rfn_coupling_po_bwd_supported(int N, int C, int H, int W);
 long rfn_coupling_po_bwd_packed_bytes(int C);
 int rfn_coupling_po_pack_bwd(const void* descs_device, int n, rfn_stream_t stream);

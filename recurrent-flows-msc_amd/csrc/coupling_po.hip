@@ -40,16 +40,82 @@
 #include "conv_common.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define PO_HD 256          // hidden width (8 output tiles of 32)
-#define PO_TAP_PAIRS 5     // 9 taps in pairs (the lane half selects the tap of a pair); the 10th tap is zero weight
 #define PO_WAVES 4
 #define PO_ROUND_PX (32 * PO_WAVES)
+
+// ---- K order of the first 3x3 product ("conv1"; backward: conv3^T go), the one description the pack kernel, the
+// kernel and the host query (rfn_coupling_po_k_order) read.  A UNIT is 8 K-values = one lane half of a k-step = one
+// 16-byte B fragment; k-step s multiplies unit 2s (lane half 0) and unit 2s + 1 (lane half 1).  For Cin input channels,
+// NG = ceil(Cin / 8) image groups of 8 channels, r = Cin % 8:
+//   * full units (tap, group), tap-major, the 9 real taps only: 9 NGT of them, 8 channels of one tap each;
+//   * narrow leftover (RP = 2 or 4 = next power of two >= r): the r leftover channels are the FIRST r input channels
+//     (the z1 half at the canonical levels; the full groups then hold channels r + 8g ..) and form the last image
+//     group; NGT = NG - 1, and ceil(9 RP / 8) leftover units follow the full ones, each 8 / RP consecutive taps x RP
+//     channels (slot j <-> tap tap0 + j / RP, channel j % RP; slots beyond tap 8 or channel r are zero weight);
+//   * otherwise (RP = 0) every group counts as full, NGT = NG, channels 8g .. in order, those >= Cin zero weight.
+// The narrow form exists where it is instantiated (po_narrow): the canonical levels 0 / 1 forward (Cin 17..18 in three
+// groups, 35..36 in five) and the 4-channel gradient image of the backward chain.  Everything else -- level 2 (r = 0),
+// the 12-channel flow, odd shapes -- takes RP = 0, which still drops the zero tenth tap of the former tap-pair order.
+struct POOrder {
+    int NG, NGT, RP, R;   // image groups, groups that form full units, slot width of the leftover units (0: none), r
+    int n_units, NS1;     // units, k-steps per quad = ceil(n_units / 2)
+};
+struct POUnit {
+    int tap0, n_taps, ch0, n_ch;   // real taps / channels of the unit (n_taps = 0: beyond the last unit, zero weight)
+    int w;                         // slot j <-> (tap0 + j / w, ch0 + j % w)
+    int g;                         // image group the unit reads
+};
+__host__ __device__ constexpr bool po_narrow(int NG, int rp, bool bwd) {
+    return bwd ? (NG == 1 && rp == 4) : ((NG == 3 && rp == 2) || (NG == 5 && rp == 4));
+}
+__host__ __device__ constexpr POOrder po_order(int Cin, bool bwd) {
+    POOrder o{};
+    o.NG = (Cin + 7) / 8;
+    o.R = Cin % 8;
+    const int rp = o.R == 0 ? 0 : o.R <= 2 ? 2 : o.R <= 4 ? 4 : 8;
+    o.RP = po_narrow(o.NG, rp, bwd) ? rp : 0;
+    o.NGT = o.RP ? o.NG - 1 : o.NG;
+    o.n_units = 9 * o.NGT + (o.RP ? (9 * o.RP + 7) / 8 : 0);
+    o.NS1 = (o.n_units + 1) / 2;
+    return o;
+}
+// image offset (positions) of tap 3 (dy + 1) + (dx + 1) from the centre on rows of IW positions
+__host__ __device__ constexpr int po_tap_off(int tap, int IW) { return (tap / 3 - 1) * IW + (tap % 3 - 1); }
+// first input channel of image group g and its valid channels from there (<= 8); staging and po_unit agree through these
+__host__ __device__ constexpr int po_group_ch0(const POOrder& o, int g) { return o.RP ? (g < o.NGT ? o.R + 8 * g : 0) : 8 * g; }
+__host__ __device__ constexpr int po_group_nch(const POOrder& o, int Cin, int g) {
+    const int n = o.RP && g == o.NGT ? o.R : Cin - po_group_ch0(o, g);
+    return n < 8 ? n : 8;
+}
+__host__ __device__ constexpr POUnit po_unit(int Cin, bool bwd, int u) {
+    const POOrder o = po_order(Cin, bwd);
+    POUnit q{};
+    q.w = 8;
+    if (u < 0 || u >= o.n_units) {   // the padding half of an odd count: reads the centre tap of group 0, zero weight
+        q.tap0 = 4;
+        return q;
+    }
+    if (u < 9 * o.NGT) {
+        q.tap0 = u / o.NGT; q.n_taps = 1; q.g = u % o.NGT;
+        q.ch0 = po_group_ch0(o, q.g);
+        q.n_ch = po_group_nch(o, Cin, q.g);
+        return q;
+    }
+    const int tpu = 8 / o.RP;   // taps per leftover unit
+    q.w = o.RP; q.g = o.NGT;
+    q.tap0 = (u - 9 * o.NGT) * tpu;
+    q.n_taps = 9 - q.tap0 < tpu ? 9 - q.tap0 : tpu;
+    q.ch0 = po_group_ch0(o, q.g); q.n_ch = po_group_nch(o, Cin, q.g);
+    return q;
+}
 
 // ---- geometry of the forward weight stream (host + device).  Unit: fragment = 64 lanes x 16 B = 1 KB; two planes
 // (hi, lo) per logical fragment.  Fragment 0 is a header: floats {1/s_w1, 1/s_w2, 1/s_w3}.  Then, consumed in order:
 //   for quad u = 0, 1  (conv1 output tiles 4u .. 4u+3):
-//       NG conv1 groups of 5 k-steps:   ((k*4 + t)*2 + plane)                                    40 fragments
+//       NS1 conv1 k-steps (po_order):    ((k*4 + t)*2 + plane)                                   8 NS1 fragments
 //       4 conv2 groups of 2 k-steps (h1 k-steps 8u + 2g + {0,1}, all 8 output tiles):
 //                                        ((k*8 + a2)*2 + plane)                                  32 fragments
 //   4 conv3 groups of 4 k-steps:         ((k*NP + jt)*2 + plane)                                 8 NP fragments
@@ -60,50 +126,68 @@ struct POGeom {
     int total_frags;
 };
 // bwd: the stream of the backward kernel (data-gradient chain): no conv3 part
-__host__ __device__ static inline POGeom po_geom(int Cin, int C, bool bwd = false) {
-    POGeom g;
+__host__ __device__ constexpr POGeom po_geom(int Cin, int C, bool bwd = false) {
+    POGeom g{};
     g.NG = (Cin + 7) / 8;
     g.NP = bwd ? 0 : (9 * C + 31) / 32;
-    g.NS1 = PO_TAP_PAIRS * g.NG;
-    g.quad_frags = g.NG * 40 + 4 * 32;
+    g.NS1 = po_order(Cin, bwd).NS1;
+    g.quad_frags = g.NS1 * 8 + 4 * 32;
     g.c3 = 1 + 2 * g.quad_frags;
     g.total_frags = g.c3 + 4 * 8 * g.NP;
     return g;
 }
 
 // Grouping of the stream for the LDS ring (the stream itself is linear in the k-step, so the grouping is the kernel's
-// choice): conv1 groups of GS1 k-steps (8 GS1 fragments; NG1 = 5 NG / GS1 groups per quad), conv2 groups of 2 k-steps
-// (32 fragments), conv3 groups of GS3 k-steps (2 NP GS3 fragments).  The canonical shallow levels (NG <= 5) take
-// GS1 = 5, GS3 = 4 (slots of 40 KB); wider inputs (NG = 9: level 2 of the canonical flow, the BAIR flow's level 0) need
-// the LDS for the input image and take GS1 = 3, GS3 = 2 (slots of 32 KB).
+// choice): NG1 = ceil(NS1 / GS1) conv1 groups per quad, as even as possible -- the first NS1 % NG1 of them one k-step
+// longer than the rest (11 = 4+4+3, 21 = 5+4+4+4+4, 41 = 13 x 3 + 2; 8 fragments per k-step) -- conv2 groups of 2
+// k-steps (32 fragments), conv3 groups of GS3 k-steps (2 NP GS3 fragments).  Every group is a multiple of 4 fragments:
+// the four waves issue the same number of DMA pieces.  The canonical shallow levels (NG <= 5) take GS1 = 5, GS3 = 4
+// (slots of 40 KB); wider inputs (NG = 9: level 2 of the canonical flow, the BAIR flow's level 0) need the LDS for the
+// input image and take GS1 = 3, GS3 = 2 (slots of 32 KB).
 __host__ __device__ constexpr int po_gs1(int NG) { return NG > 5 ? 3 : 5; }
 __host__ __device__ constexpr int po_gs3(int NP) { return NP > 3 ? 2 : 4; }
+__host__ __device__ constexpr int po_ng1(int NG, int NS1) { return (NS1 + po_gs1(NG) - 1) / po_gs1(NG); }
+// conv1 group gi of a quad: first k-step and k-steps
+__host__ __device__ constexpr int po_g1_first(int NG, int NS1, int gi) {
+    const int n = po_ng1(NG, NS1), rem = NS1 % n;
+    return gi * (NS1 / n) + (gi < rem ? gi : rem);
+}
+__host__ __device__ constexpr int po_g1_steps(int NG, int NS1, int gi) {
+    const int n = po_ng1(NG, NS1);
+    return NS1 / n + (gi < NS1 % n ? 1 : 0);
+}
 // group `idx` (0 .. 2 NG1 + 8 + 16 / GS3 - 1) of a round in consumption order: first fragment and fragment count
-__host__ __device__ constexpr int po_group_base(int NG, int NP, int idx) {
-    const int QF = NG * 40 + 128, GS1 = po_gs1(NG), NG1 = 5 * NG / GS1, F1 = 8 * GS1;
-    return idx < NG1 ? 1 + idx * F1
-         : idx < NG1 + 4 ? 1 + NG * 40 + (idx - NG1) * 32
-         : idx < 2 * NG1 + 4 ? 1 + QF + (idx - NG1 - 4) * F1
-         : idx < 2 * NG1 + 8 ? 1 + QF + NG * 40 + (idx - 2 * NG1 - 4) * 32
+__host__ __device__ constexpr int po_group_base(int NG, int NS1, int NP, int idx) {
+    const int QF = NS1 * 8 + 128, NG1 = po_ng1(NG, NS1);
+    return idx < NG1 ? 1 + 8 * po_g1_first(NG, NS1, idx)
+         : idx < NG1 + 4 ? 1 + NS1 * 8 + (idx - NG1) * 32
+         : idx < 2 * NG1 + 4 ? 1 + QF + 8 * po_g1_first(NG, NS1, idx - NG1 - 4)
+         : idx < 2 * NG1 + 8 ? 1 + QF + NS1 * 8 + (idx - 2 * NG1 - 4) * 32
          : 1 + 2 * QF + (idx - 2 * NG1 - 8) * 2 * NP * po_gs3(NP);
 }
 // positions of the haloed input image of a round on W x W maps (see the kernel)
 __host__ __device__ constexpr int po_image_positions(int W) {
     return W * W >= PO_ROUND_PX ? (PO_ROUND_PX / W + 2) * (W + 2) : (PO_ROUND_PX / (W * W)) * (W + 2) * (W + 2);
 }
-__host__ __device__ constexpr int po_slot_frags(int NG, int NP) {   // fragments (KB) per ring slot
-    const int f1 = 8 * po_gs1(NG), f3 = 2 * NP * po_gs3(NP);
+__host__ __device__ constexpr int po_slot_frags(int NG, int NS1, int NP) {   // fragments (KB) per ring slot
+    const int f1 = 8 * po_g1_steps(NG, NS1, 0), f3 = 2 * NP * po_gs3(NP);
     return (f1 > 32 ? f1 : 32) > f3 ? (f1 > 32 ? f1 : 32) : f3;
 }
-__host__ __device__ constexpr int po_group_size(int NG, int NP, int idx) {
-    const int GS1 = po_gs1(NG), NG1 = 5 * NG / GS1, F1 = 8 * GS1;
-    return idx < NG1 ? F1 : idx < NG1 + 4 ? 32 : idx < 2 * NG1 + 4 ? F1 : idx < 2 * NG1 + 8 ? 32 : 2 * NP * po_gs3(NP);
+__host__ __device__ constexpr int po_group_size(int NG, int NS1, int NP, int idx) {
+    const int NG1 = po_ng1(NG, NS1);
+    return idx < NG1 ? 8 * po_g1_steps(NG, NS1, idx) : idx < NG1 + 4 ? 32
+         : idx < 2 * NG1 + 4 ? 8 * po_g1_steps(NG, NS1, idx - NG1 - 4) : idx < 2 * NG1 + 8 ? 32 : 2 * NP * po_gs3(NP);
+}
+// dynamic LDS of an instantiation: three ring slots, parameters + reductions, the image, (backward) the channel sums
+__host__ __device__ constexpr long po_lds_bytes(int NG, int NS1, int NP, int W, bool bwd) {
+    return 3L * po_slot_frags(NG, NS1, NP) * 1024 + 4096 + 64 + 2L * NG * po_image_positions(W) * 16 +
+           (bwd ? PO_WAVES * 512 * 4 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------ weight stream
 // One fragment: lane (r = lane & 31, kk = lane >> 5) holds A[row r][8 k-values] of one plane of the scaled weights.
-//   conv1 tile a (a < 8), k-step s = tp*NG + g:   row = 32a + r, tap = 2tp + kk, element j <-> input channel 8g + j
-//       (zero beyond Cin / tap 9)                                                   value w1[row][ci][tap]
+//   conv1 tile a (a < 8), k-step s:   row = 32a + r, unit 2s + kk of po_order, element j <-> slot j of the unit
+//       (zero outside the unit's real taps / channels)                              value w1[row][ci][tap]
 //   conv2 tile a2, k-step s < 16:  row = 32a2 + r, element j <-> h1 channel 16s + 8(j>>2) + 4kk + (j&3)
 //       (the register order of an accumulator tile)                                value w2[row][c1]
 //   conv3 row tile jt, k-step s < 16:  row R = 32jt + r = tap*C + co (zero beyond 9C), element j <-> h2 channel
@@ -183,22 +267,20 @@ __global__ __launch_bounds__(256) void po_pack_fwd_kernel(const POPackDesc* __re
         float sc;
         if (k < n1) {
             const int a = k / g.NS1, s = k % g.NS1;
-            frag0 = 1 + (long)(a >> 2) * g.quad_frags + (s / 5) * 40 + ((s % 5) * 4 + (a & 3)) * 2;
+            frag0 = 1 + (long)(a >> 2) * g.quad_frags + (s * 4 + (a & 3)) * 2;
             sc = scw[0];
-            const int tp = s / g.NG, gg = s % g.NG, tap = 2 * tp + kk;
-            if (tap < 9) {
+            const POUnit q = po_unit(Cin, BWD, 2 * s + kk);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int ci = 8 * gg + j;
-                    if (ci < Cin)
-                        v[j] = BWD ? d.w3[((long)ci * PO_HD + (32 * a + r)) * 9 + (8 - tap)]
-                                   : d.w1[((long)(32 * a + r) * Cin + ci) * 9 + tap];
-                }
+            for (int j = 0; j < 8; ++j) {
+                const int t = j / q.w, c = j % q.w, tap = q.tap0 + t, ci = q.ch0 + c;
+                if (t < q.n_taps && c < q.n_ch)
+                    v[j] = BWD ? d.w3[((long)ci * PO_HD + (32 * a + r)) * 9 + (8 - tap)]
+                               : d.w1[((long)(32 * a + r) * Cin + ci) * 9 + tap];
             }
         } else if (k < n1 + n2) {
             k -= n1;
             const int a2 = k >> 4, s = k & 15;
-            frag0 = 1 + (long)(s >> 3) * g.quad_frags + g.NG * 40 + ((s & 7) >> 1) * 32 + ((s & 1) * 8 + a2) * 2;
+            frag0 = 1 + (long)(s >> 3) * g.quad_frags + g.NS1 * 8 + ((s & 7) >> 1) * 32 + ((s & 1) * 8 + a2) * 2;
             sc = scw[1];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -229,6 +311,37 @@ __global__ __launch_bounds__(256) void po_pack_fwd_kernel(const POPackDesc* __re
 
 extern "C" long rfn_coupling_po_packed_bytes(int Cin, int C) { return (long)po_geom(Cin, C).total_frags * 1024; }
 extern "C" long rfn_coupling_po_bwd_packed_bytes(int C) { return (long)po_geom(C, C, true).total_frags * 1024; }
+
+/* K order of the first product (po_order / po_unit above): the number of units for unit < 0, else the unit's real taps
+ * [tap0, tap0 + n_taps) and channels [ch0, ch0 + n_ch) and its k-step (unit / 2) as the return value */
+extern "C" int rfn_coupling_po_k_order(int Cin, int bwd, int unit, long long* tap0, long long* n_taps, long long* ch0,
+                                       long long* n_ch) {
+    RFN_CHECK_ARG(Cin > 0, -1);
+    const POOrder o = po_order(Cin, bwd != 0);
+    if (unit < 0) return o.n_units;
+    RFN_CHECK_ARG(unit < o.n_units && tap0 && n_taps && ch0 && n_ch, -2);
+    const POUnit q = po_unit(Cin, bwd != 0, unit);
+    *tap0 = q.tap0; *n_taps = q.n_taps; *ch0 = q.ch0; *n_ch = q.n_ch;
+    return unit / 2;
+}
+/* ring group idx of a round of the stream (po_group_base / po_group_size): first fragment and fragments (1 KB each;
+ * fragment 0 is the header); the number of groups for idx < 0.  C is not read for the backward stream. */
+extern "C" int rfn_coupling_po_ring_group(int Cin, int C, int bwd, int idx, long long* first_frag, long long* n_frags) {
+    RFN_CHECK_ARG(Cin > 0 && (bwd || C > 0), -1);
+    const POGeom g = po_geom(Cin, C, bwd != 0);
+    const int n = 2 * po_ng1(g.NG, g.NS1) + 8 + (bwd ? 0 : 16 / po_gs3(g.NP));
+    if (idx < 0) return n;
+    RFN_CHECK_ARG(idx < n && first_frag && n_frags, -2);
+    *first_frag = po_group_base(g.NG, g.NS1, g.NP, idx);
+    *n_frags = po_group_size(g.NG, g.NS1, g.NP, idx);
+    return 0;
+}
+/* dynamic LDS bytes of the instantiation that serves (Cin, C) on W x W maps (the launcher refuses more than 160 KB) */
+extern "C" long rfn_coupling_po_lds_bytes(int Cin, int C, int W, int bwd) {
+    RFN_CHECK_ARG(Cin > 0 && W > 0 && (bwd || C > 0), -1);
+    const POGeom g = po_geom(Cin, C, bwd != 0);
+    return po_lds_bytes(g.NG, g.NS1, g.NP, W, bwd != 0);
+}
 
 extern "C" int rfn_coupling_po_pack(const void* descs_device, int n, rfn_stream_t stream) {
     RFN_CHECK_ARG(descs_device && n >= 0, -1);
@@ -361,8 +474,15 @@ __device__ __forceinline__ int po_exp_of(const float m) {
 // the 637 MB activations are not read here at all; per-channel sums of ga2 / ga1 (ActNorm bias gradients) leave as
 // per-workgroup partial rows.  Parameter roles in BWD: z = go (Ch = C, Cc = 0), n1l = l2, n2l = l1, h1 = ga2, h2 = ga1,
 // m1 = mask of h2, m2 = mask of h1.
-template <int NG, int NP, int LOGW, int ACT, bool BWD>
+// RP: slot width of the narrow leftover units (po_order; 0: every image group forms full units)
+template <int NG, int NP, int LOGW, int ACT, bool BWD, int RP>
 __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const POFwdParams p) {
+    // the K order of the first product: a representative channel count of this instantiation names its units
+    constexpr int CREP = RP ? 8 * (NG - 1) + RP : 8 * NG;
+    constexpr POOrder ORD = po_order(CREP, BWD);
+    static_assert(ORD.NG == NG && ORD.RP == RP, "instantiation outside po_order");
+    static_assert(RP == 0 || (9 * ORD.NGT) % 2 == 0, "a k-step is two full or two leftover units");
+    constexpr int NS1 = ORD.NS1;
     // square maps of side W = 2^LOGW.  A round is 128 consecutive pixels: 128 / W image rows of one frame (H W >= 128) or
     // FPR = 128 / (H W) whole frames (8x8 maps: two).  Its haloed image: per frame part (RROWS + 2) rows of IW columns.
     constexpr int W = 1 << LOGW, HW = W * W, IW = W + 2;
@@ -371,20 +491,23 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
     constexpr int FPOS = (RROWS + 2) * IW, IPOS = FPR * FPOS;
     constexpr int PO_ITEMS = (NG * IPOS + 64 * PO_WAVES - 1) / (64 * PO_WAVES);   // staging items per thread
     constexpr int RPF_SHIFT = HW >= PO_ROUND_PX ? 2 * LOGW - 7 : 0;   // log2(rounds per frame)
-    constexpr int GS1 = po_gs1(NG), NG1 = 5 * NG / GS1;   // conv1: k-steps per ring group, groups per quad
+    constexpr int GS1 = po_gs1(NG), NG1 = po_ng1(NG, NS1);   // conv1: most k-steps per ring group, groups per quad
     constexpr int GS3 = po_gs3(NP), NG3 = 16 / GS3;       // conv3: k-steps per ring group, groups
-    constexpr bool RT = NG > 5;   // conv1 as run-time loops over channel groups inside the (unrolled) tap pairs
+    constexpr bool RT = NG > 5;   // conv1 as run-time loops over ring groups inside the (unrolled) tap pairs
     // The next round's image is loaded one quad ahead into registers (8 PO_ITEMS of them) -- where the register file has
     // room.  The wide instantiations are at the 512-register limit without them (scratch spills otherwise) and load the
     // image when its LDS buffer is free, right before converting it: the tensors were written by the launch before this
     // one and come from L2 / the Infinity Cache.
     constexpr bool LATE = RT || (BWD && NG > 1);
     constexpr bool NOHOIST = LATE || NG == 5;   // staging decomposition recomputed every round (registers, see stage_load)
-    static_assert((5 * NG) % GS1 == 0 && (!RT || NG % GS1 == 0), "conv1 grouping");
+    // RT: a tap pair is 2 NG units = NG k-steps = NG / GS1 whole ring groups; the ninth tap alone ends in a short group
+    static_assert(!RT || (RP == 0 && NG % GS1 == 0 && NG1 == 4 * (NG / GS1) + (NG / 2 + GS1) / GS1 &&
+                          po_g1_steps(NG, NS1, NG1 - 2) == GS1), "conv1 grouping");
     constexpr int G3 = 2 * NP * GS3;           // fragments per conv3 group
-    constexpr int Y1 = 2 * GS1, Y3 = G3 / 4;   // LDS-DMA instructions per wave of a conv1 / conv3 group (conv2: 8)
+    // LDS-DMA instructions per wave of the first conv1 group of a quad / of a conv3 group (conv2: 8)
+    constexpr int Y1 = 2 * po_g1_steps(NG, NS1, 0), Y3 = G3 / 4;
     static_assert(G3 % 4 == 0, "a group's fragments are shared evenly by the four waves");
-    constexpr int SLOTF = po_slot_frags(NG, NP);
+    constexpr int SLOTF = po_slot_frags(NG, NS1, NP);
     constexpr int SLOT = SLOTF * 1024;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int NGRP = 2 * NG1 + 8 + (BWD ? 0 : NG3);                    // weight groups per round
@@ -396,6 +519,7 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, kk = lane >> 5;
     const int Cin = p.Ch + p.Cc;
+    const POOrder ordr = po_order(Cin, BWD);   // (the launcher chose this instantiation by it: ordr.RP == RP)
     constexpr unsigned ch_bytes = (unsigned)HW * 4u;
 
     for (int c = tid; c < 256; c += 64 * PO_WAVES) {
@@ -437,8 +561,8 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
         const int free_slot = sl;                                                                          \
         sl = sl == 2 ? 0 : sl + 1;                                                                         \
         const int n2_ = (IDX) + 2;                                                                         \
-        if (n2_ < NGRP) dma(po_group_base(NG, NP, n2_), po_group_size(NG, NP, n2_), free_slot);            \
-        else if (more) dma(po_group_base(NG, NP, n2_ - NGRP), po_group_size(NG, NP, n2_ - NGRP), free_slot); \
+        if (n2_ < NGRP) dma(po_group_base(NG, NS1, NP, n2_), po_group_size(NG, NS1, NP, n2_), free_slot);            \
+        else if (more) dma(po_group_base(NG, NS1, NP, n2_ - NGRP), po_group_size(NG, NS1, NP, n2_ - NGRP), free_slot); \
     } while (0)
 
     const auto rs_h1 = __builtin_amdgcn_make_buffer_rsrc(p.h1, 0, 0xFFFFFFFFu, 0x00020000);
@@ -466,10 +590,10 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
             const int off = ok ? gy * W + gx : 0;
             const float* zb = p.z + (long)(n0_ + fr) * p.z_ns;
             const float* cb = p.cond + (long)(n0_ + fr) * p.cond_ns;
+            const int c0 = po_group_ch0(ordr, g), nc = po_group_nch(ordr, Cin, g);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const int ci = 8 * g + j;
-                const int cc = ci < Cin ? ci : 0;
+                const int cc = j < nc ? c0 + j : 0;
                 const float* src = cc < p.Ch ? zb + (long)cc * HW : cb + (long)(cc - p.Ch) * HW;
                 raw[it][j] = src[off];   // (masked in stage_finish: no use of the value here, the load stays in flight)
             }
@@ -490,9 +614,10 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
             const int iy = rem / IW, ix = rem - iy * IW;
             const int gy = y0_ - 1 + iy, gx = ix - 1;
             const bool ok = live && gy >= 0 && gy < W && gx >= 0 && gx < W;
+            const int nc = po_group_nch(ordr, Cin, g);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                raw[it][j] = (ok && 8 * g + j < Cin) ? raw[it][j] : 0.f;
+                raw[it][j] = (ok && j < nc) ? raw[it][j] : 0.f;
                 vm = fmaxf(vm, fabsf(raw[it][j]));
             }
         }
@@ -523,8 +648,8 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
     if (round < p.n_rounds) {
         const bool more = true;
         (void)more;
-        dma(po_group_base(NG, NP, 0), po_group_size(NG, NP, 0), 0);
-        dma(po_group_base(NG, NP, 1), po_group_size(NG, NP, 1), 1);
+        dma(po_group_base(NG, NS1, NP, 0), po_group_size(NG, NS1, NP, 0), 0);
+        dma(po_group_base(NG, NS1, NP, 1), po_group_size(NG, NS1, NP, 1), 1);
         stage_load(round);
         stage_finish(round);
     }
@@ -538,16 +663,41 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
         const int y0 = FPR > 1 ? 0 : ((round & ((1 << RPF_SHIFT) - 1)) * PO_ROUND_PX) >> LOGW;
         const float u1 = u1_next;
 
-        // its five tap-pair positions inside the image (lane half = tap of the pair)
+        // its pixel inside the image (centre tap, group 0, plane hi): every unit's B fragment lies at an offset from it
+        // that is a constant of the k-step and the lane half
         const int iy = (pix >> LOGW) - y0 + 1, ix = (pix & (W - 1)) + 1;
-        const f16x8* bp[PO_TAP_PAIRS];
+        const f16x8* pc = img + fr * FPOS + iy * IW + ix;
+        // B fragment (plane pl) of this lane's unit of k-step s (a constant once the callers' loops are unrolled).  Full
+        // units: one 16-byte read.  Narrow leftover units: 8 / RP reads of RP channels, one per tap of the unit, from the
+        // haloed leftover group (the last image group; its upper channels are not read).  Zero-weight slots (padding
+        // unit, taps beyond the ninth) read the centre tap: finite data.
+        auto load_b = [&](const int s, const int pl) __attribute__((always_inline)) -> f16x8 {
+            const POUnit qa = po_unit(CREP, BWD, 2 * s), qb = po_unit(CREP, BWD, 2 * s + 1);
+            // (the selects below are constants of the lane: computed where they are used, not kept in 2 NS1 registers
+            // across the rounds)
+            int kk = lane >> 5;
+            asm volatile("" : "+v"(kk));
+            if (RP == 0 || 2 * s < 9 * ORD.NGT) {
+                const int oa = po_tap_off(qa.tap0, IW) + (pl * NG + qa.g) * IPOS;
+                const int ob = po_tap_off(qb.tap0, IW) + (pl * NG + qb.g) * IPOS;
+                return pc[oa + kk * (ob - oa)];
+            }
+            constexpr int WB = RP ? RP : 8, T = 8 / WB;
+            const unsigned char* base = reinterpret_cast<const unsigned char*>(pc + (pl * NG + NG - 1) * IPOS);
+            u32x4 d;
 #pragma unroll
-        for (int tp = 0; tp < PO_TAP_PAIRS; ++tp) {
-            const int tA = 2 * tp, tB = 2 * tp + 1 < 9 ? 2 * tp + 1 : 4;   // the padding tap reads the centre (zero weight)
-            const int dy = kk ? (tB / 3 - 1) : (tA / 3 - 1);
-            const int dx = kk ? (tB % 3 - 1) : (tA % 3 - 1);
-            bp[tp] = img + fr * FPOS + (iy + dy) * IW + ix + dx;
-        }
+            for (int t = 0; t < T; ++t) {
+                const int oa = 16 * po_tap_off(t < qa.n_taps ? qa.tap0 + t : 4, IW);
+                const int ob = 16 * po_tap_off(t < qb.n_taps ? qb.tap0 + t : 4, IW);
+                if (WB == 4) {
+                    const uint2 v = *reinterpret_cast<const uint2*>(base + (kk ? ob : oa));
+                    d[(2 * t) & 3] = v.x; d[(2 * t + 1) & 3] = v.y;
+                } else {
+                    d[t & 3] = *reinterpret_cast<const unsigned*>(base + (kk ? ob : oa));
+                }
+            }
+            return __builtin_bit_cast(f16x8, d);
+        };
         // byte offset of (frame n, channel 4kk, this pixel) in h1 / h2 (both [N,256,H,W] with frame strides h*_ns)
         const unsigned vo1 = (unsigned)(((long)n * p.h1_ns + (long)(4 * kk) * HW + pix) * 4);
         const unsigned vo2 = (unsigned)(((long)n * p.h2_ns + (long)(4 * kk) * HW + pix) * 4);
@@ -598,16 +748,23 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
                 __builtin_amdgcn_sched_barrier(0);                                                         \
             } while (0)
             if constexpr (!RT) {
+            // ring groups of KA or KB k-steps (po_g1_steps: the longer ones first)
+            constexpr int KA = po_g1_steps(NG, NS1, 0), KB = po_g1_steps(NG, NS1, NG1 - 1);
 #pragma unroll
             for (int gi = 0; gi < NG1; ++gi) {
-                // younger than this group's DMA: the DMA of the next group (Y1 / 8 instructions per wave)
+                const int s0 = po_g1_first(NG, NS1, gi), KN = po_g1_steps(NG, NS1, gi);
+                // younger than this group's DMA: the DMA of the group issued after it -- two instructions per wave and
+                // k-step of the next conv1 group (KA or KB k-steps), 8 of conv2's first
                 // (+ the 8 PO_ITEMS image loads of the next round while they are in flight: quad 1, first two groups)
+                const bool lastg = gi + 1 == NG1, nextA = !lastg && po_g1_steps(NG, NS1, gi + 1) == KA;
                 if (u == 1 && gi < 2 && more && !LATE) {
-                    if (gi + 1 < NG1) PO_BOUNDARY(u * (NG1 + 4) + gi, Y1 + 8 * PO_ITEMS);
-                    else PO_BOUNDARY(u * (NG1 + 4) + gi, 8 + 8 * PO_ITEMS);
+                    if (lastg) PO_BOUNDARY(u * (NG1 + 4) + gi, 8 + 8 * PO_ITEMS);
+                    else if (nextA) PO_BOUNDARY(u * (NG1 + 4) + gi, 2 * KA + 8 * PO_ITEMS);
+                    else PO_BOUNDARY(u * (NG1 + 4) + gi, 2 * KB + 8 * PO_ITEMS);
                 } else {
-                    if (gi + 1 < NG1) PO_BOUNDARY(u * (NG1 + 4) + gi, Y1);
-                    else PO_BOUNDARY(u * (NG1 + 4) + gi, 8);
+                    if (lastg) PO_BOUNDARY(u * (NG1 + 4) + gi, 8);
+                    else if (nextA) PO_BOUNDARY(u * (NG1 + 4) + gi, 2 * KA);
+                    else PO_BOUNDARY(u * (NG1 + 4) + gi, 2 * KB);
                 }
                 const f16x8* fr = reinterpret_cast<const f16x8*>(lds + sl * SLOT) + lane;
                 f16x8 A[2][4][2], B[2][2];
@@ -617,43 +774,59 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
                     A[0][t][1] = fr[(t * 2 + 1) * 64];
                 }
 #pragma unroll
-                for (int pl = 0; pl < 2; ++pl) B[0][pl] = bp[(GS1 * gi) / NG][(pl * NG + (GS1 * gi) % NG) * IPOS];
+                for (int pl = 0; pl < 2; ++pl) B[0][pl] = load_b(s0, pl);
 #pragma unroll
                 for (int k = 0; k < GS1; ++k) {
-                    const int s = GS1 * gi + k, cur = k & 1, nxt = cur ^ 1;
-                    PO_C1_STEP(k + 1 == GS1, k + 1, bp[(s + 1) / NG][(pl * NG + (s + 1) % NG) * IPOS]);
+                    if (k < KN) {
+                        const int s = s0 + k, cur = k & 1, nxt = cur ^ 1;
+                        PO_C1_STEP(k + 1 == KN, k + 1, load_b(s + 1, pl));
+                    }
                 }
             }
             } else {
-            // wide inputs: k-step s = tp * NG + g with the tap pairs unrolled and the channel groups of a tap pair in a
-            // run-time loop over ring groups of GS1 (a fully unrolled round is 10 NG k-steps with compile-time
-            // addresses: at NG = 9 hipcc spills hundreds of SGPRs and its AGPR pass fails)
+            // wide inputs (every group full, RP = 0): the units of a tap pair are 2 NG consecutive ones = NG k-steps = NG / GS1
+            // whole ring groups, run in a run-time loop inside the unrolled tap pairs; the ninth tap alone is NG units =
+            // one ring group of GS1 k-steps and a short last one (a fully unrolled round is 9 NG k-steps with
+            // compile-time addresses: at NG = 9 hipcc spills hundreds of SGPRs and its AGPR pass fails).
+            // Unit uu = 2 j + kk of the pair (j = k-step of the pair): tap 2 tp, group uu, or, from uu = NG on, tap
+            // 2 tp + 1, group uu - NG (ninth tap: the padding unit, which reads group 0).
+            auto c1_group = [&](const int tp, const int gg, const int KN) __attribute__((always_inline)) {
+                const int gidx = u * (NG1 + 4) + tp * (NG / GS1) + gg;   // ring group of the round
+                // younger: the next group's DMA: 2 GS1 instructions, fewer before the short last group, 8 after it (conv2)
+                // (wide kernels load the next image late: no image loads in flight here)
+                if (tp < 4) PO_BOUNDARY(gidx, 2 * GS1);
+                else if (KN == GS1) PO_BOUNDARY(gidx, 2 * po_g1_steps(NG, NS1, NG1 - 1));
+                else PO_BOUNDARY(gidx, 8);
+                const f16x8* fr = reinterpret_cast<const f16x8*>(lds + sl * SLOT) + lane;
+                const f16x8* pa = pc + po_tap_off(2 * tp, IW);
+                const int dsel = (tp < 4 ? po_tap_off(2 * tp + 1, IW) - po_tap_off(2 * tp, IW) : 0) - NG * IPOS;
+                const int u0 = 2 * GS1 * gg + kk;
+                auto b_at = [&](const int k, const int pl) __attribute__((always_inline)) -> f16x8 {
+                    const int uu = u0 + 2 * k;
+                    return pa[(pl * NG + uu) * IPOS + (uu >= NG ? dsel : 0)];
+                };
+                f16x8 A[2][4][2], B[2][2];
 #pragma unroll
-            for (int tp = 0; tp < PO_TAP_PAIRS; ++tp) {
-#pragma unroll 1
-                for (int gg = 0; gg < NG / GS1; ++gg) {
-                    const int gq = tp * (NG / GS1) + gg;          // ring group of the quad
-                    const int gidx = u * (NG1 + 4) + gq;          // ring group of the round
-                    // younger: the next group's DMA (at least Y1 instructions) -- and, in quad 1, the image loads of the
-                    // next round, issued before its first group and still in flight during its first two
-                    if (u == 1 && tp == 0 && gg < 2 && more && !LATE) PO_BOUNDARY(gidx, Y1 + 8 * PO_ITEMS);
-                    else PO_BOUNDARY(gidx, Y1);
-                    const f16x8* fr = reinterpret_cast<const f16x8*>(lds + sl * SLOT) + lane;
-                    const f16x8* bq = bp[tp] + (GS1 * gg) * IPOS;   // channel group GS1 gg of this tap pair, plane hi
-                    f16x8 A[2][4][2], B[2][2];
+                for (int t = 0; t < 4; ++t) {
+                    A[0][t][0] = fr[(t * 2) * 64];
+                    A[0][t][1] = fr[(t * 2 + 1) * 64];
+                }
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        A[0][t][0] = fr[(t * 2) * 64];
-                        A[0][t][1] = fr[(t * 2 + 1) * 64];
-                    }
+                for (int pl = 0; pl < 2; ++pl) B[0][pl] = b_at(0, pl);
 #pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) B[0][pl] = bq[(pl * NG) * IPOS];
-#pragma unroll
-                    for (int k = 0; k < GS1; ++k) {
+                for (int k = 0; k < GS1; ++k) {
+                    if (k < KN) {
                         const int cur = k & 1, nxt = cur ^ 1;
-                        PO_C1_STEP(k + 1 == GS1, k + 1, bq[(pl * NG + k + 1) * IPOS]);
+                        PO_C1_STEP(k + 1 == KN, k + 1, b_at(k + 1, pl));
                     }
                 }
+            };
+#pragma unroll
+            for (int tp = 0; tp < 5; ++tp) {
+                const int nfull = tp < 4 ? NG / GS1 : (NG + 1) / 2 / GS1;   // whole ring groups of the pair
+#pragma unroll 1
+                for (int gg = 0; gg < nfull; ++gg) c1_group(tp, gg, GS1);
+                if (tp == 4 && (NG + 1) / 2 % GS1) c1_group(tp, nfull, (NG + 1) / 2 % GS1);
             }
             }
 #undef PO_C1_STEP
@@ -870,31 +1043,40 @@ __global__ __launch_bounds__(64 * PO_WAVES) void coupling_po_fwd_kernel(const PO
     }
 }
 
-template <int NG, int NP, int LOGW, int ACT, bool BWD>
+template <int NG, int NP, int LOGW, int ACT, bool BWD, int RP>
 static int launch_po_fwd_t(const POFwdParams& p, hipStream_t s) {
-    constexpr int SLOTF = po_slot_frags(NG, NP);
     constexpr int W = 1 << LOGW, IPOS = po_image_positions(W);
-    const size_t ldsz = (size_t)3 * SLOTF * 1024 + 4096 + 64 + (size_t)2 * NG * IPOS * 16 + (BWD ? PO_WAVES * 512 * 4 : 0);
+    constexpr int NS1 = po_order(RP ? 8 * (NG - 1) + RP : 8 * NG, BWD).NS1;
+    constexpr size_t ldsz = (size_t)po_lds_bytes(NG, NS1, NP, W, BWD);
     if (ldsz > 160 * 1024 || IPOS != p.IPOS) {
         rfn_set_error("coupling_po: %zu bytes of LDS / %d image positions (expected %d)", ldsz, p.IPOS, IPOS);
         return -5;
     }
-    auto kern = coupling_po_fwd_kernel<NG, NP, LOGW, ACT, BWD>;
+    auto kern = coupling_po_fwd_kernel<NG, NP, LOGW, ACT, BWD, RP>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz);
     const int grid = p.n_rounds < 256 ? p.n_rounds : 256;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * PO_WAVES), ldsz, s, p);
     return 0;
 }
 
-template <int NG, int NP, int LOGW, bool BWD = false>
+template <int NG, int NP, int LOGW, bool BWD, int RP>
+static int launch_po_fwd_r(const POFwdParams& p, hipStream_t s) {
+    if (p.act == 1) return launch_po_fwd_t<NG, NP, LOGW, 1, BWD, RP>(p, s);
+    if (p.act == 2) return launch_po_fwd_t<NG, NP, LOGW, 2, BWD, RP>(p, s);
+    return launch_po_fwd_t<NG, NP, LOGW, 0, BWD, RP>(p, s);
+}
+// NRP: the narrow leftover width this group count has an instantiation for (po_narrow), taken when po_order names it
+template <int NG, int NP, int LOGW, bool BWD = false, int NRP = 0>
 static int launch_po_fwd(const POFwdParams& p, hipStream_t s) {
-    if (p.act == 1) return launch_po_fwd_t<NG, NP, LOGW, 1, BWD>(p, s);
-    if (p.act == 2) return launch_po_fwd_t<NG, NP, LOGW, 2, BWD>(p, s);
-    return launch_po_fwd_t<NG, NP, LOGW, 0, BWD>(p, s);
+    static_assert(NRP == 0 || po_narrow(NG, NRP, BWD), "narrow instantiation outside po_narrow");
+    if (NRP != 0 && po_order(p.Ch + p.Cc, BWD).RP == NRP) return launch_po_fwd_r<NG, NP, LOGW, BWD, NRP>(p, s);
+    if (po_order(p.Ch + p.Cc, BWD).RP != 0) return -4;
+    return launch_po_fwd_r<NG, NP, LOGW, BWD, 0>(p, s);
 }
 
 // instantiations of the forward kernel: (channel groups of conv1's input, row tiles of the tap-expanded conv3, map side)
-//   (3, 2, 32) / (5, 3, 16)   levels 0 / 1 of the canonical flow (Cin 18 / 36, C 4 / 8)
+//   (3, 2, 32) / (5, 3, 16)   levels 0 / 1 of the canonical flow (Cin 18 / 36, C 4 / 8): with the narrow leftover units
+//                             of po_order for Cin 17..18 / 35..36, without for the other channel counts
 //   (9, 5, 8)                 level 2 of the canonical flow (Cin 72, C 16): two frames per round
 //   (9, 4, 32)                level 0 of the BAIR-shaped flow (C = 12, Cin 65..72: 6 + 64 `with_skip` condition channels)
 static bool po_fwd_instance(int NG, int NP, int W) {
@@ -954,8 +1136,8 @@ extern "C" int rfn_coupling_po_fwd(const float* z, long z_ns, const float* cond,
     po_fill_geometry(p, N, C, H, W, act);
     const POGeom g = po_geom(p.Ch + Cc, C);
     int rc = -4;
-    if (g.NG == 3 && g.NP == 2 && W == 32) rc = launch_po_fwd<3, 2, 5>(p, (hipStream_t)stream);
-    if (g.NG == 5 && g.NP == 3 && W == 16) rc = launch_po_fwd<5, 3, 4>(p, (hipStream_t)stream);
+    if (g.NG == 3 && g.NP == 2 && W == 32) rc = launch_po_fwd<3, 2, 5, false, 2>(p, (hipStream_t)stream);
+    if (g.NG == 5 && g.NP == 3 && W == 16) rc = launch_po_fwd<5, 3, 4, false, 4>(p, (hipStream_t)stream);
     if (g.NG == 9 && g.NP == 5 && W == 8) rc = launch_po_fwd<9, 5, 3>(p, (hipStream_t)stream);
     if (g.NG == 9 && g.NP == 4 && W == 32) rc = launch_po_fwd<9, 4, 5>(p, (hipStream_t)stream);
     if (rc) return rc;
@@ -1003,8 +1185,8 @@ extern "C" int rfn_coupling_po_bwd(const float* go, long go_ns, const void* wpk,
     po_fill_geometry(p, N, C, H, W, act);
     int rc = -4;
     const int NGb = (C + 7) / 8;
-    if (NGb == 1 && W == 32) rc = launch_po_fwd<1, 0, 5, true>(p, (hipStream_t)stream);
-    if (NGb == 1 && W == 16) rc = launch_po_fwd<1, 0, 4, true>(p, (hipStream_t)stream);
+    if (NGb == 1 && W == 32) rc = launch_po_fwd<1, 0, 5, true, 4>(p, (hipStream_t)stream);
+    if (NGb == 1 && W == 16) rc = launch_po_fwd<1, 0, 4, true, 4>(p, (hipStream_t)stream);
     if (NGb == 2 && W == 8) rc = launch_po_fwd<2, 0, 3, true>(p, (hipStream_t)stream);
     if (NGb == 2 && W == 32) rc = launch_po_fwd<2, 0, 5, true>(p, (hipStream_t)stream);
     if (rc) return rc;
