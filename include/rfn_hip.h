@@ -757,6 +757,26 @@ int rfn_adam_step_guarded_f32(const rfn_adam_entry* table, const int* chunks, in
                               double beta2, double eps, double weight_decay, int t, const float* stats,
                               long long* skipped, rfn_stream_t stream);
 
+/* ---- Polyak average (EMA) of the weights inside the Adam launch.  rfn_adam_ema_step_f32 / rfn_adam_ema_step_guarded_f32
+ * are rfn_adam_step_f32 / rfn_adam_step_guarded_f32 plus `ema_decay` d in [0, 1) and `ema`, a DEVICE array of one device
+ * pointer per table entry (ema[i] has table[i].n floats).  With n = that tensor's count of APPLIED steps (the s of the bias
+ * corrections: t - step_offset, minus *skipped in the guarded kernel), after the update has produced p_new:
+ *   d_n = min(d, (1 + n) / (10 + n))   in double;   w = (float)(1 - d_n);   ema <- fmaf(w, p_new - ema, ema)   in fp32.
+ * p, m, v receive the bits the kernel without the average gives on the same inputs.  The 16-byte path needs ema[i]
+ * aligned like p, g, m, v; otherwise the chunk takes the scalar loop (same arithmetic).  A step the guard skips writes
+ * nothing to ema.  ema_decay outside [0, 1) or a NULL `ema` is refused (-3 / -1) and nothing is launched.
+ *
+ * rfn_param_swap_f32: one launch over the same table and chunk list that exchanges p and ema element-wise (bit-exact
+ * moves: two launches are the identity).  g, m, v are not touched. */
+int rfn_adam_ema_step_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, int t, double ema_decay, float* const* ema,
+                          rfn_stream_t stream);
+int rfn_adam_ema_step_guarded_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1,
+                                  double beta2, double eps, double weight_decay, int t, const float* stats,
+                                  long long* skipped, double ema_decay, float* const* ema, rfn_stream_t stream);
+int rfn_param_swap_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, float* const* ema,
+                       rfn_stream_t stream);
+
 /* ---- video-prediction quality of uint8 frames  (evaluation_metrics/error_metrics.py:154-171, Evaluator.eval_seq: skimage
  * 0.17.2 `structural_similarity` / `peak_signal_noise_ratio` per channel, with their defaults on uint8: 7x7 uniform window,
  * data_range 255, K1 = 0.01, K2 = 0.03, sample covariance (x 49/48), S map averaged over the interior (H-6) x (W-6)).

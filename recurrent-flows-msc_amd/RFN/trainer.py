@@ -6,6 +6,7 @@ with zlib: pixels only, no matplotlib, no titles, no loss-curve panel; `--plot_e
 epoch (default: never).  A synthetic SM-MNIST-shaped loader is built in (`--synthetic_data`); otherwise the dataset lives on the GPU: Stochastic Moving MNIST is rendered from local
 MNIST files (`--choose_data mnist`, data_generators/moving_mnist.py), BAIR push and KTH clips are gathered from their
 packed frames (`bair`, `kth`; data_generators/clips.py).  Multi-GPU = one process per GPU (rfn_hip/dist.py)."""
+import contextlib
 import math
 import os
 
@@ -64,6 +65,10 @@ class Solver(object):
         self.guard_on = self.grad_clip_norm > 0.0 or self.skip_nonfinite_steps
         self._host_guard = {"grad_norm": 0.0, "scale": 1.0, "skipped_steps": 0}   # CPU parameters only
         self._guard_last, self._skipped_before_epoch = None, 0
+        # Polyak average of the weights (0 = off; Namespaces saved before the flag existed do not have it)
+        self.ema_decay = float(getattr(args, "ema_decay", 0.0) or 0.0)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("--ema_decay must be in [0, 1) (0 = no average), got %r" % (self.ema_decay,))
         self.rank = int(os.environ.get("RANK", 0))
         self.world = int(os.environ.get("WORLD_SIZE", 1))
         self.device = set_gpu(True)
@@ -86,7 +91,8 @@ class Solver(object):
         self.model = self.make_model().to(self.device)
         rdist.broadcast_module_state(self.model)
         self.reducer = rdist.GradBucketReducer(list(self.model.named_parameters()))
-        self.optimizer = self.make_optimizer(self.model.parameters(), self.learning_rate, **self.guard_kwargs())
+        self.optimizer = self.make_optimizer(self.model.parameters(), self.learning_rate, **self.guard_kwargs(),
+                                             ema_decay=self.ema_decay)
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, "min", patience=self.patience_lr,
                                                                     factor=self.factor_lr, min_lr=self.min_lr)
         self.earlystopping = EarlyStopping(min_delta=0, patience=self.patience_es, verbose=self.verbose)
@@ -102,17 +108,30 @@ class Solver(object):
                     rank_local=tuple(self.reducer.sharded))
 
     @staticmethod
-    def make_optimizer(params, lr, max_grad_norm=0.0, skip_nonfinite=False, rank_local=(), group=None):
+    def make_optimizer(params, lr, max_grad_norm=0.0, skip_nonfinite=False, rank_local=(), group=None, ema_decay=0.0):
         """RFN/trainer.py:96: Adam with torch's defaults.  On the GPU the whole update is one launch of the HIP kernel
         (rfn_hip.optim.HipAdam, same state layout as torch.optim.Adam) and the guard, when asked for, runs in front of it
         on the device; CPU parameters only occur in host-logic tests, where torch.optim.Adam steps and
-        `Solver.optimizer_step` guards it with a few torch ops."""
+        `Solver.optimizer_step` guards it with a few torch ops.  `ema_decay` > 0 keeps the Polyak average of the weights
+        in state[p]["ema"]: inside HipAdam's launch, or (CPU parameters) by `Solver.optimizer_step`."""
+        ema_decay = float(ema_decay)
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError("ema_decay must be in [0, 1) (0 = no average), got %r" % (ema_decay,))
         params = list(params)
         if params and params[0].is_cuda:
             from rfn_hip.optim import HipAdam
             return HipAdam(params, lr=lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
-                           rank_local=rank_local, group=group)
-        return torch.optim.Adam(params, lr=lr)
+                           rank_local=rank_local, group=group, ema_decay=ema_decay)
+        opt = torch.optim.Adam(params, lr=lr)
+        if ema_decay > 0.0:
+            opt.ema_decay = ema_decay   # (what rfn_hip.dist reads to treat "ema" like the moments)
+        return opt
+
+    @staticmethod
+    def ema_step_decay(decay, n):
+        """d_n of a tensor's n-th applied step: the warm-up min(d, (1 + n) / (10 + n)) keeps the first averages from
+        being dominated by the initial weights"""
+        return min(float(decay), (1.0 + n) / (10.0 + n))
 
     def create_loaders(self):
         if not getattr(self.args, "synthetic_data", False):
@@ -239,8 +258,10 @@ class Solver(object):
         parameters the same semantics in torch ops: global norm with the rank-local part summed over ranks, skip when
         it is not finite (an fp32 overflow of the sum of squares counts), scale by min(1, max / (norm + 1e-6))."""
         opt = self.optimizer
-        if not self.guard_on or hasattr(opt, "guard_stats"):
+        if hasattr(opt, "guard_stats"):
             return opt.step()
+        if not self.guard_on:
+            return self._host_adam_step()
         grads = [p.grad for g in opt.param_groups for p in g["params"] if p.grad is not None]
         local = {id(p.grad) for p in self.reducer.sharded if p.grad is not None}
         sq = torch.zeros(2, dtype=torch.float64)
@@ -257,7 +278,53 @@ class Solver(object):
             return None
         if scale != 1.0:
             torch._foreach_mul_(grads, scale)
-        return opt.step()
+        return self._host_adam_step()
+
+    def _host_adam_step(self):
+        """an applied step of torch.optim.Adam on CPU parameters and, with --ema_decay, HipAdam's average in torch ops:
+        state[p]["ema"] starts as the parameter before its first update, then ema += w (p_new - ema) with
+        w = float32(1 - d_n), n the tensor's own step count"""
+        opt = self.optimizer
+        if not self.ema_decay > 0.0:
+            return opt.step()
+        with torch.no_grad():
+            stepped = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
+            # (torch's Adam creates its state where the state is empty: the first copies wait until it has)
+            fresh = {p: p.detach().clone() for p in stepped if "ema" not in opt.state.get(p, ())}
+            out = opt.step()
+            for p in stepped:
+                st = opt.state[p]
+                ema = st.setdefault("ema", fresh.get(p))
+                w = float(np.float32(1.0 - self.ema_step_decay(self.ema_decay, int(float(st["step"])))))
+                ema.add_(p.detach() - ema, alpha=w)
+        return out
+
+    # ---------------------------------------------------------------------------------------------- average
+    def swap_ema(self):
+        """exchange parameters and averages (HipAdam: one launch; CPU parameters: torch copies)"""
+        opt = self.optimizer
+        if not self.ema_decay > 0.0:
+            raise RuntimeError("swap_ema: this run keeps no average (--ema_decay 0)")
+        if hasattr(opt, "swap_ema"):
+            return opt.swap_ema()
+        with torch.no_grad():
+            for g in opt.param_groups:
+                for p in g["params"]:
+                    ema = opt.state.get(p, {}).get("ema")
+                    if ema is not None:
+                        tmp = p.detach().clone()
+                        p.copy_(ema)
+                        ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """context manager: the model holds the averaged weights inside, the raw ones again outside (also when the body
+        raises).  Buffers are not averaged.  Nothing may step the optimizer inside."""
+        self.swap_ema()
+        try:
+            yield self.model
+        finally:
+            self.swap_ema()
 
     def guard_stats(self):
         """{"grad_norm", "scale", "skipped_steps"}: one device->host read with HipAdam"""
@@ -483,8 +550,10 @@ class Solver(object):
                 image = next(iter(self.test_loader))
                 image = image[0] if self.choose_data == "bair" and isinstance(image, (list, tuple)) else image
                 image = self.preprocess(image.to(self.device))
-                sheet = ops.compose_sheet(self._plot_rows(image), self.n_frames, n_bits=self.n_bits,
-                                          preprocess_range=self.preprocess_range, scanlines=True)
+                # with --ema_decay the sheet shows the averaged weights (swapped in and out again: bit-exact moves)
+                with self.ema_weights() if self.ema_decay > 0.0 else contextlib.nullcontext():
+                    sheet = ops.compose_sheet(self._plot_rows(image), self.n_frames, n_bits=self.n_bits,
+                                              preprocess_range=self.preprocess_range, scanlines=True)
             path = self.path + "png_folder/samples%d.png" % self.plot_counter
             write_png(path, sheet)
         finally:
@@ -499,7 +568,9 @@ class Solver(object):
     def checkpoint(self, model_name, epoch, loss):
         """same dict layout as RFN/trainer.py:277-300 (model/optimizer state, histories, counters, args); `args_dict` is
         the same Namespace as a plain dict.  Collective under data parallelism: the batch-sharded initial states are
-        gathered so that the file holds the GLOBAL batch rows (a single process can resume it); rank 0 writes."""
+        gathered so that the file holds the GLOBAL batch rows (a single process can resume it); rank 0 writes.  With
+        --ema_decay the averaged weights travel inside `optimizer_state_dict` (state[i]["ema"]); the top-level keys are
+        the same with and without."""
         state = rdist.gather_sharded_state(self.model)
         opt_state = rdist.gather_sharded_optimizer_state(self.optimizer, self.model)   # (moments of the sharded rows too)
         if self.rank != 0:
@@ -544,7 +615,11 @@ class Solver(object):
         rdist.load_sharded_state(self.model, load_model["model_state_dict"])
         # the file holds the moments of the GLOBAL rows of the batch-sharded initial states: every rank takes its own
         # (torch's load_state_dict does not compare shapes, and HipAdam indexes the moments by the parameter's numel)
-        self.optimizer.load_state_dict(rdist.shard_optimizer_state(load_model["optimizer_state_dict"], self.model))
+        opt_state = rdist.shard_optimizer_state(load_model["optimizer_state_dict"], self.model)
+        if not self.ema_decay > 0.0:   # a run without --ema_decay would carry the file's average along, never updated
+            opt_state = dict(opt_state, state={i: {k: v for k, v in st.items() if k != "ema"}
+                                               for i, st in opt_state["state"].items()})
+        self.optimizer.load_state_dict(opt_state)
         # (the count of skipped steps restarts with the loaded state, in HipAdam and for CPU parameters)
         self._skipped_before_epoch = self._host_guard["skipped_steps"] = 0
         self.epoch_i += load_model["epoch"]
@@ -555,6 +630,43 @@ class Solver(object):
         self.best_loss = loss
         self.model.to(self.device)
         return self.epoch_i, loss
+
+    @staticmethod
+    def ema_tensors(ckpt):
+        """{parameter index: average} of a checkpoint written with --ema_decay: `optimizer_state_dict["state"][i]["ema"]`,
+        i counting model.parameters() (global rows for the batch-sharded initial states).  ValueError when the file
+        holds none."""
+        state = (ckpt.get("optimizer_state_dict") or {}).get("state") or {}
+        out = {int(i): st["ema"] for i, st in state.items() if isinstance(st, dict) and "ema" in st}
+        if not out:
+            raise ValueError("the checkpoint holds no averaged weights (it was not written with --ema_decay)")
+        return out
+
+    def load_ema_weights(self, load_model):
+        """copy the averages saved in a checkpoint into the model's parameters (by index in model.parameters() order;
+        a batch-sharded initial state takes this rank's rows of the global ones, as `load` does).  Parameters without a
+        saved average (they never saw a gradient) and all buffers keep their values: call after `load`.  Returns the
+        number of parameters written."""
+        emas = self.ema_tensors(load_model)
+        params = list(self.model.parameters())
+        world = dist.get_world_size() if rdist.is_dist() else 1
+        sharded = set(rdist._sharded_param_indices(self.model))
+        todo = []
+        for i, ema in sorted(emas.items()):
+            if i >= len(params):
+                raise ValueError("the checkpoint averages parameter %d, the model has %d" % (i, len(params)))
+            p = params[i]
+            if i in sharded and world > 1 and ema.shape[0] == p.shape[0] * world and \
+                    tuple(ema.shape[1:]) == tuple(p.shape[1:]):
+                ema = ema[self.rank * p.shape[0]:(self.rank + 1) * p.shape[0]]
+            if tuple(ema.shape) != tuple(p.shape):
+                raise ValueError("averaged parameter %d has shape %s, the model's %s" %
+                                 (i, tuple(ema.shape), tuple(p.shape)))
+            todo.append((p, ema))
+        with torch.no_grad():
+            for p, ema in todo:
+                p.copy_(ema.to(p.device))
+        return len(todo)
 
     def status(self):
         lr = self.optimizer.param_groups[0]["lr"]

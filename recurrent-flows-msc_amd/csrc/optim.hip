@@ -14,17 +14,27 @@ constexpr int ADAM_THREADS = 256;
 // clips before the optimizer sees the gradient) and counts `skipped` steps out of the bias corrections.  The plain
 // instantiation is the kernel as it was; with scale == 1.0f the product is exact, so whatever the compiler contracts it
 // into rounds as the plain kernel does.
-template <bool GUARDED>
+//
+// EMA folds the Polyak average of the weights into the same pass: after the update of the tensor's n-th applied step,
+// ema <- ema + w (p_new - ema) with w = 1 - min(decay, (1 + n) / (10 + n)), formed in double and rounded once like w1 and
+// w2.  p_new is still in registers, so the average costs one more read and one more write per element (36 bytes against
+// 28).  The update of p, m, v is the same expression in all four instantiations: their bits do not depend on EMA.
+template <bool GUARDED, bool EMA>
 __device__ __forceinline__ void adam_chunk(const rfn_adam_entry* __restrict__ tab, const int2* __restrict__ chunks,
                                            int chunk_elems, double lr, double beta1d, double beta2d, float eps,
-                                           float weight_decay, int t, float scale, int skipped) {
-    __shared__ float s_step_size, s_bc2_sqrt;
+                                           float weight_decay, int t, float scale, int skipped, double ema_decay,
+                                           float* const* __restrict__ ema_tab) {
+    __shared__ float s_step_size, s_bc2_sqrt, s_ema_w;
     const int2 ck = chunks[blockIdx.x];
     const rfn_adam_entry e = tab[ck.x];
     if (threadIdx.x == 0) {
         const double step = (double)(t - e.step_offset - skipped);
         s_step_size = (float)(lr / (1.0 - pow(beta1d, step)));
         s_bc2_sqrt = (float)sqrt(1.0 - pow(beta2d, step));
+        if constexpr (EMA) {
+            const double warm = (1.0 + step) / (10.0 + step);
+            s_ema_w = (float)(1.0 - (ema_decay < warm ? ema_decay : warm));
+        }
     }
     __syncthreads();
     // 1 - beta in double, then rounded: 1.f - (float)0.999 is off by 1.3e-5 relative
@@ -45,7 +55,14 @@ __device__ __forceinline__ void adam_chunk(const rfn_adam_entry* __restrict__ ta
         const float denom = sqrtf(vv) / bc2_sqrt + eps;
         pp -= step_size * (mm / denom);
     };
-    const bool v4 = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
+    float* __restrict__ a = nullptr;   // the average (EMA only)
+    float ema_w = 0.f;
+    if constexpr (EMA) {
+        a = ema_tab[ck.x] + base;
+        ema_w = s_ema_w;
+    }
+    auto avg = [&](float& aa, float pp) { aa = fmaf(ema_w, pp - aa, aa); };
+    const bool v4 = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)a) & 15) == 0);
     int i0 = 0;
     if (v4) {
         const int n4 = n >> 2;
@@ -61,6 +78,14 @@ __device__ __forceinline__ void adam_chunk(const rfn_adam_entry* __restrict__ ta
             reinterpret_cast<float4*>(p)[i] = pp;
             reinterpret_cast<float4*>(m)[i] = mm;
             reinterpret_cast<float4*>(v)[i] = vv;
+            if constexpr (EMA) {
+                float4 aa = reinterpret_cast<float4*>(a)[i];
+                avg(aa.x, pp.x);
+                avg(aa.y, pp.y);
+                avg(aa.z, pp.z);
+                avg(aa.w, pp.w);
+                reinterpret_cast<float4*>(a)[i] = aa;
+            }
         }
         i0 = n4 << 2;
     }
@@ -70,6 +95,11 @@ __device__ __forceinline__ void adam_chunk(const rfn_adam_entry* __restrict__ ta
         p[i] = pp;
         m[i] = mm;
         v[i] = vv;
+        if constexpr (EMA) {
+            float aa = a[i];
+            avg(aa, pp);
+            a[i] = aa;
+        }
     }
 }
 
@@ -77,7 +107,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_kernel(const rfn_adam
                                                                    const int2* __restrict__ chunks, int chunk_elems,
                                                                    double lr, double beta1d, double beta2d, float eps,
                                                                    float weight_decay, int t) {
-    adam_chunk<false>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, 1.f, 0);
+    adam_chunk<false, false>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, 1.f, 0, 0., nullptr);
 }
 
 // stats = (norm, scale, skip) as rfn_grad_guard_f32 left them; a skipped step writes nothing at all
@@ -86,7 +116,56 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_multi_guarded_kernel(
     double beta2d, float eps, float weight_decay, int t, const float* __restrict__ stats,
     const long long* __restrict__ skipped) {
     if (stats[2] != 0.f) return;
-    adam_chunk<true>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, stats[1], (int)*skipped);
+    adam_chunk<true, false>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, stats[1], (int)*skipped,
+                            0., nullptr);
+}
+
+// ema[i] is the average of table entry i: a device array of device pointers, indexed like tab[ck.x]
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_multi_kernel(const rfn_adam_entry* __restrict__ tab,
+                                                                       const int2* __restrict__ chunks, int chunk_elems,
+                                                                       double lr, double beta1d, double beta2d, float eps,
+                                                                       float weight_decay, int t, double ema_decay,
+                                                                       float* const* __restrict__ ema) {
+    adam_chunk<false, true>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, 1.f, 0, ema_decay, ema);
+}
+
+// a skipped step leaves the average alone as well, and the count that sets its decay does not advance
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ema_multi_guarded_kernel(
+    const rfn_adam_entry* __restrict__ tab, const int2* __restrict__ chunks, int chunk_elems, double lr, double beta1d,
+    double beta2d, float eps, float weight_decay, int t, const float* __restrict__ stats,
+    const long long* __restrict__ skipped, double ema_decay, float* const* __restrict__ ema) {
+    if (stats[2] != 0.f) return;
+    adam_chunk<true, true>(tab, chunks, chunk_elems, lr, beta1d, beta2d, eps, weight_decay, t, stats[1], (int)*skipped,
+                           ema_decay, ema);
+}
+
+// p <-> ema over the same table and chunk list: bit-exact moves, so two launches are the identity
+__global__ __launch_bounds__(ADAM_THREADS) void param_swap_kernel(const rfn_adam_entry* __restrict__ tab,
+                                                                   const int2* __restrict__ chunks, int chunk_elems,
+                                                                   float* const* __restrict__ ema) {
+    const int2 ck = chunks[blockIdx.x];
+    const rfn_adam_entry e = tab[ck.x];
+    const long base = (long)ck.y * chunk_elems;
+    const long rem = e.n - base;
+    const int n = (int)(rem < chunk_elems ? rem : chunk_elems);
+    float* __restrict__ p = e.p + base;
+    float* __restrict__ a = ema[ck.x] + base;
+    int i0 = 0;
+    if ((((uintptr_t)p | (uintptr_t)a) & 15) == 0) {
+        const int n4 = n >> 2;
+        for (int i = threadIdx.x; i < n4; i += ADAM_THREADS) {
+            const float4 pp = reinterpret_cast<float4*>(p)[i];
+            const float4 aa = reinterpret_cast<float4*>(a)[i];
+            reinterpret_cast<float4*>(p)[i] = aa;
+            reinterpret_cast<float4*>(a)[i] = pp;
+        }
+        i0 = n4 << 2;
+    }
+    for (int i = i0 + threadIdx.x; i < n; i += ADAM_THREADS) {
+        const float pp = p[i], aa = a[i];
+        p[i] = aa;
+        a[i] = pp;
+    }
 }
 
 // ---- the guard: global gradient norm over the same table and chunk list -------------------------------------------
@@ -221,6 +300,45 @@ extern "C" int rfn_adam_step_guarded_f32(const rfn_adam_entry* table, const int*
     hipLaunchKernelGGL(adam_multi_guarded_kernel, dim3(n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, table,
                        reinterpret_cast<const int2*>(chunks), rfn_adam_chunk_elems(), lr, beta1, beta2, (float)eps,
                        (float)weight_decay, t, stats, skipped);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rfn_adam_ema_step_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int t, double ema_decay,
+                                     float* const* ema, rfn_stream_t stream) {
+    RFN_CHECK_ARG(table && chunks && n_chunks >= 0 && ema, -1);
+    RFN_CHECK_ARG(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0., -2);
+    RFN_CHECK_ARG(ema_decay >= 0. && ema_decay < 1., -3);
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(adam_ema_multi_kernel, dim3(n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, table,
+                       reinterpret_cast<const int2*>(chunks), rfn_adam_chunk_elems(), lr, beta1, beta2, (float)eps,
+                       (float)weight_decay, t, ema_decay, ema);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rfn_adam_ema_step_guarded_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, double lr,
+                                             double beta1, double beta2, double eps, double weight_decay, int t,
+                                             const float* stats, long long* skipped, double ema_decay, float* const* ema,
+                                             rfn_stream_t stream) {
+    RFN_CHECK_ARG(table && chunks && n_chunks >= 0 && stats && skipped && ema, -1);
+    RFN_CHECK_ARG(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0., -2);
+    RFN_CHECK_ARG(ema_decay >= 0. && ema_decay < 1., -3);
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(adam_ema_multi_guarded_kernel, dim3(n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, table,
+                       reinterpret_cast<const int2*>(chunks), rfn_adam_chunk_elems(), lr, beta1, beta2, (float)eps,
+                       (float)weight_decay, t, stats, skipped, ema_decay, ema);
+    RFN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int rfn_param_swap_f32(const rfn_adam_entry* table, const int* chunks, int n_chunks, float* const* ema,
+                                  rfn_stream_t stream) {
+    RFN_CHECK_ARG(table && chunks && n_chunks >= 0 && ema, -1);
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(param_swap_kernel, dim3(n_chunks), dim3(ADAM_THREADS), 0, (hipStream_t)stream, table,
+                       reinterpret_cast<const int2*>(chunks), rfn_adam_chunk_elems(), ema);
     RFN_LAUNCH_CHECK();
     return 0;
 }

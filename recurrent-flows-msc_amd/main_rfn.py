@@ -13,7 +13,10 @@ a job script written for the reference drives this implementation unchanged.  Ad
   --grad_clip_norm   clip the global gradient norm to this value before every Adam step (default 0: off);
   --skip_nonfinite_steps   leave parameters and Adam moments untouched on a step whose gradients are not finite, and keep
                      that step out of the loss histories (default off);
-  --max_skipped_steps      end the training after an epoch in which more steps than this were skipped (default 100).
+  --max_skipped_steps      end the training after an epoch in which more steps than this were skipped (default 100);
+  --ema_decay        keep a Polyak average of the weights with this decay in [0, 1), updated inside the Adam launch and
+                     saved in the checkpoint's optimizer state; sheets are drawn from it, tools/export_ema.py writes it
+                     out as a run the evaluation driver can score (default 0: off).
 Without `--synthetic_data` the datasets live on the GPU and a batch is one kernel launch, with no DataLoader workers:
 Stochastic Moving MNIST is rendered (`--choose_data mnist`), BAIR push and KTH clips are gathered from the packed frames.
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N main_rfn.py ... --multigpu`; one process
@@ -45,6 +48,16 @@ def restricted_float(x):
         raise argparse.ArgumentTypeError("%r not a floating-point literal" % (x,))
     if x < 0.0 or x > 1.0:
         raise argparse.ArgumentTypeError("%r not in range [0.0, 1.0]" % (x,))
+    return x
+
+
+def ema_decay_float(x):
+    try:
+        x = float(x)
+    except ValueError:
+        raise argparse.ArgumentTypeError("%r not a floating-point literal" % (x,))
+    if not 0.0 <= x < 1.0:
+        raise argparse.ArgumentTypeError("%r not in range [0.0, 1.0)" % (x,))
     return x
 
 
@@ -167,6 +180,8 @@ def build_parser():
                  help="Skip the Adam step, on the device, when the gradients are not finite")
     p.add_argument("--max_skipped_steps", help="Stop after an epoch with more skipped steps than this", default=100,
                    type=int)
+    p.add_argument("--ema_decay", help="Keep a Polyak average of the weights with this decay, in [0, 1) (0 = off)",
+                   default=0.0, type=ema_decay_float)
     return p
 
 

@@ -218,13 +218,17 @@ def gather_sharded_optimizer_state(optimizer, module, group=None, sharded_names=
     world = dist.get_world_size(group)
     dev = collective_device(group)
     state = dict(sd["state"])
+    # the Polyak average (optimizer.ema_decay > 0: the same on every rank) travels like the two moments
+    keys = ("exp_avg", "exp_avg_sq") + (("ema",) if getattr(optimizer, "ema_decay", 0.0) > 0.0 else ())
     for i in _sharded_param_indices(module, sharded_names):
         st = state.get(i)
         # every rank must enter the same collectives: a rank whose state has not been created yet contributes zeros
         p = list(module.parameters())[i]
         new = dict(st) if st is not None else {}
-        for k in ("exp_avg", "exp_avg_sq"):
-            v = (st[k] if st is not None and k in st else torch.zeros_like(p)).detach().to(dev).contiguous()
+        for k in keys:
+            # (an average that does not exist yet is the parameter itself)
+            missing = p if k == "ema" else torch.zeros_like(p)
+            v = (st[k] if st is not None and k in st else missing).detach().to(dev).contiguous()
             parts = [torch.empty_like(v) for _ in range(world)]
             dist.all_gather(parts, v, group=group)
             new[k] = torch.cat(parts, 0).to(p.device)
@@ -236,7 +240,8 @@ def gather_sharded_optimizer_state(optimizer, module, group=None, sharded_names=
 
 
 def shard_optimizer_state(state_dict, module, group=None, sharded_names=SHARDED_PARAM_NAMES):
-    """the inverse on load: moments saved for the GLOBAL rows of a batch-sharded state are cut to this rank's rows.
+    """the inverse on load: moments (and the Polyak average "ema", where the file has one) saved for the GLOBAL rows of a
+    batch-sharded state are cut to this rank's rows.
     Moments whose leading dimension fits neither the local nor the global batch are dropped (they restart from zero)
     rather than handed to the kernel with a wrong size."""
     world = dist.get_world_size(group) if is_dist() else 1
@@ -250,7 +255,7 @@ def shard_optimizer_state(state_dict, module, group=None, sharded_names=SHARDED_
         b = params[i].shape[0]
         new = dict(st)
         ok = True
-        for k in ("exp_avg", "exp_avg_sq"):
+        for k in ("exp_avg", "exp_avg_sq", "ema"):
             v = st.get(k)
             if v is None:
                 continue

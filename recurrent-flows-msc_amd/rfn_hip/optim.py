@@ -15,7 +15,15 @@ the bias corrections; the host's step counts are settled against that counter wh
 rebuild, state_dict(), guard_stats()).  Under data parallelism the squares of the rank-local gradients (`rank_local`, the
 batch-sharded initial states; GradBucketReducer.finish() has divided them by the world size) are summed over ranks with
 one scalar all-reduce, which gives every rank the norm of one process on the global batch, bit for bit, and hence the
-same decision."""
+same decision.
+
+`ema_decay` d in (0, 1) keeps a Polyak average of every parameter in state[p]["ema"], updated inside the same launch
+(rfn_adam_ema_step_f32 / rfn_adam_ema_step_guarded_f32): after a tensor's n-th APPLIED step, ema += w (p_new - ema) with
+w = 1 - min(d, (1 + n) / (10 + n)).  The average starts as a copy of the parameter when its state is first built, a step
+the guard skips leaves it alone, and swap_ema() exchanges parameters and averages in one launch.  With the default 0
+nothing of this exists: the launches and the state are those of an optimizer without the keyword."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -24,7 +32,10 @@ from . import lib as L
 
 class HipAdam(torch.optim.Adam):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
-                 skip_nonfinite=False, rank_local=(), group=None):
+                 skip_nonfinite=False, rank_local=(), group=None, ema_decay=0.0):
+        self.ema_decay = float(ema_decay)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("HipAdam: ema_decay must be in [0, 1) (0 = no average), got %r" % (ema_decay,))
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, foreach=False,
                          fused=False)
         self.max_grad_norm = float(max_grad_norm)
@@ -38,6 +49,8 @@ class HipAdam(torch.optim.Adam):
         self._guard = None    # (partials, stats, sumsq, skipped, all-reduce sumsq[1]?) for the current table
         self._settled = 0     # skipped steps already taken out of _steps
         self._key = None
+        self._ema = None      # ema on: (device array of the averages' pointers, the averages) for the current table
+        self._swap = None     # swap_ema(): (key, table, chunks, n_chunks, pointers, parameters) over ALL averaged tensors
         self._keep = None
         self._t = 0           # kernel step counter; a tensor's own count is _t - its step_offset
         self._steps = {}      # id(p) -> step count as of the last step() (host ints; state["step"] is synced lazily)
@@ -88,9 +101,65 @@ class HipAdam(torch.optim.Adam):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        if not self.ema_decay > 0.0:
+            for st in self.state.values():   # nobody would update it: a stale average is worse than none
+                st.pop("ema", None)
         self._key, self._steps, self._dirty = None, {}, False
         self._keep = self._gbuf = self._guard = None   # the skipped-step counter restarts with the loaded counts
+        self._ema = self._swap = None                  # (a state without "ema" starts its average in _build)
         self._settled = 0
+
+    # ---- the average ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _ema_of(p, st):
+        """state[p]["ema"], created as a copy of the parameter where the state has none (first step, or a state loaded
+        from a run without the average)"""
+        if "ema" not in st:
+            st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+        a = st["ema"]
+        if a.dtype != torch.float32 or not a.is_cuda or not a.is_contiguous() or a.numel() != p.numel():
+            raise RuntimeError("HipAdam: ema must be a dense fp32 device tensor of its parameter's %d elements (got %s %s, "
+                               "%d elements, contiguous=%s)" % (p.numel(), a.dtype, a.device, a.numel(), a.is_contiguous()))
+        return a
+
+    @staticmethod
+    def _ptr_array(tensors, dev):
+        """device array of the tensors' addresses (float* const* of the entry points)"""
+        host = (ctypes.c_void_p * max(1, len(tensors)))(*[t.data_ptr() for t in tensors])
+        return torch.frombuffer(host, dtype=torch.uint8).to(dev)
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """exchange every averaged parameter with its average: one rfn_param_swap_f32 launch over all tensors whose state
+        holds "ema" (whether or not the last step saw their gradient).  Calling it twice restores both, bit for bit.
+        The parameters' version counters move, so reverse caches and generation graphs keyed on them rebuild."""
+        if not self.ema_decay > 0.0:
+            raise RuntimeError("HipAdam.swap_ema: this optimizer keeps no average (ema_decay = 0)")
+        params = [p for group in self.param_groups for p in group["params"] if "ema" in self.state.get(p, ())]
+        if not params:
+            return
+        emas = [self._ema_of(p, self.state[p]) for p in params]
+        key = tuple((p.data_ptr(), a.data_ptr()) for p, a in zip(params, emas))
+        if self._swap is None or self._swap[0] != key:
+            for p in params:
+                if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous():
+                    raise RuntimeError("HipAdam.swap_ema: parameters must be dense fp32 device tensors")
+            dev = params[0].device
+            chunk = int(L.load().rfn_adam_chunk_elems())
+            ent = (L.rfn_adam_entry * len(params))()
+            chunks = []
+            for i, p in enumerate(params):
+                ent[i] = L.rfn_adam_entry(p.data_ptr(), None, None, None, p.numel(), 0, 0)   # the kernel reads p and n
+                nck = (p.numel() + chunk - 1) // chunk
+                chunks.append(np.stack([np.full(nck, i, dtype=np.int32), np.arange(nck, dtype=np.int32)], 1))
+            chunks = np.concatenate(chunks, 0)
+            self._swap = (key, torch.frombuffer(ent, dtype=torch.uint8).to(dev),
+                          torch.from_numpy(np.ascontiguousarray(chunks).reshape(-1)).to(dev), int(chunks.shape[0]),
+                          self._ptr_array(emas, dev), params)
+        _, tab_d, chk_d, nck, ptr_d, plist = self._swap
+        L.call("rfn_param_swap_f32", tab_d.data_ptr(), chk_d.data_ptr(), nck, ptr_d.data_ptr(),
+               meta=("shell", "param_swap", 0.0, "%d tensors" % len(plist), 16.0 * sum(p.numel() for p in plist)))
+        torch.autograd.graph.increment_version(plist)
 
     # ---- the step ------------------------------------------------------------------------------------------------
     def _build(self, group, params, key):
@@ -102,6 +171,7 @@ class HipAdam(torch.optim.Adam):
             self._settle_skipped()   # (the previous table's tensors; a read is allowed here)
         ent = (L.rfn_adam_entry * len(params))()
         chunks = []
+        emas = []
         for i, p in enumerate(params):
             st = self.state[p]
             if len(st) == 0:
@@ -120,6 +190,8 @@ class HipAdam(torch.optim.Adam):
                 if t.numel() != n:   # e.g. moments of another batch size loaded from a checkpoint: the kernel indexes by n
                     raise RuntimeError("HipAdam: %s has %d elements, its parameter %d (shape %s)" %
                                        (name, t.numel(), n, tuple(p.shape)))
+            if self.ema_decay > 0.0:
+                emas.append(self._ema_of(p, st))
             # the guarded kernel subtracts the device's running count of skipped steps as well
             off = self._t - self._steps[id(p)] - self._settled
             flags = 1 if id(p) in self._rank_local else 0
@@ -131,6 +203,8 @@ class HipAdam(torch.optim.Adam):
         chk_d = torch.from_numpy(np.ascontiguousarray(chunks).reshape(-1)).to(dev)
         self._keep = (tab_d, chk_d, int(chunks.shape[0]), list(params), 28.0 * sum(p.numel() for p in params))
         self._key = key
+        if self.ema_decay > 0.0:
+            self._ema = (self._ptr_array(emas, dev), emas)
         if self.guarded:
             import torch.distributed as dist
             from . import dist as rdist
@@ -170,8 +244,14 @@ class HipAdam(torch.optim.Adam):
             self._guarded_launches(group, beta1, beta2)
             torch.autograd.graph.increment_version(plist)
             return loss
-        L.call("rfn_adam_step_f32", tab_d.data_ptr(), chk_d.data_ptr(), nck, float(group["lr"]), beta1, beta2, group["eps"],
-               group["weight_decay"], self._t, meta=("shell", "adam", 0.0, "%d tensors" % len(plist), nbytes))
+        if self.ema_decay > 0.0:
+            L.call("rfn_adam_ema_step_f32", tab_d.data_ptr(), chk_d.data_ptr(), nck, float(group["lr"]), beta1, beta2,
+                   group["eps"], group["weight_decay"], self._t, self.ema_decay, self._ema[0].data_ptr(),
+                   meta=("shell", "adam_ema", 0.0, "%d tensors" % len(plist), nbytes * 36.0 / 28.0))
+        else:
+            L.call("rfn_adam_step_f32", tab_d.data_ptr(), chk_d.data_ptr(), nck, float(group["lr"]), beta1, beta2,
+                   group["eps"], group["weight_decay"], self._t,
+                   meta=("shell", "adam", 0.0, "%d tensors" % len(plist), nbytes))
         # the kernel wrote through raw pointers: tell autograd's version counters, which everything keyed on
         # `p._version` relies on (ListGlow._reverse_cache, RFN._gen_graph: cached inverse matrices / packs / hipGraph)
         torch.autograd.graph.increment_version(plist)
@@ -189,6 +269,12 @@ class HipAdam(torch.optim.Adam):
             rdist.all_reduce_sum_(sumsq[1:2], group=self._group)
         L.call("rfn_grad_guard_f32", sumsq.data_ptr(), self.max_grad_norm, int(self.skip_nonfinite), stats.data_ptr(),
                skipped.data_ptr(), meta=("shell", "grad_guard", 0.0, "", 0.0))
+        if self.ema_decay > 0.0:
+            L.call("rfn_adam_ema_step_guarded_f32", tab, chk, nck, float(group["lr"]), beta1, beta2, group["eps"],
+                   group["weight_decay"], self._t, stats.data_ptr(), skipped.data_ptr(), self.ema_decay,
+                   self._ema[0].data_ptr(),
+                   meta=("shell", "adam_ema_guarded", 0.0, "%d tensors" % len(plist), nbytes * 36.0 / 28.0))
+            return
         L.call("rfn_adam_step_guarded_f32", tab, chk, nck, float(group["lr"]), beta1, beta2, group["eps"],
                group["weight_decay"], self._t, stats.data_ptr(), skipped.data_ptr(),
                meta=("shell", "adam_guarded", 0.0, "%d tensors" % len(plist), nbytes))
