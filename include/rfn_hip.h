@@ -831,6 +831,37 @@ int rfn_keyed_normal_f32(float* const* outs, const int* numels, int n_slots, int
 int rfn_keyed_normal_tiled_f32(float* const* outs, const int* numels, int n_slots, int rows, int B, int tiles, long seed,
                                int step, long first_seq, long first_draw, rfn_stream_t stream);
 
+/* ---- RFN's importance-weighted bound, csrc/iw_bound.hip  (RFN.iw_log_weights; DESIGN.md section 24 is the contract).
+ * rfn_latent_iw_f32: one latent step of `rows` chains.  enc, pri = [rows, 2*ZHW] outputs of the encoder / prior parameter
+ * convs in rfn_latent_step_fwd_f32's layout (loc half | raw scale half), eps_q [rows, ZHW]; with ps = softplus(pri_raw),
+ * es = softplus(enc_raw) (nothing added), pm = pri_loc, em = enc_loc (+ pm when res_q):
+ *   zxt = em + es*eps_q                       [rows, ZHW], bit for bit rfn_latent_step_fwd_f32's zxt of the same inputs;
+ *   logr[row] = sum_j  -((zxt - pm)/ps)^2 / 2 - log ps + eps_q^2 / 2 + log es           [rows]
+ * i.e. log N(zxt; pm, ps) - log N(zxt; em, es) summed over the row (the 2 pi terms cancel).  An element's term is
+ * evaluated in fp64 on the fp32 values zxt, pm, ps, es, eps_q and rounded to fp32 once (its parts nearly cancel where
+ * posterior and prior are close); the sum is fp32.  Forward only.
+ * One wavefront per row, four rows per workgroup; lane l adds the terms of elements l, l + 64, ... in index order and the
+ * 64 lane sums are combined by a fixed xor butterfly (32, 16, ..., 1): no atomics, no LDS memory, a row's bits depend on
+ * that row alone (not on rows or the grid).  Any rows >= 1, ZHW >= 1; -1 (nothing launched) for smaller sizes or a NULL
+ * pointer.  One launch, no allocation: capturable. */
+int rfn_latent_iw_f32(const float* enc, const float* pri, const float* eps_q, float* zxt, float* logr, int rows, int ZHW,
+                      int res_q, rfn_stream_t stream);
+/* rfn_keyed_uniform_f32: addressed uniforms in [0, scale), the dequantisation noise of all steps of a pass in one
+ * launch.  out [n_steps, rows, numel] fp32 contiguous; row i of every step-block stands for draw first_draw + i / B of
+ * sequence first_seq + i % B (draw-major, as rfn_keyed_normal_f32), step-block s for step first_step + s.
+ * Block q of a row is Philox4x64-10(key = (seed, (step << 32) | slot), counter = (q, 0, seq, draw)), words w0..w3
+ * (csrc/philox.h).  Word w_i gives element 8q + 2i from its high half and element 8q + 2i + 1 from its low half:
+ *   value = (half >> 8) * 2^-24 * scale
+ * The first product is exact and the second is rounded once: every value lies in [0, scale).  A value depends only on
+ * (seed, step, slot, sequence, draw, element): not on rows, B, n_steps, the grid or the split into calls.
+ * slot in [8, 2^31): rfn_keyed_normal_f32 owns slots 0..7 of this key space, rfn_mol_sample_keyed uses 16 and 17 with
+ * another counter; RFN.iw_log_weights uses 24.  rows is a multiple of B >= 1; seed, first_seq, first_draw, first_step
+ * are >= 0 and first_step + n_steps <= 2^31; scale is finite and > 0.  Two 16-byte stores per lane where numel % 8 == 0
+ * and out is 16-byte aligned, single stores otherwise (out must be 4-byte aligned).  No atomics, no LDS.  One launch (none
+ * when nothing is to be written); a failed check launches nothing. */
+int rfn_keyed_uniform_f32(float* out, int n_steps, int rows, int B, int numel, float scale, long seed, int first_step,
+                          int slot, long first_seq, long first_draw, rfn_stream_t stream);
+
 /* ---- clips of a device-resident frame store as float32 batches  (the per-item work of the file-backed datasets,
  * data_generators/bair_push.py:66-109 and data_generators/kth.py:34-65, and the DataLoader collation of
  * RFN/trainer.py:132-161, for a whole batch in one launch).  store: uint8 [n_frames, H, W, Cs] device tensor,

@@ -10,6 +10,7 @@ MI355X-first restructuring of `loss` (same mathematics, RFN/RFN_new.py:116-247):
      (`frame = (t-1)·B + b`), so every kernel launch carries the whole sequence batch.
 Data dependent ActNorm initialisation uses the first B frames (t = 1) exactly like the reference's first call.
 """
+import math
 import os
 
 import torch
@@ -18,6 +19,7 @@ import torch.nn as nn
 from Flow import ListGlow
 from Flow.glow_modules import ActNorm
 from rfn_hip import ops as K
+from rfn_hip import ops   # the same module, for the methods whose argument K is the number of chains
 from rfn_hip import debug as DBG
 from Utils import VGG_upscaler, VGG_downscaler, SimpleParamNet, ConvLSTM, free_bits_kl, batch_reduce
 from Utils.modules import recurrent_pair, recurrent_pair_split
@@ -30,6 +32,15 @@ def kl_normal(q_mean, q_std, p_mean, p_std):
     var_ratio = (q_std / p_std) ** 2
     t1 = ((q_mean - p_mean) / p_std) ** 2
     return 0.5 * (var_ratio + t1 - 1 - var_ratio.log())
+
+
+def iw_bound(log_w):
+    """bound[b] = logsumexp_k log_w[k, b] - log K of a table [K, B] of log importance weights, in
+    the table's dtype and on its device; the largest entry of a column is taken out before the exponentials"""
+    if log_w.dim() != 2 or log_w.shape[0] < 1:
+        raise ValueError("iw_bound: log_w must be [K >= 1, B], got %s" % (tuple(log_w.shape),))
+    top = log_w.max(dim=0).values
+    return top + (log_w - top).exp().sum(0).log() - math.log(log_w.shape[0])
 
 
 class RFN(nn.Module):
@@ -264,6 +275,121 @@ class RFN(nn.Module):
     def forward(self, x, logdet=0):
         """Alias of `loss` so wrappers that hook `forward` (gradient all-reduce) see the training call."""
         return self.loss(x, logdet)
+
+    # ------------------------------------------------------------------------------------------------ IWAE bound
+    def _iw_arguments(self, who, K_, chains_per_pass):
+        """(K, P) of an importance-weighted call; raises before anything runs"""
+        if self.training:
+            raise RuntimeError("RFN.%s needs eval mode: in training mode the batch statistics of the normalisation "
+                               "layers would depend on K (call model.eval() first)" % who)
+        for v, nm in ((K_, "K"), (chains_per_pass, "chains_per_pass")):
+            if v is not None and (isinstance(v, bool) or int(v) != v):
+                raise ValueError("RFN.%s: %s must be an integer, got %r" % (who, nm, v))
+        K_ = int(K_)
+        if K_ < 1:
+            raise ValueError("RFN.%s: K must be at least 1, got %d" % (who, K_))
+        P = K_ if chains_per_pass is None else int(chains_per_pass)
+        if P < 1:
+            raise ValueError("RFN.%s: chains_per_pass must be at least 1, got %d" % (who, P))
+        return K_, min(P, K_)
+
+    def iw_log_weights(self, x, K, seed, first_seq=0, first_chain=0, chains_per_pass=None):
+        """The log importance weights of K posterior chains per sequence (DESIGN section 24 is the contract): a float64
+        device tensor [K, B], entry [k, b] = sum_t (log p(x_t | h_t, z_t) + log p(z_t | h_t, z_{t-1}) - log q(z_t | ...))
+        of chain first_chain + k of sequence first_seq + b, with z_t ~ q drawn along the chain and the flow's
+        dequantisation noise u_t as part of the proposal; -ln(2^n_bits)*C*H*W per frame stays inside, as in
+        flow.log_prob.  Eval mode only, run under torch.no_grad().
+        The prior of step t is ALWAYS taken on the chain's own previous posterior sample z^x_{t-1}, also when res_q is
+        False.  RFN.loss feeds the prior an ancestral prior sample in that case; importance weights with such a prior
+        would not bound log p(x), so this method does not follow it there.  The scales are softplus(raw) as in
+        rfn_latent_step; overshooting (D) and free_bits play no part.
+        The extractor, the ConvLSTM and the smoothing LSTM run once per call, with the code `loss` uses.  The chains run
+        in passes of P = chains_per_pass (default K) chains, P*B rows each, draw-major (row r*B + b): per step the encoder
+        and prior convolutions on the replicated static inputs and one rfn_hip.ops.latent_iw launch, then ONE upscaler
+        call and ONE flow.log_prob(..., steps=T-1) call for the pass's (T-1)*P*B frames, t-major as in `loss`.
+        Noise: a chain is a "draw" of the addressing.  eps_t is rfn_hip.ops.keyed_normal slot 0 at step t, u_t is
+        rfn_hip.ops.keyed_uniform slot 24 at step t with scale 2^-n_bits.  An entry therefore depends on (seed, sequence
+        id, chain id) and the data alone -- not on K, P, B or torch's generators, which are left untouched -- up to the
+        summation order of the batched kernels."""
+        assert len(x.shape) == 5, "x must be [bs, t, c, h, w]"
+        Kc, P = self._iw_arguments("iw_log_weights", K, chains_per_pass)
+        B, T = int(x.shape[0]), int(x.shape[1])
+        if T < 2:
+            raise ValueError("RFN.iw_log_weights: need at least 2 frames, got %d" % T)
+        seed, first_seq, first_chain = int(seed), int(first_seq), int(first_chain)
+        S = T - 1
+
+        def rep_steps(t, p):   # [S, B, ...] -> [S*p*B, ...]: row (s*p + r)*B + b is sequence b at step s
+            return t.unsqueeze(1).expand(S, p, *t.shape[1:]).reshape(S * p * B, *t.shape[2:])
+
+        with torch.no_grad():
+            # ---- the sample-independent front, as in `loss`: once for all chains
+            hprev, cprev, aprev, caprev, _, z0x, _, _, _ = self.get_inits()
+            x_tm = x.transpose(0, 1).reshape(T * B, *x.shape[2:])
+            feats_tb = self.extractor.forward_steps(x_tm, T)
+            last_tb = feats_tb if self.single_feature else feats_tb[-1]
+            last_steps = last_tb.view(T, B, *last_tb.shape[1:])
+            last_t = last_steps.unbind(0)
+            if self.single_feature:
+                feats = list(last_t)
+            else:
+                feats = [[f[i * B:(i + 1) * B] for f in feats_tb[:-1]] + [last_t[i]] for i in range(T)]
+            x_all = None if self.enable_smoothing else last_steps[:S]
+            store_ht, store_at, _, _ = self._deterministic_states(feats, T, hprev, cprev, aprev, caprev, x_all)
+            h_sb = torch.stack(store_ht[:S], 0)
+            # the encoder's static input channels: a_t, or (h_t, features of frame t) around the z channels
+            enc_sb = torch.stack(store_at[:S], 0) if self.enable_smoothing else last_steps[1:T]
+            skips_sb = None if self.single_feature else [f.view(T, B, *f.shape[1:])[:S] for f in feats_tb]
+            xs_sb = x_tm.view(T, B, *x.shape[2:])[1:]
+            zshape = tuple(z0x.shape[1:])
+            both_nets = recurrent_pair(self.encoder, self.prior)
+            scale = 1.0 / 2 ** self.flow.n_bits
+
+            tables = []
+            for c0 in range(0, Kc, P):
+                p = min(P, Kc - c0)
+                R = p * B
+                h_rep = rep_steps(h_sb, p)
+                h_steps, enc_steps = h_rep.view(S, R, *h_sb.shape[2:]), rep_steps(enc_sb, p).view(S, R, *enc_sb.shape[2:])
+                zx = z0x.repeat(p, 1, 1, 1)
+                base_t, logr_t = [], []
+                for i in range(1, T):
+                    ht = h_steps[i - 1]
+                    if self.enable_smoothing:
+                        enc_in = torch.cat((enc_steps[i - 1], zx), dim=1)
+                    else:
+                        enc_in = torch.cat((ht, zx, enc_steps[i - 1]), dim=1)
+                    enc_raw, pri_raw = both_nets(enc_in, torch.cat((ht, zx), dim=1))
+                    eps, = ops.keyed_normal([zshape], B, p, seed, i, first_seq, first_chain + c0, device=x.device)
+                    zx, logr = ops.latent_iw(enc_raw, pri_raw, eps, self.res_q)
+                    base_t.append(zx)
+                    logr_t.append(logr)
+                # ---- the decoder: all (T-1)*p*B frames of the pass in one call, t-major
+                base = torch.cat((h_rep, torch.cat(base_t, dim=0)), dim=1)
+                skips = None if skips_sb is None else [rep_steps(f, p) for f in skips_sb]
+                if self.skip_connection_features:
+                    conds = self.upscaler.forward_steps(base, S, skip_list=skips)
+                else:
+                    conds = self.upscaler.forward_steps(base, S)
+                if self.skip_connection_flow == "with_skip":
+                    conds = self.combineconditions(conds, skips)
+                elif self.skip_connection_flow == "only_skip":
+                    conds = skips
+                u = ops.keyed_uniform(tuple(x.shape[2:]), B, p, seed, 1, n_steps=S, scale=scale, first_seq=first_seq,
+                                    first_draw=first_chain + c0, device=x.device)
+                _, nll = self.flow.log_prob(rep_steps(xs_sb, p), conds, base, 0, u.view(S * R, *x.shape[2:]), steps=S)
+                tables.append((torch.cat(logr_t, dim=0).double() - nll.double()).view(S, p, B).sum(0))
+            return torch.cat(tables, dim=0)
+
+    def elbo_importance_weighting(self, x, K, seed=0, first_seq=0, chains_per_pass=None):
+        """The importance-weighted bound of RFN in the sign and unit of the baselines' methods of this name (nats per
+        sequence): -mean_b (logsumexp_k log w[k, b] - log K) over the K chains of `iw_log_weights` (chains 0 .. K-1 of
+        sequences first_seq .. first_seq + B - 1 under `seed`), a float64 scalar on the device.  (u, z) is a joint
+        proposal, so this is the standard sequence-level IWAE bound; K = 1 is a one-sample ELBO estimate.  The prior is
+        always taken on the chain's own posterior sample, also when res_q is False, where RFN.loss does otherwise: see
+        iw_log_weights.  Eval mode only."""
+        self._iw_arguments("elbo_importance_weighting", K, chains_per_pass)
+        return -iw_bound(self.iw_log_weights(x, K, seed, first_seq, 0, chains_per_pass)).mean()
 
     # ------------------------------------------------------------------------------------------------ generation
     # `draws` (optional, tests): the noise in the reference's draw order, see each method.

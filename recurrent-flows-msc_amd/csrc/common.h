@@ -76,6 +76,8 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm /* >= 4 floats
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
+// torch.nn.Softplus(): x itself above the threshold 20 (shell.hip's Gaussian log-prob and latent step, iw_bound.hip)
+__device__ __forceinline__ float softplusf_(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline int next_pow2(int v) {

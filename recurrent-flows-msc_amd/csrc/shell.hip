@@ -1378,7 +1378,6 @@ extern "C" int rfn_affine_zeros_bwd_f32(const float* zout, long zout_ns, const f
 
 // ------------------------------------------------------------------------------------------------ gaussian log-prob
 #define RFN_HALF_LOG_2PI 0.91893853320467274178f
-__device__ __forceinline__ float softplusf_(float x) { return x > 20.f ? x : log1pf(expf(x)); }  // torch threshold=20
 
 __device__ __forceinline__ void gauss_params(const float* on, int layout, int c, int Cz, int HW, int p, float& mean,
                                              float& raw) {

@@ -118,6 +118,10 @@ class Evaluator(object):
         self.seed = int(getattr(settings, "seed", None) or 0)
         # the inner samples of SRNN.elbo_importance_weighting in get_loss("srnn.pt") (the reference's constant: 20)
         self.iw_samples = int(getattr(settings, "iw_samples", None) or 20)
+        # optional: K chains per sequence of RFN.elbo_importance_weighting in get_loss("rfn.pt") (None or 0: off, the
+        # single-sample ELBO of RFN.loss), run in passes of iw_chains_per_pass chains (None: all K in one pass)
+        self.rfn_iw_samples = int(getattr(settings, "rfn_iw_samples", None) or 0)
+        self.iw_chains_per_pass = getattr(settings, "iw_chains_per_pass", None)
         self.num_samples_to_plot = int(getattr(settings, "num_samples_to_plot", None) or 5)
         # optional: a directory or a list of files holding the LPIPS-alex weights (rfn_hip.ops.lpips_alex_load); loaded
         # on first use
@@ -138,21 +142,34 @@ class Evaluator(object):
         """error_metrics.py:370-417: mean (and, with resampling, standard deviation) of the per-batch bits/dim over the
         test set, model in eval mode.  "rfn.pt": RFN.loss through compute_loss.  "srnn.pt" (the reference's other
         branch, :396-399): the importance-weighted bound SRNN.elbo_importance_weighting(imageloss, K) / (ln 2 * prod(dims)
-        * t) with K = settings.iw_samples (default 20, the reference's constant)."""
+        * t) with K = settings.iw_samples (default 20, the reference's constant).
+        With settings.rfn_iw_samples = K > 0, "rfn.pt" reports the same kind of figure as the baselines: batch i of
+        resample r is RFN.elbo_importance_weighting(imageloss, K, seed=settings.seed + r, first_seq=i * B,
+        chains_per_pass=settings.iw_chains_per_pass) / (ln 2 * prod(dims) * t), B being the first batch's size; the
+        noise is addressed, so the figure is reproducible and torch's generators are not touched.  Unset, "rfn.pt" is
+        the path above, unchanged."""
         rfn = check_model_name(model_name)
         loader = loader if loader is not None else self.test_loader
         with torch.no_grad():
             self.model.eval()
             means = []
-            for _ in range(loss_resamples):
+            for r in range(loss_resamples):
                 bpd = []
+                batch_size = None
                 for batch_i, true_image in enumerate(loader):
                     if max_batches is not None and batch_i >= max_batches:
                         break
                     image = true_image[0] if self.choose_data == "bair" and isinstance(true_image, (list, tuple)) else true_image
                     image = self.solver.preprocess(image.to(self.device))
                     imageloss = image[:, :self.n_trained] if self.n_trained else image
-                    if rfn:
+                    batch_size = batch_size or int(image.shape[0])
+                    if rfn and self.rfn_iw_samples:
+                        loss = self.model.elbo_importance_weighting(imageloss, self.rfn_iw_samples, seed=self.seed + r,
+                                                                    first_seq=batch_i * batch_size,
+                                                                    chains_per_pass=self.iw_chains_per_pass)
+                        b = float(loss / (np.log(2.) * torch.prod(torch.tensor(imageloss.shape[2:])) *
+                                          (imageloss.shape[1] - 1)))
+                    elif rfn:
                         _, kl, nll = self.model.loss(imageloss, 0)
                         b, _, _ = self.compute_loss(nll=nll, kl=kl, dims=imageloss.shape[2:], t=imageloss.shape[1] - 1)
                     else:

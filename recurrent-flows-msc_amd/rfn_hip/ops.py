@@ -1574,6 +1574,38 @@ class LatentStepFn(torch.autograd.Function):
         return g_enc, g_pri, None, None, None
 
 
+def latent_iw(enc_raw, pri_raw, eps_q, res_q):
+    """one latent step of the chains of RFN.iw_log_weights in one launch (rfn_latent_iw_f32; include/rfn_hip.h and DESIGN
+    section 24 hold the definition): from the raw outputs [rows, 2*Z, H, W] of the encoder / prior parameter convs and
+    eps_q [rows, Z, H, W] to (zxt [rows, Z, H, W], logr [rows]), zxt = em + es*eps_q with LatentStepFn's bits and logr the
+    row sum of log N(zxt; pm, ps) - log N(zxt; em, es).  Forward only: an input that requires grad is an error.  No CPU
+    fallback."""
+    for t, nm in ((enc_raw, "enc_raw"), (pri_raw, "pri_raw"), (eps_q, "eps_q")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("latent_iw: %s must be a tensor, got %s" % (nm, type(t).__name__))
+        if t.requires_grad:
+            raise RuntimeError("latent_iw has no backward: %s requires grad (compute it under torch.no_grad())" % nm)
+    if enc_raw.dim() < 2 or enc_raw.shape != pri_raw.shape or int(enc_raw.shape[1]) % 2:
+        raise ValueError("latent_iw: enc_raw and pri_raw must both be [rows, 2*Z, ...], got %s and %s" %
+                         (tuple(enc_raw.shape), tuple(pri_raw.shape)))
+    shp = (int(enc_raw.shape[0]), int(enc_raw.shape[1]) // 2) + tuple(int(d) for d in enc_raw.shape[2:])
+    if tuple(eps_q.shape) != shp:
+        raise ValueError("latent_iw: eps_q must be %s, got %s" % (shp, tuple(eps_q.shape)))
+    rows, ZHW = shp[0], 1
+    for d in shp[1:]:
+        ZHW *= d
+    if rows < 1 or ZHW < 1:
+        raise ValueError("latent_iw: need rows >= 1 and Z*H*W >= 1, got %s" % (shp,))
+    enc_raw, pri_raw, eps_q = enc_raw.contiguous(), pri_raw.contiguous(), eps_q.contiguous()
+    ptrs = [L.dev(enc_raw, "enc_raw"), L.dev(pri_raw, "pri_raw"), L.dev(eps_q, "eps_q")]
+    zxt = torch.empty(shp, device=enc_raw.device, dtype=torch.float32)
+    logr = torch.empty((rows,), device=enc_raw.device, dtype=torch.float32)
+    with torch.cuda.device(enc_raw.device):
+        L.call("rfn_latent_iw_f32", *ptrs, L.dev(zxt), L.dev(logr), rows, ZHW, 1 if res_q else 0,
+               meta=_shell("latent_iw", enc_raw, 3.0))
+    return zxt, logr
+
+
 GAUSS_HEADS_OUTPUTS = ("z_q", "z_p", "q_scale", "p_scale", "kl", "logq", "logp")
 # what each output reads beside p_loc / p_raw, which every call needs
 _GAUSS_HEADS_NEEDS = {"z_q": ("q_loc", "q_raw", "eps_q"), "z_p": ("eps_p",), "q_scale": ("q_loc", "q_raw"), "p_scale": (),
@@ -2555,6 +2587,66 @@ def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=
                 L.call("rfn_keyed_normal_tiled_f32", ptrs, numels, len(out), tile_rows, B, tiles, seed, step, first_seq,
                        first_draw,
                        meta=("shell", "keyed_normal", 0.0, "%dx%dx%d" % (tiles, tile_rows, total // rows), 4.0 * total))
+    return out
+
+
+KEYED_UNIFORM_SLOT_DEQUANT = 24   # the dequantisation noise of RFN.iw_log_weights (keyed_normal: 0 .. 7, mol: 16, 17)
+
+
+def keyed_uniform(shape, B, n_draws, seed, first_step, n_steps=1, slot=KEYED_UNIFORM_SLOT_DEQUANT, scale=1.0, first_seq=0,
+                  first_draw=0, device=None, out=None):
+    """Addressed uniform noise in [0, scale) (rfn_keyed_uniform_f32; include/rfn_hip.h and DESIGN section 24 hold the
+    definition): a float32 tensor [n_steps, n_draws*B, *shape].  Step-block s stands for step first_step + s, row r*B + b
+    of every block for draw first_draw + r of sequence first_seq + b, and a value depends only on (seed, step, slot,
+    sequence, draw, position in the row): the same on any grid, for any B, n_draws, n_steps and split into calls.  slot
+    in [8, 2^31): keyed_normal owns the slots below.  out: a contiguous float32 tensor of that shape to fill in place
+    instead of a fresh one (`shape` may then be None); device: where a fresh tensor goes (default: the current GPU).
+    One launch on the current stream for all steps; torch's generators are not touched; no CPU fallback."""
+    B, n_draws, seed, first_step, n_steps, first_seq, first_draw = (int(v) for v in (B, n_draws, seed, first_step, n_steps,
+                                                                                  first_seq, first_draw))
+    if isinstance(slot, bool) or not isinstance(slot, int):
+        raise TypeError("keyed_uniform: slot must be an int, got %s" % type(slot).__name__)
+    scale = float(scale)
+    if B < 1 or n_draws < 0 or n_steps < 0:
+        raise ValueError("keyed_uniform: need B >= 1, n_draws >= 0 and n_steps >= 0 (got %d, %d, %d)" %
+                         (B, n_draws, n_steps))
+    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
+        if not 0 <= v < 1 << 63:
+            raise ValueError("keyed_uniform: %s %d not in [0, 2^63)" % (nm, v))
+    if first_step < 0 or first_step + n_steps > 1 << 31:
+        raise ValueError("keyed_uniform: steps %d .. %d not in [0, 2^31)" % (first_step, first_step + n_steps - 1))
+    if not 8 <= slot < 1 << 31:
+        raise ValueError("keyed_uniform: slot %d not in [8, 2^31) (keyed_normal owns slots 0 .. 7)" % slot)
+    if not 0.0 < scale < float("inf"):
+        raise ValueError("keyed_uniform: scale must be finite and positive, got %r" % scale)
+    rows = n_draws * B
+    if rows > 0x7fffffff:
+        raise ValueError("keyed_uniform: %d rows exceed one launch" % rows)
+    if out is None:
+        if shape is None:
+            raise TypeError("keyed_uniform: give shape or out")
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("rfn_hip kernels need device tensors; keyed_uniform was asked for %s (no CPU fallback)" %
+                               device)
+        out = torch.empty((n_steps, rows) + tuple(int(d) for d in shape), device=device, dtype=torch.float32)
+    else:
+        if not isinstance(out, torch.Tensor):
+            raise TypeError("keyed_uniform: out must be a tensor, got %s" % type(out).__name__)
+        if out.dim() < 2 or tuple(out.shape[:2]) != (n_steps, rows):
+            raise ValueError("keyed_uniform: out must be [%d, %d, ...], got shape %s" % (n_steps, rows, tuple(out.shape)))
+        if shape is not None and tuple(out.shape[2:]) != tuple(int(d) for d in shape):
+            raise ValueError("keyed_uniform: out has rows %s, shape is %s" % (tuple(out.shape[2:]), tuple(shape)))
+    total = out.numel()
+    if total:
+        numel = total // (n_steps * rows)
+        if numel > 0x7fffffff or -(-numel // 8) * rows * n_steps > 0x7fffffff * 256:
+            raise ValueError("keyed_uniform: %d steps of %d rows of %d values exceed one launch" % (n_steps, rows, numel))
+        ptr = L.dev(out, "out")
+        with torch.cuda.device(out.device):
+            L.call("rfn_keyed_uniform_f32", ptr, n_steps, rows, B, numel, scale, seed, first_step, slot,
+                   first_seq, first_draw,
+                   meta=("shell", "keyed_uniform", 0.0, "%dx%dx%d" % (n_steps, rows, numel), 4.0 * total))
     return out
 
 
