@@ -902,6 +902,39 @@ int rfn_sheet_max_rows(void);
 int rfn_sheet_compose_u8(const void* rows_table, int R, int N, int C, int H, int W, int gutter, int bg, int n_bits,
                          int range_half, int lead, long out_addr, rfn_stream_t stream);
 
+/* ---- a line chart as 8-bit RGB pixels from a display list  (the matplotlib figures of Evaluator.test_temp_values and
+ * Evaluator.plot_eval_values, evaluation_metrics/error_metrics.py:600-809 and :812-1003: lines, fill_between bands,
+ * markers, error bars, axvline, grid, axes and text; DESIGN.md section 25 is the pixel contract, integer throughout).
+ * table: DEVICE array of n records of 12 int32 {type, rgba, p0..p9}, 16-byte aligned, painted in list order;
+ *   rgba = r | g<<8 | b<<16 | alpha<<24; geometry in 1/16 pixel, x right, y down, every coordinate in [-4096, 36864],
+ *   every capsule half-width in [0, 4096] (all products fit 64 bits).  A sample s = (sx, sy) is inside
+ *   0 BOX        p0..p3 = x0, y0, x1, y1: x0 <= sx < x1, y0 <= sy < y1; p4, p5 = dash on, off (>= 0): when on + off > 0
+ *                also ((t - t0) mod (on + off)) < on, t the sample's coordinate on the long axis (x if x1 - x0 >=
+ *                y1 - y0, else y), t0 the box's start on it;
+ *   1 CAPSULE    p0..p4 = ax, ay, bx, by, hw; d = b - a, p = s - a: p.d <= 0: |p|^2 <= hw^2; p.d >= |d|^2:
+ *                |s - b|^2 <= hw^2; else (d x p)^2 <= hw^2 |d|^2  (a == b: a disc);
+ *   2 TRAPEZOID  p0..p5 = x0, x1, lo0, lo1, hi0, hi1: x0 <= sx < x1, (sy - lo0)(x1 - x0) >= (lo1 - lo0)(sx - x0),
+ *                (sy - hi0)(x1 - x0) < (hi1 - hi0)(sx - x0);
+ *   3 TRIANGLE   p0..p5 = x0, y0, x1, y1, x2, y2: e_i = (x_j - x_i)(sy - y_i) - (y_j - y_i)(sx - x_i) over the edges
+ *                (0,1), (1,2), (2,0): all e_i >= 0 or all e_i <= 0; nothing when the area is zero, i.e. when
+ *                (x1 - x0)(y2 - y0) == (y1 - y0)(x2 - x0);
+ *   4 GLYPH      p0, p1 = top-left x, y, p2 = ASCII code 32..126, p3 = scale k in 1..128 (pixels per dot), p4 = 0
+ *                upright, 1 rotated 90 degrees counter-clockwise; u = sx - x, v = sy - y, q = 16 k; upright: 0 <= u < 5q,
+ *                0 <= v < 7q and dot (column floor(u/q), row floor(v/q)) of the built-in 5x7 font is set; rotated:
+ *                0 <= u < 7q, 0 <= v < 5q and dot (column 4 - floor(v/q), row floor(u/q)) is set.
+ *   Any other record paints nothing.  Pixel (px, py) has the 16 samples (16 px + i, 16 py + j), i, j in {2, 6, 10, 14};
+ *   per record, with c = samples inside and w = alpha * c: dst = (dst (4080 - w) + src w + 2040) / 4080 per channel in
+ *   integer division, from the background bg = r | g<<8 | b<<16.
+ * H, W: the canvas, 1..2048 each.  out_addr: the device address of the uint8 output, any byte alignment: lead 0:
+ * [H, W, 3]; lead 1: [H, 1 + 3 W] with byte 0 of every line 0 (the raw stream of a PNG, as rfn_sheet_compose_u8).  Every
+ * output byte is written exactly once, nothing outside it whatever the table holds; no atomics; the result does not
+ * depend on rfn_chart_chunk(), the records one workgroup culls against its 16 x 16 tile at a time.  One launch.
+ * rfn_chart_font (host only): out[5 ch + c] = column c (left to right) of character 32 + ch, bit r = the dot of row r
+ * from the top; 475 values. */
+int rfn_chart_chunk(void);
+int rfn_chart_font(long long* out);
+int rfn_chart_render_u8(const int* table, int n, int H, int W, int bg, int lead, long out_addr, rfn_stream_t stream);
+
 /* ---- LPIPS with the AlexNet trunk over a batch of uint8 frames  (evaluation_metrics/error_metrics.py:72, :173-187:
  * lpips.LPIPS(net='alex') of `lpips` 0.1.3, version 0.1, lpips=True, spatial=False, eval mode; one call per frame there).
  * Frame [C, H, W] uint8, C in {1, 3} (one channel stands for all three): x = p/255*2 - 1, then (x - shift[c]) / scale[c]

@@ -16,8 +16,10 @@ raises.
 `get_eval_values_temperatures` is the temperature study (eval_settings.py:110-126) as one pass: best-of-N at K sampling
 temperatures from one RFN.predict_draws call per pass, the temperatures being per-row inputs of generation.
 `plot_long_t`, `plot_diversity`, `plot_random_samples` and `plot_temp` (:1220-1415) are written as PNG sheets of pixels
-like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  The other plots -- the curve figures
-`plot_eval_values` / `test_temp_values`, `param_plots`, `plot_elbo_gap`, `plot_prob_of_t` -- are not drawn."""
+like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  The curve figures `plot_eval_values` /
+`test_temp_values` (:600-1003) are drawn by the chart kernel (rfn_hip.ops.render_chart, one launch per figure) from the
+statistics of evaluation_metrics/curves.py and written as PNG.  The other plots -- `param_plots`, `plot_elbo_gap`,
+`plot_prob_of_t` -- are not drawn."""
 import os
 import warnings
 
@@ -109,6 +111,9 @@ class Evaluator(object):
         self.start_predictions = (getattr(settings, "start_predictions", None) or
                                   getattr(self.args, "n_conditions", None))
         self.resample = getattr(settings, "resample", None) or 1
+        # the curve figures (plot_eval_values / test_temp_values): the x axis starts at n_conditions
+        self.n_conditions = getattr(settings, "n_conditions", None) or getattr(self.args, "n_conditions", None)
+        self.temperatures = getattr(settings, "temperatures", None)
         self.extra_plots = bool(getattr(settings, "extra_plots", False))
         self.debug_plot = bool(getattr(settings, "debug_plot", False))
         self._warned_plots = False
@@ -731,6 +736,62 @@ class Evaluator(object):
                 rows = [preds[t_list, k, 0, 0] for k in range(len(swept))]
             return [(rows, len(t_list), name)]
         return self._sheet(model_name, draw)[0]
+
+    # ---- the curve figures (error_metrics.py:600-1003), drawn by the chart kernel (rfn_hip.ops.render_chart)
+    def _curve_figures(self, entries, folder, suffix):
+        """the three figures of evaluation_metrics.curves.build_figures for `entries`, each rendered in one launch and
+        written to folder/<name><suffix>.png; returns the paths"""
+        from evaluation_metrics.curves import FIGURE_NAMES, build_figures
+        from rfn_hip import ops
+        from Utils.png import write_png
+        if self.n_conditions is None or self.n_trained is None:
+            raise ValueError("Evaluator: the curve figures need settings.n_conditions and the trained sequence length")
+        figures = build_figures(entries, int(self.n_conditions), int(self.n_trained))
+        os.makedirs(folder, exist_ok=True)
+        paths = []
+        for name in FIGURE_NAMES:
+            paths.append(os.path.join(folder, name + suffix + ".png"))
+            write_png(paths[-1], ops.render_chart(figures[name], scanlines=True))
+        return paths
+
+    def plot_eval_values(self, path, label_names, experiment_names):
+        """error_metrics.py:812-1003: best-of-N SSIM / PSNR / LPIPS against the frame index for several experiments,
+        read from `path + experiment + "/eval_folder/evaluations.pt"`: eval_plots_max (means with 95 % confidence
+        bands), eval_plots_max_median (medians with 2.5 % / 97.5 % quantile bands) and eval_plots_mean_mean (the mean
+        over draws with error bars), three panels each, x = n_conditions + arange(T), a dashed line at n_trained, a
+        grid, the legend under the panels; written into the LAST experiment's eval_folder, as the reference does.
+        1900 x 500 pixels (its 19 x 5 inches at 100 dpi).  Deviations: PNG instead of PDF, drawn by the chart kernel
+        with a 5x7 dot-matrix font; the median-LPIPS panel uses the x axis of the others (the reference's arange(0, T)
+        there is a slip); when an experiment's LPIPS entries are None (no weights were given) the LPIPS panels show
+        their title and "no LPIPS weights".  Touches neither the model nor torch's generators nor the loaders.  Returns
+        the three paths."""
+        if len(label_names) < len(experiment_names):
+            raise ValueError("Evaluator.plot_eval_values: %d labels for %d experiments" %
+                             (len(label_names), len(experiment_names)))
+        entries = []
+        for label, name in zip(label_names, experiment_names):
+            d = torch.load(path + name + "/eval_folder/evaluations.pt", map_location="cpu", weights_only=True)
+            print("Temperature is set to " + str(d["temperature"]) + " for experiment " + label)
+            entries.append((label, d))
+        return self._curve_figures(entries, path + experiment_names[-1] + "/eval_folder", "")
+
+    def test_temp_values(self, path, label_names, experiment_names):
+        """error_metrics.py:600-809: the three figures of plot_eval_values over the temperatures of ONE experiment:
+        curve k is `path + experiment_names[0] + "/eval_folder/t<T>evaluations.pt"` of settings.temperatures[k],
+        labelled "T= <T>"; written as eval_plots_max_temp, eval_plots_max_median_temp and eval_plots_mean_mean_temp
+        into experiment 0's eval_folder.  The same deviations and no side effects; label_names is unused, as in the
+        reference."""
+        if not self.temperatures:
+            raise ValueError("Evaluator.test_temp_values needs settings.temperatures")
+        folder = path + experiment_names[0] + "/eval_folder"
+        entries = []
+        for T in self.temperatures:
+            label = "T= " + str(T)
+            d = torch.load(folder + "/t" + str(T).replace(".", "") + "evaluations.pt", map_location="cpu",
+                           weights_only=True)
+            print("Temperature is set to " + str(d["temperature"]) + " for experiment " + label)
+            entries.append((label, d))
+        return self._curve_figures(entries, folder, "_temp")
 
     # ---- the analyses the reference's evaluator drives (error_metrics.py: plot_elbo_gap, plot_prob_of_t, param_plots)
     def elbo_gap(self, image, sample=False):

@@ -27,9 +27,11 @@ has no flag for it and the default is the reference's 20), get_fvd_values; the R
 with one printed line, and --test_temperature is refused (SRNN has no temperature).  Deviations: the SVG / VRNN
 baselines are not part of this package (any other model name is a ValueError); LPIPS entries are None when --lpips_weights is not given (the reference
 would need the lpips package's download); --debug_mnist / --use_validation_set evaluate the FIRST 1000 test sequences
-(the reference: a random 1000 for --debug_mnist); the curve figures plot_eval_values / test_temp_values and the figure of
-param_plots are not drawn -- one line says so when they would have run -- and --eval_parameters saves the tensors of
-Evaluator.param_analysis on the first test batch to `eval_folder/param_analysis.pt` instead.  The sheets are written to
+(the reference: a random 1000 for --debug_mnist); the curve figures of plot_eval_values / test_temp_values, the last
+step of a run, are PNG files drawn by the chart kernel (skipped with one line when the evaluations.pt files they read
+do not exist); the figure of param_plots is not drawn -- one line says so when it would have run -- and
+--eval_parameters saves the tensors of Evaluator.param_analysis on the first test batch to
+`eval_folder/param_analysis.pt` instead.  The sheets are written to
 the solver's own `eval_folder` (the run's --path under the working directory), which is the same directory when the
 driver is started where the training was."""
 import argparse
@@ -123,6 +125,32 @@ def build_evaluator(settings, i):
     return evaluator, args, exp + "/eval_folder", max_batches
 
 
+def draw_curve_figures(settings, evaluator):
+    """eval_settings.py:128-141, the driver's last step: Evaluator.test_temp_values under --test_temperature, else
+    Evaluator.plot_eval_values over all experiments, with --label_names (the experiment names when there are fewer
+    labels than experiments).  If a file the figures are read from does not exist (--no-calc_eval), or none of the
+    experiments is an RFN run, one line says so and nothing is drawn.  Returns the paths written."""
+    experiments = settings.experiment_names
+    labels = settings.label_names if len(settings.label_names) >= len(experiments) else experiments
+    if settings.test_temperature:
+        name = "test_temp_values"
+        needed = [settings.folder_path + experiments[0] + "/eval_folder/" + temperature_file_name(T)
+                  for T in settings.temperatures]
+    else:
+        name = "plot_eval_values"
+        needed = [settings.folder_path + e + "/eval_folder/evaluations.pt" for e in experiments]
+    if "rfn.pt" not in settings.model_path[:len(experiments)]:
+        # a run over baselines alone leaves nothing but its values in eval_folder (pinned by tests/test_srnn_eval.py);
+        # their curves are drawn when they are compared with an RFN run
+        print("eval_settings: the curve figures of %s are not drawn: none of the experiments is an RFN run (rfn.pt)" % name)
+        return []
+    missing = [p for p in needed if not os.path.exists(p)]
+    if missing:
+        print("eval_settings: the curve figures of %s are not drawn: %s does not exist" % (name, missing[0]))
+        return []
+    return getattr(evaluator, name)(settings.folder_path, labels, experiments)
+
+
 def main(settings):
     experiments = settings.experiment_names
     if len(settings.model_path) < len(experiments):
@@ -187,8 +215,7 @@ def main(settings):
                 evaluator.model.temperature = T
                 torch.save(eval_dict(evaluator.get_eval_values(model_name, max_batches=max_batches), T),
                            folder + "/" + temperature_file_name(T))
-    print("eval_settings: the curve figure %s is not drawn (line plots with text are not part of this package); the "
-          "values are in the files above" % ("test_temp_values" if settings.test_temperature else "plot_eval_values"))
+    draw_curve_figures(settings, evaluator)
 
 
 def add_bool_arg(parser, name, help, default=False):

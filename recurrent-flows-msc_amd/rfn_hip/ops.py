@@ -2727,6 +2727,89 @@ def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.
     return out
 
 
+def chart_chunk():
+    """records one workgroup of the chart kernel culls at a time (rfn_chart_chunk); the picture does not depend on it"""
+    return int(L.load().rfn_chart_chunk())
+
+
+def chart_font():
+    """the kernel's built-in 5x7 font (rfn_chart_font): int32 numpy [95, 5], row ch = character 32 + ch, one entry per
+    column from the left, bit r = the dot in row r from the top"""
+    import numpy as np
+    buf = (ctypes.c_longlong * (95 * 5))()
+    rc = L.load().rfn_chart_font(ctypes.cast(buf, ctypes.c_void_p))
+    if rc != 0:
+        raise RuntimeError("rfn_chart_font failed (code %d)" % rc)
+    return np.frombuffer(buf, dtype=np.int64).astype(np.int32).reshape(95, 5)
+
+
+def render_chart(chart, H=None, W=None, scanlines=False, out=None, bg=(255, 255, 255), device=None):
+    """A line chart as 8-bit RGB pixels (rfn_chart_render_u8; the pixel contract is DESIGN.md section 25).  `chart`: a
+    rfn_hip.chart.Figure or DisplayList (H, W and bg come from it; a given H / W must agree), or a display-list table
+    int32 [n, 12] -- a numpy array or CPU tensor, checked against the contract's coordinate bounds and uploaded, or a
+    contiguous device tensor, taken as it is -- painted on an H x W canvas of colour `bg` (r, g, b).  Returns uint8
+    [H, W, 3], or with scanlines=True [H, 1 + 3*W] whose lines start with the PNG filter byte 0 (Utils.png.write_png
+    takes either); `out` (optional) is a contiguous uint8 device tensor of that shape, at any byte address.  The device
+    is that of `out`, of a device table, `device`, or the current one.  One launch on the current stream; no CPU
+    fallback."""
+    import numpy as np
+    from . import chart as C
+    if isinstance(chart, C.Figure):
+        chart = C.build_display_list(chart)
+    if isinstance(chart, C.DisplayList):
+        if (H is not None and int(H) != chart.height) or (W is not None and int(W) != chart.width):
+            raise ValueError("render_chart: the figure is %dx%d, H x W = %sx%s was asked for" %
+                             (chart.height, chart.width, H, W))
+        H, W, bg, table = chart.height, chart.width, chart.bg, chart.table
+    else:
+        table = chart
+    if H is None or W is None:
+        raise TypeError("render_chart: a table needs the canvas size H, W")
+    H, W = int(H), int(W)
+    if not (1 <= H <= C.MAX_SIDE and 1 <= W <= C.MAX_SIDE):
+        raise ValueError("render_chart: the canvas is at most %d x %d pixels, got %d x %d" %
+                         (C.MAX_SIDE, C.MAX_SIDE, H, W))
+    bg = tuple(int(c) for c in bg)
+    if len(bg) != 3 or not all(0 <= c <= 255 for c in bg):
+        raise ValueError("render_chart: bg must be three bytes (r, g, b), got %s" % (bg,))
+    on_device = isinstance(table, torch.Tensor) and table.is_cuda
+    if on_device:
+        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != C.REC or not table.is_contiguous():
+            raise ValueError("render_chart: a device table must be contiguous int32 [n, %d], got %s %s" %
+                             (C.REC, table.dtype, tuple(table.shape)))
+    elif isinstance(table, (torch.Tensor, np.ndarray)):
+        table = C.check_table(table.numpy() if isinstance(table, torch.Tensor) else table)
+    else:
+        raise TypeError("render_chart: need a chart.Figure, a chart.DisplayList or an int32 [n, %d] table, got %s" %
+                        (C.REC, type(chart).__name__))
+    shape = (H, 1 + 3 * W) if scanlines else (H, W, 3)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or
+                            tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda):
+        raise ValueError("render_chart: out must be a contiguous uint8 device tensor %s" % (shape,))
+    if out is not None:
+        dev = out.device
+    elif on_device:
+        dev = table.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("render_chart: the chart kernel needs a GPU (no CPU fallback)")
+        dev = torch.device(device if device is not None else "cuda")
+        if dev.type != "cuda":
+            raise RuntimeError("render_chart: the chart kernel needs a GPU, got device %s (no CPU fallback)" % dev)
+    if on_device and table.device != dev:
+        raise ValueError("render_chart: the table is on %s, out on %s" % (table.device, dev))
+    if not on_device:
+        table = torch.from_numpy(table).to(dev)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    n = int(table.shape[0])
+    with torch.cuda.device(dev):
+        L.call("rfn_chart_render_u8", table.data_ptr() if n else None, n, H, W, bg[0] | bg[1] << 8 | bg[2] << 16,
+               1 if scanlines else 0, out.data_ptr(),
+               meta=("shell", "chart_render", 0.0, "%dx%dx%d" % (n, H, W), float(out.numel()) + 48.0 * n))
+    return out
+
+
 # LPIPS with the AlexNet trunk (rfn_hip/lpips.py holds the loader and the wrappers of csrc/lpips.hip)
 from .lpips import (LpipsAlexWeights, LpipsFeatures, lpips_alex, lpips_alex_distance, lpips_alex_features,  # noqa: E402,F401
                     lpips_alex_load, lpips_alex_pack, lpips_alex_sizes)
