@@ -349,6 +349,24 @@ int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, long h_ns, 
                                               int C, float* const* gwT, int G, int F, int H, int W, rfn_stream_t stream);
 /* label query for both (G = 0: the ungrouped entry point); "" when the shape has no mirrored route */
 const char* rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H, int W);
+/* The two forms above on maps whose rows are shorter than a staging unit of 8 pixels, which they refuse: W == 4 with an
+ * even H (a unit is two image rows of one frame) and H == W == 2 (a unit is two consecutive frames; F may be odd).
+ * rfn_conv3x3_wgrad_rows*: the arguments, checks, codes and output layout of rfn_conv3x3_wgrad_implicit*;
+ * rfn_conv3x3_wgrad_rows_mirrored*: those of rfn_conv3x3_wgrad_mirrored*.  -2 for every other (H, W); the label
+ * queries answer "" there. */
+int rfn_conv3x3_wgrad_rows_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
+                                  const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
+                                  rfn_stream_t stream);
+int rfn_conv3x3_wgrad_rows_grouped_bf16x3(const float* const* g, long g_ns, int Cout, const float* const* in1,
+                                          long in1_ns, int C1, const float* const* in2, long in2_ns, int C2,
+                                          float* const* gw, int G, int F, int H, int W, rfn_stream_t stream);
+const char* rfn_conv3x3_wgrad_rows_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W);
+int rfn_conv3x3_wgrad_rows_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C,
+                                           float* gwT, int F, int H, int W, rfn_stream_t stream);
+int rfn_conv3x3_wgrad_rows_mirrored_grouped_bf16x3(const float* const* h, long h_ns, int Cin, const float* const* g,
+                                                   long g_ns, int C, float* const* gwT, int G, int F, int H, int W,
+                                                   rfn_stream_t stream);
+const char* rfn_conv3x3_wgrad_rows_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H, int W);
 /* K split of a GROUPED launch of the LDS-DMA ring kernels (gemm_wgrad_dma_kernel, gemm_wgrad_dma_impl_kernel), as
  * host-only queries that launch nothing and run the very functions the kernels and launchers run.  The unit of work is
  * the flat stage space of one output tile: G * n_stages stages (n_stages = F * HW / 32), group g owning

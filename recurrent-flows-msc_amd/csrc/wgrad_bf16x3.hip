@@ -8,6 +8,7 @@
 //               planes of the input while staging (rfn_conv3x3_wgrad_implicit_bf16x3)
 //   * mirrored  the same for the few-output conv, Cout < Cin: the gradient's planes, taps mirrored and roles swapped
 //               (rfn_conv3x3_wgrad_mirrored_bf16x3)
+//   * implicit_rows / mirrored_rows  the two on 4-pixel rows and 2 x 2 maps (rfn_conv3x3_wgrad_rows[_mirrored]_bf16x3)
 // (its other two forms, f32 and scatter_f32, are the fp32 kernel of conv.hip).  The first three expand the SMALL operand
 // in HBM, so the shifted-window reads of a 3x3 weight gradient never reach their kernel and the 8 consecutive k (pixels) an
 // MFMA operand lane needs are 8 consecutive fp32 of one channel plane in NCHW: staged with 16-byte loads, split into
@@ -27,8 +28,9 @@ struct GemmWgradParams {
     int F, HW;  // frames, pixels per frame (HW % 4 == 0)
     long total; // F*HW
     int n_stages;
-    // implicit 3x3 mode (IMPL = 1): operand B row n = ci*9 + tap is the input plane ci shifted by the tap, read straight
-    // from the convolution's (two-source) input -- b = in1, b2 = in2 -- instead of from an im2col buffer in HBM
+    // implicit 3x3 mode (IMPL = 1; WG_ROWS4 / WG_ROWS2 on rows shorter than 8 pixels): operand B row n = ci*9 + tap is
+    // the input plane ci shifted by the tap, read straight from the convolution's (two-source) input -- b = in1,
+    // b2 = in2 -- instead of from an im2col buffer in HBM
     const float* b2;
     long b2_ns;
     int C1, C2, H, W;
@@ -247,6 +249,45 @@ __device__ __forceinline__ void wg_shift_split8(const float4 (&src)[2], const fl
     }
 }
 
+// Rows shorter than a staging unit (IMPL = WG_ROWS4 / WG_ROWS2 of gemm_wgrad_b3_kernel): the 8 pixels of a unit are
+//   * W == 4 (H even): the two image rows y0, y0 + 1 of one frame -- half h is row y0 + h + dy, one aligned 16-byte load,
+//     clamped to row y0 + h for the load with its own row-ok bit; the x shift happens inside the float4, zero fill at
+//     both ends, no edge element;
+//   * H == W == 2: two consecutive frames, one 16-byte load each (the second clamped to the first when it is past the
+//     last frame; the caller masks it); tap (dy, dx) is a fixed zero-filling permutation of the four pixels.
+// Unconditional loads like wg_tap_load; all masking in wg_shift_split4.
+constexpr int WG_ROWS4 = 2, WG_ROWS2 = 3;
+__host__ __device__ inline bool wg_rows_covers(int H, int W) {
+    return (W == 4 && H >= 2 && H % 2 == 0) || (H == 2 && W == 2);
+}
+constexpr int wg_rows_impl(int W) { return W == 4 ? WG_ROWS4 : WG_ROWS2; }
+// half a unit (4 pixels), out[y][x] = in[y + dy][x + dx] where inside -- ROWS4: one image row, x shift only (the row
+// shift was the load's); ROWS2: a 2 x 2 frame, both shifts -- zeroed unless `ok`, split into lanes c0 .. c0 + 3 of (hi, lo)
+template <int ROWS>
+__device__ __forceinline__ void wg_shift_split4(const float4 src, const int dy, const int dx, const bool ok, const int c0,
+                                                bf16x8& hi, bf16x8& lo) {
+    float v[4] = {src.x, src.y, src.z, src.w};
+    if (ROWS == WG_ROWS4) {
+        const float l[4] = {0.f, v[0], v[1], v[2]}, r[4] = {v[1], v[2], v[3], 0.f};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = dx < 0 ? l[c] : (dx > 0 ? r[c] : v[c]);
+    } else {
+        const float up[4] = {0.f, 0.f, v[0], v[1]}, dn[4] = {v[2], v[3], 0.f, 0.f};   // in[y - 1][x], in[y + 1][x]
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = dy < 0 ? up[c] : (dy > 0 ? dn[c] : v[c]);
+        const float l[4] = {0.f, v[0], 0.f, v[2]}, r[4] = {v[1], 0.f, v[3], 0.f};      // in[y][x - 1], in[y][x + 1]
+#pragma unroll
+        for (int c = 0; c < 4; ++c) v[c] = dx < 0 ? l[c] : (dx > 0 ? r[c] : v[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float x = ok ? v[c] : 0.f;
+        const __bf16 h = (__bf16)x;
+        hi[c0 + c] = h;
+        lo[c0 + c] = (__bf16)(x - (float)h);
+    }
+}
+
 // WM x WN waves (4 or 8) of TM x TN 32x32 tiles each.  The 8-wave 256-row configurations read both operands of the
 // big level-0 / level-1 gradients exactly once (a 128 x 128 tiling of a 256 x 256 gradient reads each of them twice,
 // and those launches sit on the HBM roof).
@@ -326,7 +367,30 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
 #pragma unroll
             for (int h = 0; h < 2; ++h) ast[u][h] = *reinterpret_cast<const float4*>(base + offa[h]);
         }
-        if (IMPL) {
+        if (IMPL >= WG_ROWS4) {
+            // short rows: half h of the unit is an image row (rowmask / edgemask: row-ok of half 0 / 1) or a frame
+            const unsigned qq = okq[0] ? q0 : 0u;
+            const unsigned f = qq / uHW, pix = qq - f * uHW;
+            const int y0 = (int)(pix >> 2);
+            const unsigned f1 = okq[1] ? f + 1u : f;
+            rowmask = IMPL == WG_ROWS4 ? 0u : ~0u;
+            edgemask = rowmask;
+#pragma unroll
+            for (int u = 0; u < BU; ++u) {
+                if (IMPL == WG_ROWS4) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int yy = y0 + h + udy[u];
+                        const bool rok = yy >= 0 && yy < p.H;
+                        bst[u][h] = *reinterpret_cast<const float4*>(uplane[u] + (long)f * uns[u] + (rok ? yy : y0 + h) * 4);
+                        (h ? edgemask : rowmask) |= (rok ? 1u : 0u) << u;
+                    }
+                } else {
+                    bst[u][0] = *reinterpret_cast<const float4*>(uplane[u] + (long)f * uns[u]);
+                    bst[u][1] = *reinterpret_cast<const float4*>(uplane[u] + (long)f1 * uns[u]);
+                }
+            }
+        } else if (IMPL) {
             const unsigned qq = okq[0] ? q0 : 0u;
             const unsigned f = qq / uHW, pix = qq - f * uHW;
             const int y = (int)(pix / (unsigned)p.W), x0 = (int)(pix - (unsigned)y * (unsigned)p.W);
@@ -375,7 +439,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_wgrad_b3_kernel(const GemmW
             const int o = (r0 + u * (NT / NU)) * RS + kg;
             if (BX || r0 + u * (NT / NU) < BN) {
                 const bool okr = n0 + r0 + u * (NT / NU) < p.N;
-                if (IMPL) {
+                if (IMPL >= WG_ROWS4) {
+                    bf16x8 hi, lo;
+                    wg_shift_split4<IMPL>(bst[u][0], udy[u], udx[u], okr && ((rowmask >> u) & 1u) && okq[0], 0, hi, lo);
+                    wg_shift_split4<IMPL>(bst[u][1], udy[u], udx[u], okr && ((edgemask >> u) & 1u) && okq[1], 4, hi, lo);
+                    Bh[o] = hi;
+                    Bl[o] = lo;
+                } else if (IMPL) {
                     bf16x8 hi, lo;
                     wg_shift_split8(bst[u], bedge[u], udx[u], okr && ((rowmask >> u) & 1u) && okq[0],
                                     (edgemask >> u) & 1u, hi, lo);
@@ -895,7 +965,8 @@ static void launch_gemm_wgrad(GemmWgradParams& p, hipStream_t s) {
 // launch_wgrad_route is the only place a route is mapped to a launch, the label queries of the C ABI read the same table.
 // Instantiations: gemm_wgrad_dma_kernel<WM,WN,TM,TN,KP,NST>, gemm_wgrad_b3_kernel<WM,WN,TM,TN,KP[,IMPL]>.
 enum WgradB3Route { DMA_256x256, DMA_64x256, R_256x192, R_256x256, R_64x256, R_256x64, R_128x128, IMPL_DMA_256x192,
-                    IMPL_256x192, IMPL_32x256, IMPL_128x128, IMPL_DMA_256x64, IMPL_DMA_256x128 };
+                    IMPL_256x192, IMPL_32x256, IMPL_128x128, IMPL_DMA_256x64, IMPL_DMA_256x128, ROWS4_128x128,
+                    ROWS2_128x128 };
 static const char* const kWgradB3Labels[] = {
     "gemm_wgrad_dma_kernel<2,4,4,2,32,2>",   // 256 x 256, two slots of 64 KB
     "gemm_wgrad_dma_kernel<1,8,2,1,32,3>",   // 64 x 256, ring of 3 x 40 KB
@@ -910,8 +981,10 @@ static const char* const kWgradB3Labels[] = {
     "gemm_wgrad_b3_kernel<2,2,2,2,64,1>",    // 128 x 128
     "gemm_wgrad_dma_impl_kernel<4,2,2,1>",   // implicit 3x3, narrow: 256 x 64, two workgroups per CU (mirrored conv3, C = 4)
     "gemm_wgrad_dma_impl_kernel<4,2,2,2>",   // 256 x 128 (mirrored conv3, C = 8)
+    "gemm_wgrad_b3_kernel<2,2,2,2,64,2>",    // short rows, W == 4: 128 x 128 (both orientations)
+    "gemm_wgrad_b3_kernel<2,2,2,2,64,3>",    // short rows, 2 x 2 maps
 };
-static_assert(sizeof(kWgradB3Labels) / sizeof(kWgradB3Labels[0]) == IMPL_DMA_256x128 + 1, "one label per route");
+static_assert(sizeof(kWgradB3Labels) / sizeof(kWgradB3Labels[0]) == ROWS2_128x128 + 1, "one label per route");
 static bool wgrad_dma_off() {
     static const int off = getenv("RFN_WGRAD_DMA") ? atoi(getenv("RFN_WGRAD_DMA")) == 0 : 0;
     return off;
@@ -979,6 +1052,28 @@ extern "C" const char* rfn_conv3x3_wgrad_mirrored_kernel_label_bf16x3(int Cin, l
     return choose_wgrad_implicit_mirrored(p, r) ? kWgradB3Labels[r] : "";
 }
 
+// Short-row forms (rfn_conv3x3_wgrad_rows[_mirrored]_bf16x3 below): 4-pixel rows and 2 x 2 maps, which the entry points
+// above refuse -- the 128 x 128 tile these shapes took as plain GEMMs, the shifted operand built from halves of a unit
+// (wg_shift_split4).  One route per staging form, both orientations; "": the staging does not cover the map.
+static bool choose_wgrad_rows(const GemmWgradParams& p, WgradB3Route& r) {
+    if (!wg_rows_covers(p.H, p.W)) return false;
+    r = wg_rows_impl(p.W) == WG_ROWS4 ? ROWS4_128x128 : ROWS2_128x128;
+    return true;
+}
+static const char* wgrad_rows_label(int H, int W) {
+    GemmWgradParams p = wgrad_shape(0, 0, 0, 0, 0, 0, H * W);
+    p.H = H; p.W = W;
+    WgradB3Route r;
+    return choose_wgrad_rows(p, r) ? kWgradB3Labels[r] : "";
+}
+extern "C" const char* rfn_conv3x3_wgrad_rows_kernel_label_bf16x3(int Cout, long g_ns, int G, int F, int H, int W) {
+    return wgrad_rows_label(H, W);
+}
+extern "C" const char* rfn_conv3x3_wgrad_rows_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H,
+                                                                           int W) {
+    return wgrad_rows_label(H, W);
+}
+
 // K split of the grouped ring launches, as queries that launch nothing: the workgroups per output tile the launchers
 // start, and the parts (group, first stage, count) of workgroup w of Wt -- the very functions the kernels run
 extern "C" int rfn_wgrad_split_workgroups(int tiles, int G, int n_stages) {
@@ -1013,6 +1108,8 @@ static void launch_wgrad_route(GemmWgradParams& p, WgradB3Route r, hipStream_t s
         case IMPL_128x128:     return launch_gemm_wgrad<2, 2, 2, 2, 64, 1>(p, s);
         case IMPL_DMA_256x64:  return launch_gemm_wgrad_dma_impl<4, 2, 2, 1>(p, s);
         case IMPL_DMA_256x128: return launch_gemm_wgrad_dma_impl<4, 2, 2, 2>(p, s);
+        case ROWS4_128x128:    return launch_gemm_wgrad<2, 2, 2, 2, 64, WG_ROWS4>(p, s);
+        case ROWS2_128x128:    return launch_gemm_wgrad<2, 2, 2, 2, 64, WG_ROWS2>(p, s);
     }
 }
 
@@ -1070,10 +1167,11 @@ extern "C" int rfn_gemm_wgrad_grouped_bf16x3(const float* const* a, long a_ns, i
 static int rfn_conv3x3_wgrad_implicit_bf16x3_body(int G, const float* const* g, long g_ns, int Cout,
                                                   const float* const* in1, long in1_ns, int C1, const float* const* in2,
                                                   long in2_ns, int C2, float* const* gw, int F, int H, int W,
-                                                  rfn_stream_t stream) {
+                                                  rfn_stream_t stream, bool rows = false) {
     RFN_CHECK_ARG(g && in1 && gw && Cout > 0 && C1 > 0 && C2 >= 0 && (C2 == 0 || in2) && F >= 0, -1);
     RFN_CHECK_ARG(H > 0 && W > 0, G > 0 ? -2 : -1);
-    RFN_CHECK_ARG(W % 8 == 0 && g_ns % 4 == 0 && in1_ns % 4 == 0 && (C2 == 0 || in2_ns % 4 == 0), -2);
+    RFN_CHECK_ARG((rows ? wg_rows_covers(H, W) : W % 8 == 0) && g_ns % 4 == 0 && in1_ns % 4 == 0 &&
+                      (C2 == 0 || in2_ns % 4 == 0), -2);
     for (int i = 0; i < (G > 0 ? G : 1); ++i)
         RFN_CHECK_ARG(g[i] && in1[i] && gw[i] && (C2 == 0 || in2[i]) && wg_aligned16(g[i], in1[i], C2 ? in2[i] : in1[i]),
                       -3);
@@ -1081,7 +1179,9 @@ static int rfn_conv3x3_wgrad_implicit_bf16x3_body(int G, const float* const* g, 
     if (F == 0) return 0;
     GemmWgradParams p = wgrad_params(G, g, g_ns, Cout, in1, in1_ns, C2 ? in2 : nullptr, 9 * (C1 + C2), gw, F, H * W);
     p.b2_ns = C2 ? in2_ns : in1_ns; p.C1 = C1; p.C2 = C2; p.H = H; p.W = W;
-    launch_wgrad_route(p, choose_wgrad_implicit(p), (hipStream_t)stream);
+    WgradB3Route r = rows ? ROWS4_128x128 : choose_wgrad_implicit(p);
+    if (rows) choose_wgrad_rows(p, r);
+    launch_wgrad_route(p, r, (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
 }
@@ -1106,17 +1206,18 @@ extern "C" int rfn_conv3x3_wgrad_implicit_grouped_bf16x3(const float* const* g, 
 // shape that passes the checks has a mirrored route (choose_wgrad_implicit_mirrored refuses only W % 8 != 0).
 static int rfn_conv3x3_wgrad_mirrored_bf16x3_body(int G, const float* const* h, long h_ns, int Cin,
                                                   const float* const* g, long g_ns, int C, float* const* gwT, int F, int H,
-                                                  int W, rfn_stream_t stream) {
+                                                  int W, rfn_stream_t stream, bool rows = false) {
     RFN_CHECK_ARG(h && g && gwT && Cin > 0 && C > 0 && F >= 0, -1);
     RFN_CHECK_ARG(H > 0 && W > 0, G > 0 ? -2 : -1);
-    RFN_CHECK_ARG(W % 8 == 0 && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
+    RFN_CHECK_ARG((rows ? wg_rows_covers(H, W) : W % 8 == 0) && h_ns % 4 == 0 && g_ns % 4 == 0, -2);
     for (int i = 0; i < (G > 0 ? G : 1); ++i) RFN_CHECK_ARG(h[i] && g[i] && gwT[i] && wg_aligned16(h[i], g[i]), -3);
     RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
     if (F == 0) return 0;
     GemmWgradParams p = wgrad_params(G, h, h_ns, Cin, g, g_ns, nullptr, 9 * C, gwT, F, H * W);
     p.b2_ns = g_ns; p.C1 = C; p.H = H; p.W = W; p.mirror = 1;
     WgradB3Route r = IMPL_128x128;
-    choose_wgrad_implicit_mirrored(p, r);
+    if (rows) choose_wgrad_rows(p, r);
+    else choose_wgrad_implicit_mirrored(p, r);
     launch_wgrad_route(p, r, (hipStream_t)stream);
     RFN_LAUNCH_CHECK();
     return 0;
@@ -1131,6 +1232,35 @@ extern "C" int rfn_conv3x3_wgrad_mirrored_grouped_bf16x3(const float* const* h, 
                                                          rfn_stream_t stream) {
     RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
     return rfn_conv3x3_wgrad_mirrored_bf16x3_body(G, h, h_ns, Cin, g, g_ns, C, gwT, F, H, W, stream);
+}
+
+// The two forms above on maps with rows shorter than a staging unit: 4-pixel rows (H even) and 2 x 2 maps, the shifted
+// operand built from halves of a unit (gemm_wgrad_b3_kernel<..., WG_ROWS4 / WG_ROWS2>).  Same arguments, checks and
+// output layouts; -2 for every other map.
+extern "C" int rfn_conv3x3_wgrad_rows_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
+                                             const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
+                                             rfn_stream_t stream) {
+    RFN_CHECK_ARG(g && in1 && gw && (C2 <= 0 || in2), -1);
+    return rfn_conv3x3_wgrad_implicit_bf16x3_body(0, &g, g_ns, Cout, &in1, in1_ns, C1, &in2, in2_ns, C2, &gw, F, H, W,
+                                                  stream, true);
+}
+extern "C" int rfn_conv3x3_wgrad_rows_grouped_bf16x3(const float* const* g, long g_ns, int Cout, const float* const* in1,
+                                                     long in1_ns, int C1, const float* const* in2, long in2_ns, int C2,
+                                                     float* const* gw, int G, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
+    return rfn_conv3x3_wgrad_implicit_bf16x3_body(G, g, g_ns, Cout, in1, in1_ns, C1, in2, in2_ns, C2, gw, F, H, W, stream,
+                                                  true);
+}
+extern "C" int rfn_conv3x3_wgrad_rows_mirrored_bf16x3(const float* h, long h_ns, int Cin, const float* g, long g_ns, int C,
+                                                      float* gwT, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(h && g && gwT, -1);
+    return rfn_conv3x3_wgrad_mirrored_bf16x3_body(0, &h, h_ns, Cin, &g, g_ns, C, &gwT, F, H, W, stream, true);
+}
+extern "C" int rfn_conv3x3_wgrad_rows_mirrored_grouped_bf16x3(const float* const* h, long h_ns, int Cin,
+                                                              const float* const* g, long g_ns, int C, float* const* gwT,
+                                                              int G, int F, int H, int W, rfn_stream_t stream) {
+    RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
+    return rfn_conv3x3_wgrad_mirrored_bf16x3_body(G, h, h_ns, Cin, g, g_ns, C, gwT, F, H, W, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------------ im2col (3x3, pad 1)

@@ -504,13 +504,23 @@ WgradPlan = collections.namedtuple("WgradPlan", "form G M Nc launches")
 _TAP_SCATTER, _IM2COL = ("rfn_tap_scatter_f32", "tap_scatter"), ("rfn_im2col3x3_f32", "im2col3x3")
 
 
-def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=False, min_pixels=0, stacked=False):
+def wgrad_short_rows():
+    """what the training path passes as wgrad_plan's `short_rows`: true unless RFN_WGRAD_SHORT_ROWS=0 (A/B runs)"""
+    return os.environ.get("RFN_WGRAD_SHORT_ROWS") != "0"
+
+
+def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=False, min_pixels=0, stacked=False,
+               short_rows=False):
     """How the weight gradient(s) [Cout, C1 + C2, ks, ks] of a convolution on N frames of H x W are computed, from shapes,
     strides and options alone (no tensor, no device): the one decision of the path, which _wgrad_run executes and the
     host tests query.  G = 0: one gradient; G >= 1: G of one shape in grouped launches.  g_ns / in1_ns: frame strides
     of the output gradient and of the first input source (default: dense).  few_out: the caller is a Conv2dZeros
     (one-source input), which alone may take the mirrored kernel (from `min_pixels` pixels G * N * H * W) or the fp32
     tap route.  stacked: the G output gradients are the slices of one contiguous [G, N, Cout, H, W] buffer.
+    short_rows: on maps whose rows are shorter than a staging unit (4 x 4, 2 x 2: where the library's query names a
+    kernel) a split-precision 3x3 gradient is ONE launch that shifts the taps while staging -- "mirrored_rows" for a
+    Conv2dZeros, "implicit_rows" for every other conv whatever Cin against Cout (no cat of a two-source input) --
+    instead of im2col / tap scatter + GEMM.  The training path passes wgrad_short_rows().
     Returns WgradPlan(form, G, M, Nc, launches): the form (table in DESIGN.md, "Where the labels come from"), the GEMM
     dimensions gw[M][Nc] and, in order, the (entry point, label) of every library launch.  CONV_PRECISION,
     RFN_WGRAD_IMPLICIT, RFN_WGRAD_MIRRORED and the label queries are read on every call."""
@@ -537,6 +547,15 @@ def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=Fal
         return plan("f32", Cout, ks * ks * Cin, f32(ks, Cout), *([("rfn_wgrad_finish_f32", "wgrad_finish")] if ks > 1 else []))
     if ks == 1:
         return plan("gemm", Cout, Cin, gemm(Cout, Cin, g_ns, x_ns))
+    if short_rows and b3 and ks == 3:
+        if few_out:
+            launch = _b3_launch(G, "rfn_conv3x3_wgrad_rows_mirrored_bf16x3", Cin, in1_ns, Cout, G, N, H, W)
+            if launch[1]:   # ('': the short-row staging does not cover this map)
+                return plan("mirrored_rows", Cin, 9 * Cout, launch)
+        else:
+            launch = _b3_launch(G, "rfn_conv3x3_wgrad_rows_bf16x3", Cout, g_ns, G, N, H, W)
+            if launch[1]:
+                return plan("implicit_rows", Cout, 9 * Cin, launch)
     if Cin <= Cout:   # the input is the small operand: its shifted planes built while staging, or expanded in memory
         if W % 8 == 0 and os.environ.get("RFN_WGRAD_IMPLICIT") != "0":
             return plan("implicit", Cout, 9 * Cin,
@@ -595,9 +614,9 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
             L.call(entry, L.dev(gwt), L.dev(out[0]), Cout, Cin, ks, 0, meta=_shell(label, out[0], 2))
     elif form == "gemm":
         out = [t.view(Cout, Cin, 1, 1) for t in _gemm_wgrad(G, gs, cat(), Cout, Cin, arena, next(todo))]
-    elif form == "implicit":   # rows (ci, tap) of the implicit operand: already the torch layout
+    elif form in ("implicit", "implicit_rows"):   # rows (ci, tap) of the implicit operand: already the torch layout
         gw = _b3_wgrad(next(todo), G, [(gs, "g", Cout), (in1s, "in1", C1), (in2s, "in2", C2)], Cout, 9 * Cin, (N, H, W), arena,
-                       " implicit3x3")
+                       " %s3x3" % form)
         out = [t.view(Cout, Cin, 3, 3) for t in gw]
     elif form == "im2col":
         x9s = [torch.empty((N, 9 * Cin, H, W), device=dev_, dtype=torch.float32) for _ in range(n)]
@@ -612,15 +631,16 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
         xs, gss = cat(), tap_scatter()
         gw = _gemm_wgrad(G, gss, xs, 9 * Cout, Cin, arena, next(todo))  # [g][tap*Cout + co][ci]
         out = list(gw.view(n, 3, 3, Cout, Cin).permute(0, 3, 4, 1, 2).contiguous())
-    else:   # mirrored: the input through the ring, the (dense) gradient shifted while staging; gw is [g][ci][co][tap]
+    else:   # mirrored[_rows]: the input as it is, the (dense) gradient shifted while staging; gw is [g][ci][co][tap]
+        assert form in ("mirrored", "mirrored_rows"), plan
         gw = _b3_wgrad(next(todo), G, [(in1s, "x", Cin), ([g.contiguous() for g in gs], "g", Cout)], Cin, 9 * Cout, (N, H, W),
-                       arena, " mirrored3x3")
+                       arena, " %s3x3" % form)
         out = list(gw.view(n, Cin, Cout, 3, 3).permute(0, 2, 1, 3, 4).contiguous())
     assert next(todo, None) is None, plan
     return out
 
 
-def _conv_wgrad(G, in1s, in2s, gs, Cout, ks, arena, g_stacked=None, few_out=False, min_pixels=0):
+def _conv_wgrad(G, in1s, in2s, gs, Cout, ks, arena, g_stacked=None, few_out=False, min_pixels=0, short_rows=False):
     """wgrad_plan of the operands, executed: what every public weight-gradient function of a convolution is"""
     N, C1, H, W = in1s[0].shape
     if in2s is not None and in2s[0] is None:
@@ -628,19 +648,19 @@ def _conv_wgrad(G, in1s, in2s, gs, Cout, ks, arena, g_stacked=None, few_out=Fals
     if not (G and g_stacked is not None and g_stacked.is_contiguous() and tuple(g_stacked.shape) == (G, N, Cout, H, W)):
         g_stacked = None   # (else the G gradients are its slices, in list order)
     plan = wgrad_plan(G, N, C1, 0 if in2s is None else int(in2s[0].shape[1]), Cout, H, W, ks, _frame_stride(gs[0]),
-                      _frame_stride(in1s[0]), few_out, min_pixels, g_stacked is not None)
+                      _frame_stride(in1s[0]), few_out, min_pixels, g_stacked is not None, short_rows)
     return _wgrad_run(plan, in1s, in2s, gs, ks, arena, g_stacked)
 
 
-def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_stacked=None):
+def conv2d_wgrad_grouped(in1_list, in2_list, g_list, Cout, ks, arena=None, g_stacked=None, short_rows=False):
     """the weight gradients of G convolutions of ONE shape (the K steps of a flow level) in grouped launches: list of G
     tensors [Cout, Cin, ks, ks].  g_stacked: the buffer the G gradients are slices of, if they are."""
-    return _conv_wgrad(len(g_list), in1_list, in2_list, g_list, Cout, ks, arena, g_stacked)
+    return _conv_wgrad(len(g_list), in1_list, in2_list, g_list, Cout, ks, arena, g_stacked, short_rows=short_rows)
 
 
-def conv2d_wgrad(in1, in2, g, Cout, ks, arena=None):
+def conv2d_wgrad(in1, in2, g, Cout, ks, arena=None, short_rows=False):
     """returns gw [Cout, Cin, ks, ks]"""
-    return _conv_wgrad(0, [in1], None if in2 is None else [in2], [g], Cout, ks, arena)[0]
+    return _conv_wgrad(0, [in1], None if in2 is None else [in2], [g], Cout, ks, arena, short_rows=short_rows)[0]
 
 
 TAP_MAX_COUT = 8  # 3x3 convs with at most this many outputs run tap-expanded (1x1 to 9*C channels + shift-add)
@@ -673,9 +693,9 @@ def zeros_conv_fwd(x, w, b, logs, wpk=None, prec=None, taps=None):
     return o
 
 
-def zeros_conv_wgrad(x, g_pre, C, ks, arena=None):
+def zeros_conv_wgrad(x, g_pre, C, ks, arena=None, short_rows=False):
     """weight gradient of the conv inside Conv2dZeros given g_pre = grad wrt (conv + b): wgrad_plan with few_out"""
-    return _conv_wgrad(0, [x], None, [g_pre], C, ks, arena, few_out=True)[0]
+    return _conv_wgrad(0, [x], None, [g_pre], C, ks, arena, few_out=True, short_rows=short_rows)[0]
 
 
 LEVEL_MIRRORED_MIN_PIXELS = 1 << 17
@@ -689,10 +709,10 @@ def level_mirrored_min_pixels():
     return int(env) if env is not None else LEVEL_MIRRORED_MIN_PIXELS
 
 
-def zeros_conv_wgrad_grouped(h2_list, go_list, C, arena=None, g_stacked=None, ks=3, min_pixels=0):
+def zeros_conv_wgrad_grouped(h2_list, go_list, C, arena=None, g_stacked=None, ks=3, min_pixels=0, short_rows=False):
     """zeros_conv_wgrad for the G convolutions of one shape of a flow level: list of G tensors [C, Cin, ks, ks]; the
     mirrored launch only where the G groups have `min_pixels` pixels together"""
-    return _conv_wgrad(len(go_list), h2_list, None, go_list, C, ks, arena, g_stacked, True, min_pixels)
+    return _conv_wgrad(len(go_list), h2_list, None, go_list, C, ks, arena, g_stacked, True, min_pixels, short_rows)
 
 
 def conv_epilogue_bwd(y, gy, logs, ep_mode, act, want_gl=True, arena=None, inplace=True):
@@ -865,7 +885,7 @@ class ConvFn(torch.autograd.Function):
             if fewcin_ok(in1, in2, w, ep_mode) and Cin == 1 and Cout == 16:
                 gw = conv3x3_c1_wgrad16(in1, gy)
             else:
-                gw = conv2d_wgrad(in1, in2, gy, Cout, ks)
+                gw = conv2d_wgrad(in1, in2, gy, Cout, ks, short_rows=wgrad_short_rows())
         return g1, g2, gw, gp0, gp1, None, None, None, None
 
 
@@ -1020,7 +1040,8 @@ def _net_bwd(go, out, cond, h1, h2, p, act, route, pk, arena, gz, gcond, acc_con
     w1, n1b, n1l, w2, n2b, n2l, w3 = p.w1, p.n1b, p.n1l, p.w2, p.n2b, p.n2l, p.w3
     Ch, (Hd, Cc, k1, k2, k3) = C // 2, _net_dims(p, cond)
     dfr = defer is not None
-    gw3 = None if dfr else zeros_conv_wgrad(h2, go, C, k3, arena)
+    rows = wgrad_short_rows()
+    gw3 = None if dfr else zeros_conv_wgrad(h2, go, C, k3, arena, rows)
     # the fused kernel needs the step's backward stream (POPackPlan: at most 16 channels) and, past an activation, the
     # forward's masks; what admits "po" ('mixed' arithmetic, Hd = 256) admits "dgrad_act" in its place
     chain = route.bwd_chain
@@ -1032,23 +1053,23 @@ def _net_bwd(go, out, cond, h1, h2, p, act, route, pk, arena, gz, gcond, acc_con
             w2f = _pack(pk, "w2_dgrad", lambda: b.conv(w2, True))
     if chain == "po":
         gh2, gh1, part = coupling_po_bwd(go.contiguous(), pk["po_bwd"], _f(n1l), _f(n2l), masks, act)
-        gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
+        gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena, rows)
         o4 = torch.empty((4, 256), device=go.device, dtype=torch.float32)
         gn1b, gn1l, gn2b, gn2l = o4[0], o4[1], o4[2], o4[3]
     elif chain == "dgrad_act":
         gh2, gn2b, gn2l = conv2d_dgrad_act(go, w3f, h2, _f(n2l), act, Hd, k3, arena)
-        gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
+        gw2 = None if dfr else conv2d_wgrad(h1, None, gh2, Hd, k2, arena, rows)
         gh1, gn1b, gn1l = conv2d_dgrad_act(gh2, w2f, h1, _f(n1l), act, Hd, k2, arena)
     else:
         gh2 = conv2d_raw(go, None, w3f, Hd, k3)
         # ---- actnorm2 + act bwd, conv2 (1x1) bwd
         gh2, gn2b, gn2l = conv_epilogue_bwd(h2, gh2, _f(n2l), 1, act, arena=arena)
-        gw2 = conv2d_wgrad(h1, None, gh2, Hd, k2, arena)
+        gw2 = conv2d_wgrad(h1, None, gh2, Hd, k2, arena, rows)
         gh1 = conv2d_raw(gh2, None, w2f, Hd, k2)
         # ---- actnorm1 + act bwd, conv1 bwd (grad flows to z1 (accumulated into gz's first half) and to cond)
         gh1, gn1b, gn1l = conv_epilogue_bwd(h1, gh1, _f(n1l), 1, act, arena=arena)
     z1, c2 = out[:, :Ch], (cond if Cc > 0 else None)
-    gw1 = None if dfr else conv2d_wgrad(z1, c2, gh1, Hd, k1, arena)
+    gw1 = None if dfr else conv2d_wgrad(z1, c2, gh1, Hd, k1, arena, rows)
     if chain == "po":
         ticket = FinishTicket(part, w1, gw1, _f(n1b), w2, gw2, _f(n2b), o4, step)
         if fin is not None:
@@ -1317,10 +1338,12 @@ class GlowLevelFn(torch.autograd.Function):
                 tail = _glow_shell_bwd(outs[k - 1], prm[k], Wd[k], tail.gz, gWst[k], gab, gal, os_[k - 1], gdl, prm[k - 1],
                                        clamp_type, arena, go_all[k - 1])
         if defer is not None:
-            gw1 = conv2d_wgrad_grouped(defer.z1, None if defer.c2[0] is None else defer.c2, defer.gh1, Hd, k1, arena)
-            gw2 = conv2d_wgrad_grouped(defer.h1, None, defer.gh2, Hd, k2, arena)
+            rows = wgrad_short_rows()
+            gw1 = conv2d_wgrad_grouped(defer.z1, None if defer.c2[0] is None else defer.c2, defer.gh1, Hd, k1, arena,
+                                       short_rows=rows)
+            gw2 = conv2d_wgrad_grouped(defer.h1, None, defer.gh2, Hd, k2, arena, short_rows=rows)
             gw3 = zeros_conv_wgrad_grouped(defer.h2, defer.go, C, arena, g_stacked=go_all, ks=k3,
-                                           min_pixels=level_mirrored_min_pixels())
+                                           min_pixels=level_mirrored_min_pixels(), short_rows=rows)
             grads = [g._replace(w1=a, w2=b, w3=c) for g, a, b, c in zip(grads, gw1, gw2, gw3)]
         if fin:
             coupling_po_bwd_finish([t._replace(gw1=grads[t.step].w1, gw2=grads[t.step].w2) for t in fin])
@@ -1840,7 +1863,7 @@ class ConvLSTMCellFn(torch.autograd.Function):
                L.dev(pe[0]), L.dev(pe[1]), L.dev(pe[2]), L.dev(gcc), gpp, gpns, N, Hc, HW,
                meta=_shell("convlstm_gates_bwd", gates, 3.25))
         gb = conv_epilogue_bwd(None, gcc, None, 3, 0, want_gl=False)[1] if ctx.has_bias else None
-        gw = conv2d_wgrad(x, h, gcc, 4 * Hc, ks)
+        gw = conv2d_wgrad(x, h, gcc, 4 * Hc, ks, short_rows=wgrad_short_rows())
         gx = torch.empty_like(x)
         ghp_ = torch.empty_like(h)
         conv2d_raw(gcc, None, pack_weight(w, True), Cx + Hc, ks, 0, None, None, 0, out1=gx, out2=ghp_, cout_split=Cx)
@@ -1916,7 +1939,7 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         G = gcc.view(S * B, 4 * Hc, H, W)
         gx_all = smallmap_dense(G, pk_xb, Cx).view(S, B, Cx, H, W) if ctx.needs_input_grad[0] else None
         h_prev_all = torch.cat([h0.unsqueeze(0), h_all[:S - 1]], 0).view(S * B, Hc, H, W)
-        gw = conv2d_wgrad(x_all.view(S * B, Cx, H, W), h_prev_all, G, 4 * Hc, 3)
+        gw = conv2d_wgrad(x_all.view(S * B, Cx, H, W), h_prev_all, G, 4 * Hc, 3, short_rows=wgrad_short_rows())
         gb = G.sum(dim=(0, 2, 3)) if ctx.has_bias else None
         return gx_all, gh_rec, gc, gw, gb
 

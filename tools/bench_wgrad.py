@@ -4,6 +4,9 @@ python tools/bench_wgrad.py level [frames ...]: the three weight gradients of a 
 steps per level), as ten single launches and as one grouped launch, GEMM launches only (HIP events of rfn_hip.lib.PROFILE).
 conv3 gets a second row, `mirrored`: tap scatter + GEMM (both launches counted) beside the one mirrored launch that shifts
 the gradient while staging.  python tools/bench_wgrad.py conv3 [frames ...]: the conv3 rows only.
+python tools/bench_wgrad.py rows [frames ...]: conv1 and conv3 of the two deepest levels (4 x 4 and 2 x 2 maps, ten groups):
+the expanding route -- its im2col / tap-scatter passes and its GEMM reported apart -- beside the one short-row launch
+(builds without the short-row forms print the expanding route only).
 RFN_PKG_DIR selects another build of the package (A/B on the same box, as bench.py)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,7 +100,49 @@ def level(F_, G=10, only=None):
         del h, gh, z, cond, go
 
 
+def _parts_ms(fn, reps=5):
+    """fn() reps times after one warm-up: median ms of (expansion passes, weight-gradient launches), launches per call"""
+    fn()
+    torch.cuda.synchronize()
+    rows = []
+    for _ in range(reps):
+        L.PROFILE = []
+        fn()
+        torch.cuda.synchronize()
+        ev = [(m[0], m[1], e0.elapsed_time(e1)) for (_, m, e0, e1) in L.PROFILE if m is not None]
+        L.PROFILE = None
+        rows.append((sum(t for k, n, t in ev if n in ("tap_scatter", "im2col3x3")), sum(t for k, n, t in ev if k == "wgrad")))
+    med = lambda v: sorted(v)[len(v) // 2]
+    return med([r[0] for r in rows]), med([r[1] for r in rows]), len(ev)
+
+
+def rows(F_, G=10):
+    """conv1 (3x3, C/2 + cond -> 256) and conv3 (3x3, 256 -> C) of levels 3 (4 x 4) and 4 (2 x 2)"""
+    torch.manual_seed(0)
+    rn = lambda *shape: torch.randn(*shape, device="cuda")
+    has_rows = hasattr(K, "wgrad_short_rows")
+    for lvl, (C, Cc, S) in ((3, (32, 128, 4)), (4, (64, 256, 2))):
+        h, gh = [rn(F_, 256, S, S) for _ in range(G)], [rn(F_, 256, S, S) for _ in range(G)]
+        z, cond, go = [rn(F_, C, S, S) for _ in range(G)], rn(F_, Cc, S, S), rn(G, F_, C, S, S)
+        z1, gl = [t[:, :C // 2] for t in z], [go[i] for i in range(G)]
+        for name, old, new in (
+                ("conv1 256x%d" % (9 * (C // 2 + Cc)), lambda **kw: K.conv2d_wgrad_grouped(z1, [cond] * G, gh, 256, 3, **kw),
+                 None),
+                ("conv3 %dx256" % (9 * C), lambda **kw: K.zeros_conv_wgrad_grouped(h, gl, C, g_stacked=go, **kw), None)):
+            tp, tg, n = _parts_ms(old)
+            row = "F%d level %d %-15s passes %7.3f + GEMM %7.3f = %7.3f ms in %2d launches" % (F_, lvl, name, tp, tg, tp + tg, n)
+            if has_rows:
+                _, tr, nr = _parts_ms(lambda: old(short_rows=True))
+                row += "   short rows %7.3f ms in %d launch" % (tr, nr)
+            print(row, flush=True)
+        del h, gh, z, cond, go
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "rows":
+        for F_ in [int(v) for v in sys.argv[2:]] or [608, 76]:
+            rows(F_)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] in ("level", "conv3"):
         for F_ in [int(v) for v in sys.argv[2:]] or [608, 76]:
             level(F_, only="conv3" if sys.argv[1] == "conv3" else None)
