@@ -820,6 +820,20 @@ int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long
                                 int num_digits, int step_length, int deterministic, long seed, long split,
                                 long first_id, rfn_stream_t stream);
 
+/* The synchronized variant (MovingMNIST_synchronized, stochasticMovingMnist.py:131-248): all sequences share one
+ * trajectory per digit, only the digit identities differ.  Walk of digit n: idx = randint(N), sx, sy = randint(S - 28),
+ * dx = dy = 3 (a constant whatever step_length is, as the reference has it), then per frame the y-bounce and x-bounce
+ * of the entry above with step_length and deterministic.  idx is draw 0 at the counter (0, retry, sequence id, n) of
+ * the entry above; every other draw uses the shared counter (j, retry, 2^64 - 1, n), j = 1 for sx, 2 for sy, 3, 4, ...
+ * for the bounce redraws in walk order (sequence ids are non-negative, so no id collides with it).  out, traj and the
+ * limits are those of the entry above.  hit_addr: the device address of hit, int32 [B, T] (4-byte aligned), or 0 for
+ * none (passed as an integer like the byte outputs' out_addr); hit[b, t] is the largest n + 1 over the digits that
+ * either bounce branch clamped on frame t (the reference's hit_boundary: the last digit wins), 0 if none; every row
+ * holds the same values.  No atomics, every output element is written exactly once.  One launch. */
+int rfn_moving_mnist_sync_render_f32(const void* digits, int N, float* out, long long* traj, long hit_addr, int B, int T,
+                                     int C, int S, int num_digits, int step_length, int deterministic, long seed,
+                                     long split, long first_id, rfn_stream_t stream);
+
 /* ---- addressed normal noise  (the draws of RFN.predict_draws and of the Evaluator's batched best-of-N; DESIGN.md
  * section 16).  One launch fills up to 8 tensors ("slots") of shape [rows, numel_j], fp32 contiguous, with N(0,1) values.
  * Each value depends only on its address, not on the launch geometry.

@@ -20,6 +20,16 @@
 //   for r <= 70000), else the result is high64(m).
 // Same (seed, split, sequence id) -> same bytes, on any grid, any batch composition and any number of ranks.
 //
+// Synchronized variant (MovingMNIST_synchronized, stochasticMovingMnist.py:131-248; rfn_moving_mnist_sync_render_f32):
+// all sequences share one trajectory per digit, only the digit identities differ.
+//   idx = randint(N); sx = randint(S-D); sy = randint(S-D); dx = dy = 3 (a constant whatever L is, as the reference has
+//   it); then the frame loop above with L and the deterministic flag.
+//   idx is draw 0 at the plain counter (0, retry, sequence id, n); every other draw uses the shared counter
+//   (j, retry, 2^64-1, n): j = 1 for sx, 2 for sy, 3, 4, ... for the bounce redraws in walk order.  Sequence ids are
+//   non-negative (< 2^63), so the shared address collides with none of them.  Same key, same bounded draw.
+//   hit[b, t] = the largest n + 1 over the digits that either bounce branch clamped on frame t, 0 if none (the
+//   reference's hit_boundary, which it overwrites in digit order); every row b holds the same values.
+//
 // One workgroup per (sequence, frame): lanes 0..num_digits-1 replay their digit's walk up to the frame (at most
 // 4 draws per step; T is tens of steps) and publish (idx, y, x) in LDS; the workgroup stages the digits as float32 in
 // LDS and writes the frame with 16-byte stores (scalar stores when S*S is not a multiple of 4), every output pixel
@@ -70,14 +80,61 @@ __device__ __forceinline__ int draw_below(Draws& d, uint64_t r) {
     }
 }
 
+// one frame's wall handling of the walk above: y-bounce, then x-bounce; true if either clamped the digit
+__device__ __forceinline__ bool bounce(int& sy, int& sx, int& dy, int& dx, Draws& d, int R, int L, uint64_t span,
+                                       int det) {
+    bool clamped = false;
+    if (sy < 0) {
+        sy = 0;
+        clamped = true;
+        if (det) {
+            dy = -dy;
+        } else {
+            dy = 1 + draw_below(d, (uint64_t)L);
+            dx = draw_below(d, span) - L;
+        }
+    } else if (sy >= R) {
+        sy = R - 1;
+        clamped = true;
+        if (det) {
+            dy = -dy;
+        } else {
+            dy = draw_below(d, (uint64_t)L) - L;
+            dx = draw_below(d, span) - L;
+        }
+    }
+    if (sx < 0) {
+        sx = 0;
+        clamped = true;
+        if (det) {
+            dx = -dx;
+        } else {
+            dx = 1 + draw_below(d, (uint64_t)L);
+            dy = draw_below(d, span) - L;
+        }
+    } else if (sx >= R) {
+        sx = R - 1;
+        clamped = true;
+        if (det) {
+            dx = -dx;
+        } else {
+            dx = draw_below(d, (uint64_t)L) - L;
+            dy = draw_below(d, span) - L;
+        }
+    }
+    return clamped;
+}
+
+// SYNC: the synchronized dataset (every sequence shares the trajectories; `hit` as the file header states)
+template <bool SYNC>
 __global__ __launch_bounds__(MM_THREADS) void moving_mnist_kernel(const uint8_t* __restrict__ digits, int N,
                                                                   float* __restrict__ out, long long* __restrict__ traj,
-                                                                  int T, int C, int S, int nd, int L, int det,
-                                                                  uint64_t seed, uint64_t split, uint64_t first_id,
-                                                                  int vec) {
+                                                                  int* __restrict__ hit, int T, int C, int S, int nd,
+                                                                  int L, int det, uint64_t seed, uint64_t split,
+                                                                  uint64_t first_id, int vec) {
     __shared__ float lut[256];
     __shared__ float glyph[MM_MAX_DIGITS][MM_DD];
-    __shared__ int pos[MM_MAX_DIGITS][3];
+    __shared__ int pos[MM_MAX_DIGITS][SYNC ? 4 : 3];
 
     const int t = (int)(blockIdx.x % (unsigned)T);
     const long b = (long)(blockIdx.x / (unsigned)T);
@@ -91,46 +148,18 @@ __global__ __launch_bounds__(MM_THREADS) void moving_mnist_kernel(const uint8_t*
         const int R = S - MM_D;   // start positions in [0, R), clamps to [0, R - 1]
         Draws d{seed, split, first_id + (uint64_t)b, (uint64_t)tid, 0};
         const int idx = draw_below(d, (uint64_t)N);
+        if (SYNC) {   // every draw after idx comes from the address all sequences share, starting at draw 1
+            d.seq = ~0ull;
+            d.j = 1;
+        }
         int sx = draw_below(d, (uint64_t)R);
         int sy = draw_below(d, (uint64_t)R);
         const uint64_t span = 2 * (uint64_t)L + 1;
-        int dx = draw_below(d, span) - L;
-        int dy = draw_below(d, span) - L;
+        int dx = SYNC ? 3 : draw_below(d, span) - L;
+        int dy = SYNC ? 3 : draw_below(d, span) - L;
+        bool clamped = false;
         for (int s = 0;; ++s) {
-            if (sy < 0) {
-                sy = 0;
-                if (det) {
-                    dy = -dy;
-                } else {
-                    dy = 1 + draw_below(d, (uint64_t)L);
-                    dx = draw_below(d, span) - L;
-                }
-            } else if (sy >= R) {
-                sy = R - 1;
-                if (det) {
-                    dy = -dy;
-                } else {
-                    dy = draw_below(d, (uint64_t)L) - L;
-                    dx = draw_below(d, span) - L;
-                }
-            }
-            if (sx < 0) {
-                sx = 0;
-                if (det) {
-                    dx = -dx;
-                } else {
-                    dx = 1 + draw_below(d, (uint64_t)L);
-                    dy = draw_below(d, span) - L;
-                }
-            } else if (sx >= R) {
-                sx = R - 1;
-                if (det) {
-                    dx = -dx;
-                } else {
-                    dx = draw_below(d, (uint64_t)L) - L;
-                    dy = draw_below(d, span) - L;
-                }
-            }
+            clamped = bounce(sy, sx, dy, dx, d, R, L, span, det);
             if (s == t) break;
             sy += dy;
             sx += dx;
@@ -138,6 +167,7 @@ __global__ __launch_bounds__(MM_THREADS) void moving_mnist_kernel(const uint8_t*
         pos[tid][0] = idx;
         pos[tid][1] = sy;
         pos[tid][2] = sx;
+        if constexpr (SYNC) pos[tid][3] = clamped ? 1 : 0;
         if (traj) {
             long long* o = traj + (((long)b * nd + tid) * T + t) * 3;
             o[0] = idx;
@@ -146,6 +176,15 @@ __global__ __launch_bounds__(MM_THREADS) void moving_mnist_kernel(const uint8_t*
         }
     }
     __syncthreads();
+
+    if constexpr (SYNC) {
+        if (hit && tid == 0) {   // the reference overwrites in digit order: the last clamped digit wins
+            int h = 0;
+            for (int n = 0; n < nd; ++n)
+                if (pos[n][3]) h = n + 1;
+            hit[(long)b * T + t] = h;
+        }
+    }
 
     for (int k = tid; k < nd * MM_DD; k += MM_THREADS) {
         const int n = k / MM_DD, e = k - n * MM_DD;
@@ -188,9 +227,9 @@ __global__ __launch_bounds__(MM_THREADS) void moving_mnist_kernel(const uint8_t*
 
 }  // namespace
 
-extern "C" int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long* traj, int B, int T, int C,
-                                           int S, int num_digits, int step_length, int deterministic, long seed,
-                                           long split, long first_id, rfn_stream_t stream) {
+static int mm_render(bool sync, const void* digits, int N, float* out, long long* traj, int* hit, int B, int T, int C,
+                     int S, int num_digits, int step_length, int deterministic, long seed, long split, long first_id,
+                     rfn_stream_t stream) {
     RFN_CHECK_ARG(B >= 0 && T >= 1 && C >= 1, -1);
     RFN_CHECK_ARG(S > MM_D && S <= 4096, -2);
     RFN_CHECK_ARG(num_digits >= 1 && num_digits <= MM_MAX_DIGITS, -3);
@@ -201,9 +240,26 @@ extern "C" int rfn_moving_mnist_render_f32(const void* digits, int N, float* out
     if (B == 0) return 0;
     RFN_CHECK_ARG(digits && out, -8);
     const int vec = (S * S) % 4 == 0 && ((uintptr_t)out & 15) == 0;
-    hipLaunchKernelGGL(moving_mnist_kernel, dim3((unsigned)(B * T)), dim3(MM_THREADS), 0, (hipStream_t)stream,
-                       (const uint8_t*)digits, N, out, traj, T, C, S, num_digits, step_length, deterministic,
-                       (uint64_t)seed, (uint64_t)split, (uint64_t)first_id, vec);
+    hipLaunchKernelGGL(sync ? moving_mnist_kernel<true> : moving_mnist_kernel<false>, dim3((unsigned)(B * T)),
+                       dim3(MM_THREADS), 0, (hipStream_t)stream, (const uint8_t*)digits, N, out, traj, hit, T, C, S,
+                       num_digits, step_length, deterministic, (uint64_t)seed, (uint64_t)split, (uint64_t)first_id,
+                       vec);
     RFN_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int rfn_moving_mnist_render_f32(const void* digits, int N, float* out, long long* traj, int B, int T, int C,
+                                           int S, int num_digits, int step_length, int deterministic, long seed,
+                                           long split, long first_id, rfn_stream_t stream) {
+    return mm_render(false, digits, N, out, traj, nullptr, B, T, C, S, num_digits, step_length, deterministic, seed,
+                     split, first_id, stream);
+}
+
+extern "C" int rfn_moving_mnist_sync_render_f32(const void* digits, int N, float* out, long long* traj, long hit_addr,
+                                                int B, int T, int C, int S, int num_digits, int step_length,
+                                                int deterministic, long seed, long split, long first_id,
+                                                rfn_stream_t stream) {
+    RFN_CHECK_ARG((hit_addr & 3) == 0, -9);
+    return mm_render(true, digits, N, out, traj, reinterpret_cast<int*>(hit_addr), B, T, C, S, num_digits, step_length,
+                     deterministic, seed, split, first_id, stream);
 }

@@ -7,6 +7,8 @@
 - `MovingMNIST` keeps the reference's constructor; the digit table lives on the device and a whole batch is one launch
   of rfn_moving_mnist_render_f32 (csrc/moving_mnist.hip).  Each sequence is the reference's walk draw for draw, with
   every random draw addressed by (seed, split, sequence id, digit, draw number) instead of numpy's global stream.
+- `MovingMNIST_synchronized` is the reference's dataset for its parameter analysis: every sequence shares the digits'
+  trajectories (rfn_moving_mnist_sync_render_f32) and `hit_boundary` records the wall contacts per frame.
 - `MovingMNISTLoader` is what the Solver iterates in place of a DataLoader: device batches, no worker processes.
   Sequence ids: train split, sequence i of epoch e -> e * len + i (every epoch sees fresh sequences); test split -> i
   whatever the epoch (a fixed evaluation set).  Rank r of w renders rows [r * B, (r + 1) * B) of each global batch of
@@ -136,6 +138,43 @@ class MovingMNIST(object):
         if not -self.length <= index < self.length:
             raise IndexError("MovingMNIST index %d out of range for %d sequences" % (index, self.length))
         return self.render(self.sequence_id(index % self.length), 1)[0]
+
+
+class MovingMNIST_synchronized(MovingMNIST):
+    """The reference's MovingMNIST_synchronized (stochasticMovingMnist.py:131-248), "synchronized motion for parameter
+    analysis", rendered on the GPU by rfn_moving_mnist_sync_render_f32: all sequences share one trajectory per digit
+    (drawn start position, velocity (3, 3), the wall bounces of MovingMNIST with step_length / deterministic) and
+    only the digit identities depend on the sequence id.  The constructor is the reference's plus `device` and
+    `length`, with MovingMNIST's argument checks; render / sequence_id / __len__ / __getitem__ are MovingMNIST's, so
+    MovingMNISTLoader takes it unchanged.  `hit_boundary` is the reference's float64 numpy array [seq_len]: entry t is
+    n + 1 for the last digit n clamped at a wall on frame t, 0 if none; it is computed on first use from a
+    one-sequence render (the reference fills it as a side effect of __getitem__)."""
+
+    def __init__(self, train, data_root, seq_len=20, num_digits=2, image_size=32, digit_size=28, deterministic=True,
+                 three_channels=True, step_length=4, normalize=False, make_target=False, seed=None, device=None,
+                 length=None):
+        super(MovingMNIST_synchronized, self).__init__(
+            train, data_root, seq_len=seq_len, num_digits=num_digits, image_size=image_size, digit_size=digit_size,
+            deterministic=deterministic, three_channels=three_channels, step_length=step_length, normalize=normalize,
+            make_target=make_target, seed=seed, device=device, length=length)
+        self._hit_boundary = None
+
+    def render(self, first_id, count, trajectories=False, hits=False):
+        """MovingMNIST.render of the synchronized walk; with hits=True also the int32 [count, T] hit table"""
+        from rfn_hip import ops
+        return ops.moving_mnist_sync_render(self.table(), count, self.seq_len, self.channels, self.image_size,
+                                            self.num_digits, self.step_length, self.deterministic, self.seed,
+                                            self.split, first_id, trajectories=trajectories, hits=hits)
+
+    @property
+    def hit_boundary(self):
+        if self._hit_boundary is None:
+            _, hit = self.render(0, 1, hits=True)
+            self._hit_boundary = hit[0].cpu().numpy().astype(np.float64)
+        return self._hit_boundary
+
+    def __boundary__(self):
+        return self.hit_boundary
 
 
 class MovingMNISTLoader(object):

@@ -2,7 +2,7 @@
 bookkeeping (:358-368), the bits-per-dim test-set loop `get_loss` (:370-417) that re-uses `Solver.preprocess` and
 `RFN.loss`, the per-frame image-quality scores `eval_seq` (:154-171: MSE, PSNR and SSIM with skimage 0.17.2's defaults,
 computed on the GPU by one rfn_frame_quality_u8 launch per call instead of a per-channel CPU loop), the best-of-N
-prediction evaluation `get_eval_values` (:419-598, without its plots), plus thin wrappers over the model's analysis
+prediction evaluation `get_eval_values` (:419-598), plus thin wrappers over the model's analysis
 methods (`RFN.reconstruct_elbo_gap`, `.probability_future`, `.param_analysis`, RFN/RFN_new.py:496-788).
 `plot_samples` (:128-152) writes its ground-truth / prediction grid as a PNG of pixels (no titles, no PDF).
 `get_lpips` (:173-187) scores frames with LPIPS on the AlexNet trunk (`lpips` 0.1.3, net='alex', version 0.1; the
@@ -18,8 +18,9 @@ temperatures from one RFN.predict_draws call per pass, the temperatures being pe
 `plot_long_t`, `plot_diversity`, `plot_random_samples` and `plot_temp` (:1220-1415) are written as PNG sheets of pixels
 like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  The curve figures `plot_eval_values` /
 `test_temp_values` (:600-1003) are drawn by the chart kernel (rfn_hip.ops.render_chart, one launch per figure) from the
-statistics of evaluation_metrics/curves.py and written as PNG.  The other plots -- `param_plots`, `plot_elbo_gap`,
-`plot_prob_of_t` -- are not drawn."""
+statistics of evaluation_metrics/curves.py and written as PNG.  So are the analysis figures: `plot_elbo_gap` and
+`plot_prob_of_t` (:189-270; get_eval_values("rfn.pt") draws them under settings.extra_plots) and `param_plots`
+(:1069-1218) on the synchronized Moving MNIST (data_generators.MovingMNIST_synchronized)."""
 import os
 import warnings
 
@@ -82,6 +83,36 @@ class _BestOfN(object):
         return (cat(self.best_values, "mse"), cat(self.best_values, "psnr"), cat(self.best_values, "ssim"),
                 cat(self.best_values, "lpips") if lp else None, bpd, dkl, recon,
                 cat(self.mean_values, "ssim"), cat(self.mean_values, "psnr"), cat(self.mean_values, "lpips") if lp else None)
+
+
+class _ExtraPlots(object):
+    """What get_eval_values("rfn.pt") adds under settings.extra_plots (error_metrics.py:468-476, :548-562, :585-587).
+    add(image, imageloss, start), on the first draw of every batch: nll_prob = probability_future(image, start) /
+    (ln 2 * prod(dims)) and, from reconstruct_elbo_gap(imageloss, sample=False), nllprior and nllposterior (frames
+    1.. in bits per pixel) and their difference, the amortization gap.  finish(), after the loop: the reference's
+    three printed lines, then plot_elbo_gap(the last batch) and plot_prob_of_t(all nll_prob).  The values are CPU
+    tensors; `paths` holds the two files afterwards."""
+
+    def __init__(self, evaluator):
+        self.ev, self.prob, self.prior, self.posterior, self.gap, self.last, self.paths = evaluator, [], [], [], [], None, []
+
+    def add(self, image, imageloss, start):
+        model = self.ev.model
+        scale = np.log(2.) * torch.prod(torch.tensor(imageloss.shape[2:]))
+        self.prob.append(model.probability_future(image, start) / scale)
+        _, _, _, nll = model.reconstruct_elbo_gap(imageloss, sample=False)
+        self.prior.append(nll[0, 1:, :] / scale)
+        self.posterior.append(nll[1, 1:, :] / scale)
+        self.gap.append(self.prior[-1] - self.posterior[-1])
+        self.last = image
+
+    def finish(self):
+        if self.last is None:
+            return
+        print("BPP Prior: ", torch.cat(self.prior, dim=1).mean())
+        print("BPP Posterior: ", torch.cat(self.posterior, dim=1).mean())
+        print("Amortization gap: " + str(torch.cat(self.gap, dim=1).mean()))
+        self.paths = [self.ev.plot_elbo_gap(self.last), self.ev.plot_prob_of_t(torch.cat(self.prob, dim=0))]
 
 
 MODEL_NAMES = ("rfn.pt", "srnn.pt")   # the checkpoints this package can evaluate
@@ -334,8 +365,9 @@ class Evaluator(object):
         return path
 
     def get_eval_values(self, model_name="rfn.pt", loader=None, max_batches=None):
-        """error_metrics.py:419-598 without the plots: per test batch, `resample` rounds of RFN.predict (conditioned on
-        start_predictions frames, n_frames - start_predictions predicted), the loss on the first n_trained frames and
+        """error_metrics.py:419-598 (its debug_plot sheets only on the draws_per_pass path): per test batch,
+        `resample` rounds of RFN.predict (conditioned on start_predictions frames, n_frames - start_predictions
+        predicted), the loss on the first n_trained frames and
         eval_seq of the predictions against the ground truth; per sequence the best of the draws is kept (strictly
         higher time-mean PSNR / SSIM, strictly lower MSE; ties keep the earlier draw).  Returns the reference's tuple
         (MSE, PSNR, SSIM, LPIPS, BPD, DKL, RECON, SSIM_std, PSNR_std, LPIPS_std): MSE / PSNR / SSIM [n_seq, n_pred] of the
@@ -352,16 +384,23 @@ class Evaluator(object):
         With settings.draws_per_pass = P the draws of a batch are generated P at a time with addressed noise
         (settings.seed) and the figures are reproducible: see _get_eval_values_draws.
 
+        With settings.extra_plots and "rfn.pt" (:468-476, :548-562, :585-587): on the first draw of every batch the
+        analyses of _ExtraPlots.add, after the loop its three printed lines and the figures KLDdiagnostic.png
+        (plot_elbo_gap of the last batch) and bpp_sequence.png (plot_prob_of_t); the returned tuple is the same.  Other
+        checkpoints skip the figures.  settings.debug_plot draws nothing on this path (a warning says so).
+
         "srnn.pt" takes the reference's other branch (:478-483): `kl, nll = model.loss(image)` on the WHOLE sequence,
         with the dims and t of `image`; everything else is the same code."""
         rfn = check_model_name(model_name)
         if self.draws_per_pass is not None:
             return self._get_eval_values_draws(loader, max_batches, rfn)
-        if (self.extra_plots or self.debug_plot) and not self._warned_plots:
-            warnings.warn("Evaluator.get_eval_values: extra_plots / debug_plot only draw figures; skipped")
+        if self.debug_plot and not self._warned_plots:
+            warnings.warn("Evaluator.get_eval_values: debug_plot only draws figures; skipped (the draws_per_pass path "
+                          "writes its sheets)")
             self._warned_plots = True
         loader = loader if loader is not None else self.test_loader
         start, n_frames = self.start_predictions, self.n_frames
+        extra = _ExtraPlots(self) if rfn and self.extra_plots else None
         lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
         lpips_values, lpips_std_values = [], []
         if lpips_w is not None:
@@ -382,6 +421,8 @@ class Evaluator(object):
                 for r in range(self.resample):
                     _, predictions = self.model.predict(image, n_frames - start, start)
                     bpd, kl_loss, recon_loss = self._batch_loss(imageloss if rfn else image, rfn)
+                    if r == 0 and extra is not None:
+                        extra.add(image, imageloss, start)
                     pred_u8 = self.solver.preprocess(predictions, reverse=True).permute(1, 0, 2, 3, 4)
                     pred_u8 = pred_u8.to(self.device)
                     gt_u8 = image_u8[:, start:start + pred_u8.shape[1]]
@@ -419,6 +460,8 @@ class Evaluator(object):
                 bpd_list.append(bpd)
                 dkl_list.append(kl_loss)
                 recon_list.append(recon_loss)
+            if extra is not None:
+                extra.finish()
         return (torch.cat(mse_values), torch.cat(psnr_values), torch.cat(ssim_values),
                 torch.cat(lpips_values) if lpips_w is not None else None,
                 torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list),
@@ -443,19 +486,18 @@ class Evaluator(object):
         written through plot_samples after the loop (error_metrics.py:590-597, pixels only): random_samples_ssim.png
         (the last batch's last draw), best_samples.png and worst_samples.png (the first and last of the sequences
         ordered by time-mean SSIM of their best draw, descending), settings.num_samples_to_plot sequences each
-        (default 5, capped at the sequences there are), the first six predicted frames."""
+        (default 5, capped at the sequences there are), the first six predicted frames.  With settings.extra_plots the
+        analyses of _ExtraPlots run once per batch, after the passes, and its figures are drawn after the loop."""
         P = int(self.draws_per_pass)
         if P < 1:
             raise ValueError("Evaluator: settings.draws_per_pass must be at least 1, got %d" % P)
-        if self.extra_plots and not self._warned_plots:
-            warnings.warn("Evaluator.get_eval_values: extra_plots only draws figures; skipped")
-            self._warned_plots = True
         loader = loader if loader is not None else self.test_loader
         start, n_frames, R = self.start_predictions, self.n_frames, self.resample
         n_pass = -(-R // P)
         lpips_w = self._lpips_loaded() if self.lpips_weights is not None else None
         names = ("mse", "psnr", "ssim") + (("lpips",) if lpips_w is not None else ())
         book = _BestOfN(names, self.device)
+        extra = _ExtraPlots(self) if rfn and self.extra_plots else None
         bpd_list, dkl_list, recon_list = [], [], []
         gts = []
         batch_size = None
@@ -481,12 +523,16 @@ class Evaluator(object):
                     for d in range(min(P, R - ps * P)):
                         book.add(host[:, d], pred_u8[d])
                 bpd, kl_loss, recon_loss = self._batch_loss(imageloss if rfn else image, rfn)
+                if extra is not None:
+                    extra.add(image, imageloss, start)
                 book.end_batch()
                 bpd_list.append(bpd)
                 dkl_list.append(kl_loss)
                 recon_list.append(recon_loss)
                 gts.append(gt_u8)
                 last_gt = gt_u8
+            if extra is not None:
+                extra.finish()
         out = book.result(torch.FloatTensor(bpd_list), torch.FloatTensor(dkl_list), torch.FloatTensor(recon_list))
         ssim_all, last_pred = out[2], book.last_pred
         # best_preds_ssim of the reference: every sequence's best draw by SSIM, on the device
@@ -805,3 +851,130 @@ class Evaluator(object):
     def param_analysis(self, image, n_predictions, n_conditions):
         self.model.eval()
         return self.model.param_analysis(self.solver.preprocess(image.to(self.device)), n_predictions, n_conditions)
+
+    def _chart_png(self, figure, path):
+        from rfn_hip import ops
+        from Utils.png import write_png
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        write_png(path, ops.render_chart(figure, scanlines=True))
+        return path
+
+    def elbo_gap_rows(self, image, recons):
+        """the three rows of plot_elbo_gap's sheet as uint8 device tensors [t, C, H, W]: sequence 0 of `image` (model
+        space, [B, t, C, H, W]) and of recons[0] / recons[1] ([2, t, B, C, H, W]: prior, posterior) as
+        Solver.preprocess(x, reverse=True) makes them; column 0 of the two reconstruction rows is empty (white, the
+        sheet's background)"""
+        to_u8 = lambda x: self.solver.preprocess(x.to(self.device), reverse=True).contiguous()
+        rows = [to_u8(image[0]), to_u8(recons[0, :, 0]), to_u8(recons[1, :, 0])]
+        for r in rows[1:]:
+            r[0] = 255
+        return rows
+
+    def plot_elbo_gap(self, image):
+        """error_metrics.py:189-247: `eval_folder/KLDdiagnostic.png` from the first 10 frames of `image` (model space,
+        [B, T, C, H, W]) through RFN.reconstruct_elbo_gap (sample=True).  Sequence 0 is shown as three rows of t cells
+        -- ground truth, the reconstruction under z ~ prior, under z ~ posterior -- labelled "GT:", "Prior:" and
+        "Posterior:"; below them two stacked panels over x = 0 .. t - 1: "Avg. KLD", bars of averageKLDseq[:, 0], and
+        "BPP", paired bars "Prior" / "Posterior" of averageNLLseq[z, :, 0] / (ln 2 * prod(dims)), with the reference's
+        y range (evaluation_metrics.curves.elbo_gap_figure).  200 t x 972 pixels (figsize (2 t, 1.62 * 6) at 100
+        dpi).  The chart kernel paints the figure, one compose_sheet launch the rows, and the sheet is copied on the
+        device into the figure's reserved top band.  Deviations: PNG instead of PDF; the frames are shown pixel for
+        pixel, not scaled to the reference's 2-inch cells; both panels carry a legend and x tick labels (the reference
+        hides the upper panel's); a 5x7 dot-matrix font.  Returns the path."""
+        from evaluation_metrics.curves import elbo_gap_band, elbo_gap_figure
+        from rfn_hip import ops
+        from Utils.png import write_png
+        image = image[:, :10].to(self.device)
+        with torch.no_grad():
+            self.model.eval()
+            recons, _, kld, nll = self.model.reconstruct_elbo_gap(image)
+        t, (H, W) = int(image.shape[1]), (int(d) for d in image.shape[3:])
+        bpp = nll[:, :, 0].double().numpy() / (np.log(2.) * float(np.prod(tuple(image.shape[2:]))))
+        figure = elbo_gap_figure(kld[:, 0].double().numpy(), bpp, H, W)
+        canvas = ops.render_chart(figure, scanlines=False, device=self.device)
+        sheet = ops.compose_sheet(self.elbo_gap_rows(image, recons), t, scanlines=False)
+        _, x, y, _ = elbo_gap_band(t, H, W)
+        canvas[y:y + sheet.shape[0], x:x + sheet.shape[1]] = sheet
+        folder = self.solver.path + "eval_folder"
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, "KLDdiagnostic.png")
+        write_png(path, canvas)
+        return path
+
+    def plot_prob_of_t(self, probT):
+        """error_metrics.py:250-270: `eval_folder/bpp_sequence.png`, the mean over sequences of probT[:, 0, :] ([N, 2,
+        T'], bits per pixel under z ~ prior) against x = n_conditions + arange(T') with the band -+ 1.96 std / sqrt(N)
+        (numpy's population std), a grid, a title and the axis labels "Bits per pixel" / "Frame number"
+        (evaluation_metrics.curves.prob_of_t_figure).  640 x 480 pixels (matplotlib's default figsize at 100 dpi).
+        Deviations: PNG instead of PDF; the statistics are float64; the band's alpha is the other curve figures' 0.2
+        (the reference: 0.1); plain-text title.  Returns the path."""
+        from evaluation_metrics.curves import prob_of_t_figure
+        if self.n_conditions is None:
+            raise ValueError("Evaluator.plot_prob_of_t needs settings.n_conditions")
+        return self._chart_png(prob_of_t_figure(probT, int(self.n_conditions)),
+                               os.path.join(self.solver.path + "eval_folder", "bpp_sequence.png"))
+
+    def param_plots(self, path, n_conditions, n_sequences=400):
+        """error_metrics.py:1069-1218, the parameter analysis on synchronized motion.  The first n_sequences (the
+        reference's 400) test sequences of MovingMNIST_synchronized(False, --mnist_root, seq_len=30, num_digits=2,
+        deterministic=False, three_channels=False, image_size / digit_size / step_length of the run), ids 0 .. in
+        order, in batches of the run's batch size (an incomplete last batch is dropped), go through
+        model.param_analysis(x, 30 - n_conditions, n_conditions); the six parameter tensors are summed over (C, H, W),
+        averaged over batches and sequences and min-max scaled (evaluation_metrics.curves.parameter_curves).  Written
+        into `path`:
+          parameter_analysis2.png   two stacked panels "Average" against t = 1 .. 29, x range [1, 29]: the prior's,
+                                    posterior's and base distribution's mean above, their sigmas below, a red dashed
+                                    line at every k + 1 with hit_boundary[k] == 1, a blue one where it is 2
+                                    (curves.param_figure; 1000 x 800 pixels)
+          parameter_analysis_mnist_plots_true.png / _pred.png   sequence 0 of the last batch (the frames, the
+                                    predictions) as three strips of frames 1:11, 11:21 and 21:29, one compose_sheet
+                                    launch each (rows of 10, 10 and 8 cells, no gutter) -- what the reference's permute /
+                                    reshape / transpose chain lays out.
+        Deviations: the reference takes a random 400 of the test split and shuffles them; only the digit identities
+        depend on the sequence id and the curves are means over the sequences, so the first 400 in order are used.  PNG
+        charts by the chart kernel, plain-text labels; the strips are pixels, stacked in one sheet each.  Needs an
+        SM-MNIST run (choose_data == "mnist") and the MNIST files: otherwise a ValueError names the reason.  Returns
+        the three paths."""
+        from data_generators import MovingMNIST_synchronized, MovingMNISTLoader
+        from data_generators.moving_mnist import mnist_candidate_paths
+        from evaluation_metrics.curves import param_figure, parameter_curves
+        from rfn_hip import ops
+        from Utils.png import write_png
+        if self.choose_data != "mnist":
+            raise ValueError("Evaluator.param_plots runs on synchronized Moving MNIST: it needs an SM-MNIST run "
+                             "(choose_data == 'mnist'), this one is %r" % (self.choose_data,))
+        root = getattr(self.args, "mnist_root", "Mnist")
+        candidates = mnist_candidate_paths(root, False)
+        if not any(os.path.isfile(p) for p in candidates):
+            raise ValueError("Evaluator.param_plots needs the MNIST test images; none of %s exists (nothing is "
+                             "downloaded)" % ", ".join(candidates))
+        seq_len, n_conditions, batch_size = 30, int(n_conditions), int(self.args.batch_size)
+        if not 1 <= n_conditions < seq_len or int(n_sequences) < batch_size:
+            raise ValueError("Evaluator.param_plots: need 1 <= n_conditions < %d and at least one batch of %d sequences "
+                             "(got %d, %d)" % (seq_len, batch_size, n_conditions, int(n_sequences)))
+        dataset = MovingMNIST_synchronized(False, root, seq_len=seq_len, num_digits=2,
+                                           image_size=int(self.args.image_size), digit_size=int(self.args.digit_size),
+                                           deterministic=False, three_channels=False,
+                                           step_length=int(self.args.step_length), normalize=False, make_target=False,
+                                           seed=getattr(self.args, "data_seed", 0), device=self.device,
+                                           length=int(n_sequences))
+        print("Init parameter analysis")
+        sums = []
+        with torch.no_grad():
+            self.model.eval()
+            for true_image in MovingMNISTLoader(dataset, batch_size):
+                image = self.solver.preprocess(true_image.to(self.device))
+                out = self.model.param_analysis(image, seq_len - n_conditions, n_conditions)
+                sums.append([p.sum([2, 3, 4]) for p in out[:6]])
+                prediction = out[6]
+        figure = param_figure(parameter_curves(sums), dataset.hit_boundary)
+        os.makedirs(path, exist_ok=True)
+        paths = [self._chart_png(figure, os.path.join(path, "parameter_analysis2.png"))]
+        bits, rng = int(getattr(self.solver, "n_bits", 8)), getattr(self.solver, "preprocess_range", "0.5")
+        for name, frames in (("true", image), ("pred", prediction.to(self.device))):
+            strips = [frames[0, 1:11], frames[0, 11:21], frames[0, 21:29]]
+            paths.append(os.path.join(path, "parameter_analysis_mnist_plots_%s.png" % name))
+            write_png(paths[-1], ops.compose_sheet(strips, 10, gutter=0, n_bits=bits, preprocess_range=rng,
+                                                   scanlines=True))
+        print("Parameter analysis has finished")
+        return paths

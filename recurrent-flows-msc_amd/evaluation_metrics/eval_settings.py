@@ -29,9 +29,10 @@ baselines are not part of this package (any other model name is a ValueError); L
 would need the lpips package's download); --debug_mnist / --use_validation_set evaluate the FIRST 1000 test sequences
 (the reference: a random 1000 for --debug_mnist); the curve figures of plot_eval_values / test_temp_values, the last
 step of a run, are PNG files drawn by the chart kernel (skipped with one line when the evaluations.pt files they read
-do not exist); the figure of param_plots is not drawn -- one line says so when it would have run -- and
---eval_parameters saves the tensors of Evaluator.param_analysis on the first test batch to
-`eval_folder/param_analysis.pt` instead.  The sheets are written to
+do not exist); --eval_parameters saves the tensors of Evaluator.param_analysis on the first test batch to
+`eval_folder/param_analysis.pt` and then, on an SM-MNIST run, draws the figures of Evaluator.param_plots into the
+experiment's eval_folder (on other data one line says that they need SM-MNIST); --extra_plots makes get_eval_values
+draw KLDdiagnostic.png and bpp_sequence.png (Evaluator.plot_elbo_gap / plot_prob_of_t).  The sheets are written to
 the solver's own `eval_folder` (the run's --path under the working directory), which is the same directory when the
 driver is started where the training was."""
 import argparse
@@ -180,7 +181,11 @@ def main(settings):
                 image = image[0] if args.choose_data == "bair" and isinstance(image, (list, tuple)) else image
                 out = evaluator.param_analysis(image, settings.n_frames - settings.n_conditions, settings.n_conditions)
                 torch.save(dict(zip(PARAM_KEYS, out)), folder + "/param_analysis.pt")
-                print("eval_settings: param_plots is not drawn; the tensors are in %s/param_analysis.pt" % folder)
+                if args.choose_data == "mnist":
+                    evaluator.param_plots(folder, settings.n_conditions)
+                else:
+                    print("eval_settings: the figures of param_plots need an SM-MNIST run (synchronized Moving MNIST); "
+                          "the tensors are in %s/param_analysis.pt" % folder)
             if settings.calc_fvd:
                 print("Computing FVD")
                 fvd_mean, fvd_std = evaluator.get_fvd_values(model_name, settings.fvd_predicts, max_batches=max_batches)
@@ -244,8 +249,8 @@ def build_parser():
     p.add_argument("--temperatures", nargs="+", help="Specify temperature for the model", default=[0.7], type=float)
     p.add_argument("--resample", help="Loops over the test set more than once to get better measures. WARNING: can be "
                    "slow", default=30, type=int)
-    add_bool_arg(p, "extra_plots", default=False, help="Plots the elbo gap of the RFN model and other plots (not drawn "
-                 "here: a warning is given)")
+    add_bool_arg(p, "extra_plots", default=False, help="Plots the elbo gap of the RFN model and the bits per pixel of "
+                 "future frames (KLDdiagnostic.png, bpp_sequence.png) while the eval values are computed")
     # TEST TEMPERATURE
     add_bool_arg(p, "test_temperature", default=False,
                  help="Allows one to test temperature. If enabled different temperatures (from --temperatures) are "
@@ -260,7 +265,8 @@ def build_parser():
                  help="Plots num_samples_to_plot samples to make sure the loader and eval works")
     p.add_argument("--n_conditions", help="Number of conditions used for plotting eval_values", default=5, type=int)
     add_bool_arg(p, "eval_parameters", default=False,
-                 help="If true then the parameter analysis is run and its tensors are saved")
+                 help="If true then the parameter analysis is run, its tensors are saved and, on SM-MNIST, its "
+                      "figures are drawn")
     # FVD settings
     add_bool_arg(p, "calc_fvd", default=False, help="Enabling this allows us to compute FVD (needs --fvd_weights)")
     p.add_argument("--fvd_predicts", help="How far into the future to predict", default=13, type=int)

@@ -1,12 +1,15 @@
 """Line charts as display lists for rfn_chart_render_u8 (csrc/chart.hip): what the reference draws with matplotlib in
 Evaluator.plot_eval_values / test_temp_values (evaluation_metrics/error_metrics.py:600-1003) -- panels side by side,
 per panel a title, axis labels, a grid, series with a line, a marker, a fill_between band or error bars, a dashed
-vertical line, and one legend row under the panels.  Pure host code (numpy, no GPU, no matplotlib, no font files):
+vertical line, and one legend row under the panels -- and, for the figures of plot_elbo_gap / plot_prob_of_t /
+param_plots (:189-270, :1069-1218), bar series, several coloured vertical lines, fixed axis limits and x ticks, panels
+stacked in rows, a reserved band at the top of the canvas and free text.  Pure host code (numpy, no GPU, no
+matplotlib, no font files):
 `build_display_list(figure)` turns a Figure into the int32 table the kernel paints; rfn_hip.ops.render_chart runs it.
 DESIGN.md section 25 holds the pixel contract, the tick rule and the data-to-pixel mapping stated here.
 
 Units: the kernel's geometry is in 1/16 pixel (SUB = 16), x to the right, y down.  The layout below is in whole pixels
-and a function of (width, height, number of panels, text_scale) alone."""
+and a function of (width, height, the grid of panels, the reserved top band, text_scale) alone."""
 import math
 
 import numpy as np
@@ -32,9 +35,11 @@ BAND_ALPHA = 51               # the reference's alpha_CI = 0.2 of 255
 class Series(object):
     """One curve: x, y (equal lengths), an RGB colour, an optional marker of MARKERS, the line on or off, an optional
     band (lo, hi) drawn translucent, optional error bars yerr (stems y - yerr .. y + yerr), a legend label.  Points with
-    a non-finite coordinate are left out (a line or band piece needs both its ends)."""
+    a non-finite coordinate are left out (a line or band piece needs both its ends).  bar = (width, offset) in data
+    units: every finite point also draws a box from the baseline 0 to y over [x + offset - width / 2,
+    x + offset + width / 2], clipped to the axes."""
 
-    def __init__(self, x, y, color, marker=None, line=True, band=None, yerr=None, label=None):
+    def __init__(self, x, y, color, marker=None, line=True, band=None, yerr=None, label=None, bar=None):
         self.x, self.y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
         if self.x.ndim != 1 or self.x.shape != self.y.shape:
             raise ValueError("Series: x and y must be vectors of one length, got %s and %s" % (self.x.shape, self.y.shape))
@@ -43,6 +48,9 @@ class Series(object):
         self.color, self.marker, self.line, self.label = tuple(int(c) for c in color), marker, bool(line), label
         self.band = None if band is None else tuple(np.asarray(b, dtype=np.float64) for b in band)
         self.yerr = None if yerr is None else np.asarray(yerr, dtype=np.float64)
+        self.bar = None if bar is None else (float(bar[0]), float(bar[1]))
+        if self.bar is not None and not (math.isfinite(self.bar[0]) and self.bar[0] > 0 and math.isfinite(self.bar[1])):
+            raise ValueError("Series: bar needs a positive width and a finite offset, got %r" % (bar,))
         for name, a in (("band", self.band or ()), ("yerr", () if self.yerr is None else (self.yerr,))):
             for b in a:
                 if b.shape != self.y.shape:
@@ -52,22 +60,43 @@ class Series(object):
 class Panel(object):
     """One set of axes: title, xlabel, ylabel, series, an optional dashed vertical line at x = vline, the grid on or
     off, integer_x (whole-number ticks on the x axis: the frame index) and `message`, a text shown in the middle of the
-    axes (a panel without data)."""
+    axes (a panel without data).  vlines: further dashed vertical lines [(x, (r, g, b)), ...], each in its own
+    colour; a line outside the x range is not drawn.  xlim / ylim: a fixed (lo, hi) in place of the autoscaled range.
+    xticks: explicit x tick values in place of the tick rule's (those outside the x range are left out)."""
 
-    def __init__(self, title="", xlabel="", ylabel="", series=(), vline=None, grid=True, integer_x=True, message=None):
+    def __init__(self, title="", xlabel="", ylabel="", series=(), vline=None, grid=True, integer_x=True, message=None,
+                 vlines=(), xlim=None, ylim=None, xticks=None):
         self.title, self.xlabel, self.ylabel, self.series = str(title), str(xlabel), str(ylabel), list(series)
         self.vline, self.grid, self.integer_x, self.message = vline, bool(grid), bool(integer_x), message
+        self.vlines = [(float(x), tuple(int(c) for c in color)) for x, color in vlines]
+        self.xlim, self.ylim = (None if lim is None else (float(lim[0]), float(lim[1])) for lim in (xlim, ylim))
+        for nm, lim in (("xlim", self.xlim), ("ylim", self.ylim)):
+            if lim is not None and not (math.isfinite(lim[0]) and math.isfinite(lim[1]) and lim[0] < lim[1]):
+                raise ValueError("Panel: %s must be finite with lo < hi, got %r" % (nm, lim))
+        self.xticks = None if xticks is None else [float(v) for v in xticks]
 
 
 class Figure(object):
     """Panels side by side on a width x height canvas; text_scale u is the pixels per font dot of tick labels and legend
-    (titles and axis labels use u + u // 2); the legend row lists the labelled series of `legend_panel`."""
+    (titles and axis labels use u + u // 2); the legend row lists the labelled series of `legend_panel`.  rows: the
+    panels fill a grid of `rows` rows in row-major order (their number is a multiple of rows), every row with its own
+    legend row, listing the row's panel in column `legend_panel`.  top: that many pixel rows at the top of the canvas
+    are reserved -- the grid lies below them and the display list puts nothing there but `texts`.  texts: free text
+    [(x, y, string)], the top-left corner in pixels, at scale u."""
 
-    def __init__(self, panels, width=1900, height=500, text_scale=2, legend=True, legend_panel=0):
+    def __init__(self, panels, width=1900, height=500, text_scale=2, legend=True, legend_panel=0, rows=1, top=0,
+                 texts=()):
         self.panels, self.width, self.height = list(panels), int(width), int(height)
         self.text_scale, self.legend, self.legend_panel = int(text_scale), bool(legend), int(legend_panel)
+        self.rows, self.top = int(rows), int(top)
+        self.texts = [(int(x), int(y), str(string)) for x, y, string in texts]
         if not self.panels:
             raise ValueError("Figure: no panels")
+        if self.rows < 1 or len(self.panels) % self.rows:
+            raise ValueError("Figure: %d panels do not fill %d rows" % (len(self.panels), self.rows))
+        if not 0 <= self.top < self.height:
+            raise ValueError("Figure: the reserved band of %d rows does not leave a canvas of height %d anything" %
+                             (self.top, self.height))
         if not (1 <= self.width <= MAX_SIDE and 1 <= self.height <= MAX_SIDE):
             raise ValueError("Figure: the canvas is at most %d x %d pixels, got %d x %d" %
                              (MAX_SIDE, MAX_SIDE, self.width, self.height))
@@ -141,8 +170,9 @@ def data_to_subpixel(value, lo, hi, p_lo, p_hi):
 class Axes(object):
     """Where a panel's axes lie (whole pixels, [x0, x1] x [y0, y1], y0 the top) and the data ranges mapped onto them"""
 
-    def __init__(self, x0, y0, x1, y1, xlim, ylim):
+    def __init__(self, x0, y0, x1, y1, xlim, ylim, top=0):
         self.x0, self.y0, self.x1, self.y1, self.xlim, self.ylim = x0, y0, x1, y1, xlim, ylim
+        self.top = top   # the first pixel row of the grid row that holds the panel
 
     def subpixel(self, x, y):
         """(sx, sy) of the data point (x, y) in 1/16 pixel"""
@@ -161,25 +191,36 @@ def layout(fig):
     columns [i * (W // n), (i + 1) * (W // n)); its axes start behind pad + 7t (the y label) + pad + 36u (six tick-label
     characters) + tick + pad and end 18u before the panel's right edge; vertically they run from pad + 7t + pad (the
     title) to H - (tick + pad + 7u + pad + 7t + pad) - (7u + 2 pad) (tick labels, x label, legend row).  The x range
-    covers the series' x and the vertical line, the y range their y, bands and error bars, each through autoscale()."""
+    covers the series' x and the vertical line, the y range their y, bands and error bars, each through autoscale().
+    With rows > 1 or a reserved band: n is the number of columns, H the row height (height - top) // rows, and row r
+    lies fig.top + r * H lower.  Bars add their x extents and the baseline 0 to the ranges, the coloured vertical
+    lines their x; a panel's xlim / ylim replaces the autoscaled range."""
     m = _metrics(fig)
-    n, pw = len(fig.panels), fig.width // len(fig.panels)
-    y0 = m["pad"] + m["tch"] + m["pad"]
-    y1 = fig.height - (m["tick"] + m["pad"] + m["ch"] + m["pad"] + m["tch"] + m["pad"]) - (m["ch"] + 2 * m["pad"])
+    n = len(fig.panels) // fig.rows
+    pw, rh = fig.width // n, (fig.height - fig.top) // fig.rows
     out = []
-    for i, panel in enumerate(fig.panels):
+    for k, panel in enumerate(fig.panels):
+        i, top = k % n, fig.top + (k // n) * rh
+        y0 = top + m["pad"] + m["tch"] + m["pad"]
+        y1 = top + rh - (m["tick"] + m["pad"] + m["ch"] + m["pad"] + m["tch"] + m["pad"]) - (m["ch"] + 2 * m["pad"])
         x0 = i * pw + m["pad"] + m["tch"] + m["pad"] + 6 * m["cw"] + m["tick"] + m["pad"]
         x1 = (i + 1) * pw - 3 * m["cw"]
         xs = [s.x for s in panel.series] + ([[panel.vline]] if panel.vline is not None and panel.series else [])
+        if panel.series:
+            xs += [[x for x, _ in panel.vlines]]
         ys = []
         for s in panel.series:
             ys.append(s.y)
+            if s.bar is not None:
+                xs += [s.x + s.bar[1] - s.bar[0] / 2, s.x + s.bar[1] + s.bar[0] / 2]
+                ys.append([0.0])
             if s.band is not None:
                 ys += list(s.band)
             if s.yerr is not None:
                 ys += [s.y - s.yerr, s.y + s.yerr]
         cat = lambda a: np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in a]) if a else np.zeros(0)
-        out.append(Axes(x0, y0, max(x1, x0 + 1), max(y1, y0 + 1), autoscale(cat(xs)), autoscale(cat(ys))))
+        out.append(Axes(x0, y0, max(x1, x0 + 1), max(y1, y0 + 1), panel.xlim or autoscale(cat(xs)),
+                        panel.ylim or autoscale(cat(ys)), top))
     return out
 
 
@@ -303,7 +344,8 @@ def check_table(table):
 def build_display_list(fig):
     """The display list of a Figure.  Records are emitted layer by layer over all panels in the order LAYERS --
     background (the axes' white), grid, bands, lines (with error-bar stems and the dashed vertical line), markers, frame
-    (axes and tick marks), text -- and inside a layer panel by panel, series by series, point by point: the same
+    (axes and tick marks), text -- bars go with the bands, the coloured vertical lines with the lines, the free text
+    comes last -- and inside a layer panel by panel, series by series, point by point: the same
     figure always gives the same table."""
     if not isinstance(fig, Figure):
         raise TypeError("build_display_list: need a chart.Figure, got %s" % type(fig).__name__)
@@ -319,6 +361,9 @@ def build_display_list(fig):
         sy = lambda v: clamp(data_to_subpixel(v, ax.ylim[0], ax.ylim[1], Y1, Y0))
         if panel.series:
             xt, xd = nice_ticks(ax.xlim[0], ax.xlim[1], integer=panel.integer_x)
+            if panel.xticks is not None:   # explicit ticks: the fewest decimals (at most 6) that show every value
+                xt = [v for v in panel.xticks if ax.xlim[0] <= v <= ax.xlim[1]]
+                xd = next((d for d in range(6) if all(round(v, d) == v for v in xt)), 6)
             yt, yd = nice_ticks(ax.ylim[0], ax.ylim[1])
         else:
             xt, xd, yt, yd = [], 0, [], 0
@@ -352,6 +397,15 @@ def build_display_list(fig):
                     if bok[i] and bok[i + 1] and bx[i] < bx[i + 1]:
                         L["bands"].append(trapezoid(bx[i], bx[i + 1], top[i], top[i + 1], bot[i], bot[i + 1], s.color,
                                                     BAND_ALPHA))
+            if s.bar is not None:   # opaque boxes from the baseline to y, clipped to the axes
+                base = sy(0.0)
+                for i in range(len(px)):
+                    if ok[i]:
+                        bx0, bx1 = sx(s.x[i] + s.bar[1] - s.bar[0] / 2), sx(s.x[i] + s.bar[1] + s.bar[0] / 2)
+                        bx0, bx1 = max(bx0, X0), min(bx1, X1)
+                        by0, by1 = max(min(base, py[i]), Y0), min(max(base, py[i]), Y1)
+                        if bx0 < bx1 and by0 < by1:
+                            L["bands"].append(box(bx0, by0, bx1, by1, s.color))
             if s.line:
                 for i in range(len(px) - 1):
                     if ok[i] and ok[i + 1]:
@@ -368,34 +422,44 @@ def build_display_list(fig):
         if panel.vline is not None and panel.series:
             p = sx(panel.vline)
             L["lines"].append(box(p - hw, Y0, p + hw, Y1, BLACK, dash=(SUB * 4 * u, SUB * 2 * u)))
+        if panel.series:
+            for v, colour in panel.vlines:
+                if ax.xlim[0] <= v <= ax.xlim[1]:
+                    p = sx(v)
+                    L["lines"].append(box(p - hw, Y0, p + hw, Y1, colour, dash=(SUB * 4 * u, SUB * 2 * u)))
         for a in (box(X0 - 8 * lw, Y0 - 8 * lw, X1 + 8 * lw, Y0 + 8 * lw, BLACK),
                   box(X0 - 8 * lw, Y1 - 8 * lw, X1 + 8 * lw, Y1 + 8 * lw, BLACK),
                   box(X0 - 8 * lw, Y0, X0 + 8 * lw, Y1, BLACK), box(X1 - 8 * lw, Y0, X1 + 8 * lw, Y1, BLACK)):
             L["frame"].append(a)
         cx = (ax.x0 + ax.x1) // 2
-        L["text"] += text(cx - text_width(panel.title, t) // 2, pad, panel.title, t)
+        L["text"] += text(cx - text_width(panel.title, t) // 2, ax.top + pad, panel.title, t)
         L["text"] += text(cx - text_width(panel.xlabel, t) // 2, ax.y1 + tick + pad + m["ch"] + pad, panel.xlabel, t)
         L["text"] += text(ax.x0 - tick - pad - 6 * m["cw"] - pad - m["tch"],
                           (ax.y0 + ax.y1) // 2 + text_width(panel.ylabel, t) // 2, panel.ylabel, t, rotated=True)
         if panel.message:
             L["text"] += text(cx - text_width(panel.message, u) // 2, (ax.y0 + ax.y1) // 2 - m["ch"] // 2,
                               panel.message, u)
-    if fig.legend and 0 <= fig.legend_panel < len(fig.panels):
-        entries = [s for s in fig.panels[fig.legend_panel].series if s.label]
+    cols, rh = len(fig.panels) // fig.rows, (fig.height - fig.top) // fig.rows
+    for row in range(fig.rows if fig.legend and 0 <= fig.legend_panel < cols else 0):
+        entries = [s for s in fig.panels[row * cols + fig.legend_panel].series if s.label]
         sample, gap = 24 * u, 2 * m["cw"]
         total = sum(sample + pad + text_width(s.label, u) + gap for s in entries)
         x = fig.width // 10 if fig.width // 10 + total <= fig.width else max(pad, (fig.width - total) // 2)
-        y = fig.height - pad - m["ch"]
+        y = fig.top + (row + 1) * rh - pad - m["ch"]
         cy = SUB * y + SUB * m["ch"] // 2
         for s in entries:
             if x + sample > fig.width:   # the row is full: the remaining entries would lie off the canvas
                 break
+            if s.bar is not None:   # a bar series' sample is a filled box
+                L["bands"].append(box(SUB * x, SUB * y, SUB * (x + sample), SUB * (y + m["ch"]), s.color))
             if s.line:
                 L["lines"].append(capsule(SUB * x, cy, SUB * (x + sample), cy, hw, s.color))
             if s.marker is not None:
                 L["markers"] += marker(s.marker, SUB * x + SUB * sample // 2, cy, r, s.color)
             L["text"] += text(x + sample + pad, y, s.label, u)
             x += sample + pad + text_width(s.label, u) + gap
+    for x, y, string in fig.texts:
+        L["text"] += text(x, y, string, u)
     # a glyph outside the coordinate range lies off the canvas (an over-long title or legend): it is left out
     visible = lambda rec: rec[0] != GLYPH or (COORD_MIN <= rec[2] <= COORD_MAX and COORD_MIN <= rec[3] <= COORD_MAX)
     rows = [rec for k in LAYERS for rec in L[k] if visible(rec)]

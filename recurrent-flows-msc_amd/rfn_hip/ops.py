@@ -2436,6 +2436,33 @@ def frame_quality(a, b):
     return mse, psnr, ssim
 
 
+def _moving_mnist_args(fn, digits, B, T, C, S, num_digits, step_length, seed, split, first_id):
+    """the argument checks the two Moving MNIST renderers share; returns the contiguous digits and the integers"""
+    if not isinstance(digits, torch.Tensor) or digits.dtype != torch.uint8:
+        raise TypeError("%s: digits must be a uint8 tensor, got %s" %
+                        (fn, digits.dtype if isinstance(digits, torch.Tensor) else type(digits).__name__))
+    if digits.dim() != 3 or tuple(digits.shape[1:]) != (28, 28) or digits.shape[0] < 1:
+        raise ValueError("%s: digits must be [N >= 1, 28, 28], got %s" % (fn, tuple(digits.shape),))
+    if not digits.is_cuda:
+        raise RuntimeError("rfn_hip kernels need device tensors; digits is on %s (no CPU fallback)" % digits.device)
+    B, T, C, S, nd, L_, seed, split, first_id = (int(v) for v in (B, T, C, S, num_digits, step_length, seed, split,
+                                                                  first_id))
+    if B < 0 or T < 1 or C < 1:
+        raise ValueError("%s: need B >= 0, T >= 1, C >= 1 (got %d, %d, %d)" % (fn, B, T, C))
+    if not 28 < S <= 4096:
+        raise ValueError("%s: image size %d must exceed the digit size 28 (and be <= 4096)" % (fn, S))
+    if not 1 <= nd <= 8:
+        raise ValueError("%s: num_digits %d not in [1, 8]" % (fn, nd))
+    if not 1 <= L_ <= 1 << 20:
+        raise ValueError("%s: step_length %d must be >= 1" % (fn, L_))
+    for v, nm in ((seed, "seed"), (split, "split"), (first_id, "first_id")):
+        if not 0 <= v < 1 << 63:
+            raise ValueError("%s: %s %d not in [0, 2^63)" % (fn, nm, v))
+    if B * T > 0x7fffffff:
+        raise ValueError("%s: B * T = %d frames exceed one launch" % (fn, B * T))
+    return digits.contiguous(), B, T, C, S, nd, L_, seed, split, first_id
+
+
 def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, deterministic, seed, split, first_id,
                         trajectories=False):
     """Stochastic Moving MNIST batch rendered on the GPU (rfn_moving_mnist_render_f32: the reference's
@@ -2443,29 +2470,8 @@ def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, determinist
     [B, T, C, S, S] in [0, 1] on the digits' device, sequence b having the id first_id + b; with trajectories=True also
     the int64 [B, num_digits, T, 3] (digit index, y, x) of every digit and frame.  `digits`: uint8 [N, 28, 28] device
     table.  One launch on the current stream; no CPU fallback."""
-    if not isinstance(digits, torch.Tensor) or digits.dtype != torch.uint8:
-        raise TypeError("moving_mnist_render: digits must be a uint8 tensor, got %s" %
-                        (digits.dtype if isinstance(digits, torch.Tensor) else type(digits).__name__))
-    if digits.dim() != 3 or tuple(digits.shape[1:]) != (28, 28) or digits.shape[0] < 1:
-        raise ValueError("moving_mnist_render: digits must be [N >= 1, 28, 28], got %s" % (tuple(digits.shape),))
-    if not digits.is_cuda:
-        raise RuntimeError("rfn_hip kernels need device tensors; digits is on %s (no CPU fallback)" % digits.device)
-    B, T, C, S, nd, L_, seed, split, first_id = (int(v) for v in (B, T, C, S, num_digits, step_length, seed, split,
-                                                                  first_id))
-    if B < 0 or T < 1 or C < 1:
-        raise ValueError("moving_mnist_render: need B >= 0, T >= 1, C >= 1 (got %d, %d, %d)" % (B, T, C))
-    if not 28 < S <= 4096:
-        raise ValueError("moving_mnist_render: image size %d must exceed the digit size 28 (and be <= 4096)" % S)
-    if not 1 <= nd <= 8:
-        raise ValueError("moving_mnist_render: num_digits %d not in [1, 8]" % nd)
-    if not 1 <= L_ <= 1 << 20:
-        raise ValueError("moving_mnist_render: step_length %d must be >= 1" % L_)
-    for v, nm in ((seed, "seed"), (split, "split"), (first_id, "first_id")):
-        if not 0 <= v < 1 << 63:
-            raise ValueError("moving_mnist_render: %s %d not in [0, 2^63)" % (nm, v))
-    if B * T > 0x7fffffff:
-        raise ValueError("moving_mnist_render: B * T = %d frames exceed one launch" % (B * T))
-    digits = digits.contiguous()
+    digits, B, T, C, S, nd, L_, seed, split, first_id = _moving_mnist_args(
+        "moving_mnist_render", digits, B, T, C, S, num_digits, step_length, seed, split, first_id)
     out = torch.empty((B, T, C, S, S), device=digits.device, dtype=torch.float32)
     traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
     if B:
@@ -2475,6 +2481,30 @@ def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, determinist
                    S, nd, L_, 1 if deterministic else 0, seed, split, first_id,
                    meta=("shell", "moving_mnist", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
     return (out, traj) if trajectories else out
+
+
+def moving_mnist_sync_render(digits, B, T, C, S, num_digits, step_length, deterministic, seed, split, first_id,
+                             trajectories=False, hits=False):
+    """Synchronized Moving MNIST batch (rfn_moving_mnist_sync_render_f32: the reference's MovingMNIST_synchronized,
+    stochasticMovingMnist.py:131-248): moving_mnist_render's arguments and outputs, but all sequences share one
+    trajectory per digit (start position drawn, velocity (3, 3), the bounces with step_length / deterministic) and only
+    the digit identities depend on the sequence id.  With hits=True also the int32 [B, T] hit table: the largest
+    n + 1 over the digits clamped at a wall on frame t, 0 if none (every row the same).  Returns out, or the tuple
+    (out[, traj][, hit]).  One launch on the current stream; no CPU fallback."""
+    digits, B, T, C, S, nd, L_, seed, split, first_id = _moving_mnist_args(
+        "moving_mnist_sync_render", digits, B, T, C, S, num_digits, step_length, seed, split, first_id)
+    out = torch.empty((B, T, C, S, S), device=digits.device, dtype=torch.float32)
+    traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
+    hit = torch.empty((B, T), device=digits.device, dtype=torch.int32) if hits else None
+    if B:
+        with torch.cuda.device(digits.device):
+            L.call("rfn_moving_mnist_sync_render_f32", digits.data_ptr(), int(digits.shape[0]),
+                   L.dev(out), traj.data_ptr() if traj is not None else None,
+                   hit.data_ptr() if hit is not None else 0, B, T, C,
+                   S, nd, L_, 1 if deterministic else 0, seed, split, first_id,
+                   meta=("shell", "moving_mnist_sync", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
+    extra = tuple(v for v in (traj, hit) if v is not None)
+    return (out,) + extra if extra else out
 
 
 def clip_gather(store, first, T, C):
