@@ -367,6 +367,22 @@ int rfn_conv3x3_wgrad_rows_mirrored_grouped_bf16x3(const float* const* h, long h
                                                    long g_ns, int C, float* const* gwT, int G, int F, int H, int W,
                                                    rfn_stream_t stream);
 const char* rfn_conv3x3_wgrad_rows_mirrored_kernel_label_bf16x3(int Cin, long h_ns, int C, int G, int F, int H, int W);
+/* 3x3 (pad 1) weight gradient of a conv whose BOTH channel counts are small (Cout <= 128, C1 + C2 <= 128; W % 8 == 0),
+ * whichever is larger: the arguments, codes, accumulation into the caller's zeroed gw and the output layout
+ * [Cout][Cin][3][3] of rfn_conv3x3_wgrad_implicit_bf16x3.  The unit of work is a band of R image rows of one frame (R
+ * divides H, R * W % 16 == 0): a persistent workgroup stages the band of g and of the input (with its halo rows) once
+ * per band, split to bf16 (hi, lo), the three x shifts as three copies in LDS; every tap is an LDS address.  Columns
+ * are split by whole input channels over blockIdx.y, rows beyond 64 over blockIdx.z; one tail of float atomics per
+ * launch.  -2 where rfn_conv3x3_wgrad_band_supported answers 0 (no band of the map fits the LDS of half a CU, W % 8
+ * != 0, a channel count above 128); the label query answers "" there.  The entry point takes every supported shape;
+ * the size rule is rfn_hip.ops.wgrad_plan's.  rfn_conv3x3_wgrad_band_geometry: what a launch would use, {R, channels
+ * per column block, grid x, y, z, LDS bytes}, without a device. */
+int rfn_conv3x3_wgrad_band_supported(int Cout, int Cin, int H, int W);
+int rfn_conv3x3_wgrad_band_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
+                                  const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
+                                  rfn_stream_t stream);
+const char* rfn_conv3x3_wgrad_band_kernel_label_bf16x3(int Cout, int Cin, int F, int H, int W);
+int rfn_conv3x3_wgrad_band_geometry(int Cout, int Cin, int F, int H, int W, long long* out6);
 /* K split of a GROUPED launch of the LDS-DMA ring kernels (gemm_wgrad_dma_kernel, gemm_wgrad_dma_impl_kernel), as
  * host-only queries that launch nothing and run the very functions the kernels and launchers run.  The unit of work is
  * the flat stage space of one output tile: G * n_stages stages (n_stages = F * HW / 32), group g owning

@@ -9,6 +9,8 @@
 //   * mirrored  the same for the few-output conv, Cout < Cin: the gradient's planes, taps mirrored and roles swapped
 //               (rfn_conv3x3_wgrad_mirrored_bf16x3)
 //   * implicit_rows / mirrored_rows  the two on 4-pixel rows and 2 x 2 maps (rfn_conv3x3_wgrad_rows[_mirrored]_bf16x3)
+//   * band      3x3 with few channels on BOTH sides, ungrouped: nothing expanded, nothing loaded per row -- bands of image rows of both operands
+//               staged once, every tap an LDS address (wgrad_band_kernel, rfn_conv3x3_wgrad_band_bf16x3, further down)
 // (its other two forms, f32 and scatter_f32, are the fp32 kernel of conv.hip).  The first three expand the SMALL operand
 // in HBM, so the shifted-window reads of a 3x3 weight gradient never reach their kernel and the 8 consecutive k (pixels) an
 // MFMA operand lane needs are 8 consecutive fp32 of one channel plane in NCHW: staged with 16-byte loads, split into
@@ -1261,6 +1263,307 @@ extern "C" int rfn_conv3x3_wgrad_rows_mirrored_grouped_bf16x3(const float* const
                                                               int G, int F, int H, int W, rfn_stream_t stream) {
     RFN_CHECK_ARG(G >= 1 && G <= 16, -1);
     return rfn_conv3x3_wgrad_mirrored_bf16x3_body(G, h, h_ns, Cin, g, g_ns, C, gwT, F, H, W, stream, true);
+}
+
+// ------------------------------------------------------------------------------------------------ band kernel
+// 3x3 weight gradients whose BOTH channel counts are small (the extractor / upscaler blocks, 16 .. 128 channels on
+// 64 x 64 .. 8 x 8 maps): gemm_wgrad_b3_kernel<..., IMPL = 1> fetches every input pixel nine times, once per row
+// (ci, tap) of its B operand, and the Cin > Cout layers expand the gradient ninefold in HBM first.  Here the unit of work
+// is a BAND, R consecutive image rows of one frame (R | H, R W % 16 == 0): a workgroup stages the band of g (its Cout
+// planes) and the band of the input with one halo row above and below (zero beyond the frame) ONCE, split to bf16
+// (hi, lo) on the way into LDS, and every shifted operand is LDS addressing:
+//   * a dy shift is a row offset;
+//   * the three dx shifts are three staged copies of the input band, zero beyond the row ends, so a B fragment of column
+//     n = ci*9 + tap is ONE aligned 16-byte read of 8 consecutive pixels: copy tap % 3, plane ci, row y + tap / 3;
+//   * strides (16-byte units): rows RSU = W/8 | 1, planes PS = 9a, copies CS = a (mod 16) with a = 11 RSU (3a = RSU):
+//     column n reads unit a n + const (mod 16), a odd, so the 16 lanes of a ds_read_b128 group (16 consecutive n mod 16)
+//     hit 16 different 16-byte slots of the 256-byte bank row.  The gradient's rows have an odd stride for the same reason.
+// K = the band's pixels: the four waves of a workgroup take the 16-pixel k-steps of a band in turn and each keeps ALL
+// MT x NTC accumulator tiles (every fragment is read from LDS by exactly one wave).  Workgroups are persistent, two per
+// CU (one stages while the other multiplies): each walks a contiguous range of the (frame, band) units with its
+// accumulators in registers, then the four waves' tiles are summed through LDS and flushed with float atomics once.
+// PF: the loads of the next band's first staging round are issued ahead of the MFMAs of the current band and committed
+// after them (one row tile: 0.164 -> 0.128 ms for 16 x 144 on 640 frames of 64 x 64); with two row tiles the 160
+// accumulator registers leave no room for the round (it spilled), and the second workgroup of the CU is the only overlap.
+// Columns are split by whole input channels over blockIdx.y (CPB channels, 9 CPB <= 32 NTC columns: a block stages only
+// its planes), rows of more than 32 MT output channels over blockIdx.z.  Both orientations (Cin <= Cout, Cin > Cout)
+// are the same problem; the output is the torch layout [Cout][Cin][3][3].
+struct WgBandGeom {
+    int R, CPB;                  // rows per band, input channels per column block
+    int WU, RSU, PS, CS, AS;     // 16-byte units: per image row, strides of staged rows / planes / copies, of a g row
+    int Arows;                   // gradient rows a block stages
+    size_t lds;
+};
+struct WgBandParams {
+    const float* g; const float* in1; const float* in2;
+    float* gw;
+    long g_ns, in1_ns, in2_ns;
+    int Cout, C1, C2, F, H, W;
+    int nbands, units;           // bands per frame, F * nbands
+    WgBandGeom q;
+};
+constexpr int WG_BAND_NTC = 5, WG_BAND_CPB = 32 * WG_BAND_NTC / 9;   // 16 channels = 144 of 160 columns
+constexpr size_t WG_BAND_LDS_MAX = 79 * 1024;                         // two workgroups per CU
+constexpr size_t WG_BAND_RED = 4 * 16 * 64 * sizeof(float);           // the flush's scratch: one tile of four waves
+constexpr int wg_band_pad16(int x, int r) { return x + ((r - x % 16) + 16) % 16; }   // smallest y >= x, y % 16 == r
+// LDS image of a block: a constexpr function of (channels per column block, gradient rows, W, R)
+constexpr WgBandGeom wg_band_geom(int cpb, int arows, int W, int R) {
+    WgBandGeom q{};
+    q.R = R; q.CPB = cpb; q.Arows = arows;
+    q.WU = W / 8;
+    q.RSU = q.WU | 1;
+    const int a = 11 * q.RSU % 16;
+    q.PS = wg_band_pad16((R + 2) * q.RSU, 9 * a % 16);
+    q.CS = wg_band_pad16(cpb * q.PS, a);
+    q.AS = (R * q.WU) | 1;
+    q.lds = (size_t)16 * (2 * arows * q.AS + 6 * q.CS);
+    if (q.lds < WG_BAND_RED) q.lds = WG_BAND_RED;
+    return q;
+}
+static_assert(wg_band_geom(16, 16, 64, 2).lds <= WG_BAND_LDS_MAX, "16 channels of a 64-pixel-wide map: two rows per band");
+// row tiles per block (MT), and the geometry: the most channels per column block (at most WG_BAND_CPB, evenly over the
+// blocks), then the tallest band whose image fits two workgroups per CU.  false: no band fits, or W % 8 != 0.
+static bool wg_band_choose(int Cout, int Cin, int H, int W, int& mt, WgBandGeom& q) {
+    if (Cout < 1 || Cin < 1 || Cout > 128 || Cin > 128 || H < 1 || W < 8 || W % 8 != 0) return false;
+    mt = Cout <= 32 ? 1 : 2;
+    const int arows = Cout < 32 * mt ? Cout : 32 * mt;
+    for (int cap = Cin < WG_BAND_CPB ? Cin : WG_BAND_CPB; cap >= 1; cap /= 2) {
+        const int cpb = ceil_div(Cin, ceil_div(Cin, cap));
+        for (int R = H; R >= 1; --R) {
+            if (H % R != 0 || (R * W) % 16 != 0) continue;
+            q = wg_band_geom(cpb, arows, W, R);
+            if (q.lds <= WG_BAND_LDS_MAX) return true;
+        }
+    }
+    return false;
+}
+
+template <int MT, int NTC, bool PF>
+__global__ __launch_bounds__(256, 2) void wgrad_band_kernel(const WgBandParams p) {
+    constexpr int NT = 256, U = 2;   // U: units of each operand a thread has in flight per staging round
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    const WgBandGeom& q = p.q;
+    bf16x8* Ah = reinterpret_cast<bf16x8*>(lds_raw);
+    bf16x8* Al = Ah + q.Arows * q.AS;
+    bf16x8* Bh = Al + q.Arows * q.AS;
+    bf16x8* Bl = Bh + 3 * q.CS;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, kk = lane >> 5;
+    const int Cin = p.C1 + p.C2, HW = p.H * p.W;
+    const int c0 = blockIdx.y * q.CPB, nch = Cin - c0 < q.CPB ? Cin - c0 : q.CPB;
+    const int m0 = blockIdx.z * 32 * MT, mrows = p.Cout - m0 < 32 * MT ? p.Cout - m0 : 32 * MT;
+    // my units: a contiguous range (neighbouring bands share their halo rows in L2); none left for the last workgroups
+    // when the units do not divide
+    const int per = (p.units + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int u0 = blockIdx.x * per, u1 = u0 + per < p.units ? u0 + per : p.units;
+    if (u0 >= u1) return;
+
+    f32x16 acc[MT][NTC];
+    wg_zero(acc);
+    // fragment bases: gradient row m (rows beyond the block's take row 0, columns beyond 9 nch column 0; never flushed)
+    int aoff[MT], boff[NTC];
+#pragma unroll
+    for (int i = 0; i < MT; ++i) aoff[i] = (i * 32 + l31 < mrows ? i * 32 + l31 : 0) * q.AS;
+#pragma unroll
+    for (int j = 0; j < NTC; ++j) {
+        const int n = j * 32 + l31 < 9 * nch ? j * 32 + l31 : 0;
+        const int ci = n / 9, tap = n - ci * 9;
+        boff[j] = (tap % 3) * q.CS + ci * q.PS + (tap / 3) * q.RSU;
+    }
+    const int PU = q.R * q.WU, nA = mrows * PU;                    // units of the gradient band
+    const int perch = (q.R + 2) * q.WU, nB = nch * perch;          // units of the input band with its halo rows
+    const int nmax = nA > nB ? nA : nB;
+
+    // One staging round: U units of each operand per thread, unit e = base + k NT.  The loads are unconditional (clamped;
+    // the masks apply at the stores) and are not touched before store_round, so a round issued ahead of the MFMAs of the
+    // band before stays in flight behind them.
+    float4 av[U][2], bv[U][2];
+    float bl_[U], br_[U];
+    int ao[U], bo[U];
+    bool aok[U], bok[U], rok[U];
+    auto load_round = [&](const int u, const int base) {
+        const int f = u / p.nbands, y0 = (u - f * p.nbands) * q.R;
+        const float* gsrc = p.g + (long)f * p.g_ns + (long)m0 * HW + y0 * p.W;
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int e = base + k * NT;
+            aok[k] = e < nA;
+            const int ee = aok[k] ? e : 0;
+            const int co = ee / PU, pu = ee - co * PU;
+            const float* src = gsrc + (long)co * HW + pu * 8;
+            av[k][0] = *reinterpret_cast<const float4*>(src);
+            av[k][1] = *reinterpret_cast<const float4*>(src + 4);
+            ao[k] = co * q.AS + pu;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            const int e = base + k * NT;
+            bok[k] = e < nB;
+            const int ee = bok[k] ? e : 0;
+            const int ci = ee / perch, r = ee - ci * perch;
+            const int rr = r / q.WU, xg = r - rr * q.WU;
+            const int yy = y0 - 1 + rr, cg = c0 + ci;
+            rok[k] = yy >= 0 && yy < p.H;
+            const float* plane = cg < p.C1 ? p.in1 + (long)f * p.in1_ns + (long)cg * HW
+                                           : p.in2 + (long)f * p.in2_ns + (long)(cg - p.C1) * HW;
+            const float* src = plane + (rok[k] ? yy : y0) * p.W + xg * 8;
+            bv[k][0] = *reinterpret_cast<const float4*>(src);
+            bv[k][1] = *reinterpret_cast<const float4*>(src + 4);
+            // the elements beyond the 8, clamped into them where the image row ends (rok then also clears them)
+            bl_[k] = src[xg > 0 ? -1 : 0];
+            br_[k] = src[xg + 1 < q.WU ? 8 : 7];
+            bo[k] = (ci * q.PS + rr * q.RSU + xg) | (xg > 0 ? 0 : 1 << 30) | (xg + 1 < q.WU ? 0 : 1 << 29);
+        }
+    };
+    auto store_round = [&]() {
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (aok[k]) {
+                bf16x8 hi, lo;
+                wg_split8(f32x4{av[k][0].x, av[k][0].y, av[k][0].z, av[k][0].w},
+                          f32x4{av[k][1].x, av[k][1].y, av[k][1].z, av[k][1].w}, hi, lo);
+                Ah[ao[k]] = hi;
+                Al[ao[k]] = lo;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            if (bok[k]) {
+                // the 10 pixels x - 1 .. x + 8 split once; copy d holds pixels d .. d + 7 of them: in[x + d - 1]
+                const int o = bo[k] & 0xFFFFFF;
+                const float v[10] = {(bo[k] >> 30) & 1 ? 0.f : bl_[k], bv[k][0].x, bv[k][0].y, bv[k][0].z, bv[k][0].w,
+                                     bv[k][1].x, bv[k][1].y, bv[k][1].z, bv[k][1].w, (bo[k] >> 29) & 1 ? 0.f : br_[k]};
+                __bf16 h[10], l[10];
+#pragma unroll
+                for (int c = 0; c < 10; ++c) {
+                    const float x = rok[k] ? v[c] : 0.f;
+                    h[c] = (__bf16)x;
+                    l[c] = (__bf16)(x - (float)h[c]);
+                }
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    bf16x8 hi, lo;
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) {
+                        hi[c] = h[c + d];
+                        lo[c] = l[c + d];
+                    }
+                    Bh[d * q.CS + o] = hi;
+                    Bl[d * q.CS + o] = lo;
+                }
+            }
+        }
+    };
+
+    if (PF) load_round(u0, tid);
+    for (int u = u0; u < u1; ++u) {
+        __syncthreads();   // everybody has left the previous band's fragments
+        if (PF) store_round();
+        for (int b0 = PF ? NT * U : 0; b0 < nmax; b0 += NT * U) {   // (PF: the rounds after the first, not ahead)
+            load_round(u, b0 + tid);
+            store_round();
+        }
+        __syncthreads();
+        if (PF) {   // the next band's first round, in flight behind this band's MFMAs (past the end: this band again, unused)
+            load_round(u + 1 < u1 ? u + 1 : u, tid);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // the band's k-steps of 16 pixels, wave w the steps w, w + 4, ...: lane (l31, kk) reads pixel group 2 s + kk
+        for (int s = wave; 2 * s < PU; s += 4) {
+            const int pg = 2 * s + kk;
+            const int yl = pg / q.WU, xg = pg - yl * q.WU;
+            const int ko = yl * q.RSU + xg;
+            bf16x8 ah[MT], al[MT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                ah[i] = Ah[aoff[i] + pg];
+                al[i] = Al[aoff[i] + pg];
+            }
+#pragma unroll
+            for (int j = 0; j < NTC; ++j) {
+                const bf16x8 bh = Bh[boff[j] + ko], bl = Bl[boff[j] + ko];
+#pragma unroll
+                for (int i = 0; i < MT; ++i) wg_mfma3(acc[i][j], ah[i], al[i], bh, bl);
+            }
+        }
+    }
+
+    // flush: per tile, the four waves' copies through LDS -- wave w adds registers 4w .. 4w + 3 of all four -- and one
+    // float atomic per real output
+    float* red = reinterpret_cast<float*>(lds_raw);   // [wave][register][lane]
+    const int Nc = 9 * Cin;
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NTC; ++j) {
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[i][j][r];
+            __syncthreads();
+            const int n = j * 32 + l31;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int r = wave * 4 + t;
+                float sum = 0.f;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) sum += red[(w * 16 + r) * 64 + lane];
+                const int m = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                if (m < mrows && n < 9 * nch) atomicAdd(&p.gw[(long)(m0 + m) * Nc + 9 * c0 + n], sum);
+            }
+        }
+}
+
+static const char* const kWgradBandLabels[2] = {"wgrad_band_kernel<1,5,1>", "wgrad_band_kernel<2,5,0>"};
+extern "C" int rfn_conv3x3_wgrad_band_supported(int Cout, int Cin, int H, int W) {
+    int mt;
+    WgBandGeom q;
+    return wg_band_choose(Cout, Cin, H, W, mt, q) ? 1 : 0;
+}
+extern "C" const char* rfn_conv3x3_wgrad_band_kernel_label_bf16x3(int Cout, int Cin, int F, int H, int W) {
+    int mt;
+    WgBandGeom q;
+    return wg_band_choose(Cout, Cin, H, W, mt, q) ? kWgradBandLabels[mt - 1] : "";
+}
+// the launch geometry, for the tests and the benchmark: {R, CPB, grid x, y, z, LDS bytes}; 0, or -2 as the entry point
+extern "C" int rfn_conv3x3_wgrad_band_geometry(int Cout, int Cin, int F, int H, int W, long long* out6) {
+    int mt;
+    WgBandGeom q;
+    RFN_CHECK_ARG(out6 && F >= 1, -1);
+    RFN_CHECK_ARG(wg_band_choose(Cout, Cin, H, W, mt, q), -2);
+    const int gy = ceil_div(Cin, q.CPB), gz = ceil_div(Cout, 32 * mt);
+    const long units = (long)F * (H / q.R), slots = 512 / (gy * gz) > 1 ? 512 / (gy * gz) : 1;
+    out6[0] = q.R; out6[1] = q.CPB; out6[2] = (int)(units < slots ? units : slots); out6[3] = gy; out6[4] = gz;
+    out6[5] = (int)q.lds;
+    return 0;
+}
+// The contract of rfn_conv3x3_wgrad_implicit_bf16x3 (two-source input, frame strides, accumulates into the caller's
+// zeroed gw, no memset), for every shape rfn_conv3x3_wgrad_band_supported names, however small.
+extern "C" int rfn_conv3x3_wgrad_band_bf16x3(const float* g, long g_ns, int Cout, const float* in1, long in1_ns, int C1,
+                                             const float* in2, long in2_ns, int C2, float* gw, int F, int H, int W,
+                                             rfn_stream_t stream) {
+    RFN_CHECK_ARG(g && in1 && gw && Cout > 0 && C1 > 0 && C2 >= 0 && (C2 == 0 || in2) && F >= 0 && H > 0 && W > 0, -1);
+    int mt;
+    WgBandParams p{};
+    RFN_CHECK_ARG(wg_band_choose(Cout, C1 + C2, H, W, mt, p.q) && g_ns % 4 == 0 && in1_ns % 4 == 0 &&
+                      (C2 == 0 || in2_ns % 4 == 0), -2);
+    RFN_CHECK_ARG(wg_aligned16(g, in1, C2 ? in2 : in1), -3);
+    RFN_CHECK_ARG((long)F * H * W < (1L << 31) - 4096, -4);
+    if (F == 0) return 0;
+    p.g = g; p.in1 = in1; p.in2 = C2 ? in2 : in1; p.gw = gw;
+    p.g_ns = g_ns; p.in1_ns = in1_ns; p.in2_ns = C2 ? in2_ns : in1_ns;
+    p.Cout = Cout; p.C1 = C1; p.C2 = C2; p.F = F; p.H = H; p.W = W;
+    p.nbands = H / p.q.R;
+    p.units = F * p.nbands;
+    const int gy = ceil_div(C1 + C2, p.q.CPB), gz = ceil_div(Cout, 32 * mt);
+    const int slots = 512 / (gy * gz) > 1 ? 512 / (gy * gz) : 1;   // two workgroups on each of the 256 CUs
+    const dim3 grid(p.units < slots ? p.units : slots, gy, gz);
+    auto kern = mt == 1 ? wgrad_band_kernel<1, WG_BAND_NTC, true> : wgrad_band_kernel<2, WG_BAND_NTC, false>;
+    if (p.q.lds > 65536)
+        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.q.lds);
+    hipLaunchKernelGGL(kern, grid, dim3(256), p.q.lds, (hipStream_t)stream, p);
+    RFN_LAUNCH_CHECK();
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ im2col (3x3, pad 1)

@@ -509,6 +509,18 @@ def wgrad_short_rows():
     return os.environ.get("RFN_WGRAD_SHORT_ROWS") != "0"
 
 
+WGRAD_BAND_MIN_PIXELS = (1 << 15, 1 << 17)
+
+
+def wgrad_band_min_pixels(Cout=1):
+    """fewest pixels N * H * W at which an ungrouped 3x3 gradient with Cout <= 128 and Cin <= 128 takes the band kernel:
+    RFN_WGRAD_BAND_MIN_PIXELS, or 2^15 up to 32 output channels (one row tile: the kernel that prefetches the next band)
+    and 2^17 above (two row tiles, a longer tail of atomics: between 2^13 and 2^17 pixels it loses to the implicit
+    kernel on some shapes) -- tools/bench_wgrad.py band, DESIGN.md section 4.  RFN_WGRAD_BAND=0: never."""
+    env = os.environ.get("RFN_WGRAD_BAND_MIN_PIXELS")
+    return int(env) if env is not None else WGRAD_BAND_MIN_PIXELS[0 if Cout <= 32 else 1]
+
+
 def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=False, min_pixels=0, stacked=False,
                short_rows=False):
     """How the weight gradient(s) [Cout, C1 + C2, ks, ks] of a convolution on N frames of H x W are computed, from shapes,
@@ -521,9 +533,11 @@ def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=Fal
     kernel) a split-precision 3x3 gradient is ONE launch that shifts the taps while staging -- "mirrored_rows" for a
     Conv2dZeros, "implicit_rows" for every other conv whatever Cin against Cout (no cat of a two-source input) --
     instead of im2col / tap scatter + GEMM.  The training path passes wgrad_short_rows().
+    "band": an ungrouped split-precision 3x3 gradient with Cout <= 128, Cin <= 128 and W % 8 == 0 on at least
+    wgrad_band_min_pixels(Cout) pixels N * H * W, where the library names a band kernel -- one launch, either orientation.
     Returns WgradPlan(form, G, M, Nc, launches): the form (table in DESIGN.md, "Where the labels come from"), the GEMM
     dimensions gw[M][Nc] and, in order, the (entry point, label) of every library launch.  CONV_PRECISION,
-    RFN_WGRAD_IMPLICIT, RFN_WGRAD_MIRRORED and the label queries are read on every call."""
+    RFN_WGRAD_IMPLICIT, RFN_WGRAD_MIRRORED, RFN_WGRAD_BAND[_MIN_PIXELS] and the label queries are read on every call."""
     Cin, HW, n = C1 + C2, H * W, max(G, 1)
     g_ns = Cout * HW if g_ns is None else g_ns
     in1_ns = C1 * HW if in1_ns is None else in1_ns
@@ -556,6 +570,12 @@ def wgrad_plan(G, N, C1, C2, Cout, H, W, ks, g_ns=None, in1_ns=None, few_out=Fal
             launch = _b3_launch(G, "rfn_conv3x3_wgrad_rows_bf16x3", Cout, g_ns, G, N, H, W)
             if launch[1]:
                 return plan("implicit_rows", Cout, 9 * Cin, launch)
+    if (ks == 3 and b3 and not G and Cout <= 128 and Cin <= 128 and W % 8 == 0 and N * HW >= wgrad_band_min_pixels(Cout)
+            and os.environ.get("RFN_WGRAD_BAND") != "0"):
+        # both channel counts small, whichever is larger: bands of image rows staged once, every tap an LDS address
+        launch = _b3_launch(0, "rfn_conv3x3_wgrad_band_bf16x3", Cout, Cin, N, H, W)
+        if launch[1]:   # ('': no band of this map fits the kernel's LDS image)
+            return plan("band", Cout, 9 * Cin, launch)
     if Cin <= Cout:   # the input is the small operand: its shifted planes built while staging, or expanded in memory
         if W % 8 == 0 and os.environ.get("RFN_WGRAD_IMPLICIT") != "0":
             return plan("implicit", Cout, 9 * Cin,
@@ -614,7 +634,7 @@ def _wgrad_run(plan, in1s, in2s, gs, ks, arena=None, g_stacked=None):
             L.call(entry, L.dev(gwt), L.dev(out[0]), Cout, Cin, ks, 0, meta=_shell(label, out[0], 2))
     elif form == "gemm":
         out = [t.view(Cout, Cin, 1, 1) for t in _gemm_wgrad(G, gs, cat(), Cout, Cin, arena, next(todo))]
-    elif form in ("implicit", "implicit_rows"):   # rows (ci, tap) of the implicit operand: already the torch layout
+    elif form in ("implicit", "implicit_rows", "band"):   # rows (ci, tap) of the shifted operand: already the torch layout
         gw = _b3_wgrad(next(todo), G, [(gs, "g", Cout), (in1s, "in1", C1), (in2s, "in2", C2)], Cout, 9 * Cin, (N, H, W), arena,
                        " %s3x3" % form)
         out = [t.view(Cout, Cin, 3, 3) for t in gw]

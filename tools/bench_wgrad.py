@@ -7,6 +7,9 @@ the gradient while staging.  python tools/bench_wgrad.py conv3 [frames ...]: the
 python tools/bench_wgrad.py rows [frames ...]: conv1 and conv3 of the two deepest levels (4 x 4 and 2 x 2 maps, ten groups):
 the expanding route -- its im2col / tap-scatter passes and its GEMM reported apart -- beside the one short-row launch
 (builds without the short-row forms print the expanding route only).
+python tools/bench_wgrad.py band [frames ...]: the 3x3 weight gradients of the few-channel layers (extractor / upscaler
+blocks; both orientations), all launches of the old route (implicit, or tap scatter + GEMM; RFN_WGRAD_BAND=0) beside the
+one band launch, ms and TB/s of the operand bytes (builds without the band kernel print the old route only).
 RFN_PKG_DIR selects another build of the package (A/B on the same box, as bench.py)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,7 +141,50 @@ def rows(F_, G=10):
         del h, gh, z, cond, go
 
 
+# (Cout, Cin, S): the implicit few-channel rows of a B = 32 step, then the Cin > Cout layers
+BAND_SHAPES = ((16, 16, 64), (16, 16, 32), (32, 32, 32), (32, 16, 32), (32, 32, 16), (64, 64, 16), (64, 32, 16), (64, 64, 8),
+               (128, 128, 8), (16, 64, 32), (32, 128, 16))
+
+
+def _route_ms(fn, reps=7):
+    """fn() reps times after a warm-up: median over the reps of the summed time of ALL its launches, launches, first label"""
+    fn()
+    torch.cuda.synchronize()
+    sums = []
+    for _ in range(reps):
+        L.PROFILE = []
+        fn()
+        torch.cuda.synchronize()
+        ev = [(m[1], e0.elapsed_time(e1)) for (_, m, e0, e1) in L.PROFILE if m is not None]
+        L.PROFILE = None
+        sums.append(sum(t for _, t in ev))
+    return sorted(sums)[len(sums) // 2], len(ev), ev[-1][0]
+
+
+def band(F_):
+    torch.manual_seed(0)
+    has_band = hasattr(K, "wgrad_band_min_pixels")
+    for Cout, Cin, S in BAND_SHAPES:
+        x, g = torch.randn(F_, Cin, S, S, device="cuda"), torch.randn(F_, Cout, S, S, device="cuda")
+        by = 4.0 * F_ * S * S * (Cin + Cout)
+        os.environ["RFN_WGRAD_BAND"] = "0"
+        t0, n0, l0 = _route_ms(lambda: K.conv2d_wgrad(x, None, g, Cout, 3))
+        row = "F%d %3dx%-4d HW%-4d  old %7.4f ms %5.2f TB/s in %d (%s)" % (F_, Cout, 9 * Cin, S * S, t0, by / t0 / 1e9, n0, l0)
+        if has_band:
+            os.environ["RFN_WGRAD_BAND"] = "1"
+            os.environ["RFN_WGRAD_BAND_MIN_PIXELS"] = "1"
+            t1, n1, l1 = _route_ms(lambda: K.conv2d_wgrad(x, None, g, Cout, 3))
+            del os.environ["RFN_WGRAD_BAND_MIN_PIXELS"]
+            row += "   band %7.4f ms %5.2f TB/s in %d (%s)  x%.2f" % (t1, by / t1 / 1e9, n1, l1, t0 / t1)
+        print(row, flush=True)
+        del x, g
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "band":
+        for F_ in [int(v) for v in sys.argv[2:]] or [640, 608]:
+            band(F_)
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "rows":
         for F_ in [int(v) for v in sys.argv[2:]] or [608, 76]:
             rows(F_)
