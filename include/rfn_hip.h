@@ -1048,6 +1048,49 @@ int rfn_i3d_resize_u8(const void* frames, long frame_stride, int NF, int C, int 
 int rfn_i3d_head_f32(const float* in, long in_floats, int N, int Tp, int P, int C, const float* wpack, long wpack_floats,
                      const float* bias, int Cout, float* out, rfn_stream_t stream);
 
+/* ---- the linear-extrapolation baseline, csrc/linear_extrap.hip  (averagemodel/averagemodel.py, SimpleLinearModel;
+ * DESIGN.md section 26 is the contract).  x: float32 [B, T, C, H, W] whose frames are dense blocks of CHW = C*H*W
+ * floats, seq_stride / frame_stride in elements; the window is frames start .. start+n-1 of every sequence, read in
+ * place.  Features of one pixel's window x_0 .. x_{n-1}, in this order: x_f for f = 0 .. n-1, then for k = 0 .. n-2 and
+ * inside that j = 0 .. n-k-2 the difference x_j - x_{j+k+1} (get_lagged_differences, :65-71); F = n (n + 1) / 2,
+ * 1 <= n <= RFN_LINEXT_MAX_FRAMES.  w: F floats, bias: 1 float;  pred = bias + sum_f w[f] feat_f as one fma chain in
+ * feature order, the differences formed in registers (never collapsed into per-frame weights).  16-byte loads and
+ * stores when CHW and both strides are multiples of 4 and the bases are 16-byte aligned, single floats otherwise.
+ *
+ * rfn_linext_train_f32: target = frame start+n (start + n + 1 <= T), r = pred - target;
+ *   out[0] = mean r^2 over B*CHW,  out[1 + f] = mean 2 r feat_f  (= dL/dW[f]),  out[F + 1] = mean 2 r  (= dL/dbias).
+ *   Stage 1 (grid sized to the device, at most rfn_linext_max_blocks() workgroups and partial_floats / (F + 2)) writes
+ *   per-workgroup fp32 sums [blocks, F+2] to `partials`; stage 2, one workgroup, adds the rows in row order in fp64
+ *   and rounds once.  Two launches, no allocation.
+ * rfn_linext_rollout_f32: out [B, P, C, H, W] dense; frame t is pred of the window, which then drops its oldest frame
+ *   and takes the prediction (no clamping); a thread keeps its pixels' window in registers and writes all P frames.
+ *   start + n <= T, P >= 1; P = 1 is get_prediction.  One launch.
+ * rfn_gauss_quality_f32: pred, truth float32 [N, C, H, W] dense, read once as clamp(v * scale, lo, hi); per image
+ *   mse[n] = mean over C*H*W of the squared difference, and ssim[n] = pytorch_msssim.ssim(X, Y, data_range=255) of
+ *   that image: window g[i] = exp(-(i-5)^2 / (2 * 1.5^2)), i = 0..10, normalised to sum 1, applied separably per
+ *   channel without padding ((H-10) x (W-10) outputs); mu1 = g*X, mu2 = g*Y, s1 = g*(X X) - mu1^2, s2 = g*(Y Y) - mu2^2,
+ *   s12 = g*(X Y) - mu1 mu2, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ *   map = ((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)) ((2 s12 + C2) / (s1 + s2 + C2)); mean of map, then over channels.
+ *   The five row sums of a chunk of rows are fp32 fma chains formed in LDS from one load of X and Y; the column pass
+ *   and the formula run in fp64.  RFN_GAUSS_QUALITY_MIN_SIDE <= H, W <= RFN_GAUSS_QUALITY_MAX_SIDE.  One workgroup per image, one launch.
+ * All three: no atomics, fixed reduction orders (bit-identical run to run on one device); a bad size returns -1, a
+ * NULL pointer -2, and nothing is launched.  The three limits are read by the binding through the host-only queries
+ * below, like rfn_sheet_max_rows() (they are written in parentheses: the binding mirrors plain-integer defines only). */
+#define RFN_LINEXT_MAX_FRAMES (10)
+#define RFN_GAUSS_QUALITY_MIN_SIDE (11)
+#define RFN_GAUSS_QUALITY_MAX_SIDE (128)
+int rfn_linext_max_frames(void);
+int rfn_linext_max_blocks(void);
+int rfn_gauss_quality_min_side(void);
+int rfn_gauss_quality_max_side(void);
+int rfn_linext_train_f32(const float* x, long seq_stride, long frame_stride, int start, const float* w,
+                         const float* bias, float* partials, long partial_floats, float* out, int B, int T, int n,
+                         long CHW, rfn_stream_t stream);
+int rfn_linext_rollout_f32(const float* x, long seq_stride, long frame_stride, int start, const float* w,
+                           const float* bias, float* out, int B, int T, int n, int P, long CHW, rfn_stream_t stream);
+int rfn_gauss_quality_f32(const float* pred, const float* truth, float* ssim, float* mse, int N, int C, int H, int W,
+                          float scale, float lo, float hi, rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
