@@ -76,7 +76,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* sm /* >= 4 floats
 }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
-// torch.nn.Softplus(): x itself above the threshold 20 (shell.hip's Gaussian log-prob and latent step, iw_bound.hip)
+// torch.nn.Softplus(): x itself above the threshold 20 (gauss.hip's log-prob, recurrent_shell.hip's latent step, iw_bound.hip)
 __device__ __forceinline__ float softplusf_(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
@@ -101,4 +101,11 @@ static inline void rfn_zero_f32(float* p, long n, hipStream_t s) {
     long blocks = (n + 1023) / 1024;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(rfn_zero_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, n);
+}
+
+// Elementwise kernels templated on the accesses' width: launches k4 (kernel<4>, 16-byte accesses) when v4, else k1
+// (kernel<1>), with 256 threads per workgroup.  The two instantiations take the same arguments.
+template <typename... P, typename... A>
+static void launch_vec(bool v4, void (*k4)(P...), void (*k1)(P...), dim3 grid, hipStream_t s, A... args) {
+    hipLaunchKernelGGL(v4 ? k4 : k1, grid, dim3(256), 0, s, args...);
 }

@@ -21,7 +21,7 @@
 //     pixels (z1 | cond, a few KB) staged in LDS once per round -- loaded and converted one round ahead;
 //   * the last 3x3 convolution runs tap-expanded: P[tap*C + co][pixel] = Σ_c w3[co][c][tap] h2[c][pixel] is one more
 //     1x1 product on the register-resident h2 (9C <= 96 rows), and the cross-pixel part o[co] = Σ_tap P[tap,co][px+tap]
-//     is left to the gather kernel (shell.hip) -- 9C floats per pixel instead of the 256-channel h2.
+//     is left to the gather kernel (glow_shell.hip) -- 9C floats per pixel instead of the 256-channel h2.
 // h1 and h2 are still WRITTEN once (the backward pass needs them); they are never read back in the forward pass.
 //
 // Arithmetic ("f16x3s").  bits/dim parity (north_star: 1e-4) is decided by the forward pass, and two bf16 pieces per

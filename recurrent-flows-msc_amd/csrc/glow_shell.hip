@@ -1,56 +1,9 @@
-// HBM-bound "shell" kernels of the Glow step and the ConvLSTM gate update (gfx950).
-// Everything here is a streaming pass: coalesced NCHW loads along the pixel dimension (consecutive lanes =
-// consecutive pixels), per-frame / per-channel reductions done with wave shuffles + one LDS hop, never a GEMM.
+// The shell of a Glow step (gfx950): squeeze2d, channel statistics, ActNorm + InvConv forward / reverse / backward, affine
+// coupling, the fused forward and backward shell kernels, tap gather / scatter and the conv-epilogue backward.  Every
+// kernel is a streaming pass: coalesced NCHW loads along the pixel dimension, reductions by wave shuffles + one LDS hop,
+// never a GEMM.  Called by rfn_hip.ops (the Glow step and level nodes) and, through it, by Flow/.
 #include "common.h"
 #include "../../include/rfn_hip.h"
-#include <stdarg.h>
-
-static thread_local char g_err[512] = "";
-void rfn_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-extern "C" const char* rfn_last_error(void) { return g_err; }
-extern "C" int rfn_abi_version(void) { return 2; }
-
-#include <map>
-#include <mutex>
-#include <vector>
-float* rfn_workspace(hipStream_t s, size_t floats) {
-    // ONE buffer per device, whatever the stream: a hipGraph is captured on a fresh stream of its own, which must find
-    // the buffer its eager warm-up runs (on other streams) have grown.  Consequence, stated in include/rfn_hip.h: split-K
-    // convolutions issued on DIFFERENT streams of one device must not overlap in time.
-    static std::mutex mu;
-    static std::map<int, std::pair<float*, size_t>> tab;
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    auto& e = tab[dev];
-    if (e.second >= floats) return e.first;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone) {
-        rfn_set_error("split-K workspace must grow to %zu floats during a hipGraph capture: run this shape eagerly first", floats);
-        return nullptr;
-    }
-    // An outgrown buffer is NOT freed: a captured hipGraph has its address baked into kernel arguments and may be replayed
-    // after an eager call of a larger shape made the buffer grow (generation between training steps).  Growth is geometric,
-    // so the retired buffers add up to less than the live one; all of them go with the process.
-    static std::vector<float*> retired;
-    if (e.first) retired.push_back(e.first);
-    e.first = nullptr;
-    e.second = 0;
-    const size_t want = 2 * floats + 1024;
-    float* ptr = nullptr;
-    if (hipMalloc(&ptr, want * sizeof(float)) != hipSuccess) {
-        rfn_set_error("split-K workspace: hipMalloc of %zu bytes failed", want * sizeof(float));
-        return nullptr;
-    }
-    e.first = ptr;
-    e.second = want;
-    return ptr;
-}
 
 // ------------------------------------------------------------------------------------------------ squeeze2d
 // forward: each thread reads one float2 (input row 2h+i, cols 2w,2w+1) and writes the two output planes j=0,1.
@@ -1376,143 +1329,6 @@ extern "C" int rfn_affine_zeros_bwd_f32(const float* zout, long zout_ns, const f
     return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ gaussian log-prob
-#define RFN_HALF_LOG_2PI 0.91893853320467274178f
-
-__device__ __forceinline__ void gauss_params(const float* on, int layout, int c, int Cz, int HW, int p, float& mean,
-                                             float& raw) {
-    if (layout == 0) {
-        mean = on[(long)(2 * c) * HW + p];
-        raw = on[(long)(2 * c + 1) * HW + p];
-    } else {
-        mean = on[(long)c * HW + p];
-        raw = on[(long)(Cz + c) * HW + p];
-    }
-}
-
-__global__ __launch_bounds__(256) void gauss_logp_kernel(const float* __restrict__ z, long z_ns,
-                                                         const float* __restrict__ o, long o_ns,
-                                                         float* __restrict__ logp, int layout, int std_mode, int Cz,
-                                                         int HW) {
-    __shared__ float sm[4];
-    const int n = blockIdx.x;
-    const float* zn = z + n * z_ns;
-    const float* on = o + n * o_ns;
-    float acc = 0.f;
-    for (int e = threadIdx.x; e < Cz * HW; e += 256) {
-        int c = e / HW, p = e - c * HW;
-        float mean, raw;
-        gauss_params(on, layout, c, Cz, HW, p, mean, raw);
-        float logstd, std;
-        if (std_mode == 0) {
-            std = softplusf_(raw) + 1e-8f;
-            logstd = logf(std);
-        } else {
-            std = expf(raw);
-            logstd = raw;
-        }
-        float d = zn[e] - mean;
-        acc += -(d * d) / (2.f * std * std) - logstd - RFN_HALF_LOG_2PI;
-    }
-    float tot = block_sum_256(acc, sm);
-    if (threadIdx.x == 0) logp[n] += tot;
-}
-extern "C" int rfn_gauss_logp_f32(const float* z, long z_ns, const float* o, long o_ns, float* logp, int layout,
-                                  int std_mode, int N, int Cz, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(z && o && logp && N >= 0 && Cz > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    hipLaunchKernelGGL(gauss_logp_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, z, z_ns, o, o_ns, logp, layout,
-                       std_mode, Cz, HW);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ __launch_bounds__(256) void gauss_logp_bwd_kernel(const float* __restrict__ z, long z_ns,
-                                                             const float* __restrict__ o, long o_ns,
-                                                             const float* __restrict__ glogp, float* __restrict__ gz,
-                                                             long gz_ns, float* __restrict__ go, long go_ns, int layout,
-                                                             int std_mode, int Cz, int HW) {
-    const int n = blockIdx.x;
-    const float* zn = z + n * z_ns;
-    const float* on = o + n * o_ns;
-    float* gzn = gz + n * gz_ns;
-    float* gon = go + n * go_ns;
-    const float g = glogp[n];
-    for (int e = threadIdx.x; e < Cz * HW; e += 256) {
-        int c = e / HW, p = e - c * HW;
-        float mean, raw;
-        gauss_params(on, layout, c, Cz, HW, p, mean, raw);
-        float std, dstd_draw;
-        if (std_mode == 0) {
-            std = softplusf_(raw) + 1e-8f;
-            dstd_draw = raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw));
-        } else {
-            std = expf(raw);
-            dstd_draw = std;
-        }
-        float d = zn[e] - mean;
-        float inv = 1.f / (std * std);
-        float gzv = -d * inv * g;                        // d logp / d z
-        float gstd = (d * d * inv / std - 1.f / std) * g;  // d logp / d std
-        gzn[e] = gzv;
-        if (layout == 0) {
-            gon[(long)(2 * c) * HW + p] = -gzv;
-            gon[(long)(2 * c + 1) * HW + p] = gstd * dstd_draw;
-        } else {
-            gon[(long)c * HW + p] = -gzv;
-            gon[(long)(Cz + c) * HW + p] = gstd * dstd_draw;
-        }
-    }
-}
-extern "C" int rfn_gauss_logp_bwd_f32(const float* z, long z_ns, const float* o, long o_ns, const float* glogp,
-                                      float* gz, long gz_ns, float* go, long go_ns, int layout, int std_mode, int N,
-                                      int Cz, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(z && o && glogp && gz && go && N >= 0 && Cz > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    hipLaunchKernelGGL(gauss_logp_bwd_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, z, z_ns, o, o_ns, glogp, gz,
-                       gz_ns, go, go_ns, layout, std_mode, Cz, HW);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// temperature_rows (may be null): one temperature per frame, uniform per block; null: the scalar for every frame.  One
-// kernel for both, so a vector filled with the scalar's value gives the scalar call's bits.
-__global__ __launch_bounds__(256) void gauss_sample_kernel(const float* __restrict__ o, long o_ns,
-                                                           const float* __restrict__ eps, float* __restrict__ z,
-                                                           long z_ns, float temperature,
-                                                           const float* __restrict__ temperature_rows, int layout,
-                                                           int std_mode, int Cz, int HW) {
-    const int n = blockIdx.x;
-    const float* on = o + n * o_ns;
-    const float t = temperature_rows ? temperature_rows[n] : temperature;
-    for (int e = threadIdx.x; e < Cz * HW; e += 256) {
-        int c = e / HW, p = e - c * HW;
-        float mean, raw;
-        gauss_params(on, layout, c, Cz, HW, p, mean, raw);
-        float std = std_mode == 0 ? softplusf_(raw) + 1e-8f : expf(raw);
-        z[n * z_ns + e] = mean + std * t * eps[(long)n * Cz * HW + e];
-    }
-}
-extern "C" int rfn_gauss_sample_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns, float temperature,
-                                    int layout, int std_mode, int N, int Cz, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(o && eps && z && N >= 0 && Cz > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    hipLaunchKernelGGL(gauss_sample_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, o, o_ns, eps, z, z_ns,
-                       temperature, (const float*)nullptr, layout, std_mode, Cz, HW);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int rfn_gauss_sample_rows_f32(const float* o, long o_ns, const float* eps, float* z, long z_ns,
-                                         const float* temperature_rows, int layout, int std_mode, int N, int Cz,
-                                         int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(o && eps && z && temperature_rows && N >= 0 && Cz > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    hipLaunchKernelGGL(gauss_sample_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, o, o_ns, eps, z, z_ns, 0.0f,
-                       temperature_rows, layout, std_mode, Cz, HW);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ conv epilogue bwd
 // grid (C, S): block (c, s) sweeps frames n = s, s+S, ... of channel c.
 __global__ __launch_bounds__(256) void conv_epilogue_bwd_kernel(const float* __restrict__ y, long y_ns,
@@ -1664,1182 +1480,6 @@ extern "C" int rfn_tap_scatter_f32(const float* g, float* Gs, int N, int C, int 
     long tot = (long)N * 9 * C * H * W;
     int grid = (int)((tot + 255) / 256 < 8192 ? (tot + 255) / 256 : 8192);
     hipLaunchKernelGGL(tap_scatter_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, Gs, N, C, H, W);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-
-// ------------------------------------------------------------------------------------------------ per-step BatchNorm
-// The reference runs its VGG extractor / upscaler once per timestep (RFN_new.py:126-128,191-194), so every BatchNorm
-// sees the B samples of ONE step.  Time-batched here: x is [S*B, C, HW] step-major and the statistics are per (step,
-// channel) over (B, HW).  Four kernels replace the permute-copy / batch_norm / permute-copy / activation chain (and its
-// backward): statistics (two-pass, second pass from L2), apply + activation, backward reduction, backward apply.
-// act: 0 none, 1 relu, 2 leaky_relu(slope), 3 tanh.
-__device__ __forceinline__ float stepbn_act(float u, int act, float slope) {
-    if (act == 1) return u > 0.f ? u : 0.f;
-    if (act == 2) return u > 0.f ? u : slope * u;
-    if (act == 3) return tanhf(u);
-    return u;
-}
-__device__ __forceinline__ float stepbn_dact(float u, int act, float slope) {  // from the activation's INPUT u = xhat*g + b
-    if (act == 1) return u > 0.f ? 1.f : 0.f;                                  // (recomputed: saves a pass over y)
-    if (act == 2) return u > 0.f ? 1.f : slope;
-    if (act == 3) {
-        const float t = tanhf(u);
-        return 1.f - t * t;
-    }
-    return 1.f;
-}
-// block (sc, j) = frames j, j+gridDim.y, ... of one (step, channel): shifted sums s1 = sum(x-K), s2 = sum((x-K)^2) with
-// K = the pair's first element (keeps the one-pass variance well conditioned).  Every block stores ITS partial pair at
-// acc[j][sc][2] (no atomics, nothing to zero, deterministic); the consumers add the gridDim.y <= STEPBN_MAX_SPLIT partials.
-constexpr int STEPBN_MAX_SPLIT = 16;
-static int stepbn_split(int S, int B, int C) {  // workgroups per (step, channel): enough blocks for the chip, <= B
-    int ny = 2048 / (S * C);
-    if (ny > STEPBN_MAX_SPLIT) ny = STEPBN_MAX_SPLIT;
-    if (ny > B) ny = B;
-    return ny < 1 ? 1 : ny;
-}
-__global__ __launch_bounds__(256) void stepbn_stats_kernel(const float* __restrict__ x, float* __restrict__ acc, int B,
-                                                           int C, int HW) {
-    __shared__ float sm[4];
-    const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-    const float* base = x + ((long)s * B * C + c) * HW;
-    const long fs = (long)C * HW;
-    const float K = base[0];
-    float a = 0.f, v = 0.f;
-    if ((HW & 3) == 0 && (((uintptr_t)x) & 15) == 0) {  // 16-byte loads (frames and channel planes stay aligned)
-        // (frame, pixel quad) pairs of this block flattened over the threads: small maps keep all 256 lanes busy
-        const int HW4 = HW >> 2, nb = (B - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
-        for (int idx = threadIdx.x; idx < nb * HW4; idx += 256) {
-            const int bi = idx / HW4, p = idx - bi * HW4;
-            const float4 q = reinterpret_cast<const float4*>(base + (blockIdx.y + (long)bi * gridDim.y) * fs)[p];
-            const float d0 = q.x - K, d1 = q.y - K, d2 = q.z - K, d3 = q.w - K;
-            a += (d0 + d1) + (d2 + d3);
-            v = fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, fmaf(d3, d3, v))));
-        }
-    } else {
-        for (int b = blockIdx.y; b < B; b += gridDim.y) {
-            const float* row = base + b * fs;
-            for (int p = threadIdx.x; p < HW; p += 256) {
-                const float d = row[p] - K;
-                a += d;
-                v = fmaf(d, d, v);
-            }
-        }
-    }
-    const float ta = block_sum_256(a, sm);
-    const float tv = block_sum_256(v, sm);
-    if (threadIdx.x == 0) {
-        float* dst = acc + ((long)blockIdx.y * gridDim.x + blockIdx.x) * 2;
-        dst[0] = ta;
-        dst[1] = tv;
-    }
-}
-// elementwise kernels: VEC = 4 consecutive pixels per thread when HW % 4 == 0 (16-byte accesses); 32-bit index math
-// (the host checks total < 2^31).  The statistics come straight from the stats kernel's partial sums (no finalize launch);
-// ONE extra workgroup (the first: dispatched first, so no streaming block is delayed by it) writes mean / var for the
-// backward and applies the S running-statistics updates of the step-wise calls in closed form.
-struct StepBnFused {
-    const float* acc;      // [ny][S*C][2] partial shifted sums of stepbn_stats_kernel
-    float* mean_out;
-    float* var_out;
-    float* run_mean;       // optional [C]: r <- decay r + sum_s coef[s] mean[s]   (and var with coef_u)
-    float* run_var;
-    const float* coef;
-    const float* coef_u;
-    float decay;
-    long long* nbt;        // optional: += S
-    int S, ny;
-};
-__device__ __forceinline__ void stepbn_moments(const float* __restrict__ x, const float* __restrict__ acc, int sc, int s,
-                                               int c, int B, int C, int HW, int ny, int SC, float& m, float& v) {
-    if (!acc) return;   // statistics given by the caller (m, v preloaded): synchronised BatchNorm
-    const float K = x[((long)s * B * C + c) * HW];
-    const float n = (float)B * HW;
-    float s1 = 0.f, s2 = 0.f;
-    for (int y = 0; y < ny; ++y) {
-        s1 += acc[((long)y * SC + sc) * 2];
-        s2 += acc[((long)y * SC + sc) * 2 + 1];
-    }
-    const float m1 = s1 / n;
-    m = K + m1;
-    const float vv = s2 / n - m1 * m1;
-    v = vv > 0.f ? vv : 0.f;
-}
-// the extra first workgroup of a forward apply kernel (pooled or not)
-__device__ __forceinline__ void stepbn_finalise(const float* __restrict__ x, int B, int C, int HW, const StepBnFused& f) {
-    const int SC = f.S * C;
-    if (!f.acc) return;   // given statistics: nothing to finalise
-    for (int sc = threadIdx.x; sc < SC; sc += blockDim.x) {
-        float m, v;
-        stepbn_moments(x, f.acc, sc, sc / C, sc % C, B, C, HW, f.ny, SC, m, v);
-        f.mean_out[sc] = m;
-        f.var_out[sc] = v;
-    }
-    if (f.run_mean) {
-        for (int c = threadIdx.x; c < C; c += blockDim.x) {  // loads only inside the loop: they pipeline
-            float em = 0.f, ev = 0.f;
-#pragma unroll 4
-            for (int s = 0; s < f.S; ++s) {
-                float m, v;
-                stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, v);
-                em = fmaf(f.coef[s], m, em);
-                ev = fmaf(f.coef_u[s], v, ev);
-            }
-            f.run_mean[c] = fmaf(f.decay, f.run_mean[c], em);
-            f.run_var[c] = fmaf(f.decay, f.run_var[c], ev);
-        }
-    }
-    if (f.nbt && threadIdx.x == 0) *f.nbt += f.S;
-}
-template <int VEC>
-__global__ void stepbn_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                    const float* __restrict__ beta, float* __restrict__ y, unsigned total, int B, int C,
-                                    int HW, float eps, int act, float slope, StepBnFused f) {
-    const int SC = f.S * C;
-    const unsigned nblk = gridDim.x - 1, bid = blockIdx.x - 1;
-    if (blockIdx.x == 0) {
-        stepbn_finalise(x, B, C, HW, f);
-        return;
-    }
-    const unsigned nvec = total / VEC;
-    for (unsigned iv = bid * blockDim.x + threadIdx.x; iv < nvec; iv += nblk * blockDim.x) {
-        const unsigned idx = iv * VEC;
-        const unsigned r = idx / (unsigned)HW;  // frame * C + c
-        const int c = (int)(r % (unsigned)C);
-        const int s = (int)(r / (unsigned)C / (unsigned)B);
-        float m = f.acc ? 0.f : f.mean_out[s * C + c], vr = f.acc ? 0.f : f.var_out[s * C + c];
-        stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, vr);
-        const float rstd = rsqrtf(vr + eps);
-        const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-        float v[VEC];
-        if (VEC == 4) {
-            const float4 t = *reinterpret_cast<const float4*>(x + idx);
-            v[0] = t.x; v[1 % VEC] = t.y; v[2 % VEC] = t.z; v[3 % VEC] = t.w;
-        } else {
-            v[0] = x[idx];
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) v[j] = stepbn_act((v[j] - m) * rstd * ga + be, act, slope);
-        if (VEC == 4)
-            *reinterpret_cast<float4*>(y + idx) = float4{v[0], v[1 % VEC], v[2 % VEC], v[3 % VEC]};
-        else
-            y[idx] = v[0];
-    }
-}
-// block (sc, j): partial sums of g' and g' * xhat over frames j, j+gridDim.y, ...  with g' = g * act'(y), stored at
-// sg[j][sc] / sgx[j][sc] (no atomics, nothing to zero)
-__global__ __launch_bounds__(256) void stepbn_bwd_reduce_kernel(const float* __restrict__ x,
-                                                                const float* __restrict__ gamma,
-                                                                const float* __restrict__ beta,
-                                                                const float* __restrict__ g,
-                                                                const float* __restrict__ mean,
-                                                                const float* __restrict__ var, float* __restrict__ sg,
-                                                                float* __restrict__ sgx, int B, int C, int HW, float eps,
-                                                                int act, float slope) {
-    __shared__ float sm[4];
-    const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-    const long off = ((long)s * B * C + c) * HW, fs = (long)C * HW;
-    const float m = mean[blockIdx.x], rstd = rsqrtf(var[blockIdx.x] + eps);
-    const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-    float a = 0.f, ax = 0.f;
-    if ((HW & 3) == 0 && ((((uintptr_t)x) | ((uintptr_t)g)) & 15) == 0) {  // 16-byte loads
-        const int HW4 = HW >> 2, nb = (B - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
-        for (int idx = threadIdx.x; idx < nb * HW4; idx += 256) {
-            const int bi = idx / HW4, p = idx - bi * HW4;
-            const long e0 = off + (blockIdx.y + (long)bi * gridDim.y) * fs;
-            const float4 xq = reinterpret_cast<const float4*>(x + e0)[p], gq = reinterpret_cast<const float4*>(g + e0)[p];
-            const float xv[4] = {xq.x, xq.y, xq.z, xq.w}, gv[4] = {gq.x, gq.y, gq.z, gq.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float xh = (xv[i] - m) * rstd;
-                const float gp = gv[i] * stepbn_dact(xh * ga + be, act, slope);
-                a += gp;
-                ax = fmaf(gp, xh, ax);
-            }
-        }
-    } else {
-        for (int b = blockIdx.y; b < B; b += gridDim.y) {
-            const long e0 = off + b * fs;
-            for (int p = threadIdx.x; p < HW; p += 256) {
-                const float xh = (x[e0 + p] - m) * rstd;
-                const float gp = g[e0 + p] * stepbn_dact(xh * ga + be, act, slope);
-                a += gp;
-                ax = fmaf(gp, xh, ax);
-            }
-        }
-    }
-    const float ta = block_sum_256(a, sm);
-    const float tx = block_sum_256(ax, sm);
-    if (threadIdx.x == 0) {
-        sg[(long)blockIdx.y * gridDim.x + blockIdx.x] = ta;
-        sgx[(long)blockIdx.y * gridDim.x + blockIdx.x] = tx;
-    }
-}
-// the extra first workgroup of a backward apply kernel (pooled or not): the parameter gradients
-__device__ __forceinline__ void stepbn_param_grads(const float* __restrict__ sg, const float* __restrict__ sgx,
-                                                   float* __restrict__ ggamma, float* __restrict__ gbeta, int C, int S,
-                                                   int ny, int world) {
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float a = 0.f, b = 0.f;
-        for (int i = 0; i < ny * S; ++i) {  // [ny][S][C]: all partials of channel c
-            a += sgx[(long)i * C + c];
-            b += sg[(long)i * C + c];
-        }
-        // (world > 1: the partial sums were added over the ranks for gx; a parameter gradient is this rank's
-        // share of a rank average, so the sum over ranks is divided by their number)
-        ggamma[c] = a / (float)world;
-        gbeta[c] = b / (float)world;
-    }
-}
-template <int VEC>
-__global__ void stepbn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ beta,
-                                        const float* __restrict__ g, const float* __restrict__ mean,
-                                        const float* __restrict__ var, const float* __restrict__ gamma,
-                                        const float* __restrict__ sg, const float* __restrict__ sgx,
-                                        float* __restrict__ gx, unsigned total, int B, int C, int HW, float eps, int act,
-                                        float slope, float* __restrict__ ggamma, float* __restrict__ gbeta, int S, int ny,
-                                        int world) {
-    // (one extra workgroup, the first, for the parameter gradients = the per-step sums added over the steps)
-    const int SC = S * C;
-    const unsigned nblk = ggamma ? gridDim.x - 1 : gridDim.x, bid = ggamma ? blockIdx.x - 1 : blockIdx.x;
-    if (ggamma && blockIdx.x == 0) {
-        stepbn_param_grads(sg, sgx, ggamma, gbeta, C, S, ny, world);
-        return;
-    }
-    const float inv_n = 1.f / ((float)(B * HW) * (float)world);
-    const unsigned nvec = total / VEC;
-    for (unsigned iv = bid * blockDim.x + threadIdx.x; iv < nvec; iv += nblk * blockDim.x) {
-        const unsigned idx = iv * VEC;
-        const unsigned r = idx / (unsigned)HW;
-        const int c = (int)(r % (unsigned)C);
-        const int s = (int)(r / (unsigned)C / (unsigned)B);
-        const int sc = s * C + c;
-        const float rstd = rsqrtf(var[sc] + eps), m = mean[sc];
-        const float w = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-        float k1 = 0.f, k2 = 0.f;
-        for (int yy = 0; yy < ny; ++yy) {
-            k1 += sg[(long)yy * SC + sc];
-            k2 += sgx[(long)yy * SC + sc];
-        }
-        k1 *= inv_n;
-        k2 *= inv_n;
-        float xv[VEC], gv[VEC];
-        if (VEC == 4) {
-            const float4 t = *reinterpret_cast<const float4*>(x + idx);
-            const float4 u = *reinterpret_cast<const float4*>(g + idx);
-            xv[0] = t.x; xv[1 % VEC] = t.y; xv[2 % VEC] = t.z; xv[3 % VEC] = t.w;
-            gv[0] = u.x; gv[1 % VEC] = u.y; gv[2 % VEC] = u.z; gv[3 % VEC] = u.w;
-        } else {
-            xv[0] = x[idx];
-            gv[0] = g[idx];
-        }
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            const float xh = (xv[j] - m) * rstd;
-            const float gp = gv[j] * stepbn_dact(xh * w + be, act, slope);
-            xv[j] = w * rstd * (gp - k1 - xh * k2);
-        }
-        if (VEC == 4)
-            *reinterpret_cast<float4*>(gx + idx) = float4{xv[0], xv[1 % VEC], xv[2 % VEC], xv[3 % VEC]};
-        else
-            gx[idx] = xv[0];
-    }
-}
-// The launch decisions of the per-step BatchNorm entry points, made once: the launchers below launch what this says and
-// rfn_stepbn_kernel_label prints it.  `aligned` bit 0: every pointer the stats (x) / reduce (x, g) kernel tests is
-// 16-byte aligned; bit 1: the same for the apply kernel (forward x, y; backward x, g, gx).  The stats / reduce kernels
-// decide their load width on the device, by the test restated in stats_vec.
-struct StepBnRoute {
-    int ny;          // workgroups per (step, channel) of the stats / reduce kernel (stepbn_split)
-    bool stats_vec;  // stats / reduce kernel: 16-byte loads over flattened (frame, pixel quad) pairs; else the scalar loops
-    bool v4;         // apply kernel: stepbn_*apply_kernel<4>; else <1>
-    int grid;        // streaming workgroups of the apply kernel (the launch adds the one that finalises, if any)
-    int sweeps;      // most grid-stride iterations of an apply workgroup
-};
-static StepBnRoute choose_stepbn(int S, int B, int C, int HW, int aligned) {
-    StepBnRoute r;
-    const long total = (long)S * B * C * HW;
-    r.ny = stepbn_split(S, B, C);
-    r.stats_vec = HW % 4 == 0 && (aligned & 1);
-    r.v4 = HW % 4 == 0 && (aligned & 2);
-    const long nthr = r.v4 ? total / 4 : total;
-    r.grid = (int)((nthr + 255) / 256 < 16384 ? (nthr + 255) / 256 : 16384);
-    r.sweeps = (int)((nthr + (long)r.grid * 256 - 1) / ((long)r.grid * 256));
-    return r;
-}
-static int stepbn_aligned(const void* s0, const void* s1, const void* a0, const void* a1, const void* a2) {
-    const uintptr_t st = (uintptr_t)s0 | (uintptr_t)s1, ap = (uintptr_t)a0 | (uintptr_t)a1 | (uintptr_t)a2;
-    return ((st & 15) == 0 ? 1 : 0) | ((ap & 15) == 0 ? 2 : 0);
-}
-// bwd says which pair of kernels `aligned` was derived for (forward: stats + apply, backward: reduce + apply); the
-// route arithmetic is the same either way, so it changes nothing printed
-extern "C" const char* rfn_stepbn_kernel_label(int S, int B, int C, int HW, int aligned, int bwd) {
-    static thread_local char buf[160];
-    if (S <= 0 || B <= 0 || C <= 0 || HW <= 0 || (long)S * B * C * HW >= (1L << 31)) return "unsupported";
-    const StepBnRoute r = choose_stepbn(S, B, C, HW, aligned);
-    (void)bwd;
-    snprintf(buf, sizeof(buf), "stepbn ny=%d stats=%s apply=%s grid=%d sweeps=%d", r.ny, r.stats_vec ? "vec" : "scalar",
-             r.v4 ? "vec4" : "vec1", r.grid, r.sweeps);
-    return buf;
-}
-// floats of scratch rfn_stepbn_fwd_f32 (acc) / rfn_stepbn_bwd_f32 (sums) need for these sizes
-extern "C" long rfn_stepbn_scratch_floats(int S, int B, int C) {
-    if (S <= 0 || B <= 0 || C <= 0) return 0;
-    return 2L * S * C * stepbn_split(S, B, C);
-}
-// stats + normalise + activate + running statistics in TWO launches (partial sums, apply): what per_step_batchnorm_act
-// needs of one BatchNorm layer.  mean / var [S*C] are outputs (kept for the backward); run_mean / run_var [C] (both or
-// neither) receive r <- decay r + sum_s coef[s] stat[s] with coef / coef_u [S] on the device; nbt (optional) += S.
-extern "C" int rfn_stepbn_fwd_f32(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* var,
-                                  float* acc, float* run_mean, float* run_var, const float* coef, const float* coef_u,
-                                  float decay, long long* nbt, int S, int B, int C, int HW, float eps, int act, float slope,
-                                  rfn_stream_t stream) {
-    RFN_CHECK_ARG(x && y && mean && var && acc && S > 0 && B > 0 && C > 0 && HW > 0, -1);
-    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((run_mean && run_var && coef && coef_u) || (!run_mean && !run_var)),
-                  -2);
-    const long total = (long)S * B * C * HW;
-    RFN_CHECK_ARG(total < (1L << 31), -3);
-    hipStream_t st = (hipStream_t)stream;
-    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, nullptr, x, y, nullptr));
-    const int ny = r.ny, grid = r.grid;
-    hipLaunchKernelGGL(stepbn_stats_kernel, dim3(S * C, ny), dim3(256), 0, st, x, acc, B, C, HW);
-    StepBnFused f;
-    f.acc = acc; f.mean_out = mean; f.var_out = var; f.run_mean = run_mean; f.run_var = run_var; f.coef = coef;
-    f.coef_u = coef_u; f.decay = decay; f.nbt = nbt; f.S = S; f.ny = ny;
-    if (r.v4)
-        hipLaunchKernelGGL(stepbn_apply_kernel<4>, dim3(grid + 1), dim3(256), 0, st, x, gamma, beta, y, (unsigned)total, B, C,
-                           HW, eps, act, slope, f);
-    else
-        hipLaunchKernelGGL(stepbn_apply_kernel<1>, dim3(grid + 1), dim3(256), 0, st, x, gamma, beta, y, (unsigned)total, B, C,
-                           HW, eps, act, slope, f);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-/* normalise + activate with GIVEN per-step statistics mean / var [S*C] (synchronised BatchNorm across data-parallel
- * ranks: the caller combined the ranks' moments); one launch */
-extern "C" int rfn_stepbn_apply_f32(const float* x, const float* gamma, const float* beta, float* y, const float* mean,
-                                    const float* var, int S, int B, int C, int HW, float eps, int act, float slope,
-                                    rfn_stream_t stream) {
-    RFN_CHECK_ARG(x && y && mean && var && S > 0 && B > 0 && C > 0 && HW > 0, -1);
-    RFN_CHECK_ARG((gamma && beta) || (!gamma && !beta), -2);
-    const long total = (long)S * B * C * HW;
-    RFN_CHECK_ARG(total < (1L << 31), -3);
-    StepBnFused f;
-    memset(&f, 0, sizeof(f));
-    f.mean_out = const_cast<float*>(mean); f.var_out = const_cast<float*>(var); f.S = S;
-    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, nullptr, x, y, nullptr));
-    const int grid = r.grid;
-    if (r.v4)
-        hipLaunchKernelGGL(stepbn_apply_kernel<4>, dim3(grid + 1), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
-                           (unsigned)total, B, C, HW, eps, act, slope, f);
-    else
-        hipLaunchKernelGGL(stepbn_apply_kernel<1>, dim3(grid + 1), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, y,
-                           (unsigned)total, B, C, HW, eps, act, slope, f);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-// the whole backward of one layer in TWO launches (per-step partial sums, apply): sums = scratch
-// [rfn_stepbn_scratch_floats] (sg | sgx); ggamma / gbeta [C] (both or neither) = the parameter gradients, written by the
-// apply kernel
-extern "C" int rfn_stepbn_bwd_f32(const float* x, const float* gamma, const float* beta, const float* g, const float* mean,
-                                  const float* var, float* sums, float* gx, float* ggamma, float* gbeta, int S, int B,
-                                  int C, int HW, float eps, int act, float slope, int stage, int world,
-                                  rfn_stream_t stream) {
-    // stage 0: both launches; 1: the partial sums only; 2: the apply only (the caller has added `sums` over `world`
-    // data-parallel ranks in between: synchronised BatchNorm; mean / var are the global statistics)
-    RFN_CHECK_ARG(x && g && mean && var && sums && gx && S > 0 && B > 0 && C > 0 && HW > 0, -1);
-    RFN_CHECK_ARG(stage >= 0 && stage <= 2 && world >= 1, -4);
-    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((ggamma && gbeta) || (!ggamma && !gbeta)), -2);
-    const long total = (long)S * B * C * HW;
-    RFN_CHECK_ARG(total < (1L << 31), -3);
-    hipStream_t st = (hipStream_t)stream;
-    const StepBnRoute r = choose_stepbn(S, B, C, HW, stepbn_aligned(x, g, x, g, gx));
-    const int ny = r.ny, grid = r.grid;
-    float* sg = sums;
-    float* sgx = sums + (long)ny * S * C;
-    if (stage != 2)
-        hipLaunchKernelGGL(stepbn_bwd_reduce_kernel, dim3(S * C, ny), dim3(256), 0, st, x, gamma, beta, g, mean, var, sg, sgx,
-                           B, C, HW, eps, act, slope);
-    if (stage == 1) {
-        RFN_LAUNCH_CHECK();
-        return 0;
-    }
-    const int extra = ggamma ? 1 : 0;
-    if (r.v4)
-        hipLaunchKernelGGL(stepbn_bwd_apply_kernel<4>, dim3(grid + extra), dim3(256), 0, st, x, beta, g, mean, var, gamma,
-                           sg, sgx, gx, (unsigned)total, B, C, HW, eps, act, slope, ggamma, gbeta, S, ny, world);
-    else
-        hipLaunchKernelGGL(stepbn_bwd_apply_kernel<1>, dim3(grid + extra), dim3(256), 0, st, x, beta, g, mean, var, gamma,
-                           sg, sgx, gx, (unsigned)total, B, C, HW, eps, act, slope, ggamma, gbeta, S, ny, world);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- per-step BatchNorm + 2x2 max-pool
-// conv -> BatchNorm -> activation -> MaxPool2d(2, 2) of the extractor: the apply kernel writes only the pooled map
-// p [S*B, C, H/2, W/2], and the backward recomputes each window's winner from x, so neither the full-resolution
-// activation, nor an index map, nor a full-resolution gradient exists.  The statistics kernel, the moments, the finalising
-// workgroup and the parameter-gradient workgroup are those of the unpooled kernels above.
-// A window's winner by max_pool2d's rule: the ACTIVATED values in the order (0,0), (0,1), (1,0), (1,1); a candidate
-// replaces the best when it is larger or NaN.  xv = the four inputs in that order -> the winner's position (0..3), its
-// activated value, its xhat and its activation input u.
-__device__ __forceinline__ int stepbn_pool_winner(const float xv[4], float m, float rstd, float ga, float be, int act,
-                                                  float slope, float& best, float& xh_w, float& u_w) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float xh = (xv[j] - m) * rstd;
-        const float u = xh * ga + be;
-        const float a = stepbn_act(u, act, slope);
-        if (j == 0 || a > best || isnan(a)) {
-            best = a;
-            xh_w = xh;
-            u_w = u;
-            k = j;
-        }
-    }
-    return k;
-}
-// A thread's unit: VEC == 4: rows 2i, 2i+1 x columns 4j..4j+3 of one plane (two 16-byte loads) = two windows; VEC == 1:
-// one window, scalar accesses.  Unit u of either kind: q = u / (units per pooled row) = plane * H/2 + i, its first input
-// element is q * 2W + (VEC == 4 ? 4 : 2) * (u - q * units per row) and its first pooled element is u * (VEC == 4 ? 2 : 1).
-template <int VEC>
-__device__ __forceinline__ void stepbn_pool_load(const float* __restrict__ x, unsigned in0, int W, float xv[2][4]) {
-    if (VEC == 4) {
-        const float4 r0 = *reinterpret_cast<const float4*>(x + in0);
-        const float4 r1 = *reinterpret_cast<const float4*>(x + in0 + W);
-        xv[0][0] = r0.x; xv[0][1] = r0.y; xv[0][2] = r1.x; xv[0][3] = r1.y;
-        xv[1][0] = r0.z; xv[1][1] = r0.w; xv[1][2] = r1.z; xv[1][3] = r1.w;
-    } else {
-        xv[0][0] = x[in0]; xv[0][1] = x[in0 + 1]; xv[0][2] = x[in0 + W]; xv[0][3] = x[in0 + W + 1];
-    }
-}
-template <int VEC>
-__global__ void stepbn_pool_apply_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
-                                         const float* __restrict__ beta, float* __restrict__ p, unsigned nunits, int B,
-                                         int C, int H, int W, float eps, int act, float slope, StepBnFused f) {
-    constexpr int NW = VEC == 4 ? 2 : 1;  // windows per unit
-    const int SC = f.S * C, HW = H * W;
-    const unsigned nblk = gridDim.x - 1, bid = blockIdx.x - 1;
-    if (blockIdx.x == 0) {
-        stepbn_finalise(x, B, C, HW, f);
-        return;
-    }
-    const unsigned upr = (unsigned)W / (2 * NW), Ho = (unsigned)H / 2;
-    for (unsigned u = bid * blockDim.x + threadIdx.x; u < nunits; u += nblk * blockDim.x) {
-        const unsigned q = u / upr;
-        const unsigned r = q / Ho;  // frame * C + c
-        const int c = (int)(r % (unsigned)C);
-        const int s = (int)(r / (unsigned)C / (unsigned)B);
-        float m = f.acc ? 0.f : f.mean_out[s * C + c], vr = f.acc ? 0.f : f.var_out[s * C + c];
-        stepbn_moments(x, f.acc, s * C + c, s, c, B, C, HW, f.ny, SC, m, vr);
-        const float rstd = rsqrtf(vr + eps);
-        const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-        float xv[2][4], o[NW];
-        stepbn_pool_load<VEC>(x, q * 2u * (unsigned)W + 2u * NW * (u - q * upr), W, xv);
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            float xh, uu;
-            stepbn_pool_winner(xv[w], m, rstd, ga, be, act, slope, o[w], xh, uu);
-        }
-        if (VEC == 4)
-            *reinterpret_cast<float2*>(p + 2u * u) = float2{o[0], o[NW - 1]};
-        else
-            p[u] = o[0];
-    }
-}
-// block (sc, j): partial sums of g' and g' * xhat_winner over the windows of frames j, j+gridDim.y, ... with
-// g' = gp * act'(u_winner), stored like stepbn_bwd_reduce_kernel's (the same terms: a lost position's gradient is zero).
-// A block adds its terms in fp64 and rounds its pair once (a quarter of the unpooled kernel's loads feed the sums, so the
-// adds are hidden behind them): the fp32 partial rows and their consumers are unchanged.
-__device__ __forceinline__ double block_sum_256_f64(double v, double* sm /* >= 4 doubles */) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) sm[wave] = v;
-    __syncthreads();
-    return (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
-template <int VEC>
-__global__ __launch_bounds__(256) void stepbn_pool_bwd_reduce_kernel(
-    const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ gp, const float* __restrict__ mean, const float* __restrict__ var, float* __restrict__ sg,
-    float* __restrict__ sgx, int B, int C, int H, int W, float eps, int act, float slope) {
-    constexpr int NW = VEC == 4 ? 2 : 1;
-    __shared__ double sm[4];
-    const int s = blockIdx.x / C, c = blockIdx.x - s * C;
-    const int HW = H * W, upr = W / (2 * NW), upf = (H / 2) * upr;  // units per pooled row / per plane
-    const unsigned pl0 = (unsigned)(s * B) * C + c;                 // plane of frame 0 of this step
-    const float m = mean[blockIdx.x], rstd = rsqrtf(var[blockIdx.x] + eps);
-    const float ga = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-    double a = 0., ax = 0.;
-    const int nb = (B - (int)blockIdx.y + (int)gridDim.y - 1) / (int)gridDim.y;
-    for (int idx = threadIdx.x; idx < nb * upf; idx += 256) {
-        const int bi = idx / upf, t = idx - bi * upf;
-        const unsigned pl = pl0 + (blockIdx.y + (unsigned)bi * gridDim.y) * (unsigned)C;
-        const int i = t / upr, j = t - i * upr;
-        float xv[2][4], gv[NW];
-        stepbn_pool_load<VEC>(x, pl * (unsigned)HW + 2u * i * W + 2u * NW * j, W, xv);
-        const unsigned o0 = pl * (unsigned)(HW / 4) + (unsigned)t * NW;
-        if (VEC == 4) {
-            const float2 g2 = *reinterpret_cast<const float2*>(gp + o0);
-            gv[0] = g2.x; gv[NW - 1] = g2.y;
-        } else {
-            gv[0] = gp[o0];
-        }
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            float best, xh, u;
-            stepbn_pool_winner(xv[w], m, rstd, ga, be, act, slope, best, xh, u);
-            const float g1 = gv[w] * stepbn_dact(u, act, slope);
-            a += (double)g1;
-            ax = fma((double)g1, (double)xh, ax);
-        }
-    }
-    const float ta = (float)block_sum_256_f64(a, sm);
-    const float tx = (float)block_sum_256_f64(ax, sm);
-    if (threadIdx.x == 0) {
-        sg[(long)blockIdx.y * gridDim.x + blockIdx.x] = ta;
-        sgx[(long)blockIdx.y * gridDim.x + blockIdx.x] = tx;
-    }
-}
-// gx = gamma rstd (g' [winner] - k1 - xhat k2) at the four positions of every window
-template <int VEC>
-__global__ void stepbn_pool_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ beta,
-                                             const float* __restrict__ gp, const float* __restrict__ mean,
-                                             const float* __restrict__ var, const float* __restrict__ gamma,
-                                             const float* __restrict__ sg, const float* __restrict__ sgx,
-                                             float* __restrict__ gx, unsigned nunits, int B, int C, int H, int W,
-                                             float eps, int act, float slope, float* __restrict__ ggamma,
-                                             float* __restrict__ gbeta, int S, int ny, int world) {
-    constexpr int NW = VEC == 4 ? 2 : 1;
-    const int SC = S * C, HW = H * W;
-    const unsigned nblk = ggamma ? gridDim.x - 1 : gridDim.x, bid = ggamma ? blockIdx.x - 1 : blockIdx.x;
-    if (ggamma && blockIdx.x == 0) {
-        stepbn_param_grads(sg, sgx, ggamma, gbeta, C, S, ny, world);
-        return;
-    }
-    const float inv_n = 1.f / ((float)(B * HW) * (float)world);
-    const unsigned upr = (unsigned)W / (2 * NW), Ho = (unsigned)H / 2;
-    for (unsigned u = bid * blockDim.x + threadIdx.x; u < nunits; u += nblk * blockDim.x) {
-        const unsigned q = u / upr;
-        const unsigned r = q / Ho;
-        const int c = (int)(r % (unsigned)C);
-        const int s = (int)(r / (unsigned)C / (unsigned)B);
-        const int sc = s * C + c;
-        const float rstd = rsqrtf(var[sc] + eps), m = mean[sc];
-        const float w = gamma ? gamma[c] : 1.f, be = gamma ? beta[c] : 0.f;
-        float k1 = 0.f, k2 = 0.f;
-        for (int yy = 0; yy < ny; ++yy) {
-            k1 += sg[(long)yy * SC + sc];
-            k2 += sgx[(long)yy * SC + sc];
-        }
-        k1 *= inv_n;
-        k2 *= inv_n;
-        const unsigned in0 = q * 2u * (unsigned)W + 2u * NW * (u - q * upr);
-        float xv[2][4], gv[NW];
-        stepbn_pool_load<VEC>(x, in0, W, xv);
-        if (VEC == 4) {
-            const float2 g2 = *reinterpret_cast<const float2*>(gp + 2u * u);
-            gv[0] = g2.x; gv[NW - 1] = g2.y;
-        } else {
-            gv[0] = gp[u];
-        }
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) {
-            float best, xhw, uw;
-            const int k = stepbn_pool_winner(xv[ww], m, rstd, w, be, act, slope, best, xhw, uw);
-            const float g1 = gv[ww] * stepbn_dact(uw, act, slope);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float xh = (xv[ww][j] - m) * rstd;
-                const float gpos = j == k ? g1 : 0.f;
-                xv[ww][j] = w * rstd * (gpos - k1 - xh * k2);
-            }
-        }
-        if (VEC == 4) {
-            *reinterpret_cast<float4*>(gx + in0) = float4{xv[0][0], xv[0][1], xv[NW - 1][0], xv[NW - 1][1]};
-            *reinterpret_cast<float4*>(gx + in0 + W) = float4{xv[0][2], xv[0][3], xv[NW - 1][2], xv[NW - 1][3]};
-        } else {
-            gx[in0] = xv[0][0]; gx[in0 + 1] = xv[0][1]; gx[in0 + W] = xv[0][2]; gx[in0 + W + 1] = xv[0][3];
-        }
-    }
-}
-// The launch decisions of the pooled entry points, made once (rfn_stepbn_pool_kernel_label prints them).  `aligned` as for
-// choose_stepbn: bit 0 = the pointers of the statistics kernel (x) or, with bwd, of the reduce kernel (x, gp); bit 1 =
-// those of the apply kernel (x, p; with bwd x, gp, gx).  The statistics kernel is the unpooled one and tests H*W % 4
-// (always 0 here); the pooled kernels read two 16-byte row pieces per unit and need W % 4 == 0.
-constexpr int STEPBN_POOL_GRID_CAP = 8192;
-struct StepBnPoolRoute {
-    int ny;          // workgroups per (step, channel) of the stats / reduce kernel (stepbn_split)
-    bool stats_vec;  // stats kernel (bwd: reduce kernel) on 16-byte loads
-    bool v4;         // apply kernel: stepbn_pool_*apply_kernel<4> (units of two windows); else <1> (one window)
-    long nunits;     // units of the apply kernel
-    int grid;        // its streaming workgroups
-    int sweeps;      // most grid-stride iterations of one
-};
-static StepBnPoolRoute choose_stepbn_pool(int S, int B, int C, int H, int W, int aligned, int bwd) {
-    StepBnPoolRoute r;
-    const long total = (long)S * B * C * H * W;
-    r.ny = stepbn_split(S, B, C);
-    r.stats_vec = (aligned & 1) && (bwd ? W % 4 == 0 : true);
-    r.v4 = W % 4 == 0 && (aligned & 2);
-    r.nunits = r.v4 ? total / 8 : total / 4;
-    const long nb = (r.nunits + 255) / 256;
-    r.grid = (int)(nb < STEPBN_POOL_GRID_CAP ? nb : STEPBN_POOL_GRID_CAP);
-    r.sweeps = (int)((nb + r.grid - 1) / r.grid);
-    return r;
-}
-static bool stepbn_pool_sizes_ok(int S, int B, int C, int H, int W) {
-    return S > 0 && B > 0 && C > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0;
-}
-extern "C" const char* rfn_stepbn_pool_kernel_label(int S, int B, int C, int H, int W, int aligned, int bwd) {
-    static thread_local char buf[160];
-    if (!stepbn_pool_sizes_ok(S, B, C, H, W) || (long)S * B * C * H * W >= (1L << 31)) return "unsupported";
-    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, aligned, bwd);
-    snprintf(buf, sizeof(buf), "stepbn_pool ny=%d stats=%s apply=%s grid=%d sweeps=%d", r.ny,
-             r.stats_vec ? "vec" : "scalar", r.v4 ? "vec4" : "vec1", r.grid, r.sweeps);
-    return buf;
-}
-// rfn_stepbn_fwd_f32 with the 2x2 max-pool folded into the apply launch: p [S*B, C, H/2, W/2] is the only map written
-extern "C" int rfn_stepbn_pool_fwd_f32(const float* x, const float* gamma, const float* beta, float* p, float* mean,
-                                       float* var, float* acc, float* run_mean, float* run_var, const float* coef,
-                                       const float* coef_u, float decay, long long* nbt, int S, int B, int C, int H, int W,
-                                       float eps, int act, float slope, rfn_stream_t stream) {
-    RFN_CHECK_ARG(x && p && mean && var && acc && S > 0 && B > 0 && C > 0 && H > 0 && W > 0, -1);
-    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((run_mean && run_var && coef && coef_u) || (!run_mean && !run_var)),
-                  -2);
-    RFN_CHECK_ARG(H % 2 == 0 && W % 2 == 0, -5);
-    const long total = (long)S * B * C * H * W;
-    RFN_CHECK_ARG(total < (1L << 31), -3);
-    hipStream_t st = (hipStream_t)stream;
-    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, stepbn_aligned(x, nullptr, x, p, nullptr), 0);
-    hipLaunchKernelGGL(stepbn_stats_kernel, dim3(S * C, r.ny), dim3(256), 0, st, x, acc, B, C, H * W);
-    StepBnFused f;
-    f.acc = acc; f.mean_out = mean; f.var_out = var; f.run_mean = run_mean; f.run_var = run_var; f.coef = coef;
-    f.coef_u = coef_u; f.decay = decay; f.nbt = nbt; f.S = S; f.ny = r.ny;
-    if (r.v4)
-        hipLaunchKernelGGL(stepbn_pool_apply_kernel<4>, dim3(r.grid + 1), dim3(256), 0, st, x, gamma, beta, p,
-                           (unsigned)r.nunits, B, C, H, W, eps, act, slope, f);
-    else
-        hipLaunchKernelGGL(stepbn_pool_apply_kernel<1>, dim3(r.grid + 1), dim3(256), 0, st, x, gamma, beta, p,
-                           (unsigned)r.nunits, B, C, H, W, eps, act, slope, f);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-// the backward of that layer from the POOLED gradient gp [S*B, C, H/2, W/2]: stage / world as rfn_stepbn_bwd_f32
-extern "C" int rfn_stepbn_pool_bwd_f32(const float* x, const float* gamma, const float* beta, const float* gp,
-                                       const float* mean, const float* var, float* sums, float* gx, float* ggamma,
-                                       float* gbeta, int S, int B, int C, int H, int W, float eps, int act, float slope,
-                                       int stage, int world, rfn_stream_t stream) {
-    RFN_CHECK_ARG(x && gp && mean && var && sums && gx && S > 0 && B > 0 && C > 0 && H > 0 && W > 0, -1);
-    RFN_CHECK_ARG(stage >= 0 && stage <= 2 && world >= 1, -4);
-    RFN_CHECK_ARG(((gamma && beta) || (!gamma && !beta)) && ((ggamma && gbeta) || (!ggamma && !gbeta)), -2);
-    RFN_CHECK_ARG(H % 2 == 0 && W % 2 == 0, -5);
-    const long total = (long)S * B * C * H * W;
-    RFN_CHECK_ARG(total < (1L << 31), -3);
-    hipStream_t st = (hipStream_t)stream;
-    const StepBnPoolRoute r = choose_stepbn_pool(S, B, C, H, W, stepbn_aligned(x, gp, x, gp, gx), 1);
-    const int ny = r.ny;
-    float* sg = sums;
-    float* sgx = sums + (long)ny * S * C;
-    if (stage != 2) {
-        if (r.stats_vec)
-            hipLaunchKernelGGL(stepbn_pool_bwd_reduce_kernel<4>, dim3(S * C, ny), dim3(256), 0, st, x, gamma, beta, gp, mean,
-                               var, sg, sgx, B, C, H, W, eps, act, slope);
-        else
-            hipLaunchKernelGGL(stepbn_pool_bwd_reduce_kernel<1>, dim3(S * C, ny), dim3(256), 0, st, x, gamma, beta, gp, mean,
-                               var, sg, sgx, B, C, H, W, eps, act, slope);
-    }
-    if (stage == 1) {
-        RFN_LAUNCH_CHECK();
-        return 0;
-    }
-    const int extra = ggamma ? 1 : 0;
-    if (r.v4)
-        hipLaunchKernelGGL(stepbn_pool_bwd_apply_kernel<4>, dim3(r.grid + extra), dim3(256), 0, st, x, beta, gp, mean, var,
-                           gamma, sg, sgx, gx, (unsigned)r.nunits, B, C, H, W, eps, act, slope, ggamma, gbeta, S, ny, world);
-    else
-        hipLaunchKernelGGL(stepbn_pool_bwd_apply_kernel<1>, dim3(r.grid + extra), dim3(256), 0, st, x, beta, gp, mean, var,
-                           gamma, sg, sgx, gx, (unsigned)r.nunits, B, C, H, W, eps, act, slope, ggamma, gbeta, S, ny, world);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---------------------------------------------------------------------------- nearest 2x up-sampling + channel cat
-// The upscaler's NearestUp2x -> torch.cat((x, skip), 1) in one launch: out[n, c] = up2x(x[n, c]) for c < Cx, else
-// skip[n, c - Cx].  Backward: gx = the 2x2 block sums of g[:, :Cx], read in place through g's frame stride (each sum is
-// formed in fp64 and rounded once); the skip's gradient is the view g[:, Cx:].  VEC == 4: 16-byte pieces of the 2w-wide
-// rows (w even, aligned pointers and frame strides); VEC == 1: one element per thread.
-constexpr int UP2X_GRID_CAP = 8192;
-template <int VEC>
-__global__ void up2x_cat_kernel(const float* __restrict__ x, long x_ns, const float* __restrict__ skip, long s_ns,
-                                float* __restrict__ out, unsigned nunits, int Cx, int Cs, int h, int w) {
-    const unsigned upr = VEC == 4 ? (unsigned)w / 2 : 2u * w, H2 = 2u * h, Ct = (unsigned)(Cx + Cs);
-    for (unsigned u = blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += gridDim.x * blockDim.x) {
-        const unsigned row = u / upr, k = u - row * upr;  // row = (n * Ct + c) * 2h + Y
-        const unsigned rc = row / H2, Y = row - rc * H2;
-        const unsigned n = rc / Ct, c = rc - n * Ct;
-        if (VEC == 4) {
-            float4 v;
-            if (c < (unsigned)Cx) {
-                const float2 t = *reinterpret_cast<const float2*>(x + n * x_ns + ((long)c * h + Y / 2) * w + 2 * k);
-                v = float4{t.x, t.x, t.y, t.y};
-            } else {
-                v = *reinterpret_cast<const float4*>(skip + n * s_ns + ((long)(c - Cx) * H2 + Y) * (2 * w) + 4 * k);
-            }
-            *reinterpret_cast<float4*>(out + 4ul * u) = v;
-        } else {
-            out[u] = c < (unsigned)Cx ? x[n * x_ns + ((long)c * h + Y / 2) * w + k / 2]
-                                      : skip[n * s_ns + ((long)(c - Cx) * H2 + Y) * (2 * w) + k];
-        }
-    }
-}
-template <int VEC>
-__global__ void up2x_cat_bwd_kernel(const float* __restrict__ g, long g_ns, float* __restrict__ gx, unsigned nunits,
-                                    int Cx, int h, int w) {
-    const unsigned upr = VEC == 4 ? (unsigned)w / 2 : (unsigned)w;
-    for (unsigned u = blockIdx.x * blockDim.x + threadIdx.x; u < nunits; u += gridDim.x * blockDim.x) {
-        const unsigned row = u / upr, k = u - row * upr;  // row = (n * Cx + c) * h + i
-        const unsigned rc = row / (unsigned)h, i = row - rc * (unsigned)h;
-        const unsigned n = rc / (unsigned)Cx, c = rc - n * (unsigned)Cx;
-        const float* r0 = g + n * g_ns + ((long)c * 2 * h + 2 * i) * (2 * w) + (VEC == 4 ? 4 : 2) * k;
-        const float* r1 = r0 + 2 * w;
-        if (VEC == 4) {
-            const float4 a = *reinterpret_cast<const float4*>(r0), b = *reinterpret_cast<const float4*>(r1);
-            *reinterpret_cast<float2*>(gx + 2ul * u) = float2{(float)(((double)a.x + a.y) + ((double)b.x + b.y)),
-                                                              (float)(((double)a.z + a.w) + ((double)b.z + b.w))};
-        } else {
-            gx[u] = (float)(((double)r0[0] + r0[1]) + ((double)r1[0] + r1[1]));
-        }
-    }
-}
-struct Up2xRoute {
-    bool v4;
-    long nunits;
-    int grid, sweeps;
-};
-// `aligned`: every pointer is 16-byte aligned and every frame stride a multiple of 4 floats; out_elems = the elements of
-// out (forward) or of gx (backward)
-static Up2xRoute choose_up2x(long out_elems, int w, int aligned, int bwd) {
-    Up2xRoute r;
-    r.v4 = w % 2 == 0 && aligned;
-    r.nunits = r.v4 ? out_elems / (bwd ? 2 : 4) : out_elems;
-    const long nb = (r.nunits + 255) / 256;
-    r.grid = (int)(nb < UP2X_GRID_CAP ? nb : UP2X_GRID_CAP);
-    r.sweeps = (int)((nb + r.grid - 1) / r.grid);
-    return r;
-}
-static bool up2x_sizes_ok(int N, int Cx, int Cs, int h, int w, int bwd) {
-    return N > 0 && Cx > 0 && Cs >= 0 && h > 0 && w > 0 && 4L * N * (bwd ? Cx : Cx + Cs) * h * w < (1L << 31);
-}
-extern "C" const char* rfn_up2x_cat_kernel_label(int N, int Cx, int Cs, int h, int w, int aligned, int bwd) {
-    static thread_local char buf[128];
-    if (!up2x_sizes_ok(N, Cx, Cs, h, w, bwd)) return "unsupported";
-    const Up2xRoute r = choose_up2x(bwd ? (long)N * Cx * h * w : 4L * N * (Cx + Cs) * h * w, w, aligned, bwd);
-    snprintf(buf, sizeof(buf), "up2x_cat%s access=%s grid=%d sweeps=%d", bwd ? "_bwd" : "", r.v4 ? "vec4" : "vec1", r.grid,
-             r.sweeps);
-    return buf;
-}
-extern "C" int rfn_up2x_cat_f32(const float* x, long x_ns, const float* skip, long skip_ns, float* out, int N, int Cx,
-                                int Cs, int h, int w, rfn_stream_t stream) {
-    RFN_CHECK_ARG(x && skip && out && Cs > 0 && up2x_sizes_ok(N, Cx, Cs, h, w, 0), -1);
-    RFN_CHECK_ARG(x_ns >= (long)Cx * h * w && skip_ns >= 4L * Cs * h * w, -2);
-    const int aligned = ((((uintptr_t)x | (uintptr_t)skip | (uintptr_t)out) & 15) == 0 && x_ns % 4 == 0 && skip_ns % 4 == 0);
-    const Up2xRoute r = choose_up2x(4L * N * (Cx + Cs) * h * w, w, aligned, 0);
-    if (r.v4)
-        hipLaunchKernelGGL(up2x_cat_kernel<4>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, x, x_ns, skip, skip_ns, out,
-                           (unsigned)r.nunits, Cx, Cs, h, w);
-    else
-        hipLaunchKernelGGL(up2x_cat_kernel<1>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, x, x_ns, skip, skip_ns, out,
-                           (unsigned)r.nunits, Cx, Cs, h, w);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int rfn_up2x_cat_bwd_f32(const float* g, long g_ns, float* gx, int N, int Cx, int h, int w,
-                                    rfn_stream_t stream) {
-    RFN_CHECK_ARG(g && gx && up2x_sizes_ok(N, Cx, 0, h, w, 1), -1);
-    RFN_CHECK_ARG(g_ns >= 4L * Cx * h * w, -2);
-    const int aligned = ((((uintptr_t)g | (uintptr_t)gx) & 15) == 0 && g_ns % 4 == 0);
-    const Up2xRoute r = choose_up2x((long)N * Cx * h * w, w, aligned, 1);
-    if (r.v4)
-        hipLaunchKernelGGL(up2x_cat_bwd_kernel<4>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, g, g_ns, gx,
-                           (unsigned)r.nunits, Cx, h, w);
-    else
-        hipLaunchKernelGGL(up2x_cat_bwd_kernel<1>, dim3(r.grid), dim3(256), 0, (hipStream_t)stream, g, g_ns, gx,
-                           (unsigned)r.nunits, Cx, h, w);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ InvConv.get_weight
-// Flow/glow_modules.py:178-207 for the K steps of a flow level in one launch each way (the reference -- and a torch
-// restatement -- spends ~17 launches per level forward and ~20 backward on this C x C algebra):
-//   Lm = lower o tril(-1) + I,   Um = upper o triu(+1) + diag(sign_s * exp(log_s)),   W = P Lm Um,
-//   dlogdet = HW * sum(log_s)  (summed over the K steps, in step order, into ONE scalar that is WRITTEN: no atomics).
-// Backward, given gW and the gradient gc of the scalar:  gT = P^T gW;  g_lower = (gT Um^T) o tril(-1);
-//   g_upper = (Lm^T gT) o triu(+1);  g_log_s = diag(Lm^T gT) * sign_s * exp(log_s) + gc * HW.
-// One workgroup per step, the three matrices in LDS (C <= RFN_INVCONV_MAX_CHANNELS).  Parameters arrive as pointer arrays in the kernel
-// arguments (no stacking copies): K <= RFN_INVCONV_MAX_STEPS.
-struct InvConvWeightsParams {
-    const float* p[RFN_INVCONV_MAX_STEPS];
-    const float* lower[RFN_INVCONV_MAX_STEPS];
-    const float* upper[RFN_INVCONV_MAX_STEPS];
-    const float* log_s[RFN_INVCONV_MAX_STEPS];
-    const float* sign_s[RFN_INVCONV_MAX_STEPS];
-    float* W;            // [K][C][C]
-    float* logdet;       // scalar, written
-    const float* gW;     // backward: [K][C][C]
-    const float* gc;     // backward: gradient of the scalar (may be null)
-    float* g_lower;      // [K][C][C]
-    float* g_upper;      // [K][C][C]
-    float* g_log_s;      // [K][C]
-    int C;
-    float hw;
-};
-// LDS matrices have row stride C + 1: column walks (transposed operands) are bank-conflict free
-__device__ __forceinline__ void invconv_load_LU(const InvConvWeightsParams& q, int k, float* Lm, float* Um) {
-    const int C = q.C, CP = C + 1;
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
-        const int r = i / C, c = i - r * C;
-        Lm[r * CP + c] = r > c ? q.lower[k][i] : (r == c ? 1.f : 0.f);
-        Um[r * CP + c] = r < c ? q.upper[k][i] : (r == c ? q.sign_s[k][r] * expf(q.log_s[k][r]) : 0.f);
-    }
-}
-__device__ __forceinline__ void invconv_load(const float* __restrict__ src, float* dst, int C) {
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) dst[(i / C) * (C + 1) + i % C] = src[i];
-}
-// out(r, c) = sum_j A(r, j) * B(j, c) for the C x C matrices in LDS (row stride C + 1), each thread a 4 x 4 block of the
-// result (8 LDS reads per 16 multiply-adds); TA / TB: the operand is read transposed.  C % 4 == 0 or the scalar tail runs.
-template <bool TA, bool TB, typename Store>
-__device__ __forceinline__ void invconv_mm(const float* __restrict__ A, const float* __restrict__ B, int C, Store store) {
-    const int CP = C + 1, nb = C >> 2;
-    for (int blk = threadIdx.x; blk < nb * nb; blk += blockDim.x) {
-        const int r0 = (blk / nb) * 4, c0 = (blk % nb) * 4;
-        float acc[4][4] = {};
-        for (int j = 0; j < C; ++j) {
-            float av[4], bv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                av[i] = TA ? A[j * CP + r0 + i] : A[(r0 + i) * CP + j];
-                bv[i] = TB ? B[(c0 + i) * CP + j] : B[j * CP + c0 + i];
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[i][k] = fmaf(av[i], bv[k], acc[i][k]);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) store(r0 + i, c0 + k, acc[i][k]);
-    }
-    const int Cm = nb * 4;  // ragged edge (C % 4 != 0): the last rows and columns one element at a time
-    for (int i = threadIdx.x; i < C * C; i += blockDim.x) {
-        const int r = i / C, c = i - r * C;
-        if (r < Cm && c < Cm) continue;
-        float a = 0.f;
-        for (int j = 0; j < C; ++j)
-            a = fmaf(TA ? A[j * CP + r] : A[r * CP + j], TB ? B[c * CP + j] : B[j * CP + c], a);
-        store(r, c, a);
-    }
-}
-__global__ __launch_bounds__(256) void invconv_weights_fwd_kernel(const InvConvWeightsParams q) {
-    extern __shared__ float sm_iw[];
-    const int C = q.C, CP = C + 1, k = blockIdx.x;
-    float* B0 = sm_iw;            // Lm, then P
-    float* B1 = B0 + C * CP;      // Um
-    float* B2 = B1 + C * CP;      // T = Lm Um
-    invconv_load_LU(q, k, B0, B1);
-    __syncthreads();
-    invconv_mm<false, false>(B0, B1, C, [&](int r, int c, float v) { B2[r * CP + c] = v; });
-    __syncthreads();
-    invconv_load(q.p[k], B0, C);
-    __syncthreads();
-    float* W = q.W + (long)k * C * C;
-    invconv_mm<false, false>(B0, B2, C, [&](int r, int c, float v) { W[r * C + c] = v; });  // W = P T
-    if (k == 0 && threadIdx.x < 64) {  // one wave of ONE block: HW * sum over the steps (in order) of sum(log_s): no atomics
-        float tot = 0.f;
-        for (int kk = 0; kk < (int)gridDim.x; ++kk) {
-            float v = 0.f;
-            for (int c = threadIdx.x; c < C; c += 64) v += q.log_s[kk][c];
-            tot += wave_sum(v) * q.hw;
-        }
-        if (threadIdx.x == 0) *q.logdet = tot;
-    }
-}
-__global__ __launch_bounds__(256) void invconv_weights_bwd_kernel(const InvConvWeightsParams q) {
-    extern __shared__ float sm_iw[];
-    const int C = q.C, CP = C + 1, k = blockIdx.x;
-    float* B0 = sm_iw;            // P, then Lm
-    float* B1 = B0 + C * CP;      // gW, then Um
-    float* B2 = B1 + C * CP;      // gT = P^T gW
-    invconv_load(q.p[k], B0, C);
-    invconv_load(q.gW + (long)k * C * C, B1, C);
-    __syncthreads();
-    invconv_mm<true, false>(B0, B1, C, [&](int r, int c, float v) { B2[r * CP + c] = v; });
-    __syncthreads();
-    invconv_load_LU(q, k, B0, B1);
-    __syncthreads();
-    const float* Um = B1;
-    const float gc = q.gc ? q.gc[0] * q.hw : 0.f;
-    float* gl = q.g_lower + (long)k * C * C;
-    float* gu = q.g_upper + (long)k * C * C;
-    float* gs = q.g_log_s + (long)k * C;
-    // g_lower = (gT Um^T) o tril(-1);  g_upper = (Lm^T gT) o triu(+1);  g_log_s from the diagonal of Lm^T gT
-    invconv_mm<false, true>(B2, B1, C, [&](int r, int c, float v) { gl[r * C + c] = r > c ? v : 0.f; });
-    invconv_mm<true, false>(B0, B2, C, [&](int r, int c, float v) {
-        gu[r * C + c] = r < c ? v : 0.f;
-        if (r == c) gs[r] = v * Um[r * CP + r] + gc;
-    });
-}
-static int invconv_weights_fill(InvConvWeightsParams& q, const float* const* p, const float* const* lower,
-                                const float* const* upper, const float* const* log_s, const float* const* sign_s, int K,
-                                int C, int HW) {
-    if (!(p && lower && upper && log_s && sign_s && K >= 1 && K <= RFN_INVCONV_MAX_STEPS && C >= 1 &&
-          C <= RFN_INVCONV_MAX_CHANNELS && HW > 0))
-        return -1;
-    memset(&q, 0, sizeof(q));
-    for (int k = 0; k < K; ++k) {
-        if (!(p[k] && lower[k] && upper[k] && log_s[k] && sign_s[k])) return -2;
-        q.p[k] = p[k]; q.lower[k] = lower[k]; q.upper[k] = upper[k]; q.log_s[k] = log_s[k]; q.sign_s[k] = sign_s[k];
-    }
-    q.C = C;
-    q.hw = (float)HW;
-    return 0;
-}
-extern "C" int rfn_invconv_weights_fwd_f32(const float* const* p, const float* const* lower, const float* const* upper,
-                                           const float* const* log_s, const float* const* sign_s, float* W, float* logdet,
-                                           int K, int C, int HW, rfn_stream_t stream) {
-    InvConvWeightsParams q;
-    int rc = invconv_weights_fill(q, p, lower, upper, log_s, sign_s, K, C, HW);
-    if (rc || !W || !logdet) {
-        rfn_set_error("rfn_invconv_weights_fwd_f32: argument check failed (%d)", rc ? rc : -3);
-        return rc ? rc : -3;
-    }
-    q.W = W;
-    q.logdet = logdet;
-    if (C > 64)  // three padded C x C matrices: 112 KB at C = 96 (the LDS of a CU is 160 KB)
-        (void)hipFuncSetAttribute((const void*)invconv_weights_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  3 * C * (C + 1) * (int)sizeof(float));
-    hipLaunchKernelGGL(invconv_weights_fwd_kernel, dim3(K), dim3(256), (size_t)3 * C * (C + 1) * sizeof(float),
-                       (hipStream_t)stream, q);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int rfn_invconv_weights_bwd_f32(const float* const* p, const float* const* lower, const float* const* upper,
-                                           const float* const* log_s, const float* const* sign_s, const float* gW,
-                                           const float* gc, float* g_lower, float* g_upper, float* g_log_s, int K, int C,
-                                           int HW, rfn_stream_t stream) {
-    InvConvWeightsParams q;
-    int rc = invconv_weights_fill(q, p, lower, upper, log_s, sign_s, K, C, HW);
-    if (rc || !gW || !g_lower || !g_upper || !g_log_s) {
-        rfn_set_error("rfn_invconv_weights_bwd_f32: argument check failed (%d)", rc ? rc : -3);
-        return rc ? rc : -3;
-    }
-    q.gW = gW; q.gc = gc; q.g_lower = g_lower; q.g_upper = g_upper; q.g_log_s = g_log_s;
-    if (C > 64)
-        (void)hipFuncSetAttribute((const void*)invconv_weights_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  3 * C * (C + 1) * (int)sizeof(float));
-    hipLaunchKernelGGL(invconv_weights_bwd_kernel, dim3(K), dim3(256), (size_t)3 * C * (C + 1) * sizeof(float),
-                       (hipStream_t)stream, q);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ SRNN latent step
-// RFN.loss per timestep (RFN_new.py:167-184,206-207): enc / pri are the outputs [B, 2*Z, HW] of the encoder / prior
-// parameter convs (loc | raw scale, "chunk(2,1)" halves, SimpleParamNet.forward Utils/modules.py:240-244):
-//   ps = softplus(pri_raw), es = softplus(enc_raw), pm = pri_loc, em = enc_loc (+ pm with res_q)
-//   zt = pm + ps*eps_p ;  zxt = em + es*eps_q ;  kl = KL(N(em,es) || N(pm,ps)) element-wise
-// One launch instead of ~25 tiny elementwise kernels per timestep (and ~50 in backward).
-// grid of an elementwise grid-stride kernel of 256 threads: one thread per element up to `cap` workgroups (the latent
-// step and ConvLSTM gate launchers launch this; their label queries print it)
-struct StrideRoute {
-    int grid;    // workgroups
-    int sweeps;  // most grid-stride iterations of a thread
-};
-static StrideRoute choose_stride_grid(long tot, int cap) {
-    StrideRoute r;
-    const long blocks = (tot + 255) / 256;
-    r.grid = (int)(blocks < cap ? blocks : cap);
-    r.sweeps = (int)((blocks + r.grid - 1) / r.grid);
-    return r;
-}
-constexpr int LATENT_STEP_MAX_GRID = 1024, CONVLSTM_GATES_MAX_GRID = 2048;
-extern "C" const char* rfn_latent_step_kernel_label(int B, int ZHW) {
-    static thread_local char buf[96];
-    if (B <= 0 || ZHW <= 0) return "unsupported";
-    const StrideRoute r = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID);
-    snprintf(buf, sizeof(buf), "latent_step grid=%d sweeps=%d", r.grid, r.sweeps);
-    return buf;
-}
-extern "C" const char* rfn_convlstm_gates_kernel_label(int N, int Hc, int HW) {
-    static thread_local char buf[96];
-    if (N <= 0 || Hc <= 0 || HW <= 0) return "unsupported";
-    const StrideRoute r = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID);
-    snprintf(buf, sizeof(buf), "convlstm_gates grid=%d sweeps=%d", r.grid, r.sweeps);
-    return buf;
-}
-
-__device__ __forceinline__ float sigmoid_sp(float raw) { return raw > 20.f ? 1.f : 1.f / (1.f + expf(-raw)); }
-
-__global__ void latent_step_fwd_kernel(const float* __restrict__ enc, const float* __restrict__ pri,
-                                       const float* __restrict__ eps_p, const float* __restrict__ eps_q,
-                                       float* __restrict__ zt, float* __restrict__ zxt, float* __restrict__ kl,
-                                       float* __restrict__ em_o, float* __restrict__ es_o, int B, int ZHW, int res_q) {
-    const long total = (long)B * ZHW;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long b = idx / ZHW, e = idx - b * ZHW;
-        const float pm = pri[b * 2 * ZHW + e], ps = softplusf_(pri[b * 2 * ZHW + ZHW + e]);
-        const float es = softplusf_(enc[b * 2 * ZHW + ZHW + e]);
-        const float em = enc[b * 2 * ZHW + e] + (res_q ? pm : 0.f);
-        zt[idx] = pm + ps * eps_p[idx];
-        zxt[idx] = em + es * eps_q[idx];
-        const float r = es / ps, d = (em - pm) / ps;
-        kl[idx] = 0.5f * (r * r + d * d - 1.f - logf(r * r));
-        em_o[idx] = em;
-        es_o[idx] = es;
-    }
-}
-__global__ void latent_step_bwd_kernel(const float* __restrict__ enc, const float* __restrict__ pri,
-                                       const float* __restrict__ eps_p, const float* __restrict__ eps_q,
-                                       const float* __restrict__ g_zt, long g_zt_ns,
-                                       const float* __restrict__ g_zxt, long g_zxt_ns,
-                                       const float* __restrict__ g_kl, const float* __restrict__ g_em,
-                                       const float* __restrict__ g_es, float* __restrict__ g_enc,
-                                       float* __restrict__ g_pri, int B, int ZHW, int res_q) {
-    const long total = (long)B * ZHW;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const long b = idx / ZHW, e = idx - b * ZHW;
-        const float praw = pri[b * 2 * ZHW + ZHW + e], eraw = enc[b * 2 * ZHW + ZHW + e];
-        const float pm = pri[b * 2 * ZHW + e], ps = softplusf_(praw), es = softplusf_(eraw);
-        const float em = enc[b * 2 * ZHW + e] + (res_q ? pm : 0.f);
-        const float gzt = g_zt ? g_zt[b * g_zt_ns + e] : 0.f, gzx = g_zxt ? g_zxt[b * g_zxt_ns + e] : 0.f;
-        const float gk = g_kl ? g_kl[idx] : 0.f;
-        const float ips = 1.f / ps, d = (em - pm) * ips * ips;  // (em-pm)/ps^2
-        const float d_em = gzx + gk * d + (g_em ? g_em[idx] : 0.f);
-        const float d_es = gzx * eps_q[idx] + gk * (es * ips * ips - 1.f / es) + (g_es ? g_es[idx] : 0.f);
-        float d_pm = gzt - gk * d;
-        const float d_ps = gzt * eps_p[idx] + gk * (ips - (es * es + (em - pm) * (em - pm)) * ips * ips * ips);
-        if (res_q) d_pm += d_em;
-        g_enc[b * 2 * ZHW + e] = d_em;
-        g_enc[b * 2 * ZHW + ZHW + e] = d_es * sigmoid_sp(eraw);
-        g_pri[b * 2 * ZHW + e] = d_pm;
-        g_pri[b * 2 * ZHW + ZHW + e] = d_ps * sigmoid_sp(praw);
-    }
-}
-extern "C" int rfn_latent_step_fwd_f32(const float* enc, const float* pri, const float* eps_p, const float* eps_q,
-                                       float* zt, float* zxt, float* kl, float* em, float* es, int B, int ZHW,
-                                       int res_q, rfn_stream_t stream) {
-    RFN_CHECK_ARG(enc && pri && eps_p && eps_q && zt && zxt && kl && em && es && B >= 0 && ZHW > 0, -1);
-    if (B == 0) return 0;
-    const int grid = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID).grid;
-    hipLaunchKernelGGL(latent_step_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc, pri, eps_p, eps_q, zt,
-                       zxt, kl, em, es, B, ZHW, res_q);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-extern "C" int rfn_latent_step_bwd_f32(const float* enc, const float* pri, const float* eps_p, const float* eps_q,
-                                       const float* g_zt, long g_zt_ns, const float* g_zxt, long g_zxt_ns,
-                                       const float* g_kl, const float* g_em, const float* g_es, float* g_enc,
-                                       float* g_pri, int B, int ZHW, int res_q, rfn_stream_t stream) {
-    RFN_CHECK_ARG(enc && pri && eps_p && eps_q && g_enc && g_pri && B >= 0 && ZHW > 0, -1);
-    RFN_CHECK_ARG((!g_zt || g_zt_ns >= ZHW) && (!g_zxt || g_zxt_ns >= ZHW), -1);
-    if (B == 0) return 0;
-    const int grid = choose_stride_grid((long)B * ZHW, LATENT_STEP_MAX_GRID).grid;
-    hipLaunchKernelGGL(latent_step_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, enc, pri, eps_p, eps_q,
-                       g_zt, g_zt_ns, g_zxt, g_zxt_ns, g_kl, g_em, g_es, g_enc, g_pri, B, ZHW, res_q);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------------ ConvLSTM gates
-__global__ void convlstm_gates_fwd_kernel(const float* __restrict__ cc, const float* __restrict__ c_prev, long c_ns,
-                                          const float* __restrict__ Wci, const float* __restrict__ Wcf,
-                                          const float* __restrict__ Wco, float* __restrict__ h_out, long h_ns,
-                                          float* __restrict__ c_out, long co_ns, float* __restrict__ gates, int N,
-                                          int Hc, int HW) {
-    const long per = (long)Hc * HW;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)N * per;
-         idx += (long)gridDim.x * blockDim.x) {
-        int n = (int)(idx / per);
-        long e = idx - n * per;  // channel*HW + p
-        const float* ccn = cc + (long)n * 4 * per;
-        float cp = c_prev[n * c_ns + e];
-        float wi = Wci ? Wci[e] : 0.f, wf = Wcf ? Wcf[e] : 0.f, wo = Wco ? Wco[e] : 0.f;
-        float i = 1.f / (1.f + expf(-(ccn[e] + wi * cp)));
-        float f = 1.f / (1.f + expf(-(ccn[per + e] + wf * cp)));
-        float g = tanhf(ccn[3 * per + e]);
-        float cn = f * cp + i * g;
-        float o = 1.f / (1.f + expf(-(ccn[2 * per + e] + wo * cn)));
-        h_out[n * h_ns + e] = o * tanhf(cn);
-        c_out[n * co_ns + e] = cn;
-        if (gates) {
-            float* gn = gates + (long)n * 4 * per;
-            gn[e] = i;
-            gn[per + e] = f;
-            gn[2 * per + e] = o;
-            gn[3 * per + e] = g;
-        }
-    }
-}
-extern "C" int rfn_convlstm_gates_fwd_f32(const float* cc, const float* c_prev, long c_ns, const float* Wci,
-                                          const float* Wcf, const float* Wco, float* h_out, long h_ns, float* c_out,
-                                          long co_ns, float* gates, int N, int Hc, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(cc && c_prev && h_out && c_out && N >= 0 && Hc > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    const int grid = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID).grid;
-    hipLaunchKernelGGL(convlstm_gates_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, cc, c_prev, c_ns, Wci,
-                       Wcf, Wco, h_out, h_ns, c_out, co_ns, gates, N, Hc, HW);
-    RFN_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ void convlstm_gates_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ c_prev, long c_ns,
-                                          const float* __restrict__ c_out, long co_ns, const float* __restrict__ gh,
-                                          long gh_ns, const float* __restrict__ gc_next, long gcn_ns,
-                                          const float* __restrict__ Wci, const float* __restrict__ Wcf,
-                                          const float* __restrict__ Wco, float* __restrict__ gcc,
-                                          float* __restrict__ gc_prev, long gcp_ns, int N, int Hc, int HW) {
-    const long per = (long)Hc * HW;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)N * per;
-         idx += (long)gridDim.x * blockDim.x) {
-        int n = (int)(idx / per);
-        long e = idx - n * per;
-        const float* gn = gates + (long)n * 4 * per;
-        float i = gn[e], f = gn[per + e], o = gn[2 * per + e], g = gn[3 * per + e];
-        float cp = c_prev[n * c_ns + e];
-        float cn = c_out[n * co_ns + e];
-        float wi = Wci ? Wci[e] : 0.f, wf = Wcf ? Wcf[e] : 0.f, wo = Wco ? Wco[e] : 0.f;
-        float ghv = gh ? gh[n * gh_ns + e] : 0.f;
-        float gcn = gc_next ? gc_next[n * gcn_ns + e] : 0.f;
-        float tc = tanhf(cn);
-        float go_pre = ghv * tc * o * (1.f - o);  // grad wrt (cc_o + Wco*cn)
-        float gc = gcn + ghv * o * (1.f - tc * tc) + go_pre * wo;
-        float gi_pre = gc * g * i * (1.f - i);
-        float gf_pre = gc * cp * f * (1.f - f);
-        float gg_pre = gc * i * (1.f - g * g);
-        float* gccn = gcc + (long)n * 4 * per;
-        gccn[e] = gi_pre;
-        gccn[per + e] = gf_pre;
-        gccn[2 * per + e] = go_pre;
-        gccn[3 * per + e] = gg_pre;
-        gc_prev[n * gcp_ns + e] = gc * f + gi_pre * wi + gf_pre * wf;
-    }
-}
-extern "C" int rfn_convlstm_gates_bwd_f32(const float* gates, const float* c_prev, long c_ns, const float* c_out,
-                                          long co_ns, const float* gh, long gh_ns, const float* gc_next, long gcn_ns,
-                                          const float* Wci, const float* Wcf, const float* Wco, float* gcc,
-                                          float* gc_prev, long gcp_ns, int N, int Hc, int HW, rfn_stream_t stream) {
-    RFN_CHECK_ARG(gates && c_prev && c_out && gcc && gc_prev && N >= 0 && Hc > 0 && HW > 0, -1);
-    if (N == 0) return 0;
-    const int grid = choose_stride_grid((long)N * Hc * HW, CONVLSTM_GATES_MAX_GRID).grid;
-    hipLaunchKernelGGL(convlstm_gates_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, gates, c_prev, c_ns,
-                       c_out, co_ns, gh, gh_ns, gc_next, gcn_ns, Wci, Wcf, Wco, gcc, gc_prev, gcp_ns, N, Hc, HW);
     RFN_LAUNCH_CHECK();
     return 0;
 }

@@ -1964,6 +1964,40 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         return gx_all, gh_rec, gc, gw, gb
 
 
+def _stepbn_fwd_buffers(x, gamma, beta, S, pooled=False):
+    """What a per-step BatchNorm forward (plain, synchronised or pooled) allocates for x [S*B, C, H, W]: (B, mean [S, C],
+    var [S, C], the output, the detached gamma and beta, the floats of scratch either direction needs, the scratch)."""
+    SB, C, H, W = (int(v) for v in x.shape)
+    B = SB // S
+    mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
+    var = torch.empty((S, C), device=x.device, dtype=torch.float32)
+    out = torch.empty((SB, C, H // 2, W // 2), device=x.device, dtype=torch.float32) if pooled else torch.empty_like(x)
+    gm = None if gamma is None else gamma.detach().contiguous()
+    bt = None if beta is None else beta.detach().contiguous()
+    nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))  # partial sums of the split reductions (either way)
+    acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
+    return B, mean, var, out, gm, bt, nscr, acc
+
+
+def _stepbn_running_args(running):
+    """the running-statistics arguments of rfn_stepbn_fwd_f32 / rfn_stepbn_pool_fwd_f32 from `running` (or None)"""
+    if running is None:
+        return None, None, None, None, 1.0, None
+    rm, rv, cf, cfu, decay, nbt = running
+    if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+        raise RuntimeError("num_batches_tracked must be an int64 device tensor")
+    return L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr()
+
+
+def _stepbn_bwd_buffers(x, C, affine, nscr):
+    """what a per-step BatchNorm backward allocates: (sums, gx, ggamma, gbeta); the last two None without affine"""
+    sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
+    gx = torch.empty_like(x)
+    ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+    gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+    return sums, gx, ggamma, gbeta
+
+
 class StepBatchNormActFn(torch.autograd.Function):
     """Training-mode BatchNorm2d with per-timestep statistics on a step-major time-batched tensor [S*B, C, H, W],
     fused with the activation that follows it (rfn_stepbn_{fwd,bwd}_f32: two launches each way).  Returns (y, mean[S, C],
@@ -1979,24 +2013,10 @@ class StepBatchNormActFn(torch.autograd.Function):
         if rdist.sync_batchnorm_on():
             return StepBatchNormActFn._forward_sync(ctx, x, gamma, beta, S, eps, act, slope, running)
         ctx.world = 1
-        SB, C, H, W = (int(v) for v in x.shape)
-        B, HW = SB // S, H * W
-        mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        var = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        y = torch.empty_like(x)
-        gm = None if gamma is None else gamma.detach().contiguous()
-        bt = None if beta is None else beta.detach().contiguous()
-        nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))  # partial sums of the split reductions (either way)
-        acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-        rm = rv = cf = cfu = nbt = None
-        decay = 1.0
-        if running is not None:
-            rm, rv, cf, cfu, decay, nbt = running
-            if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
-                raise RuntimeError("num_batches_tracked must be an int64 device tensor")
+        C, HW = int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])
+        B, mean, var, y, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S)
         L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr(), S, B, C, HW,
-               eps, act, slope, meta=_shell("stepbn_fwd", x, 3))
+               *_stepbn_running_args(running), S, B, C, HW, eps, act, slope, meta=_shell("stepbn_fwd", x, 3))
         ctx.save_for_backward(x, mean, var, gm, bt)
         ctx.cfg = (S, B, C, HW, eps, act, slope, gamma is not None, nscr)
         ctx.mark_non_differentiable(mean, var)
@@ -2009,18 +2029,11 @@ class StepBatchNormActFn(torch.autograd.Function):
         statistics; the running statistics follow the global moments (torch ops on [C] vectors)."""
         import torch.distributed as dist
         from . import dist as rdist
-        SB, C, H, W = (int(v) for v in x.shape)
-        B, HW = SB // S, H * W
+        C, HW = int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])
         world = dist.get_world_size()
-        mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        var = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        y = torch.empty_like(x)
-        gm = None if gamma is None else gamma.detach().contiguous()
-        bt = None if beta is None else beta.detach().contiguous()
-        nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))
-        acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
+        B, mean, var, y, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S)
         L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               None, None, None, None, 1.0, None, S, B, C, HW, eps, act, slope)
+               *_stepbn_running_args(None), S, B, C, HW, eps, act, slope)
         st = rdist.all_gather_cat(torch.stack((mean, var)).unsqueeze(0))          # [world, 2, S, C]
         mean = st[:, 0].mean(0).contiguous()
         var = (st[:, 1].mean(0) + (st[:, 0] - mean).pow(2).mean(0)).contiguous()  # equal counts per rank
@@ -2047,10 +2060,7 @@ class StepBatchNormActFn(torch.autograd.Function):
         if g is None:
             return (None,) * 8
         g = g.contiguous()
-        sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-        gx = torch.empty_like(x)
-        ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
-        gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+        sums, gx, ggamma, gbeta = _stepbn_bwd_buffers(x, C, affine, nscr)
         args = (L.dev(x), L.dev(gm), L.dev(bt), L.dev(g), L.dev(mean), L.dev(var), L.dev(sums), L.dev(gx), L.dev(ggamma),
                 L.dev(gbeta), S, B, C, HW, eps, act, slope)
         if ctx.world > 1:   # synchronised: partial sums, added over the ranks, apply
@@ -2073,25 +2083,11 @@ class StepBatchNormActPoolFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, S, eps, act, slope, running=None):
         ctx.set_materialize_grads(False)
         x = x.contiguous()
-        SB, C, H, W = (int(v) for v in x.shape)
-        B = SB // S
-        mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        var = torch.empty((S, C), device=x.device, dtype=torch.float32)
-        p = torch.empty((SB, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        gm = None if gamma is None else gamma.detach().contiguous()
-        bt = None if beta is None else beta.detach().contiguous()
-        nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))
-        acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-        rm = rv = cf = cfu = nbt = None
-        decay = 1.0
-        if running is not None:
-            rm, rv, cf, cfu, decay, nbt = running
-            if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
-                raise RuntimeError("num_batches_tracked must be an int64 device tensor")
+        C, H, W = (int(v) for v in x.shape[1:])
+        B, mean, var, p, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S, pooled=True)
         # x read by the statistics and by the apply launch, a quarter of it written
         L.call("rfn_stepbn_pool_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(p), L.dev(mean), L.dev(var), L.dev(acc),
-               L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr(), S, B, C, H, W,
-               eps, act, slope, meta=_shell("stepbn_pool_fwd", x, 2.25))
+               *_stepbn_running_args(running), S, B, C, H, W, eps, act, slope, meta=_shell("stepbn_pool_fwd", x, 2.25))
         ctx.save_for_backward(x, mean, var, gm, bt)
         ctx.cfg = (S, B, C, H, W, eps, act, slope, gamma is not None, nscr)
         ctx.mark_non_differentiable(mean, var)
@@ -2104,10 +2100,7 @@ class StepBatchNormActPoolFn(torch.autograd.Function):
         if gp is None:
             return (None,) * 8
         gp = gp.contiguous()
-        sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-        gx = torch.empty_like(x)
-        ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
-        gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
+        sums, gx, ggamma, gbeta = _stepbn_bwd_buffers(x, C, affine, nscr)
         # x and the pooled gradient read by the reduce and by the apply launch, gx written
         L.call("rfn_stepbn_pool_bwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(gp), L.dev(mean), L.dev(var), L.dev(sums),
                L.dev(gx), L.dev(ggamma), L.dev(gbeta), S, B, C, H, W, eps, act, slope, 0, 1,

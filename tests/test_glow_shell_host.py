@@ -1,7 +1,7 @@
 """Launch routes, size limits and argument checks of the Glow shell entry points, without a device.
 
 rfn_glow_shell_fwd_kernel_label / rfn_glow_shell_bwd_kernel_label print the host structs the launchers themselves read
-(choose_shell_fwd / choose_shell_bwd in csrc/shell.hip).  The tables below say, from a reading of the kernels, which
+(choose_shell_fwd / choose_shell_bwd in csrc/glow_shell.hip).  The tables below say, from a reading of the kernels, which
 branch each shape of tests/test_glow_shell.py takes; this module holds the library to them on any machine, and
 test_glow_shell.py runs the same rows on the GPU.  The log-det class is decided on the device, block by block: here the
 kernel's three tests are restated per block (ld_classes) and must give the class the label prints.

@@ -1,7 +1,7 @@
 """Case tables, launch routes and fp64 references of the recurrent / likelihood shell kernels, without a device.
 
 rfn_stepbn_kernel_label, rfn_convlstm_gates_kernel_label and rfn_latent_step_kernel_label print the host structs the
-launchers themselves read (choose_stepbn / choose_stride_grid in csrc/shell.hip).  The tables below say, from a reading of
+launchers themselves read (choose_stepbn in csrc/stepbn.hip, choose_stride_grid in csrc/recurrent_shell.hip).  The tables below say, from a reading of
 the kernels, which branch each shape of tests/test_recurrent_shell.py is there for; this module holds the library to them
 on any machine, and test_recurrent_shell.py runs the same rows on the GPU.
 

@@ -1,7 +1,7 @@
 """Case table, launch routes and fp64 reference of the per-step BatchNorm + activation + 2x2 max-pool kernels
 (rfn_stepbn_pool_{fwd,bwd}_f32), without a device.  tests/test_stepbn_pool.py runs the same rows on the GPU.
 
-rfn_stepbn_pool_kernel_label prints the host struct the launchers read (choose_stepbn_pool in csrc/shell.hip).  `aligned`
+rfn_stepbn_pool_kernel_label prints the host struct the launchers read (choose_stepbn with its pool flag in csrc/stepbn.hip).  `aligned`
 bit 0: x (statistics kernel) or, backward, x and gp (reduce kernel) are 16-byte aligned; bit 1: the apply kernel's
 pointers (x, p; backward x, gp, gx).  The pooled kernels also need W % 4 == 0 for their 16-byte route; the statistics
 kernel is the unpooled one and tests H*W % 4, which even sides always satisfy.

@@ -1,4 +1,4 @@
-"""GPU tests of the two kernels behind per-row temperatures: rfn_gauss_sample_rows_f32 (csrc/shell.hip; one temperature
+"""GPU tests of the two kernels behind per-row temperatures: rfn_gauss_sample_rows_f32 (csrc/gauss.hip; one temperature
 per frame, the same kernel as the scalar entry point) against fp64 and against the scalar call's bits, and the tiled
 addressed noise rfn_keyed_normal_tiled_f32 (csrc/keyed_normal.hip through ops.keyed_normal(tiles=K)) against the untiled
 call, plus the argument errors of both wrappers.

@@ -1,6 +1,6 @@
 """Launch routes of rfn_up2x_cat_f32 / rfn_up2x_cat_bwd_f32 (nearest 2x up-sampling + channel concatenation in one launch
 each way), without a device.  rfn_up2x_cat_kernel_label prints the host struct the launchers read (choose_up2x in
-csrc/shell.hip); `aligned` = every pointer 16-byte aligned and every frame stride a multiple of 4 floats.
+csrc/up2x_cat.hip); `aligned` = every pointer 16-byte aligned and every frame stride a multiple of 4 floats.
 tests/test_up2x_cat.py runs the same shapes on the GPU."""
 import ctypes
 
