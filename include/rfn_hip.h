@@ -922,6 +922,41 @@ int rfn_keyed_uniform_f32(float* out, int n_steps, int rows, int B, int numel, f
  * B == 0 returns 0 without a launch.  One launch. */
 int rfn_clip_gather_u8_f32(const void* store, long n_frames, const void* first, float* out, int B, int T, int C, int Cs,
                            int H, int W, rfn_stream_t stream);
+/* rfn_clip_gather_aug_u8_f32: the same gather with a temporal stride and two per-clip augmentations (csrc/clip_gather.hip;
+ * data_generators/clip_folder.py).  store, n_frames, first, out, B, T, C, Cs, H, W as above;
+ * step >= 1: store frames between two frames of a clip; flags: int32 [B] device tensor or NULL (all 0), bit 0 mirrors x,
+ * bit 1 reverses time, other bits are ignored.
+ *   out[b,t,c,y,x] = lut[ store[first[b] + tt*step, y, xx, c'] ],   tt = bit1 ? T-1-t : t,   xx = bit0 ? W-1-x : x
+ * with the same correctly rounded k/255 table and the same channel rule c'.  A clip with first[b] < 0 or
+ * first[b] + (T-1)*step + 1 > n_frames reads nothing: all its T frames are NaN.  With flags == NULL and step == 1 the
+ * output is rfn_clip_gather_u8_f32's bit for bit.  16-byte loads and float4 stores under rfn_clip_gather_u8_f32's
+ * conditions; a mirrored clip keeps them where W % 4 == 0 (the four pixels of a group are reversed in registers and
+ * stored at the mirrored group of their row) and goes pixel by pixel at any other width.  No atomics, no scratch.
+ * Returns -1 for sizes or a step below their minimum, -2 for the channel rule, -3 / -4 for a frame or a batch beyond one
+ * launch, -5 for a NULL store, first or out, -6 for flags that are not 4-byte aligned; nothing is launched then.  B == 0
+ * returns 0 without a launch.  One launch, no allocation: capturable. */
+int rfn_clip_gather_aug_u8_f32(const void* store, long n_frames, const void* first, const void* flags, float* out, int B,
+                               int T, int C, int Cs, int H, int W, int step, rfn_stream_t stream);
+
+/* ---- frames of any size and channel count into a frame store's geometry  (csrc/frame_resize.hip; the ingest step of
+ * data_generators/clip_folder.py).  src: uint8 [F, Hs, Ws, Cs] device tensor, channel-interleaved,
+ * of any byte alignment; dst_addr: the device address of the uint8 output [F, H, W, Cd], of any byte alignment (the
+ * header has no mutable byte pointer type); Cs, Cd in {1, 3}; (y0, x0, Hc, Wc): the crop window, which must lie
+ * inside the source frame.  Exact integer area mean, rounded half up: output row y covers [y*Hc, (y+1)*Hc) on a grid
+ * where window row i covers [i*H, (i+1)*H), so
+ *   wy(i) = min((y+1)*Hc, (i+1)*H) - max(y*Hc, i*H)   for i = floor(y*Hc/H) .. ceil((y+1)*Hc/H) - 1
+ * (every wy(i) > 0, their sum is Hc), wx(j) alike with W and Wc, and per stored channel
+ *   v = (sum_i sum_j wy(i) * wx(j) * src[f, y0+i, x0+j, c] + (Hc*Wc)/2) / (Hc*Wc)            (integer division)
+ * accumulated in 64 bits.  Equal sizes give the identity, a constant frame stays constant, enlarging is the same
+ * formula.  Channels, on the rounded bytes: Cs == Cd copies; 3 -> 1 is (19595 R + 38470 G + 7471 B + 32768) >> 16;
+ * 1 -> 3 is three copies.  Every output byte is written exactly once; nothing is read outside the windows.
+ * One workgroup per (frame, band of output rows); the source rows under the band pass through LDS in pieces of at most
+ * 2 KiB of a row, with 16-byte loads when src is 16-byte aligned and Ws*Cs is a multiple of 16, single bytes otherwise.
+ * No atomics, no scratch.  Returns -1 for F < 0 or a side outside [1, 32768], -2 for channel counts other than 1 and 3,
+ * -3 for an empty window or one that leaves the frame, -4 for more than 2^31 - 1 workgroups, -5 for a NULL src or a
+ * dst_addr of 0; nothing is launched then.  F == 0 returns 0 without a launch.  One launch, no allocation: capturable. */
+int rfn_frames_resize_u8(const void* src, long dst_addr, long F, int Hs, int Ws, int Cs, int H, int W, int Cd, int y0, int x0,
+                         int Hc, int Wc, rfn_stream_t stream);
 
 /* ---- a sheet of frames as 8-bit RGB pixels  (the subplot grids of plotter(), RFN/trainer.py:325-417, and of
  * Evaluator.plot_samples, evaluation_metrics/error_metrics.py:128-152, as pixels only: no text, axes or titles).

@@ -137,6 +137,8 @@ class Solver(object):
         if not getattr(self.args, "synthetic_data", False):
             if self.choose_data == "mnist":
                 return self.create_mnist_loaders()
+            if self.choose_data == "folder":
+                return self.create_folder_loaders()
             return self.create_clip_loaders()
         c = self.args.x_dim[1]
         mk = lambda seed: SyntheticMovingMNIST(seq_len=self.n_frames, image_size=self.image_size,
@@ -206,6 +208,35 @@ class Solver(object):
                                                 seed=seed, device=self.device, channels=c, length=length,
                                                 cache=cache("kth_" + ("train" if train else "test")))
             trainset, testset = mk(True, length), mk(False)
+        return (ClipLoader(trainset, self.batch_size, self.rank, self.world),
+                ClipLoader(testset, self.batch_size, self.rank, self.world))
+
+    def create_folder_loaders(self):
+        """`--choose_data folder`: any tree of frame directories and .npy sequences under
+        --data_root/{train,test} (data_generators/clip_folder.py).  x_dim's C, H, W is the target geometry (1 or 3
+        channels, non-square allowed): frames of another size are resampled on the GPU once, over the window of
+        --resize_mode, and the packed store is kept under --data_cache while the files match.  --frame_step is the
+        distance between two frames of a clip; --augment flip / reverse switch the mirror and time-reversal bits of
+        the train split on.  With --use_validation_set the train split has 500 clips per epoch."""
+        from data_generators import ClipFolder, ClipLoader
+        root = getattr(self.args, "data_root", None)
+        if root is None:
+            raise ValueError("--choose_data folder needs --data_root: the directory holding train/ and test/ (nothing is "
+                             "searched for or downloaded)")
+        if not os.path.isdir(root):
+            raise FileNotFoundError("--data_root %s is not a directory" % root)
+        cache_dir = getattr(self.args, "data_cache", None)
+        step = getattr(self.args, "frame_step", 1)   # (Namespaces saved before these flags existed)
+        augment = list(getattr(self.args, "augment", None) or [])
+        mode = getattr(self.args, "resize_mode", "crop")
+        _, c, h, w = self.args.x_dim
+        cache = lambda split: None if cache_dir is None else os.path.join(
+            cache_dir, "folder_%s_%dx%dx%d_%s" % (split, h, w, c, mode))
+        mk = lambda train, length=None: ClipFolder(
+            train, root, seq_len=self.n_frames, channels=c, height=h, width=w, step=step, flip="flip" in augment,
+            reverse="reverse" in augment, resize_mode=mode, seed=getattr(self.args, "data_seed", 0), device=self.device,
+            cache=cache("train" if train else "test"), length=length)
+        trainset, testset = mk(True, 500 if self.use_validation_set else None), mk(False)
         return (ClipLoader(trainset, self.batch_size, self.rank, self.world),
                 ClipLoader(testset, self.batch_size, self.rank, self.world))
 

@@ -3,3 +3,4 @@ from .moving_mnist import MovingMNIST, MovingMNIST_synchronized, MovingMNISTLoad
 from .clips import ClipLoader, FrameStore  # noqa: F401
 from .bair_push import PushDataset  # noqa: F401
 from .kth import KTH, read_t7  # noqa: F401
+from .clip_folder import ClipFolder  # noqa: F401

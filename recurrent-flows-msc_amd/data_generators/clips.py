@@ -10,7 +10,9 @@ that choose the clips of an epoch, and the device loader.
   of csrc/moving_mnist.hip, here vectorised in numpy on the host.  A dataset computes the first-frame index of every
   clip of an epoch at once (`epoch_table`); the table is uploaded as one int64 tensor and a batch is one launch of
   rfn_clip_gather_u8_f32 (csrc/clip_gather.hip) reading its B rows: no per-batch copy, no synchronisation.
-- `ClipLoader`: MovingMNISTLoader's contract over such a dataset."""
+- `ClipLoader`: MovingMNISTLoader's contract over such a dataset.  A dataset that has `device_flags(epoch)`
+  (clip_folder.py: the augmentation bits of the epoch's clips) is handed its rows of them along with the first frames.
+- `pack_resized_or_load`: pack_or_load for sequences of any frame size (clip_folder.py), resampled on the GPU."""
 import os
 
 import numpy as np
@@ -173,6 +175,43 @@ def pack_or_load(cache, root, files, decode, H, W, Cs, also=()):
     return store
 
 
+RESIZE_CHUNK_BYTES = 64 << 20   # most source bytes of one upload of pack_resized_or_load
+
+
+def pack_resized_or_load(cache, root, files, read, H, W, C, window, device=None):
+    """pack_or_load for sequences whose frames may have any size: the FrameStore [F, H, W, C] of `files` ([[path, ...]
+    per sequence], under `root`), from the prefix `cache` when its fingerprint and geometry match, else built from
+    `read(n) -> uint8 [T, Hs, Ws, Cs]` (sequence n, Cs in {1, 3}) and, with a prefix, saved there.  A sequence that
+    already is H x W x C is copied on the host, with no kernel and no GPU.  Any other one is uploaded to `device`
+    (default: the current GPU) at most RESIZE_CHUNK_BYTES of source frames at a time, at least one frame, and resampled
+    there by rfn_hip.ops.frames_resize over `window(Hs, Ws) -> (y0, x0, Hc, Wc)`; there is no host resize."""
+    paths, sizes = fingerprint(root, [p for seq in files for p in seq])
+    store = FrameStore.cached(cache, paths, sizes)
+    if store is not None and (store.H, store.W, store.Cs) == (H, W, C) and len(store) == len(files):
+        return store
+    parts = []
+    for n in range(len(files)):
+        a = np.asarray(read(n))
+        if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] not in (1, 3):
+            raise ValueError("sequence %s: frames must be uint8 [T, H, W, 1 or 3], got %s %s" %
+                             (files[n][0] if files[n] else n, a.dtype, a.shape))
+        if a.shape[1:] != (H, W, C) and a.shape[0]:
+            from rfn_hip import ops
+            dev = torch.device(device) if device is not None else torch.device("cuda")
+            per = max(1, RESIZE_CHUNK_BYTES // int(np.prod(a.shape[1:])))
+            win = window(a.shape[1], a.shape[2])
+            a = np.concatenate([ops.frames_resize(torch.from_numpy(np.ascontiguousarray(a[k:k + per])).to(dev), H, W, C,
+                                                  win).cpu().numpy() for k in range(0, a.shape[0], per)])
+        parts.append(a.reshape(-1, H, W, C))
+    length = np.array([p.shape[0] for p in parts], dtype=np.int64)
+    offset = np.concatenate([[0], np.cumsum(length)[:-1]]).astype(np.int64) if len(parts) else length
+    frames = np.concatenate(parts) if parts else np.empty((0, H, W, C), dtype=np.uint8)
+    store = FrameStore(frames, offset, length, paths, sizes)
+    if cache is not None:
+        store.save(cache)
+    return store
+
+
 # ------------------------------------------------------------------------------------------------- datasets, loader
 class ClipDataset(object):
     """Base of PushDataset and KTH: a FrameStore, a clip length, a seed and a split.  A subclass supplies
@@ -247,7 +286,11 @@ class ClipLoader(object):
 
     def batch(self, g):
         lo, hi = self.rows(g)
-        return self.dataset.gather(self.dataset.device_table(self.epoch)[lo:hi])
+        first = self.dataset.device_table(self.epoch)[lo:hi]
+        flags = getattr(self.dataset, "device_flags", None)   # (ClipFolder: the augmentation bits of the epoch's clips)
+        if flags is None:
+            return self.dataset.gather(first)
+        return self.dataset.gather(first, flags(self.epoch)[lo:hi])
 
     def __iter__(self):
         for g in range(len(self)):

@@ -8,6 +8,13 @@ a job script written for the reference drives this implementation unchanged.  Ad
   --data_root        where `--choose_data bair` / `kth` read their files (default, as the reference:
                      `bair_robot_data/processed_data/` / `kth_data` in the working directory; never downloaded);
   --data_cache       directory for the packed frame stores of BAIR / KTH (decoded once, reused while the files match);
+  --choose_data folder   train on any tree `--data_root/{train,test}/...` whose directories of image files and .npy
+                     arrays are the recorded sequences (data_generators/clip_folder.py); frames are resampled on the
+                     GPU to x_dim's C, H, W once and cached under --data_cache;
+  --frame_step       folder: frames between two frames of a clip (default 1);
+  --augment          folder: `flip` and / or `reverse`, a mirror bit and a time-reversal bit drawn per train clip and
+                     applied inside the gather launch (default none);
+  --resize_mode      folder: `crop` (largest centred window of the target's aspect ratio, default) or `stretch`;
   --plot_every       write a sheet of ground truth, samples, predictions and reconstructions of one test sequence to
                      `png_folder/samples<k>.png` after every N-th epoch (default 0: never);
   --grad_clip_norm   clip the global gradient norm to this value before every Adam step (default 0: off);
@@ -74,7 +81,8 @@ def build_parser():
     # DATA
     p.add_argument("--batch_size", help="Specify batch size", default=35, type=int)
     p.add_argument("--n_frames", help="Specify number of frames", default=10, type=int)
-    p.add_argument("--choose_data", help="Specify dataset", choices=["mnist", "bair", "kth"], default="bair", type=str)
+    p.add_argument("--choose_data", help="Specify dataset", choices=["mnist", "bair", "kth", "folder"],
+                   default="bair", type=str)
     p.add_argument("--image_size", help="Specify the image size of mnist", default=64, type=int)
     p.add_argument("--digit_size", help="Specify the size of mnist digit", default=32, type=int)
     p.add_argument("--step_length", help="Specify the step size of mnist digit", default=4, type=int)
@@ -172,6 +180,12 @@ def build_parser():
                    "reference's, under the working directory)", default=None, type=str)
     p.add_argument("--data_cache", help="Directory for the packed frame stores of --choose_data bair / kth",
                    default=None, type=str)
+    p.add_argument("--frame_step", help="--choose_data folder: frames between two frames of a clip", default=1, type=int)
+    p.add_argument("--augment", help="--choose_data folder: augmentations of the train split, drawn per clip",
+                   nargs="*", choices=["flip", "reverse"], default=[], type=str)
+    p.add_argument("--resize_mode", help="--choose_data folder: frames of another size are centre-cropped to the "
+                   "target's aspect ratio (crop) or taken whole (stretch) before the area-mean resize",
+                   choices=["crop", "stretch"], default="crop", type=str)
     p.add_argument("--plot_every", help="Write png_folder/samples<k>.png after every N-th epoch (0 = never)", default=0,
                    type=int)
     p.add_argument("--grad_clip_norm", help="Clip the global gradient norm to this value before the Adam step (0 = off)",
