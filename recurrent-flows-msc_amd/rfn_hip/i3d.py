@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .frame_metrics import _u8_frames
 
 
 SIDE = 224                    # the public path resizes every frame to SIDE x SIDE
@@ -363,7 +364,6 @@ def _check_videos(v, who):
 
 
 def _resize_into(videos, out):
-    from .ops import _u8_frames
     N, T, C, H, W = (int(d) for d in videos.shape)
     if N * T:
         v, p, ns = _u8_frames(videos, C, H, W)

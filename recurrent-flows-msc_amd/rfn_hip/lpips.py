@@ -23,6 +23,7 @@ import os
 import torch
 
 from . import lib as L
+from .frame_metrics import _u8_frames
 
 
 MIN_SIDE = 31
@@ -146,7 +147,6 @@ def lpips_alex_features(w, frames, chunk=None):
     (rfn_lpips_alex_features_u8): an LpipsFeatures pack.  Frames are processed `chunk` at a time (default: as many as keep
     the pooled-map workspace under 64 MiB, at most 1024); a frame's features do not depend on the chunking.  Views such as
     x[:, start:] or a channel slice are accepted."""
-    from .ops import _u8_frames
     C, H, W = _check_frames(frames, "frames", "lpips_alex_features")
     _, F, work = lpips_alex_sizes(H, W)
     _check_device(w, frames, "frames", "lpips_alex_features")

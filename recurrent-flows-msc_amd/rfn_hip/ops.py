@@ -3,15 +3,20 @@
 Everything here runs on the GPU through librfn_hip.so; torch is used for memory, streams and autograd plumbing.
 Frame-batched layout: tensors are [N, C, H, W] fp32 where N = all frames handed over by the caller (the RFN driver
 time-batches B*(T-1) frames into one call).
+
+This module holds the training core (the convolutions and their gradients, the Glow nodes, the latent step and the
+ConvLSTM), whose functions read CONV_PRECISION / MIXED_FWD and call each other through this namespace.  Every other
+wrapper family has a module of its own, named after the csrc file it wraps; the block at the bottom re-exports their
+public names, so callers write rfn_hip.ops.X for all of them ("Where the Python wrappers live").
 """
 import collections
-import ctypes
 import functools
 import itertools
 
 import torch
 
 from . import lib as L
+from .args import flat as _f, shell as _shell
 
 import os
 
@@ -69,11 +74,6 @@ def kernel_label(query, *args):
     (the *_kernel_label_* functions of include/rfn_hip.h, answered by the function the launcher itself switches on): the
     label of a launch's profiling metadata.  Memoised: the library reads its selector knobs once per process."""
     return getattr(L.load(), query)(*args).decode()
-
-
-def _shell(name, t, n_tensors):
-    """profiling metadata of a memory-bound shell launch: algorithmic bytes = n_tensors x the tensor's fp32 size"""
-    return ("shell", name, 0.0, "x".join(str(int(d)) for d in t.shape), 4.0 * n_tensors * t.numel())
 
 
 def channel_stats(x):
@@ -915,10 +915,6 @@ def conv_ep(in1, in2, w, p0, p1, ep_mode, act, prec=None, packs=None):
     return ConvFn.apply(in1, in2, w, p0, p1, ep_mode, act, prec, packs)
 
 
-def _f(t):
-    return None if t is None else t.detach().reshape(-1).contiguous()
-
-
 # the packed weights of one Glow step's coupling net, kept fresh by the caller (Flow/glow.py ListGlow._packed_weights).
 # *_fwd / *_dgrad: conv packs of the forward (in the map's split forward arithmetic) / data-gradient convolutions;
 # po_fwd / po_bwd: the fused kernels' weight streams (POPackPlan); *_dense_*: dense small-map packs (smallmap_conv).
@@ -1649,193 +1645,6 @@ def latent_iw(enc_raw, pri_raw, eps_q, res_q):
     return zxt, logr
 
 
-GAUSS_HEADS_OUTPUTS = ("z_q", "z_p", "q_scale", "p_scale", "kl", "logq", "logp")
-# what each output reads beside p_loc / p_raw, which every call needs
-_GAUSS_HEADS_NEEDS = {"z_q": ("q_loc", "q_raw", "eps_q"), "z_p": ("eps_p",), "q_scale": ("q_loc", "q_raw"), "p_scale": (),
-                      "kl": ("q_loc", "q_raw"), "logq": ("q_loc", "q_raw", "eps_q"), "logp": ("eps_p",)}
-
-
-def gauss_heads_check(q_loc, q_raw, p_loc, p_raw, eps_q, eps_p, want):
-    """(B, Z) of a gauss_heads call, or a ValueError naming what does not fit.  Needs no device."""
-    given = {"q_loc": q_loc, "q_raw": q_raw, "p_loc": p_loc, "p_raw": p_raw, "eps_q": eps_q, "eps_p": eps_p}
-    want = tuple(want)
-    if not want or len(set(want)) != len(want) or any(w not in GAUSS_HEADS_OUTPUTS for w in want):
-        raise ValueError("gauss_heads: want must name distinct outputs of %s, got %r" % (GAUSS_HEADS_OUTPUTS, want))
-    if p_loc is None or p_raw is None:
-        raise ValueError("gauss_heads: p_loc and p_raw are always needed")
-    if (q_loc is None) != (q_raw is None):
-        raise ValueError("gauss_heads: q_loc and q_raw come together (both None: the prior-only form)")
-    if q_loc is None and eps_q is not None:
-        raise ValueError("gauss_heads: eps_q without q_loc / q_raw")
-    for w in want:
-        missing = [n for n in _GAUSS_HEADS_NEEDS[w] if given[n] is None]
-        if missing:
-            raise ValueError("gauss_heads: output %r needs %s" % (w, ", ".join(missing)))
-    if p_loc.dim() != 2 or p_loc.shape[0] < 1 or p_loc.shape[1] < 1:
-        raise ValueError("gauss_heads: inputs are [B, Z] with B, Z >= 1, got p_loc %s" % (tuple(p_loc.shape),))
-    for n, t in given.items():
-        if t is not None and tuple(t.shape) != tuple(p_loc.shape):
-            raise ValueError("gauss_heads: %s has shape %s, p_loc %s" % (n, tuple(t.shape), tuple(p_loc.shape)))
-    return int(p_loc.shape[0]), int(p_loc.shape[1])
-
-
-class GaussHeadsFn(torch.autograd.Function):
-    """the diagonal Gaussians of one VRNN step in one kernel each way (rfn_gauss_heads_{fwd,bwd}_f32, include/rfn_hip.h):
-    returns the seven GAUSS_HEADS_OUTPUTS in that order, None where `want` does not name one.  Saves the six inputs
-    only; the backward recomputes sigma."""
-
-    @staticmethod
-    def forward(ctx, q_loc, q_raw, p_loc, p_raw, eps_q, eps_p, want):
-        ctx.set_materialize_grads(False)  # unused outputs arrive as None
-        B, Z = gauss_heads_check(q_loc, q_raw, p_loc, p_raw, eps_q, eps_p, want)
-        ins = [None if t is None else t.contiguous() for t in (q_loc, q_raw, p_loc, p_raw, eps_q, eps_p)]
-        ptrs = [L.dev(t, n) for t, n in zip(ins, ("q_loc", "q_raw", "p_loc", "p_raw", "eps_q", "eps_p"))]
-        outs = []
-        for name in GAUSS_HEADS_OUTPUTS:
-            shape = (B,) if name in ("kl", "logq", "logp") else (B, Z)
-            outs.append(torch.empty(shape, device=p_loc.device, dtype=torch.float32) if name in want else None)
-        L.call("rfn_gauss_heads_fwd_f32", *ptrs, *[L.dev(o) for o in outs], B, Z,
-               meta=_shell("gauss_heads_fwd", p_loc, sum(t is not None for t in ins + outs)))
-        ctx.save_for_backward(*ins)
-        ctx.cfg = (B, Z)
-        # the ABI has no upstream gradient for the scales: they are values (the KL and the densities are outputs of their own)
-        ctx.mark_non_differentiable(*[o for o in outs[2:4] if o is not None])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, g_zq, g_zp, g_qs, g_ps, g_kl, g_logq, g_logp):
-        ins = ctx.saved_tensors
-        q_loc, p_loc = ins[0], ins[2]
-        B, Z = ctx.cfg
-        # g_zq / g_zp may arrive as column slices of a wider gradient: read in place (row stride)
-        strided, keep = [], []
-        for g in (g_zq, g_zp):
-            if g is None:
-                strided += [None, 0]
-                continue
-            if (Z > 1 and g.stride(1) != 1) or (B > 1 and g.stride(0) < Z):
-                g = g.contiguous()
-            keep.append(g)
-            strided += [L.dev(g, "g_z", check_contiguous=False), int(g.stride(0)) if B > 1 else Z]
-        gs = [None if g is None else g.contiguous() for g in (g_kl, g_logq, g_logp)]
-        g_q = [None, None] if q_loc is None else [torch.empty_like(q_loc), torch.empty_like(q_loc)]
-        g_p = [torch.empty_like(p_loc), torch.empty_like(p_loc)]
-        L.call("rfn_gauss_heads_bwd_f32", *[L.dev(t) for t in ins], *strided, *[L.dev(g) for g in gs],
-               *[L.dev(g) for g in g_q + g_p], B, Z, meta=_shell("gauss_heads_bwd", p_loc, 10))
-        return g_q[0], g_q[1], g_p[0], g_p[1], None, None, None
-
-
-def gauss_heads(q_loc, q_raw, p_loc, p_raw, eps_q=None, eps_p=None, want=("z_q", "kl")):
-    """The outputs named in `want`, in that order, of the [B, Z] Gaussians N(q_loc, softplus(q_raw)) and N(p_loc,
-    softplus(p_raw)): "z_q" / "z_p" = loc + sigma * eps, "q_scale" / "p_scale" = sigma (no gradient is taken through
-    them), "kl" [B] = KL(q || p) summed over the row, "logq" / "logp" [B] = the row-summed log-density of each
-    distribution at its own sample.  q_loc = q_raw = eps_q = None is the prior-only form.  One launch each way on the
-    current stream; no CPU fallback."""
-    gauss_heads_check(q_loc, q_raw, p_loc, p_raw, eps_q, eps_p, want)
-    outs = GaussHeadsFn.apply(q_loc, q_raw, p_loc, p_raw, eps_q, eps_p, tuple(want))
-    return tuple(outs[GAUSS_HEADS_OUTPUTS.index(w)] for w in want)
-
-
-def lstm_cell_check(x, h, c, w_ih, w_hh, b_ih, b_hh):
-    """(B, I, H) of an lstm_cell call, or a ValueError naming what does not fit.  Needs no device."""
-    given = {"x": x, "h": h, "c": c, "w_ih": w_ih, "w_hh": w_hh, "b_ih": b_ih, "b_hh": b_hh}
-    for n, t in given.items():
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("lstm_cell: %s must be a tensor, got %s" % (n, type(t).__name__))
-        if t.dtype != x.dtype or t.dtype not in (torch.float32, torch.float64):
-            raise ValueError("lstm_cell: tensors are float32 (float64 on the torch route) and of one dtype; %s is %s, x %s"
-                             % (n, t.dtype, x.dtype))
-        if t.device != x.device:
-            raise ValueError("lstm_cell: %s is on %s, x on %s" % (n, t.device, x.device))
-        if not t.is_contiguous():
-            raise ValueError("lstm_cell: %s must be contiguous, got shape %s stride %s"
-                             % (n, tuple(t.shape), tuple(t.stride())))
-    if x.dim() != 2 or h.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or h.shape[1] < 1:
-        raise ValueError("lstm_cell: x is [B, I] and h [B, H] with B, I, H >= 1, got x %s, h %s"
-                         % (tuple(x.shape), tuple(h.shape)))
-    B, I, H = int(x.shape[0]), int(x.shape[1]), int(h.shape[1])
-    for n, shape in (("h", (B, H)), ("c", (B, H)), ("w_ih", (4 * H, I)), ("w_hh", (4 * H, H)), ("b_ih", (4 * H,)),
-                     ("b_hh", (4 * H,))):
-        if tuple(given[n].shape) != shape:
-            raise ValueError("lstm_cell: %s has shape %s, B = %d, I = %d, H = %d need %s"
-                             % (n, tuple(given[n].shape), B, I, H, shape))
-    return B, I, H
-
-
-# Route of lstm_cell for device tensors when RFN_LSTM_CELL is unset (DESIGN.md section 22 has the measurement it follows):
-# True = the kernels, False = the torch ops.
-LSTM_CELL_KERNEL_DEFAULT = True
-
-
-def lstm_cell_route(x):
-    """"kernel" or "torch" for an lstm_cell call on x: CPU tensors and float64 always take the torch ops; for float32
-    device tensors RFN_LSTM_CELL=0 / 1 chooses (read at every call, as RFN_UP2X_CAT is), else LSTM_CELL_KERNEL_DEFAULT"""
-    if not x.is_cuda or x.dtype != torch.float32:
-        return "torch"
-    env = os.environ.get("RFN_LSTM_CELL")
-    if env in ("0", "1"):
-        return "kernel" if env == "1" else "torch"
-    return "kernel" if LSTM_CELL_KERNEL_DEFAULT else "torch"
-
-
-def lstm_cell_torch(x, h, c, w_ih, w_hh, b_ih, b_hh):
-    """the formulas of lstm_cell as torch ops (the RFN_LSTM_CELL=0 route, and the only one for CPU tensors)"""
-    H = h.shape[1]
-    pre = torch.addmm(b_ih + b_hh, x, w_ih.t()) + torch.mm(h, w_hh.t())
-    i, f, o = torch.sigmoid(pre[:, :H]), torch.sigmoid(pre[:, H:2 * H]), torch.sigmoid(pre[:, 3 * H:])
-    g = torch.tanh(pre[:, 2 * H:3 * H])
-    c_new = f * c + i * g
-    return o * torch.tanh(c_new), c_new
-
-
-class LSTMCellFn(torch.autograd.Function):
-    """one torch.nn.LSTMCell call in one kernel each way (rfn_lstm_cell_{fwd,bwd}_f32, include/rfn_hip.h): returns
-    (h', c').  Saves x, h, c, the weights, c' and the gate activations [B, 4H]; the backward kernel gives D, g_c and the
-    bias gradient, the four matrix products of the backward are torch.mm calls."""
-
-    @staticmethod
-    def forward(ctx, x, h, c, w_ih, w_hh, b_ih, b_hh):
-        ctx.set_materialize_grads(False)  # a missing upstream arrives as None and travels as a NULL pointer
-        B, I, H = lstm_cell_check(x, h, c, w_ih, w_hh, b_ih, b_hh)
-        h_out, c_out = torch.empty_like(h), torch.empty_like(c)
-        gates = torch.empty((B, 4 * H), device=x.device, dtype=torch.float32)
-        L.call("rfn_lstm_cell_fwd_f32", L.dev(x, "x"), L.dev(h, "h"), L.dev(c, "c"), L.dev(w_ih, "w_ih"),
-               L.dev(w_hh, "w_hh"), L.dev(b_ih, "b_ih"), L.dev(b_hh, "b_hh"), L.dev(h_out), L.dev(c_out), L.dev(gates),
-               B, I, H, meta=_shell("lstm_cell_fwd", gates, 4))
-        ctx.save_for_backward(x, h, c, w_ih, w_hh, c_out, gates)
-        ctx.cfg = (B, I, H)
-        return h_out, c_out
-
-    @staticmethod
-    def backward(ctx, gh, gc):
-        x, h, c, w_ih, w_hh, c_out, gates = ctx.saved_tensors
-        if gh is None and gc is None:
-            return (None,) * 7
-        B, I, H = ctx.cfg
-        gh = None if gh is None else gh.contiguous()
-        gc = None if gc is None else gc.contiguous()
-        D, g_c, g_bias = torch.empty_like(gates), torch.empty_like(c), torch.empty(4 * H, device=x.device, dtype=torch.float32)
-        L.call("rfn_lstm_cell_bwd_f32", L.dev(gh, "gh"), L.dev(gc, "gc"), L.dev(gates), L.dev(c), L.dev(c_out), L.dev(D),
-               L.dev(g_c), L.dev(g_bias), B, H, meta=_shell("lstm_cell_bwd", gates, 3))
-        need = ctx.needs_input_grad
-        return (torch.mm(D, w_ih) if need[0] else None, torch.mm(D, w_hh) if need[1] else None,
-                g_c if need[2] else None, torch.mm(D.t(), x) if need[3] else None,
-                torch.mm(D.t(), h) if need[4] else None, g_bias if need[5] else None, g_bias if need[6] else None)
-
-
-def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh, route=None):
-    """(h', c') of torch.nn.LSTMCell with these parameters on x [B, I] and the state (h, c) [B, H]; gate order i, f, g, o.
-    route: None (lstm_cell_route decides), "kernel" (one launch each way on the current stream, float32 device tensors
-    only: anything else raises, there is no fallback) or "torch"."""
-    lstm_cell_check(x, h, c, w_ih, w_hh, b_ih, b_hh)
-    route = lstm_cell_route(x) if route is None else route
-    if route == "kernel":
-        return LSTMCellFn.apply(x, h, c, w_ih, w_hh, b_ih, b_hh)
-    if route != "torch":
-        raise ValueError("lstm_cell: route is None, 'kernel' or 'torch', got %r" % (route,))
-    return lstm_cell_torch(x, h, c, w_ih, w_hh, b_ih, b_hh)
-
-
 class ConvLSTMCellFn(torch.autograd.Function):
     """ConvLSTMLayer.forward (Utils/modules.py:355-377): conv3x3(cat(x,h))+b on the MFMA conv kernel, then the fused
     gate update.  Peephole tensors may be None (== 0)."""
@@ -1964,1184 +1773,25 @@ class ConvLSTMSeqFn(torch.autograd.Function):
         return gx_all, gh_rec, gc, gw, gb
 
 
-def _stepbn_fwd_buffers(x, gamma, beta, S, pooled=False):
-    """What a per-step BatchNorm forward (plain, synchronised or pooled) allocates for x [S*B, C, H, W]: (B, mean [S, C],
-    var [S, C], the output, the detached gamma and beta, the floats of scratch either direction needs, the scratch)."""
-    SB, C, H, W = (int(v) for v in x.shape)
-    B = SB // S
-    mean = torch.empty((S, C), device=x.device, dtype=torch.float32)
-    var = torch.empty((S, C), device=x.device, dtype=torch.float32)
-    out = torch.empty((SB, C, H // 2, W // 2), device=x.device, dtype=torch.float32) if pooled else torch.empty_like(x)
-    gm = None if gamma is None else gamma.detach().contiguous()
-    bt = None if beta is None else beta.detach().contiguous()
-    nscr = int(L.load().rfn_stepbn_scratch_floats(S, B, C))  # partial sums of the split reductions (either way)
-    acc = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-    return B, mean, var, out, gm, bt, nscr, acc
-
-
-def _stepbn_running_args(running):
-    """the running-statistics arguments of rfn_stepbn_fwd_f32 / rfn_stepbn_pool_fwd_f32 from `running` (or None)"""
-    if running is None:
-        return None, None, None, None, 1.0, None
-    rm, rv, cf, cfu, decay, nbt = running
-    if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
-        raise RuntimeError("num_batches_tracked must be an int64 device tensor")
-    return L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cfu), decay, None if nbt is None else nbt.data_ptr()
-
-
-def _stepbn_bwd_buffers(x, C, affine, nscr):
-    """what a per-step BatchNorm backward allocates: (sums, gx, ggamma, gbeta); the last two None without affine"""
-    sums = torch.empty((nscr,), device=x.device, dtype=torch.float32)
-    gx = torch.empty_like(x)
-    ggamma = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
-    gbeta = torch.empty((C,), device=x.device, dtype=torch.float32) if affine else None
-    return sums, gx, ggamma, gbeta
-
-
-class StepBatchNormActFn(torch.autograd.Function):
-    """Training-mode BatchNorm2d with per-timestep statistics on a step-major time-batched tensor [S*B, C, H, W],
-    fused with the activation that follows it (rfn_stepbn_{fwd,bwd}_f32: two launches each way).  Returns (y, mean[S, C],
-    biased var[S, C]).  act: 0 none, 1 relu, 2 leaky_relu(slope), 3 tanh.  running (optional) = (running_mean, running_var,
-    coef[S], coef_u[S], decay, num_batches_tracked or None): the S exponential-average updates of the step-wise calls,
-    applied by the same launch (r <- decay r + sum_s coef[s] stat[s]); without it the caller does them."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, S, eps, act, slope, running=None):
-        ctx.set_materialize_grads(False)  # mean / var are not differentiable: no zero gradients built for them
-        x = x.contiguous()
-        from . import dist as rdist
-        if rdist.sync_batchnorm_on():
-            return StepBatchNormActFn._forward_sync(ctx, x, gamma, beta, S, eps, act, slope, running)
-        ctx.world = 1
-        C, HW = int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])
-        B, mean, var, y, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S)
-        L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               *_stepbn_running_args(running), S, B, C, HW, eps, act, slope, meta=_shell("stepbn_fwd", x, 3))
-        ctx.save_for_backward(x, mean, var, gm, bt)
-        ctx.cfg = (S, B, C, HW, eps, act, slope, gamma is not None, nscr)
-        ctx.mark_non_differentiable(mean, var)
-        return y, mean, var
-
-    @staticmethod
-    def _forward_sync(ctx, x, gamma, beta, S, eps, act, slope, running):
-        """synchronised BatchNorm (rfn_hip.dist.sync_batchnorm_on): the statistics of every step are those of the GLOBAL
-        batch -- local moments, one all-gather of [2, S, C] floats, equal-count combination, apply with the given
-        statistics; the running statistics follow the global moments (torch ops on [C] vectors)."""
-        import torch.distributed as dist
-        from . import dist as rdist
-        C, HW = int(x.shape[1]), int(x.shape[2]) * int(x.shape[3])
-        world = dist.get_world_size()
-        B, mean, var, y, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S)
-        L.call("rfn_stepbn_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), L.dev(acc),
-               *_stepbn_running_args(None), S, B, C, HW, eps, act, slope)
-        st = rdist.all_gather_cat(torch.stack((mean, var)).unsqueeze(0))          # [world, 2, S, C]
-        mean = st[:, 0].mean(0).contiguous()
-        var = (st[:, 1].mean(0) + (st[:, 0] - mean).pow(2).mean(0)).contiguous()  # equal counts per rank
-        L.call("rfn_stepbn_apply_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(y), L.dev(mean), L.dev(var), S, B,
-               C, HW, eps, act, slope)
-        if running is not None:
-            rm, rv, cf, cfu, decay, nbt = running
-            n = B * HW * world
-            cfu_g = cf * (n / max(n - 1, 1))          # unbiased variance of the global batch
-            rm.mul_(decay).add_((cf.view(-1, 1) * mean).sum(0))
-            rv.mul_(decay).add_((cfu_g.view(-1, 1) * var).sum(0))
-            if nbt is not None:
-                nbt.add_(S)
-        ctx.save_for_backward(x, mean, var, gm, bt)
-        ctx.cfg = (S, B, C, HW, eps, act, slope, gamma is not None, nscr)
-        ctx.world = world
-        ctx.mark_non_differentiable(mean, var)
-        return y, mean, var
-
-    @staticmethod
-    def backward(ctx, g, _gm, _gv):
-        x, mean, var, gm, bt = ctx.saved_tensors
-        S, B, C, HW, eps, act, slope, affine, nscr = ctx.cfg
-        if g is None:
-            return (None,) * 8
-        g = g.contiguous()
-        sums, gx, ggamma, gbeta = _stepbn_bwd_buffers(x, C, affine, nscr)
-        args = (L.dev(x), L.dev(gm), L.dev(bt), L.dev(g), L.dev(mean), L.dev(var), L.dev(sums), L.dev(gx), L.dev(ggamma),
-                L.dev(gbeta), S, B, C, HW, eps, act, slope)
-        if ctx.world > 1:   # synchronised: partial sums, added over the ranks, apply
-            from . import dist as rdist
-            L.call("rfn_stepbn_bwd_f32", *args, 1, ctx.world)
-            rdist.all_reduce_sum_(sums)
-            L.call("rfn_stepbn_bwd_f32", *args, 2, ctx.world)
-        else:
-            L.call("rfn_stepbn_bwd_f32", *args, 0, 1)
-        return gx, ggamma, gbeta, None, None, None, None, None
-
-
-class StepBatchNormActPoolFn(torch.autograd.Function):
-    """StepBatchNormActFn followed by MaxPool2d(2, 2) (rfn_stepbn_pool_{fwd,bwd}_f32: two launches each way).  Only the
-    pooled map is written; the backward recomputes every window's winner from x, so no full-resolution activation, index
-    map or full-resolution gradient exists.  Returns (p [S*B, C, H/2, W/2], mean[S, C], biased var[S, C]); arguments as
-    StepBatchNormActFn.  H and W even; not for synchronised BatchNorm (the caller keeps the unfused route there)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, S, eps, act, slope, running=None):
-        ctx.set_materialize_grads(False)
-        x = x.contiguous()
-        C, H, W = (int(v) for v in x.shape[1:])
-        B, mean, var, p, gm, bt, nscr, acc = _stepbn_fwd_buffers(x, gamma, beta, S, pooled=True)
-        # x read by the statistics and by the apply launch, a quarter of it written
-        L.call("rfn_stepbn_pool_fwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(p), L.dev(mean), L.dev(var), L.dev(acc),
-               *_stepbn_running_args(running), S, B, C, H, W, eps, act, slope, meta=_shell("stepbn_pool_fwd", x, 2.25))
-        ctx.save_for_backward(x, mean, var, gm, bt)
-        ctx.cfg = (S, B, C, H, W, eps, act, slope, gamma is not None, nscr)
-        ctx.mark_non_differentiable(mean, var)
-        return p, mean, var
-
-    @staticmethod
-    def backward(ctx, gp, _gm, _gv):
-        x, mean, var, gm, bt = ctx.saved_tensors
-        S, B, C, H, W, eps, act, slope, affine, nscr = ctx.cfg
-        if gp is None:
-            return (None,) * 8
-        gp = gp.contiguous()
-        sums, gx, ggamma, gbeta = _stepbn_bwd_buffers(x, C, affine, nscr)
-        # x and the pooled gradient read by the reduce and by the apply launch, gx written
-        L.call("rfn_stepbn_pool_bwd_f32", L.dev(x), L.dev(gm), L.dev(bt), L.dev(gp), L.dev(mean), L.dev(var), L.dev(sums),
-               L.dev(gx), L.dev(ggamma), L.dev(gbeta), S, B, C, H, W, eps, act, slope, 0, 1,
-               meta=_shell("stepbn_pool_bwd", x, 3.5))
-        return gx, ggamma, gbeta, None, None, None, None, None
-
-
-class Up2xCatFn(torch.autograd.Function):
-    """torch.cat((nearest_up2x(x), skip), 1) in one launch (rfn_up2x_cat_f32); backward: gx = the 2x2 block sums of
-    g[:, :Cx] read in place (rfn_up2x_cat_bwd_f32), the skip's gradient is the view g[:, Cx:]."""
-
-    @staticmethod
-    def forward(ctx, x, skip):
-        N, Cx, h, w = (int(v) for v in x.shape)
-        Cs = int(skip.shape[1])
-        if tuple(skip.shape) != (N, Cs, 2 * h, 2 * w):
-            raise RuntimeError("Up2xCatFn: skip %s does not fit x %s" % (tuple(skip.shape), tuple(x.shape)))
-        dense = lambda t: all(t.shape[d] == 1 or t.stride(d) == e for d, e in
-                              ((3, 1), (2, t.shape[3]), (1, t.shape[2] * t.shape[3])))
-        x, skip = (t if dense(t) else t.contiguous() for t in (x, skip))   # channel-slice views are read in place
-        xp, xns = L.frames(x, "x")
-        sp, sns = L.frames(skip, "skip")
-        out = torch.empty((N, Cx + Cs, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
-        L.call("rfn_up2x_cat_f32", xp, xns, sp, sns, L.dev(out), N, Cx, Cs, h, w,
-               meta=_shell("up2x_cat", out, 1.0 + (0.25 * Cx + Cs) / (Cx + Cs)))
-        ctx.cfg = (N, Cx, h, w)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        N, Cx, h, w = ctx.cfg
-        g = g.contiguous()
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gp, gns = L.frames(g, "g")
-            gx = torch.empty((N, Cx, h, w), device=g.device, dtype=torch.float32)
-            L.call("rfn_up2x_cat_bwd_f32", gp, gns, L.dev(gx), N, Cx, h, w, meta=_shell("up2x_cat_bwd", gx, 5))
-        return gx, (g[:, Cx:] if ctx.needs_input_grad[1] else None)
-
-
-def bnflow_coef(steps, momentum):
-    """(coef [steps] as float64, decay) of the closed form of `steps` running-statistics updates r <- m r + (1 - m) stat_s of
-    BatchNormFlow (glow_modules.py:81-87; the momentum weights the OLD value): r <- decay r + sum_s coef[s] stat_s with
-    decay = m^S, coef[s] = (1 - m) m^(S-1-s) and 0^0 = 1.  Needs no device."""
-    m = float(momentum)
-    coef = (1.0 - m) * torch.tensor([m ** (steps - 1 - s) for s in range(steps)], dtype=torch.float64)
-    return coef, m ** steps
-
-
-class BatchNormFlowFn(torch.autograd.Function):
-    """BatchNormFlow in training mode, forward direction (glow_modules.py:76-98), on a step-major time-batched tensor
-    x [steps*B, C, H, W] with the statistics of EACH step's B rows (rfn_bnflow_{fwd,bwd}_f32, two launches each way).
-    log_gamma / beta: [1, C, H, W].  Returns (z, dl [steps]); dl[s] belongs to the log-det of every row of step s.
-    running = (running_mean, running_var, coef [steps] device tensor, decay) or None: the `steps` updates of the
-    step-wise calls, applied by the same launches in closed form (bnflow_coef)."""
-
-    @staticmethod
-    def forward(ctx, x, log_gamma, beta, steps, eps, running=None):
-        x = x.contiguous()
-        S, B = int(steps), int(x.shape[0]) // int(steps)
-        E = x[0].numel()
-        if S * B != x.shape[0] or log_gamma.numel() != E or beta.numel() != E:
-            raise RuntimeError("BatchNormFlowFn: x %s is not %d steps of rows of %d elements" % (tuple(x.shape), S, log_gamma.numel()))
-        lg, bt = _f(log_gamma), _f(beta)
-        z = torch.empty_like(x)
-        mean = torch.empty((S, E), device=x.device, dtype=torch.float32)
-        var = torch.empty((S, E), device=x.device, dtype=torch.float32)
-        dl = torch.empty((S,), device=x.device, dtype=torch.float32)
-        scr = torch.empty((int(L.load().rfn_bnflow_scratch_floats(S, B, E, 0)),), device=x.device, dtype=torch.float32)
-        rm = rv = cf = None
-        decay = 1.0
-        if running is not None:
-            rm, rv, cf, decay = running
-            if not (rm.is_contiguous() and rv.is_contiguous()) or rm.numel() != E or rv.numel() != E or cf.numel() != S:
-                raise RuntimeError("BatchNormFlowFn: running statistics must be dense [%d] tensors, coef [%d]" % (E, S))
-        L.call("rfn_bnflow_fwd_f32", L.dev(x), L.dev(lg), L.dev(bt), L.dev(z), L.dev(mean), L.dev(var), L.dev(dl),
-               L.dev(scr), L.dev(rm), L.dev(rv), L.dev(cf), L.dev(cf), decay, S, B, E,
-               eps, meta=_shell("bnflow_fwd", x, 2))
-        ctx.save_for_backward(x, lg, mean, var)
-        ctx.cfg = (S, B, E, log_gamma.shape)
-        return z, dl
-
-    @staticmethod
-    def backward(ctx, gz, gdl):
-        x, lg, mean, var = ctx.saved_tensors
-        S, B, E, pshape = ctx.cfg
-        gz = torch.zeros_like(x) if gz is None else gz.contiguous()
-        gdl = None if gdl is None else gdl.contiguous()
-        gx = torch.empty_like(x)
-        glg = torch.empty(pshape, device=x.device, dtype=torch.float32)
-        gbt = torch.empty(pshape, device=x.device, dtype=torch.float32)
-        scr = torch.empty((int(L.load().rfn_bnflow_scratch_floats(S, B, E, 1)),), device=x.device, dtype=torch.float32)
-        L.call("rfn_bnflow_bwd_f32", L.dev(x), L.dev(lg), L.dev(gz), L.dev(gdl), L.dev(mean), L.dev(var), L.dev(gx),
-               L.dev(glg), L.dev(gbt), L.dev(scr), S, B, E, meta=_shell("bnflow_bwd", x, 3))
-        return gx, glg, gbt, None, None, None
-
-
-def bnflow_apply(x, log_gamma, beta, running_mean, running_var, reverse):
-    """BatchNormFlow with GIVEN statistics (glow_modules.py:90-103: eval mode, and the reverse direction in any mode), no
-    gradient: (y, dl [1]) by rfn_bnflow_apply_f32; dl is to be ADDED to the log-det of every row (it carries the reverse
-    direction's minus sign)."""
-    x = x.detach().contiguous()
-    N, E = int(x.shape[0]), x[0].numel()
-    y = torch.empty_like(x)
-    dl = torch.empty((1,), device=x.device, dtype=torch.float32)
-    lg, bt, rm, rv = _f(log_gamma), _f(beta), _f(running_mean), _f(running_var)
-    if not (lg.numel() == bt.numel() == rm.numel() == rv.numel() == E):
-        raise RuntimeError("bnflow_apply: parameters do not match rows of %d elements" % E)
-    L.call("rfn_bnflow_apply_f32", L.dev(x), L.dev(lg), L.dev(bt), L.dev(rm), L.dev(rv), L.dev(y), L.dev(dl), N, E,
-           1 if reverse else 0, meta=_shell("bnflow_apply", x, 2))
-    return y, dl
-
-
-# ----------------------------------------------------------------------------------------------- mixture of logistics
-def mol_dims(x, l):
-    """(N, C, M, HW) of a mixture-of-discretized-logistics call, or a RuntimeError naming what does not fit.  x [N,C,H,W]
-    with C in {1, 3}; l [N,Cl,H,W] with Cl = 10 M (C = 3) or 3 M (C = 1).  Needs no device."""
-    if x.dim() != 4 or l.dim() != 4:
-        raise RuntimeError("mol: x and l must be [N,C,H,W], got %s and %s" % (tuple(x.shape), tuple(l.shape)))
-    N, C, H, W = (int(d) for d in x.shape)
-    if C not in (1, 3):
-        raise RuntimeError("mol: x must have 1 or 3 channels, got %d" % C)
-    per = 10 if C == 3 else 3
-    Cl = int(l.shape[1])
-    if (int(l.shape[0]), int(l.shape[2]), int(l.shape[3])) != (N, H, W) or Cl < per or Cl % per:
-        raise RuntimeError("mol: logits %s do not fit x %s: need [%d, %d*M, %d, %d] with M >= 1" %
-                           (tuple(l.shape), tuple(x.shape), N, per, H, W))
-    return N, C, Cl // per, H * W
-
-
-class MolNllFn(torch.autograd.Function):
-    """nll_pix [N,H,W] (reduce = 0) or its per-frame sum nll [N] (reduce = 1) of x under the mixture of discretized
-    logistics with parameters l (rfn_mol_nll_fwd / rfn_mol_nll_bwd).  Gradient into l only."""
-
-    @staticmethod
-    def forward(ctx, x, l, per_frame):
-        N, C, M, HW = mol_dims(x, l)
-        x, l = x.detach().contiguous(), l.contiguous()
-        L.dev(x, "x"), L.dev(l, "l")  # (device fp32 tensors, before anything is allocated or loaded)
-        nll_pix =torch.empty((N, x.shape[2], x.shape[3]), device=l.device, dtype=torch.float32)
-        lse = torch.empty_like(nll_pix)
-        nll = torch.empty((N,), device=l.device, dtype=torch.float32)
-        part = torch.empty((int(L.load().rfn_mol_part_floats(N, HW)),), device=l.device, dtype=torch.float32)
-        L.call("rfn_mol_nll_fwd", L.dev(x, "x"), L.dev(l, "l"), L.dev(nll_pix), L.dev(lse), L.dev(nll), L.dev(part), N, C,
-               M, HW, meta=_shell("mol_nll_fwd", l, 1))
-        ctx.save_for_backward(x, l, lse)
-        ctx.cfg = (N, C, M, HW, per_frame)
-        return nll if per_frame else nll_pix
-
-    @staticmethod
-    def backward(ctx, g):
-        x, l, lse = ctx.saved_tensors
-        N, C, M, HW, per_frame = ctx.cfg
-        g = g.contiguous()
-        dl = torch.empty_like(l)
-        L.call("rfn_mol_nll_bwd", L.dev(x), L.dev(l), L.dev(lse), L.dev(g, "grad"), 0 if per_frame else 1, L.dev(dl),
-               N, C, M, HW, meta=_shell("mol_nll_bwd", l, 2))
-        return None, dl, None
-
-
-def mol_nll(x, l, reduce="frame"):
-    """Negative log-likelihood of x [N,C,H,W] in [-1,1] under the mixture of discretized logistics l [N,Cl,H,W]:
-    reduce="pixel" -> [N,H,W], reduce="frame" -> [N], each frame's pixels summed in a fixed order (the bits of a frame do
-    not depend on the other frames of the call).  Differentiable in l; x must not require a gradient."""
-    if reduce not in ("frame", "pixel"):
-        raise ValueError("mol_nll: reduce must be 'frame' or 'pixel', got %r" % (reduce,))
-    if x.requires_grad:
-        raise RuntimeError("mol_nll: no gradient flows into x; pass x.detach()")
-    return MolNllFn.apply(x, l, reduce == "frame")
-
-
-def mol_sample(l, u_mix=None, u_x=None, generator=None, channels=None):
-    """Draw x [N,C,H,W] from the mixture l [N,Cl,H,W] (rfn_mol_sample); no gradient.  u_mix [N,H,W,M] and u_x [N,H,W,C]
-    are the reference's two uniform draws, in (1e-5, 1 - 1e-5); drawn here, in that order, from `generator` when not
-    given.  C is `channels`, else the last extent of u_x, else what Cl allows (10 M: RGB, 3 M: gray); a Cl that allows
-    both (30, 60, ...) needs one of the two."""
-    if l.dim() != 4:
-        raise RuntimeError("mol_sample: l must be [N,Cl,H,W], got %s" % (tuple(l.shape),))
-    N, Cl, H, W = (int(d) for d in l.shape)
-    C = channels
-    if C is None and u_x is not None:
-        C = int(u_x.shape[-1])
-    if C is None:
-        fits = [c for c, per in ((3, 10), (1, 3)) if Cl >= per and Cl % per == 0]
-        if len(fits) != 1:
-            raise RuntimeError("mol_sample: %d logit channels %s; pass channels=1 or 3" %
-                               (Cl, "fit both RGB and gray" if fits else "fit neither 10*M nor 3*M"))
-        C = fits[0]
-    per = 10 if C == 3 else 3
-    if C not in (1, 3) or Cl < per or Cl % per:
-        raise RuntimeError("mol_sample: %d logit channels do not fit %d colour channels (need %d*M)" % (Cl, C, per))
-    M = Cl // per
-    l = l.detach().contiguous()
-    L.dev(l, "l")
-    if u_mix is None:
-        u_mix = torch.empty((N, H, W, M), device=l.device, dtype=torch.float32).uniform_(1e-5, 1. - 1e-5, generator=generator)
-    if u_x is None:
-        u_x = torch.empty((N, H, W, C), device=l.device, dtype=torch.float32).uniform_(1e-5, 1. - 1e-5, generator=generator)
-    if tuple(u_mix.shape) != (N, H, W, M) or tuple(u_x.shape) != (N, H, W, C):
-        raise RuntimeError("mol_sample: uniforms must be [N,H,W,M] = %s and [N,H,W,C] = %s, got %s and %s" %
-                           ((N, H, W, M), (N, H, W, C), tuple(u_mix.shape), tuple(u_x.shape)))
-    u_mix, u_x = u_mix.contiguous(), u_x.contiguous()
-    out = torch.empty((N, C, H, W), device=l.device, dtype=torch.float32)
-    L.call("rfn_mol_sample", L.dev(l), L.dev(u_mix, "u_mix"), L.dev(u_x, "u_x"), L.dev(out), N, C, M,
-           H * W, meta=_shell("mol_sample", l, 1))
-    return out
-
-
-MOL_KEYED_SLOT_MIX, MOL_KEYED_SLOT_COLOUR = 16, 17   # the key's slot word (keyed_normal owns 0 .. 7)
-
-
-def _mol_channels(who, Cl, channels):
-    """(C, M) of Cl logit channels: C is `channels`, else what Cl allows (10 M: RGB, 3 M: gray)"""
-    C = channels
-    if C is None:
-        fits = [c for c, per in ((3, 10), (1, 3)) if Cl >= per and Cl % per == 0]
-        if len(fits) != 1:
-            raise RuntimeError("%s: %d logit channels %s; pass channels=1 or 3" %
-                               (who, Cl, "fit both RGB and gray" if fits else "fit neither 10*M nor 3*M"))
-        C = fits[0]
-    per = 10 if C == 3 else 3
-    if C not in (1, 3) or Cl < per or Cl % per:
-        raise RuntimeError("%s: %d logit channels do not fit %d colour channels (need %d*M)" % (who, Cl, C, per))
-    return C, Cl // per
-
-
-def _mol_keyed_address(who, rows, B, seed, step, first_seq, first_draw):
-    B, seed, step, first_seq, first_draw = (int(v) for v in (B, seed, step, first_seq, first_draw))
-    if B < 1 or rows < 1 or rows % B:
-        raise ValueError("%s: %d rows are no positive multiple of B = %d (row r*B + b is draw first_draw + r of sequence "
-                         "first_seq + b)" % (who, rows, B))
-    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
-        if not 0 <= v < 1 << 63:
-            raise ValueError("%s: %s %d not in [0, 2^63)" % (who, nm, v))
-    if not 0 <= step < 1 << 31:
-        raise ValueError("%s: step %d not in [0, 2^31)" % (who, step))
-    return B, seed, step, first_seq, first_draw
-
-
-def mol_sample_keyed(l, B, seed, step, first_seq=0, first_draw=0, channels=None):
-    """mol_sample with addressed uniforms (rfn_mol_sample_keyed; include/rfn_hip.h and DESIGN section 20 hold the
-    definition): x [rows,C,H,W] from the mixture l [rows,Cl,H,W], rows a multiple of B.  Row r*B + b is draw first_draw +
-    r of sequence first_seq + b, and a pixel's uniforms depend only on (seed, step, sequence, draw, pixel, element): the
-    same for any B, number of draws and split of the draws into calls.  No uniform tensor exists and torch's generator
-    is not touched; mol_keyed_uniforms writes the numbers out.  One launch on the current stream; no CPU fallback."""
-    if l.dim() != 4:
-        raise RuntimeError("mol_sample_keyed: l must be [rows,Cl,H,W], got %s" % (tuple(l.shape),))
-    rows, Cl, H, W = (int(d) for d in l.shape)
-    C, M = _mol_channels("mol_sample_keyed", Cl, channels)
-    B, seed, step, first_seq, first_draw = _mol_keyed_address("mol_sample_keyed", rows, B, seed, step, first_seq,
-                                                              first_draw)
-    l = l.detach().contiguous()
-    L.dev(l, "l")
-    out = torch.empty((rows, C, H, W), device=l.device, dtype=torch.float32)
-    with torch.cuda.device(l.device):
-        L.call("rfn_mol_sample_keyed", L.dev(l), L.dev(out), rows, B, C, M, H * W, seed, step, first_seq, first_draw,
-               meta=_shell("mol_sample_keyed", l, 1))
-    return out
-
-
-def mol_keyed_uniforms(shape_or_l, B, M, channels, seed, step, first_seq=0, first_draw=0, device=None):
-    """(u_mix [rows,H,W,M], u_x [rows,H,W,C]): the uniforms mol_sample_keyed uses at that address
-    (rfn_mol_keyed_uniforms), so that mol_sample(l, u_mix, u_x) replays it bit for bit.  shape_or_l: the logits (their
-    rows, H, W and device are taken) or (rows, H, W); device: where the tensors go for a shape (default: the current
-    GPU)."""
-    if isinstance(shape_or_l, torch.Tensor):
-        if shape_or_l.dim() != 4:
-            raise RuntimeError("mol_keyed_uniforms: l must be [rows,Cl,H,W], got %s" % (tuple(shape_or_l.shape),))
-        rows, _, H, W = (int(d) for d in shape_or_l.shape)
-        device = shape_or_l.device
-    else:
-        if len(shape_or_l) != 3:
-            raise ValueError("mol_keyed_uniforms: give the logits or (rows, H, W), got %s" % (tuple(shape_or_l),))
-        rows, H, W = (int(d) for d in shape_or_l)
-    M, C = int(M), int(channels)
-    if M < 1 or C not in (1, 3) or H < 1 or W < 1:
-        raise ValueError("mol_keyed_uniforms: need M >= 1, channels 1 or 3 and a non-empty frame (got M = %d, channels = "
-                         "%d, %dx%d)" % (M, C, H, W))
-    B, seed, step, first_seq, first_draw = _mol_keyed_address("mol_keyed_uniforms", rows, B, seed, step, first_seq,
-                                                              first_draw)
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("rfn_hip kernels need device tensors; mol_keyed_uniforms was asked for %s (no CPU fallback)" %
-                           device)
-    u_mix = torch.empty((rows, H, W, M), device=device, dtype=torch.float32)
-    u_x = torch.empty((rows, H, W, C), device=device, dtype=torch.float32)
-    with torch.cuda.device(device):
-        L.call("rfn_mol_keyed_uniforms", L.dev(u_mix), L.dev(u_x), rows, B, C, M, H * W, seed, step, first_seq,
-               first_draw, meta=("shell", "mol_keyed_uniforms", 0.0, "%dx%dx%d" % (rows, H * W, M + C),
-                                 4.0 * (u_mix.numel() + u_x.numel())))
-    return u_mix, u_x
-
-
-# ----------------------------------------------------------------------------------------------- evaluation metrics
-def _u8_frames(t, C, H, W):
-    """(tensor, pointer, frame stride) of a uint8 device tensor [..., C, H, W] seen as [N, C, H, W] frames (lib.dev stays
-    fp32-only): no copy when the leading dims collapse to one frame stride and every frame is dense and disjoint (e.g.
-    a channel slice), a contiguous copy otherwise (e.g. `x[:, start:]` of [B, T, C, H, W]).  Returns the tensor the
-    pointer refers to as well: the caller keeps it alive over the launch."""
-    v = t.reshape(-1, C, H, W)
-    s = v.stride()
-    dense = s[3] == 1 and s[2] == W and (s[1] == H * W or C == 1)
-    if not dense or (v.shape[0] > 1 and s[0] < C * H * W):
-        v = v.contiguous()
-    ns = v.stride(0) if v.shape[0] > 1 else C * H * W
-    return v, v.data_ptr(), int(ns)
-
-
-def frame_quality(a, b):
-    """Per-frame (mse, psnr, ssim) of two uint8 video tensors [..., C, H, W] on the GPU (rfn_frame_quality_u8: the
-    reference's Evaluator.eval_seq, error_metrics.py:154-171, with skimage 0.17.2's SSIM / PSNR defaults): float32
-    tensors over the leading shape.  mse = sum of squared differences / (C*H*W); psnr, ssim = means over channels of the
-    single-channel figures (psnr is +inf on an identical channel).  No CPU fallback."""
-    for t, nm in ((a, "a"), (b, "b")):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("frame_quality: %s must be a tensor, got %s" % (nm, type(t).__name__))
-        if t.dtype != torch.uint8:
-            raise TypeError("frame_quality: %s must be uint8, got %s" % (nm, t.dtype))
-        if t.dim() < 3:
-            raise ValueError("frame_quality: %s must be [..., C, H, W], got shape %s" % (nm, tuple(t.shape)))
-    if a.shape != b.shape:
-        raise ValueError("frame_quality: shapes differ: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
-    C, H, W = (int(d) for d in a.shape[-3:])
-    if H < 7 or W < 7:
-        raise ValueError("frame_quality: the 7x7 SSIM window exceeds the %dx%d frame" % (H, W))
-    if C < 1:
-        raise ValueError("frame_quality: frames have no channel")
-    for t, nm in ((a, "a"), (b, "b")):
-        if not t.is_cuda:
-            raise RuntimeError("rfn_hip kernels need device tensors; %s is on %s (no CPU fallback)" % (nm, t.device))
-    if a.device != b.device:
-        raise ValueError("frame_quality: a is on %s, b on %s" % (a.device, b.device))
-    lead = tuple(a.shape[:-3])
-    mse = torch.empty(lead, device=a.device, dtype=torch.float32)
-    psnr = torch.empty_like(mse)
-    ssim = torch.empty_like(mse)
-    N = mse.numel()
-    if N == 0:
-        return mse, psnr, ssim
-    av, ap, ans = _u8_frames(a, C, H, W)
-    bv, bp, bns = _u8_frames(b, C, H, W)
-    with torch.cuda.device(a.device):
-        L.call("rfn_frame_quality_u8", ap, ans, bp, bns, L.dev(mse), L.dev(psnr), L.dev(ssim), N, C,
-               H, W, meta=("shell", "frame_quality", 0.0, "x".join(str(int(d)) for d in a.shape),
-                                  2.0 * a.numel()))
-    return mse, psnr, ssim
-
-
-# ----------------------------------------------------------------------------------------------- linear-extrapolation baseline
-@functools.lru_cache(maxsize=None)
-def linext_limits():
-    """(most conditioning frames, smallest and largest frame side of gauss_quality): the library's host-only queries
-    (include/rfn_hip.h), read once; needs no device"""
-    lib = L.load()
-    return lib.rfn_linext_max_frames(), lib.rfn_gauss_quality_min_side(), lib.rfn_gauss_quality_max_side()
-
-
-def linear_extrap_pairs(n):
-    """the features of a window of n frames in the kernels' order (SimpleLinearModel.get_prediction): a list of
-    (i, j or None), frame i itself or the difference frame i - frame j; n (n + 1) / 2 entries"""
-    n = int(n)
-    if n < 1:
-        raise ValueError("linear_extrap_pairs: n must be >= 1, got %d" % n)
-    pairs = [(f, None) for f in range(n)]
-    for k in range(n - 1):
-        pairs += [(j, j + k + 1) for j in range(n - k - 1)]
-    return pairs
-
-
-def linear_extrap_check(x, W, bias, n, start=0, P=None):
-    """(B, T, CHW, F) of a linear_extrap_loss (P None) or linear_extrap_rollout call, or a ValueError naming what does
-    not fit.  Needs no device."""
-    who = "linear_extrap_loss" if P is None else "linear_extrap_rollout"
-    for nm, v in (("n", n), ("start", start)) + ((("P", P),) if P is not None else ()):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError("%s: %s must be an int, got %r" % (who, nm, v))
-    if not 1 <= n <= linext_limits()[0]:
-        raise ValueError("%s: n must be in 1..%d, got %d" % (who, linext_limits()[0], n))
-    if start < 0:
-        raise ValueError("%s: start must be >= 0, got %d" % (who, start))
-    if P is not None and P < 1:
-        raise ValueError("%s: P must be >= 1, got %d" % (who, P))
-    for nm, t in (("x", x), ("W", W), ("bias", bias)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("%s: %s must be a tensor, got %s" % (who, nm, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise ValueError("%s: %s must be float32, got %s" % (who, nm, t.dtype))
-        if t.device != x.device:
-            raise ValueError("%s: %s is on %s, x on %s" % (who, nm, t.device, x.device))
-    if x.dim() != 5 or min(x.shape) < 1:
-        raise ValueError("%s: x must be [B, T, C, H, W] with no empty dimension, got shape %s" % (who, tuple(x.shape)))
-    B, T = int(x.shape[0]), int(x.shape[1])
-    need = start + n + (1 if P is None else 0)
-    if T < need:
-        raise ValueError("%s: T = %d frames, start = %d and n = %d need T >= %d%s"
-                         % (who, T, start, n, need, " (the window and its target)" if P is None else ""))
-    F = n * (n + 1) // 2
-    if W.numel() != F:
-        raise ValueError("%s: W has %d elements (shape %s), n = %d needs F = n (n + 1) / 2 = %d"
-                         % (who, W.numel(), tuple(W.shape), n, F))
-    if bias.numel() != 1:
-        raise ValueError("%s: bias has %d elements (shape %s), 1 is needed" % (who, bias.numel(), tuple(bias.shape)))
-    CHW = int(x.shape[2]) * int(x.shape[3]) * int(x.shape[4])
-    if B >= 2 ** 31 or (P is not None and P >= 2 ** 31):
-        raise ValueError("%s: B and P must fit an int32" % who)
-    return B, T, CHW, F
-
-
-def _linext_frames(x):
-    """(tensor, sequence stride, frame stride) of x [B, T, C, H, W] for the linear-extrapolation kernels: x itself when
-    every frame is a dense block (a slice along B or T is read in place), a contiguous copy otherwise"""
-    _, T, C, H, W = x.shape
-    s = x.stride()
-    dense = (W == 1 or s[4] == 1) and (H == 1 or s[3] == W) and (C == 1 or s[2] == H * W)
-    if not dense or (T > 1 and s[1] < C * H * W) or (x.shape[0] > 1 and s[0] < (T - 1) * s[1] + C * H * W):
-        x = x.contiguous()
-        s = x.stride()
-    fs = int(s[1]) if T > 1 else C * H * W
-    ss = int(s[0]) if x.shape[0] > 1 else (T - 1) * fs + C * H * W
-    return x, ss, fs
-
-
-class LinearExtrapLossFn(torch.autograd.Function):
-    """the MSE of the one-step prediction and the gradients of its 16-odd parameters in one pass over the frames
-    (rfn_linext_train_f32, include/rfn_hip.h).  Saves the gradients; the backward scales them by the incoming scalar.
-    There is no gradient to x."""
-
-    @staticmethod
-    def forward(ctx, x, W, bias, n, start):
-        B, T, CHW, F = linear_extrap_check(x, W, bias, n, start)
-        xv, ss, fs = _linext_frames(x.detach())
-        w, b = W.detach().contiguous(), bias.detach().contiguous()
-        ptrs = (L.dev(xv, "x", check_contiguous=False), L.dev(w, "W"), L.dev(b, "bias"))   # (device tensors or an error)
-        partials = torch.empty(L.load().rfn_linext_max_blocks() * (F + 2), device=x.device, dtype=torch.float32)
-        out = torch.empty(F + 2, device=x.device, dtype=torch.float32)
-        with torch.cuda.device(x.device):
-            L.call("rfn_linext_train_f32", ptrs[0], ss, fs, start, ptrs[1], ptrs[2], L.dev(partials), partials.numel(), L.dev(out), B, T, n, CHW,
-                   meta=("shell", "linext_train", 0.0, "x".join(str(int(d)) for d in x.shape), 4.0 * B * (n + 1) * CHW))
-        ctx.save_for_backward(out)
-        ctx.shapes = (tuple(W.shape), tuple(bias.shape), F)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (out,) = ctx.saved_tensors
-        w_shape, b_shape, F = ctx.shapes
-        need = ctx.needs_input_grad
-        scaled = out[1:] * g    # one fp32 multiply per gradient
-        return (None, scaled[:F].reshape(w_shape) if need[1] else None,
-                scaled[F:].reshape(b_shape) if need[2] else None, None, None)
-
-
-def linear_extrap_loss(x, W, bias, n, start=0):
-    """MSE (mean over B*C*H*W) between the linear-extrapolation prediction from frames start .. start+n-1 of x
-    [B, T, C, H, W] and frame start+n, differentiable in W [F] (any shape of F elements) and bias (one element).  Two
-    launches on the current stream (the pass over the frames and the fixed-order sum of its partials); no CPU fallback."""
-    linear_extrap_check(x, W, bias, n, start)
-    return LinearExtrapLossFn.apply(x, W, bias, n, start)
-
-
-def linear_extrap_rollout(x, W, bias, n, P, start=0):
-    """[B, P, C, H, W]: P frames predicted autoregressively from the window x[:, start:start+n], each prediction
-    replacing the window's oldest frame (SimpleLinearModel.sample; P = 1 is get_prediction).  No clamping, no gradient.
-    One launch on the current stream; no CPU fallback."""
-    B, T, CHW, _ = linear_extrap_check(x, W, bias, n, start, P)
-    xv, ss, fs = _linext_frames(x.detach())
-    w, b = W.detach().contiguous(), bias.detach().contiguous()
-    ptrs = (L.dev(xv, "x", check_contiguous=False), L.dev(w, "W"), L.dev(b, "bias"))   # (device tensors or an error)
-    out = torch.empty((B, P) + tuple(x.shape[2:]), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        L.call("rfn_linext_rollout_f32", ptrs[0], ss, fs, start, ptrs[1], ptrs[2], L.dev(out), B, T, n, P, CHW,
-               meta=("shell", "linext_rollout", 0.0, "x".join(str(int(d)) for d in out.shape), 4.0 * B * (n + P) * CHW))
-    return out
-
-
-def gauss_quality_check(pred, true, scale=255.0, lo=0.0, hi=255.0):
-    """(N, C, H, W) of a gauss_quality call, or a ValueError naming what does not fit.  Needs no device."""
-    for nm, t in (("pred", pred), ("true", true)):
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("gauss_quality: %s must be a tensor, got %s" % (nm, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise ValueError("gauss_quality: %s must be float32, got %s" % (nm, t.dtype))
-        if t.dim() != 4 or min(t.shape) < 1:
-            raise ValueError("gauss_quality: %s must be [N, C, H, W] with no empty dimension, got shape %s"
-                             % (nm, tuple(t.shape)))
-    if tuple(pred.shape) != tuple(true.shape):
-        raise ValueError("gauss_quality: shapes differ: pred %s, true %s" % (tuple(pred.shape), tuple(true.shape)))
-    if pred.device != true.device:
-        raise ValueError("gauss_quality: pred is on %s, true on %s" % (pred.device, true.device))
-    N, C, H, W = (int(d) for d in pred.shape)
-    _, side_min, side_max = linext_limits()
-    for nm, v in (("H", H), ("W", W)):
-        if not side_min <= v <= side_max:
-            raise ValueError("gauss_quality: %s = %d, frames of %d..%d rows and columns are supported (the 11-tap window "
-                             "needs 11; the kernel holds rows of at most 128)"
-                             % (nm, v, side_min, side_max))
-    scale, lo, hi = float(scale), float(lo), float(hi)
-    if not (scale == scale and lo <= hi):
-        raise ValueError("gauss_quality: scale must be a number and lo <= hi, got scale %r, lo %r, hi %r" % (scale, lo, hi))
-    return N, C, H, W
-
-
-def gauss_quality(pred, true, scale=255.0, lo=0.0, hi=255.0):
-    """(ssim [N], psnr [N], mse [N]) of float32 frames [N, C, H, W], each read once as clamp(v * scale, lo, hi) (no
-    scaled copy is written): ssim is pytorch_msssim.ssim(X, Y, data_range=255) per image (11-tap Gaussian window,
-    sigma 1.5, no padding; DESIGN.md section 26 states it), mse the mean squared difference over C*H*W,
-    psnr = 10 log10(255^2 / mse), +inf where mse == 0.  The data range of ssim and psnr is 255 whatever the scale.  One
-    launch on the current stream; no CPU fallback."""
-    N, C, H, W = gauss_quality_check(pred, true, scale, lo, hi)
-    p, t = pred.detach().contiguous(), true.detach().contiguous()
-    ptrs = (L.dev(p, "pred"), L.dev(t, "true"))   # (device tensors or an error)
-    ssim = torch.empty(N, device=pred.device, dtype=torch.float32)
-    mse = torch.empty_like(ssim)
-    with torch.cuda.device(pred.device):
-        L.call("rfn_gauss_quality_f32", ptrs[0], ptrs[1], L.dev(ssim), L.dev(mse), N, C, H, W,
-               float(scale), float(lo), float(hi),
-               meta=("shell", "gauss_quality", 0.0, "x".join(str(int(d)) for d in pred.shape), 8.0 * pred.numel()))
-    psnr = 10.0 * torch.log10(255.0 ** 2 / mse)   # (+inf at mse == 0: IEEE division)
-    return ssim, psnr, mse
-
-
-def _moving_mnist_args(fn, digits, B, T, C, S, num_digits, step_length, seed, split, first_id):
-    """the argument checks the two Moving MNIST renderers share; returns the contiguous digits and the integers"""
-    if not isinstance(digits, torch.Tensor) or digits.dtype != torch.uint8:
-        raise TypeError("%s: digits must be a uint8 tensor, got %s" %
-                        (fn, digits.dtype if isinstance(digits, torch.Tensor) else type(digits).__name__))
-    if digits.dim() != 3 or tuple(digits.shape[1:]) != (28, 28) or digits.shape[0] < 1:
-        raise ValueError("%s: digits must be [N >= 1, 28, 28], got %s" % (fn, tuple(digits.shape),))
-    if not digits.is_cuda:
-        raise RuntimeError("rfn_hip kernels need device tensors; digits is on %s (no CPU fallback)" % digits.device)
-    B, T, C, S, nd, L_, seed, split, first_id = (int(v) for v in (B, T, C, S, num_digits, step_length, seed, split,
-                                                                  first_id))
-    if B < 0 or T < 1 or C < 1:
-        raise ValueError("%s: need B >= 0, T >= 1, C >= 1 (got %d, %d, %d)" % (fn, B, T, C))
-    if not 28 < S <= 4096:
-        raise ValueError("%s: image size %d must exceed the digit size 28 (and be <= 4096)" % (fn, S))
-    if not 1 <= nd <= 8:
-        raise ValueError("%s: num_digits %d not in [1, 8]" % (fn, nd))
-    if not 1 <= L_ <= 1 << 20:
-        raise ValueError("%s: step_length %d must be >= 1" % (fn, L_))
-    for v, nm in ((seed, "seed"), (split, "split"), (first_id, "first_id")):
-        if not 0 <= v < 1 << 63:
-            raise ValueError("%s: %s %d not in [0, 2^63)" % (fn, nm, v))
-    if B * T > 0x7fffffff:
-        raise ValueError("%s: B * T = %d frames exceed one launch" % (fn, B * T))
-    return digits.contiguous(), B, T, C, S, nd, L_, seed, split, first_id
-
-
-def moving_mnist_render(digits, B, T, C, S, num_digits, step_length, deterministic, seed, split, first_id,
-                        trajectories=False):
-    """Stochastic Moving MNIST batch rendered on the GPU (rfn_moving_mnist_render_f32: the reference's
-    MovingMNIST.__getitem__, stochasticMovingMnist.py:48-127, with addressed random draws): a fresh float32 tensor
-    [B, T, C, S, S] in [0, 1] on the digits' device, sequence b having the id first_id + b; with trajectories=True also
-    the int64 [B, num_digits, T, 3] (digit index, y, x) of every digit and frame.  `digits`: uint8 [N, 28, 28] device
-    table.  One launch on the current stream; no CPU fallback."""
-    digits, B, T, C, S, nd, L_, seed, split, first_id = _moving_mnist_args(
-        "moving_mnist_render", digits, B, T, C, S, num_digits, step_length, seed, split, first_id)
-    out = torch.empty((B, T, C, S, S), device=digits.device, dtype=torch.float32)
-    traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
-    if B:
-        with torch.cuda.device(digits.device):
-            L.call("rfn_moving_mnist_render_f32", digits.data_ptr(), int(digits.shape[0]),
-                   L.dev(out), traj.data_ptr() if traj is not None else None, B, T, C,
-                   S, nd, L_, 1 if deterministic else 0, seed, split, first_id,
-                   meta=("shell", "moving_mnist", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
-    return (out, traj) if trajectories else out
-
-
-def moving_mnist_sync_render(digits, B, T, C, S, num_digits, step_length, deterministic, seed, split, first_id,
-                             trajectories=False, hits=False):
-    """Synchronized Moving MNIST batch (rfn_moving_mnist_sync_render_f32: the reference's MovingMNIST_synchronized,
-    stochasticMovingMnist.py:131-248): moving_mnist_render's arguments and outputs, but all sequences share one
-    trajectory per digit (start position drawn, velocity (3, 3), the bounces with step_length / deterministic) and only
-    the digit identities depend on the sequence id.  With hits=True also the int32 [B, T] hit table: the largest
-    n + 1 over the digits clamped at a wall on frame t, 0 if none (every row the same).  Returns out, or the tuple
-    (out[, traj][, hit]).  One launch on the current stream; no CPU fallback."""
-    digits, B, T, C, S, nd, L_, seed, split, first_id = _moving_mnist_args(
-        "moving_mnist_sync_render", digits, B, T, C, S, num_digits, step_length, seed, split, first_id)
-    out = torch.empty((B, T, C, S, S), device=digits.device, dtype=torch.float32)
-    traj = torch.empty((B, nd, T, 3), device=digits.device, dtype=torch.int64) if trajectories else None
-    hit = torch.empty((B, T), device=digits.device, dtype=torch.int32) if hits else None
-    if B:
-        with torch.cuda.device(digits.device):
-            L.call("rfn_moving_mnist_sync_render_f32", digits.data_ptr(), int(digits.shape[0]),
-                   L.dev(out), traj.data_ptr() if traj is not None else None,
-                   hit.data_ptr() if hit is not None else 0, B, T, C,
-                   S, nd, L_, 1 if deterministic else 0, seed, split, first_id,
-                   meta=("shell", "moving_mnist_sync", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, S, S), 4.0 * out.numel()))
-    extra = tuple(v for v in (traj, hit) if v is not None)
-    return (out,) + extra if extra else out
-
-
-def _clip_gather_args(fn, store, first, T, C):
-    """the argument checks the two clip gathers share; returns the contiguous tensors and the integers"""
-    for t, nm, dt in ((store, "store", torch.uint8), (first, "first", torch.int64)):
-        if not isinstance(t, torch.Tensor) or t.dtype != dt:
-            raise TypeError("%s: %s must be a %s tensor, got %s" %
-                            (fn, nm, str(dt).replace("torch.", ""),
-                             t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
-    if store.dim() != 4 or min(int(d) for d in store.shape[1:3]) < 1:
-        raise ValueError("%s: store must be [F, H >= 1, W >= 1, Cs], got %s" % (fn, tuple(store.shape),))
-    if first.dim() != 1:
-        raise ValueError("%s: first must be [B], got %s" % (fn, tuple(first.shape),))
-    F, H, W, Cs = (int(d) for d in store.shape)
-    B, T, C = int(first.shape[0]), int(T), int(C)
-    if T < 1:
-        raise ValueError("%s: need T >= 1, got %d" % (fn, T))
-    if (C, Cs) not in ((1, 1), (3, 1), (3, 3)):
-        raise ValueError("%s: %d output channels from %d stored ones (C == Cs in {1, 3}, or 3 copies of 1)" %
-                         (fn, C, Cs))
-    for t, nm in ((store, "store"), (first, "first")):
-        if not t.is_cuda:
-            raise ValueError("%s: %s is on %s; the kernel needs device tensors (no CPU fallback)" % (fn, nm, t.device))
-    if store.device != first.device:
-        raise ValueError("%s: store is on %s, first on %s" % (fn, store.device, first.device))
-    if B and F < 1:
-        raise ValueError("%s: the store holds no frame" % fn)
-    chunks = -(-H * W // 1024)
-    if H * W > 0x7fffffff // 4 or B * T * chunks > 0x7fffffff:
-        raise ValueError("%s: %d clips of %d frames of %dx%d exceed one launch" % (fn, B, T, H, W))
-    return store.contiguous(), first.contiguous(), F, H, W, Cs, B, T, C
-
-
-def clip_gather(store, first, T, C):
-    """Clips of a device-resident frame store as one float32 batch (rfn_clip_gather_u8_f32: what the reference's
-    PushDataset / KTH __getitem__ and the DataLoader's collation produce, bair_push.py:66-109, kth.py:34-65,
-    trainer.py:132-161): a fresh [B, T, C, H, W] tensor on the store's device, clip b being frames first[b] ..
-    first[b] + T - 1 as float32(byte) / 255.  `store`: uint8 [F, H, W, Cs] device tensor, Cs in {1, 3}; `first`: int64
-    [B] on the same device; C == Cs, or C == 3 copies of a one-channel store.  A clip that would leave the store is
-    NaN (nothing is read).  One launch on the current stream; no CPU fallback."""
-    store, first, F, H, W, Cs, B, T, C = _clip_gather_args("clip_gather", store, first, T, C)
-    out = torch.empty((B, T, C, H, W), device=store.device, dtype=torch.float32)
-    if B:
-        with torch.cuda.device(store.device):
-            L.call("rfn_clip_gather_u8_f32", store.data_ptr(), F, first.data_ptr(), L.dev(out), B, T, C, Cs, H, W,
-                   meta=("shell", "clip_gather", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, H, W),
-                         4.0 * out.numel() + float(B * T * H * W * Cs)))
-    return out
-
-
-CLIP_MIRROR, CLIP_REVERSE = 1, 2   # the bits of clip_gather_aug's flags
-
-
-def clip_gather_aug(store, first, T, C, step=1, flags=None):
-    """clip_gather with a temporal stride and per-clip augmentations (rfn_clip_gather_aug_u8_f32): clip b is the T
-    frames first[b], first[b] + step, ...; `flags`: None, or int32 [B] on the store's device, bit 0 (CLIP_MIRROR)
-    mirrors the clip's frames in x, bit 1 (CLIP_REVERSE) reverses its frames in time, other bits are ignored.  A clip
-    with first[b] < 0 or first[b] + (T - 1) * step + 1 > F is NaN (nothing is read).  With step 1 and no flags the
-    result is clip_gather's bit for bit.  One launch on the current stream; no CPU fallback."""
-    store, first, F, H, W, Cs, B, T, C = _clip_gather_args("clip_gather_aug", store, first, T, C)
-    if isinstance(step, bool) or not isinstance(step, int) or not 1 <= step <= 0x7fffffff:
-        raise ValueError("clip_gather_aug: step must be an int in [1, 2^31), got %r" % (step,))
-    if flags is not None:
-        if not isinstance(flags, torch.Tensor) or flags.dtype != torch.int32:
-            raise TypeError("clip_gather_aug: flags must be an int32 tensor, got %s" %
-                            (flags.dtype if isinstance(flags, torch.Tensor) else type(flags).__name__))
-        if tuple(flags.shape) != (B,):
-            raise ValueError("clip_gather_aug: flags must be [%d], got %s" % (B, tuple(flags.shape)))
-        if flags.device != store.device:
-            raise ValueError("clip_gather_aug: store is on %s, flags on %s (no CPU fallback)" %
-                             (store.device, flags.device))
-        flags = flags.contiguous()
-    out = torch.empty((B, T, C, H, W), device=store.device, dtype=torch.float32)
-    if B:
-        with torch.cuda.device(store.device):
-            L.call("rfn_clip_gather_aug_u8_f32", store.data_ptr(), F, first.data_ptr(),
-                   flags.data_ptr() if flags is not None else None, L.dev(out), B, T, C, Cs, H, W, step,
-                   meta=("shell", "clip_gather_aug", 0.0, "%dx%dx%dx%dx%d" % (B, T, C, H, W),
-                         4.0 * out.numel() + float(B * T * H * W * Cs)))
-    return out
-
-
-RESIZE_MAX_SIDE = 32768   # rfn_frames_resize_u8's largest source or target side
-
-
-def resize_window(Hs, Ws, H, W, mode="crop"):
-    """the crop window (y0, x0, Hc, Wc) of an Hs x Ws frame for frames_resize to H x W: "stretch" is the whole frame,
-    "crop" the largest centred window of the target's aspect ratio (the longer side is cut; integer floor)."""
-    Hs, Ws, H, W = int(Hs), int(Ws), int(H), int(W)
-    if min(Hs, Ws, H, W) < 1:
-        raise ValueError("resize_window: sizes must be >= 1, got %dx%d -> %dx%d" % (Hs, Ws, H, W))
-    if mode == "stretch":
-        return 0, 0, Hs, Ws
-    if mode != "crop":
-        raise ValueError("resize_window: mode must be 'crop' or 'stretch', got %r" % (mode,))
-    if Ws * H >= Hs * W:
-        Hc, Wc = Hs, max(1, Hs * W // H)
-    else:
-        Hc, Wc = max(1, Ws * H // W), Ws
-    return (Hs - Hc) // 2, (Ws - Wc) // 2, Hc, Wc
-
-
-def frames_resize(src, H, W, Cd, window=None):
-    """Frames resampled into another geometry on the GPU (rfn_frames_resize_u8; include/rfn_hip.h states the
-    arithmetic): `src` uint8 [F, Hs, Ws, Cs] device tensor, Cs in {1, 3}; returns a fresh uint8 [F, H, W, Cd], Cd in
-    {1, 3}, the exact integer area mean (rounded half up) of `window` = (y0, x0, Hc, Wc) of every frame (default: the
-    whole frame), then 3 -> 1 channels by the integer luma weights or 1 -> 3 by copies.  One launch on the current
-    stream; no CPU fallback."""
-    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
-        raise TypeError("frames_resize: src must be a uint8 tensor, got %s" %
-                        (src.dtype if isinstance(src, torch.Tensor) else type(src).__name__))
-    if src.dim() != 4:
-        raise ValueError("frames_resize: src must be [F, Hs, Ws, Cs], got %s" % (tuple(src.shape),))
-    F, Hs, Ws, Cs = (int(d) for d in src.shape)
-    H, W, Cd = int(H), int(W), int(Cd)
-    if not (1 <= Hs <= RESIZE_MAX_SIDE and 1 <= Ws <= RESIZE_MAX_SIDE and 1 <= H <= RESIZE_MAX_SIDE and
-            1 <= W <= RESIZE_MAX_SIDE):
-        raise ValueError("frames_resize: sides must be in [1, %d], got %dx%d -> %dx%d" % (RESIZE_MAX_SIDE, Hs, Ws, H, W))
-    if Cs not in (1, 3) or Cd not in (1, 3):
-        raise ValueError("frames_resize: 1 or 3 channels on either side, got %d -> %d" % (Cs, Cd))
-    y0, x0, Hc, Wc = (int(v) for v in (window if window is not None else (0, 0, Hs, Ws)))
-    if Hc < 1 or Wc < 1 or y0 < 0 or x0 < 0 or y0 + Hc > Hs or x0 + Wc > Ws:
-        raise ValueError("frames_resize: the window (y0 %d, x0 %d, %dx%d) is empty or leaves the %dx%d frame" %
-                         (y0, x0, Hc, Wc, Hs, Ws))
-    if not src.is_cuda:
-        raise ValueError("frames_resize: src is on %s; the kernel needs device tensors (no CPU fallback)" % (src.device,))
-    bands = -(-H // min(H, max(1, 256 // min(W, 256))))
-    if F * bands > 0x7fffffff:
-        raise ValueError("frames_resize: %d frames of %dx%d exceed one launch" % (F, H, W))
-    src = src.contiguous()
-    out = torch.empty((F, H, W, Cd), device=src.device, dtype=torch.uint8)
-    if F:
-        with torch.cuda.device(src.device):
-            L.call("rfn_frames_resize_u8", src.data_ptr(), out.data_ptr(), F, Hs, Ws, Cs, H, W, Cd, y0, x0, Hc, Wc,
-                   meta=("shell", "frames_resize", 0.0, "%dx%dx%dx%d>%dx%dx%d" % (F, Hs, Ws, Cs, H, W, Cd),
-                         float(F * (Hc * Wc * Cs + H * W * Cd))))
-    return out
-
-
-KEYED_NORMAL_MAX_SLOTS = 8
-
-
-def keyed_normal_tiled_row(k, r, b, n_draws, B):
-    """the row of tile k, draw r (local to the call), sequence b (local to the batch) in a tensor of keyed_normal(...,
-    tiles=K): tile-major, then draw-major.  It holds what row r*B + b holds with tiles = 1.  The batch of a
-    temperature sweep (RFN.predict_draws(temperatures=...)) has the same layout, k being the temperature."""
-    return (k * n_draws + r) * B + b
-
-
-def keyed_normal(shapes, B, n_draws, seed, step, first_seq=0, first_draw=0, out=None, device=None, tiles=1):
-    """Addressed N(0,1) noise (rfn_keyed_normal_f32; include/rfn_hip.h and DESIGN section 16 hold the definition): a list
-    of float32 tensors [n_draws*B, *shape_j], slot j being the list position (at most 8).  Row r*B + b of every tensor
-    stands for draw first_draw + r of sequence first_seq + b, and a value depends only on (seed, step, slot, sequence,
-    draw, position in the row): the same on any grid, for any B, n_draws and split of the draws into calls.  An entry
-    None of `shapes` skips that slot (None in the result).  out: tensors to fill in place instead of fresh ones (None
-    where the slot is skipped), each contiguous float32 of n_draws*B rows on one device; with out, `shapes` may be None.
-    device: where fresh tensors go (default: the current GPU).  One launch on the current stream; no CPU fallback.
-    tiles = K > 1 (rfn_keyed_normal_tiled_f32): every tensor has K*n_draws*B rows and row (k*n_draws + r)*B + b holds
-    exactly what row r*B + b holds with tiles = 1, for every k (the blocks of a temperature sweep share their noise);
-    still one launch.  tiles = 1 is the untiled entry point."""
-    B, n_draws, seed, step, first_seq, first_draw = (int(v) for v in (B, n_draws, seed, step, first_seq, first_draw))
-    if isinstance(tiles, bool) or not isinstance(tiles, int):
-        raise TypeError("keyed_normal: tiles must be an int, got %s" % type(tiles).__name__)
-    if tiles < 1:
-        raise ValueError("keyed_normal: tiles must be at least 1, got %d" % tiles)
-    if B < 1 or n_draws < 0:
-        raise ValueError("keyed_normal: need B >= 1 and n_draws >= 0 (got %d, %d)" % (B, n_draws))
-    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
-        if not 0 <= v < 1 << 63:
-            raise ValueError("keyed_normal: %s %d not in [0, 2^63)" % (nm, v))
-    if not 0 <= step < 1 << 31:
-        raise ValueError("keyed_normal: step %d not in [0, 2^31)" % step)
-    tile_rows = n_draws * B          # the rows that are computed; every tensor holds them `tiles` times
-    rows = tiles * tile_rows
-    if rows > 0x7fffffff:
-        raise ValueError("keyed_normal: %d rows exceed one launch" % rows)
-    if out is None:
-        if shapes is None:
-            raise TypeError("keyed_normal: give shapes or out")
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("rfn_hip kernels need device tensors; keyed_normal was asked for %s (no CPU fallback)" %
-                               device)
-        out = [None if sh is None else torch.empty((rows,) + tuple(int(d) for d in sh), device=device,
-                                                   dtype=torch.float32) for sh in shapes]
-    else:
-        out = list(out)
-        if shapes is not None and len(shapes) != len(out):
-            raise ValueError("keyed_normal: %d shapes for %d out tensors" % (len(shapes), len(out)))
-        for j, t in enumerate(out):
-            if t is None:
-                continue
-            if not isinstance(t, torch.Tensor):
-                raise TypeError("keyed_normal: out[%d] must be a tensor, got %s" % (j, type(t).__name__))
-            if t.dim() < 1 or int(t.shape[0]) != rows:
-                raise ValueError("keyed_normal: out[%d] must have %d rows, got shape %s" % (j, rows, tuple(t.shape)))
-            if shapes is not None and shapes[j] is not None and tuple(t.shape[1:]) != tuple(int(d) for d in shapes[j]):
-                raise ValueError("keyed_normal: out[%d] has rows %s, shapes[%d] is %s" %
-                                 (j, tuple(t.shape[1:]), j, tuple(shapes[j])))
-    if not 1 <= len(out) <= KEYED_NORMAL_MAX_SLOTS:
-        raise ValueError("keyed_normal: %d slots, one launch fills 1 to %d" % (len(out), KEYED_NORMAL_MAX_SLOTS))
-    live = [t for t in out if t is not None]
-    for t in live:
-        if t.device != live[0].device:
-            raise ValueError("keyed_normal: the tensors are on %s and %s" % (live[0].device, t.device))
-    ptrs = (ctypes.c_void_p * len(out))()
-    numels = (ctypes.c_int * len(out))()
-    total = 0
-    for j, t in enumerate(out):
-        if t is None or rows == 0:
-            continue
-        n = t.numel() // rows
-        if n > 0x7fffffff:
-            raise ValueError("keyed_normal: rows of %d values exceed one launch" % n)
-        if n:
-            ptrs[j] = L.dev(t, "out[%d]" % j).value
-        numels[j] = n
-        total += t.numel()
-    if total:
-        with torch.cuda.device(live[0].device):
-            if tiles == 1:
-                L.call("rfn_keyed_normal_f32", ptrs, numels, len(out), rows, B, seed, step, first_seq, first_draw,
-                       meta=("shell", "keyed_normal", 0.0, "%dx%d" % (rows, total // rows), 4.0 * total))
-            else:
-                L.call("rfn_keyed_normal_tiled_f32", ptrs, numels, len(out), tile_rows, B, tiles, seed, step, first_seq,
-                       first_draw,
-                       meta=("shell", "keyed_normal", 0.0, "%dx%dx%d" % (tiles, tile_rows, total // rows), 4.0 * total))
-    return out
-
-
-KEYED_UNIFORM_SLOT_DEQUANT = 24   # the dequantisation noise of RFN.iw_log_weights (keyed_normal: 0 .. 7, mol: 16, 17)
-
-
-def keyed_uniform(shape, B, n_draws, seed, first_step, n_steps=1, slot=KEYED_UNIFORM_SLOT_DEQUANT, scale=1.0, first_seq=0,
-                  first_draw=0, device=None, out=None):
-    """Addressed uniform noise in [0, scale) (rfn_keyed_uniform_f32; include/rfn_hip.h and DESIGN section 24 hold the
-    definition): a float32 tensor [n_steps, n_draws*B, *shape].  Step-block s stands for step first_step + s, row r*B + b
-    of every block for draw first_draw + r of sequence first_seq + b, and a value depends only on (seed, step, slot,
-    sequence, draw, position in the row): the same on any grid, for any B, n_draws, n_steps and split into calls.  slot
-    in [8, 2^31): keyed_normal owns the slots below.  out: a contiguous float32 tensor of that shape to fill in place
-    instead of a fresh one (`shape` may then be None); device: where a fresh tensor goes (default: the current GPU).
-    One launch on the current stream for all steps; torch's generators are not touched; no CPU fallback."""
-    B, n_draws, seed, first_step, n_steps, first_seq, first_draw = (int(v) for v in (B, n_draws, seed, first_step, n_steps,
-                                                                                  first_seq, first_draw))
-    if isinstance(slot, bool) or not isinstance(slot, int):
-        raise TypeError("keyed_uniform: slot must be an int, got %s" % type(slot).__name__)
-    scale = float(scale)
-    if B < 1 or n_draws < 0 or n_steps < 0:
-        raise ValueError("keyed_uniform: need B >= 1, n_draws >= 0 and n_steps >= 0 (got %d, %d, %d)" %
-                         (B, n_draws, n_steps))
-    for v, nm in ((seed, "seed"), (first_seq, "first_seq"), (first_draw, "first_draw")):
-        if not 0 <= v < 1 << 63:
-            raise ValueError("keyed_uniform: %s %d not in [0, 2^63)" % (nm, v))
-    if first_step < 0 or first_step + n_steps > 1 << 31:
-        raise ValueError("keyed_uniform: steps %d .. %d not in [0, 2^31)" % (first_step, first_step + n_steps - 1))
-    if not 8 <= slot < 1 << 31:
-        raise ValueError("keyed_uniform: slot %d not in [8, 2^31) (keyed_normal owns slots 0 .. 7)" % slot)
-    if not 0.0 < scale < float("inf"):
-        raise ValueError("keyed_uniform: scale must be finite and positive, got %r" % scale)
-    rows = n_draws * B
-    if rows > 0x7fffffff:
-        raise ValueError("keyed_uniform: %d rows exceed one launch" % rows)
-    if out is None:
-        if shape is None:
-            raise TypeError("keyed_uniform: give shape or out")
-        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("rfn_hip kernels need device tensors; keyed_uniform was asked for %s (no CPU fallback)" %
-                               device)
-        out = torch.empty((n_steps, rows) + tuple(int(d) for d in shape), device=device, dtype=torch.float32)
-    else:
-        if not isinstance(out, torch.Tensor):
-            raise TypeError("keyed_uniform: out must be a tensor, got %s" % type(out).__name__)
-        if out.dim() < 2 or tuple(out.shape[:2]) != (n_steps, rows):
-            raise ValueError("keyed_uniform: out must be [%d, %d, ...], got shape %s" % (n_steps, rows, tuple(out.shape)))
-        if shape is not None and tuple(out.shape[2:]) != tuple(int(d) for d in shape):
-            raise ValueError("keyed_uniform: out has rows %s, shape is %s" % (tuple(out.shape[2:]), tuple(shape)))
-    total = out.numel()
-    if total:
-        numel = total // (n_steps * rows)
-        if numel > 0x7fffffff or -(-numel // 8) * rows * n_steps > 0x7fffffff * 256:
-            raise ValueError("keyed_uniform: %d steps of %d rows of %d values exceed one launch" % (n_steps, rows, numel))
-        ptr = L.dev(out, "out")
-        with torch.cuda.device(out.device):
-            L.call("rfn_keyed_uniform_f32", ptr, n_steps, rows, B, numel, scale, seed, first_step, slot,
-                   first_seq, first_draw,
-                   meta=("shell", "keyed_uniform", 0.0, "%dx%dx%d" % (n_steps, rows, numel), 4.0 * total))
-    return out
-
-
-SHEET_MAX_ROWS = L.CONSTANTS["RFN_SHEET_MAX_ROWS"]   # the row descriptors travel in the launch's arguments
-
-
-def sheet_shape(n_rows, n_cols, H, W, gutter):
-    """(Hs, Ws) of a sheet of n_rows x n_cols cells of H x W pixels with `gutter` pixels between and around them"""
-    return n_rows * H + (n_rows + 1) * gutter, n_cols * W + (n_cols + 1) * gutter
-
-
-def compose_sheet(rows, n_cols, gutter=2, bg=255, n_bits=8, preprocess_range="0.5", scanlines=False, out=None):
-    """A sheet of frames as 8-bit RGB pixels (rfn_sheet_compose_u8: the subplot grids of the reference's plotter and
-    Evaluator.plot_samples, trainer.py:325-417, error_metrics.py:128-152, as pixels only).  `rows`: a list of device
-    tensors [n, C, H, W], n <= n_cols, fp32 in model space or uint8, each with dense CHW frames and any stride along n
-    (pass views such as image[0] of [B, T, C, H, W] or samples[:, 0] of [T, B, C, H, W]: nothing is copied).  Row r fills
-    the first n cells of sheet row r, the rest is background `bg`; cells are `gutter` pixels apart.  fp32 frames become
-    bytes exactly as Solver.preprocess(x, reverse=True) with this n_bits / preprocess_range makes them; uint8 frames are
-    copied; C == 1 is written to R, G and B.  Returns uint8 [Hs, Ws, 3], or with scanlines=True [Hs, 1 + 3*Ws] whose
-    lines start with the PNG filter byte 0 (Utils.png.write_png takes either); `out` (optional) is a contiguous uint8
-    tensor of that shape on the rows' device to write into, at any byte address.  One launch on the current stream; no
-    CPU fallback."""
-    if not isinstance(rows, (list, tuple)) or not rows:
-        raise TypeError("compose_sheet: rows must be a non-empty list of tensors, got %s" % type(rows).__name__)
-    for r, t in enumerate(rows):
-        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8):
-            raise TypeError("compose_sheet: row %d must be a float32 or uint8 tensor, got %s" %
-                            (r, t.dtype if isinstance(t, torch.Tensor) else type(t).__name__))
-        if t.dim() != 4:
-            raise ValueError("compose_sheet: row %d must be [n, C, H, W], got %s" % (r, tuple(t.shape)))
-    n_cols, gutter, bg, n_bits = int(n_cols), int(gutter), int(bg), int(n_bits)
-    C, H, W = (int(d) for d in rows[0].shape[1:])
-    if C not in (1, 3) or H < 1 or W < 1:
-        raise ValueError("compose_sheet: frames must be [C in {1, 3}, H >= 1, W >= 1], got %s" % ((C, H, W),))
-    for r, t in enumerate(rows):
-        if tuple(t.shape[1:]) != (C, H, W):
-            raise ValueError("compose_sheet: row %d has frames %s, row 0 has %s" % (r, tuple(t.shape[1:]), (C, H, W)))
-        s = t.stride()
-        if not ((W == 1 or s[3] == 1) and (H == 1 or s[2] == W) and (C == 1 or s[1] == H * W)):
-            raise ValueError("compose_sheet: the frames of row %d must be dense CHW, got shape %s stride %s" %
-                             (r, tuple(t.shape), tuple(s)))
-    if n_cols < 1 or gutter < 0 or not 0 <= bg <= 255 or not 1 <= n_bits <= 8:
-        raise ValueError("compose_sheet: need n_cols >= 1, gutter >= 0, bg in [0, 255], n_bits in [1, 8] (got %d, %d, "
-                         "%d, %d)" % (n_cols, gutter, bg, n_bits))
-    if len(rows) > SHEET_MAX_ROWS:
-        raise ValueError("compose_sheet: %d rows exceed the %d of one launch" % (len(rows), SHEET_MAX_ROWS))
-    for r, t in enumerate(rows):
-        if int(t.shape[0]) > n_cols:
-            raise ValueError("compose_sheet: row %d holds %d frames for %d columns" % (r, int(t.shape[0]), n_cols))
-    for r, t in enumerate(rows):
-        if not t.is_cuda:
-            raise ValueError("compose_sheet: row %d is on %s; the kernel needs device tensors (no CPU fallback)" %
-                             (r, t.device))
-        if t.device != rows[0].device:
-            raise ValueError("compose_sheet: row 0 is on %s, row %d on %s" % (rows[0].device, r, t.device))
-    Hs, Ws = sheet_shape(len(rows), n_cols, H, W, gutter)
-    if Hs > 0x7fffffff or 3 * Ws + 1 > 0x7fffffff or C * H * W > 0x7fffffff:
-        raise ValueError("compose_sheet: a %dx%d sheet of %dx%dx%d frames exceeds one launch" % (Hs, Ws, C, H, W))
-    tab = (L.rfn_sheet_row * len(rows))()
-    for r, t in enumerate(rows):
-        n = int(t.shape[0])
-        tab[r].ptr = t.data_ptr() if n else None
-        tab[r].step = int(t.stride(0)) if n > 1 else 0
-        tab[r].kind = 1 if t.dtype == torch.uint8 else 0
-        tab[r].count = n
-    dev = rows[0].device
-    shape = (Hs, 1 + 3 * Ws) if scanlines else (Hs, Ws, 3)
-    if out is None:
-        out = torch.empty(shape, device=dev, dtype=torch.uint8)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or
-          not out.is_contiguous() or out.device != dev):
-        raise ValueError("compose_sheet: out must be a contiguous uint8 tensor %s on %s" % (shape, dev))
-    with torch.cuda.device(dev):
-        L.call("rfn_sheet_compose_u8", tab, len(rows), n_cols, C, H, W, gutter, bg, n_bits,
-               1 if preprocess_range == "0.5" else 0, 1 if scanlines else 0, out.data_ptr(),
-               meta=("shell", "sheet_compose", 0.0, "%dx%dx%dx%dx%d" % (len(rows), n_cols, C, H, W),
-                     float(out.numel()) + sum(float(t.numel() * t.element_size()) for t in rows)))
-    return out
-
-
-def chart_chunk():
-    """records one workgroup of the chart kernel culls at a time (rfn_chart_chunk); the picture does not depend on it"""
-    return int(L.load().rfn_chart_chunk())
-
-
-def chart_font():
-    """the kernel's built-in 5x7 font (rfn_chart_font): int32 numpy [95, 5], row ch = character 32 + ch, one entry per
-    column from the left, bit r = the dot in row r from the top"""
-    import numpy as np
-    buf = (ctypes.c_longlong * (95 * 5))()
-    rc = L.load().rfn_chart_font(ctypes.cast(buf, ctypes.c_void_p))
-    if rc != 0:
-        raise RuntimeError("rfn_chart_font failed (code %d)" % rc)
-    return np.frombuffer(buf, dtype=np.int64).astype(np.int32).reshape(95, 5)
-
-
-def render_chart(chart, H=None, W=None, scanlines=False, out=None, bg=(255, 255, 255), device=None):
-    """A line chart as 8-bit RGB pixels (rfn_chart_render_u8; the pixel contract is DESIGN.md section 25).  `chart`: a
-    rfn_hip.chart.Figure or DisplayList (H, W and bg come from it; a given H / W must agree), or a display-list table
-    int32 [n, 12] -- a numpy array or CPU tensor, checked against the contract's coordinate bounds and uploaded, or a
-    contiguous device tensor, taken as it is -- painted on an H x W canvas of colour `bg` (r, g, b).  Returns uint8
-    [H, W, 3], or with scanlines=True [H, 1 + 3*W] whose lines start with the PNG filter byte 0 (Utils.png.write_png
-    takes either); `out` (optional) is a contiguous uint8 device tensor of that shape, at any byte address.  The device
-    is that of `out`, of a device table, `device`, or the current one.  One launch on the current stream; no CPU
-    fallback."""
-    import numpy as np
-    from . import chart as C
-    if isinstance(chart, C.Figure):
-        chart = C.build_display_list(chart)
-    if isinstance(chart, C.DisplayList):
-        if (H is not None and int(H) != chart.height) or (W is not None and int(W) != chart.width):
-            raise ValueError("render_chart: the figure is %dx%d, H x W = %sx%s was asked for" %
-                             (chart.height, chart.width, H, W))
-        H, W, bg, table = chart.height, chart.width, chart.bg, chart.table
-    else:
-        table = chart
-    if H is None or W is None:
-        raise TypeError("render_chart: a table needs the canvas size H, W")
-    H, W = int(H), int(W)
-    if not (1 <= H <= C.MAX_SIDE and 1 <= W <= C.MAX_SIDE):
-        raise ValueError("render_chart: the canvas is at most %d x %d pixels, got %d x %d" %
-                         (C.MAX_SIDE, C.MAX_SIDE, H, W))
-    bg = tuple(int(c) for c in bg)
-    if len(bg) != 3 or not all(0 <= c <= 255 for c in bg):
-        raise ValueError("render_chart: bg must be three bytes (r, g, b), got %s" % (bg,))
-    on_device = isinstance(table, torch.Tensor) and table.is_cuda
-    if on_device:
-        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != C.REC or not table.is_contiguous():
-            raise ValueError("render_chart: a device table must be contiguous int32 [n, %d], got %s %s" %
-                             (C.REC, table.dtype, tuple(table.shape)))
-    elif isinstance(table, (torch.Tensor, np.ndarray)):
-        table = C.check_table(table.numpy() if isinstance(table, torch.Tensor) else table)
-    else:
-        raise TypeError("render_chart: need a chart.Figure, a chart.DisplayList or an int32 [n, %d] table, got %s" %
-                        (C.REC, type(chart).__name__))
-    shape = (H, 1 + 3 * W) if scanlines else (H, W, 3)
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or
-                            tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda):
-        raise ValueError("render_chart: out must be a contiguous uint8 device tensor %s" % (shape,))
-    if out is not None:
-        dev = out.device
-    elif on_device:
-        dev = table.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("render_chart: the chart kernel needs a GPU (no CPU fallback)")
-        dev = torch.device(device if device is not None else "cuda")
-        if dev.type != "cuda":
-            raise RuntimeError("render_chart: the chart kernel needs a GPU, got device %s (no CPU fallback)" % dev)
-    if on_device and table.device != dev:
-        raise ValueError("render_chart: the table is on %s, out on %s" % (table.device, dev))
-    if not on_device:
-        table = torch.from_numpy(table).to(dev)
-    if out is None:
-        out = torch.empty(shape, device=dev, dtype=torch.uint8)
-    n = int(table.shape[0])
-    with torch.cuda.device(dev):
-        L.call("rfn_chart_render_u8", table.data_ptr() if n else None, n, H, W, bg[0] | bg[1] << 8 | bg[2] << 16,
-               1 if scanlines else 0, out.data_ptr(),
-               meta=("shell", "chart_render", 0.0, "%dx%dx%d" % (n, H, W), float(out.numel()) + 48.0 * n))
-    return out
-
+# ----------------------------------------------------------------------------------------------- the other families
+# Each lives in the module named after the csrc file it wraps and is re-exported here: rfn_hip.ops is the import surface
+# (callers and tests reach, and patch, these names as attributes of it), the module is the home.  None of them reads
+# the precision switches or calls into the core, and none imports this module.
+from .gauss_heads import GAUSS_HEADS_OUTPUTS, GaussHeadsFn, gauss_heads, gauss_heads_check  # noqa: E402,F401
+from .lstm_cell import (LSTM_CELL_KERNEL_DEFAULT, LSTMCellFn, lstm_cell, lstm_cell_check, lstm_cell_route,  # noqa: E402,F401
+                        lstm_cell_torch)
+from .stepbn import StepBatchNormActFn, StepBatchNormActPoolFn, Up2xCatFn  # noqa: E402,F401
+from .bnflow import BatchNormFlowFn, bnflow_apply, bnflow_coef  # noqa: E402,F401
+from .mol import (MOL_KEYED_SLOT_COLOUR, MOL_KEYED_SLOT_MIX, MolNllFn, mol_dims, mol_keyed_uniforms, mol_nll,  # noqa: E402,F401
+                  mol_sample, mol_sample_keyed)
+from .frame_metrics import frame_quality  # noqa: E402,F401
+from .linext import (LinearExtrapLossFn, gauss_quality, gauss_quality_check, linear_extrap_check,  # noqa: E402,F401
+                     linear_extrap_loss, linear_extrap_pairs, linear_extrap_rollout, linext_limits)
+from .frames import (CLIP_MIRROR, CLIP_REVERSE, RESIZE_MAX_SIDE, clip_gather, clip_gather_aug, frames_resize,  # noqa: E402,F401
+                     moving_mnist_render, moving_mnist_sync_render, resize_window)
+from .noise import (KEYED_NORMAL_MAX_SLOTS, KEYED_UNIFORM_SLOT_DEQUANT, keyed_normal, keyed_normal_tiled_row,  # noqa: E402,F401
+                    keyed_uniform)
+from .pictures import SHEET_MAX_ROWS, chart_chunk, chart_font, compose_sheet, render_chart, sheet_shape  # noqa: E402,F401
 
 # LPIPS with the AlexNet trunk (rfn_hip/lpips.py holds the loader and the wrappers of csrc/lpips.hip)
 from .lpips import (LpipsAlexWeights, LpipsFeatures, lpips_alex, lpips_alex_distance, lpips_alex_features,  # noqa: E402,F401
