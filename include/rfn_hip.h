@@ -1018,6 +1018,47 @@ int rfn_chart_chunk(void);
 int rfn_chart_font(long long* out);
 int rfn_chart_render_u8(const int* table, int n, int H, int W, int bg, int lead, long out_addr, rfn_stream_t stream);
 
+/* ---- an animation of prediction draws as 8-bit RGB pixels, csrc/clip_compose.hip  (the moving counterpart of
+ * rfn_sheet_compose_u8: ground truth, draws, their mean and their spread side by side, each cell inside a coloured ring
+ * as the reference's figures frame their subplots; DESIGN.md section 28 is the pixel contract).  One launch writes all T
+ * frames.  Every frame is a grid of R x N cells of Hc x Wc = (zoom*H + 2*border) x (zoom*W + 2*border) pixels with
+ * `gutter` pixels of the grey level `bg` between the cells and around the grid:
+ *   Hs = R*Hc + (R+1)*gutter,  Ws = N*Wc + (N+1)*gutter,  cell (r, i) at (gutter + r*(Hc+gutter), gutter + i*(Wc+gutter)).
+ * cells: DEVICE array of R*N records of eight int64 words, 8-byte aligned, cell (r, i) at index r*N + i (a device table,
+ * as the chart's: the cell count is not bounded by the launch's arguments); its contents are the caller's responsibility:
+ *   w0  byte address of member 0, frame 0 (4-byte aligned for kind 0; 0 for an empty cell)
+ *   w1  elements between consecutive frames          w2  elements between consecutive group members
+ *   w3  count, the frames available (0: an empty cell)
+ *   w4  group size G, 1..RFN_CLIP_MAX_GROUP
+ *   w5  kind | mode << 8 | gain << 16: kind 0 fp32 in model space, 1 uint8; mode 0 FRAME, 1 MEAN, 2 SPREAD;
+ *       gain 1..RFN_CLIP_MAX_GAIN
+ *   w6  switch_at                                     w7  rgb_before | rgb_after << 32, a colour being r | g<<8 | b<<16
+ * Frames are dense [C, H, W] blocks, C in {1, 3}; C == 1 goes to R, G and B.  Pixel rules of frame t, integer after the
+ * byte conversion: b_g = the byte of member g at source pixel (c, y, x) of frame f = min(t, count - 1), made as
+ * rfn_sheet_compose_u8 makes it (kind 0: Solver.preprocess(x, reverse=True) with n_bits / range_half, NaN -> 0; kind 1:
+ * a copy);
+ *   FRAME   b_0
+ *   MEAN    (sum_g b_g + G/2) / G
+ *   SPREAD  min(255, isqrt(gain^2 (G sum_g b_g^2 - (sum_g b_g)^2)) / G): gain times the population standard deviation
+ *           of the bytes, rounded down; isqrt is the exact integer square root (the radicand has at most 44 bits)
+ * with floor divisions and sums in member order.  Zoom is nearest: interior pixel (yy, xx) of a cell shows source pixel
+ * (yy / zoom, xx / zoom).  The ring of `border` pixels around the interior has the colour rgb_before for t < switch_at,
+ * else rgb_after.  An empty cell is all bg, ring included.
+ * out_addr: the device address of the uint8 output, of any byte alignment: lead 0: [T, Hs, Ws, 3];  lead 1:
+ * [T, Hs, 1 + 3*Ws] with byte 0 of every line 0, i.e. T raw PNG streams.  Every output byte is written exactly once
+ * (dword stores on the aligned part of each line, byte stores at its ragged ends), nothing outside it; only listed
+ * frames are read; no atomics, no LDS, no scratch.  One launch, no allocation: capturable.
+ * Returns -1 unless R, N, T, H, W >= 1; -2 unless C in {1, 3}; -3 unless 1 <= zoom <= 16, 0 <= border <= 64, gutter >= 0
+ * and 0 <= bg <= 255; -4 unless 1 <= n_bits <= 8 and lead in {0, 1}; -5 unless 3*Ws + lead <= 2^31 - 1 and T*Hs <=
+ * 2^31 - 1; -6 for a NULL table or an out_addr of 0; nothing is launched then.  The two limits are read by the binding
+ * through the host-only queries below (they are written in parentheses, like RFN_LINEXT_MAX_FRAMES). */
+#define RFN_CLIP_MAX_GROUP (1024)
+#define RFN_CLIP_MAX_GAIN (16)
+int rfn_clip_max_group(void);
+int rfn_clip_max_gain(void);
+int rfn_clip_compose_u8(const void* cells, int R, int N, int T, int C, int H, int W, int zoom, int border, int gutter,
+                        int bg, int n_bits, int range_half, int lead, long out_addr, rfn_stream_t stream);
+
 /* ---- LPIPS with the AlexNet trunk over a batch of uint8 frames  (evaluation_metrics/error_metrics.py:72, :173-187:
  * lpips.LPIPS(net='alex') of `lpips` 0.1.3, version 0.1, lpips=True, spatial=False, eval mode; one call per frame there).
  * Frame [C, H, W] uint8, C in {1, 3} (one channel stands for all three): x = p/255*2 - 1, then (x - shift[c]) / scale[c]

@@ -23,6 +23,7 @@
 // byte of `out` is written exactly once (background and lead bytes included: nothing is zeroed first), nothing outside
 // it is touched, and only the listed frames are read.  No atomics, no LDS, no scratch.
 #include "common.h"
+#include "pixel_quant.h"
 #include "../../include/rfn_hip.h"
 
 static_assert(sizeof(rfn_sheet_row) == 24, "rfn_sheet_row layout is part of the ABI");
@@ -43,10 +44,7 @@ struct SheetGeom {
 };
 
 __device__ __forceinline__ uint32_t sheet_quantise(float x, const SheetGeom& g) {
-    float v = g.range_half ? __fadd_rn(x, 0.5f) : x;
-    v = __fmul_rn(v, g.n_bins);
-    const float q = __fmul_rn(floorf(v), g.scale);
-    return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);   // fmaxf(NaN, 0) = 0
+    return rfn_quantise_u8(x, g.range_half, g.n_bins, g.scale);   // (shared with clip_compose.hip)
 }
 
 // byte `xb` of the current line; src = channel 0 of the line's pixel row in column 0's frame (nullptr: a gutter line)

@@ -16,7 +16,9 @@ raises.
 `get_eval_values_temperatures` is the temperature study (eval_settings.py:110-126) as one pass: best-of-N at K sampling
 temperatures from one RFN.predict_draws call per pass, the temperatures being per-row inputs of generation.
 `plot_long_t`, `plot_diversity`, `plot_random_samples` and `plot_temp` (:1220-1415) are written as PNG sheets of pixels
-like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  The curve figures `plot_eval_values` /
+like `plot_samples` (no titles, no coloured frames around the cells, no PDF).  `plot_clips` (ours) shows the draws of a
+stochastic model as an animated PNG next to the ground truth, their mean and their spread, and it does draw the
+coloured frames: green around given frames, red around generated ones.  The curve figures `plot_eval_values` /
 `test_temp_values` (:600-1003) are drawn by the chart kernel (rfn_hip.ops.render_chart, one launch per figure) from the
 statistics of evaluation_metrics/curves.py and written as PNG.  So are the analysis figures: `plot_elbo_gap` and
 `plot_prob_of_t` (:189-270; get_eval_values("rfn.pt") draws them under settings.extra_plots) and `param_plots`
@@ -362,6 +364,53 @@ class Evaluator(object):
         os.makedirs(folder, exist_ok=True)
         path = os.path.join(folder, name + ".png")
         write_png(path, sheet)
+        return path
+
+    @staticmethod
+    def clip_cells(predictions, true_image, n, n_conditions, gain, show=None):
+        """the grid of plot_clips: row k = sequence k; columns: the ground truth, the first `show` (default: all) of
+        the D draws, the MEAN and the SPREAD of all D.  predictions uint8 [D, bs, T, C, H, W], true_image uint8
+        [bs, T, C, H, W], on one device; nothing is copied."""
+        from rfn_hip import ops
+        D = int(predictions.shape[0])
+        cell = lambda frames, mode="frame": ops.ClipCell(frames, mode, gain=gain, switch_at=n_conditions)
+        return [[cell(true_image[k])] + [cell(predictions[d, k]) for d in range(D if show is None else show)] +
+                [cell(predictions[:, k].transpose(0, 1), "mean"), cell(predictions[:, k].transpose(0, 1), "spread")]
+                for k in range(n)]
+
+    def plot_clips(self, predictions, true_image, name="clips", n=None, n_conditions=None, zoom=2, border=2, gain=4,
+                   delay_ms=100):
+        """The draws of a stochastic model as an animation, `<path>eval_folder/<name>.png` (an animated PNG: viewers that
+        do not know the format show frame 0): one row per sequence for the first n (default: all bs) sequences, columns
+        ground truth | the D draws | their per-pixel MEAN | their SPREAD (gain x the population standard deviation of
+        the bytes), every cell zoomed `zoom` times inside a ring of `border` pixels that is green while the frames are
+        given (t < n_conditions, default: the evaluator's) and red once they are generated.  predictions: uint8
+        [D, bs, T, C, H, W] or [bs, T, C, H, W] (one draw); true_image: uint8 [bs, T, C, H, W]; on either device (moved
+        to the solver's).  One compose launch for all T frames (rfn_hip.ops.compose_clip); returns the file's path."""
+        from rfn_hip import ops
+        from Utils.png import write_apng
+        for t, nm, dims in ((predictions, "predictions", (5, 6)), (true_image, "true_image", (5,))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() not in dims:
+                raise ValueError("plot_clips: %s must be a uint8 tensor [%sbs, T, C, H, W], got %s" %
+                                 (nm, "D, " if len(dims) > 1 else "",
+                                  (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if predictions.dim() == 5:
+            predictions = predictions.unsqueeze(0)
+        if tuple(predictions.shape[1:]) != tuple(true_image.shape):
+            raise ValueError("plot_clips: predictions %s and true_image %s differ in shape" %
+                             (tuple(predictions.shape), tuple(true_image.shape)))
+        D, bs, T = (int(d) for d in predictions.shape[:3])
+        n = bs if n is None else int(n)
+        if not 1 <= n <= bs or T < 1 or D < 1:
+            raise ValueError("plot_clips: n = %d sequences of %d, %d draws of %d frames each" % (n, bs, D, T))
+        n_conditions = int(n_conditions if n_conditions is not None else (self.n_conditions or 0))
+        predictions, true_image = predictions.to(self.device), true_image.to(self.device)
+        clip = ops.compose_clip(self.clip_cells(predictions, true_image, n, n_conditions, int(gain)), T, zoom=int(zoom),
+                                border=int(border), scanlines=True)
+        folder = self.solver.path + "eval_folder"
+        os.makedirs(folder, exist_ok=True)
+        path = os.path.join(folder, name + ".png")
+        write_apng(path, clip, delay_ms=delay_ms)
         return path
 
     def get_eval_values(self, model_name="rfn.pt", loader=None, max_batches=None):

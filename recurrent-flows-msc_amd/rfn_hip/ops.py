@@ -1792,6 +1792,7 @@ from .frames import (CLIP_MIRROR, CLIP_REVERSE, RESIZE_MAX_SIDE, clip_gather, cl
 from .noise import (KEYED_NORMAL_MAX_SLOTS, KEYED_UNIFORM_SLOT_DEQUANT, keyed_normal, keyed_normal_tiled_row,  # noqa: E402,F401
                     keyed_uniform)
 from .pictures import SHEET_MAX_ROWS, chart_chunk, chart_font, compose_sheet, render_chart, sheet_shape  # noqa: E402,F401
+from .clip_compose import CLIP_MODES, ClipCell, clip_limits, clip_shape, compose_clip  # noqa: E402,F401
 
 # LPIPS with the AlexNet trunk (rfn_hip/lpips.py holds the loader and the wrappers of csrc/lpips.hip)
 from .lpips import (LpipsAlexWeights, LpipsFeatures, lpips_alex, lpips_alex_distance, lpips_alex_features,  # noqa: E402,F401

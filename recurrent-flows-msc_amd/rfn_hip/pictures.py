@@ -1,10 +1,13 @@
 """Pictures as 8-bit RGB pixels: the sample sheets and the chart rasteriser; wrappers of csrc/sheet.hip and
-csrc/chart.hip (rfn_hip/chart.py builds the display lists).  rfn_hip.ops re-exports the public names."""
+csrc/chart.hip (rfn_hip/chart.py builds the display lists).  rfn_hip.ops re-exports the public names.  The moving
+pictures (csrc/clip_compose.hip) have their wrapper in rfn_hip/clip_compose.py, a module named after its csrc file like
+every other family's; its names are reachable here as well."""
 import ctypes
 
 import torch
 
 from . import lib as L
+from .clip_compose import ClipCell, clip_limits, clip_shape, compose_clip  # noqa: F401
 
 
 SHEET_MAX_ROWS = L.CONSTANTS["RFN_SHEET_MAX_ROWS"]   # the row descriptors travel in the launch's arguments
