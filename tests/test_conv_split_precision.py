@@ -377,20 +377,25 @@ def test_pack_plan_bit_exact(K):
             _check_pack(b, pack_ref(w.cpu(), m & 3, 3 if m & 4 else 2), ("pack plan", n_rep, tuple(w.shape), m))
 
 
-def smallmap_pack_ref(w, H, W, transpose):
-    """CPU restatement of the small-map dense pack (smallmap_pack_batched_kernel) as int16 bits.  Dense matrix
-    M[(ci,pi)][(co,po)] = w[co][ci][tap(po, pi)] (transpose: M^T), zero-padded to KS*16 rows and NT*32 columns, split
-    into bf16 hi = bf16(v), lo = bf16(v - hi); unit index ((tile*KS + ks)*2 + plane)*64 + lane, element j <->
-    k = ks*16 + (lane/32)*8 + j, n = tile*32 + lane%32."""
+def smallmap_dense_matrix(w, H, W, transpose):
+    """the dense matrix of a 3x3 / pad 1 convolution on an H x W map, in w's dtype and before any padding:
+    M[(ci,pi)][(co,po)] = w[co][ci][tap(po, pi)] (transpose: M^T)"""
     Cout, Cin, HW = int(w.shape[0]), int(w.shape[1]), H * W
-    M = torch.zeros(Cin * HW, Cout * HW)
+    M = torch.zeros(Cin * HW, Cout * HW, dtype=w.dtype)
     for po in range(HW):
         for pi in range(HW):
             dy, dx = pi // W - po // W + 1, pi % W - po % W + 1
             if 0 <= dy < 3 and 0 <= dx < 3:
                 M[pi::HW, po::HW] = w[:, :, dy, dx].t()
-    if transpose:
-        M = M.t()
+    return M.t() if transpose else M
+
+
+def smallmap_pack_ref(w, H, W, transpose):
+    """CPU restatement of the small-map dense pack (smallmap_pack_batched_kernel) as int16 bits.  Dense matrix
+    M[(ci,pi)][(co,po)] = w[co][ci][tap(po, pi)] (transpose: M^T), zero-padded to KS*16 rows and NT*32 columns, split
+    into bf16 hi = bf16(v), lo = bf16(v - hi); unit index ((tile*KS + ks)*2 + plane)*64 + lane, element j <->
+    k = ks*16 + (lane/32)*8 + j, n = tile*32 + lane%32."""
+    M = smallmap_dense_matrix(w, H, W, transpose)
     KS, NT = -(-M.shape[0] // 16), -(-M.shape[1] // 32)
     P = torch.zeros(KS * 16, NT * 32)
     P[:M.shape[0], :M.shape[1]] = M
