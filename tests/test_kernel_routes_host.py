@@ -9,6 +9,7 @@ import pytest
 
 from tests.test_conv_grad_model import ACTBWD_CASES, CONV_CASES, GEMM_CASES, WGRAD_CASES
 from tests.test_conv_split_precision import FWD_CASES, X6_KERNELS
+from tests.test_wgrad_routes_model import ALL_LABELS, BAND_ENTRY, EXACT_CASES, GEMM, ROUTE_CASES, assert_ring, grouped
 
 B3, F32 = "rfn_conv2d_kernel_label_bf16x3", "rfn_conv2d_kernel_label_f32"
 
@@ -76,6 +77,36 @@ def test_wgrad_cases_take_their_table_routes(K, name):
     G, N, C1, C2, Cout, H, W, ks, view, want = WGRAD_CASES[name]
     plan = K.wgrad_plan(G, N, C1, C2, Cout, H, W, ks, in1_ns=2 * C1 * H * W if view else None, stacked=bool(G))
     assert plan.launches == want
+
+
+@pytest.mark.parametrize("name", list(EXACT_CASES))
+def test_route_model_cases_take_their_table_routes(K, name):
+    """the cases of tests/test_wgrad_routes_model.py (mirrored, short rows, level split, and its restatements of the
+    GEMM_CASES, WGRAD_CASES and band cases): the launches of K.wgrad_plan / the GEMM label query for the strides of the
+    channel-slice views, and the workgroups of a grouped ring launch that change group in mid-range"""
+    c = EXACT_CASES[name]
+    HW = c.H * c.W
+    in1_ns = (c.xview[0] if c.xview else c.C1) * HW
+    g_ns = (c.gview[0] if c.gview else c.Cout) * HW
+    if c.kind == "gemm":
+        label = K.kernel_label("rfn_gemm_wgrad_kernel_label_bf16x3", c.Cout, c.C1, g_ns, in1_ns, c.G, c.N, HW)
+        assert [(GEMM[1 if c.G else 0], grouped(label) if c.G else label)] == c.want
+    elif c.kind == "band":
+        assert [(BAND_ENTRY, K.kernel_label("rfn_conv3x3_wgrad_band_kernel_label_bf16x3", c.Cout, c.C1 + c.C2, c.N, c.H,
+                                            c.W))] == c.want
+    else:
+        plan = K.wgrad_plan(c.G, c.N, c.C1, c.C2, c.Cout, c.H, c.W, c.ks, g_ns=g_ns, in1_ns=in1_ns,
+                            few_out=c.kind == "zeros", stacked=bool(c.G) and c.gview is None, short_rows=c.short)
+        assert plan.launches == c.want
+    assert_ring(c)
+
+
+def test_route_model_cases_cover_every_weight_gradient_label():
+    """every label of kWgradB3Labels, single and grouped (a group never takes the 32-row implicit tiling), and the two of
+    the band kernel: 31"""
+    seen = {label for c in EXACT_CASES.values() for _, label in c.want if "wgrad" in label}
+    assert seen == ALL_LABELS and len(ALL_LABELS) == 31, (sorted(seen - ALL_LABELS), sorted(ALL_LABELS - seen))
+    assert all(c.ring is not None for n, c in ROUTE_CASES.items() if n.startswith(("split_", "mir_narrow")))
 
 
 def test_fp32_1x1_between_65_and_128_outputs_takes_the_128_row_block(K):
