@@ -1167,6 +1167,50 @@ int rfn_linext_rollout_f32(const float* x, long seq_stride, long frame_stride, i
 int rfn_gauss_quality_f32(const float* pred, const float* truth, float* ssim, float* mse, int N, int C, int H, int W,
                           float scale, float lo, float hi, rfn_stream_t stream);
 
+/* ---- pixel log-likelihoods of the baselines' importance-weighted bound, csrc/pixel_loglik.hip  (forward only; DESIGN.md
+ * section 29 is the contract).
+ *
+ * rfn_pixel_loglik_f32  (VRNN/VRNN.py:400-415, SVG/SVG.py:371-380 inside :344-385, SRNN/SRNN.py:482-579 of the reference:
+ *   `lpx_Gz_obs` of one time step for all K inner samples at once, in place of x.repeat(K, ...), the torch.distributions
+ *   log_prob chain and batch_reduce).  pred: [R, N] dense, row r = k*B + b;  target: B rows of N floats, target_stride
+ *   floats apart (>= N), row r of pred is scored against row r % B: the frame is never repeated in memory;  noise: NULL
+ *   or [R, N] dense, added to the target of its row (the "gaussian" dequantisation x + u, one draw per inner sample);
+ *   out: [R], out[r] = sum_n l(pred[r, n], x[r, n]) with x = target (+ noise) and, by `mode`,
+ *     RFN_PIXEL_LOGLIK_BERNOULLI  l = x log(pc) + (1 - x) log1p(-pc),  pc = min(max(p, 2^-23), 1 - 2^-23)
+ *                                 (torch.distributions.Bernoulli(probs=p).log_prob(x) written out; x need not be binary)
+ *     RFN_PIXEL_LOGLIK_GAUSSIAN   l = -(x - p)^2 / (2 scale^2) - log(scale) - log(2 pi) / 2
+ *     RFN_PIXEL_LOGLIK_MSE        l = -(p - x)^2
+ *   `scale` is read by GAUSSIAN only (positive and finite).  A term's sums, differences, products and squares are fp64
+ *   operations on the fp32 inputs, the two logs are the accurate fp32 logf / log1pf, and the term is rounded to fp32
+ *   once.  Summation order, a function of N alone: one workgroup of 256 lanes per row; the row is cut into groups of four
+ *   consecutive elements (the last may be short), lane t takes groups t, t + 256, t + 512, ... and adds their terms to
+ *   an fp32 sum that starts at +0, in element order; the 64 sums of each wavefront are combined by the xor butterfly
+ *   (offsets 32, 16, 8, 4, 2, 1), and the four wavefront sums w0..w3 are added as ((w0 + w1) + w2) + w3.  The longest
+ *   chain has A(N) = L - 1 + 9 additions, L = the elements of lane 0 (48 at N = 12288).  A group is read as one 16-byte
+ *   load per operand when the row's bases in pred, target and noise are all 16-byte aligned (decided per row), else as
+ *   single floats: the same values in the same order either way.  No atomics; out[r] depends on row r, its target row
+ *   and N alone, not on R, on the other rows of the call or on the launch (rows beyond the grid are taken by a
+ *   grid-stride loop).  Any N >= 1, any 4-byte aligned bases, 0 <= R <= 2^31 - 1 (R = 0: nothing is launched), R a
+ *   multiple of B.  One launch.  Returns -1 for a bad size, -2 for an unknown mode, -3 for a bad scale, -4 for a NULL or
+ *   misaligned pointer; nothing is launched then.
+ *
+ * rfn_normal_logvar_pair_f32  (SVG/SVG.py:344-385: `Normal(mu, exp(logvar / 2)).log_prob(z).sum(-1)` of the prior and of
+ *   the posterior of one inner sample).  Six [B, Z] dense inputs, out_a / out_b: [B];
+ *   out_a[b] = sum_j -logvar_a[b,j] / 2 - (z_a[b,j] - mu_a[b,j])^2 exp(-logvar_a[b,j]) / 2 - log(2 pi) / 2, out_b likewise:
+ *   the caller chooses which z goes with which distribution.  Terms in fp64 (fp64 exp), rounded to fp32 once.  One
+ *   wavefront per row and distribution: lane l adds the terms j = l, l + 64, ... in index order, then the xor butterfly.
+ *   No atomics, one launch for both.  Returns -1 for a bad size, -2 for a NULL pointer.
+ * (The three modes are written in parentheses, like RFN_LINEXT_MAX_FRAMES: the binding mirrors plain-integer defines
+ * only; rfn_hip/pixel_loglik.py keeps the names in this order.) */
+#define RFN_PIXEL_LOGLIK_BERNOULLI (0)
+#define RFN_PIXEL_LOGLIK_GAUSSIAN (1)
+#define RFN_PIXEL_LOGLIK_MSE (2)
+int rfn_pixel_loglik_f32(const float* pred, const float* target, long target_stride, const float* noise, float* out,
+                         long R, int B, long N, int mode, double scale, rfn_stream_t stream);
+int rfn_normal_logvar_pair_f32(const float* mu_a, const float* logvar_a, const float* z_a, const float* mu_b,
+                               const float* logvar_b, const float* z_b, float* out_a, float* out_b, int B, int Z,
+                               rfn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,13 +150,18 @@ class SRNN(nn.Module):
     def get_inits(self):
         return self.h_0, self.c_0, self.z_0, self.z_0x, self.a_0, self.ca_0, 0, 0, 0
 
-    def uniform_binning_correction(self, x, draws=None):
+    def _dequant_draw(self, x, d):
+        """(u, objective) of uniform_binning_correction, whose x_noise is x + u"""
         b, c, h, w = x.size()
         n_bins = 2 ** self.bits
-        d = draws if isinstance(draws, _Draws) else _Draws(draws, x.device)
-        x_noise = x + d.uniform(x.shape, 0, 1.0 / n_bins)
+        u = d.uniform(x.shape, 0, 1.0 / n_bins)
         objective = -np.log(n_bins) * (c * h * w) * torch.ones(b, device=x.device)
-        return x_noise, objective
+        return u, objective
+
+    def uniform_binning_correction(self, x, draws=None):
+        d = draws if isinstance(draws, _Draws) else _Draws(draws, x.device)
+        u, objective = self._dequant_draw(x, d)
+        return x + u, objective
 
     def _prior_dist(self, ht, z):
         prior_t = self.prior(torch.cat([ht, self.phi_z(z)], 1))
@@ -369,6 +374,22 @@ class SRNN(nn.Module):
             return K.mol_nll(x_i.detach(), dec_mean_t, reduce="frame")
         raise ValueError("undefined loss %r" % (self.loss_type,))
 
+    def _frame_nll_rows(self, dec_mean_t, x_i, u=None, nll_unif=None, scale=None):
+        """_frame_nll of the R = K*B rows (k*B + b) of a deferred decoder call under the B frames x_i; u [R, ...]: the
+        dequantisation uniforms of "gaussian", one draw per row, nll_unif [R] their objective.  Without a gradient to
+        keep, "bernoulli", "gaussian" and "mse" are one rfn_hip.ops.pixel_loglik launch that reads x_i in place (scale: a
+        callable giving softplus(variance) as a Python float); otherwise, and with RFN_PIXEL_LOGLIK=0, the frames are
+        repeated K times and the torch chain of _frame_nll runs ("mol" has its own kernel there)."""
+        from rfn_hip import ops
+        gauss = self.loss_type == "gaussian"
+        if self.loss_type in ops.PIXEL_LOGLIK_MODES and ops.pixel_loglik_route(
+                dec_mean_t, x_i, u, self.variance if gauss else None) == "kernel":
+            if gauss:
+                return -ops.pixel_loglik(dec_mean_t, x_i, "gaussian", scale=scale(), noise=u) - nll_unif
+            return -ops.pixel_loglik(dec_mean_t, x_i, self.loss_type)
+        x_rep = x_i.repeat(dec_mean_t.shape[0] // x_i.shape[0], 1, 1, 1)
+        return self._frame_nll(dec_mean_t, x_rep, x_rep + u if gauss else None, nll_unif)
+
     def elbo_importance_weighting(self, xt, K, draws=None, defer_decoder=None):
         """The importance-weighted bound the reference reports as its baselines' bits/dim (SRNN/SRNN.py:482-579 of the
         reference), as that code behaves: zprevx and zprev chain through the K inner samples and on into the next time
@@ -380,7 +401,9 @@ class SRNN(nn.Module):
         a time step therefore run ONCE over the K*B rows collected in the k loop (one mol_nll launch per step in place
         of K), and the deterministic phi_x_t(x_i) is taken from the pass over the frames; in training mode every inner
         sample makes its own calls, because the batch statistics of the norm layers are per call in the reference.
-        defer_decoder = False / True forces either form of the decoder."""
+        defer_decoder = False / True forces either form of the decoder.  The deferred likelihood is _frame_nll_rows:
+        for the non-"mol" losses one pixel_loglik launch per time step when no gradient is kept, with softplus(variance)
+        of "gaussian" read to the host once per call."""
         b, t, c, h, w = xt.shape
         K = int(K)
         if K < 1:
@@ -396,6 +419,12 @@ class SRNN(nn.Module):
         if self.enable_smoothing:
             store_at = self._smoothing_states(store_ht, lambda i: feats[i], t, aprev, caprev)
         log_k = float(np.log(K))
+        host_scale = []
+
+        def scale():   # one device-to-host read per call, and only when a kernel launch needs it
+            if not host_scale:
+                host_scale.append(float(nn.functional.softplus(self.variance.detach())))
+            return host_scale[0]
         loss = 0
         for i in range(1, t):
             ht, x_i = store_ht[i - 1], xt[:, i]
@@ -414,22 +443,23 @@ class SRNN(nn.Module):
                 enc_dist = td.Normal(enc_mean_t, enc_std_t)
                 z_tx = d.rsample(enc_dist)
                 z_t = d.rsample(prior_dist)
-                x_noise = nll_unif = None
+                u = nll_unif = None
                 if self.loss_type == "gaussian":
-                    x_noise, nll_unif = self.uniform_binning_correction(x_i, d)
+                    u, nll_unif = self._dequant_draw(x_i, d)
                 if defer:
                     ztxs.append(z_tx)
-                    noisy.append(x_noise)
+                    noisy.append(u)
                     unifs.append(nll_unif)
                 else:
-                    nlls.append(self._frame_nll(self._decode(ht, z_tx), x_i, x_noise, nll_unif))
+                    nlls.append(self._frame_nll(self._decode(ht, z_tx), x_i, None if u is None else x_i + u, nll_unif))
                 logpzs.append(prior_dist.log_prob(z_t).sum([-1]))
                 logqzxs.append(enc_dist.log_prob(z_tx).sum([-1]))
                 zprevx, zprev = z_tx, z_t
             if defer:   # rows k*B + b
                 gauss = self.loss_type == "gaussian"
-                nll = self._frame_nll(self._decode(ht.repeat(K, 1, 1, 1), torch.cat(ztxs, 0)), x_i.repeat(K, 1, 1, 1),
-                                      torch.cat(noisy, 0) if gauss else None, torch.cat(unifs, 0) if gauss else None)
+                nll = self._frame_nll_rows(self._decode(ht.repeat(K, 1, 1, 1), torch.cat(ztxs, 0)), x_i,
+                                           torch.cat(noisy, 0) if gauss else None, torch.cat(unifs, 0) if gauss else None,
+                                           scale)
                 nll = nll.view(K, b)
             else:
                 nll = torch.stack(nlls, 0)

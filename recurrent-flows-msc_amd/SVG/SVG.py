@@ -338,6 +338,27 @@ class SVG(nn.Module):
         log-likelihood for "bernoulli" and "gaussian", minus the squared error for "mse" """
         return -self._nll_pixels(x_pred, x_i).sum([-1, -2, -3])
 
+    def _lpx_rows(self, x_pred, x_i):
+        """_lpx of the R = K*B rows (k*B + b) of a deferred decoder call under the B frames x_i: without a gradient to
+        keep one rfn_hip.ops.pixel_loglik launch that reads x_i in place; otherwise, and with RFN_PIXEL_LOGLIK=0, the
+        frames are repeated K times and the torch chain of _lpx runs."""
+        from rfn_hip import ops
+        if self.loss_type in ops.PIXEL_LOGLIK_MODES and ops.pixel_loglik_route(x_pred, x_i) == "kernel":
+            scale = float(self.variance) if self.loss_type == "gaussian" else None   # (a Python number here)
+            return ops.pixel_loglik(x_pred, x_i, self.loss_type, scale=scale)
+        return self._lpx(x_pred, x_i.repeat(x_pred.shape[0] // x_i.shape[0], 1, 1, 1))
+
+    @staticmethod
+    def _log_densities(mu_p, logvar_p, z_t, mu_q, logvar_q, z_tx):
+        """(log p(z_t), log q(z_tx | x)) per row: the densities of N(mu_p, exp(logvar_p / 2)) at z_t and of N(mu_q,
+        exp(logvar_q / 2)) at z_tx, summed over the latent; one rfn_hip.ops.normal_logvar_pair launch without a gradient
+        to keep, the two torch.distributions chains otherwise and with RFN_PIXEL_LOGLIK=0"""
+        from rfn_hip import ops
+        if ops.pixel_loglik_route(mu_p, logvar_p, z_t, mu_q, logvar_q, z_tx) == "kernel":
+            return ops.normal_logvar_pair(mu_p, logvar_p, z_t, mu_q, logvar_q, z_tx)
+        return (td.Normal(mu_p, torch.exp(logvar_p * 0.5)).log_prob(z_t).sum([-1]),
+                td.Normal(mu_q, torch.exp(logvar_q * 0.5)).log_prob(z_tx).sum([-1]))
+
     def elbo_importance_weighting(self, x, K, draws=None, defer_decoder=None):
         """The importance-weighted bound of the reference (SVG.py:344-385), as that code behaves: the hidden states of
         the three nets advance K times per frame and carry into the next frame; per inner sample the draws are the
@@ -347,7 +368,9 @@ class SVG(nn.Module):
         The decoder does not feed the recurrence.  In eval mode (defer_decoder None) the decoder and the likelihood of a
         time step run ONCE over the K*B rows collected in the k loop, with the skip tensors repeated; in training mode
         every inner sample makes its own decoder call, because the batch statistics are per call in the reference.
-        defer_decoder = False / True forces either form."""
+        defer_decoder = False / True forces either form.  Without a gradient to keep, the two densities of an inner
+        sample are one normal_logvar_pair launch and the deferred likelihood one pixel_loglik launch per time step
+        (_log_densities, _lpx_rows)."""
         b, t = x.shape[0], x.shape[1]
         K = int(K)
         if K < 1:
@@ -366,15 +389,16 @@ class SVG(nn.Module):
                 z_t, mu_q, logvar_q = self.posterior(h_target, d)
                 z_tx, mu_p, logvar_p = self.prior(h, d)
                 h_pred = self.frame_predictor(torch.cat([h, z_t], 1))
-                logpzs.append(td.Normal(mu_p, torch.exp(logvar_p * 0.5)).log_prob(z_t).sum([-1]))
-                logqzxs.append(td.Normal(mu_q, torch.exp(logvar_q * 0.5)).log_prob(z_tx).sum([-1]))
+                logp, logq = self._log_densities(mu_p, logvar_p, z_t, mu_q, logvar_q, z_tx)
+                logpzs.append(logp)
+                logqzxs.append(logq)
                 if defer:
                     h_preds.append(h_pred)
                 else:
                     lpxs.append(self._lpx(self.decoder([h_pred, skip]), x_i))
             if defer:   # rows k*B + b
                 x_pred = self.decoder([torch.cat(h_preds, 0), [s.repeat(K, 1, 1, 1) for s in skip]])
-                lpx = self._lpx(x_pred, x_i.repeat(K, 1, 1, 1)).view(K, b)
+                lpx = self._lpx_rows(x_pred, x_i).view(K, b)
             else:
                 lpx = torch.stack(lpxs, 0)
             table = lpx + torch.stack(logpzs, 0) - torch.stack(logqzxs, 0)

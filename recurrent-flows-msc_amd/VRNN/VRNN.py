@@ -108,13 +108,18 @@ class VRNN(nn.Module):
     def get_inits(self):
         return self.h_0, self.c_0, self.z_0, self.z_0x, 0, 0, 0
 
-    def uniform_binning_correction(self, x, draws=None):
+    def _dequant_draw(self, x, d):
+        """(u, objective) of uniform_binning_correction, whose x_noise is x + u"""
         b, c, h, w = x.size()
         n_bins = 2 ** self.bits
-        d = draws if isinstance(draws, _Draws) else _Draws(draws, x.device)
-        x_noise = x + d.uniform(x.shape, 0, 1.0 / n_bins)
+        u = d.uniform(x.shape, 0, 1.0 / n_bins)
         objective = -np.log(n_bins) * (c * h * w) * torch.ones(b, device=x.device)
-        return x_noise, objective
+        return u, objective
+
+    def uniform_binning_correction(self, x, draws=None):
+        d = draws if isinstance(draws, _Draws) else _Draws(draws, x.device)
+        u, objective = self._dequant_draw(x, d)
+        return x + u, objective
 
     def _step(self, ut, z_in, hprev, cprev):
         """the recurrent cell on (phi_x_t of the previous frame, phi_z of the previous latent)"""
@@ -339,6 +344,22 @@ class VRNN(nn.Module):
             return K.mol_nll(x_i.detach(), dec_mean_t, reduce="frame")
         raise ValueError("undefined loss %r" % (self.loss_type,))
 
+    def _lpx_rows(self, dec_mean_t, x_i, u=None, nll_unif=None, scale=None):
+        """_lpx of the R = K*B rows (k*B + b) of a deferred decoder call under the B frames x_i; u [R, ...]: the
+        dequantisation uniforms of "gaussian", one draw per row, nll_unif [R] their objective.  Without a gradient to
+        keep, "bernoulli", "gaussian" and "mse" are one rfn_hip.ops.pixel_loglik launch that reads x_i in place (scale: a
+        callable giving softplus(variance) as a Python float); otherwise, and with RFN_PIXEL_LOGLIK=0, the frames are
+        repeated K times and the torch chain of _lpx runs."""
+        from rfn_hip import ops
+        gauss = self.loss_type == "gaussian"
+        if self.loss_type in ops.PIXEL_LOGLIK_MODES and ops.pixel_loglik_route(
+                dec_mean_t, x_i, u, self.variance if gauss else None) == "kernel":
+            if gauss:
+                return ops.pixel_loglik(dec_mean_t, x_i, "gaussian", scale=scale(), noise=u) - nll_unif
+            return ops.pixel_loglik(dec_mean_t, x_i, self.loss_type)
+        x_rep = x_i.repeat(dec_mean_t.shape[0] // x_i.shape[0], 1, 1, 1)
+        return self._lpx(dec_mean_t, x_rep, x_rep + u if gauss else None, nll_unif)
+
     def elbo_importance_weighting(self, xt, K, draws=None, defer_decoder=None):
         """The importance-weighted bound the reference reports as its baselines' bits/dim (VRNN/VRNN.py:366-428 of the
         reference), as that code behaves: hprev, cprev and zxprev chain through the K inner samples and on into the next
@@ -350,7 +371,8 @@ class VRNN(nn.Module):
         a time step therefore run ONCE over the K*B rows collected in the k loop, and phi_x_t of the two frames runs once
         per time step as in the reference; in training mode every inner sample makes its own decoder call, because the
         batch statistics of the norm layers are per call in the reference.  defer_decoder = False / True forces either
-        form of the decoder."""
+        form of the decoder.  The deferred likelihood is _lpx_rows: one pixel_loglik launch per time step when no
+        gradient is kept, with softplus(variance) of "gaussian" read to the host once per call."""
         from rfn_hip import ops
         b, t, c, h, w = xt.shape
         K = int(K)
@@ -360,6 +382,12 @@ class VRNN(nn.Module):
         d = _Draws(draws, xt.device)
         hprev, cprev, _, zxprev, _, _, _ = self.get_inits()
         log_k = float(np.log(K))
+        host_scale = []
+
+        def scale():   # one device-to-host read per call, and only when a kernel launch needs it
+            if not host_scale:
+                host_scale.append(float(nn.functional.softplus(self.variance.detach())))
+            return host_scale[0]
         loss = 0
         for i in range(1, t):
             x_i = xt[:, i]
@@ -374,23 +402,23 @@ class VRNN(nn.Module):
                 eps_p = d.normal(p_loc.shape)
                 zx_t, logq, logp = ops.gauss_heads(q_loc, q_raw, p_loc, p_raw, eps_q=eps_q, eps_p=eps_p,
                                                    want=("z_q", "logq", "logp"))
-                x_noise = nll_unif = None
+                u = nll_unif = None
                 if self.loss_type == "gaussian":
-                    x_noise, nll_unif = self.uniform_binning_correction(x_i, d)
+                    u, nll_unif = self._dequant_draw(x_i, d)
                 if defer:
                     hts.append(ht)
                     zxs.append(zx_t)
-                    noisy.append(x_noise)
+                    noisy.append(u)
                     unifs.append(nll_unif)
                 else:
-                    lpxs.append(self._lpx(self._decode(ht, zx_t), x_i, x_noise, nll_unif))
+                    lpxs.append(self._lpx(self._decode(ht, zx_t), x_i, None if u is None else x_i + u, nll_unif))
                 logpzs.append(logp)
                 logqzxs.append(logq)
                 zxprev, hprev, cprev = zx_t, ht, ct
             if defer:   # rows k*B + b
                 gauss = self.loss_type == "gaussian"
-                lpx = self._lpx(self._decode(torch.cat(hts, 0), torch.cat(zxs, 0)), x_i.repeat(K, 1, 1, 1),
-                                torch.cat(noisy, 0) if gauss else None, torch.cat(unifs, 0) if gauss else None)
+                lpx = self._lpx_rows(self._decode(torch.cat(hts, 0), torch.cat(zxs, 0)), x_i,
+                                     torch.cat(noisy, 0) if gauss else None, torch.cat(unifs, 0) if gauss else None, scale)
                 lpx = lpx.view(K, b)
             else:
                 lpx = torch.stack(lpxs, 0)

@@ -129,8 +129,16 @@ def check_model_name(model_name):
     return model_name == "rfn.pt"
 
 
+BASELINE_MODEL_NAMES = ("srnn.pt", "vrnn.pt", "svg.pt")   # what tools/eval_baselines.py asks an Evaluator to accept
+
+
 class Evaluator(object):
-    def __init__(self, solver, args=None, settings=None):
+    def __init__(self, solver, args=None, settings=None, model_names=None):
+        """model_names: the checkpoint names this instance evaluates; None is MODEL_NAMES, what the reference-shaped
+        driver (eval_settings.py) accepts.  tools/eval_baselines.py passes BASELINE_MODEL_NAMES: every name but "rfn.pt"
+        takes the non-RFN branches (model.loss(image) -> (kl, nll) on the whole sequence,
+        model.elbo_importance_weighting(imageloss, iw_samples), model._predict_device / _predict_draws_device)."""
+        self.model_names = MODEL_NAMES if model_names is None else tuple(model_names)
         self.solver = solver
         self.model = solver.model
         self.args = args if args is not None else solver.args
@@ -169,6 +177,16 @@ class Evaluator(object):
         self.fvd_weights = getattr(settings, "fvd_weights", None)
         self._i3d = None
 
+    def check_model_name(self, model_name):
+        """True for "rfn.pt", False for another checkpoint name this instance accepts, else a ValueError: with the default
+        names that of the module's check_model_name"""
+        if self.model_names == MODEL_NAMES:
+            return check_model_name(model_name)
+        if model_name not in self.model_names:
+            raise ValueError("Evaluator: cannot evaluate %r: this Evaluator accepts %s" %
+                             (model_name, ", ".join(self.model_names)))
+        return model_name == "rfn.pt"
+
     def compute_loss(self, nll, kl, dims, t=10):
         """error_metrics.py:358-368 -> (bits/dim, kl / t, nll / t)"""
         kl_store, nll_store = kl.detach(), nll.detach()
@@ -186,7 +204,7 @@ class Evaluator(object):
         chains_per_pass=settings.iw_chains_per_pass) / (ln 2 * prod(dims) * t), B being the first batch's size; the
         noise is addressed, so the figure is reproducible and torch's generators are not touched.  Unset, "rfn.pt" is
         the path above, unchanged."""
-        rfn = check_model_name(model_name)
+        rfn = self.check_model_name(model_name)
         loader = loader if loader is not None else self.test_loader
         with torch.no_grad():
             self.model.eval()
@@ -300,7 +318,7 @@ class Evaluator(object):
         they are computed in the first pass only.  n_predicts defaults to n_frames - start_predictions and must be at
         least 9; fewer than 16 sequences is a ValueError.  Needs settings.fvd_weights."""
         from rfn_hip import ops
-        rfn = check_model_name(model_name)
+        rfn = self.check_model_name(model_name)
         w = self._i3d_loaded()
         # (srnn.pt: the frames stay where they were computed; the embeddings are computed there)
         predict = self.model.predict if rfn else self.model._predict_device
@@ -440,7 +458,7 @@ class Evaluator(object):
 
         "srnn.pt" takes the reference's other branch (:478-483): `kl, nll = model.loss(image)` on the WHOLE sequence,
         with the dims and t of `image`; everything else is the same code."""
-        rfn = check_model_name(model_name)
+        rfn = self.check_model_name(model_name)
         if self.draws_per_pass is not None:
             return self._get_eval_values_draws(loader, max_batches, rfn)
         if self.debug_plot and not self._warned_plots:
@@ -639,7 +657,7 @@ class Evaluator(object):
         and the K tuples share them.  self.best_preds_ssim becomes a dict {T: uint8 tensor on the device} in this call
         only.  The debug_plot sheets are not written here (they would overwrite one another per temperature).
         RFN only: SRNN has no sampling temperature, "srnn.pt" is a ValueError."""
-        if not check_model_name(model_name):
+        if not self.check_model_name(model_name):
             raise ValueError("Evaluator.get_eval_values_temperatures: %s has no sampling temperature; the temperature "
                              "study is for rfn.pt" % model_name)
         temps = [float(t) for t in temperatures]

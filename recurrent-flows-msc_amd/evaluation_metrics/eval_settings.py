@@ -99,12 +99,13 @@ def write_avg_losses(path, d):
             print(k + ":", d[k], file=f)
 
 
-def build_evaluator(settings, i):
+def build_evaluator(settings, i, solver_for=None, model_names=None):
     """Solver and Evaluator of experiment i: the stored arguments on one rank, test sequences of settings.n_frames frames
-    (the loss is still evaluated on as many frames as the run was trained on)"""
+    (the loss is still evaluated on as many frames as the run was trained on).  solver_for / model_names: another table
+    of checkpoint names (tools/eval_baselines.py); None is this driver's solver_class and the Evaluator's default."""
     from evaluation_metrics.error_metrics import Evaluator
     model_name = settings.model_path[i]
-    Solver = solver_class(model_name)
+    Solver = (solver_for or solver_class)(model_name)
     exp = settings.folder_path + settings.experiment_names[i]
     ckpt = Solver.read_checkpoint(exp + "/model_folder/" + model_name)
     args = Solver.args_for_world(ckpt, 1)
@@ -115,7 +116,7 @@ def build_evaluator(settings, i):
     solver.load(ckpt)
     ev_settings = copy.copy(settings)
     ev_settings.n_trained = n_trained
-    evaluator = Evaluator(solver, args, ev_settings)
+    evaluator = Evaluator(solver, args, ev_settings, model_names=model_names)
     os.makedirs(exp + "/eval_folder", exist_ok=True)
     os.makedirs(solver.path + "eval_folder", exist_ok=True)
     evaluator.model.eval()

@@ -1784,6 +1784,8 @@ from .stepbn import StepBatchNormActFn, StepBatchNormActPoolFn, Up2xCatFn  # noq
 from .bnflow import BatchNormFlowFn, bnflow_apply, bnflow_coef  # noqa: E402,F401
 from .mol import (MOL_KEYED_SLOT_COLOUR, MOL_KEYED_SLOT_MIX, MolNllFn, mol_dims, mol_keyed_uniforms, mol_nll,  # noqa: E402,F401
                   mol_sample, mol_sample_keyed)
+from .pixel_loglik import (PIXEL_LOGLIK_KERNEL_DEFAULT, PIXEL_LOGLIK_MODES, normal_logvar_pair,  # noqa: E402,F401
+                           normal_logvar_pair_check, pixel_loglik, pixel_loglik_check, pixel_loglik_route)
 from .frame_metrics import frame_quality  # noqa: E402,F401
 from .linext import (LinearExtrapLossFn, gauss_quality, gauss_quality_check, linear_extrap_check,  # noqa: E402,F401
                      linear_extrap_loss, linear_extrap_pairs, linear_extrap_rollout, linext_limits)
